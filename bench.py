@@ -223,6 +223,27 @@ def build_map(obj, traj, P, first, warm, warm_t):
         obj.process_scan(pts, tb)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, poses, x36, P900):
+    """--dump-outputs: what the timed path handed its caller in the last timed step - per scan the pose record copied to the host (lk_pose)
+    and the filter slot's state record (state 36 + covariance 900) - one float64 .npy per array, so that two builds can be compared output for
+    output.  Beyond DUMP_MAX_BYTES a fixed, seeded sample of the scans is written (scan_index.npy names them)."""
+    arrays = {"pose_rot": poses["rot"], "pose_pos": poses["pos"], "pose_vel": poses["vel"], "pose_n_effect": poses["n_effect"],
+              "pose_n_buckets": poses["n_buckets"], "pose_n_updates": poses["n_updates"], "state_x36": x36, "state_P900": P900}
+    n = len(poses)
+    assert all(len(a) == n for a in arrays.values()), {k: len(a) for k, a in arrays.items()}
+    row_bytes = 8 * (1 + sum(int(np.prod(a.shape[1:])) for a in arrays.values()))
+    idx = np.arange(n)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(20260).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scan_index.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(np.asarray(a)[idx], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,6 +283,8 @@ def main():
     ap.add_argument("--step-sweep", action="store_true", help="also time regions of 1..64 steps (extra.step_sweep_ms)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes generating the synthetic scans (0 = auto)")
     ap.add_argument("--cache-dir", default="", help="keep generated inputs here between runs of one session (profiling passes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step delivered (every scan's "
+                    "pose record and its slot's state record, float64) as DIR/<name>.npy, at most 64 MB (a seeded sample of the scans beyond that)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -491,6 +514,17 @@ def main():
     total_scans = (args.total_scans if strong else S * world_size) * args.steps
     value = total_scans / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:   # untimed, before anything else replays into the slots of the last timed step
+        last_slot = ((args.steps - 1) % max(2, args.in_flight)) * S_max
+        xs_last, Ps_last = replay.gather_state_records(dist, g, last_slot, S, world_size, dev)
+        if rank == 0:
+            if dist is None:
+                poses_last = timed_last
+            else:   # every rank's records of its last step, in rank order (a rank's row holds its own shard's scans first)
+                shards = [replay.shard_range(args.total_scans, r, world_size) if strong else (0, S) for r in range(world_size)]
+                poses_last = np.concatenate([rec[r, (args.steps - 1) % ring_rows].view(_abi.pose_dtype())[: b - a] for r, (a, b) in enumerate(shards)])
+            dump_outputs(args.dump_outputs, poses_last, xs_last.cpu().numpy(), Ps_last.cpu().numpy())
+        del xs_last, Ps_last
 
     # ---- sustained run (>= 1 s of back-to-back steps; same loop, not the graded number)
     extra = {}

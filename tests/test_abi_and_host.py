@@ -75,21 +75,21 @@ def test_product_never_references_the_oracle():
     assert "oracle" not in out
 
 
-def test_host_mirror_compiles_against_the_c_abi():
+def test_host_mirror_compiles_against_the_c_abi(tmp_path):
     """leg-kilo_amd/host/*.hpp (the C++ mirror of ESKF / VoxelMapManager / KILO path) is header-only over the C-ABI."""
     src = os.path.join(ROOT, "leg-kilo_amd", "host", "example_kilo_path.cc")
-    exe = "/tmp/lk_host_example"
+    exe = str(tmp_path / "lk_host_example")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "leg-kilo_amd", "host"),
                         src, "-o", exe, "-L", os.path.join(ROOT, "leg-kilo_amd"), "-llegkilo_hip",
                         "-Wl,-rpath," + os.path.join(ROOT, "leg-kilo_amd")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
 
 
-def test_host_rccl_example_compiles_against_rccl_and_the_c_abi():
+def test_host_rccl_example_compiles_against_rccl_and_the_c_abi(tmp_path):
     """The C++ multi-GPU hook (host/legkilo_rccl.hpp: map broadcast over a caller-owned ncclComm_t, shard partition, all-gather of the
     result records) and its one-process-all-GPUs example compile and link against rccl.h, the HIP runtime and the C-ABI."""
     src = os.path.join(ROOT, "leg-kilo_amd", "host", "example_replay_rccl.cc")
-    exe = "/tmp/lk_host_rccl_example"
+    exe = str(tmp_path / "lk_host_rccl_example")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(ROOT, "include"),
                         "-I", os.path.join(ROOT, "leg-kilo_amd", "host"), src, "-o", exe, "-L", os.path.join(ROOT, "leg-kilo_amd"), "-llegkilo_hip",
                         "-L", "/opt/rocm/lib", "-lrccl", "-lamdhip64", "-lpthread", "-Wl,-rpath," + os.path.join(ROOT, "leg-kilo_amd"),

@@ -16,13 +16,19 @@ config 3's per-scan semantics:
   N>1: rank 0 builds the map and broadcasts the device blob over RCCL; scans are sharded with no data-path collective;
   per-step poses are all-gathered.  Default = weak scaling (1024 scans per GPU); `--total-scans 1024` = strong scaling
   (BASELINE config 5 as worded: 1024 scans in total, 128 per GPU at N = 8); the JSON line says which.
-The line is self-checking: the cpu_baseline leg replays a sample of the batch through the oracle ON THE MAP THE DEVICE
+With --full the line is self-checking: the cpu_baseline leg replays a sample of the batch through the oracle ON THE MAP THE DEVICE
 HOLDS and compares counts and poses with what the TIMED loop delivered for the same scans (`parity_check`; a violation
 exits non-zero).  `roofline` describes lk_residual_kernel with counter-derived bounds (profiles/latest_pmc.json, made
 by tools/gpu_prof_r02.sh + tools/collect_r02.py from rocprofv3 --pmc passes of this very command): HBM fraction from FETCH_SIZE/WRITE_SIZE,
 L2 fraction from TCC_REQ, VALU-issue fraction from SQ_INSTS_VALU, launch time from the timed region.
 `cpu_baseline` = the oracle (kind "port") on one pinned host thread, plus the reference's own build (oracle/_ref,
 literal N x N update) timed on the config-1 scans for the record.
+
+A plain run does only what the headline needs: it generates the batch and the map's scans, builds the map, uploads and prepares
+the batch, runs the W warm-up and K timed steps, writes --dump-outputs and prints the line (`value`, `ms_per_step`, `roofline` from
+the timed region and the stored counters; `cpu_baseline` and `parity_check` null).  Everything else it measures or checks - the
+parity check and CPU baselines, the sustained / shard128 / shuffled-order / PCIe / overlay / config-1, -2, -3, -4 extras, the
+kernel-event pass, the second map transport at N > 1 - runs with `--full`.
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ import time
 
 import numpy as np
 
+T_PROCESS0 = time.time()   # extra.setup_s: what a run spends before its first warm-up step, from here
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
@@ -285,6 +292,10 @@ def main():
     ap.add_argument("--cache-dir", default="", help="keep generated inputs here between runs of one session (profiling passes)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step delivered (every scan's "
                     "pose record and its slot's state record, float64) as DIR/<name>.npy, at most 64 MB (a seeded sample of the scans beyond that)")
+    ap.add_argument("--full", action="store_true", help="also run every extra measurement and check after the timed steps: parity check and CPU baselines "
+                    "(--cpu-sample), sustained run, 128-scan shard, shuffled order (--shuffle-check), kernel-event pass, overlay batch (--overlay-scans), "
+                    "configs 1-4 (--config1-scans, --config2-scans, --stream-scans, --config4-scans), PCIe-inclusive step, state-record gather and, at N > 1, "
+                    "the scatter + all-gather map transport.  Without it the options of those extras are ignored")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -321,22 +332,22 @@ def main():
     warm_t = [t0 + 3.0 * k for k in range(args.map_warm)]       # 20 poses over the 60 s figure-eight
     t_after = 5.0
 
-    # ---- generation (fork pool, before any GPU work)
+    # ---- generation (fork pool, before any GPU work); a plain run generates only the batch and the map's scans
     t_gen0 = time.time()
     ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     workers = args.gen_workers or max(1, min(64, ncpu // max(1, world_size)))
     jobs = [("dense", (scan_time(t_after, g0 + u), N_BUCKETS, 5005 + g0 + u, 1_000_003 + g0 + u)) for u in range(U)]
     n_batch_jobs = len(jobs)
-    ns = args.stream_scans if rank == 0 else 0
+    ns = args.stream_scans if (rank == 0 and args.full) else 0
     n51 = max(3, min(ns, 6)) if ns >= 2 else 0
-    U1 = 8 if (rank == 0 and world_size == 1 and args.config1_scans > 0) else 0
+    U1 = 8 if (rank == 0 and world_size == 1 and args.full and args.config1_scans > 0) else 0
     if rank == 0:
         jobs.append(("first", (t0,)))
         jobs += [("dense", (tb, N_BUCKETS, 2002 + k, 3003 + k)) for k, tb in enumerate(warm_t)]
     jobs += [("dense", (t_after + 0.1 * k, N_BUCKETS, 8008 + k, 8108 + k)) for k in range(ns)]
     jobs += [("dense", (t_after + 0.1 * (ns + k), 51, 8208 + k, 8308 + k)) for k in range(n51)]
     jobs += [("vlp", (t_after + 0.1 * k, 7007 + k)) for k in range(U1)]
-    U4 = args.config4_scans if (rank == 0 and world_size == 1) else 0
+    U4 = args.config4_scans if (rank == 0 and world_size == 1 and args.full) else 0
     if U4:
         jobs.append(("ouster", (T0_CONFIG4, 3999, True)))
         jobs += [("ouster", (T0_CONFIG4 + 0.1 * k, 4000 + k, False)) for k in range(U4)]
@@ -406,7 +417,7 @@ def main():
     map_bytes, bsecs = replay.broadcast_map(g, dist, rank, world_size, dev, src=0, algo="broadcast")
     bcast_ms = bsecs * 1e3 if world_size > 1 else None
     bcast2_ms = None
-    if world_size > 1:
+    if world_size > 1 and args.full:
         # the same payload again as scatter + all-gather (all xGMI links of the root busy); a failure is REPORTED, never hidden
         try:
             _, s2 = replay.broadcast_map(g, dist, rank, world_size, dev, src=0, algo="scatter_allgather")
@@ -420,7 +431,7 @@ def main():
     n_roots, n_nodes, n_blocks = g.map_stats()
     map_build_s = time.time() - t_map0
     # the checker replays against EXACTLY this snapshot: exported now, before the stream extras (which insert) touch the map
-    map_blob_for_oracle = g.map_export() if (rank == 0 and world_size == 1 and args.cpu_sample > 0) else None
+    map_blob_for_oracle = g.map_export() if (rank == 0 and world_size == 1 and args.full and args.cpu_sample > 0) else None
 
     # ---- resident batch
     host_batch = np.stack([np.ascontiguousarray(sc).view(np.uint8).reshape(-1) for sc in scans])      # U x 1.6 MB
@@ -486,6 +497,7 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    t_setup_s = time.time() - T_PROCESS0
     for k in range(args.ramp_steps):   # untimed: brings the clocks up (the sustained rate is what the timed region should see)
         step(k)
     finish(min(args.ramp_steps, ring_rows))
@@ -505,7 +517,7 @@ def main():
         elapsed = float(tt.item())
     timed_last = ring[(args.steps - 1) % ring_rows][: S * pose_sz].numpy().view(_abi.pose_dtype()).copy()   # what the timed loop delivered
     gather_ok = None
-    if dist is not None:   # untimed: the gathered records are what every rank delivered (rank r's last step == its own ring row)
+    if dist is not None and (args.full or args.dump_outputs):   # untimed: the gathered records are what every rank delivered (rank r's last step == its own ring row)
         rec = gathered[0].cpu().numpy().reshape(world_size, -1, S_max * pose_sz)
         mine = rec[rank, (args.steps - 1) % ring_rows, : S * pose_sz].view(_abi.pose_dtype())
         gather_ok = bool(np.array_equal(mine["pos"], timed_last["pos"]) and all(
@@ -527,15 +539,16 @@ def main():
         del xs_last, Ps_last
 
     # ---- sustained run (>= 1 s of back-to-back steps; same loop, not the graded number)
-    extra = {}
-    # untimed: SURVEY 8(e)'s full per-scan result record - state 36 + covariance 900 - of the last batch in slots [0, S), gathered on
-    # the device by one kernel (lk_batch_get_states_dev) and, for N > 1, all-gathered device to device over RCCL
-    xs_all, Ps_all = replay.gather_state_records(dist, g, 0, S, world_size, dev)
-    extra["state_records_gathered"] = int(xs_all.shape[0])
-    extra["state_record_bytes_per_scan"] = 936 * 8
-    extra["state_records_cov_finite"] = bool(torch.isfinite(Ps_all).all().item())
-    del xs_all, Ps_all
-    if args.sustained_s > 0:
+    extra = {"full": args.full, "setup_s": round(t_setup_s, 2)}
+    if args.full:
+        # untimed: SURVEY 8(e)'s full per-scan result record - state 36 + covariance 900 - of the last batch in slots [0, S), gathered on
+        # the device by one kernel (lk_batch_get_states_dev) and, for N > 1, all-gathered device to device over RCCL
+        xs_all, Ps_all = replay.gather_state_records(dist, g, 0, S, world_size, dev)
+        extra["state_records_gathered"] = int(xs_all.shape[0])
+        extra["state_record_bytes_per_scan"] = 936 * 8
+        extra["state_records_cov_finite"] = bool(torch.isfinite(Ps_all).all().item())
+        del xs_all, Ps_all
+    if args.full and args.sustained_s > 0:
         n_sus = max(4, int(math.ceil(args.sustained_s * 1e3 / ms_per_step)))
         sync_all()
         ts = time.perf_counter()
@@ -550,7 +563,7 @@ def main():
 
     # ---- the strong-scaling shard on ONE GPU: BASELINE config 5 at N = 8 gives every GPU 128 of the 1024 scans.  The same loop with
     # 128-scan batches (three in flight, rotating over three slot ranges / streams) - what a GPU of the 8-GPU run executes per step.
-    if S >= 128:
+    if args.full and S >= 128:
         S8 = 128
         ring8 = max(1, min(3, (max(2, args.in_flight) * S_max) // S8))   # slot ranges the 128-scan batches rotate over (a 128-scan rank has 256 slots: two)
 
@@ -592,7 +605,7 @@ def main():
     shuf = None
     shuf_auto = None
     resorted = None
-    if rank == 0 and world_size == 1 and args.shuffle_check > 0 and not args.shuffle_main:
+    if rank == 0 and world_size == 1 and args.full and args.shuffle_check > 0 and not args.shuffle_main:
         d_shuf = shuffled_in_bucket(d_batch, 4242)
         torch.cuda.synchronize()
         g.batch_order(0)   # LK_BATCH_ORDER_AS_GIVEN: what the random order costs when the library is told to leave the batch alone
@@ -685,14 +698,14 @@ def main():
         del d_shuf
 
     # ---- kernel-level timing pass (HIP events on the handle's stream, whole-batch launches on ONE stream), outside the timed region
-    g.profile_reset()
-    g.profile_enable(1)
-    g.batch_set_priors_dev(d_x.data_ptr(), d_P.data_ptr(), S)
-    g.batch_replay_dev(d_batch.data_ptr(), S, N_PTS, 0.0, off, dt)
-    g.profile_enable(0)
-    prof = {k: g.profile_get(k) for k in ("predict", "residual", "update")}
-    n_res, ms_res = prof["residual"]
-    ev_res_ms = ms_res / max(n_res, 1)
+    prof = None
+    if args.full:
+        g.profile_reset()
+        g.profile_enable(1)
+        g.batch_set_priors_dev(d_x.data_ptr(), d_P.data_ptr(), S)
+        g.batch_replay_dev(d_batch.data_ptr(), S, N_PTS, 0.0, off, dt)
+        g.profile_enable(0)
+        prof = {k: g.profile_get(k) for k in ("predict", "residual", "update")}
     pts_per_launch = S * (N_PTS // N_BUCKETS)
     # the launch time the roofline uses comes from the TIMED region: one step = N_BUCKETS residual launches with everything
     # else (update / predict / priors / pose copies) hidden under them or charged to them
@@ -743,13 +756,15 @@ def main():
         "mfma_f64_ops": pmc.get("mfma_f64_ops") if pmc else None,
         "pmc_source": None if not pmc else f"profiles/latest_pmc.json (tag {pmc.get('tag')}, commit {pmc.get('commit')}, {pmc.get('slots')} slots x {pmc.get('unique_scans')} unique scans)",
         "launch_ms": round(launch_ms, 4), "launch_ms_source": f"timed region: ms_per_step / {N_BUCKETS} residual launches",
-        "launch_ms_single_stream_events": round(ev_res_ms, 4), "launches_event_pass": n_res,
         "points_per_launch": pts_per_launch, "ps_per_point": round(launch_ms * 1e9 / pts_per_launch, 2),
         # algorithmic bytes served mostly by L2/MALL - NOT an HBM fraction (at SURVEY's 288 B/point it would exceed the peak)
         "alg_bytes_per_point": ALG_BYTES_RESIDUAL, "alg_GBs_cache_served": round(alg_GBs, 1),
         "survey_alg_bytes_per_point": ALG_BYTES_SURVEY, "alg_GBs_cache_served_at_survey_bytes": round(alg_GBs * ALG_BYTES_SURVEY / ALG_BYTES_RESIDUAL, 1),
-        "other_kernels_ms": {k: round(v[1] / max(v[0], 1), 4) for k, v in prof.items() if k != "residual"},
     }
+    if prof is not None:   # --full: the event pass's per-launch times
+        roofline["launch_ms_single_stream_events"] = round(prof["residual"][1] / max(prof["residual"][0], 1), 4)
+        roofline["launches_event_pass"] = prof["residual"][0]
+        roofline["other_kernels_ms"] = {k: round(v[1] / max(v[0], 1), 4) for k, v in prof.items() if k != "residual"}
     # where the kernel's waves wait: L1 / LDS / SQ counters of the same launch, profiles/r06_pmc_memory_pipe.json (tools/gpu_prof_mempipe.sh)
     mp_file = os.path.join(ROOT, "profiles", "r06_pmc_memory_pipe.json")
     if os.path.exists(mp_file):
@@ -777,7 +792,7 @@ def main():
     # ---- extra: the same batch WITH the map insert - every scan on its own copy-on-write overlay of the shared map (SURVEY 8d config 5,
     # "scan-local insert overlay"; KILO.cc:216-233 after every bucket): what KILO::process computes per scan, for the whole batch
     ov = None
-    S_ov = min(args.overlay_scans, S)   # every rank replays its own shard with insert (an overlay is private to its scan: no collective on the data path)
+    S_ov = min(args.overlay_scans, S) if args.full else 0   # every rank replays its own shard with insert (an overlay is private to its scan: no collective on the data path)
     if S_ov > 0:
         try:
             g.batch_set_priors_dev(d_x.data_ptr(), d_P.data_ptr(), S_ov)
@@ -837,7 +852,7 @@ def main():
     # of KILO.cc:122-210 for S2 x 100 000 points in ONE launch, every scan under its prior state, rows h (1x6) / z / R / valid MATERIALISED in
     # HBM (lk_batch_residuals_dev).  This is the one place SURVEY 8(d)'s HBM roofline applies as written: 16 B in + 65 B out per point.
     c2 = None
-    S2 = min(args.config2_scans, S) if (rank == 0 and world_size == 1) else 0
+    S2 = min(args.config2_scans, S) if (rank == 0 and world_size == 1 and args.full) else 0
     if S2 > 0:
         try:
             N2 = S2 * N_PTS
@@ -916,7 +931,7 @@ def main():
                   "ranks_sharing_one_gpu": bool(os.environ.get("LEGKILO_BENCH_SHARE_GPU") == "1") if dist is not None else None})
     # ---- extra: the same batch step when the scans start in (pinned) host memory: upload of batch k+1 on a copy stream under
     # the replay of batch k (the boundary also takes host buffers; this rate is never `value`)
-    if rank == 0 and world_size == 1 and not args.no_pcie:
+    if rank == 0 and world_size == 1 and args.full and not args.no_pcie:
         try:
             h_batch = torch.empty(d_batch.shape, dtype=d_batch.dtype).pin_memory()
             h_batch.copy_(d_batch)
@@ -1153,7 +1168,7 @@ def main():
         sb, stl, srd = g.stream_stats()
         extra["stream_pipeline_stats"] = {"pipelined_buckets": sb, "tiles_verified": stl, "tiles_evaluated_again": srd}
 
-    if rank == 0 and args.cpu_sample > 0 and world_size == 1:
+    if rank == 0 and args.full and args.cpu_sample > 0 and world_size == 1:
         # ---- CPU baseline + in-line parity check: the oracle (port), 1 pinned thread, a bounded sample of the SAME batch on the
         # SAME map (the device's blob, imported into the oracle), compared with the poses the TIMED loop delivered
         sys.path.insert(0, os.path.join(ROOT, "oracle"))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of library variants: tools/ab_libs.sh lib_a.so lib_b.so ...  (paths relative to leg-kilo_amd/)
 for v in "$@"; do
-  LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --steps 10 --warmup 2 --cpu-sample 0 --stream-scans 0 2>/dev/null > /tmp/ab_lib.json
+  LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --full --steps 10 --warmup 2 --cpu-sample 0 --stream-scans 0 2>/dev/null > /tmp/ab_lib.json
   python - "$v" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_lib.json").read().strip().splitlines()[-1])

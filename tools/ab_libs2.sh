@@ -3,7 +3,7 @@
 R=$1; shift
 for r in $(seq 1 $R); do
 for v in "$@"; do
-  LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --steps 40 --warmup 30 --cpu-sample 0 --stream-scans 0 --config1-scans 0 --no-pcie --overlay-scans 0 --sustained-s 0.6 --cache-dir /tmp/lkcache 2>/dev/null > /tmp/ab_lib.json
+  LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --full --steps 40 --warmup 30 --cpu-sample 0 --stream-scans 0 --config1-scans 0 --no-pcie --overlay-scans 0 --sustained-s 0.6 --cache-dir /tmp/lkcache 2>/dev/null > /tmp/ab_lib.json
   python - "$v" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_lib.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 libs=("$@"); [ ${#libs[@]} -eq 0 ] && libs=(liblegkilo_hip.so)
 for v in "${libs[@]}"; do
   for spec in 0 1 0 1; do
-    LEGKILO_SPEC=$spec LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --steps 2 --warmup 1 --cpu-sample 0 --scans-per-gpu 32 --stream-scans 24 --config1-scans 64 --sustained-s 0 --no-pcie 2>/tmp/ab_spec.err > /tmp/ab_spec.json || tail -5 /tmp/ab_spec.err
+    LEGKILO_SPEC=$spec LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --scans-per-gpu 32 --stream-scans 24 --config1-scans 64 --sustained-s 0 --no-pcie 2>/tmp/ab_spec.err > /tmp/ab_spec.json || tail -5 /tmp/ab_spec.err
     python - "$v" "$spec" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_spec.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 R=$1; shift
 for r in $(seq 1 $R); do
 for v in "$@"; do
-  LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --steps 10 --warmup 5 --cpu-sample 0 --stream-scans 24 --config1-scans 2048 --no-pcie --overlay-scans ${OVS:-0} --sustained-s 0 --cache-dir /tmp/lkcache 2>/dev/null > /tmp/ab_lib.json
+  LEGKILO_HIP_LIB=$PWD/leg-kilo_amd/$v python bench.py --full --steps 10 --warmup 5 --cpu-sample 0 --stream-scans 24 --config1-scans 2048 --no-pcie --overlay-scans ${OVS:-0} --sustained-s 0 --cache-dir /tmp/lkcache 2>/dev/null > /tmp/ab_lib.json
   python - "$v" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_lib.json").read().strip().splitlines()[-1])

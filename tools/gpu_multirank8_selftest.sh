@@ -9,7 +9,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd $REPO
-COMMON="--gpus 8 --steps 3 --warmup 1 --cpu-sample 0 --stream-scans 0 --config1-scans 0 --config4-scans 0 --config2-scans 0 --no-pcie --sustained-s 0 --shuffle-check 0 --gen-workers 8"
+COMMON="--full --gpus 8 --steps 3 --warmup 1 --cpu-sample 0 --stream-scans 0 --config1-scans 0 --config4-scans 0 --config2-scans 0 --no-pcie --sustained-s 0 --shuffle-check 0 --gen-workers 8"
 {
   echo "# strong scaling, BASELINE config 5 as worded: 1024 scans in total, 128 per rank, 8 ranks on one GPU over gloo";
   timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29527 \

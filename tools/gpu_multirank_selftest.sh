@@ -6,7 +6,7 @@
 export LEGKILO_BENCH_BACKEND=gloo LEGKILO_BENCH_SHARE_GPU=1
 OUT=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out
 mkdir -p $OUT
-COMMON="--gpus 2 --steps 3 --warmup 1 --cpu-sample 0 --stream-scans 0 --config1-scans 0 --no-pcie --sustained-s 0 --map-warm 4 --gen-workers 16"
+COMMON="--full --gpus 2 --steps 3 --warmup 1 --cpu-sample 0 --stream-scans 0 --config1-scans 0 --no-pcie --sustained-s 0 --map-warm 4 --gen-workers 16"
 {
   echo "# weak: 32 scans per rank";
   timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \

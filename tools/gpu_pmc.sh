@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 TAG=${1:-r01b}
 ONLY=${2:-}   # optional space-separated list of pass numbers to run, e.g. "1 2 7"
-ARGS="--steps 2 --warmup 0 --cpu-sample 0 --stream-scans 0 --map-warm 4 --unique-scans 8"
+ARGS="--full --steps 2 --warmup 0 --cpu-sample 0 --stream-scans 0 --map-warm 4 --unique-scans 8"
 cd /tmp && export TMPDIR=/tmp
 export LEGKILO_REPLAY_GROUPS=1   # whole-batch launches, comparable across rounds
 i=0

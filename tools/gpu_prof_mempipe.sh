@@ -11,7 +11,7 @@ ORDERS=${3:-"cell shuffled"}
 OUT=$REPO/gpurun_out/prof_mempipe_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-COMMON="--cpu-sample 0 --config1-scans 0 --no-pcie --sustained-s 0 --overlay-scans 0 --shuffle-check 0 --stream-scans 0 --config2-scans 0 --cache-dir /tmp/lkcache --steps 2 --warmup 0"
+COMMON="--full --cpu-sample 0 --config1-scans 0 --no-pcie --sustained-s 0 --overlay-scans 0 --shuffle-check 0 --stream-scans 0 --config2-scans 0 --cache-dir /tmp/lkcache --steps 2 --warmup 0"
 timeout 300 python $REPO/bench.py $COMMON > $OUT/warm.log 2>&1 < /dev/null
 pass() {  # name, order, counters...
   local name=$1 order=$2; shift 2

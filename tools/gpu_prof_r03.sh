@@ -10,7 +10,7 @@ OUT=$REPO/gpurun_out
 TAG=${1:-r03a}
 PASSES=${2:-"stats fetch write sq1 sq2 sq3 tcc"}
 export LK_PROF_COMMIT=${3:-unknown}   # commit the snapshot was taken from (the GPU box has no .git)
-COMMON=${COMMON:-"--cpu-sample 0 --config1-scans 0 --no-pcie --sustained-s 0 --cache-dir /tmp/lkcache"}
+COMMON=${COMMON:-"--full --cpu-sample 0 --config1-scans 0 --no-pcie --sustained-s 0 --cache-dir /tmp/lkcache"}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, extra bench args, rocprof args...

@@ -9,7 +9,7 @@ export LK_PROF_COMMIT=${2:-unknown}
 OUT=$REPO/gpurun_out/prof_ragov_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--cpu-sample 0 --no-pcie --sustained-s 0 --overlay-scans 0 --shuffle-check 0 --stream-scans 0 --config2-scans 0 --config4-scans 0 --steps 2 --warmup 1 --cache-dir /tmp/lkcache"
+ARGS="--full --cpu-sample 0 --no-pcie --sustained-s 0 --overlay-scans 0 --shuffle-check 0 --stream-scans 0 --config2-scans 0 --config4-scans 0 --steps 2 --warmup 1 --cache-dir /tmp/lkcache"
 timeout 400 python $REPO/bench.py $ARGS > $OUT/warm.json 2>/dev/null < /dev/null   # fills the input cache outside any profiler; its line = the unprofiled time
 for p in stats fetch write sq; do
   rm -rf /tmp/rgp_$p

@@ -6,7 +6,7 @@ set -u
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 TAG=${1:-r01}
-ARGS="--steps 3 --warmup 1 --cpu-sample 0 --stream-scans 3"
+ARGS="--full --steps 3 --warmup 1 --cpu-sample 0 --stream-scans 3"
 T="timeout 240"
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

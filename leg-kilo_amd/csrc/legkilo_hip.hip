@@ -389,7 +389,7 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
         const bool is_imu = WITH_IMU && qi < qn && rg.imu[mstride * (size_t)qi] < tb_;
         const double t = is_imu ? rg.imu[mstride * (size_t)qi] : tb_;
         SW_STAMP(0);
-        if (!LK_X_NOPRED) wave_predict_core(sm, Q, t - t_upd, t - t_pred, lane, rg.q_diag != 0);   // KILO.cc:111-115 / :240-244
+        wave_predict_core(sm, Q, t - t_upd, t - t_pred, lane, rg.q_diag != 0);   // KILO.cc:111-115 / :240-244
         SW_STAMP(1);
         t_pred = t;
         if (is_imu) {   // predictUpdateImu, KILO.cc:235-258 / predictUpdateKinImu, KILO.cc:260-314
@@ -418,8 +418,7 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
         SW_STAMP(2);
         for (int i0 = 0; i0 < n; i0 += LK_WAVE) {
             __builtin_amdgcn_wave_barrier();  // the previous tile's reads of the rows are complete
-            const double a = LK_X_NORES ? ((lane == 28) ? 1.0 : 0.0)
-                                        : residual_tile<false, 2, false, true>(map, pr, bc, reinterpret_cast<const float4*>(pts + base), i0 + lane, n, rows, lane, ro, (size_t)0);
+            const double a = residual_tile<false, 2, false, true>(map, pr, bc, reinterpret_cast<const float4*>(pts + base), i0 + lane, n, rows, lane, ro, (size_t)0);
             totv += (lane < 29) ? a : 0.0;
         }
         const int N = (int)(lane_bcast<28>(totv) + 0.5);
@@ -428,7 +427,7 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
         if (N > 0) {
             n_updates += 1, n_effect += (unsigned long long)N;
             t_upd = t;  // KILO.cc:212
-            if (!LK_X_NOUPD) wave_update_core(sm, totv, N, lane);
+            wave_update_core(sm, totv, N, lane);
         }
         SW_STAMP(4);
         __syncthreads();
@@ -584,14 +583,11 @@ int frozen_map(lk_handle* h, LkMap* out) {
 
 // The residual kernel of the uniform batch entries, specialised at compile time for what is launch-uniform: root lookup through
 // the frozen-map grid, and ext_R == I (no 3 x 3 extrinsic products, and 18 fewer scalar registers in a kernel whose occupancy
-// is set by registers).  LEGKILO_XID=0 keeps the generic instantiation (A/B).
+// is set by registers).  LEGKILO_XID=0 keeps the generic instantiation.
 using ResidualKernelFn = void (*)(LkMap, LkParams, const LkFilter*, const lk_point*, size_t, int, double*, size_t, ResidualOut, size_t);
 static ResidualKernelFn batch_residual_kernel(const lk_handle* h, const LkMap& fmap) {
-    static const bool xid_enable = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
     if (!fmap.grid_on) return lk_residual_kernel<false, 0, false>;
-    static const bool pair = getenv("LEGKILO_RES_PAIR") != nullptr && atoi(getenv("LEGKILO_RES_PAIR")) != 0;   // round-5 experiment: two tiles per wave (A/B; off)
-    if (pair) return (h->pr.ext_identity && xid_enable) ? lk_residual_pair_kernel<true> : lk_residual_pair_kernel<false>;
-    return (h->pr.ext_identity && xid_enable) ? lk_residual_kernel<false, 1, true> : lk_residual_kernel<false, 1, false>;
+    return (h->pr.ext_identity && lk_xid_enabled()) ? lk_residual_kernel<false, 1, true> : lk_residual_kernel<false, 1, false>;
 }
 
 // Grid of a batch residual launch over `sn` slots x `nblk` tiles: plain 2-D grid (tile, slot); LEGKILO_XCDMAP=1: the XCD-aware 1-D grid of ResidualOut::xmap_slots (A/B)
@@ -1746,9 +1742,8 @@ int lk_batch_residuals_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, 
     if (rc) return rc;
     rc = join_side_streams(h);
     if (rc) return rc;
-    static const bool xid_enable = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
     const ResidualKernelFn k = !fmap.grid_on ? lk_residual_kernel<true, 0, false>
-                                             : ((h->pr.ext_identity && xid_enable) ? lk_residual_kernel<true, 1, true> : lk_residual_kernel<true, 1, false>);
+                                             : ((h->pr.ext_identity && lk_xid_enabled()) ? lk_residual_kernel<true, 1, true> : lk_residual_kernel<true, 1, false>);
     ResidualOut ro;
     memset(&ro, 0, sizeof(ro));
     ro.rows8 = d_rows8, ro.valid = d_valid;

@@ -368,35 +368,19 @@ __device__ __forceinline__ V3 point_world(float bx, float by, float bz, const Bu
 // These are identities in exact arithmetic for ANY R / ext_R (no orthonormality is assumed); in fp64 they differ
 // from the reference's matrix route by rounding only (~1e-16 relative), ~60 flops per candidate instead of ~230 per
 // point + 12 per candidate, and ~40 fewer live VGPRs.
-// 1 / x for the residual kernel's two divisions per point (finite x well inside the normal range): v_rcp_f64 + two Newton steps
-// instead of the IEEE division sequence (two v_div_scale, v_rcp, five fma, v_div_fmas, v_div_fixup) - the same value to the last
-// bit or one ulp beside it, ~20 instructions fewer per point.  LK_FAST_RCP=0: the full division (A/B).
-#ifndef LK_FAST_RCP
-#define LK_FAST_RCP 0   // measured +1.5 % (662 k vs 652 k scans/s, same box) - and one match of the 1024-scan batch flips (a gate within an ulp of its threshold): the oracle divides, so does the shipped build
-#endif
+// 1 / x for the residual kernel's two divisions per point: the IEEE division.  v_rcp_f64 + two Newton steps - the same value to the
+// last bit or one ulp beside it, ~20 instructions fewer per point - measured +1.5 % (662 k vs 652 k scans/s, same box), but one match
+// of the 1024-scan batch flips (a gate within an ulp of its threshold): the oracle divides, so does the shipped build.
 __device__ __forceinline__ double lk_inv(double x) {
-#if LK_FAST_RCP
-    double r = __builtin_amdgcn_rcp(x);
-    r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-    r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-    return r;
-#else
     return 1.0 / x;
-#endif
 }
-// 1 / x for a value that feeds NO decision: v_rcp_f64 + two Newton steps (5 instructions instead of the ~12 of an IEEE division; the last bit may differ)
-#ifndef LK_FAST_RCP_ROW
-#define LK_FAST_RCP_ROW 1   // round 6: 1.548 -> 1.538 ms per step, parity sample unchanged (A/B: -DLK_FAST_RCP_ROW=0)
-#endif
+// 1 / x for a value that feeds NO decision: v_rcp_f64 + two Newton steps (5 instructions instead of the ~12 of an IEEE division; the last bit may differ;
+// round 6: 1.548 -> 1.538 ms per step, parity sample unchanged)
 __device__ __forceinline__ double lk_inv_nodecision(double x) {
-#if LK_FAST_RCP_ROW
     double r = __builtin_amdgcn_rcp(x);
     r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
     r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
     return r;
-#else
-    return 1.0 / x;
-#endif
 }
 struct PointLite {
     V3 p_i, p_w;
@@ -480,10 +464,6 @@ __host__ __device__ __forceinline__ unsigned int lk_hash3(int x, int y, int z) {
 __device__ __forceinline__ void pin_chunk(double2& v) { asm volatile("" : "+v"(v.x), "+v"(v.y)); }
 __device__ __forceinline__ void pin_chunk(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 __device__ __forceinline__ void pin_chunk(int4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-#ifndef LK_PIN_RECORD
-#define LK_PIN_RECORD 1   // records and table entries are requested whole and PINNED ahead of the first test of any part of them (0: loads
-                          // where the source has them - the compiler sinks them behind the tests; A/B)
-#endif
 // Linear probing, two consecutive slots per round trip: a wave waits for its slowest lane, and with ~14 distinct keys
 // per wave at load factor 0.3 some lane almost always needs a second probe; both slots are requested together.
 __device__ __forceinline__ int hash_find(const LkMap& m, int kx, int ky, int kz) {
@@ -491,9 +471,7 @@ __device__ __forceinline__ int hash_find(const LkMap& m, int kx, int ky, int kz)
     for (unsigned int probe = 0; probe <= m.hash_mask; probe += 2) {
         int4 e0 = m.hash[s];
         int4 e1 = m.hash[(s + 1) & m.hash_mask];
-#if LK_PIN_RECORD
         pin_chunk(e0), pin_chunk(e1);   // really ONE round trip: left alone, the compiler fetches e0.w, then e0's key, then e1
-#endif
         if (e0.w == LK_EMPTY) return -1;
         if (e0.w >= 0 && e0.x == kx && e0.y == ky && e0.z == kz) return e0.w;
         if (e1.w == LK_EMPTY) return -1;
@@ -506,51 +484,29 @@ __device__ __forceinline__ int hash_find(const LkMap& m, int kx, int ky, int kz)
 // Broadcast of one lane's value when the SOURCE LANE IS A COMPILE-TIME CONSTANT: two v_readlane_b32 into an SGPR pair instead of
 // the two ds_bpermute_b32 that __shfl compiles to - no trip through the LDS pipe (which the one-wave filter kernels saturate) and
 // the result is a scalar operand.  Same bits as __shfl(v, lane).
-#ifndef LK_READLANE
-#define LK_READLANE 1
-#endif
 template <int LANE>
 __device__ __forceinline__ double lane_bcast(double v) {
-#if LK_READLANE
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), LANE), hi = __builtin_amdgcn_readlane(__double2hiint(v), LANE);
     return __hiloint2double(hi, lo);
-#else
-    return __shfl(v, LANE, LK_WAVE);
-#endif
 }
 template <int LANE>
 __device__ __forceinline__ int lane_bcast(int v) {
-#if LK_READLANE
     return __builtin_amdgcn_readlane(v, LANE);
-#else
-    return __shfl(v, LANE, LK_WAVE);
-#endif
 }
 // the same for a lane index that is constant after unrolling (i in a `#pragma unroll` loop): the builtin wants a uniform value
 __device__ __forceinline__ double lane_bcast_u(double v, int lane) {
-#if LK_READLANE
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
     return __hiloint2double(hi, lo);
-#else
-    return __shfl(v, lane, LK_WAVE);
-#endif
 }
 __device__ __forceinline__ int lane_bcast_u(int v, int lane) {
-#if LK_READLANE
     return __builtin_amdgcn_readlane(v, lane);
-#else
-    return __shfl(v, lane, LK_WAVE);
-#endif
 }
 
 // wave-wide sum, result in every lane: the xor butterfly 32, 16, 8, 4, 2, 1.  Built from gfx950's v_permlane32_swap / v_permlane16_swap
 // (a swap of a register with a copy of itself leaves the two halves / row pairs side by side, and a + b == b + a) and DPP moves
 // (row_ror:8 == lane ^ 8 inside a row of 16; row_half_mirror then quad_perm [3,2,1,0] == lane ^ 4; quad_perm for ^ 2 and ^ 1)
 // instead of six pairs of ds_bpermute_b32: the same partners, the same additions, the same bits in every lane
-// (tools/probes/wave_sum_dpp_butterfly.hip), no trip through the LDS pipe.  LK_DPP_SUM=0: the __shfl_xor form.
-#ifndef LK_DPP_SUM
-#define LK_DPP_SUM 1
-#endif
+// (tools/probes/wave_sum_dpp_butterfly.hip), no trip through the LDS pipe.
 typedef unsigned int lk_u2 __attribute__((ext_vector_type(2)));
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov_f64(double v) {
@@ -559,7 +515,6 @@ __device__ __forceinline__ double dpp_mov_f64(double v) {
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double wave_sum(double v) {
-#if LK_DPP_SUM
     {
         const unsigned int lo = (unsigned int)__double2loint(v), hi = (unsigned int)__double2hiint(v);
         const lk_u2 l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
@@ -577,9 +532,4 @@ __device__ __forceinline__ double wave_sum(double v) {
     v += dpp_mov_f64<0x4E>(v);
     v += dpp_mov_f64<0xB1>(v);
     return v;
-#else
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, LK_WAVE);
-    return v;
-#endif
 }

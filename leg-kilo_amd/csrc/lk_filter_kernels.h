@@ -12,12 +12,6 @@
 #include "lk_device.h"
 
 #define LK_FB 256  // threads per filter block
-#ifndef LK_MFMA_COV
-#define LK_MFMA_COV 0   // 1 (A/B build): the covariance update P -= P[:,0:6] X of the one-wave update core on v_mfma_f64_16x16x4_f64
-#endif
-#ifndef LK_X_P
-#define LK_X_P 0   // perf attribution only (never set in the product build): bit 1 skip the rotations of the wave predict, 2 the
-#endif             // covariance products, 4 the Q term, 8 the Gauss-Jordan sweep of the wave update, 16 its P update, 32 its (+)
 
 struct FilterSmem {
     double P[900];
@@ -332,9 +326,6 @@ __device__ void dev_point_update(LkFilter* f, FilterSmem& sm, const double* A21,
     dev_kalman_apply(f, sm, 6);
 }
 
-#ifndef LK_BLOCK_UPDATE_WAVE
-#define LK_BLOCK_UPDATE_WAVE 1   // the 256-thread kernels solve and apply the point update in their wave 0 (0 = dev_point_update, barrier-separated)
-#endif
 __device__ void dev_point_update_wave0(LkFilter* f, FilterSmem& sm, const double* tot, int N);   // defined behind wave_update_core
 // The bucket's totals [A(21) b(6) sumR count] are in tot[] (LDS, visible to the whole workgroup): bookkeeping of
 // KILO.cc:193,211-212 and the information-form update.  Called by all LK_FB threads.
@@ -351,18 +342,7 @@ __device__ void dev_update_from_totals(LkFilter* f, FilterSmem& sm, double* tot,
             f->last_update_t = t;  // KILO.cc:212
         }
     }
-    if (N > 0 && LK_BLOCK_UPDATE_WAVE) {
-        dev_point_update_wave0(f, sm, tot, N);
-    } else if (N > 0) {
-        if (N == 1) {  // eskf.cc:98-104: s = 1/(0.0001 + hPh^T + r)  <=>  r' = r + 1e-4
-            double r = tot[27];
-            double sc = r / (r + 0.0001);
-            __syncthreads();
-            if (tid < 27) tot[tid] *= sc;
-        }
-        __syncthreads();
-        dev_point_update(f, sm, &tot[0], &tot[21]);
-    }
+    if (N > 0) dev_point_update_wave0(f, sm, tot, N);   // the point update solved and applied by wave 0
 }
 
 // reduce the per-wave partial records (fixed order -> deterministic) and update; partials: [nblk][LK_NPART] per slot.
@@ -461,16 +441,9 @@ static_assert(sizeof(WaveSmem) == 7680, "one residual workgroup's worth of LDS")
 // work on (WaveSmem and the row area) is touched by that wave alone, and the LDS executes one wave's instructions in issue order: what
 // is needed is that the COMPILER keeps the order - wavefront-scope fences + a wave barrier, no s_waitcnt.  (Workgroup scope, as first
 // written, drains the wave's LDS AND vector-memory queues at every one of the ~15 barriers of a bucket.)
-#ifndef LK_CORE_SYNC_WG
-#define LK_CORE_SYNC_WG 0
-#endif
 template <bool MW>
 __device__ __forceinline__ void core_sync() {
-    if (MW && LK_CORE_SYNC_WG) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else if (MW) {
+    if (MW) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -508,7 +481,7 @@ __device__ __forceinline__ void wave_update_core(WaveSmem& sm, double totv, int 
     CORE_STAMP(8);
     // -- Gauss-Jordan with partial pivoting (dev_solve), one column per lane
 #pragma unroll
-    for (int k = 0; k < ((LK_X_P & 8) ? 0 : 6); ++k) {
+    for (int k = 0; k < 6; ++k) {
         int p = k;
         double best = fabs(col[k]);
 #pragma unroll
@@ -549,65 +522,6 @@ __device__ __forceinline__ void wave_update_core(WaveSmem& sm, double totv, int 
         for (int m = 0; m < 6; ++m) dxv += sm.P[i * 30 + m] * lane_bcast_u(col[m], 36);
         asm volatile("" : "+v"(dxv));  // finished here: keeps its six operands from living across the loop below
     }
-#if LK_MFMA_COV
-    // -- P -= P[:,0:6] X[:,0:30] on the matrix pipe (A/B build, -DLK_MFMA_COV=1): the 30 x 30 result as 2 x 2 tiles of
-    // v_mfma_f64_16x16x4_f64, K = 6 padded to 8 -> eight instructions.  Operand layout measured on gfx950
-    // (tools/probes/mfma_f64_16x16x4_layout.hip): lane l feeds A[l % 16][l / 16] and B[l / 16][l % 16]; d[v] of lane l is
-    // D[l / 16 + 4 v][l % 16].  A = -P[:,0:6] from LDS, B = X gathered from the lanes that hold its columns (X[m][c] = col[m] of lane
-    // 6 + c), C = P.  A different summation order than the VALU form below (k = 0..3, then 4..7): not bit-identical to it.
-    {
-        typedef double lk_d4 __attribute__((ext_vector_type(4)));
-        const int r16 = lane & 15, k4 = lane >> 4;
-        double Bop[2][2], Aop[2][2];   // [k-step][tile]
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            const int j = 16 * tj + r16;
-            const int src = 6 + (j < 30 ? j : 0);
-            double t[6];
-#pragma unroll
-            for (int m = 0; m < 6; ++m) t[m] = __shfl(col[m], src, LK_WAVE);
-            Bop[0][tj] = j < 30 ? (k4 == 0 ? t[0] : k4 == 1 ? t[1] : k4 == 2 ? t[2] : t[3]) : 0.0;
-            Bop[1][tj] = (j < 30 && k4 < 2) ? (k4 == 0 ? t[4] : t[5]) : 0.0;
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            const int i = 16 * ti + r16;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int k = 4 * ks + k4;
-                Aop[ks][ti] = (i < 30 && k < 6) ? -sm.P[i * 30 + k] : 0.0;
-            }
-        }
-        lk_d4 acc[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int i = 16 * ti + k4 + 4 * v, j = 16 * tj + r16;
-                    acc[ti][tj][v] = (i < 30 && j < 30) ? sm.P[i * 30 + j] : 0.0;
-                }
-        core_sync<MW>();   // every operand has been read before any entry of P is rewritten
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[0][ti], Bop[0][tj], acc[ti][tj], 0, 0, 0);
-                acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[1][ti], Bop[1][tj], acc[ti][tj], 0, 0, 0);
-            }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int i = 16 * ti + k4 + 4 * v, j = 16 * tj + r16;
-                    if (i < 30 && j < 30) sm.P[i * 30 + j] = acc[ti][tj][v];
-                }
-        core_sync<MW>();
-    }
-#else
     CORE_STAMP(10);
     // -- P -= P[:,0:6] X[:,0:30]: lane -> column lane % 30, rows 15 * (lane / 30) ...  A row's new values depend on
     // that row only, so five rows at a time are read, then written.
@@ -617,7 +531,7 @@ __device__ __forceinline__ void wave_update_core(WaveSmem& sm, double totv, int 
 #pragma unroll
         for (int m = 0; m < 6; ++m) X[m] = __shfl(col[m], 6 + jc, LK_WAVE);
 #pragma unroll 1
-        for (int r0 = 0; r0 < ((LK_X_P & 16) ? 0 : 15); r0 += 5) {
+        for (int r0 = 0; r0 < 15; r0 += 5) {
             double nv[5];
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
@@ -635,11 +549,10 @@ __device__ __forceinline__ void wave_update_core(WaveSmem& sm, double totv, int 
             core_sync<MW>();
         }
     }
-#endif
     CORE_STAMP(11);
     // -- x (+)= dx (eskf.cc:18-29): rotation by lane 0, the 27 additive components by lanes 3..29
     const double d0 = lane_bcast_u(dxv, 0), d1 = lane_bcast_u(dxv, 1), d2 = lane_bcast_u(dxv, 2);
-    if (lane == 0 && !(LK_X_P & 32)) {
+    if (lane == 0) {
         double E[9], Rn[9];
         exp3_1e5(d0, d1, d2, E);
         mat3_mul(sm.x, E, Rn);
@@ -979,7 +892,7 @@ __device__ __forceinline__ void wave_predict_core(WaveSmem& sm, const double* __
     // where it is used is a trip to the L2 on a chain that has nothing else to do)
     double qd = 0.0;
     if (q_diag && lane < 30) qd = Q[lane * 31];
-    if (lane < 2 && !(LK_X_P & 1)) {
+    if (lane < 2) {
         const double* x = sm.x;
         const double sc = lane == 0 ? -dt_cov : dt;
         const double thr = lane == 0 ? 0.0000001 : 0.00001;   // math_utils.hpp:19-32 / :54-68
@@ -1007,7 +920,7 @@ __device__ __forceinline__ void wave_predict_core(WaveSmem& sm, const double* __
     // [I | dt I at col 6], rows 6..8 = [B60 | I | dt I at col 15 | dt R at col 18].  Each block is handled by ALL lanes with one
     // straight-line expression (90 entries = two rounds of 64 lanes) instead of one loop whose lanes fall into different blocks
     // and execute all three shapes in turn; every entry is the same sum in the same order as before (bit-identical).
-    if (!(LK_X_P & 2)) {  // rows 0..8 of B = Fx * P, in place (rows >= 9 of B are rows of P)
+    {  // rows 0..8 of B = Fx * P, in place (rows >= 9 of B are rows of P)
         double nb[6];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -1048,7 +961,7 @@ __device__ __forceinline__ void wave_predict_core(WaveSmem& sm, const double* __
     }
     core_sync<MW>();
     CORE_STAMP(1);
-    if (!(LK_X_P & 2)) {  // columns 0..8 of B * Fx^T, in place: the same three shapes, 30 rows x 3 columns each
+    {  // columns 0..8 of B * Fx^T, in place: the same three shapes, 30 rows x 3 columns each
         double nc[6];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -1094,13 +1007,12 @@ __device__ __forceinline__ void wave_predict_core(WaveSmem& sm, const double* __
     core_sync<MW>();
     CORE_STAMP(2);
     const double dt2 = dt_cov * dt_cov;
-    if (LK_X_P & 4) {
-    } else if (q_diag) {   // Q of initProcessCovQ (eskf.cc:47-62) is diagonal: the other 870 terms are + dt^2 * 0
+    if (q_diag) {   // Q of initProcessCovQ (eskf.cc:47-62) is diagonal: the other 870 terms are + dt^2 * 0
         if (lane < 30) sm.P[lane * 31] = sm.P[lane * 31] + dt2 * qd;
     } else {
         for (int e = lane; e < 900; e += LK_WAVE) sm.P[e] = sm.P[e] + dt2 * Q[e];
     }
-    if (lane == 1 && !(LK_X_P & 1)) {
+    if (lane == 1) {
         double* x = sm.x;
         for (int i = 0; i < 9; ++i) x[i] = Rn[i];
         for (int i = 0; i < 6; ++i) x[9 + i] += dpv[i];

@@ -211,10 +211,14 @@ static int launch(lk_handle* h, const char* name, F&& f) {
 // Every device allocation of this library.  LEGKILO_POISON_POOLS=1 (test aid): the fresh memory is filled with 0x5a bytes instead of whatever the
 // allocator hands out - in a young process zeros, in a long-lived one somebody's old data - so that a kernel which trusts memory nobody has
 // written meets garbage in EVERY run (the whole GPU suite is run that way once per round: tools/gpu_poison_suite.sh)
+// (set when the process starts, or by a test around single calls: both count)
+static bool lk_poison_pools() {
+    static const bool at_start = getenv("LEGKILO_POISON_POOLS") != nullptr;
+    return at_start || getenv("LEGKILO_POISON_POOLS") != nullptr;
+}
 static hipError_t lk_hip_malloc(void** p, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes);
-    static const bool poison = getenv("LEGKILO_POISON_POOLS") != nullptr;
-    if (e == hipSuccess && (poison || getenv("LEGKILO_POISON_POOLS")) && bytes) {
+    if (e == hipSuccess && lk_poison_pools() && bytes) {
         e = hipMemset(*p, 0x5a, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();   // (the fill runs on the null stream, the library's streams do not wait for that one)
     }
@@ -242,6 +246,12 @@ struct DevTemps {
         return e;
     }
 };
+
+// LEGKILO_XID=0: the generic residual kernels instead of those specialised for ext_R == I (the tests' reference); read once per process
+static bool lk_xid_enabled() {
+    static const bool v = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
+    return v;
+}
 
 static unsigned int next_pow2(unsigned int v) {
     unsigned int p = 1;

@@ -19,13 +19,6 @@
 #include "lk_eig3.h"
 
 #define LK_MB 256  // threads per block in the per-root kernels (4 waves = 4 roots in flight)
-#ifndef LK_X_CHILD_CONST
-#ifndef LK_X_ATTR
-#define LK_X_ATTR 0   // attribution builds only (results WRONG by construction): 1 no plane_var, 2 no eigen-decomposition in the full fit, 4 no
-                      // point_geom for the new points, 8 no refit-event tests, 16 no index sort - tools/gpu_ov_attr.sh times the overlay root pass on each
-#endif
-#define LK_X_CHILD_CONST 1   // apply_leaf: a child it has just created is known without reading it back (0: node_load, A/B)
-#endif
 
 __device__ __forceinline__ void wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -46,9 +39,6 @@ __device__ __forceinline__ int wave_min_i(int v) {
 // the second), so the count halves with every step: ceil(N/2) + ceil(N/4) + ... exchanges instead of 6 N (N = 21: 24 instead of
 // 126; N = 9: 13 instead of 54), after which lane L holds the complete sum of ONE component, and N more shuffles gather them.
 // The summation order differs from wave_sum's butterfly (a different, equally valid rounding of the same sum).
-#ifndef LK_WSN_READLANE
-#define LK_WSN_READLANE 0
-#endif
 template <int N>
 __device__ __forceinline__ void wave_sum_n(double* v) {
     const int lane = threadIdx.x & 63;
@@ -82,12 +72,8 @@ __device__ __forceinline__ void wave_sum_n(double* v) {
         if (rem >= H0) rem -= H0, src |= 1;
         // gathered with ds_bpermute, not v_readlane: 2 N scalar results at once (N = 21: 42 SGPRs on top of a kernel that already
         // spills scalars) gave wrong values in lk_insert_root_kernel - varying with unrelated code changes - while the vector form
-        // is stable (round 3, tools A/B: -DLK_READLANE=0 fixed every failing test)
-#if LK_WSN_READLANE
-        r[c] = lane_bcast_u(v[0], src);    // A/B build only (tools/probes/readlane_gather): the v_readlane form of the gather
-#else
+        // is stable (round 3: the vector form fixed every failing test)
         r[c] = __shfl(v[0], src, LK_WAVE);
-#endif
     }
 #pragma unroll
     for (int c = 0; c < N; ++c) v[c] = r[c];
@@ -106,69 +92,11 @@ __device__ __forceinline__ void load_pt(const lk_pt_rec* base, const int* idx, i
     for (int c = 0; c < 6; ++c) var[c] = r->var[c];
 }
 
-// symmetric 3x3 eigen-solver; evecs columns = eigenvectors (stand-in for EigenSolver, voxel_map.cc:55).  Default: the closed form
-// of lk_eig3.h (one plane fit is the serial work of one wave: ~0.5 us instead of the 3.8 us of 6-7 Jacobi sweeps); -DLK_EIG_JACOBI=1
-// keeps the cyclic Jacobi iteration the oracle runs (A/B).
-#ifndef LK_EIG_JACOBI
-#define LK_EIG_JACOBI 0
-#endif
+// symmetric 3x3 eigen-solver (stand-in for EigenSolver, voxel_map.cc:55): the closed form of lk_eig3.h (one plane fit is the serial work of
+// one wave: ~0.5 us instead of the 3.8 us of 6-7 sweeps of the cyclic Jacobi iteration the oracle runs).
 // eigenvectors as three separate vectors (see lk_eig_sym3_cols: a 3 x 3 array picked by a run-time column index ends up in LDS / scratch)
-__device__ __forceinline__ void eig_sym3_dev(const double* Ain, double* ev, double* V);
 __device__ __forceinline__ void eig_sym3_cols_dev(const double* Ain, double* ev, double* v0, double* v1, double* v2) {
-#if !LK_EIG_JACOBI
     lk_eig_sym3_cols(Ain, ev, v0, v1, v2);
-#else
-    double V[9];
-    eig_sym3_dev(Ain, ev, V);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v0[k] = V[3 * k + 0], v1[k] = V[3 * k + 1], v2[k] = V[3 * k + 2];
-#endif
-}
-__device__ __forceinline__ void eig_sym3_dev(const double* Ain, double* ev, double* V) {
-#if !LK_EIG_JACOBI
-    lk_eig_sym3(Ain, ev, V);
-    return;
-#endif
-    double a[3][3] = {{Ain[0], Ain[1], Ain[2]}, {Ain[1], Ain[3], Ain[4]}, {Ain[2], Ain[4], Ain[5]}};
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-        double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
-        if (off <= 1e-300 || off <= 1e-34 * diag) break;
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 3; ++q) {
-                if (a[p][q] != 0.0) {
-                    double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-                    double t = ((theta >= 0) ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        double akp = a[k][p], akq = a[k][q];
-                        a[k][p] = c * akp - s * akq;
-                        a[k][q] = s * akp + c * akq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        double apk = a[p][k], aqk = a[q][k];
-                        a[p][k] = c * apk - s * aqk;
-                        a[q][k] = s * apk + c * aqk;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        double vkp = v[k][p], vkq = v[k][q];
-                        v[k][p] = c * vkp - s * vkq;
-                        v[k][q] = s * vkp + c * vkq;
-                    }
-                }
-            }
-    }
-    ev[0] = a[0][0], ev[1] = a[1][1], ev[2] = a[2][2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[3 * i + j] = v[i][j];
 }
 
 // init_plane, voxel_map.cc:42-117.  Whole wave; returns is_plane (uniform).
@@ -720,7 +648,7 @@ static_assert(sizeof(LkGroup) == 64, "group descriptor must be 64 B");
 #endif
 // Round 6: the four header words {leaf, block, cnt, decided} live in a DENSE int4 array of their own (LkOverlay::jobhdr, same [g][t] index): the fit passes look at
 // every touched root's three job slots and nearly all are empty - at a 96-B stride that scan was half of their HBM traffic.  The words below stay for the layout.
-struct LkFitJob {   // 96 B: a plane fit the overlay replay's root pass leaves to lk_ov_fit_lane_kernel (apply_leaf<DEFER>)
+struct LkFitJob {   // 96 B: a plane fit the overlay replay's root pass leaves to lk_ov_fit_group_kernel (apply_leaf<DEFER>)
     int leaf, block, cnt, decided;   // (header, now in jobhdr) cnt = points of the leaf's last refit event (0: no fit), block = where they are, decided = is_plane of that event
     double s9[9];                    // its moment sums (sum p, sum p p^T)
     int base_block, n_base;          // a SPLIT leaf (lk_ov_root_lane_kernel): its first n_base points are in the base map's block base_block; else n_base = 0
@@ -785,7 +713,7 @@ __device__ __forceinline__ void insert_defer(const LkMap& map, int leaf, int do_
 // still sit in the BASE map's block cow_src.  They are read from there and ALL node points (old + new) are stored to the private block;
 // the return value says whether that happened (false: the leaf did not take the register path, the caller copies the old points).
 // DEFER (overlay replay): the leaf's one full plane fit is not made here - lane 0 writes a job (leaf, block, the last event's count,
-// decision and moment sums) and lk_ov_fit_lane_kernel, one lane per job, does the eigen-decomposition, plane_var and the commit.
+// decision and moment sums) and lk_ov_fit_eig_kernel / lk_ov_fit_group_kernel do the eigen-decomposition, plane_var and the commit.
 template <bool DEFER = false, typename PointAt, typename StoreIdx>
 __device__ __forceinline__ bool apply_leaf(const LkMap& map, const LkParams& pr, const int Tn, const int Tp, const int To, const int g,
                                            const int root, const LeafInfo& li, int off, PointAt point_at, StoreIdx store_idx,
@@ -808,11 +736,7 @@ __device__ __forceinline__ bool apply_leaf(const LkMap& map, const LkParams& pr,
         double pc[3] = {pn->voxel_center[0], pn->voxel_center[1], pn->voxel_center[2]};
         const int pl = bcast0(pn->layer);
         leaf = create_child(map, Tp, To, pc, pn->quater_length, pl);
-#if LK_X_CHILD_CONST
         r.npts = 0, r.new_points = 0, r.block = -1, r.layer = pl + 1, r.state = LK_NODE_UPDATE_ENABLE;
-#else
-        r = node_load(&map.nodes[leaf]);
-#endif
         lplane = false;
     }
     lk_node_rec* ln = &map.nodes[leaf];
@@ -877,13 +801,7 @@ __device__ __forceinline__ bool apply_leaf(const LkMap& map, const LkParams& pr,
             const int k = max(min(rem, lim), 1);
             cur += k, newp += k, consumed += k;
             if (m0 == 0 ? cur > thr : newp > 5) {
-#if LK_X_ATTR & 8
-                fit.is_plane = true;
-#pragma unroll
-                for (int q = 0; q < 9; ++q) fit.s9[q] = ppw[q % 3] + (double)cur;
-#else
                 fit = plane_test_regs<true>(ppw, lane < cur, cur, pr.planer_threshold);
-#endif
                 fit_count = cur, fitted = true, newp = 0;
                 if (m0 == 0) {
                     if (fit.is_plane) {
@@ -943,21 +861,11 @@ __device__ __forceinline__ bool apply_leaf(const LkMap& map, const LkParams& pr,
                 const bool decided = fit.is_plane;
                 const PlaneFit last = fit;   // the last event tested exactly these fit_count points: its sums are reused
                 INS_STAMP(3);
-#if LK_X_ATTR & 2
-                fit = plane_test_regs<true, true>(ppw, lane < fit_count, fit_count, pr.planer_threshold, &last);
-                fit.vmin[2] = fit.vmid[1] = fit.vmax[0] = 1.0, fit.emin = 1e-3, fit.emid = 1.0, fit.emax = 2.0;
-#else
                 fit = plane_test_regs<false, true>(ppw, lane < fit_count, fit_count, pr.planer_threshold, &last);
-#endif
                 INS_STAMP(4);
                 fit.is_plane = decided;  // control flow above already followed the event's decision
                 double acc21[21];
-#if LK_X_ATTR & 1
-#pragma unroll
-                for (int q = 0; q < 21; ++q) acc21[q] = 1e-6;
-#else
                 if (fit.is_plane) plane_var_regs(fit, ppw, pvar, lane < fit_count, fit_count, acc21);
-#endif
                 INS_STAMP(5);
                 plane_commit(&map.planes[leaf], &map.match[leaf], fit, acc21, fit_count);
                 INS_STAMP(6);
@@ -1127,7 +1035,7 @@ __device__ __forceinline__ void dev_insert_root(const LkMap& map, const LkParams
         }
         const lk_pt_rec* cow_src = nullptr;
         // this root's fit jobs (apply_leaf<DEFER>): none yet.  Entry [g][t] = its g-th inline leaf group: nearly every root is ONE group, so
-        // plane 0 is dense for lk_ov_fit_lane_kernel's lanes (job_stride = entries per plane)
+        // plane 0 is dense for the fit kernels' lanes (job_stride = entries per plane)
         if (OV && lane < LK_INLINE_GROUPS) jobhdr[(size_t)lane * job_stride + tix].z = 0;
         int job_i = 0;
         int cow_n = 0;   // old points that still sit in the base block
@@ -1209,11 +1117,7 @@ __device__ __forceinline__ void dev_insert_root(const LkMap& map, const LkParams
         // sort the root's indices in registers: rank = number of smaller indices, then a forward permute
         const int myidx = (lane < m) ? (in_slots ? slot_idx : map.scratch[base + lane]) : 0x7fffffff;
         int rank = 0;
-#if LK_X_ATTR & 16
-        rank = lane;
-#else
         for (int j = 0; j < m; ++j) rank += (__builtin_amdgcn_readlane(myidx, j) < myidx) ? 1 : 0;
-#endif
         const int sidx = __builtin_amdgcn_ds_permute(((lane < m) ? rank : lane) << 2, myidx);  // lane j: j-th smallest
         const bool mine = lane < m;
         // every lane walks (read-only) to the node its point would be pushed into: down through initialised non-planar nodes
@@ -1276,15 +1180,12 @@ __device__ __forceinline__ void dev_insert_root(const LkMap& map, const LkParams
                 ++ngroups;
             }
         }
-#ifndef LK_X_NOINLINE
-#define LK_X_NOINLINE 0   // debug / A-B only: 1 = every root hands its groups to lk_insert_apply_kernel
-#endif
         if (OV && cow_src) {   // fused only when the root itself is the one leaf all its points go to
             const int l0 = __ffsll((long long)__ballot(mine)) - 1;
-            if (ngroups != 1 || LK_X_NOINLINE || __builtin_amdgcn_readlane(tnode, l0 < 0 ? 0 : l0) != root) cow_finalise();
+            if (ngroups != 1 || __builtin_amdgcn_readlane(tnode, l0 < 0 ? 0 : l0) != root) cow_finalise();
         }
         ROOT_HIST(5, tr_);
-        if (ngroups <= LK_INLINE_GROUPS && !LK_X_NOINLINE) {
+        if (ngroups <= LK_INLINE_GROUPS) {
             // ---- one leaf group (98 % of the roots) or a few: applied here, from registers, one after the other.  A group's points are
             // compacted to lanes 0 .. g-1 in lane (= input) order - the identity when the root is one group.  The launch for the emitted
             // groups then finds nothing to do in the steady state (a handful of groups cost it ~10 us per bucket otherwise).
@@ -1312,14 +1213,7 @@ __device__ __forceinline__ void dev_insert_root(const LkMap& map, const LkParams
                         if (valid) load_pt(pv, nullptr, idx, pt.pw, pt.var);
                     } else {
                         const float qx = __shfl(cx, rr, LK_WAVE), qy = __shfl(cy, rr, LK_WAVE), qz = __shfl(cz, rr, LK_WAVE);
-#if LK_X_ATTR & 4
-                        if (valid) {
-                            pt.pw[0] = qx, pt.pw[1] = qy, pt.pw[2] = qz;
-                            pt.var[0] = pt.var[3] = pt.var[5] = 1e-4, pt.var[1] = pt.var[2] = pt.var[4] = 0.0;
-                        }
-#else
                         if (valid) geom_to_pt(point_geom(qx, qy, qz, bc, pr), pt);
-#endif
                     }
                 };
                 auto store_idx = [&](int gb) {

@@ -3,18 +3,13 @@
 #define LK_TU_OVERLAY 1
 #include "lk_internal.h"
 
-static int ov_root_bits() {   // LEGKILO_OV_ROOT_BITS=0: no "takes the point at the root" bit for the re-projection pass (A/B)
-    static const int v = getenv("LEGKILO_OV_ROOT_BITS") == nullptr || atoi(getenv("LEGKILO_OV_ROOT_BITS")) != 0;
-    return v;
-}
-
 // Round 6: the FRONT of a bucket index of the ragged batch with insert as ONE launch when every bucket holds <= LK_SCAN_WAVE_MAX points (a recorded
 // scan's 2 ms bins): lk_rag_advance_kernel (messages + predict), lk_ov_residual_kernel, lk_update_wave_ragged_kernel, lk_ov_begin_kernel and
 // lk_ov_reproject_kernel were five one-wave-per-scan launches, each paying a launch boundary (~5 us for 1 024 one-wave workgroups whatever they do) and
 // its own load / store of the filter's 7.6 KB.  Here one wave per scan runs the five bodies back to back - the one-wave filter cores and the tile code
 // of dev_scan_wave, the overlay lookup of lk_ov_residual_kernel - with state and covariance in LDS from the first message to the update.  Same device
 // functions, same order of sums (tile totals in tile order, as lk_update_wave_kernel adds up to eight of them): bit-identical to the five launches
-// (test_batch_replay_overlay_ragged compares both against the oracle; LEGKILO_RAG_FUSE=0 is the A/B).
+// (test_batch_replay_overlay_ragged compares both against the oracle).
 extern "C++" {
 template <bool XID>
 __global__ void __launch_bounds__(LK_WAVE, 2)
@@ -251,7 +246,7 @@ static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t bigges
     if (e == hipSuccess) e = get(&o.cplx, s * n.scan_cap * 2 * sizeof(int));
     if (e == hipSuccess) e = get(&o.ptroot, s * n.scan_cap * sizeof(int));
     if (e == hipSuccess && !h->d_ov_status) e = hipMalloc(&h->d_ov_status, 8 * sizeof(unsigned int));
-    if (e == hipSuccess && getenv("LEGKILO_POISON_POOLS")) {
+    if (e == hipSuccess && lk_poison_pools()) {
         // test aid: fresh pools hold 0x5a bytes instead of whatever the allocator hands out (usually zeros) - a kernel that trusts a record
         // nobody has written then faults HERE AND NOW, not in the one process whose allocation history leaves garbage there
         hipLaunchKernelGGL(lk_ov_poison_nodes_kernel, dim3((unsigned int)((s * n.nodes_cap + 255) / 256)), dim3(256), 0, h->stream, o.nodes, s * n.nodes_cap);
@@ -348,30 +343,20 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
     if (rc) return rc;
     hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, st, h->d_filters, S, t_begin);
     HIPCHK(h, hipMemsetAsync(ov.frozen, 0, (size_t)2 * ov.bit_words * sizeof(unsigned int), st));
-    static const bool frozen_bits = getenv("LEGKILO_OV_FROZEN_BITS") == nullptr || atoi(getenv("LEGKILO_OV_FROZEN_BITS")) != 0;   // 0: every point through the probes and the walk (A/B)
-    if (frozen_bits) LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, ov_root_bits()));
-    static const bool xid_enable = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
-    const auto res_kernel = (h->pr.ext_identity && xid_enable) ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
-    // root pass: the fast path (lk_ov_point_geom_kernel + lk_ov_root_lane_kernel: root leaves that append / refit / freeze) and the generic pass over what it leaves
-    // (LEGKILO_OV_FAST=0: the generic pass over every touched root, round 4's path; A/B)
-    // LEGKILO_OV_FAST: 1 (default) = the fast path - one thread per point (geometry) + one lane per root (lk_ov_point_geom_kernel,
-    // lk_ov_root_lane_kernel), the generic pass for what they leave; 0 = the generic pass over every touched root (round 4's path; A/B)
-    static const bool ov_fast = getenv("LEGKILO_OV_FAST") == nullptr || atoi(getenv("LEGKILO_OV_FAST")) != 0;
-    static const int root_waves = getenv("LEGKILO_OV_ROOT_WAVES") ? atoi(getenv("LEGKILO_OV_ROOT_WAVES")) : 3;   // generic pass without the fit: 184 VGPRs at 2 waves, 168 at 3
-    const auto root_kernel = ov_fast ? (root_waves >= 4 ? lk_ov_insert_root_kernel<4, true> : root_waves == 3 ? lk_ov_insert_root_kernel<3, true> : lk_ov_insert_root_kernel<2, true>)
-                                     : (root_waves >= 4 ? lk_ov_insert_root_kernel<4, false> : root_waves == 3 ? lk_ov_insert_root_kernel<3, false> : lk_ov_insert_root_kernel<2, false>);
-    if (ov_fast) LAUNCH(h, "ov_base_sums", hipLaunchKernelGGL(lk_ov_base_sums_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, ov.base_sums));
-    static const int ov_mat_wg = getenv("LEGKILO_OV_MAT_WG") ? std::max(1, atoi(getenv("LEGKILO_OV_MAT_WG"))) : 0;
-    static const int ov_root_wg = getenv("LEGKILO_OV_ROOT_WG") ? std::max(1, atoi(getenv("LEGKILO_OV_ROOT_WG"))) : 0;
-    static const int fit_blocks = getenv("LEGKILO_OV_FIT_BLOCKS") ? std::max(1, atoi(getenv("LEGKILO_OV_FIT_BLOCKS"))) : 12;   // round 6: with the job headers in a dense array 6 / 8 / 12 / 16 / 24 waves per scan -> fit pass 1.75 / 1.92 / 1.61 / 2.12 / 1.71 ms (before: best at 6, 1.89)
-    static const int ov_waves_per_slot = getenv("LEGKILO_OV_WG_PER_SLOT") ? std::max(1, atoi(getenv("LEGKILO_OV_WG_PER_SLOT"))) : 0;
-    // Slot groups on separate HIP streams (LEGKILO_OV_GROUPS, default 4 - round 6, same box: 15.14 / 13.48 / 13.02 / 12.74 ms with 1 / 2 / 3 / 4 groups, 14.8 / 14.2 with
+    // both bits of every cell (LkOverlay::frozen): frozen leaf, and takes the point at the root
+    LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, 1));
+    const auto res_kernel = (h->pr.ext_identity && lk_xid_enabled()) ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
+    // root pass: one thread per point (geometry) + one lane per root (lk_ov_point_geom_kernel, lk_ov_root_lane_kernel: root leaves that append / refit /
+    // freeze), then the generic pass over what they leave - three waves per SIMD (without the fit: 184 VGPRs at 2 waves, 168 at 3)
+    LAUNCH(h, "ov_base_sums", hipLaunchKernelGGL(lk_ov_base_sums_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, ov.base_sums));
+    const int fit_blocks = 12;   // round 6: with the job headers in a dense array 6 / 8 / 12 / 16 / 24 waves per scan -> fit pass 1.75 / 1.92 / 1.61 / 2.12 / 1.71 ms (before: best at 6, 1.89)
+    // Four slot groups on separate HIP streams (round 6, same box: 15.14 / 13.48 / 13.02 / 12.74 ms with 1 / 2 / 3 / 4 groups, 14.8 / 14.2 with
     // 6 / 8: beyond four streams the queues share hardware): the scans are independent, and the passes of a bucket are of two
     // kinds - the root pass issues VALU work at 2.8 TB/s of HBM traffic, the others (re-projection, copy-on-write, plane fits) only move
     // bytes - so one group's root pass runs beside the other group's memory passes.  A group is the same launches with every per-slot
     // array offset to its first slot (ov_at).  Profiling mode (per-launch events + sync) and small batches stay on one stream.
-    static const int ov_groups_env = getenv("LEGKILO_OV_GROUPS") ? std::min(std::max(atoi(getenv("LEGKILO_OV_GROUPS")), 1), (int)lk_handle::kMaxGroups) : 4;
-    const int ngroups = (!h->profiling && S >= 64 * ov_groups_env) ? ov_groups_env : 1;
+    const int ov_groups = 4;
+    const int ngroups = (!h->profiling && S >= 64 * ov_groups) ? ov_groups : 1;
     hipStream_t streams[lk_handle::kMaxGroups];
     streams[0] = h->stream;
     for (int g = 1; g < lk_handle::kMaxGroups; ++g) streams[g] = h->side[g - 1];
@@ -408,30 +393,18 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
         LAUNCH(h, "ov_begin", hipLaunchKernelGGL(lk_ov_begin_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, ov));
         LAUNCH(h, "ov_reproject", hipLaunchKernelGGL(lk_ov_reproject_kernel, dim3((nb + LK_WAVE - 1) / LK_WAVE, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
         // per-root passes: enough waves per slot to cover its touched roots a few at a time, ~4096 workgroups per launch at least
-        const int per_slot = ov_waves_per_slot ? ov_waves_per_slot : std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
+        const int per_slot = std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
         // (measured at 1024 slots x 20 000-point buckets, workgroups per slot: copy-on-write 2.8 / 6.6 / 12.2 ms per batch at 4 / 16 / 32 - a wave takes 64
         // roots, more waves only find nothing to do; root pass 12.8 / 11.0 / 11.7 - a wave works through its roots one after the other)
-        const int mat_per_slot = ov_mat_wg ? ov_mat_wg : std::max(1, per_slot / 2), root_per_slot = ov_root_wg ? ov_root_wg : 3 * per_slot;
-        LAUNCH(h, "ov_materialise", hipLaunchKernelGGL(ov_fast ? lk_ov_materialise_kernel<true> : lk_ov_materialise_kernel<false>, dim3(mat_per_slot, Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr));
-        // one WAVE per touched root (the leaf's plane fit only decided), then the fits one LANE each
-        if (ov_fast) {
-            LAUNCH(h, "ov_point_geom", hipLaunchKernelGGL(lk_ov_point_geom_kernel, dim3((nb + 255) / 256, Sg), dim3(256), 0, st, ov, h->pr, fl, src));
-            static const int lane_blocks = getenv("LEGKILO_OV_LANE_BLOCKS") ? std::max(1, atoi(getenv("LEGKILO_OV_LANE_BLOCKS"))) : 0;
-            LAUNCH(h, "ov_root_lane", hipLaunchKernelGGL(lk_ov_root_lane_kernel, dim3(lane_blocks ? lane_blocks : std::max(4, (nb + 16 * LK_WAVE - 1) / (16 * LK_WAVE)), Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-            LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL(root_kernel, dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
-        } else {
-            LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL(root_kernel, dim3(root_per_slot, Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
-        }
+        LAUNCH(h, "ov_materialise", hipLaunchKernelGGL(lk_ov_materialise_kernel<true>, dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr));
+        // one WAVE per touched root (the leaf's plane fit only decided), then the fits a group of lanes each
+        LAUNCH(h, "ov_point_geom", hipLaunchKernelGGL(lk_ov_point_geom_kernel, dim3((nb + 255) / 256, Sg), dim3(256), 0, st, ov, h->pr, fl, src));
+        LAUNCH(h, "ov_root_lane", hipLaunchKernelGGL(lk_ov_root_lane_kernel, dim3(std::max(4, (nb + 16 * LK_WAVE - 1) / (16 * LK_WAVE)), Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+        LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL((lk_ov_insert_root_kernel<3, true>), dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
         LAUNCH(h, "ov_fit_eig", hipLaunchKernelGGL(lk_ov_fit_eig_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-        static const bool fit_group = getenv("LEGKILO_OV_FIT_GROUP") == nullptr || atoi(getenv("LEGKILO_OV_FIT_GROUP")) != 0;   // 0: round 5's one lane per fit (A/B)
-        if (fit_group)
-            LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-        else
-            LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_lane_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-        static const int ov_apply_wg = getenv("LEGKILO_OV_APPLY_WG") ? std::max(1, atoi(getenv("LEGKILO_OV_APPLY_WG"))) : 0;
-        static const int ov_fb_wg = getenv("LEGKILO_OV_FB_WG") ? std::max(1, atoi(getenv("LEGKILO_OV_FB_WG"))) : 0;
-        LAUNCH(h, "ov_insert_apply", hipLaunchKernelGGL(lk_ov_insert_apply_kernel, dim3(ov_apply_wg ? ov_apply_wg : per_slot, Sg), dim3(LK_MB), 0, st, ov, h->pr, fl, src));
-        LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(Sg, ov_fb_wg ? ov_fb_wg : 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, Sg));   // (1 024 slots, workgroups 8 / 32 / 128 / 256 / 512: 0.54 / 0.26 / 0.15 / 0.17 / 0.16 ms per batch; a workgroup or more per slot: 0.34)
+        LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+        LAUNCH(h, "ov_insert_apply", hipLaunchKernelGGL(lk_ov_insert_apply_kernel, dim3(per_slot, Sg), dim3(LK_MB), 0, st, ov, h->pr, fl, src));
+        LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(Sg, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, Sg));   // (1 024 slots, workgroups 8 / 32 / 128 / 256 / 512: 0.54 / 0.26 / 0.15 / 0.17 / 0.16 ms per batch; a workgroup or more per slot: 0.34)
         if (k + 1 < live.size())
             LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q,
                                                     t_begin + bucket_dt[live[k + 1]], 2));
@@ -523,8 +496,8 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
     }
     hipStream_t st = h->stream;
     HIPCHK(h, hipMemcpyAsync(h->d_ov_priors, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
-    static const bool xid_enable = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
-    const auto res_kernel = (h->pr.ext_identity && xid_enable) ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
+    const bool xid = h->pr.ext_identity && lk_xid_enabled();
+    const auto res_kernel = xid ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
     unsigned int stt[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     for (int attempt = 0;; ++attempt) {
         const LkOverlay ov = h->ov;
@@ -533,13 +506,13 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
         if (rc) return rc;
         hipLaunchKernelGGL(lk_set_times_ragged_kernel, dim3((S + 63) / 64), dim3(64), 0, st, fl, S, d_tbegin);
         HIPCHK(h, hipMemsetAsync(ov.frozen, 0, (size_t)2 * ov.bit_words * sizeof(unsigned int), st));
-        LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, ov_root_bits()));
+        LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, 1));
         LAUNCH(h, "ov_base_sums", hipLaunchKernelGGL(lk_ov_base_sums_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, ov.base_sums));
         {
             const unsigned int per = std::max(std::max(ov.hash_cap, ov.bit_words), (unsigned int)LK_CTR_COUNT);
             LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, S), dim3(256), 0, st, ov));
         }
-        const bool rag_resident = getenv("LEGKILO_RAG_RESIDENT") == nullptr || atoi(getenv("LEGKILO_RAG_RESIDENT")) != 0;   // 0: launch by launch (A/B, and the bit-identity reference of the tests: read at every call)
+        const bool rag_resident = getenv("LEGKILO_RAG_RESIDENT") == nullptr || atoi(getenv("LEGKILO_RAG_RESIDENT")) != 0;   // 0: launch by launch (the bit-identity reference of the tests: read at every call)
         h->ov_res_rounds = 0;
         const bool resident = rag_resident && biggest <= LK_SCAN_WAVE_MAX && !rg.bstart;
         if (resident) {
@@ -554,10 +527,9 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
             unsigned int* pending = reinterpret_cast<unsigned int*>(cur + 2 * (size_t)S);
             HIPCHK(h, hipMemsetAsync(cur, 0, sizeof(int) * (2 * (size_t)S + 4), st));
             const LkPtSrc fsrc = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, 0, fb_b};
-            static const int ov_fb_wg_s = getenv("LEGKILO_OV_FB_WG") ? std::max(1, atoi(getenv("LEGKILO_OV_FB_WG"))) : 0;
             unsigned int rounds = 0;
             for (;; ++rounds) {
-                rc = ov_scan_launch(h, h->pr.ext_identity && xid_enable, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending);   // lk_ovscan.hip
+                rc = ov_scan_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending);   // lk_ovscan.hip
                 if (rc) return rc;
                 unsigned int n_pending = 0;
                 HIPCHK(h, hipMemcpyAsync(&n_pending, pending, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -565,51 +537,38 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
                 if (!n_pending) break;
                 if (rounds > ldb + 1) return fail(h, LK_ERR_STATE, "scan-resident overlay replay: more fallback rounds than buckets");
                 HIPCHK(h, hipMemsetAsync(pending, 0, sizeof(unsigned int), st));
-                LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, ov_fb_wg_s ? ov_fb_wg_s : 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, fsrc, (int)S));
+                LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, fsrc, (int)S));
             }
             h->ov_res_rounds = rounds + 1;
-            if (getenv("LEGKILO_RAG_VERBOSE")) fprintf(stderr, "[legkilo] scan-resident overlay replay: %u launches of the scan kernel for %d scans x <= %zu buckets\n", rounds + 1, S, ldb);
         }
         for (size_t b = 0; b < (resident ? 0 : ldb); ++b) {
             const int nb = std::max(1, max_n ? max_n[b] : biggest);
-            const int nblk = (nb + LK_RB - 1) / LK_RB;
             const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr};
-            static const bool rag_fuse = getenv("LEGKILO_RAG_FUSE") == nullptr || atoi(getenv("LEGKILO_RAG_FUSE")) != 0;   // 0: the five launches (A/B, and the bit-identity reference)
-            if (rag_fuse && biggest <= LK_SCAN_WAVE_MAX) {
-                const auto front = (h->pr.ext_identity && xid_enable) ? lk_rag_ov_front_kernel<true> : lk_rag_ov_front_kernel<false>;
+            if (biggest <= LK_SCAN_WAVE_MAX) {
+                // buckets of <= LK_SCAN_WAVE_MAX points: three launches per bucket index (front, mid, tail); the tail at one wave per slot:
+                // 29.2 -> 26.4 ms against four (fewer waves to dispatch)
+                const auto front = xid ? lk_rag_ov_front_kernel<true> : lk_rag_ov_front_kernel<false>;
                 LAUNCH(h, "rag_ov_front", hipLaunchKernelGGL(front, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, h->d_Q, rg, d_pts, (int)b, msg_kind));
+                LAUNCH(h, "ov_mid", hipLaunchKernelGGL(lk_ov_mid_kernel<true>, dim3(S), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
+                LAUNCH(h, "ov_tail", hipLaunchKernelGGL(lk_ov_tail_kernel, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
             } else {
+                const int nblk = (nb + LK_RB - 1) / LK_RB;
+                const int per_slot = std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
+                const int fit_blocks = std::max(1, std::min(8, (nb + 63) / 64));
                 LAUNCH(h, "rag_advance", hipLaunchKernelGGL(lk_rag_advance_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_Q, rg, (int)b, msg_kind));
                 LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, S), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, h->d_partials, h->part_stride));
                 LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_partials, h->part_stride, h->d_Q, rg, (int)b, 1));
                 LAUNCH(h, "ov_begin", hipLaunchKernelGGL(lk_ov_begin_kernel, dim3(S), dim3(LK_WAVE), 0, st, ov));
                 LAUNCH(h, "ov_reproject", hipLaunchKernelGGL(lk_ov_reproject_kernel, dim3((nb + LK_WAVE - 1) / LK_WAVE, S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
-            }
-            const int per_slot = std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
-            if (rag_fuse && biggest <= LK_SCAN_WAVE_MAX) {
-                static const int mid_threads = getenv("LEGKILO_RAG_MID_THREADS") ? (atoi(getenv("LEGKILO_RAG_MID_THREADS")) <= 64 ? 64 : atoi(getenv("LEGKILO_RAG_MID_THREADS")) <= 128 ? 128 : 256) : LK_MB;
-                LAUNCH(h, "ov_mid", hipLaunchKernelGGL(lk_ov_mid_kernel<true>, dim3(S), dim3(mid_threads), 0, st, fmap, ov, h->pr, fl, src));
-            } else {
                 LAUNCH(h, "ov_materialise", hipLaunchKernelGGL(lk_ov_materialise_kernel<true>, dim3(std::max(1, per_slot / 2), S), dim3(LK_MB), 0, st, fmap, ov, h->pr));
                 LAUNCH(h, "ov_point_geom", hipLaunchKernelGGL(lk_ov_point_geom_kernel, dim3((nb + 255) / 256, S), dim3(256), 0, st, ov, h->pr, fl, src));
                 LAUNCH(h, "ov_root_lane", hipLaunchKernelGGL(lk_ov_root_lane_kernel, dim3(std::max(1, (nb + 16 * LK_WAVE - 1) / (16 * LK_WAVE)), S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-            }
-            static const bool fit_group_r = getenv("LEGKILO_OV_FIT_GROUP") == nullptr || atoi(getenv("LEGKILO_OV_FIT_GROUP")) != 0;
-            static const bool rag_tail = getenv("LEGKILO_RAG_TAIL") == nullptr || atoi(getenv("LEGKILO_RAG_TAIL")) != 0;   // 0: the four launches (A/B)
-            if (rag_fuse && rag_tail && fit_group_r && biggest <= LK_SCAN_WAVE_MAX) {
-                static const int tail_threads = getenv("LEGKILO_RAG_TAIL_THREADS") ? std::min(LK_MB, std::max(64, atoi(getenv("LEGKILO_RAG_TAIL_THREADS")) & ~63)) : LK_WAVE;   // one wave per slot: 29.2 -> 26.4 ms against four (fewer waves to dispatch)
-                LAUNCH(h, "ov_tail", hipLaunchKernelGGL(lk_ov_tail_kernel, dim3(S), dim3(tail_threads), 0, st, fmap, ov, h->pr, fl, src));
-            } else {
                 LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL((lk_ov_insert_root_kernel<3, true>), dim3(std::max(1, per_slot / 2), S), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
-                LAUNCH(h, "ov_fit_eig", hipLaunchKernelGGL(lk_ov_fit_eig_kernel, dim3(std::max(1, std::min(8, (nb + 63) / 64)), S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-                if (fit_group_r)
-                    LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(std::max(1, std::min(8, (nb + 63) / 64)), S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-                else
-                    LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_lane_kernel, dim3(std::max(1, std::min(8, (nb + 63) / 64)), S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+                LAUNCH(h, "ov_fit_eig", hipLaunchKernelGGL(lk_ov_fit_eig_kernel, dim3(fit_blocks, S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+                LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(fit_blocks, S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
                 LAUNCH(h, "ov_insert_apply", hipLaunchKernelGGL(lk_ov_insert_apply_kernel, dim3(per_slot, S), dim3(LK_MB), 0, st, ov, h->pr, fl, src));
             }
-            static const int ov_fb_wg_r = getenv("LEGKILO_OV_FB_WG") ? std::max(1, atoi(getenv("LEGKILO_OV_FB_WG"))) : 0;
-            LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, ov_fb_wg_r ? ov_fb_wg_r : 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, (int)S));
+            LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, (int)S));
         }
         HIPCHK(h, hipGetLastError());
         h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;

@@ -17,7 +17,7 @@
 //     the private LkMap with the slot as a second grid dimension - 10^6 roots per launch instead of ~1000 - in their batch form
 //     (template flag OV): a thin root's old points are read from the base block and written, with the new ones, to the private
 //     block; the next root's record is requested a root ahead; the plane fit that ends a leaf's bucket is only DECIDED and left as
-//     a 96-B job to lk_ov_fit_lane_kernel, which fits one plane per LANE;
+//     a 96-B job to the fit passes (lk_ov_fit_eig_kernel one lane per fit, lk_ov_fit_group_kernel eight);
 //   * the residual pass of the next bucket finds a key's root through one bit per base grid cell ("this slot has a private root
 //     here", 12.8 KB per slot for the bench map: L2-resident): clear -> the frozen-map grid cell as before (match_flat); set -> the
 //     slot's private table and the pre-order walk of the private tree (match_root, the stream path's matcher).
@@ -98,7 +98,7 @@ struct LkOverlay {
     unsigned int* frozen;        // [2 * bit_words], shared by all slots: TWO bits per grid cell c of the BASE map (lk_ov_frozen_bits_kernel): bit 0 = its voxel is a
                                  // frozen leaf (UpdateOctoTree ignores the point), bit 1 = its voxel takes the point AT THE ROOT (a live leaf, or not initialised
                                  // yet): not ignored, and nothing below the root to look at - the re-projection needs no read of the base tree for it
-    struct LkFitJob* jobs;       // [S][hash_cap][LK_INLINE_GROUPS]: the plane fits the root pass leaves to lk_ov_fit_lane_kernel (current bucket)
+    struct LkFitJob* jobs;       // [S][hash_cap][LK_INLINE_GROUPS]: the plane fits the root pass leaves to lk_ov_fit_group_kernel (current bucket)
     int4* jobhdr;                // [S][LK_INLINE_GROUPS][hash_cap]: their headers {leaf, block, cnt, decided}, dense (what the fit passes scan)
     struct LkLeafSum* sums;      // [S][hash_cap]: moment sums of a leading part of a private ROOT leaf's points (lk_ov_root_lane_kernel)
     struct LkLeafSum* base_sums; // [base max_nodes], shared: the same for the BASE map's root leaves, once per replay (lk_ov_base_sums_kernel)
@@ -194,9 +194,7 @@ __device__ __forceinline__ void ov_root_record_reset(lk_node_rec* nd) {   // a r
     nd->pad_[LK_PAD_BASE] = 0;
     // "no block": what lk_ov_point_geom_kernel (thread per point, no error test of its own) sees in a root the re-projection has claimed but
     // lk_ov_materialise_kernel never filled in because the slot's pools had overflowed - whatever the memory held before would be a block id
-#ifndef LK_X_NO_BLOCK_RESET   // (build switch of the regression check only: tools/gpu_r05_poison.sh shows the fault without this line)
     nd->block = -1;
-#endif
 }
 // once per allocation: every table entry empty, every root record's queue fields clean
 #ifdef LK_TU_OVERLAY   // compiled in the overlay unit only (lk_internal.h)
@@ -298,7 +296,7 @@ __global__ void __launch_bounds__(256) lk_ov_frozen_bits_kernel(LkMap base, unsi
     if (!(st & LK_NODE_INIT_OCTO)) cls = 2u;
     else if ((pf & LK_PLANE_IS_PLANE) != 0 || base.nodes[e.w].layer >= max_layer) cls = (st & LK_NODE_UPDATE_ENABLE) ? 2u : 1u;
     else return;
-    if (cls == 2u && !root_bits) return;   // LEGKILO_OV_ROOT_BITS=0 (A/B): such a voxel through the walk, as before round 6
+    if (cls == 2u && !root_bits) return;   // root_bits = 0: such a voxel through the walk, as before round 6
     const int key[3] = {e.x, e.y, e.z};
     unsigned int cell;
     if (ov_cell_of(base, key, &cell)) atomicOr(&frozen[cell >> 4], cls << (2u * (cell & 15u)));
@@ -643,7 +641,7 @@ __global__ void __launch_bounds__(LK_MB) lk_ov_materialise_kernel(LkMap base, Lk
 // scans - the pass moves 1.7 KB per fit in 16-B pieces, 2 TB/s.)
 // First half of a fit, one lane per job: init_plane's centroid, scatter matrix and eigen-decomposition (voxel_map.cc:46-66) from the event's moment
 // sums.  A "not a plane" event ends here (flag cleared); for a plane the centre, the three eigenvectors and eigenvalues are left in the leaf's
-// private plane record (centre, normal = v_min; v_mid, v_max and the eigenvalues in the first nine plane_var words) for lk_ov_fit_lane_kernel,
+// private plane record (centre, normal = v_min; v_mid, v_max and the eigenvalues in the first nine plane_var words) for lk_ov_fit_group_kernel,
 // which overwrites them with the finished plane.  Two kernels because the closed-form eigen-solver (acos, two cos) and the loop over the leaf's
 // points each fit 128 registers and together do not: the single kernel ran at two waves per SIMD.
 // (thread i_first of i_stride over the slot's jobs: the kernel below, and one phase of lk_ov_tail_kernel)
@@ -694,93 +692,13 @@ __global__ void __launch_bounds__(LK_WAVE, 5) lk_ov_fit_eig_kernel(LkMap base, L
     ov_fit_eig_body(base, ov, pr, blockIdx.y, (int)(blockIdx.x * LK_WAVE + threadIdx.x), (int)(gridDim.x * LK_WAVE));
 }
 #endif
-#ifdef LK_TU_OVERLAY   // compiled in the overlay unit only (lk_internal.h)
-__global__ void __launch_bounds__(LK_WAVE, LK_FIT_WAVES) lk_ov_fit_lane_kernel(LkMap base, LkOverlay ov, LkParams pr) {
-    const unsigned int slot = blockIdx.y;
-    const LkMap pm = ov_slot_map(ov, slot);
-    if (pm.counters[LK_CTR_ERR]) return;
-    const int n_touched = (int)pm.counters[LK_CTR_TOUCHED];
-    const LkFitJob* jobs = ov.jobs + (size_t)slot * ov.hash_cap * LK_INLINE_GROUPS;   // entry [g][t]: inline leaf group g of touched root t
-    for (int i = blockIdx.x * LK_WAVE + threadIdx.x; i < n_touched * LK_INLINE_GROUPS; i += gridDim.x * LK_WAVE) {
-        const int g = i / n_touched, t = i - g * n_touched;
-        const LkFitJob* job = &jobs[(size_t)g * ov.hash_cap + t];
-        const int4 hd = (ov.jobhdr + (size_t)slot * ov.hash_cap * LK_INLINE_GROUPS)[(size_t)g * ov.hash_cap + t];
-        const int root = hd.x /* the leaf's node id */, block = hd.y, cnt = hd.z;
-        if (cnt <= 0) continue;
-        if (hd.w == 0) continue;   // the event said "not a plane": lk_ov_fit_eig_kernel has cleared the flag, there is no plane_var to make
-        // centre, eigenvectors and eigenvalues of the fit: left in the leaf's private plane record by lk_ov_fit_eig_kernel
-        PlaneFit fit;
-        {
-            const lk_plane_rec* pl = &pm.planes[root];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) fit.c[k] = pl->center[k], fit.vmin[k] = pl->normal[k], fit.vmid[k] = pl->plane_var[k], fit.vmax[k] = pl->plane_var[3 + k];
-            fit.emin = pl->plane_var[6], fit.emid = pl->plane_var[7], fit.emax = pl->plane_var[8];
-        }
-        fit.is_plane = true;
-        double acc21[21];
-#pragma unroll
-        for (int q = 0; q < 21; ++q) acc21[q] = 0.0;
-        if (fit.is_plane) {
-            // plane_var = sum_i J_i var_i J_i^T (voxel_map.cc:76-95) with J_i = [A_i ; I / n], A_i = v_mid FA_i^T + v_max FB_i^T (rank 2; the row of
-            // v_min is zero), FA_i = ((q.v_mid) v_min + (q.v_min) v_mid) / den_A, FB_i likewise with v_max, q = p_i - centre.  With a = var FA, b = var FB:
-            //   A var A^T = v_mid v_mid^T (FA.a) + (v_mid v_max^T + v_max v_mid^T) (FA.b) + v_max v_max^T (FB.b),   A var = v_mid a^T + v_max b^T
-            // so the 21 sums of 3 x 3 products per point become 15 running sums of a few dot products - the same value (a different, equally
-            // valid rounding), a quarter of the arithmetic and half the registers: four waves per SIMD instead of two
-            const double invA = 1.0 / (cnt * (fit.emin - fit.emid)), invB = 1.0 / (cnt * (fit.emin - fit.emax));
-            const double invn = 1.0 / cnt;
-            const lk_pt_rec* __restrict__ bp = pm.blocks[block].pts;
-            // a split leaf (lk_ov_root_lane_kernel): its first n_base points are still the base map's
-            const int n_base = job->n_base;
-            const lk_pt_rec* __restrict__ bb = n_base > 0 ? base.blocks[job->base_block].pts : bp;
-            double sa[3] = {0.0, 0.0, 0.0}, sb[3] = {0.0, 0.0, 0.0}, saa = 0.0, sab = 0.0, sbb = 0.0, sV[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll 1
-            for (int j = 0; j < cnt; ++j) {
-                double pw[3], var[6];
-                const lk_pt_rec* __restrict__ pj = (j < n_base ? bb : bp) + j;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) pw[c] = pj->pw[c];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) var[c] = pj->var[c];
-                const double q0 = pw[0] - fit.c[0], q1 = pw[1] - fit.c[1], q2 = pw[2] - fit.c[2];
-                const double dmin = q0 * fit.vmin[0] + q1 * fit.vmin[1] + q2 * fit.vmin[2];
-                const double dmid = (q0 * fit.vmid[0] + q1 * fit.vmid[1] + q2 * fit.vmid[2]) * invA;
-                const double dmax = (q0 * fit.vmax[0] + q1 * fit.vmax[1] + q2 * fit.vmax[2]) * invB;
-                const double dmA = dmin * invA, dmB = dmin * invB;
-                double FA[3], FB[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) FA[c] = dmid * fit.vmin[c] + dmA * fit.vmid[c], FB[c] = dmax * fit.vmin[c] + dmB * fit.vmax[c];
-                const double a0 = var[0] * FA[0] + var[1] * FA[1] + var[2] * FA[2], a1 = var[1] * FA[0] + var[3] * FA[1] + var[4] * FA[2],
-                             a2 = var[2] * FA[0] + var[4] * FA[1] + var[5] * FA[2];
-                const double b0 = var[0] * FB[0] + var[1] * FB[1] + var[2] * FB[2], b1 = var[1] * FB[0] + var[3] * FB[1] + var[4] * FB[2],
-                             b2 = var[2] * FB[0] + var[4] * FB[1] + var[5] * FB[2];
-                saa += FA[0] * a0 + FA[1] * a1 + FA[2] * a2;
-                sab += FA[0] * b0 + FA[1] * b1 + FA[2] * b2;
-                sbb += FB[0] * b0 + FB[1] * b1 + FB[2] * b2;
-                sa[0] += a0, sa[1] += a1, sa[2] += a2, sb[0] += b0, sb[1] += b1, sb[2] += b2;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) sV[c] += var[c];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // the 21 unique entries, upper triangle row by row: rows 0..2 = [A var A^T | A var / n], rows 3..5 = [. | sum var / n^2]
-            int kk = 0;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                for (int cc = r; cc < 3; ++cc)
-                    acc21[kk++] = fit.vmid[r] * fit.vmid[cc] * saa + (fit.vmid[r] * fit.vmax[cc] + fit.vmax[r] * fit.vmid[cc]) * sab + fit.vmax[r] * fit.vmax[cc] * sbb;
-#pragma unroll
-                for (int cc = 0; cc < 3; ++cc) acc21[kk++] = (fit.vmid[r] * sa[cc] + fit.vmax[r] * sb[cc]) * invn;
-            }
-            const double invn2 = invn * invn;
-            acc21[15] = sV[0] * invn2, acc21[16] = sV[1] * invn2, acc21[17] = sV[2] * invn2, acc21[18] = sV[3] * invn2, acc21[19] = sV[4] * invn2, acc21[20] = sV[5] * invn2;
-        }
-        plane_commit<true>(&pm.planes[root], &pm.match[root], fit, acc21, cnt);
-    }
-}
-#endif
 
-// Round 6: the same fit by a GROUP of eight lanes.  One lane per fit walks the leaf's <= 50 points one after the other - 34 of the 129 us of GPU
+// Second half of a fit: plane_var and the commit.  plane_var = sum_i J_i var_i J_i^T (voxel_map.cc:76-95) with J_i = [A_i ; I / n], A_i = v_mid FA_i^T +
+// v_max FB_i^T (rank 2; the row of v_min is zero), FA_i = ((q.v_mid) v_min + (q.v_min) v_mid) / den_A, FB_i likewise with v_max, q = p_i - centre.
+// With a = var FA, b = var FB:  A var A^T = v_mid v_mid^T (FA.a) + (v_mid v_max^T + v_max v_mid^T) (FA.b) + v_max v_max^T (FB.b),  A var = v_mid a^T + v_max b^T
+// - so the 21 sums of 3 x 3 products per point become 15 running sums of a few dot products: the same value (a different, equally valid rounding),
+// a quarter of the arithmetic and half the registers.
+// Round 6: a GROUP of eight lanes per fit.  One lane per fit (round 5) walked the leaf's <= 50 points one after the other - 34 of the 129 us of GPU
 // time a bucket index of the recorded-run batch costs (1 024 slots x one or two fits: a latency chain), and in the uniform batch the lanes of a wave
 // each read their own 72-B records (2.6 of 17.9 ms).  Here a wave first finds the real jobs among its 64 job slots (most are empty: a slot per touched
 // root and inline group), then takes them eight at a time: lane `sub` of a group handles points sub, sub + 8, ... - eight consecutive 72-B records per
@@ -916,7 +834,7 @@ __global__ void __launch_bounds__(LK_WAVE, LK_FIT_WAVES) lk_ov_fit_group_kernel(
 //   * the simulation of voxel_map.cc:186-204 is side-effect free, so a root that turns out to need the generic code (a cut:
 //     init_octo_tree says "not a plane"; a plane that stops being one; more than a slot line of points; a tree below the root) is
 //     handed over as it was found.
-// The fit that ends a leaf's bucket is left to lk_ov_fit_eig_kernel / lk_ov_fit_lane_kernel (96-B job).
+// The fit that ends a leaf's bucket is left to lk_ov_fit_eig_kernel / lk_ov_fit_group_kernel (96-B job).
 // (First version of the round, measured and replaced: the same fast path one WAVE per root - 128 VGPRs, four waves per SIMD, real
 // one-root-ahead requests - 5.6 ms per batch against the generic pass's 10.8: bound by VALU issue, ~600 wave instructions per root for
 // the ~8 lanes a root's points occupy.  profiles/EXPERIMENTS.md.)

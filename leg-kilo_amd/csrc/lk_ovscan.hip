@@ -13,18 +13,11 @@ extern "C++" {
 // lk_ov_tail_kernel (generic root pass, plane fits, apply).  What the launch cannot hold is the fallback code (256 registers + 6.4 KB of scratch per lane,
 // lk_ov_insert_fallback_kernel): a scan whose bucket leaves fallback items stops behind that bucket (cur[slot] = the next one, fb_b[slot] = this one), the host
 // runs the fallback launch for the stopped scans and launches again - LkResume's protocol of the stream path.  Same device functions in the same order per
-// scan: bit-identical to the launch-by-launch form (test_batch_replay_overlay_ragged; LEGKILO_RAG_RESIDENT=0 is the A/B).
+// scan: bit-identical to the launch-by-launch form (test_batch_replay_overlay_ragged; LEGKILO_RAG_RESIDENT=0 is its reference).
 // Between two phases of the scan kernel: workgroup-scope fence + barrier, as in the fused kernels above.  (Its workgroup IS one wave, so a wavefront-scope fence
-// + wave barrier - the compiler keeps the order, nothing is waited for - would do: -DLK_SCAN_SYNC_WG=0, measured 10.86 against 10.85 ms per batch, green.  The
+// + wave barrier - the compiler keeps the order, nothing is waited for - would do: measured 10.86 against 10.85 ms per batch, green.  The
 // waits are not what a bucket costs; the stronger form stays.)
-#ifndef LK_SCAN_SYNC_WG
-#define LK_SCAN_SYNC_WG 1
-#endif
-#if LK_SCAN_SYNC_WG
 #define LK_SCAN_PHASE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __syncthreads(); } while (0)
-#else
-#define LK_SCAN_PHASE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-#endif
 #ifndef LK_SCAN_WAVES
 #define LK_SCAN_WAVES 1   // waves per SIMD the register allocation aims at
 #endif

@@ -16,47 +16,7 @@
 #include "lk_device.h"
 
 #define LK_PB 256
-#ifndef LK_PTS_NT
-#define LK_PTS_NT 1    // the 16-B scan point with a non-temporal load (round 6: 1.560 -> 1.537 ms per step, same bits; A/B: -DLK_PTS_NT=0)
-#endif
-#ifndef LK_ROWS_NT
-#define LK_ROWS_NT 1   // config 2's materialised rows leave with non-temporal stores (A/B: -DLK_ROWS_NT=0)
-#endif
-#if LK_ROWS_NT
-#define LK_ROWS_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define LK_ROWS_STORE(v, p) (*(p) = (v))
-#endif
-#ifndef LK_ROWS_AT_TAKE
-#define LK_ROWS_AT_TAKE 1   // a matched lane writes its final LDS row [h z | h/R | R 1] when it takes its plane: no LDS read-back before K3
-                            // (0 = park the raw row and finish it after the matching; A/B: 1.798 -> 1.775 ms per step, same bits)
-#endif
-#ifndef LK_MFMA_RED
-#define LK_MFMA_RED 0   // 1: the per-tile normal-equation sums on v_mfma_f64_4x4x4 (A/B build; see residual_tile)
-#endif
-// perf-attribution switches (tools/ab_env.sh builds with -DLK_X_...=1): each removes one piece of the residual pass so that its
-// marginal cost can be measured; results are wrong with any of them set, the product build sets none
-#ifndef LK_X_NORETRY
-#define LK_X_NORETRY 0
-#endif
-#ifndef LK_X_NOCHILD
-#define LK_X_NOCHILD 0
-#endif
-#ifndef LK_X_NOEVAL
-#define LK_X_NOEVAL 0
-#endif
-#ifndef LK_X_NORED
-#define LK_X_NORED 0
-#endif
-#ifndef LK_X_NOPRED
-#define LK_X_NOPRED 0
-#endif
-#ifndef LK_X_NOUPD
-#define LK_X_NOUPD 0
-#endif
-#ifndef LK_X_NORES
-#define LK_X_NORES 0
-#endif
+#define LK_ROWS_STORE(v, p) __builtin_nontemporal_store((v), (p))   // config 2's materialised rows leave with non-temporal stores
 // The residual kernel runs ONE wave per workgroup: with no block barrier in it there is nothing to share, and the
 // scheduler can refill a SIMD slot the moment a wave retires instead of waiting for a 4-wave workgroup's worth of
 // slots and LDS (measured on the 1024-scan batch: 642 us per bucket at 256 threads, 582 at 128, 578 at 64).
@@ -126,17 +86,14 @@ __device__ __forceinline__ void eval_plane(const lk_match_rec* __restrict__ mr, 
         r[0] = t.w.x, r[1] = t.w.y, r[2] = t.w.z;
         r[3] = n.x, r[4] = n.y, r[5] = n.z;
         r[6] = -(double)(float)sd;  // z = -dis_to_plane_, the signed distance stored as float (voxel_map.h:92, .cc:401-402)
-#if LK_ROWS_AT_TAKE
-        // the row in its final form [h z | h/R | R 1] right here: nothing is read back from LDS before the reduction
+        // the row in its final form [h z | h/R | R 1] right here: nothing is read back from LDS before the reduction (against parking
+        // the raw row and finishing it after the matching: 1.798 -> 1.775 ms per step, same bits)
         const double Rv = pr.lidar_ratio * sig_r;   // KILO.cc:205-206
         const double ri = lk_inv_nodecision(Rv);   // scales the row for the sums A = sum h h^T / R, b = sum h z / R: no gate reads it
         r[7] = t.w.x * ri, r[8] = t.w.y * ri, r[9] = t.w.z * ri;
         r[10] = n.x * ri, r[11] = n.y * ri, r[12] = n.z * ri;
         r[13] = Rv;
         r[14] = 1.0;
-#else
-        r[13] = sig_r;              // J_nq plane_var J_nq^T + n^T (R ext_R) body_cov (R ext_R)^T n (KILO.cc:205-206, before lidar_ratio)
-#endif
     }
 }
 
@@ -160,28 +117,22 @@ __device__ __forceinline__ bool match_root(const LkMap& m, int root, const bool 
             const double2* q = reinterpret_cast<const double2*>(pl);
             double2 q0 = q[0], q1 = q[1], q2 = q[2];
             float4 tail = *reinterpret_cast<const float4*>(&pl->d);  // d, radius, flags, pad (grid cells: node id)
-#if LK_PIN_RECORD
             RecTail rt;   // the whole record in one round trip (see pin_chunk)
             rt.v0 = q[4], rt.v1 = q[5], rt.v2 = q[6], rt.v3 = q[7], rt.v4 = q[8];
             pin_chunk(q0), pin_chunk(q1), pin_chunk(q2), pin_chunk(tail);
             pin_chunk(rt.v0), pin_chunk(rt.v1), pin_chunk(rt.v2), pin_chunk(rt.v3), pin_chunk(rt.v4);
-#endif
             if (grid_cell && level == 0) {
                 const unsigned int id = __float_as_uint(tail.w);
                 if (id == LK_GRID_EMPTY) return false;  // no root voxel at this key
                 n0 = node = (int)id;
             }
-            if (!LK_X_NOEVAL && (__float_as_uint(tail.z) & LK_PLANE_IS_PLANE)) {
-#if LK_PIN_RECORD
+            if (__float_as_uint(tail.z) & LK_PLANE_IS_PLANE) {
                 eval_plane<XID, true>(pl, q0, q1, q2, tail.x, tail.y, node, level, g, bc, pr, success, prob, best, &rt);
-#else
-                eval_plane<XID>(pl, q0, q1, q2, tail.x, tail.y, node, level, g, bc, pr, success, prob, best);
-#endif
                 --level;
                 fresh = false;
                 continue;
             }
-            if (LK_X_NOCHILD || level >= max_layer || level >= LK_MAX_LAYER) {
+            if (level >= max_layer || level >= LK_MAX_LAYER) {
                 --level;
                 fresh = false;
                 continue;
@@ -190,9 +141,7 @@ __device__ __forceinline__ bool match_root(const LkMap& m, int root, const bool 
         }
         const int4* ch = reinterpret_cast<const int4*>(m.nodes[node].child);
         int4 ca = ch[0], cb = ch[1];
-#if LK_PIN_RECORD
         pin_chunk(ca), pin_chunk(cb);
-#endif
         unsigned int ci = (cis >> (4 * level)) & 15u;
         int child = -1;
         while (ci < 8u && child < 0) {
@@ -229,28 +178,21 @@ __device__ __forceinline__ bool match_flat(const LkMap& m, int cell, const Point
         const double2* q = reinterpret_cast<const double2*>(pl);
         double2 q0 = q[0], q1 = q[1], q2 = q[2];
         float4 tail = *reinterpret_cast<const float4*>(&pl->d);  // d, radius, flags, node id
-#if LK_PIN_RECORD
         RecTail rt;
         rt.v0 = q[4], rt.v1 = q[5], rt.v2 = q[6], rt.v3 = q[7], rt.v4 = q[8];
         pin_chunk(q0), pin_chunk(q1), pin_chunk(q2), pin_chunk(tail);
         pin_chunk(rt.v0), pin_chunk(rt.v1), pin_chunk(rt.v2), pin_chunk(rt.v3), pin_chunk(rt.v4);
-#endif
         const unsigned int fl = __float_as_uint(tail.z);
         if (header) {
             header = false;
             if (__float_as_uint(tail.w) == LK_GRID_EMPTY) return false;  // no root voxel at this key
             if (!(fl & LK_PLANE_IS_PLANE)) {
-                if (LK_X_NOCHILD) return true;
                 idx = (int)(unsigned int)__double_as_longlong(q0.x);            // {first, count} in the header's first 8 bytes
                 remaining = (int)(unsigned int)(__double_as_longlong(q0.x) >> 32);
                 continue;
             }
         }
-#if LK_PIN_RECORD
-        if (!LK_X_NOEVAL) eval_plane<XID, true>(pl, q0, q1, q2, tail.x, tail.y, 0, 0, g, bc, pr, success, prob, best, &rt);
-#else
-        if (!LK_X_NOEVAL) eval_plane<XID>(pl, q0, q1, q2, tail.x, tail.y, 0, 0, g, bc, pr, success, prob, best);
-#endif
+        eval_plane<XID, true>(pl, q0, q1, q2, tail.x, tail.y, 0, 0, g, bc, pr, success, prob, best, &rt);
         ++idx;
         --remaining;
     }
@@ -384,12 +326,8 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
         PointLite g;
         int root = -1, nroot = -1;
         if (i < n) {
-#if LK_PTS_NT
             typedef float lk_f4v __attribute__((ext_vector_type(4)));
-            const lk_f4v p = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(spts) + i);   // read once: keep it from displacing plane records in L2
-#else
-            const float4 p = spts[i];
-#endif
+            const lk_f4v p = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(spts) + i);   // read once: keep it from displacing plane records in L2 (round 6: 1.560 -> 1.537 ms per step, same bits)
             g = point_lite<XID>(p.x, p.y, p.z, bc, pr);
             if (out.world) {
                 float4 w = make_float4((float)g.p_w.x, (float)g.p_w.y, (float)g.p_w.z, 0.f);
@@ -417,7 +355,7 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
         if (root >= 0) home = grid_cell ? match_flat<XID>(map, root, g, bc, pr, success, prob, best) : match_root<XID>(map, root, false, g, bc, pr, success, prob, best);
         else if (GRID == 3 && root <= -2) home = match_root<XID>(pmv, -2 - root, false, g, bc, pr, success, prob, best);
         // the one-neighbour retry (KILO.cc:156-178): only when the home voxel EXISTS (the lookup at KILO.cc:149 found a tree)
-        if (home && !success && !LK_X_NORETRY) {
+        if (home && !success) {
             float loc[3];     // re-derived here rather than kept alive across the home voxel's walk
             int key[3], near[3];
             key_trunc(g.p_w, pr, loc, key);
@@ -438,42 +376,18 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
             }
         }
         ok = success;
-#if LK_ROWS_AT_TAKE
         // (EMIT_ROWS: the rows go to HBM from the wave's LDS region behind the wave barrier below - whole 16-B pieces, consecutive lanes)
-#else
-        if (ok) {  // KILO.cc:195-209: h (1x6), z, R for the matched point, from the parked row
-            const double* r = best.row;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) h[a] = r[a];
-            z = r[6];
-            R = pr.lidar_ratio * r[13];  // (R ext_R) body_cov (R ext_R)^T only, no state covariance (KILO.cc:205-206)
-        }
-#endif
     }
     // K3, per wave and without any block barrier.  Every lane stores its row [h(6) z | h(6)/R | R valid] (zeros when
     // it did not match) in the wave's LDS region; lane (q = lane & 31, half = lane >> 5) then accumulates component q
     // of [A(21) b(6) sumR count] over the 32 rows of its half, in row order, branch-free and with ONE fma per row
     // (ds_read_b64 broadcasts, all loads independent of the arithmetic); the two halves are combined with one
     // cross-lane read.
-#if LK_ROWS_AT_TAKE
     if (!ok) {   // matched lanes wrote their final row when they took their plane
         double* r = rows + lane * LK_ROW2;
 #pragma unroll
         for (int a = 0; a < LK_ROW2; ++a) r[a] = 0.0;
     }
-#else
-    {
-        double* r = rows + lane * LK_ROW2;
-        const double ri = ok ? 1.0 / R : 0.0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) r[a] = h[a];   // h, z are zero for unmatched lanes
-        r[6] = z;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) r[7 + a] = h[a] * ri;
-        r[13] = ok ? R : 0.0;
-        r[14] = ok ? 1.0 : 0.0;
-    }
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -520,36 +434,6 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
         if (lane < nv) LK_ROWS_STORE((unsigned char)(rows[lane * LK_ROW2 + 14] != 0.0 ? 1 : 0), out.valid + o0 + lane);
         return 0.0;   // config 2 ends here ("residuals only"): no caller of a row-emitting launch reads the tile's sums A, b (K3)
     }
-    if (LK_X_NORED) return (lane == 28) ? (ok ? 1.0 : 0.0) : 0.0;
-#if LK_MFMA_RED
-    // K3 on the matrix cores: G = X^T Y over the tile's 64 rows with X = [h/R (6), R, valid] (row doubles 7..14) and
-    // Y = [h (6), z, valid] (row doubles 0..6, 14): G(i,j), i <= j < 6, is A; G(i,6) is b; G(6,7) = sum R; G(7,7) = count.
-    // v_mfma_f64_4x4x4_4b: four independent 4 x 4 blocks, K = 4 per instruction -> the four blocks are the 2 x 2 tiling of the
-    // 8 x 8 result and 16 instructions walk the 64 rows.  Operand layout measured on gfx950 (tools/probes/mfma_f64_4x4x4_layout.hip):
-    // lane = 16 k + 4 b + m supplies A[b][m][k] and B[b][k][m]; D[b][i][j] lands in lane 16 i + 4 b + j.
-    {
-        const int k = lane >> 4, b = (lane >> 2) & 3, m = lane & 3;
-        const int ca = 7 + 4 * (b >> 1) + m;
-        const int cb0 = 4 * (b & 1) + m, cb = cb0 < 7 ? cb0 : 14;
-        const double* pa = rows + k * LK_ROW2 + ca;
-        const double* pb = rows + k * LK_ROW2 + cb;
-        double d0 = 0.0, d1 = 0.0;   // two accumulators: consecutive MFMAs do not wait for each other
-#pragma unroll
-        for (int t = 0; t < 16; t += 2) {
-            d0 = __builtin_amdgcn_mfma_f64_4x4x4f64(pa[(4 * t) * LK_ROW2], pb[(4 * t) * LK_ROW2], d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f64_4x4x4f64(pa[(4 * t + 4) * LK_ROW2], pb[(4 * t + 4) * LK_ROW2], d1, 0, 0, 0);
-        }
-        const double g = d0 + d1;
-        // lane q (both halves) wants component q of [A(21) b(6) sumR count]
-        const int q = lane & 31;
-        // (gi, gj) of component q, packed gi | gj << 4, eight per 64-bit word: the upper triangle of A row by row, then (i, 6), (6, 7), (7, 7)
-        const unsigned long long tw = (q < 8) ? 0x2111504030201000ull : (q < 16) ? 0x3352423222514131ull : (q < 24) ? 0x6261605554445343ull : 0x0000007776656463ull;
-        const unsigned int ij = (unsigned int)(tw >> ((q & 7) * 8)) & 0xffu;
-        const int gi = (int)(ij & 15u), gj = (int)(ij >> 4);
-        const int src = 16 * (gi & 3) + 4 * (2 * (gi >> 2) + (gj >> 2)) + (gj & 3);
-        return __shfl(g, src, LK_WAVE);
-    }
-#endif
     const int q = lane & 31, half = lane >> 5;
     // component q = sum over rows of r[a] * r[b]:  A(i,j) = sum (h_i / R) h_j (upper triangle, row-major: q < 21,
     // a = 7 + i, b = j), b_i = sum (h_i / R) z (q = 21 + i: a = 7 + i, b = 6), sum R (q = 27: 13, 14), count (14, 14).
@@ -608,129 +492,6 @@ __global__ void LK_RES_BOUNDS
         const size_t wave_id = (size_t)bx * (LK_RB / LK_WAVE) + wv;
         partials[(size_t)slot * part_slot_stride + wave_id * LK_NPART + lane] = (lane < 29) ? acc : 0.0;
     }
-}
-
-// ---------------------------------------------------------------- round 5 experiment: TWO tiles per wave (-> profiles/EXPERIMENTS.md)
-// The batch kernel waits 46 % of a wave's life: one trip for the point, one for the candidate's record.  Here a wave takes two 64-point
-// tiles and requests BOTH tiles' points, then both tiles' cell records (18 pinned 16-B pieces per lane), before it evaluates either: the
-// second tile's trips overlap the first tile's arithmetic.  The price is the second record and point in registers.  Frozen-map grid only
-// (match_flat), no row emission; arithmetic and order of sums per tile exactly those of residual_tile (the same bits per partial record).
-struct TilePre {
-    PointLite g;
-    int root;
-    double2 q0, q1, q2;
-    float4 tail;
-    RecTail rt;
-};
-template <bool XID>
-__device__ __forceinline__ void tile_request(const LkMap& map, const LkParams& pr, const BucketConst& bc, const float4& p, bool in_range, TilePre& t) {
-    t.root = -1;
-    if (in_range) {
-        t.g = point_lite<XID>(p.x, p.y, p.z, bc, pr);
-        float loc[3];
-        int key[3];
-        key_trunc(t.g.p_w, pr, loc, key);
-        t.root = find_root<1>(map, key[0], key[1], key[2]);
-    }
-    const lk_match_rec* pl = &map.match[t.root >= 0 ? t.root : (int)map.grid_base];   // (clamped: every lane requests, nothing is merged in)
-    const double2* q = reinterpret_cast<const double2*>(pl);
-    t.q0 = q[0], t.q1 = q[1], t.q2 = q[2];
-    t.tail = *reinterpret_cast<const float4*>(&pl->d);
-    t.rt.v0 = q[4], t.rt.v1 = q[5], t.rt.v2 = q[6], t.rt.v3 = q[7], t.rt.v4 = q[8];
-}
-// match_flat with the cell's own record already requested (t): the first iteration uses it, list records are loaded as before
-template <bool XID>
-__device__ __forceinline__ bool match_flat_pre(const LkMap& m, TilePre& t, const BucketConst& bc, const LkParams& pr, bool& success, double& prob, Match& best) {
-    pin_chunk(t.q0), pin_chunk(t.q1), pin_chunk(t.q2), pin_chunk(t.tail);
-    pin_chunk(t.rt.v0), pin_chunk(t.rt.v1), pin_chunk(t.rt.v2), pin_chunk(t.rt.v3), pin_chunk(t.rt.v4);
-    const unsigned int fl0 = __float_as_uint(t.tail.z);
-    if (__float_as_uint(t.tail.w) == LK_GRID_EMPTY) return false;
-    if (fl0 & LK_PLANE_IS_PLANE) {
-        eval_plane<XID, true>(&m.match[t.root], t.q0, t.q1, t.q2, t.tail.x, t.tail.y, 0, 0, t.g, bc, pr, success, prob, best, &t.rt);
-        return true;
-    }
-    int idx = (int)(unsigned int)__double_as_longlong(t.q0.x), remaining = (int)(unsigned int)(__double_as_longlong(t.q0.x) >> 32);
-    while (remaining > 0) {
-        const lk_match_rec* pl = &m.match[idx];
-        const double2* q = reinterpret_cast<const double2*>(pl);
-        double2 q0 = q[0], q1 = q[1], q2 = q[2];
-        float4 tail = *reinterpret_cast<const float4*>(&pl->d);
-        RecTail rt;
-        rt.v0 = q[4], rt.v1 = q[5], rt.v2 = q[6], rt.v3 = q[7], rt.v4 = q[8];
-        pin_chunk(q0), pin_chunk(q1), pin_chunk(q2), pin_chunk(tail);
-        pin_chunk(rt.v0), pin_chunk(rt.v1), pin_chunk(rt.v2), pin_chunk(rt.v3), pin_chunk(rt.v4);
-        eval_plane<XID, true>(pl, q0, q1, q2, tail.x, tail.y, 0, 0, t.g, bc, pr, success, prob, best, &rt);
-        ++idx;
-        --remaining;
-    }
-    return true;
-}
-// the rest of a tile: K2 (home voxel from the requested record, one neighbour retry), row, K3
-template <bool XID>
-__device__ __forceinline__ double tile_finish(const LkMap& map, const LkParams& pr, const BucketConst& bc, TilePre& t, double* rows, int lane) {
-    bool success = false;
-    double prob = 0;
-    Match best;
-    best.row = rows + lane * LK_ROW2;
-    bool home = false;
-    if (t.root >= 0) home = match_flat_pre<XID>(map, t, bc, pr, success, prob, best);
-    if (home && !success) {
-        float loc[3];
-        int key[3], near[3];
-        key_trunc(t.g.p_w, pr, loc, key);
-        neighbour_key(pr, loc, key, near);
-        int nroot = -1;
-        if (near[0] != key[0] || near[1] != key[1] || near[2] != key[2]) nroot = find_root<1>(map, near[0], near[1], near[2]);
-        if (nroot >= 0) match_flat<XID>(map, nroot, t.g, bc, pr, success, prob, best);
-    }
-    const bool ok = success;
-    if (!ok) {
-        double* r = rows + lane * LK_ROW2;
-#pragma unroll
-        for (int a = 0; a < LK_ROW2; ++a) r[a] = 0.0;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int q = lane & 31, half = lane >> 5;
-    const unsigned long long tw = (q < 8) ? 0x2818574737271707ull : (q < 16) ? 0x3a59493929584838ull : (q < 24) ? 0x6968675c5b4b5a4aull : 0xeeeeeeeeed6c6b6aull;
-    const unsigned int ab = (unsigned int)(tw >> ((q & 7) * 8)) & 0xffu;
-    const int a = (int)(ab & 15u), b = (int)(ab >> 4);
-    const double* base = rows + (half * 32) * LK_ROW2;
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const double* r = base + j * LK_ROW2;
-        acc = __builtin_fma(r[a], r[b], acc);
-    }
-    acc += __shfl_xor(acc, 32, LK_WAVE);
-    return acc;
-}
-#ifndef LK_PAIR_WAVES
-#define LK_PAIR_WAVES 3
-#endif
-template <bool XID>
-__global__ void __launch_bounds__(LK_RB, LK_PAIR_WAVES)
-    lk_residual_pair_kernel(LkMap map, LkParams pr, const LkFilter* __restrict__ filters, const lk_point* __restrict__ pts, size_t pts_slot_stride, int n,
-                            double* __restrict__ partials, size_t part_slot_stride, ResidualOut out, size_t out_slot_stride) {
-    static_assert(LK_RB == LK_WAVE, "one wave per workgroup");
-    __shared__ double stage[64 * LK_ROW2];
-    if (blockIdx.x & 1u) return;   // the launch keeps lk_residual_kernel's grid: even workgroups take tiles b and b + 1
-    const int slot = blockIdx.y, lane = threadIdx.x;
-    BucketConst bc;
-    load_bucket_const<false>(&filters[slot], pr, bc);
-    const float4* spts = reinterpret_cast<const float4*>(pts + (size_t)slot * pts_slot_stride);
-    const int i0 = blockIdx.x * LK_RB + lane, i1 = i0 + LK_RB;
-    const float4 p0 = spts[min(i0, n - 1)], p1 = spts[min(i1, n - 1)];   // both points first, clamped: no lane test in front of a load
-    TilePre t0, t1;
-    tile_request<XID>(map, pr, bc, p0, i0 < n, t0);
-    tile_request<XID>(map, pr, bc, p1, i1 < n, t1);
-    const double acc0 = tile_finish<XID>(map, pr, bc, t0, stage, lane);
-    if (lane < LK_NPART) partials[(size_t)slot * part_slot_stride + (size_t)blockIdx.x * LK_NPART + lane] = (lane < 29) ? acc0 : 0.0;
-    if ((int)((blockIdx.x + 1) * LK_RB) >= n) return;
-    __builtin_amdgcn_wave_barrier();   // tile 0's reads of the rows are complete
-    const double acc1 = tile_finish<XID>(map, pr, bc, t1, stage, lane);
-    if (lane < LK_NPART) partials[(size_t)slot * part_slot_stride + (size_t)(blockIdx.x + 1) * LK_NPART + lane] = (lane < 29) ? acc1 : 0.0;
 }
 
 // ---------------------------------------------------------------- pipelined stream path: verify pass
@@ -915,7 +676,6 @@ __device__ __forceinline__ void dev_reproject_point_bc(const LkMap& map, const L
         bool ignore = false;
         for (int depth = 0; depth <= LK_MAX_LAYER; ++depth) {
             const lk_node_rec* nr = &map.nodes[node];
-#if LK_PIN_RECORD
             // the node's record (children, centre, layer, state: bytes 0..79) and its plane flags in ONE round trip
             int4 n0 = reinterpret_cast<const int4*>(nr)[0], n1 = reinterpret_cast<const int4*>(nr)[1], n2 = reinterpret_cast<const int4*>(nr)[2],
                  n3 = reinterpret_cast<const int4*>(nr)[3], n4 = reinterpret_cast<const int4*>(nr)[4];
@@ -935,22 +695,6 @@ __device__ __forceinline__ void dev_reproject_point_bc(const LkMap& map, const L
             const int child = oct == 0 ? n0.x : oct == 1 ? n0.y : oct == 2 ? n0.z : oct == 3 ? n0.w : oct == 4 ? n1.x : oct == 5 ? n1.y : oct == 6 ? n1.z : n1.w;
             if (child < 0) break;
             node = child;
-#else
-            const unsigned int st = nr->state;
-            const unsigned int pf = map.planes[node].flags;
-            if (!(st & LK_NODE_INIT_OCTO)) break;
-            const bool is_plane = (pf & LK_PLANE_IS_PLANE) != 0;
-            const int layer = nr->layer;
-            if (is_plane || layer >= pr.max_layer) {
-                ignore = !(st & LK_NODE_UPDATE_ENABLE);
-                break;
-            }
-            const int oct = ((g.p_w.x > nr->voxel_center[0]) ? 4 : 0) + ((g.p_w.y > nr->voxel_center[1]) ? 2 : 0) +
-                            ((g.p_w.z > nr->voxel_center[2]) ? 1 : 0);
-            const int child = nr->child[oct];
-            if (child < 0) break;
-            node = child;
-#endif
         }
         if (ignore) return;
     }

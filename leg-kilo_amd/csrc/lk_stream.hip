@@ -253,12 +253,6 @@ struct LkResume {
     int fb_bucket;     // the bucket whose fallback items are pending (its snapshot: snap2[fb_bucket & 1]); -1: none
     int pad_[3];
 };
-#ifndef LK_X_DYNROOT
-#define LK_X_DYNROOT 1   // A/B builds: 0 = the grid-resident kernel's root pass strides the touched list
-#endif
-#ifndef LK_X_SLEEP
-#define LK_X_SLEEP 0   // sensitivity probes (never in the product build): ~1 us of sleep per bucket on 1 the filter wave, 2 the insert team before / 4 behind its stamps
-#endif
 #ifdef LK_DEBUG_RES
 __device__ unsigned long long lk_res_dbg[32];   // DEBUG BUILD ONLY: 100 MHz ticks per phase of the resident kernel's two roles; [0..7] filter wave, [8..15] insert wave 1, [31] buckets
 __device__ unsigned long long lk_res_ts[6][1024];   // per bucket: 0 filter posted, 1 insert saw the post, 2 insert posted decided, 3 filter began to wait for decided, 4 filter saw decided, 5 insert done
@@ -272,24 +266,10 @@ __device__ unsigned long long lk_res_ts[6][1024];   // per bucket: 0 filter post
 #define RS_STAMP(k) do { } while (0)
 #define RS_FLUSH(o) do { } while (0)
 #endif
-// The message updates of the scan-resident stream kernel as CALLS (-DLK_MSG_CALL=1; A/B): a kinematic + IMU message is an 18-column Gauss-Jordan in registers,
-// run a few dozen times per scan; inlined, its register demand is the whole kernel's (256 + 240 B of scratch for MSG == 2 against 96 B without messages) and the
-// per-bucket code pays the spills.
-#ifndef LK_MSG_CALL
-#define LK_MSG_CALL 0
-#endif
-// -DLK_PT_PREFETCH=1 (A/B, measured: no gain): the filter wave asks for the next bucket's scan points as soon as the current bucket's tiles are done
-#ifndef LK_PT_PREFETCH
-#define LK_PT_PREFETCH 0
-#endif
-#if LK_MSG_CALL
-__device__ __attribute__((noinline)) void stream_kin_update_call(WaveSmem& sm, double* scratch, const double* msg, double acc_scale, const double* Rn6, double kin_noise, int lane) {
-    wave_kin_update_core<true>(sm, scratch, msg, acc_scale, Rn6, kin_noise, lane);
-}
-__device__ __attribute__((noinline)) void stream_imu_update_call(WaveSmem& sm, const double* acc, const double* gyr, double acc_scale, const double* Rn6, int lane) {
-    wave_imu_update_core<true>(sm, acc, gyr, acc_scale, Rn6, lane);
-}
-#endif
+// The message updates of the scan-resident stream kernel are inlined.  A kinematic + IMU message is an 18-column Gauss-Jordan in registers, run a few
+// dozen times per scan, so its register demand is the whole kernel's (256 + 240 B of scratch for MSG == 2 against 96 B without messages) and the
+// per-bucket code pays the spills - yet behind noinline calls config 4 measured slower: 10.03-10.14 -> 10.53-10.56 ms per scan.  Requesting the next
+// bucket's scan points early measured no gain either (config-1 live 4.03 -> 4.06 ms): consecutive buckets share cache lines.
 template <int MSG, bool XID>
 __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
     lk_scan_stream_kernel(LkMap map, LkParams pr, LkFilter* filters, const lk_point* __restrict__ pts, LkRagged rg, const double* __restrict__ Q,
@@ -334,10 +314,6 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
             if (!FLAG_WAIT(f_post, inject_stall && b >= 3 ? nbk + 1 : b)) break;   // (injected stall: a post that never comes)
             if (rank == 0) RS_TS(1, b);
             RS_STAMP(0);
-#if LK_X_SLEEP & 2
-            if (rank == 0) __builtin_amdgcn_s_sleep(38);   // sensitivity probe: ~1 us on the insert team's chain, before its stamps are final
-            if (!TEAM_BARRIER(team_ctr, phase)) break;
-#endif
             RS_STAMP(1);
             for (int i = rank * LK_WAVE + lane; i < n; i += LK_INS_WAVES * LK_WAVE) dev_reproject_point(m, pr, sn, pts + base, world ? world + 4 * base : nullptr, 1, i);
             if (!TEAM_BARRIER(team_ctr, phase)) break;
@@ -352,7 +328,7 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
             if (n_touched > 0) {
                 if (!TEAM_BARRIER(team_ctr, phase)) break;   // the stamping pass has read the roots' queues before the root pass resets them
                 RS_STAMP(3);
-                dev_insert_root<false>(m, pr, sn, pts + base, (const lk_pt_rec*)nullptr, n, rank, LK_INS_WAVES, nullptr, nullptr, 0, LK_X_DYNROOT ? &root_ticket : nullptr);
+                dev_insert_root<false>(m, pr, sn, pts + base, (const lk_pt_rec*)nullptr, n, rank, LK_INS_WAVES, nullptr, nullptr, 0, &root_ticket);
                 if (!TEAM_BARRIER(team_ctr, phase)) break;
                 RS_STAMP(4);
                 dev_insert_apply<false>(m, pr, sn, pts + base, (const lk_pt_rec*)nullptr, n, rank, LK_INS_WAVES);
@@ -371,9 +347,6 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
                     break;
                 }
             }
-#if LK_X_SLEEP & 4
-            if (rank == 0) __builtin_amdgcn_s_sleep(38);   // sensitivity probe: ~1 us on the insert team's chain, behind its stamps
-#endif
             if (!TEAM_BARRIER(team_ctr, phase)) break;
             if (rank == 0) FLAG_POST(f_done, b);
             if (rank == 0) RS_TS(5, b);
@@ -398,17 +371,10 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
     constexpr size_t mstride = MSG == 2 ? 33 : 7;
     RS_DECL;
     bool predicted = stage1_0 != 0;   // picked up behind a predict (LkResume::stage1)
-#if LK_PT_PREFETCH
-    const unsigned long long pts_end = po[nbk];   // one past the scan's last point
-    float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
     bool stopped = false;             // left the loop in a wait for the insert team
     int b = bf0;
     while (b < nbk) {
         const double tb_ = T[b];
-#if LK_X_SLEEP & 1
-        __builtin_amdgcn_s_sleep(38);   // sensitivity probe: ~1 us on the filter wave's chain
-#endif
         const bool is_msg = !predicted && MSG && qi < qn && rg.imu[mstride * (size_t)qi] < tb_;
         const double t = is_msg ? rg.imu[mstride * (size_t)qi] : tb_;
         if (!predicted) wave_predict_core<true>(sm, Q, t - t_upd, t - t_pred, lane, rg.q_diag != 0);   // KILO.cc:111-115 / :240-244
@@ -417,17 +383,10 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
         RS_STAMP(0);
         if (is_msg) {   // predictUpdateImu, KILO.cc:235-258 / predictUpdateKinImu, KILO.cc:260-314
             const double* mm = rg.imu + mstride * (size_t)qi;
-#if LK_MSG_CALL
-            if (MSG == 2)
-                stream_kin_update_call(sm, rows, mm, rg.acc_scale, rg.Rn, rg.kin_noise, lane);
-            else
-                stream_imu_update_call(sm, mm + 1, mm + 4, rg.acc_scale, rg.Rn, lane);
-#else
             if (MSG == 2)
                 wave_kin_update_core<true>(sm, rows, mm, rg.acc_scale, rg.Rn, rg.kin_noise, lane);
             else
                 wave_imu_update_core<true>(sm, mm + 1, mm + 4, rg.acc_scale, rg.Rn, lane);
-#endif
             t_upd = t;  // KILO.cc:256 / :312
             ++qi;
             RS_STAMP(6);
@@ -463,14 +422,6 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
         }
         double totv = (lane < 29) ? (((0.0 + a0) + a1) + a2) + a3 : 0.0;  // tot[j] in lanes 0..31
         RS_STAMP(1);
-#if LK_PT_PREFETCH
-        // the NEXT bucket's points, requested now: their trip runs beside this bucket's wait, update and predict instead of at the head of the next tile (the
-        // value is only kept until the update is done - the tile's own load then finds the lines in the CU's L1)
-        {
-            const unsigned long long q = base + (unsigned long long)n + (unsigned long long)lane;
-            if (q < pts_end) pf = reinterpret_cast<const float4*>(pts)[q];
-        }
-#endif
         if (b > 0) {
             RS_TS(3, b - 1);
             if (!FLAG_WAIT_X(f_decided, b - 1)) { stopped = true; break; }   // the stamps of insert b - 1 are final (and insert b - 2 is complete)
@@ -509,9 +460,6 @@ __global__ void __launch_bounds__((1 + LK_INS_WAVES) * LK_WAVE)
             wave_update_core<true>(sm, totv, N, lane);
         }
         core_sync<true>();
-#if LK_PT_PREFETCH
-        asm volatile("" ::"v"(pf.x), "v"(pf.y), "v"(pf.z), "v"(pf.w));   // the request has to exist; nothing reads the value
-#endif
         RS_STAMP(4);
         // the posterior for the insert (dev_snapshot_posterior's fields): the buffer of bucket b - 2 is free once that insert is done
         if (b >= 2 && !FLAG_WAIT(f_done, b - 2)) break;   // (never behind a team that has left: its f_decided(b - 1) came after f_done(b - 2))
@@ -758,7 +706,7 @@ __global__ void __launch_bounds__(LK_FB)   // (compiled for two waves per SIMD -
         const int n_touched = (int)__hip_atomic_load(&map.counters[LK_CTR_TOUCHED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (n_touched > 0) {
             dev_insert_root<false>(map, pr, snap, bp, (const lk_pt_rec*)nullptr, n, wg * (LK_FB / LK_WAVE) + wv, G * (LK_FB / LK_WAVE), nullptr, nullptr, 0,
-                                   LK_X_DYNROOT ? &map.counters[LK_CTR_HEAVY] : nullptr);   // (LK_CTR_HEAVY: zeroed by dev_bucket_begin, otherwise unused on this path)
+                                   &map.counters[LK_CTR_HEAVY]);   // (LK_CTR_HEAVY: zeroed by dev_bucket_begin, otherwise unused on this path)
             GS_STAMP(6);
             if (!grid_barrier()) return;
             GS_STAMP(7);
@@ -921,11 +869,6 @@ extern "C++" __global__ void __launch_bounds__(LK_WAVE)
 // predict -> residual (+A,b partials) -> 6x6 update -> re-project + hash -> per-root insert
 // t_next: time of the NEXT bucket if the caller knows that it follows directly (no IMU / kinematic message in between) and is itself
 // a large bucket - its predict then runs in this bucket's launch (`*pre_predicted` tells the next call) -, NaN otherwise.
-// dynamic-LDS padding knobs of the stream launches (placement experiments): clamped to what a workgroup may ask for on top of its static LDS
-static int lds_knob(const char* name) {
-    const char* e = getenv(name);
-    return e ? std::min(std::max(atoi(e), 0), 48 * 1024) : 0;
-}
 static int enqueue_bucket(lk_handle* h, const lk_point* d_pts, int n, double t, float* d_world, bool do_insert, double t_next = NAN,
                           bool* pre_predicted = nullptr) {
     const LkMap& m = h->map;
@@ -937,29 +880,25 @@ static int enqueue_bucket(lk_handle* h, const lk_point* d_pts, int n, double t, 
     const LkFilter* ins_filters = h->d_filters;   // what the insert reads the posterior from (large buckets: its snapshot)
     bool predict_in_root = false;                 // large buckets: the next bucket's predict rides in the root pass's launch
     if (do_insert && h->spec_enable && !h->profiling && n > LK_SMALL_MAX && !was_pre) {
-        static const bool xid_en = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
-        return enqueue_bucket_spec(h, d_pts, n, t, d_world, h->pr.ext_identity && xid_en);
+        return enqueue_bucket_spec(h, d_pts, n, t, d_world, h->pr.ext_identity && lk_xid_enabled());
     }
     if (h->spec_open) {   // a bucket on the sequential path follows the inserts in flight
         int rcj = spec_join(h);
         if (rcj) return rcj;
     }
     // the stream path's residual code specialised for ext_R == I like the batch kernel (LEGKILO_XID=0: generic)
-    static const bool xid_enable = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
-    const bool xid = h->pr.ext_identity && xid_enable;
-    // tiny buckets (a real scan's 2 ms bins: a dozen points): fewer dependent launches - re-projection inside the bucket kernel, light +
-    // group pass as one launch (LEGKILO_FUSE_MAX: largest such bucket, 0 = off)
-    static const int fuse_max = getenv("LEGKILO_FUSE_MAX") ? atoi(getenv("LEGKILO_FUSE_MAX")) : 64;
-    const bool fuse = n <= fuse_max && n <= LK_SMALL_MAX;
-    static const bool tiny_enable = getenv("LEGKILO_TINY") == nullptr || atoi(getenv("LEGKILO_TINY")) != 0;
-    if (fuse && tiny_enable && n <= LK_WAVE) {
+    const bool xid = h->pr.ext_identity && lk_xid_enabled();
+    // tiny buckets (a real scan's 2 ms bins: a dozen points, at most one wave): fewer dependent launches - re-projection inside the
+    // bucket kernel, light + group pass as one launch
+    const bool fuse = n <= LK_WAVE;
+    if (fuse) {
         const auto tiny_kernel = xid ? lk_tiny_bucket_kernel<true> : lk_tiny_bucket_kernel<false>;
         LAUNCH(h, "small_bucket", hipLaunchKernelGGL(tiny_kernel, dim3(1), dim3(LK_WAVE), 0, h->stream, m, h->pr, h->d_filters, h->d_Q,
                                                      h->q_diag ? 1 : 0, t, d_pts, n, d_world, (d_world || do_insert) ? (do_insert ? 2 : 1) : 0));
     } else if (n <= LK_SMALL_MAX) {
         const auto small_kernel = xid ? lk_small_bucket_kernel<true> : lk_small_bucket_kernel<false>;
         LAUNCH(h, "small_bucket", hipLaunchKernelGGL(small_kernel, dim3(1), dim3(LK_FB), 0, h->stream, m, h->pr, h->d_filters,
-                                                     h->d_Q, t, d_pts, n, d_world, fuse && (d_world || do_insert) ? (do_insert ? 2 : 1) : 0));
+                                                     h->d_Q, t, d_pts, n, d_world, 0));
     } else {
         // residual pass, then ONE single-workgroup launch for everything else on the filter side: the fixed-order sum of the tiles'
         // partial records + the update, the posterior's snapshot for the insert, the insert's pool bookkeeping and - t_next known -
@@ -970,43 +909,35 @@ static int enqueue_bucket(lk_handle* h, const lk_point* d_pts, int n, double t, 
         memset(&ro, 0, sizeof(ro));
         ro.world = d_world;
         const bool fuse_next = pre_predicted != nullptr && t_next == t_next;
-        static const bool predict_in_root_on = getenv("LEGKILO_PREDICT_IN_ROOT") == nullptr || atoi(getenv("LEGKILO_PREDICT_IN_ROOT")) != 0;
-        predict_in_root = fuse_next && do_insert && predict_in_root_on;   // n > LK_SMALL_MAX here: the insert below is the three-launch form
+        predict_in_root = fuse_next && do_insert;   // n > LK_SMALL_MAX here: the insert below is the three-launch form
         const auto res_kernel = xid ? lk_residual_kernel<false, 0, true> : lk_residual_kernel<false, 0, false>;
-        static const int lds_res = lds_knob("LEGKILO_LDS_RES");
-        LAUNCH(h, "residual", hipLaunchKernelGGL(res_kernel, dim3(nblk_r, 1), dim3(LK_RB), lds_res, h->stream, m, h->pr, h->d_filters, d_pts, (size_t)0, n,
+        LAUNCH(h, "residual", hipLaunchKernelGGL(res_kernel, dim3(nblk_r, 1), dim3(LK_RB), 0, h->stream, m, h->pr, h->d_filters, d_pts, (size_t)0, n,
                                                  h->d_partials, h->part_stride, ro, (size_t)0));
         LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_snap_kernel, dim3(2), dim3(LK_FB), 0, h->stream, m, h->d_filters, h->d_partials,
                                                nblk_r * (LK_RB / LK_WAVE), t, h->d_Q, fuse_next ? t_next : 0.0, fuse_next && !predict_in_root ? 1 : 0, h->d_snap));
         if (fuse_next) *pre_predicted = true;
         ins_filters = h->d_snap;
     }
-    static const int lds_rp = lds_knob("LEGKILO_LDS_REPROJ");
-    static const int lds_root = lds_knob("LEGKILO_LDS_ROOT");
-    static const int lds_apply = lds_knob("LEGKILO_LDS_APPLY");
-    static const int lds_rootp = lds_knob("LEGKILO_LDS_ROOTP");
     if ((d_world || do_insert) && !fuse)
-        LAUNCH(h, "reproject", hipLaunchKernelGGL(lk_reproject_wave_kernel, dim3((n + LK_WAVE - 1) / LK_WAVE), dim3(LK_WAVE), lds_rp, h->stream, m, h->pr,
+        LAUNCH(h, "reproject", hipLaunchKernelGGL(lk_reproject_wave_kernel, dim3((n + LK_WAVE - 1) / LK_WAVE), dim3(LK_WAVE), 0, h->stream, m, h->pr,
                                                   ins_filters, d_pts, n, d_world, do_insert ? 1 : 0));
     if (do_insert) {
         // one wave per touched root (append / group / apply of single-group roots), then one wave per emitted leaf group (2 resident
         // waves per SIMD at ~200 VGPRs: 512 blocks x 4 waves is one resident round on 256 CUs), then the generic fallback for the few
         // groups that need it; all loops are grid-stride and read their work counts on the device
-        static const int root_grid_cap = getenv("LEGKILO_ROOT_GRID") ? std::max(1, atoi(getenv("LEGKILO_ROOT_GRID"))) : 512;
-        int grid = std::min(std::max((n + 3) / 4, 1), root_grid_cap);
-        static const bool small_insert = getenv("LEGKILO_SMALL_INSERT") == nullptr || atoi(getenv("LEGKILO_SMALL_INSERT")) != 0;
-        if (n <= LK_SMALL_MAX && small_insert) {   // small bucket: root pass + (in the last workgroup) apply + fallback as one launch
+        const int grid = std::min(std::max((n + 3) / 4, 1), 512);
+        if (n <= LK_SMALL_MAX) {   // small bucket: root pass + (in the last workgroup) apply + fallback as one launch
             LAUNCH(h, "insert_root", hipLaunchKernelGGL(lk_insert_small_kernel, dim3(std::min(grid, 128)), dim3(LK_MB), 0, h->stream, h->map, h->pr,
                                                         ins_filters, d_pts, n));
             return LK_OK;
         }
         if (predict_in_root)
-            LAUNCH(h, "insert_root", hipLaunchKernelGGL(lk_insert_root_predict_kernel, dim3(grid + 1), dim3(LK_MB), lds_rootp, h->stream, h->map, h->pr,
+            LAUNCH(h, "insert_root", hipLaunchKernelGGL(lk_insert_root_predict_kernel, dim3(grid + 1), dim3(LK_MB), 0, h->stream, h->map, h->pr,
                                                         ins_filters, d_pts, n, h->d_filters, h->d_Q, t_next, h->q_diag ? 1 : 0));
         else
-            LAUNCH(h, "insert_root", hipLaunchKernelGGL(lk_insert_root_kernel<false>, dim3(grid), dim3(LK_MB), lds_root, h->stream, h->map, h->pr,
+            LAUNCH(h, "insert_root", hipLaunchKernelGGL(lk_insert_root_kernel<false>, dim3(grid), dim3(LK_MB), 0, h->stream, h->map, h->pr,
                                                         ins_filters, d_pts, (const lk_pt_rec*)nullptr, n));
-        LAUNCH(h, "insert", hipLaunchKernelGGL(lk_insert_apply_kernel<false>, dim3(grid), dim3(LK_MB), lds_apply, h->stream, h->map, h->pr,
+        LAUNCH(h, "insert", hipLaunchKernelGGL(lk_insert_apply_kernel<false>, dim3(grid), dim3(LK_MB), 0, h->stream, h->map, h->pr,
                                                ins_filters, d_pts, (const lk_pt_rec*)nullptr, n));
         LAUNCH(h, "insert_fallback", hipLaunchKernelGGL(lk_insert_fallback_kernel<false>, dim3(std::min(grid, 8)), dim3(LK_MB), 0, h->stream,
                                                         h->map, h->pr, ins_filters, d_pts, (const lk_pt_rec*)nullptr, n));
@@ -1050,27 +981,23 @@ static int finish_scan(lk_handle* h, lk_pose* pose, const void* d_resume = nullp
     hipLaunchKernelGGL(lk_scan_finish_kernel, dim3(1), dim3(64), 0, h->stream, h->d_filters, h->map.counters, h->d_result, seq, static_cast<const int*>(d_resume));
     HIPCHK(h, hipGetLastError());
     // a scan is a fraction of a millisecond to a few: the caller's thread POLLS the sequence word the kernel writes last (a blocking
-    // synchronisation wakes through an interrupt, 10-20 us later) - for at most 20 ms, then it blocks (which also surfaces device errors).
-    // LEGKILO_SPIN_WAIT=0: always block
-    static const bool spin = getenv("LEGKILO_SPIN_WAIT") == nullptr || atoi(getenv("LEGKILO_SPIN_WAIT")) != 0;
+    // synchronisation wakes through an interrupt, 10-20 us later) - for at most 20 ms, then it blocks (which also surfaces device errors)
     bool seen = false;
-    if (spin) {
-        volatile unsigned int* sq = &h->h_result->seq;
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-        for (unsigned int it = 0;; ++it) {
-            if (*sq == seq) {
-                seen = true;
-                break;
-            }
-            if ((it & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) break;
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#else
-            std::this_thread::yield();
-#endif
+    volatile unsigned int* sq = &h->h_result->seq;
+    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
+    for (unsigned int it = 0;; ++it) {
+        if (*sq == seq) {
+            seen = true;
+            break;
         }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        if ((it & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) break;
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#else
+        std::this_thread::yield();
+#endif
     }
+    std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
     *pose = h->h_result->pose;
     return check_map_errors(h, h->h_result->ctr);
@@ -1165,6 +1092,11 @@ static int rag_reserve(lk_handle* h, size_t bytes) {
     return LK_OK;
 }
 
+// bound of the resident kernels' device-side waits (LEGKILO_RESIDENT_TIMEOUT_MS, debug aid: raise it under a profiler); read once per process
+static unsigned int resident_timeout_ms() {
+    static const unsigned int v = getenv("LEGKILO_RESIDENT_TIMEOUT_MS") ? (unsigned int)std::max(1, atoi(getenv("LEGKILO_RESIDENT_TIMEOUT_MS"))) : LK_RESIDENT_TIMEOUT_MS;
+    return v;
+}
 // filters[0] before a scan that works on it in place (grid-resident kernel, pipelined launches): check_map_errors restores it on LK_ERR_TIMEOUT
 static int backup_filter(lk_handle* h) {
     if (!h->d_fbackup) HIPCHK(h, hipMalloc(&h->d_fbackup, sizeof(LkFilter)));
@@ -1214,8 +1146,7 @@ static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vec
     rg.acc_scale = h->cfg.gravity / h->acc_norm;
     imu_noise(h->cfg, rg.Rn);
     h->grid_valid = false;   // the map changes
-    static const bool xid_en = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
-    const bool xid = h->pr.ext_identity && xid_en;
+    const bool xid = h->pr.ext_identity && lk_xid_enabled();
     if (h->epoch + (unsigned int)nb + 16u < h->epoch || h->epoch >= 0xf0000000u) {   // stamps are plain unsigned numbers: start over long before they wrap
         HIPCHK(h, hipMemsetAsync(h->map.dirty, 0, sizeof(unsigned int) * (size_t)h->map.max_nodes, h->stream));
         HIPCHK(h, hipMemsetAsync(h->map.newroot, 0, sizeof(unsigned int) * (size_t)(LK_NEWROOT_MASK + 1), h->stream));
@@ -1224,7 +1155,7 @@ static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vec
     const unsigned int epoch0 = h->epoch + 1u;
     h->epoch += (unsigned int)nb;
     h->spec_base = h->epoch + 1u;
-    static const unsigned int timeout_ms = getenv("LEGKILO_RESIDENT_TIMEOUT_MS") ? (unsigned int)std::max(1, atoi(getenv("LEGKILO_RESIDENT_TIMEOUT_MS"))) : LK_RESIDENT_TIMEOUT_MS;
+    const unsigned int timeout_ms = resident_timeout_ms();
     void (*k)(LkMap, LkParams, LkFilter*, const lk_point*, LkRagged, const double*, LkFilter*, float*, int2*, unsigned int, unsigned int, LkResume*) =
         msg_kind == 2 ? (xid ? lk_scan_stream_kernel<2, true> : lk_scan_stream_kernel<2, false>)
       : msg_kind == 1 ? (xid ? lk_scan_stream_kernel<1, true> : lk_scan_stream_kernel<1, false>)
@@ -1331,12 +1262,10 @@ static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<
     rg.imu_off = reinterpret_cast<const unsigned int*>(dr + o_io);
     rg.q_diag = h->q_diag ? 1 : 0;
     h->grid_valid = false;   // the map changes
-    static const bool xid_en = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
-    const bool xid = h->pr.ext_identity && xid_en;
-    static const unsigned int timeout_ms = getenv("LEGKILO_RESIDENT_TIMEOUT_MS") ? (unsigned int)std::max(1, atoi(getenv("LEGKILO_RESIDENT_TIMEOUT_MS"))) : LK_RESIDENT_TIMEOUT_MS;
-    static const int wg_env = getenv("LEGKILO_GRIDSCAN_WG") ? atoi(getenv("LEGKILO_GRIDSCAN_WG")) : 0;
+    const bool xid = h->pr.ext_identity && lk_xid_enabled();
+    const unsigned int timeout_ms = resident_timeout_ms();
     const int tiles = (int)((biggest + LK_WAVE - 1) / LK_WAVE);
-    int G = wg_env > 0 ? wg_env : std::max(16, (tiles + 3) / 4 + 12);  // a wave per tile of the largest bucket and some more for the per-root passes; every
+    int G = std::max(16, (tiles + 3) / 4 + 12);  // a wave per tile of the largest bucket and some more for the per-root passes; every
                                                                       // further workgroup makes each barrier dearer (51 x 1 960 points, round 5: 8 workgroups 2.67 ms, 12: 2.37, 16: 2.30, 24: 2.29, 32: 2.31; round 4: 128: 2.81)
     G = std::min(G, LK_GRIDSCAN_WG_MAX);                             // 128 workgroups of 4 waves are resident on 256 CUs whatever else is true
     {   // a partitioned / smaller device (CPX: 32 CUs): never more spinning workgroups than can be resident at once
@@ -1353,9 +1282,8 @@ static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<
         }
         G = std::max(1, std::min(G, resident_max));
     }
-    // up to one workgroup per CU of an XCD: launch 8 G blocks and let only every eighth work (LEGKILO_GRIDSCAN_XCD=0: all G blocks, any XCD)
-    static const bool one_xcd_en = getenv("LEGKILO_GRIDSCAN_XCD") == nullptr || atoi(getenv("LEGKILO_GRIDSCAN_XCD")) != 0;
-    const int stride = (one_xcd_en && G <= 32) ? 8 : 1;
+    // up to one workgroup per CU of an XCD: launch 8 G blocks and let only every eighth work
+    const int stride = G <= 32 ? 8 : 1;
     const auto k = xid ? lk_scan_grid_kernel<true> : lk_scan_grid_kernel<false>;
     LkResume* d_rs = reinterpret_cast<LkResume*>(dr + o_rs);
     h->grid_scans += 1;

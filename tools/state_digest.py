@@ -1,5 +1,5 @@
 """Digest of the filter state and the map after a short stream - to compare library builds / environment switches bit for bit:
-    LEGKILO_PREDICT_IN_ROOT=0 python tools/state_digest.py --kind 51   vs   LEGKILO_PREDICT_IN_ROOT=1 ...
+    LEGKILO_HIP_LIB=$PWD/a.so python tools/state_digest.py --kind 51   vs   LEGKILO_HIP_LIB=$PWD/b.so ...
 The map is compared through its canonical form (tests/scenes.py: pool order depends on racing allocations, the trees do not)."""
 import argparse
 import hashlib

@@ -442,6 +442,56 @@ int lk_batch_replay_ragged_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n
 int lk_batch_replay_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
                               int msg_kind, const uint32_t* n_msg, const void* msgs, lk_pose* out);
 
+/* ---- leg kinematics front end: unitree_legged_msgs/HighState -> lk_kin_imu on the device ----
+ * What the reference runs for every /high_state message before the filter sees it: the redundancy filter of
+ * RosInterface::kinematicImuCallBack (ros_interface.cc:221-248), Kinematics::processing (kinematics.cc:5-90: leg order
+ * FL FR RL RR -> FR FL RR RL, forward kinematics + Jacobian foot velocity in fp64, the hysteresis ContactDetector of
+ * kinematics.h per leg), and the kin branch of syncPackage (ros_interface.cc:303-328) that hands the records to the scans.
+ * A message is its ROS1 serialisation (fixed size, no length prefixes), LK_HIGHSTATE_BYTES apart. */
+#define LK_HIGHSTATE_BYTES 1095
+
+/* Kinematics::Config (kinematics.h) + the yaml key `redundancy`.  Key names are the yaml's. */
+typedef struct lk_kin_config {
+    double leg_offset_x;
+    double leg_offset_y;
+    double leg_calf_length;
+    double leg_thigh_length;
+    double leg_thigh_offset;
+    double contact_force_threshold_up;    /* T_on: a foot off the ground touches down at force > T_on */
+    double contact_force_threshold_down;  /* T_off: a foot on the ground lifts off at force < T_off (may exceed T_on: diter.yaml) */
+    int32_t redundancy;                   /* != 0: drop a message whose imu acc z AND gyr z equal the previous message's */
+    int32_t pad_;
+} lk_kin_config;
+
+/* What the front end carries from one message to the next: checkpoint it with lk_kin_get_frontend, resume with lk_kin_set_frontend. */
+typedef struct lk_kin_frontend_state {
+    int32_t contact[4];      /* ContactDetector::in_contact_ per project leg FR FL RR RL (0 / 1) */
+    float last_acc_z;        /* the previous message's imu.accelerometer[2] / gyroscope[2], kept or not (the callback's static) */
+    float last_gyr_z;
+    double last_stamp;       /* stamp of the last kept message (-inf: none yet) */
+} lk_kin_frontend_state;
+
+/* Sets the geometry, thresholds and redundancy flag AND resets the carried state: contacts all 1, last acc z / gyr z 0, last stamp -inf. */
+int lk_kin_configure(lk_handle* h, const lk_kin_config* cfg);
+int lk_kin_get_frontend(lk_handle* h, lk_kin_frontend_state* st);
+int lk_kin_set_frontend(lk_handle* h, const lk_kin_frontend_state* st);
+/* n messages (n x LK_HIGHSTATE_BYTES, any alignment) -> the *n_out <= n records of the kept ones, in order.  The carried state advances
+ * by exactly these messages, so a stream decoded in chunks gives what one call gives.  LK_ERR_STATE before lk_kin_configure;
+ * LK_ERR_INVALID when a kept stamp is older than the kept one before it (in the call or carried): the carried state is then unchanged
+ * and the output undefined.  _dev: device input, device output (n records of room), synchronous; the host variant copies both ways. */
+int lk_decode_highstate(lk_handle* h, const void* msgs, size_t n, lk_kin_imu* out, size_t* n_out);
+int lk_decode_highstate_dev(lk_handle* h, const void* d_msgs, size_t n, lk_kin_imu* d_out, size_t* n_out);
+/* The kin branch of syncPackage over time-sorted records (lk_decode_highstate_dev's output) and scans with non-decreasing end times
+ * scan_end[n_scans] (host): scan s takes the pending records stamped before scan_end[s], and one more stamped exactly scan_end[s] if it
+ * took any.  A scan is packaged when the newest record is >= its end time and a record is pending; packaging stops at the first scan that
+ * is not.  Outputs (host): n_msg[s] records of packaged scan s (0 for the others), *n_packaged, *n_consumed = sum of n_msg: the records
+ * d_kins[0, n_consumed) are those of the packaged scans, concatenated - ready for lk_batch_replay_scans_kin_dev.  Stateless. */
+int lk_kin_split_dev(lk_handle* h, const lk_kin_imu* d_kins, size_t n_kins, const double* scan_end, size_t n_scans, uint32_t* n_msg,
+                     size_t* n_packaged, size_t* n_consumed);
+/* lk_batch_replay_scans_dev with msg_kind 2 and the records already in HBM (d_kins: the n_msg[s] records of each scan, concatenated). */
+int lk_batch_replay_scans_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
+                                  const uint32_t* n_msg, const lk_kin_imu* d_kins, lk_pose* out);
+
 /* ---- measurement hooks ---- */
 int lk_profile_enable(lk_handle* h, int on);                           /* HIP-event timing around each kernel */
 int lk_profile_get(lk_handle* h, const char* kernel, uint64_t* launches, double* total_ms);

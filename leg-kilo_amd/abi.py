@@ -70,6 +70,32 @@ class lk_kin_imu(C.Structure):
     ]
 
 
+LK_HIGHSTATE_BYTES = 1095   # ROS1 serialisation of unitree_legged_msgs/HighState (fixed size)
+
+
+class lk_kin_config(C.Structure):
+    _fields_ = [
+        ("leg_offset_x", C.c_double),
+        ("leg_offset_y", C.c_double),
+        ("leg_calf_length", C.c_double),
+        ("leg_thigh_length", C.c_double),
+        ("leg_thigh_offset", C.c_double),
+        ("contact_force_threshold_up", C.c_double),
+        ("contact_force_threshold_down", C.c_double),
+        ("redundancy", C.c_int32),
+        ("pad_", C.c_int32),
+    ]
+
+
+class lk_kin_frontend_state(C.Structure):
+    _fields_ = [
+        ("contact", C.c_int32 * 4),
+        ("last_acc_z", C.c_float),
+        ("last_gyr_z", C.c_float),
+        ("last_stamp", C.c_double),
+    ]
+
+
 class lk_pose(C.Structure):
     _fields_ = [
         ("rot", C.c_double * 9),

@@ -22,6 +22,8 @@ EXPORTS = [
     "lk_update_points", "lk_update_imu", "lk_update_kin_imu", "lk_process_scan", "lk_process_scan_dev",
     "lk_decode_scan", "lk_decode_scan_dev", "lk_preprocess_scan", "lk_preprocess_scan_dev", "lk_process_raw_scan", "lk_batch_set_priors", "lk_batch_set_priors_dev", "lk_batch_get_states", "lk_batch_get_states_dev", "lk_batch_residuals_dev", "lk_batch_order", "lk_batch_changed", "lk_batch_prepare_dev", "lk_batch_order_stats", "lk_batch_replay_dev", "lk_batch_sort_by_voxel_dev", "lk_batch_replay_async_dev", "lk_batch_replay_ragged_dev", "lk_batch_replay_ragged_imu_dev", "lk_batch_replay_ragged_kin_dev", "lk_batch_replay_scans_dev", "lk_batch_replay_overlay_dev", "lk_batch_replay_overlay_ragged_dev", "lk_overlay_reserve", "lk_overlay_export", "lk_overlay_stats", "lk_overlay_pool_bytes", "lk_overlay_resident_rounds", "lk_profile_enable", "lk_profile_get", "lk_profile_reset",
     "lk_device_malloc", "lk_device_free", "lk_memcpy_h2d", "lk_memcpy_d2h", "lk_synchronize", "lk_stream", "lk_stream_pipeline", "lk_stream_resident", "lk_stream_grid", "lk_stream_grid_placement", "lk_stream_stats", "lk_stream_resident_stats", "lk_test_stall",
+    "lk_kin_configure", "lk_kin_get_frontend", "lk_kin_set_frontend", "lk_decode_highstate", "lk_decode_highstate_dev", "lk_kin_split_dev",
+    "lk_batch_replay_scans_kin_dev",
 ]
 
 
@@ -553,6 +555,66 @@ class LegKiloHip:
             return self.batch_replay_ragged_dev(d, self.ragged_tables(scan_off, [t[0] for t in tabs], [t[1] for t in tabs], t_begins, imus, kins))
         finally:
             self.device_free(d)
+
+    # ---- leg kinematics front end (HighState -> lk_kin_imu, the kin branch of syncPackage) ----
+    def kin_configure(self, params=None):
+        """Kinematics::Config + `redundancy` from a yaml-keyed parameter dict (config.kin_config); resets the carried state."""
+        from . import config
+
+        self._chk(self.L.lk_kin_configure(self.h, C.byref(config.kin_config(params))))
+
+    def kin_get_frontend(self):
+        """The carried state as a dict(contact int32[4], last_acc_z, last_gyr_z, last_stamp)."""
+        st = abi.lk_kin_frontend_state()
+        self._chk(self.L.lk_kin_get_frontend(self.h, C.byref(st)))
+        return dict(contact=np.array(st.contact, dtype=np.int32), last_acc_z=np.float32(st.last_acc_z), last_gyr_z=np.float32(st.last_gyr_z),
+                    last_stamp=st.last_stamp)
+
+    def kin_set_frontend(self, fe):
+        st = abi.lk_kin_frontend_state()
+        st.contact = (C.c_int32 * 4)(*[int(v) for v in fe["contact"]])
+        st.last_acc_z, st.last_gyr_z, st.last_stamp = float(fe["last_acc_z"]), float(fe["last_gyr_z"]), float(fe["last_stamp"])
+        self._chk(self.L.lk_kin_set_frontend(self.h, C.byref(st)))
+
+    def decode_highstate(self, msgs):
+        """Serialized HighState messages (bytes / uint8 array, n x LK_HIGHSTATE_BYTES) -> KIN_DTYPE records of the kept ones."""
+        from . import synth
+
+        data = np.ascontiguousarray(np.frombuffer(bytes(msgs) if not isinstance(msgs, np.ndarray) else msgs.tobytes(), dtype=np.uint8))
+        assert data.size % abi.LK_HIGHSTATE_BYTES == 0
+        n = data.size // abi.LK_HIGHSTATE_BYTES
+        out = np.zeros(max(n, 1), dtype=synth.KIN_DTYPE)
+        n_out = C.c_size_t(0)
+        self._chk(self.L.lk_decode_highstate(self.h, _p(data), C.c_size_t(n), _p(out), C.byref(n_out)))
+        return out[: n_out.value]
+
+    def decode_highstate_dev(self, d_msgs, n, d_out):
+        """n messages in HBM -> records at the device pointer d_out (room for n); returns the number kept."""
+        n_out = C.c_size_t(0)
+        self._chk(self.L.lk_decode_highstate_dev(self.h, C.c_void_p(d_msgs), C.c_size_t(n), C.c_void_p(d_out), C.byref(n_out)))
+        return n_out.value
+
+    def kin_split_dev(self, d_kins, n_kins, scan_end):
+        """syncPackage's kin branch over n_kins time-sorted records in HBM and the scans' end times -> (n_msg uint32[n_scans], n_packaged,
+        n_consumed)."""
+        ends = _f64(scan_end)
+        n_msg = np.zeros(max(len(ends), 1), dtype=np.uint32)
+        npk, ncs = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.L.lk_kin_split_dev(self.h, C.c_void_p(d_kins), C.c_size_t(n_kins), _p(ends), C.c_size_t(len(ends)), _p(n_msg), C.byref(npk),
+                                          C.byref(ncs)))
+        return n_msg[: len(ends)], npk.value, ncs.value
+
+    def batch_replay_scans_kin_dev(self, d_pts, scan_off, t_begins, n_msg, d_kins, want_poses=True):
+        """lk_batch_replay_scans_dev in leg-fusion mode with the records already in HBM (d_kins: n_msg[s] records per scan, concatenated)."""
+        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
+        n_scans = len(so) - 1
+        tb = _f64(t_begins)
+        nm = np.ascontiguousarray(n_msg, dtype=np.uint32)
+        assert len(tb) == n_scans and len(nm) == n_scans
+        poses = (abi.lk_pose * n_scans)() if want_poses else None
+        self._chk(self.L.lk_batch_replay_scans_kin_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(so), _p(tb), _p(nm),
+                                                       C.c_void_p(d_kins) if d_kins else None, poses))
+        return poses
 
     # ---- measurement / memory hooks ----
     def profile_enable(self, on):

@@ -31,15 +31,33 @@ DITER = dict(
 )
 
 
+# keys the leg kinematics front end reads besides those above (ros_interface.cc:73: `redundancy`, default false when absent; every shipped
+# yaml file sets it true).  Kept apart from LEG_FUSION, whose keys are also written into the reference's own yaml files.
+FRONTEND = dict(redundancy=True)
+
+
 def load_yaml(path):
-    """Read a reference-style flat YAML file into a parameter dict (missing keys -> LEG_FUSION)."""
+    """Read a reference-style flat YAML file into a parameter dict (missing keys -> LEG_FUSION / FRONTEND)."""
     import yaml
 
     with open(path) as f:
         y = yaml.safe_load(f)
     p = dict(LEG_FUSION)
-    p.update({k: v for k, v in y.items() if k in p})
+    p.update({k: v for k, v in y.items() if k in p or k in FRONTEND})
     return p
+
+
+def kin_config(params=None):
+    """lk_kin_config from a parameter dict keyed like the yaml (Kinematics::Config, ros_interface.cc:82-88, and `redundancy`)."""
+    from .abi import lk_kin_config
+
+    p = dict(FRONTEND, **(LEG_FUSION if params is None else params))
+    c = lk_kin_config()
+    for k in ("leg_offset_x", "leg_offset_y", "leg_calf_length", "leg_thigh_length", "leg_thigh_offset", "contact_force_threshold_up",
+              "contact_force_threshold_down"):
+        setattr(c, k, float(p[k]))
+    c.redundancy = 1 if p["redundancy"] else 0
+    return c
 
 
 def make_config(params=None, device_id=0, n_slots=1, max_roots=1 << 18, max_nodes=1 << 19,

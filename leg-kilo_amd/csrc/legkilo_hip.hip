@@ -171,6 +171,7 @@ void lk_destroy(lk_handle* h) {
     if (h->h_rag) hipHostFree(h->h_rag);
     if (h->h_result) hipHostFree(h->h_result);
     ov_free(h);
+    kin_free(h);
     for (auto& e : h->ord) {
         if (e.copy) hipFree(e.copy);
         if (e.d_ref) hipFree(e.d_ref);
@@ -1960,6 +1961,18 @@ int lk_batch_replay_ragged_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n
 int lk_batch_replay_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
                               int msg_kind, const uint32_t* n_msg, const void* msgs, lk_pose* out) {
     CHECK_H(h);
+    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, msg_kind, n_msg, msgs, false, out);
+}
+// The same with the kinematic records already in HBM (lk_decode_highstate_dev + lk_kin_split_dev): a device-to-device copy instead of the upload.
+int lk_batch_replay_scans_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
+                                  const uint32_t* n_msg, const lk_kin_imu* d_kins, lk_pose* out) {
+    CHECK_H(h);
+    if (!n_msg) return fail(h, LK_ERR_INVALID, "null argument");
+    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, 2, n_msg, d_kins, true, out);
+}
+// Body of both entries: msgs is a host pointer, or a device pointer when msgs_on_device.
+int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
+                 const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out) {
     if (n_scans == 0 || n_scans > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_scans must be in [1, n_slots]");
     if (!d_pts || !scan_off || !t_begin) return fail(h, LK_ERR_INVALID, "null argument");
     if (msg_kind < 0 || msg_kind > 2 || (msg_kind && !n_msg)) return fail(h, LK_ERR_INVALID, "msg_kind must be 0 (none), 1 (lk_imu) or 2 (lk_kin_imu) with n_msg given");
@@ -2003,7 +2016,8 @@ int lk_batch_replay_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scan
         moff.resize(S + 1, 0);
         for (size_t s = 0; s < S; ++s) moff[s + 1] = moff[s] + n_msg[s];
         HIPCHK(h, hipMemcpyAsync(d_mo, moff.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
-        if (n_msg_total) HIPCHK(h, hipMemcpyAsync(d + o_ms, msgs, msg_bytes * n_msg_total, hipMemcpyHostToDevice, h->stream));
+        if (n_msg_total)
+            HIPCHK(h, hipMemcpyAsync(d + o_ms, msgs, msg_bytes * n_msg_total, msgs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, hipMemsetAsync(d_st, 0, 16, h->stream));
     const unsigned int nblk = (unsigned int)((n + 255) / 256);

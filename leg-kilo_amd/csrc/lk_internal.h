@@ -2,13 +2,13 @@
 // headers.  Round 6: the library is five units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
 // kernel but the overlay's and the stream path's own), lk_stream.hip (LK_TU_STREAM: one live scan after the other with the map insert - the per-bucket
 // launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries that run them), lk_overlay.hip (LK_TU_OVERLAY: batch replay
-// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
+// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_kin.hip (LK_TU_KIN: the leg kinematics front end - HighState decode, contact detector, scan split - and its entries, lk_kin_kernels.h), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
 // (LK_KERNELS_ELSEWHERE) and launches it through the main unit's host stub.  The overlay header's own kernels are compiled in the overlay unit only.
 #pragma once
-#if !defined(LK_TU_MAIN) && !defined(LK_TU_OVERLAY) && !defined(LK_TU_STREAM) && !defined(LK_TU_OVSCAN)
-#error "define LK_TU_MAIN, LK_TU_STREAM, LK_TU_OVERLAY or LK_TU_OVSCAN before including lk_internal.h"
+#if !defined(LK_TU_MAIN) && !defined(LK_TU_OVERLAY) && !defined(LK_TU_STREAM) && !defined(LK_TU_OVSCAN) && !defined(LK_TU_KIN)
+#error "define LK_TU_MAIN, LK_TU_STREAM, LK_TU_OVERLAY, LK_TU_OVSCAN or LK_TU_KIN before including lk_internal.h"
 #endif
-#if defined(LK_TU_OVERLAY) || defined(LK_TU_STREAM) || defined(LK_TU_OVSCAN)
+#if defined(LK_TU_OVERLAY) || defined(LK_TU_STREAM) || defined(LK_TU_OVSCAN) || defined(LK_TU_KIN)
 #define LK_KERNELS_ELSEWHERE 1
 #endif
 // legkilo_hip.hip — implementation of the C-ABI in include/legkilo_hip.h for gfx950.
@@ -158,6 +158,14 @@ struct lk_handle {
     uint64_t ord_tick = 0, ord_examined = 0, ord_sorted = 0, ord_stale = 0;
     int batch_order_mode = 1;              // LK_BATCH_ORDER_AUTO; LEGKILO_BATCH_ORDER=0 / lk_batch_order(h, 0): replay every batch as given
     int batch_order_after = 2;             // a batch is sorted once this many replays in a row have found the same content in its buffer (the sort pays for itself after ~10)
+    // leg kinematics front end (lk_kin.hip): configuration, the state carried from message to message, grow-only scratch
+    bool kin_configured = false;
+    lk_kin_config kin_cfg = {};
+    lk_kin_frontend_state kin_fe = {};
+    void* d_kin = nullptr;        // keep flags, ranks, transition maps, their scan, status words
+    size_t kin_cap = 0;
+    void* d_kintmp = nullptr;     // rocPRIM scan scratch
+    size_t kintmp_cap = 0;
     bool profiling = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::map<std::string, ProfEntry> prof;
@@ -325,6 +333,8 @@ int join_side_streams(lk_handle* h);
 int zero_scan_counters(lk_handle* h, uint32_t first_slot, uint32_t n_slots);
 int fetch_poses(lk_handle* h, lk_pose* out, int n);
 int export_map_blob(lk_handle* h, const LkMap& m, unsigned int hash_cap, void* blob, size_t* bytes);
+int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
+                 const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out);   // lk_batch_replay_scans(_kin)_dev
 int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets, const uint32_t* bucket_off,
                   const double* bucket_dt, const double* t_begin, const uint32_t* n_imu, const void* imus, size_t msg_bytes, lk_pose* out, bool with_insert = false);
 __global__ void lk_set_times_kernel(LkFilter* filters, int n, double t);
@@ -335,6 +345,8 @@ int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n,
              size_t n_kin, float* xyz_world_out, lk_pose* out);          // the bucket loop of KILO::process on a sorted cloud that is in HBM (and on the host, for the bucket bounds)
 // overlay unit (lk_overlay.hip)
 void ov_free(lk_handle* h);
+// kinematics unit (lk_kin.hip)
+void kin_free(lk_handle* h);
 // lk_ovscan.hip (LK_TU_OVSCAN: the scan-resident kernel of the recorded-run replay with insert, a unit of its own for the build time): one launch of it
 int ov_scan_launch(lk_handle* h, bool xid, int S, hipStream_t st, const LkMap& fmap, const LkOverlay& ov, LkFilter* fl, const LkRagged& rg, const lk_point* d_pts, int msg_kind,
                    int* cur, int* fb_b, unsigned int* pending);

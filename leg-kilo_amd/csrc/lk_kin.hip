@@ -1,0 +1,194 @@
+// lk_kin.hip - the leg kinematics unit of liblegkilo_hip.so (see lk_internal.h): unitree_legged_msgs/HighState messages -> lk_kin_imu records on the
+// device (lk_kin_kernels.h), the kin branch of syncPackage that hands them to the scans, and the C-ABI entries around both.
+#define LK_TU_KIN 1
+#include "lk_internal.h"
+#include "lk_kin_kernels.h"
+
+static_assert(sizeof(lk_kin_config) == 64, "lk_kin_config must be 64 B");
+static_assert(sizeof(lk_kin_frontend_state) == 32, "lk_kin_frontend_state must be 32 B");
+
+static int kin_scratch(lk_handle* h, size_t bytes) {
+    if (bytes <= h->kin_cap) return LK_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_kin) hipFree(h->d_kin), h->d_kin = nullptr, h->kin_cap = 0;
+    HIPCHK(h, hipMalloc(&h->d_kin, bytes + bytes / 4));
+    h->kin_cap = bytes + bytes / 4;
+    return LK_OK;
+}
+static int kin_tmp(lk_handle* h, size_t bytes) {
+    if (bytes <= h->kintmp_cap) return LK_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_kintmp) hipFree(h->d_kintmp), h->d_kintmp = nullptr, h->kintmp_cap = 0;
+    HIPCHK(h, hipMalloc(&h->d_kintmp, bytes));
+    h->kintmp_cap = bytes;
+    return LK_OK;
+}
+static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// flags -> two scans -> scatter -> check; the carried state moves only when the call succeeds
+static int kin_decode(lk_handle* h, const unsigned char* d_msgs, size_t n_sz, lk_kin_imu* d_out, size_t* n_out) {
+    const unsigned int n = (unsigned int)n_sz;
+    // scratch: keep u32[n] | rank u32[n] | maps u8[n] | scanned maps u8[n] | status
+    const size_t o_keep = 0, o_rank = align16(4 * n_sz), o_map = o_rank + align16(4 * n_sz), o_cmap = o_map + align16(n_sz),
+                 o_st = o_cmap + align16(n_sz), bytes = o_st + align16(sizeof(LkKinStatus));
+    int rc = kin_scratch(h, bytes);
+    if (rc) return rc;
+    unsigned char* d = static_cast<unsigned char*>(h->d_kin);
+    auto* keep = reinterpret_cast<unsigned int*>(d + o_keep);
+    auto* rank = reinterpret_cast<unsigned int*>(d + o_rank);
+    auto* maps = d + o_map;
+    auto* cmaps = d + o_cmap;
+    auto* st = reinterpret_cast<LkKinStatus*>(d + o_st);
+    size_t b0 = 0, b1 = 0;
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, b0, keep, rank, n_sz, h->stream));
+    HIPCHK(h, lk_prim_compose_scan(nullptr, b1, maps, cmaps, n_sz, h->stream));
+    size_t tb = std::max(b0, b1);
+    rc = kin_tmp(h, tb);
+    if (rc) return rc;
+    const lk_kin_config& c = h->kin_cfg;
+    const lk_kin_frontend_state& fe = h->kin_fe;
+    const int4 c0 = make_int4(fe.contact[0], fe.contact[1], fe.contact[2], fe.contact[3]);
+    HIPCHK(h, hipMemsetAsync(st, 0, sizeof(LkKinStatus), h->stream));
+    const unsigned int nb = (n + 255) / 256;
+    LAUNCH(h, "kin_flags", hipLaunchKernelGGL(lk_kin_flags_kernel, dim3(nb), dim3(256), 0, h->stream, d_msgs, n, fe.last_acc_z, fe.last_gyr_z,
+                                              c.redundancy ? 1 : 0, c.contact_force_threshold_up, c.contact_force_threshold_down, keep, maps));
+    size_t t0 = tb, t1 = tb;
+    HIPCHK(h, lk_prim_exclusive_scan(h->d_kintmp, t0, keep, rank, n_sz, h->stream));
+    HIPCHK(h, lk_prim_compose_scan(h->d_kintmp, t1, maps, cmaps, n_sz, h->stream));
+    const unsigned int ns = (n + LK_KIN_MSGS_PER_BLOCK - 1) / LK_KIN_MSGS_PER_BLOCK;
+    LAUNCH(h, "kin_scatter", hipLaunchKernelGGL(lk_kin_scatter_kernel, dim3(ns), dim3(4 * LK_KIN_MSGS_PER_BLOCK), 0, h->stream, d_msgs, n, c, c0, keep,
+                                                rank, cmaps, d_out));
+    LAUNCH(h, "kin_finish", hipLaunchKernelGGL(lk_kin_finish_kernel, dim3(nb), dim3(256), 0, h->stream, d_msgs, n, fe.last_stamp, c0, keep, rank,
+                                               cmaps, d_out, st));
+    LkKinStatus hs;
+    HIPCHK(h, hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hs.err) return fail(h, LK_ERR_INVALID, "HighState stamps go backwards (a kept message is older than the kept one before it); the front end keeps its state");
+    for (int j = 0; j < 4; ++j) h->kin_fe.contact[j] = hs.contact[j];
+    h->kin_fe.last_acc_z = hs.acc_z;
+    h->kin_fe.last_gyr_z = hs.gyr_z;
+    h->kin_fe.last_stamp = hs.last_stamp;
+    *n_out = hs.n_out;
+    return LK_OK;
+}
+
+static void kin_reset_frontend(lk_handle* h) {
+    for (int j = 0; j < 4; ++j) h->kin_fe.contact[j] = 1;   // ContactDetector::in_contact_{true}
+    h->kin_fe.last_acc_z = 0.0f;                            // the callback's zero-initialised static message
+    h->kin_fe.last_gyr_z = 0.0f;
+    h->kin_fe.last_stamp = -HUGE_VAL;
+}
+
+extern "C" {
+
+void kin_free(lk_handle* h) {
+    if (h->d_kin) hipFree(h->d_kin);
+    if (h->d_kintmp) hipFree(h->d_kintmp);
+    h->d_kin = h->d_kintmp = nullptr;
+    h->kin_cap = h->kintmp_cap = 0;
+}
+
+int lk_kin_configure(lk_handle* h, const lk_kin_config* cfg) {
+    CHECK_H(h);
+    if (!cfg) return fail(h, LK_ERR_INVALID, "null argument");
+    h->kin_cfg = *cfg;
+    h->kin_cfg.pad_ = 0;
+    h->kin_configured = true;
+    kin_reset_frontend(h);
+    return LK_OK;
+}
+
+int lk_kin_get_frontend(lk_handle* h, lk_kin_frontend_state* st) {
+    CHECK_H(h);
+    if (!st) return fail(h, LK_ERR_INVALID, "null argument");
+    if (!h->kin_configured) return fail(h, LK_ERR_STATE, "the kinematics front end is not configured (lk_kin_configure)");
+    *st = h->kin_fe;
+    return LK_OK;
+}
+
+int lk_kin_set_frontend(lk_handle* h, const lk_kin_frontend_state* st) {
+    CHECK_H(h);
+    if (!st) return fail(h, LK_ERR_INVALID, "null argument");
+    if (!h->kin_configured) return fail(h, LK_ERR_STATE, "the kinematics front end is not configured (lk_kin_configure)");
+    for (int j = 0; j < 4; ++j)
+        if (st->contact[j] != 0 && st->contact[j] != 1) return fail(h, LK_ERR_INVALID, "contact states must be 0 or 1");
+    h->kin_fe = *st;
+    return LK_OK;
+}
+
+int lk_decode_highstate_dev(lk_handle* h, const void* d_msgs, size_t n, lk_kin_imu* d_out, size_t* n_out) {
+    CHECK_H(h);
+    if (!n_out || (n && (!d_msgs || !d_out))) return fail(h, LK_ERR_INVALID, "null argument");
+    if (!h->kin_configured) return fail(h, LK_ERR_STATE, "the kinematics front end is not configured (lk_kin_configure)");
+    if (n >= ((size_t)1 << 31)) return fail(h, LK_ERR_INVALID, "more than 2^31 messages in one call");
+    *n_out = 0;
+    if (n == 0) return LK_OK;
+    return kin_decode(h, static_cast<const unsigned char*>(d_msgs), n, d_out, n_out);
+}
+
+int lk_decode_highstate(lk_handle* h, const void* msgs, size_t n, lk_kin_imu* out, size_t* n_out) {
+    CHECK_H(h);
+    if (!n_out || (n && (!msgs || !out))) return fail(h, LK_ERR_INVALID, "null argument");
+    if (!h->kin_configured) return fail(h, LK_ERR_STATE, "the kinematics front end is not configured (lk_kin_configure)");
+    if (n >= ((size_t)1 << 31)) return fail(h, LK_ERR_INVALID, "more than 2^31 messages in one call");
+    *n_out = 0;
+    if (n == 0) return LK_OK;
+    DevTemps tmp;
+    unsigned char* d_msgs = nullptr;
+    lk_kin_imu* d_out = nullptr;
+    HIPCHK(h, tmp.alloc(&d_msgs, n * (size_t)LK_HIGHSTATE_BYTES));
+    HIPCHK(h, tmp.alloc(&d_out, n * sizeof(lk_kin_imu)));
+    HIPCHK(h, hipMemcpyAsync(d_msgs, msgs, n * (size_t)LK_HIGHSTATE_BYTES, hipMemcpyHostToDevice, h->stream));
+    size_t cnt = 0;
+    const int rc = kin_decode(h, d_msgs, n, d_out, &cnt);
+    if (rc != LK_OK) {
+        hipStreamSynchronize(h->stream);   // (the temporaries are freed on return)
+        return rc;
+    }
+    if (cnt) HIPCHK(h, hipMemcpyAsync(out, d_out, cnt * sizeof(lk_kin_imu), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_out = cnt;
+    return LK_OK;
+}
+
+int lk_kin_split_dev(lk_handle* h, const lk_kin_imu* d_kins, size_t n_kins, const double* scan_end, size_t n_scans, uint32_t* n_msg,
+                     size_t* n_packaged, size_t* n_consumed) {
+    CHECK_H(h);
+    if (!n_packaged || !n_consumed || (n_scans && (!scan_end || !n_msg)) || (n_kins && !d_kins)) return fail(h, LK_ERR_INVALID, "null argument");
+    if (n_kins >= ((size_t)1 << 31) || n_scans >= ((size_t)1 << 31)) return fail(h, LK_ERR_INVALID, "more than 2^31 records or scans");
+    for (size_t s = 0; s < n_scans; ++s) {
+        if (scan_end[s] != scan_end[s]) return fail(h, LK_ERR_INVALID, "scan end time is NaN");
+        if (s && scan_end[s] < scan_end[s - 1]) return fail(h, LK_ERR_INVALID, "scan end times must be non-decreasing");
+    }
+    *n_packaged = 0;
+    *n_consumed = 0;
+    for (size_t s = 0; s < n_scans; ++s) n_msg[s] = 0;
+    if (n_scans == 0 || n_kins == 0) return LK_OK;   // an empty cache packages nothing (ros_interface.cc:307)
+    const unsigned int S = (unsigned int)n_scans, n = (unsigned int)n_kins;
+    // scratch: ends f64[S] | lb u32[S] | n_msg u32[S] | eq u8[S] | st u32[2]
+    const size_t o_end = 0, o_lb = align16(8 * n_scans), o_nm = o_lb + align16(4 * n_scans), o_eq = o_nm + align16(4 * n_scans),
+                 o_st = o_eq + align16(n_scans), bytes = o_st + 16;
+    int rc = kin_scratch(h, bytes);
+    if (rc) return rc;
+    unsigned char* d = static_cast<unsigned char*>(h->d_kin);
+    auto* ends = reinterpret_cast<double*>(d + o_end);
+    auto* lb = reinterpret_cast<unsigned int*>(d + o_lb);
+    auto* nm = reinterpret_cast<unsigned int*>(d + o_nm);
+    auto* eq = d + o_eq;
+    auto* st = reinterpret_cast<unsigned int*>(d + o_st);
+    HIPCHK(h, hipMemcpyAsync(ends, scan_end, 8 * n_scans, hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "kin_lb", hipLaunchKernelGGL(lk_kin_lb_kernel, dim3((S + 255) / 256), dim3(256), 0, h->stream, d_kins, n, ends, S, lb, eq));
+    LAUNCH(h, "kin_split", hipLaunchKernelGGL(lk_kin_split_kernel, dim3(1), dim3(LK_WAVE), 0, h->stream, lb, eq, S, n, nm, st));
+    unsigned int hs[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(hs, st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hs[0]) {
+        HIPCHK(h, hipMemcpyAsync(n_msg, nm, 4 * (size_t)hs[0], hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    *n_packaged = hs[0];
+    *n_consumed = hs[1];
+    return LK_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// lk_prim.h - the three rocPRIM device-wide primitives the library uses, behind plain functions.
+// lk_prim.h - the four rocPRIM device-wide primitives the library uses, behind plain functions.
 // They live in a translation unit of their own (lk_prim.hip): rocPRIM is header-only and its sorts and scans are the slowest templates of the
 // build to instantiate; compiled beside legkilo_hip.hip instead of inside it they cost no wall-clock time (make -j2).
 // Calling convention = rocPRIM's: tmp == nullptr asks for the temporary storage size in `bytes`, the second call does the work on `stream`.
@@ -16,3 +16,6 @@ hipError_t lk_prim_exclusive_scan(void* tmp, size_t& bytes, const unsigned int* 
 hipError_t lk_prim_segmented_sort_pairs(void* tmp, size_t& bytes, const unsigned int* keys_in, unsigned int* keys_out, const unsigned int* vals_in,
                                         unsigned int* vals_out, unsigned int n, unsigned int n_segments, const unsigned int* begin, const unsigned int* end,
                                         unsigned int bit0, unsigned int bit1, hipStream_t stream);
+// inclusive scan of per-leg transition maps under composition (the leg kinematics front end's contact detectors, lk_kin.hip): byte = 4 x 2 bits,
+// bits 2j / 2j+1 = the image of state 0 / 1 of leg j; out[i] = in[i] o ... o in[0] (in[0] applied first).  Associative, not commutative: order kept.
+hipError_t lk_prim_compose_scan(void* tmp, size_t& bytes, const unsigned char* in, unsigned char* out, size_t n, hipStream_t stream);

@@ -17,3 +17,19 @@ hipError_t lk_prim_segmented_sort_pairs(void* tmp, size_t& bytes, const unsigned
                                         unsigned int bit0, unsigned int bit1, hipStream_t stream) {
     return rocprim::segmented_radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, n_segments, begin, end, bit0, bit1, stream);
 }
+namespace {
+struct LkComposeMaps {   // (a then b): leg j of the result maps x to b_j(a_j(x))
+    __host__ __device__ unsigned char operator()(unsigned char a, unsigned char b) const {
+        unsigned int r = 0;
+        for (int j = 0; j < 4; ++j) {
+            const unsigned int a0 = (a >> (2 * j)) & 1u, a1 = (a >> (2 * j + 1)) & 1u;
+            r |= ((b >> (2 * j + a0)) & 1u) << (2 * j);
+            r |= ((b >> (2 * j + a1)) & 1u) << (2 * j + 1);
+        }
+        return (unsigned char)r;
+    }
+};
+}  // namespace
+hipError_t lk_prim_compose_scan(void* tmp, size_t& bytes, const unsigned char* in, unsigned char* out, size_t n, hipStream_t stream) {
+    return rocprim::inclusive_scan(tmp, bytes, in, out, n, LkComposeMaps(), stream);
+}

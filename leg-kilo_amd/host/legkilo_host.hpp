@@ -5,6 +5,8 @@
 //   legkilo::VoxelMapManager   <- legkilo/src/core/slam/voxel_map.h:180-244 (live members)
 //   legkilo::KiloPath          <- KILO::predictUpdatePoint / predictUpdateImu / predictUpdateKinImu and the
 //                                 bucket loop of KILO::process (KILO.cc:108-399)
+//   legkilo::Kinematics        <- legkilo/src/preprocess/kinematics.h (Kinematics::processing for a batch of serialized HighState
+//                                 messages, with kinematicImuCallBack's redundancy filter) + the kin branch of syncPackage
 //
 // Same method names, argument meaning and (void / bool) error behaviour as the reference.  Differences forced
 // by the state living in HBM: state()/cov()/Q() return COPIES (use setState/setCov/setQ to write back), and
@@ -526,6 +528,56 @@ class KiloPath {
     std::shared_ptr<Device> dev_;
     std::unique_ptr<ESKF> eskf_;
     std::unique_ptr<VoxelMapManager> map_manager_;
+};
+
+// Kinematics::Config (kinematics.h) + the callback's `redundancy` flag.  processing() takes serialized unitree_legged_msgs/HighState
+// messages (ROS1 serialisation, LK_HIGHSTATE_BYTES each, e.g. the bytes of a recorded /high_state topic) instead of one deserialised
+// message, and returns the records of the kept ones (a dropped one yields none): what kinematicImuCallBack pushes into kin_imu_cache_.
+// State carried across calls: the four ContactDetectors, the previous message, the last kept stamp (frontend() / setFrontend()).
+class Kinematics {
+   public:
+    struct Config {
+        double leg_offset_x;
+        double leg_offset_y;
+        double leg_calf_length;
+        double leg_thigh_length;
+        double leg_thigh_offset;
+        double contact_force_threshold_up;
+        double contact_force_threshold_down;
+        bool redundancy = true;
+    };
+
+    Kinematics(const Config& config, std::shared_ptr<Device> dev) : dev_(std::move(dev)) {
+        lk_kin_config c{config.leg_offset_x, config.leg_offset_y, config.leg_calf_length, config.leg_thigh_length, config.leg_thigh_offset,
+                        config.contact_force_threshold_up, config.contact_force_threshold_down, config.redundancy ? 1 : 0, 0};
+        dev_->check(lk_kin_configure(dev_->h(), &c));
+    }
+    std::vector<lk_kin_imu> processing(const void* msgs, size_t n_msgs) {
+        std::vector<lk_kin_imu> out(std::max<size_t>(n_msgs, 1));
+        size_t n_out = 0;
+        dev_->check(lk_decode_highstate(dev_->h(), msgs, n_msgs, out.data(), &n_out));
+        out.resize(n_out);
+        return out;
+    }
+    lk_kin_frontend_state frontend() const {
+        lk_kin_frontend_state st;
+        dev_->check(lk_kin_get_frontend(dev_->h(), &st));
+        return st;
+    }
+    void setFrontend(const lk_kin_frontend_state& st) { dev_->check(lk_kin_set_frontend(dev_->h(), &st)); }
+    // syncPackage's kin branch (ros_interface.cc:303-328) over records already in HBM; n_msg[s] = records of packaged scan s
+    size_t syncPackages(const lk_kin_imu* d_kins, size_t n_kins, const std::vector<double>& scan_end, std::vector<uint32_t>& n_msg,
+                        size_t* n_consumed) {
+        n_msg.assign(std::max<size_t>(scan_end.size(), 1), 0);
+        size_t n_packaged = 0, consumed = 0;
+        dev_->check(lk_kin_split_dev(dev_->h(), d_kins, n_kins, scan_end.data(), scan_end.size(), n_msg.data(), &n_packaged, &consumed));
+        n_msg.resize(scan_end.size());
+        if (n_consumed) *n_consumed = consumed;
+        return n_packaged;
+    }
+
+   private:
+    std::shared_ptr<Device> dev_;
 };
 
 }  // namespace LEGKILO_HOST_NAMESPACE

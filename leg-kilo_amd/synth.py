@@ -366,6 +366,96 @@ def kin_stream(traj, t0, t1, params, rate=500.0, seed=3003, acc_noise=0.02, gyr_
     return out
 
 
+HIGHSTATE_BYTES = 1095   # ROS1 serialisation of unitree_legged_msgs/HighState (fixed size: every array has a fixed length)
+# byte offsets of the fields the front end reads (field order of unitree_legged_msgs/msg/{HighState,IMU,MotorState}.msg)
+HS_SEC, HS_NSEC, HS_GYR, HS_ACC, HS_MOTOR0, HS_MOTOR_BYTES, HS_FORCE = 0, 4, 46, 58, 83, 38, 877   # motorState[k]: q at +1, dq at +5
+
+
+def _legs_fk_jac(q, p):
+    """foot_pos_vel's position and Jacobian for q (..., 4, 3), vectorised (only used to pick joint rates)."""
+    lt, lc, d, ox, oy = p["leg_thigh_length"], p["leg_calf_length"], p["leg_thigh_offset"], p["leg_offset_x"], p["leg_offset_y"]
+    lfoot = np.array([1.0, -1.0, 1.0, -1.0])
+    ffoot = np.array([1.0, 1.0, -1.0, -1.0])
+    s1, s2, s23 = np.sin(q[..., 0]), np.sin(q[..., 1]), np.sin(q[..., 1] + q[..., 2])
+    c1, c2, c23 = np.cos(q[..., 0]), np.cos(q[..., 1]), np.cos(q[..., 1] + q[..., 2])
+    pos = np.stack([-lt * s2 - lc * s23 + ffoot * ox, lfoot * d * c1 + lc * s1 * c23 + lt * c2 * s1 + lfoot * oy,
+                    lfoot * d * s1 - lc * c1 * c23 - lt * c1 * c2], axis=-1)
+    J = np.zeros(q.shape[:-1] + (3, 3))
+    J[..., 0, 1], J[..., 0, 2] = -lc * c23 - lt * c2, -lc * c23
+    J[..., 1, 0], J[..., 1, 1], J[..., 1, 2] = lt * c1 * c2 - lfoot * d * s1 + lc * c1 * c23, -s1 * (lc * s23 + lt * s2), -lc * s23 * s1
+    J[..., 2, 0], J[..., 2, 1], J[..., 2, 2] = lt * c2 * s1 + lfoot * d * c1 + lc * s1 * c23, c1 * (lc * s23 + lt * s2), lc * s23 * c1
+    return pos, J
+
+
+def highstate_stream(traj, t0, t1, params, rate=500.0, hold=10, seed=3003, acc_noise=0.02, gyr_noise=0.002):
+    """Serialized unitree_legged_msgs/HighState messages (what a recorded /high_state topic holds) for the trot of kin_stream:
+    (msgs uint8 [n, HIGHSTATE_BYTES], truth) with truth = dict(sec, nsec (uint32), acc, gyr (f32 [n, 3]), q, dq (f32 [n, 20], Unitree
+    motor order FL FR RL RR x hip thigh calf), force (int16 [n, 4], Unitree foot order)).
+      - joint angles and rates of the trot, rates solved from the leg Jacobian for non-slipping stance feet, written as f32;
+      - foot forces ramp through the two contact thresholds and dwell between them (inside (40, 60) of diter.yaml the detector toggles on
+        every message; in leg_fusion.yaml's (200, 220) it holds), and stay low in swing, high in stance;
+      - IMU values are held for `hold` messages (published at 500 Hz, updated at 50 Hz: what the `redundancy` flag is for);
+      - every byte the front end does not read is random."""
+    rng = np.random.default_rng(seed + 41)
+    n = int(np.floor((t1 - t0) * rate))
+    t = t0 + (np.arange(n) + 0.5) / rate
+    sec = np.floor(t).astype(np.uint32)
+    nsec = np.minimum(np.round((t - sec) * 1e9), 999_999_999).astype(np.uint32)
+    # IMU: every message of a block of `hold` repeats the block's first one
+    blk = (np.arange(n) // hold) * hold
+    th = t[blk]
+    R = traj.rot(th)
+    acc = (np.einsum("nji,nj->ni", R, traj.acc(th) - G_WORLD) + rng.normal(0, acc_noise, (n, 3))).astype(np.float32)
+    gyr = (traj.omega_body(th) + rng.normal(0, gyr_noise, (n, 3))).astype(np.float32)
+    acc, gyr = acc[blk], gyr[blk]
+    # trot (kin_stream's model), project legs FR FL RR RL
+    Rt, vw, w = traj.rot(t), traj.vel(t), traj.omega_body(t)
+    gait_T = 0.5
+    ph = (t / gait_T) % 1.0
+    ph_leg = np.stack([ph, (ph + 0.5) % 1.0, (ph + 0.5) % 1.0, ph], axis=1)
+    contact = ph_leg < 0.6
+    sway = 0.15 * np.sin(2 * np.pi * t[:, None] / gait_T + np.array([0, np.pi, np.pi, 0]))
+    q = np.stack([np.full((n, 4), 0.02), 0.8 + sway, np.full((n, 4), -1.6)], axis=2)
+    pos, J = _legs_fk_jac(q, params)
+    vb = -np.einsum("nji,nj->ni", Rt, vw)
+    vf = vb[:, None, :] - np.cross(w[:, None, :], pos)
+    swing = np.stack([np.full(n, 1.2), np.zeros(n), 0.3 * np.cos(2 * np.pi * ph)], axis=1)
+    vf = vf + (~contact)[..., None] * swing[:, None, :]
+    dq = np.linalg.solve(J, vf[..., None])[..., 0]
+    # foot force per project leg: stance high, swing low, ramps through the thresholds with dwells inside the window between them
+    lo = min(params["contact_force_threshold_up"], params["contact_force_threshold_down"])
+    hi = max(params["contact_force_threshold_up"], params["contact_force_threshold_down"])
+    mid, jit = 0.5 * (lo + hi), max(0, min(3, int((hi - lo) // 2) - 1))
+    x = (ph_leg + 0.05) % 1.0   # 0 .. 0.6: stance (shifted a little against the kinematic contact)
+    f = np.select([x < 0.45, x < 0.52, x < 0.58, x < 0.64, x < 0.86, x < 0.92, x < 0.97],
+                  [hi + 60, hi + 60 + (mid - hi - 60) * (x - 0.45) / 0.07, mid, mid + (max(lo - 40, 0) - mid) * (x - 0.58) / 0.06,
+                   max(lo - 40, 0), max(lo - 40, 0) + (mid - max(lo - 40, 0)) * (x - 0.86) / 0.06, mid], hi + 60)
+    dwell = ((x >= 0.52) & (x < 0.58)) | ((x >= 0.92) & (x < 0.97))
+    f = np.round(f) + dwell * rng.integers(-jit, jit + 1, f.shape)
+    # Unitree order: project leg j <- Unitree leg j ^ 1 (kinematics.cc:20-37)
+    uni = [1, 0, 3, 2]
+    force = f[:, uni].astype(np.int16)
+    q20 = np.zeros((n, 20), dtype=np.float32)
+    dq20 = np.zeros((n, 20), dtype=np.float32)
+    q20[:, :12] = q[:, uni, :].reshape(n, 12)
+    dq20[:, :12] = dq[:, uni, :].reshape(n, 12)
+    msgs = rng.integers(0, 256, (n, HIGHSTATE_BYTES), dtype=np.uint8)
+
+    def put(off, arr):
+        b = np.ascontiguousarray(arr).view(np.uint8).reshape(n, -1)
+        msgs[:, off:off + b.shape[1]] = b
+
+    put(HS_SEC, sec.astype("<u4"))
+    put(HS_NSEC, nsec.astype("<u4"))
+    put(HS_GYR, gyr.astype("<f4"))
+    put(HS_ACC, acc.astype("<f4"))
+    for k in range(20):
+        put(HS_MOTOR0 + HS_MOTOR_BYTES * k + 1, q20[:, k:k + 1].astype("<f4"))
+        put(HS_MOTOR0 + HS_MOTOR_BYTES * k + 5, dq20[:, k:k + 1].astype("<f4"))
+    put(HS_FORCE, force.astype("<i2"))
+    return msgs, dict(sec=sec, nsec=nsec, acc=acc, gyr=gyr, q=q20, dq=dq20, force=force)
+
+
 # --------------------------------------------------------------------------- filter priors
 def initial_state(traj, t, params, perturb_rng=None, sig_pos=0.0, sig_ang_deg=0.0):
     """x36 at trajectory time t (true pose, velocity, gravity; imu_a/imu_w from the true motion),

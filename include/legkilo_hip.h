@@ -296,6 +296,19 @@ int lk_decode_scan_dev(lk_handle* h, const void* d_msg_data, size_t n_points, co
  * out_sorted must hold n_raw points; *n_out receives the number of cells. */
 int lk_preprocess_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float leaf, lk_point* out_sorted, size_t* n_out);
 int lk_preprocess_scan_dev(lk_handle* h, const lk_point* d_raw, size_t n_raw, float leaf, lk_point* d_out_sorted, size_t* n_out);
+/* The lidar front end of a recorded run: n_msgs sensor_msgs/PointCloud2 payloads -> per message what lk_decode_scan_dev followed by
+ * lk_preprocess_scan_dev give (lidarCallBack + LidarProcessing::processing, lidar_processing.cc:25-108; pcl::VoxelGrid + time sort,
+ * KILO.cc:356-370), bit for bit, in one call.  Message s = n_points[s] points of layout->point_step bytes at d_msgs + msg_off[s]
+ * (any alignment, gaps allowed); one layout / time_scale / filter_num / blind / leaf for the run.  Outputs: scan s = d_out[scan_off[s],
+ * scan_off[s+1]) (d_out: room for sum(n_points) points; scan_off: n_msgs + 1 host entries, first 0), t_begin[s] / t_end[s] =
+ * LidarScan::lidar_begin_time_ / lidar_end_time_ (host, may be NULL) - ready for lk_batch_replay_scans(_kin)_dev and lk_kin_split_dev.
+ * The tables msg_off / n_points / header_stamp are host arrays of n_msgs entries.  LK_ERR_INVALID, naming the first offending message,
+ * for what the two per-scan entries refuse, a message without points, more than 0x7fffffff points in all (split the run), header stamps
+ * that decrease (lidarCallBack's time check, ros_interface.cc; the reference clears its cache there), a message that decodes to no
+ * points, and a voxel-index overflow in any message; the output is then undefined and the handle stays usable.  Synchronous. */
+int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const uint64_t* msg_off, const uint32_t* n_points,
+                        const double* header_stamp, const lk_cloud_layout* layout, double time_scale, int filter_num, float blind,
+                        float leaf, lk_point* d_out, uint64_t* scan_off, double* t_begin, double* t_end);
 /* raw scan -> pose without the cloud leaving HBM: lk_preprocess_scan_dev + the bucket loop of lk_process_scan
  * (only the n_out x 16 B sorted cloud is read back, for the bucket bounds and the IMU interleave). */
 int lk_process_raw_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float leaf, double t_begin, const lk_imu* imus,

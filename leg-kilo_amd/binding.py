@@ -23,7 +23,7 @@ EXPORTS = [
     "lk_decode_scan", "lk_decode_scan_dev", "lk_preprocess_scan", "lk_preprocess_scan_dev", "lk_process_raw_scan", "lk_batch_set_priors", "lk_batch_set_priors_dev", "lk_batch_get_states", "lk_batch_get_states_dev", "lk_batch_residuals_dev", "lk_batch_order", "lk_batch_changed", "lk_batch_prepare_dev", "lk_batch_order_stats", "lk_batch_replay_dev", "lk_batch_sort_by_voxel_dev", "lk_batch_replay_async_dev", "lk_batch_replay_ragged_dev", "lk_batch_replay_ragged_imu_dev", "lk_batch_replay_ragged_kin_dev", "lk_batch_replay_scans_dev", "lk_batch_replay_overlay_dev", "lk_batch_replay_overlay_ragged_dev", "lk_overlay_reserve", "lk_overlay_export", "lk_overlay_stats", "lk_overlay_pool_bytes", "lk_overlay_resident_rounds", "lk_profile_enable", "lk_profile_get", "lk_profile_reset",
     "lk_device_malloc", "lk_device_free", "lk_memcpy_h2d", "lk_memcpy_d2h", "lk_synchronize", "lk_stream", "lk_stream_pipeline", "lk_stream_resident", "lk_stream_grid", "lk_stream_grid_placement", "lk_stream_stats", "lk_stream_resident_stats", "lk_test_stall",
     "lk_kin_configure", "lk_kin_get_frontend", "lk_kin_set_frontend", "lk_decode_highstate", "lk_decode_highstate_dev", "lk_kin_split_dev",
-    "lk_batch_replay_scans_kin_dev",
+    "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
 ]
 
 
@@ -294,6 +294,30 @@ class LegKiloHip:
         self._chk(self.L.lk_decode_scan(self.h, _p(data), C.c_size_t(n_points), C.byref(lay), C.c_double(time_scale), int(filter_num),
                                         C.c_float(blind), C.c_double(header_stamp), _p(out), C.byref(n_out), C.byref(tb), C.byref(te)))
         return out[: n_out.value], tb.value, te.value
+
+    def decode_scan_dev(self, d_msg, n_points, layout, time_scale, filter_num, blind, header_stamp, d_out):
+        """One message in HBM -> its decoded points at the device pointer d_out (room for n_points); returns (n_out, t_begin, t_end)."""
+        lay = abi.lk_cloud_layout(**layout)
+        n_out, tb, te = C.c_size_t(0), C.c_double(0), C.c_double(0)
+        self._chk(self.L.lk_decode_scan_dev(self.h, C.c_void_p(d_msg), C.c_size_t(n_points), C.byref(lay), C.c_double(time_scale), int(filter_num),
+                                            C.c_float(blind), C.c_double(header_stamp), C.c_void_p(d_out), C.byref(n_out), C.byref(tb), C.byref(te)))
+        return n_out.value, tb.value, te.value
+
+    def decode_scans_dev(self, d_msgs, msg_off, n_points, header_stamps, layout, time_scale, filter_num, blind, leaf, d_out):
+        """A run's PointCloud2 messages in HBM (message s: n_points[s] points at byte offset msg_off[s] from d_msgs) -> decoded, voxel-grid
+        filtered, time-sorted scans back to back at the device pointer d_out (room for sum(n_points) points), in one call
+        (lk_decode_scans_dev).  Returns (scan_off uint64[S + 1], t_begin float64[S], t_end float64[S])."""
+        mo = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        npts = np.ascontiguousarray(n_points, dtype=np.uint32)
+        hs = _f64(header_stamps)
+        S = len(mo)
+        assert len(npts) == S and len(hs) == S
+        lay = abi.lk_cloud_layout(**layout)
+        so = np.zeros(S + 1, dtype=np.uint64)
+        tb, te = np.zeros(S), np.zeros(S)
+        self._chk(self.L.lk_decode_scans_dev(self.h, C.c_void_p(d_msgs), C.c_size_t(S), _p(mo), _p(npts), _p(hs), C.byref(lay), C.c_double(time_scale),
+                                             int(filter_num), C.c_float(blind), C.c_float(leaf), C.c_void_p(d_out), _p(so), _p(tb), _p(te)))
+        return so, tb, te
 
     def preprocess_scan(self, raw_pts, leaf):
         raw = np.ascontiguousarray(raw_pts)

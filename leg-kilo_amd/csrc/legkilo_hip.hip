@@ -165,7 +165,7 @@ void lk_destroy(lk_handle* h) {
     for (void* p : ptrs)
         if (p) hipFree(p);
     void* pre[] = {h->pre_raw, h->pre_cells, h->pre_out, h->pre_k0, h->pre_k1, h->pre_flags, h->pre_pos, h->pre_misc,
-                   h->pre_v0, h->pre_v1, h->pre_starts, h->pre_tmp};
+                   h->pre_v0, h->pre_v1, h->pre_starts, h->pre_tmp, h->d_dsc, h->d_dsctmp};
     for (void* p : pre)
         if (p) hipFree(p);
     if (h->h_rag) hipHostFree(h->h_rag);
@@ -1179,17 +1179,23 @@ static int pre_reserve(lk_handle* h, size_t n) {
     return LK_OK;
 }
 
+// what lk_decode_scan(s)_dev refuse in a point layout (nullptr: none)
+static const char* cloud_layout_error(const lk_cloud_layout* layout) {
+    if (layout->lidar_type < 1 || layout->lidar_type > 3) return "lidar_type must be 1, 2 or 3";
+    const uint32_t tsz = layout->lidar_type == 3 ? 8u : 4u;
+    if (layout->off_x + 4 > layout->point_step || layout->off_y + 4 > layout->point_step || layout->off_z + 4 > layout->point_step ||
+        layout->off_time + tsz > layout->point_step)
+        return "field offsets exceed point_step";
+    return nullptr;
+}
+
 int lk_decode_scan_dev(lk_handle* h, const void* d_msg, size_t n_points, const lk_cloud_layout* layout, double time_scale,
                        int filter_num, float blind, double header_stamp, lk_point* d_out, size_t* n_out, double* begin_time,
                        double* end_time) {
     CHECK_H(h);
     if (!d_msg || !layout || !d_out || !n_out || n_points == 0 || filter_num < 1 || n_points > 0x7fffffffu)
         return fail(h, LK_ERR_INVALID, "lk_decode_scan: bad argument");
-    if (layout->lidar_type < 1 || layout->lidar_type > 3) return fail(h, LK_ERR_INVALID, "lidar_type must be 1, 2 or 3");
-    const uint32_t tsz = layout->lidar_type == 3 ? 8u : 4u;
-    if (layout->off_x + 4 > layout->point_step || layout->off_y + 4 > layout->point_step || layout->off_z + 4 > layout->point_step ||
-        layout->off_time + tsz > layout->point_step)
-        return fail(h, LK_ERR_INVALID, "field offsets exceed point_step");
+    if (const char* e = cloud_layout_error(layout)) return fail(h, LK_ERR_INVALID, e);
     int rc = pre_reserve(h, n_points);
     if (rc) return rc;
     LkDecodeArgs a;
@@ -1272,6 +1278,152 @@ int lk_preprocess_scan_dev(lk_handle* h, const lk_point* d_raw, size_t n_raw, fl
                                                h->pre_cells, h->pre_v1, (int)nc, d_out));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_out = nc;
+    return LK_OK;
+}
+
+// ------------------------------------------------------------------ a run's lidar front end in one call (lk_pre_kernels.h, lk_dscan_*)
+// Three host round trips per call, none per message: after the decode (per-message decoded counts and raw times: empty messages are refused),
+// after the centroids (per-scan overflow words and cell offsets) and at the end.  Both sorts are rocPRIM's stable segmented radix sort with one
+// segment per scan, so ties keep the order the per-scan chain's global sorts keep.
+namespace {
+struct DscPool {   // the per-call view of h->d_dsc
+    unsigned int *flags, *pos, *sid, *k0, *k1, *v0, *v1;
+    int* starts;
+    lk_point *dec, *cells;
+    unsigned long long* msg_off;
+    unsigned int *pt_off, *dec_off, *cell_off, *err, *misc;   // cell_off [S + 1] and err [S] of the call adjacent: one read-back
+    int* mm;
+    double* first_last;
+};
+// carves the arrays out of `base` (nullptr: only counts) and returns the bytes they take
+size_t dsc_carve(void* base, size_t P, size_t S, DscPool& d) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        void* r = base ? static_cast<char*>(base) + off : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return r;
+    };
+    d.flags = (unsigned int*)take(4 * P), d.pos = (unsigned int*)take(4 * P), d.sid = (unsigned int*)take(4 * P);
+    d.k0 = (unsigned int*)take(4 * P), d.k1 = (unsigned int*)take(4 * P), d.v0 = (unsigned int*)take(4 * P), d.v1 = (unsigned int*)take(4 * P);
+    d.starts = (int*)take(4 * P);
+    d.dec = (lk_point*)take(sizeof(lk_point) * P), d.cells = (lk_point*)take(sizeof(lk_point) * P);
+    d.msg_off = (unsigned long long*)take(8 * S);
+    d.pt_off = (unsigned int*)take(4 * (S + 1)), d.dec_off = (unsigned int*)take(4 * (S + 1));
+    d.cell_off = (unsigned int*)take(4 * (2 * S + 1)), d.err = nullptr;   // err: set per call, right behind the call's S + 1 offsets
+    d.misc = (unsigned int*)take(4 * 8);
+    d.mm = (int*)take(4 * 6 * S);
+    d.first_last = (double*)take(8 * 2 * S);
+    return off;
+}
+}  // namespace
+
+static int dsc_reserve(lk_handle* h, size_t P, size_t S, DscPool& d) {
+    if (P > h->dsc_pt_cap || S > h->dsc_msg_cap) {
+        if (h->d_dsc) hipFree(h->d_dsc), h->d_dsc = nullptr;
+        const size_t pc = std::max(P, h->dsc_pt_cap), sc = std::max(S, h->dsc_msg_cap);
+        h->dsc_pt_cap = h->dsc_msg_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_dsc, dsc_carve(nullptr, pc, sc, d)));
+        h->dsc_pt_cap = pc, h->dsc_msg_cap = sc;
+    }
+    dsc_carve(h->d_dsc, h->dsc_pt_cap, h->dsc_msg_cap, d);
+    d.err = d.cell_off + S + 1;
+    size_t t1 = 0, t2 = 0;
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, d.flags, d.pos, P, h->stream));
+    HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)P, (unsigned int)S, d.dec_off, d.dec_off + 1, 0, 32,
+                                           h->stream));
+    const size_t need = std::max(t1, t2);
+    if (need > h->dsctmp_cap) {
+        if (h->d_dsctmp) hipFree(h->d_dsctmp), h->d_dsctmp = nullptr;
+        h->dsctmp_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_dsctmp, need));
+        h->dsctmp_cap = need;
+    }
+    return LK_OK;
+}
+
+int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const uint64_t* msg_off, const uint32_t* n_points,
+                        const double* header_stamp, const lk_cloud_layout* layout, double time_scale, int filter_num, float blind,
+                        float leaf, lk_point* d_out, uint64_t* scan_off, double* t_begin, double* t_end) {
+    CHECK_H(h);
+    if (!d_msgs || n_msgs == 0 || !msg_off || !n_points || !header_stamp || !layout || !d_out || !scan_off || filter_num < 1 || !(leaf > 0.f))
+        return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: bad argument");
+    if (n_msgs > 0x7fffffffu) return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: too many messages");
+    if (const char* e = cloud_layout_error(layout)) return fail(h, LK_ERR_INVALID, e);
+    const size_t S = n_msgs;
+    std::vector<unsigned int> pt_off(S + 1);
+    size_t P = 0;
+    for (size_t s = 0; s < S; ++s) {
+        if (n_points[s] == 0) return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: message " + std::to_string(s) + " has no points");
+        if (s && header_stamp[s] < header_stamp[s - 1])   // lidarCallBack's time check (ros_interface.cc)
+            return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: message " + std::to_string(s) + ": header stamp older than message " +
+                                               std::to_string(s - 1) + "'s");
+        pt_off[s] = (unsigned int)P;
+        P += n_points[s];
+        if (P > 0x7fffffffu)
+            return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: more than 0x7fffffff points from message " + std::to_string(s) + " on: split the run");
+    }
+    pt_off[S] = (unsigned int)P;
+    DscPool d;
+    int rc = dsc_reserve(h, P, S, d);
+    if (rc) return rc;
+    LkDecodeArgs a;
+    a.lay = *layout, a.time_scale = time_scale, a.filter_num = filter_num, a.blind = blind;
+    const unsigned int n = (unsigned int)P, nb = (n + 255) / 256, Si = (unsigned int)S;
+    const unsigned char* base = (const unsigned char*)d_msgs;
+    HIPCHK(h, hipMemcpyAsync(d.msg_off, msg_off, 8 * S, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d.pt_off, pt_off.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
+    // 1. decode: keep flags, compaction, scatter
+    LAUNCH(h, "dscan_flags", hipLaunchKernelGGL(lk_dscan_flags_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a, d.flags));
+    size_t tb = h->dsctmp_cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->d_dsctmp, tb, d.flags, d.pos, P, h->stream));
+    LAUNCH(h, "dscan_scatter", hipLaunchKernelGGL(lk_dscan_scatter_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a,
+                                                  d.flags, d.pos, d.dec, d.sid, d.dec_off, d.first_last, d.mm, d.err));
+    std::vector<unsigned int> dec_off(S + 1);
+    std::vector<double> fl(2 * S);
+    HIPCHK(h, hipMemcpyAsync(dec_off.data(), d.dec_off, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(fl.data(), d.first_last, 8 * 2 * S, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t s = 0; s < S; ++s)
+        if (dec_off[s + 1] == dec_off[s])
+            return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: message " + std::to_string(s) + " decodes to no points (filter_num / blind)");
+    const unsigned int D = dec_off[S], db = (D + 255) / 256;
+    // 2. voxel grid: per-scan bounds and cell keys, a stable sort by cell inside each scan, cells (a new one at every scan boundary), centroids
+    const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
+    const unsigned int gy = std::min(64u, std::max(1u, D / Si / 2048u));
+    LAUNCH(h, "dscan_minmax", hipLaunchKernelGGL(lk_dscan_minmax_kernel, dim3(Si, gy), dim3(256), 0, h->stream, d.dec, d.dec_off, d.mm));
+    LAUNCH(h, "dscan_cellidx", hipLaunchKernelGGL(lk_dscan_cellidx_kernel, dim3(db), dim3(256), 0, h->stream, d.dec, D, inv, d.mm, d.sid, d.k0, d.v0,
+                                                  d.err));
+    tb = h->dsctmp_cap;
+    HIPCHK(h, lk_prim_segmented_sort_pairs(h->d_dsctmp, tb, d.k0, d.k1, d.v0, d.v1, D, Si, d.dec_off, d.dec_off + 1, 0, 32, h->stream));
+    LAUNCH(h, "dscan_heads", hipLaunchKernelGGL(lk_dscan_heads_kernel, dim3(db), dim3(256), 0, h->stream, d.k1, d.sid, D, d.flags));
+    tb = h->dsctmp_cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->d_dsctmp, tb, d.flags, d.pos, D, h->stream));
+    unsigned int* ncells_d = d.misc;
+    LAUNCH(h, "dscan_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(db), dim3(256), 0, h->stream, d.flags, d.pos, (int)D, d.starts, ncells_d));
+    LAUNCH(h, "dscan_centroid", hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(db), dim3(256), 0, h->stream, d.dec, (const int*)d.v1, d.starts, ncells_d,
+                                                 (int)D, d.cells, d.k0, (int*)d.v0));
+    LAUNCH(h, "dscan_celloff", hipLaunchKernelGGL(lk_dscan_celloff_kernel, dim3((Si + 1 + 255) / 256), dim3(256), 0, h->stream, d.dec_off, d.pos, ncells_d,
+                                                  (int)S, d.cell_off));
+    std::vector<unsigned int> ce(2 * S + 1);   // cell_off [S + 1] | err [S]
+    HIPCHK(h, hipMemcpyAsync(ce.data(), d.cell_off, 4 * (2 * S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t s = 0; s < S; ++s)
+        if (ce[S + 1 + s])
+            return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: message " + std::to_string(s) +
+                                               ": voxel grid leaf too small for the cloud extent (index overflow)");
+    const unsigned int Cn = ce[S];
+    // 3. time sort inside each scan's cells, gather into the caller's buffer
+    tb = h->dsctmp_cap;
+    HIPCHK(h, lk_prim_segmented_sort_pairs(h->d_dsctmp, tb, d.k0, d.k1, d.v0, d.v1, Cn, Si, d.cell_off, d.cell_off + 1, 0, 32, h->stream));
+    LAUNCH(h, "dscan_gather", hipLaunchKernelGGL(lk_pre_gather_kernel, dim3((Cn + 255) / 256), dim3(256), 0, h->stream, d.cells, (const int*)d.v1, (int)Cn,
+                                               d_out));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t s = 0; s <= S; ++s) scan_off[s] = ce[s];
+    for (size_t s = 0; s < S; ++s) {
+        const double b = layout->lidar_type == 3 ? 0.0 : header_stamp[s];  // lidar_processing.cc:34-35,63-64 vs :91-92
+        if (t_begin) t_begin[s] = b + fl[2 * s];
+        if (t_end) t_end[s] = b + fl[2 * s + 1];
+    }
     return LK_OK;
 }
 

@@ -124,6 +124,11 @@ struct lk_handle {
     unsigned int *pre_k0 = nullptr, *pre_k1 = nullptr, *pre_flags = nullptr, *pre_pos = nullptr, *pre_misc = nullptr;
     int *pre_v0 = nullptr, *pre_v1 = nullptr, *pre_starts = nullptr;
     void* pre_tmp = nullptr;
+    // grow-only scratch of lk_decode_scans_dev: per-point arrays for dsc_pt_cap raw points, per-message tables for dsc_msg_cap messages
+    void* d_dsc = nullptr;
+    size_t dsc_pt_cap = 0, dsc_msg_cap = 0;
+    void* d_dsctmp = nullptr;     // rocPRIM scan / segmented sort scratch
+    size_t dsctmp_cap = 0;
     // batch replay with a per-scan insert overlay (lk_overlay_kernels.h): the pools of all slots, grow-only
     LkOverlay ov = {};
     uint32_t ov_slots = 0;                                // slots the pools were allocated for

@@ -15,15 +15,9 @@ __device__ __forceinline__ int lk_f2ord(float f) {
 __device__ __forceinline__ float lk_ord2f(int i) { return __int_as_float(i >= 0 ? i : (i ^ 0x7fffffff)); }
 
 // mm[0..2] = min x,y,z ; mm[3..5] = max x,y,z   (order-preserving int image; init: INT_MAX / INT_MIN)
-__global__ void __launch_bounds__(256) lk_pre_minmax_kernel(const lk_point* __restrict__ pts, int n, int* mm) {
+// a 256-thread block's per-lane bounds -> one atomicMin / atomicMax per field into mm (order-free: the result does not depend on the schedule)
+__device__ __forceinline__ void lk_pre_minmax_merge(int lo[3], int hi[3], int* mm) {
     __shared__ int smin[3][4], smax[3][4];
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float4 p = reinterpret_cast<const float4*>(pts)[i];
-        const int v[3] = {lk_f2ord(p.x), lk_f2ord(p.y), lk_f2ord(p.z)};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lo[c] = min(lo[c], v[c]), hi[c] = max(hi[c], v[c]);
-    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
 #pragma unroll
@@ -40,23 +34,39 @@ __global__ void __launch_bounds__(256) lk_pre_minmax_kernel(const lk_point* __re
         atomicMax(&mm[3 + c], max(max(smax[c][0], smax[c][1]), max(smax[c][2], smax[c][3])));
     }
 }
+__global__ void __launch_bounds__(256) lk_pre_minmax_kernel(const lk_point* __restrict__ pts, int n, int* mm) {
+    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float4 p = reinterpret_cast<const float4*>(pts)[i];
+        const int v[3] = {lk_f2ord(p.x), lk_f2ord(p.y), lk_f2ord(p.z)};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lo[c] = min(lo[c], v[c]), hi[c] = max(hi[c], v[c]);
+    }
+    lk_pre_minmax_merge(lo, hi, mm);
+}
 
 // cell index idx = ijk0 + ijk1*div0 + ijk2*div0*div1 with ijk = floor(p * inv) - min_b (float arithmetic)
+__device__ __forceinline__ void lk_cell_grid(const int* __restrict__ mm, float inv, int mn[3], int dv[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mn[c] = (int)floorf(lk_ord2f(mm[c]) * inv);
+        dv[c] = (int)floorf(lk_ord2f(mm[3 + c]) * inv) - mn[c] + 1;
+    }
+}
+__device__ __forceinline__ bool lk_cell_overflow(const int dv[3]) { return (double)dv[0] * (double)dv[1] * (double)dv[2] > 2147483647.0; }
+__device__ __forceinline__ unsigned int lk_cell_key(float4 p, float inv, const int mn[3], const int dv[3]) {
+    const int i0 = (int)floorf(p.x * inv) - mn[0], i1 = (int)floorf(p.y * inv) - mn[1], i2 = (int)floorf(p.z * inv) - mn[2];
+    return (unsigned int)(i0 + i1 * dv[0] + i2 * dv[0] * dv[1]);
+}
 __global__ void __launch_bounds__(256)
     lk_pre_cellidx_kernel(const lk_point* __restrict__ pts, int n, float inv, const int* __restrict__ mm,
                           unsigned int* __restrict__ keys, int* __restrict__ vals, unsigned int* err) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int mn[3], dv[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        mn[c] = (int)floorf(lk_ord2f(mm[c]) * inv);
-        dv[c] = (int)floorf(lk_ord2f(mm[3 + c]) * inv) - mn[c] + 1;
-    }
-    if (i == 0 && (double)dv[0] * (double)dv[1] * (double)dv[2] > 2147483647.0) atomicOr(err, 1u);  // PCL refuses this too
-    const float4 p = reinterpret_cast<const float4*>(pts)[i];
-    const int i0 = (int)floorf(p.x * inv) - mn[0], i1 = (int)floorf(p.y * inv) - mn[1], i2 = (int)floorf(p.z * inv) - mn[2];
-    keys[i] = (unsigned int)(i0 + i1 * dv[0] + i2 * dv[0] * dv[1]);
+    lk_cell_grid(mm, inv, mn, dv);
+    if (i == 0 && lk_cell_overflow(dv)) atomicOr(err, 1u);  // PCL refuses this too
+    keys[i] = lk_cell_key(reinterpret_cast<const float4*>(pts)[i], inv, mn, dv);
     vals[i] = i;
 }
 
@@ -120,15 +130,43 @@ __device__ __forceinline__ double lk_ld_f64(const unsigned char* p) {
     unsigned long long u = (unsigned long long)lk_ld_u32(p) | ((unsigned long long)lk_ld_u32(p + 4) << 32);
     return __longlong_as_double((long long)u);
 }
-// per point: keep flag (every filter_num-th point outside the blind radius)
+// keep flag of point i (counted from its message's first point) at p: every filter_num-th point outside the blind radius
+__device__ __forceinline__ unsigned int lk_decode_keep(const unsigned char* p, int i, const LkDecodeArgs& a) {
+    const float x = lk_ld_f32(p + a.lay.off_x), y = lk_ld_f32(p + a.lay.off_y), z = lk_ld_f32(p + a.lay.off_z);
+    const bool blind = a.blind * a.blind > x * x + y * y + z * z;  // blindCheck, lidar_processing.h:96-98
+    return ((i % a.filter_num) || blind) ? 0u : 1u;
+}
+// curvature of the point at p and its message's first / last raw time (t0 / tl: the time fields of the first / last point), per handler
+__device__ __forceinline__ float lk_decode_time(const unsigned char* t0, const unsigned char* tl, const unsigned char* p, const LkDecodeArgs& a,
+                                                double& first_d, double& last_d) {
+    float curv;
+    if (a.lay.lidar_type == 3) {  // hesaiHandler: doubles
+        first_d = a.time_scale * lk_ld_f64(t0);
+        last_d = a.time_scale * lk_ld_f64(tl);
+        const double cur = a.time_scale * lk_ld_f64(p + a.lay.off_time);
+        curv = (float)(round((cur - first_d) * (double)500.0f) / (double)500.0f);
+    } else {
+        float first_f, last_f, cur_f;
+        if (a.lay.lidar_type == 2) {  // ousterHander: uint32 t
+            first_f = (float)(a.time_scale * (double)lk_ld_u32(t0));
+            last_f = (float)(a.time_scale * (double)lk_ld_u32(tl));
+            cur_f = (float)(a.time_scale * (double)lk_ld_u32(p + a.lay.off_time));
+        } else {  // velodyneHandler: float time
+            first_f = (float)(a.time_scale * (double)lk_ld_f32(t0));
+            last_f = (float)(a.time_scale * (double)lk_ld_f32(tl));
+            cur_f = (float)(a.time_scale * (double)lk_ld_f32(p + a.lay.off_time));
+        }
+        first_d = (double)first_f, last_d = (double)last_f;
+        curv = roundf((cur_f - first_f) * 500.0f) / 500.0f;
+    }
+    return curv;
+}
+// per point: keep flag
 __global__ void __launch_bounds__(256)
     lk_decode_flags_kernel(const unsigned char* __restrict__ data, int n, LkDecodeArgs a, unsigned int* __restrict__ flags) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const unsigned char* p = data + (size_t)i * a.lay.point_step;
-    const float x = lk_ld_f32(p + a.lay.off_x), y = lk_ld_f32(p + a.lay.off_y), z = lk_ld_f32(p + a.lay.off_z);
-    const bool blind = a.blind * a.blind > x * x + y * y + z * z;  // blindCheck, lidar_processing.h:96-98
-    flags[i] = ((i % a.filter_num) || blind) ? 0u : 1u;
+    flags[i] = lk_decode_keep(data + (size_t)i * a.lay.point_step, i, a);
 }
 // scatter the kept points in input order; time arithmetic per handler
 __global__ void __launch_bounds__(256)
@@ -140,27 +178,8 @@ __global__ void __launch_bounds__(256)
     const unsigned char* p0 = data + a.lay.off_time;
     const unsigned char* pl = data + (size_t)(n - 1) * a.lay.point_step + a.lay.off_time;
     const unsigned char* p = data + (size_t)i * a.lay.point_step;
-    float curv;
     double first_d, last_d;
-    if (a.lay.lidar_type == 3) {  // hesaiHandler: doubles
-        first_d = a.time_scale * lk_ld_f64(p0);
-        last_d = a.time_scale * lk_ld_f64(pl);
-        const double cur = a.time_scale * lk_ld_f64(p + a.lay.off_time);
-        curv = (float)(round((cur - first_d) * (double)500.0f) / (double)500.0f);
-    } else {
-        float first_f, last_f, cur_f;
-        if (a.lay.lidar_type == 2) {  // ousterHander: uint32 t
-            first_f = (float)(a.time_scale * (double)lk_ld_u32(p0));
-            last_f = (float)(a.time_scale * (double)lk_ld_u32(pl));
-            cur_f = (float)(a.time_scale * (double)lk_ld_u32(p + a.lay.off_time));
-        } else {  // velodyneHandler: float time
-            first_f = (float)(a.time_scale * (double)lk_ld_f32(p0));
-            last_f = (float)(a.time_scale * (double)lk_ld_f32(pl));
-            cur_f = (float)(a.time_scale * (double)lk_ld_f32(p + a.lay.off_time));
-        }
-        first_d = (double)first_f, last_d = (double)last_f;
-        curv = roundf((cur_f - first_f) * 500.0f) / 500.0f;
-    }
+    const float curv = lk_decode_time(p0, pl, p, a, first_d, last_d);
     if (i == 0) first_last[0] = first_d, first_last[1] = last_d;
     if (i == n - 1) *n_out = pos[i] + flags[i];
     if (flags[i]) {
@@ -171,6 +190,102 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+
+// ---------------------------------------------------------------- a run's PointCloud2 messages in one call (lk_decode_scans_dev)
+// The per-scan chain above - decode flags, compaction, scatter, then min/max, cell keys, cell sort, heads, starts, centroids, time sort,
+// gather - over all messages at once.  Message s = raw points [pt_off[s], pt_off[s+1]) of the run, its bytes at base + msg_off[s].  Every
+// per-point quantity is the per-scan kernels' own arithmetic (the helpers above) with the point index counted from its message's first
+// point; the decoded points of message s are [dec_off[s], dec_off[s+1]) and carry their message id (sid), which keeps bounds, cell keys
+// and cells inside their scan.
+__device__ __forceinline__ int lk_msg_of_point(const unsigned int* __restrict__ pt_off, int S, unsigned int i) {
+    int lo = 0, hi = S;   // pt_off[lo] <= i < pt_off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pt_off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__global__ void __launch_bounds__(256)
+    lk_dscan_flags_kernel(const unsigned char* __restrict__ base, const unsigned long long* __restrict__ msg_off, const unsigned int* __restrict__ pt_off,
+                          int S, unsigned int n, LkDecodeArgs a, unsigned int* __restrict__ flags) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int s = lk_msg_of_point(pt_off, S, i);
+    const unsigned int j = i - pt_off[s];
+    flags[i] = lk_decode_keep(base + msg_off[s] + (size_t)j * a.lay.point_step, (int)j, a);
+}
+// scatter the kept points in input order with their message id; the first point of a message also writes the message's first / last
+// raw time, its first decoded index and the initial bounds / overflow word of its scan
+__global__ void __launch_bounds__(256)
+    lk_dscan_scatter_kernel(const unsigned char* __restrict__ base, const unsigned long long* __restrict__ msg_off, const unsigned int* __restrict__ pt_off,
+                            int S, unsigned int n, LkDecodeArgs a, const unsigned int* __restrict__ flags, const unsigned int* __restrict__ pos,
+                            lk_point* __restrict__ out, unsigned int* __restrict__ sid, unsigned int* __restrict__ dec_off, double* __restrict__ first_last,
+                            int* __restrict__ mm, unsigned int* __restrict__ err) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int s = lk_msg_of_point(pt_off, S, i);
+    const unsigned int j = i - pt_off[s], m = pt_off[s + 1] - pt_off[s];
+    const unsigned char* mb = base + msg_off[s];
+    const unsigned char* p = mb + (size_t)j * a.lay.point_step;
+    double first_d, last_d;
+    const float curv = lk_decode_time(mb + a.lay.off_time, mb + (size_t)(m - 1) * a.lay.point_step + a.lay.off_time, p, a, first_d, last_d);
+    if (j == 0) {
+        first_last[2 * s] = first_d, first_last[2 * s + 1] = last_d;
+        dec_off[s] = pos[i];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) mm[6 * s + c] = 0x7fffffff, mm[6 * s + 3 + c] = (int)0x80000000;
+        err[s] = 0u;
+    }
+    if (i == n - 1) dec_off[S] = pos[i] + flags[i];
+    if (flags[i]) {
+        lk_point o;
+        o.x = lk_ld_f32(p + a.lay.off_x), o.y = lk_ld_f32(p + a.lay.off_y), o.z = lk_ld_f32(p + a.lay.off_z);
+        o.curvature = curv;
+        out[pos[i]] = o;
+        sid[pos[i]] = (unsigned int)s;
+    }
+}
+// per-scan bounds: blockIdx.x = scan, gridDim.y blocks stride over its decoded points
+__global__ void __launch_bounds__(256) lk_dscan_minmax_kernel(const lk_point* __restrict__ pts, const unsigned int* __restrict__ dec_off, int* mm) {
+    const int s = blockIdx.x;
+    const unsigned int e = dec_off[s + 1];
+    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    for (unsigned int i = dec_off[s] + blockIdx.y * 256u + threadIdx.x; i < e; i += gridDim.y * 256u) {
+        const float4 p = reinterpret_cast<const float4*>(pts)[i];
+        const int v[3] = {lk_f2ord(p.x), lk_f2ord(p.y), lk_f2ord(p.z)};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lo[c] = min(lo[c], v[c]), hi[c] = max(hi[c], v[c]);
+    }
+    lk_pre_minmax_merge(lo, hi, mm + 6 * s);
+}
+// cell keys under each scan's own bounds; the scan's first point reports its overflow
+__global__ void __launch_bounds__(256)
+    lk_dscan_cellidx_kernel(const lk_point* __restrict__ pts, unsigned int n, float inv, const int* __restrict__ mm, const unsigned int* __restrict__ sid,
+                            unsigned int* __restrict__ keys, unsigned int* __restrict__ vals, unsigned int* __restrict__ err) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const unsigned int s = sid[i];
+    int mn[3], dv[3];
+    lk_cell_grid(mm + 6 * s, inv, mn, dv);
+    if ((i == 0 || sid[i - 1] != s) && lk_cell_overflow(dv)) err[s] = 1u;
+    keys[i] = lk_cell_key(reinterpret_cast<const float4*>(pts)[i], inv, mn, dv);
+    vals[i] = i;
+}
+// lk_pre_heads_kernel with a new cell at every scan boundary as well (equal keys of two scans are two cells)
+__global__ void __launch_bounds__(256)
+    lk_dscan_heads_kernel(const unsigned int* __restrict__ keys, const unsigned int* __restrict__ sid, unsigned int n, unsigned int* __restrict__ flags) {
+    const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) flags[i] = (i == 0 || keys[i] != keys[i - 1] || sid[i] != sid[i - 1]) ? 1u : 0u;
+}
+// first cell of every scan (the rank of its first decoded point among the cell heads) and the total: the scans' CSR offsets over the cells
+__global__ void __launch_bounds__(256)
+    lk_dscan_celloff_kernel(const unsigned int* __restrict__ dec_off, const unsigned int* __restrict__ pos, const unsigned int* __restrict__ ncells, int S,
+                            unsigned int* __restrict__ cell_off) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s < S) cell_off[s] = pos[dec_off[s]];
+    else if (s == S) cell_off[S] = *ncells;
+}
 
 // ---------------------------------------------------------------- time buckets of a batch of scans, found on the device
 // KILO.cc:375-378: a bucket is a run of EXACTLY equal curvature inside a time-sorted scan.  For a batch laid out back to back

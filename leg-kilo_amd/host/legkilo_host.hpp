@@ -7,6 +7,8 @@
 //                                 bucket loop of KILO::process (KILO.cc:108-399)
 //   legkilo::Kinematics        <- legkilo/src/preprocess/kinematics.h (Kinematics::processing for a batch of serialized HighState
 //                                 messages, with kinematicImuCallBack's redundancy filter) + the kin branch of syncPackage
+//   legkilo::LidarProcessing   <- legkilo/src/preprocess/lidar_processing.h (LidarProcessing::processing for a recorded run's
+//                                 PointCloud2 messages in HBM, with the voxel grid and time sort of KILO.cc:356-370)
 //
 // Same method names, argument meaning and (void / bool) error behaviour as the reference.  Differences forced
 // by the state living in HBM: state()/cov()/Q() return COPIES (use setState/setCov/setQ to write back), and
@@ -577,6 +579,68 @@ class Kinematics {
     }
 
    private:
+    std::shared_ptr<Device> dev_;
+};
+
+// LidarProcessing::Config (lidar_processing.h) + the PointCloud2 point layout its handler reads.  processRun() is the lidar half of a recorded
+// run: the payloads of n sensor_msgs/PointCloud2 messages, already in HBM, become what lidarCallBack + LidarProcessing::processing +
+// the voxel grid and time sort of KILO.cc:356-370 make of each message - the scans stay in HBM, with the tables
+// lk_batch_replay_scans(_kin)_dev and lk_kin_split_dev take.  Refusals (lk_decode_scans_dev) throw, naming the offending message.
+class LidarProcessing {
+   public:
+    struct Config {
+        float blind_ = 1.0f;
+        int filter_num_ = 1;
+        int lidar_type_ = 1;      // common::LidarType: 1 Velodyne, 2 Ouster, 3 Hesai
+        double time_scale_ = 1.0;
+        lk_cloud_layout layout{}; // point_step and field offsets of the messages (layout.lidar_type is set from lidar_type_)
+    };
+    // the decoded scans of a run: scan s = data()[scan_off[s], scan_off[s+1]) in HBM, owned (lk_device_free on destruction)
+    class DeviceScans {
+       public:
+        DeviceScans(std::shared_ptr<Device> dev, size_t n_points) : dev_(std::move(dev)) {
+            void* p = nullptr;
+            dev_->check(lk_device_malloc(dev_->h(), &p, sizeof(lk_point) * std::max<size_t>(n_points, 1)));
+            d_ = static_cast<lk_point*>(p);
+        }
+        ~DeviceScans() {
+            if (d_) lk_device_free(dev_->h(), d_);
+        }
+        DeviceScans(DeviceScans&& o) noexcept
+            : scan_off(std::move(o.scan_off)), t_begin(std::move(o.t_begin)), t_end(std::move(o.t_end)), dev_(std::move(o.dev_)), d_(o.d_) {
+            o.d_ = nullptr;
+        }
+        DeviceScans(const DeviceScans&) = delete;
+        DeviceScans& operator=(const DeviceScans&) = delete;
+        DeviceScans& operator=(DeviceScans&&) = delete;
+        lk_point* data() const { return d_; }
+        size_t size() const { return scan_off.empty() ? 0 : scan_off.size() - 1; }
+        std::vector<uint64_t> scan_off;   // n + 1 entries, first 0
+        std::vector<double> t_begin;      // LidarScan::lidar_begin_time_
+        std::vector<double> t_end;        // LidarScan::lidar_end_time_ (syncPackage's scan end)
+
+       private:
+        std::shared_ptr<Device> dev_;
+        lk_point* d_ = nullptr;
+    };
+
+    LidarProcessing(const Config& config, std::shared_ptr<Device> dev) : cfg_(config), dev_(std::move(dev)) { cfg_.layout.lidar_type = cfg_.lidar_type_; }
+    // message s: n_points[s] points at d_msgs + msg_off[s], header stamp header_stamp[s] (non-decreasing); leaf = voxel_grid_resolution
+    DeviceScans processRun(const void* d_msgs, const std::vector<uint64_t>& msg_off, const std::vector<uint32_t>& n_points,
+                           const std::vector<double>& header_stamp, float leaf) {
+        if (msg_off.size() != n_points.size() || header_stamp.size() != n_points.size()) throw std::invalid_argument("processRun: table sizes differ");
+        size_t total = 0;
+        for (uint32_t n : n_points) total += n;
+        DeviceScans out(dev_, total);
+        const size_t n = n_points.size();
+        out.scan_off.resize(n + 1), out.t_begin.resize(n), out.t_end.resize(n);
+        dev_->check(lk_decode_scans_dev(dev_->h(), d_msgs, n, msg_off.data(), n_points.data(), header_stamp.data(), &cfg_.layout, cfg_.time_scale_,
+                                        cfg_.filter_num_, cfg_.blind_, leaf, out.data(), out.scan_off.data(), out.t_begin.data(), out.t_end.data()));
+        return out;
+    }
+
+   private:
+    Config cfg_;
     std::shared_ptr<Device> dev_;
 };
 

@@ -247,6 +247,62 @@ def preprocess_velodyne(raw, filter_num=3, blind=1.5):
     return out
 
 
+# --------------------------------------------------------------------------- sensor_msgs/PointCloud2 payloads of a recorded run
+# The point layouts the three handlers read (lidar_processing.cc:25-108; the same as oracle/preprocess_oracle.py's *_DTYPE) and their time
+# field / time_scale: Velodyne `time` f32 offset in s, Ouster `t` u32 offset in ns, Hesai `timestamp` f64 absolute in s.
+CLOUD_DTYPES = {
+    1: np.dtype({"names": ["x", "y", "z", "intensity", "time", "ring"], "formats": ["<f4", "<f4", "<f4", "<f4", "<f4", "<u2"],
+                 "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 22}),
+    2: np.dtype({"names": ["x", "y", "z", "intensity", "t", "reflectivity", "ring", "ambient", "range"],
+                 "formats": ["<f4", "<f4", "<f4", "<f4", "<u4", "<u2", "u1", "<u2", "<u4"], "offsets": [0, 4, 8, 16, 20, 24, 26, 28, 32], "itemsize": 48}),
+    3: np.dtype({"names": ["x", "y", "z", "intensity", "timestamp", "ring"], "formats": ["<f4", "<f4", "<f4", "<f4", "<f8", "<u2"],
+                 "offsets": [0, 4, 8, 16, 24, 32], "itemsize": 40}),
+}
+CLOUD_TIME_FIELD = {1: "time", 2: "t", 3: "timestamp"}
+CLOUD_TIME_SCALE = {1: 1.0, 2: 1e-9, 3: 1.0}
+
+
+def cloud_layout(lidar_type, dtype=None):
+    """The lk_cloud_layout fields (as a dict) of a point dtype (default: the handler's own)."""
+    dt = CLOUD_DTYPES[lidar_type] if dtype is None else dtype
+    f = dt.fields
+    return dict(point_step=dt.itemsize, off_x=f["x"][1], off_y=f["y"][1], off_z=f["z"][1], off_time=f[CLOUD_TIME_FIELD[lidar_type]][1],
+                lidar_type=lidar_type)
+
+
+def cloud_message(pts, lidar_type, header_stamp, seed=0):
+    """A POINT_DTYPE scan whose curvature is each point's time offset in s (vlp16_scan, ouster_scan) -> the payload of its PointCloud2
+    message in the handler's layout (CLOUD_DTYPES), stamped header_stamp.  Fields the decoder does not read hold random values."""
+    dt = CLOUD_DTYPES[lidar_type]
+    rng = np.random.default_rng(seed)
+    raw = np.frombuffer(rng.integers(0, 256, size=len(pts) * dt.itemsize, dtype=np.uint8).tobytes(), dtype=dt).copy()
+    raw["x"], raw["y"], raw["z"] = pts["x"], pts["y"], pts["z"]
+    if lidar_type == 1:
+        raw["time"] = pts["curvature"]
+    elif lidar_type == 2:
+        raw["t"] = np.round(pts["curvature"].astype(np.float64) * 1e9).astype(np.uint32)
+    else:
+        raw["timestamp"] = header_stamp + pts["curvature"].astype(np.float64)
+    return raw
+
+
+def pack_cloud_run(msgs, seed=0, max_gap=61):
+    """Lay the payloads of a run's messages (structured arrays of one point dtype) into one byte buffer the way a bag file holds them:
+    every message at an odd byte offset, random bytes of 1 .. max_gap between two messages.  Returns (buf uint8, msg_off uint64[S],
+    n_points uint32[S]) - the tables lk_decode_scans_dev takes."""
+    rng = np.random.default_rng(seed)
+    gaps = rng.integers(1, max_gap + 1, size=len(msgs))
+    msg_off, end = np.zeros(len(msgs), dtype=np.int64), 0
+    for k, m in enumerate(msgs):
+        o = end + int(gaps[k])
+        msg_off[k] = o + 1 - o % 2   # odd offsets (the first message included): no field is aligned
+        end = int(msg_off[k]) + m.nbytes
+    buf = rng.integers(0, 256, size=end + 7, dtype=np.uint8)
+    for o, m in zip(msg_off, msgs):
+        buf[o:o + m.nbytes] = np.frombuffer(np.ascontiguousarray(m).tobytes(), dtype=np.uint8)
+    return buf, msg_off.astype(np.uint64), np.array([len(m) for m in msgs], dtype=np.uint32)
+
+
 def voxel_grid_centroid(pts, leaf):
     """Centroid of all fields (x, y, z, curvature) per leaf cell — the behaviour of pcl::VoxelGrid that the
     reference relies on at KILO.cc:356-360 (it de-quantises the time stamps).  Host definition of what

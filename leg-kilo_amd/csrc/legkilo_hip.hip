@@ -56,7 +56,7 @@ static int create_pools(lk_handle* h, const lk_config* cfg) {
     if (const char* e = getenv("LEGKILO_UPDATE_CLASSIC")) h->wave_update = atoi(e) == 0;
     if (const char* e = getenv("LEGKILO_GRID")) h->grid_enable = atoi(e) != 0;
     if (const char* e = getenv("LEGKILO_BATCH_ORDER")) h->batch_order_mode = atoi(e) != 0;
-    HIPCHK(h, hipMalloc(&h->d_grid_mm, 8 * sizeof(int)));
+    HIPCHK(h, pool_alloc(h, &h->d_grid_mm, 8 * sizeof(int)));
     if (const char* e = getenv("LEGKILO_REPLAY_GROUPS")) h->replay_groups = std::min(std::max(atoi(e), 1), (int)lk_handle::kMaxGroups);
     HIPCHK(h, hipEventCreate(&h->ev0));
     HIPCHK(h, hipEventCreate(&h->ev1));
@@ -97,26 +97,26 @@ static int create_pools(lk_handle* h, const lk_config* cfg) {
     m.max_nodes = cfg->max_nodes;
     m.max_blocks = cfg->max_point_blocks;
     m.max_scan = cfg->max_scan_points;
-    HIPCHK(h, hipMalloc(&m.hash, sizeof(int4) * (size_t)h->hash_cap));
-    HIPCHK(h, hipMalloc(&m.planes, sizeof(lk_plane_rec) * (size_t)m.max_nodes));
-    HIPCHK(h, hipMalloc(&m.match, sizeof(lk_match_rec) * (size_t)m.max_nodes));
-    HIPCHK(h, hipMalloc(&m.nodes, sizeof(lk_node_rec) * (size_t)m.max_nodes));
-    HIPCHK(h, hipMalloc(&m.blocks, sizeof(lk_block_rec) * (size_t)m.max_blocks));
-    HIPCHK(h, hipMalloc(&m.counters, sizeof(unsigned int) * LK_CTR_COUNT));
-    HIPCHK(h, hipMalloc(&m.touched, sizeof(int) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&m.heavy, sizeof(int) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&m.next, sizeof(int) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&m.slots, sizeof(int) * (size_t)LK_SLOTS * (size_t)m.max_nodes));
-    HIPCHK(h, hipMalloc(&m.scratch, sizeof(int) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&m.groups, sizeof(LkGroup) * 2 * (size_t)m.max_scan));   // leaf-group descriptors, then the fallback items
-    HIPCHK(h, hipMalloc(&m.gidx, sizeof(int) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&m.free_list, sizeof(int) * (size_t)m.max_blocks));
-    HIPCHK(h, hipMalloc(&m.freed_next, sizeof(int) * (size_t)m.max_blocks));
-    HIPCHK(h, hipMalloc(&m.dirty, sizeof(unsigned int) * (size_t)m.max_nodes));
+    HIPCHK(h, pool_alloc(h, &m.hash, sizeof(int4) * (size_t)h->hash_cap));
+    HIPCHK(h, pool_alloc(h, &m.planes, sizeof(lk_plane_rec) * (size_t)m.max_nodes));
+    HIPCHK(h, pool_alloc(h, &m.match, sizeof(lk_match_rec) * (size_t)m.max_nodes));
+    HIPCHK(h, pool_alloc(h, &m.nodes, sizeof(lk_node_rec) * (size_t)m.max_nodes));
+    HIPCHK(h, pool_alloc(h, &m.blocks, sizeof(lk_block_rec) * (size_t)m.max_blocks));
+    HIPCHK(h, pool_alloc(h, &m.counters, sizeof(unsigned int) * LK_CTR_COUNT));
+    HIPCHK(h, pool_alloc(h, &m.touched, sizeof(int) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &m.heavy, sizeof(int) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &m.next, sizeof(int) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &m.slots, sizeof(int) * (size_t)LK_SLOTS * (size_t)m.max_nodes));
+    HIPCHK(h, pool_alloc(h, &m.scratch, sizeof(int) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &m.groups, sizeof(LkGroup) * 2 * (size_t)m.max_scan));   // leaf-group descriptors, then the fallback items
+    HIPCHK(h, pool_alloc(h, &m.gidx, sizeof(int) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &m.free_list, sizeof(int) * (size_t)m.max_blocks));
+    HIPCHK(h, pool_alloc(h, &m.freed_next, sizeof(int) * (size_t)m.max_blocks));
+    HIPCHK(h, pool_alloc(h, &m.dirty, sizeof(unsigned int) * (size_t)m.max_nodes));
     HIPCHK(h, hipMemsetAsync(m.dirty, 0, sizeof(unsigned int) * (size_t)m.max_nodes, h->stream));
-    HIPCHK(h, hipMalloc(&m.newroot, sizeof(unsigned int) * (size_t)(LK_NEWROOT_MASK + 1)));
+    HIPCHK(h, pool_alloc(h, &m.newroot, sizeof(unsigned int) * (size_t)(LK_NEWROOT_MASK + 1)));
     HIPCHK(h, hipMemsetAsync(m.newroot, 0, sizeof(unsigned int) * (size_t)(LK_NEWROOT_MASK + 1), h->stream));
-    HIPCHK(h, hipMalloc(&m.spec, sizeof(unsigned int) * LK_SPEC_WORDS));
+    HIPCHK(h, pool_alloc(h, &m.spec, sizeof(unsigned int) * LK_SPEC_WORDS));
     HIPCHK(h, hipMemsetAsync(m.spec, 0, sizeof(unsigned int) * LK_SPEC_WORDS, h->stream));
     m.epoch = 0;
     HIPCHK(h, hipStreamCreateWithFlags(&h->ins, hipStreamNonBlocking));
@@ -128,22 +128,22 @@ static int create_pools(lk_handle* h, const lk_config* cfg) {
     if (const char* e = getenv("LEGKILO_SPEC")) h->spec_enable = atoi(e) != 0;
     if (const char* e = getenv("LEGKILO_RESIDENT")) h->resident_enable = atoi(e) != 0;
     if (const char* e = getenv("LEGKILO_GRIDSCAN")) h->gridscan_mode = std::min(std::max(atoi(e), 0), 2);
-    HIPCHK(h, hipMalloc(&h->d_snap, sizeof(LkFilter) * 2));
+    HIPCHK(h, pool_alloc(h, &h->d_snap, sizeof(LkFilter) * 2));
     HIPCHK(h, hipMemsetAsync(h->d_snap, 0, sizeof(LkFilter) * 2, h->stream));
-    HIPCHK(h, hipMalloc(&h->d_ids, sizeof(int2) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&h->d_filters, sizeof(LkFilter) * (size_t)cfg->n_slots));
+    HIPCHK(h, pool_alloc(h, &h->d_ids, sizeof(int2) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &h->d_filters, sizeof(LkFilter) * (size_t)cfg->n_slots));
     HIPCHK(h, hipMemsetAsync(h->d_filters, 0, sizeof(LkFilter) * (size_t)cfg->n_slots, h->stream));
-    HIPCHK(h, hipMalloc(&h->d_Q, sizeof(double) * 900));
+    HIPCHK(h, pool_alloc(h, &h->d_Q, sizeof(double) * 900));
     HIPCHK(h, hipMemsetAsync(h->d_Q, 0, sizeof(double) * 900, h->stream));
     size_t nblk_max = ((size_t)m.max_scan + LK_RB - 1) / LK_RB;
     h->part_stride = nblk_max * (LK_RB / LK_WAVE) * LK_NPART;  // one partial record per wave
-    HIPCHK(h, hipMalloc(&h->d_partials, sizeof(double) * h->part_stride * cfg->n_slots));
-    HIPCHK(h, hipMalloc(&h->d_scan, sizeof(lk_point) * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&h->d_world, sizeof(float) * 4 * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&h->d_rows, sizeof(double) * 8 * (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&h->d_valid, (size_t)m.max_scan));
-    HIPCHK(h, hipMalloc(&h->d_tmp, sizeof(double) * 4096));
-    HIPCHK(h, hipMalloc(&h->d_poses, sizeof(lk_pose) * (size_t)cfg->n_slots));
+    HIPCHK(h, pool_alloc(h, &h->d_partials, sizeof(double) * h->part_stride * cfg->n_slots));
+    HIPCHK(h, pool_alloc(h, &h->d_scan, sizeof(lk_point) * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &h->d_world, sizeof(float) * 4 * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &h->d_rows, sizeof(double) * 8 * (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &h->d_valid, (size_t)m.max_scan));
+    HIPCHK(h, pool_alloc(h, &h->d_tmp, sizeof(double) * 4096));
+    HIPCHK(h, pool_alloc(h, &h->d_poses, sizeof(lk_pose) * (size_t)cfg->n_slots));
     unsigned int ninit = std::max(h->hash_cap, m.max_nodes);
     hipLaunchKernelGGL(lk_pool_init_kernel, dim3((ninit + 255) / 256), dim3(256), 0, h->stream, m, h->hash_cap);
     HIPCHK(h, hipGetLastError());
@@ -158,26 +158,15 @@ void lk_destroy(lk_handle* h) {
     if (h->ins) hipStreamSynchronize(h->ins);
     for (int i = 0; i < lk_handle::kMaxGroups - 1; ++i)   // an asynchronous batch may still be running on a side stream
         if (h->side[i]) hipStreamSynchronize(h->side[i]);
-    void* ptrs[] = {h->map.hash, h->map.planes, h->map.match, h->map.nodes, h->map.blocks, h->map.counters, h->map.touched, h->map.heavy,
-                    h->map.next, h->map.slots, h->map.scratch, h->map.groups, h->map.gidx, h->map.free_list, h->map.freed_next, h->d_filters, h->d_Q, h->d_partials, h->d_scan, h->d_world,
-                    h->d_rows, h->d_valid, h->d_tmp, h->d_poses, h->d_rag, h->d_grid_mm, h->d_ragdev, h->d_ragtmp,
-                    h->map.dirty, h->map.newroot, h->map.spec, h->d_snap, h->d_ids, h->d_fbackup, h->d_ov_priors, h->d_ov_res, h->d_query};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    void* pre[] = {h->pre_raw, h->pre_cells, h->pre_out, h->pre_k0, h->pre_k1, h->pre_flags, h->pre_pos, h->pre_misc,
-                   h->pre_v0, h->pre_v1, h->pre_starts, h->pre_tmp, h->d_dsc, h->d_dsctmp};
-    for (void* p : pre)
-        if (p) hipFree(p);
-    if (h->h_rag) hipHostFree(h->h_rag);
+    for (DevBuf* b : h->grown) buf_release(*b);
+    for (void* p : h->pools) hipFree(p);
     if (h->h_result) hipHostFree(h->h_result);
     ov_free(h);
-    kin_free(h);
     for (auto& e : h->ord) {
         if (e.copy) hipFree(e.copy);
         if (e.d_ref) hipFree(e.d_ref);
         if (e.h_seen) hipHostFree(e.h_seen);
     }
-    if (h->d_ov_status) hipFree(h->d_ov_status);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -551,6 +540,7 @@ int frozen_map(lk_handle* h, LkMap* out) {
                     HIPCHK(h, hipMemcpyAsync(bigger, h->map.match, (size_t)h->map.max_nodes * sizeof(lk_match_rec), hipMemcpyDeviceToDevice, h->stream));
                     HIPCHK(h, hipStreamSynchronize(h->stream));
                     hipFree(h->map.match);
+                    std::replace(h->pools.begin(), h->pools.end(), (void*)h->map.match, (void*)bigger);   // the handle owns the new pool instead
                     h->map.match = bigger;
                     h->grid_cap = want;
                     fm.match = bigger;
@@ -747,25 +737,23 @@ int lk_match_points(lk_handle* h, size_t n, const int32_t* keys3, const double* 
     if (n > (size_t)INT_MAX / 9) return fail(h, LK_ERR_INVALID, "lk_match_points: n too large");
     int rc = join_side_streams(h);   // the map as every earlier call on this handle left it
     if (rc) return rc;
-    // one device buffer for the inputs and outputs of a query, kept by the handle and grown on demand (a caller of the class surface may ask point by point):
-    // doubles first, then the 4-byte arrays, then the bytes
-    const size_t need = sizeof(double) * (3 + 9 + 8) * n + sizeof(int) * (3 + 1) * n + sizeof(float) * n + 2 * n;
-    if (h->query_cap < need) {
-        if (h->d_query) {
-            HIPCHK(h, hipFree(h->d_query));
-            h->d_query = nullptr, h->query_cap = 0;
-        }
-        const size_t cap = std::max(need + need / 2, (size_t)65536);
-        HIPCHK(h, lk_hip_malloc(&h->d_query, cap));
-        h->query_cap = cap;
-    }
-    double* d_pw = reinterpret_cast<double*>(h->d_query);
-    double* d_var = d_pw + 3 * n;
-    double* d_f64 = d_var + 9 * n;   // prob | normal | center | d
-    int* d_keys = reinterpret_cast<int*>(d_f64 + 8 * n);
-    int* d_layer = d_keys + 3 * n;
-    float* d_dis = reinterpret_cast<float*>(d_layer + n);
-    unsigned char* d_u8 = reinterpret_cast<unsigned char*>(d_dis + n);   // found | success
+    // one device buffer for the inputs and outputs of a query, kept by the handle and grown on demand (a caller of the class surface may ask point by point)
+    double *d_pw = nullptr, *d_var = nullptr, *d_f64 = nullptr;
+    int *d_keys = nullptr, *d_layer = nullptr;
+    float* d_dis = nullptr;
+    unsigned char* d_u8 = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        d_pw = c.take<double>(3 * n), d_var = c.take<double>(9 * n);
+        d_f64 = c.take<double>(8 * n);   // prob | normal | center | d
+        d_keys = c.take<int>(3 * n), d_layer = c.take<int>(n);
+        d_dis = c.take<float>(n);
+        d_u8 = c.take<unsigned char>(2 * n);   // found | success
+        return c.total();
+    };
+    const size_t need = carve(nullptr);
+    LKCHK(reserve(h, h->query, need, std::max(need + need / 2, (size_t)65536) - need));
+    carve(h->query.p);
     HIPCHK(h, hipMemcpyAsync(d_keys, keys3, sizeof(int) * 3 * n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_pw, pw, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_var, var9, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
@@ -1151,32 +1139,33 @@ int lk_map_import_dev(lk_handle* h, const void* d_blob, size_t bytes) {
 }
 
 // ------------------------------------------------------------------ voxel-grid centroid filter + time sort
-static int pre_reserve(lk_handle* h, size_t n) {
-    if (n <= h->pre_cap) return LK_OK;
-    void** ptrs[] = {(void**)&h->pre_raw, (void**)&h->pre_cells, (void**)&h->pre_out, (void**)&h->pre_k0, (void**)&h->pre_k1,
-                     (void**)&h->pre_flags, (void**)&h->pre_pos, (void**)&h->pre_misc, (void**)&h->pre_v0, (void**)&h->pre_v1,
-                     (void**)&h->pre_starts, (void**)&h->pre_tmp};
-    for (void** p : ptrs)
-        if (*p) hipFree(*p), *p = nullptr;
-    size_t cap = n + n / 4 + 1024;
-    HIPCHK(h, hipMalloc(&h->pre_raw, sizeof(lk_point) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_cells, sizeof(lk_point) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_out, sizeof(lk_point) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_k0, sizeof(unsigned int) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_k1, sizeof(unsigned int) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_flags, sizeof(unsigned int) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_pos, sizeof(unsigned int) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_misc, sizeof(unsigned int) * 32));
-    HIPCHK(h, hipMalloc(&h->pre_v0, sizeof(int) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_v1, sizeof(int) * cap));
-    HIPCHK(h, hipMalloc(&h->pre_starts, sizeof(int) * cap));
+namespace {
+struct PrePool {   // the per-call view of h->pre
+    lk_point *raw, *cells, *out;
+    unsigned int *k0, *k1, *flags, *pos, *misc;
+    int *v0, *v1, *starts;
+};
+// carves the arrays for P points out of `base` (nullptr: only counts) and returns the bytes they take
+size_t pre_carve(void* base, size_t P, PrePool& d) {
+    LkCarve c(base, 256);
+    d.raw = c.take<lk_point>(P), d.cells = c.take<lk_point>(P), d.out = c.take<lk_point>(P);
+    d.k0 = c.take<unsigned int>(P), d.k1 = c.take<unsigned int>(P), d.flags = c.take<unsigned int>(P), d.pos = c.take<unsigned int>(P);
+    d.misc = c.take<unsigned int>(32);
+    d.v0 = c.take<int>(P), d.v1 = c.take<int>(P), d.starts = c.take<int>(P);
+    return c.total();
+}
+}  // namespace
+// The arrays are laid out for the call's n: an entry that hands one of them to another entry (lk_preprocess_scan -> lk_preprocess_scan_dev)
+// passes the same n on, so both see the same layout.  The rocPRIM temporary storage is sized for n as well (every sort and scan of the
+// call runs over at most n elements).
+static int pre_reserve(lk_handle* h, size_t n, PrePool& d) {
+    const size_t need = pre_carve(nullptr, n, d);
+    LKCHK(reserve(h, h->pre, need, pre_carve(nullptr, n + n / 4 + 1024, d) - need));
+    pre_carve(h->pre.p, n, d);
     size_t t1 = 0, t2 = 0;
-    HIPCHK(h, lk_prim_sort_pairs(nullptr, t1, h->pre_k0, h->pre_k1, h->pre_v0, h->pre_v1, cap, 0, 32, h->stream));
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t2, h->pre_flags, h->pre_pos, cap, h->stream));
-    h->pre_tmp_bytes = std::max(t1, t2);
-    HIPCHK(h, hipMalloc(&h->pre_tmp, h->pre_tmp_bytes));
-    h->pre_cap = cap;
-    return LK_OK;
+    HIPCHK(h, lk_prim_sort_pairs(nullptr, t1, d.k0, d.k1, d.v0, d.v1, n, 0, 32, h->stream));
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t2, d.flags, d.pos, n, h->stream));
+    return reserve(h, h->prim_tmp, std::max(t1, t2));
 }
 
 // what lk_decode_scan(s)_dev refuse in a point layout (nullptr: none)
@@ -1196,19 +1185,20 @@ int lk_decode_scan_dev(lk_handle* h, const void* d_msg, size_t n_points, const l
     if (!d_msg || !layout || !d_out || !n_out || n_points == 0 || filter_num < 1 || n_points > 0x7fffffffu)
         return fail(h, LK_ERR_INVALID, "lk_decode_scan: bad argument");
     if (const char* e = cloud_layout_error(layout)) return fail(h, LK_ERR_INVALID, e);
-    int rc = pre_reserve(h, n_points);
+    PrePool d;
+    int rc = pre_reserve(h, n_points, d);
     if (rc) return rc;
     LkDecodeArgs a;
     a.lay = *layout, a.time_scale = time_scale, a.filter_num = filter_num, a.blind = blind;
     const int n = (int)n_points, nb = (n + 255) / 256;
-    unsigned int* n_out_d = h->pre_misc + 7;
-    double* fl = reinterpret_cast<double*>(h->pre_misc + 8);
+    unsigned int* n_out_d = d.misc + 7;
+    double* fl = reinterpret_cast<double*>(d.misc + 8);
     LAUNCH(h, "decode_flags", hipLaunchKernelGGL(lk_decode_flags_kernel, dim3(nb), dim3(256), 0, h->stream,
-                                                 (const unsigned char*)d_msg, n, a, h->pre_flags));
-    size_t tb = h->pre_tmp_bytes;
-    HIPCHK(h, lk_prim_exclusive_scan(h->pre_tmp, tb, h->pre_flags, h->pre_pos, n_points, h->stream));
+                                                 (const unsigned char*)d_msg, n, a, d.flags));
+    size_t tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, n_points, h->stream));
     LAUNCH(h, "decode_scatter", hipLaunchKernelGGL(lk_decode_scatter_kernel, dim3(nb), dim3(256), 0, h->stream,
-                                                   (const unsigned char*)d_msg, n, a, h->pre_flags, h->pre_pos, d_out, n_out_d, fl));
+                                                   (const unsigned char*)d_msg, n, a, d.flags, d.pos, d_out, n_out_d, fl));
     unsigned int cnt = 0;
     double tfl[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(&cnt, n_out_d, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
@@ -1228,12 +1218,13 @@ int lk_decode_scan(lk_handle* h, const void* msg, size_t n_points, const lk_clou
     void* d_msg = nullptr;
     const size_t bytes = n_points * (size_t)layout->point_step;
     HIPCHK(h, hipMalloc(&d_msg, bytes));
-    int rc = pre_reserve(h, n_points);
+    PrePool d;
+    int rc = pre_reserve(h, n_points, d);
     if (rc == LK_OK) {
         hipMemcpyAsync(d_msg, msg, bytes, hipMemcpyHostToDevice, h->stream);
-        rc = lk_decode_scan_dev(h, d_msg, n_points, layout, time_scale, filter_num, blind, header_stamp, h->pre_out, n_out, begin_time, end_time);
+        rc = lk_decode_scan_dev(h, d_msg, n_points, layout, time_scale, filter_num, blind, header_stamp, d.out, n_out, begin_time, end_time);
         if (rc == LK_OK) {
-            hipMemcpyAsync(out, h->pre_out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream);
+            hipMemcpyAsync(out, d.out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream);
             hipStreamSynchronize(h->stream);
         }
     }
@@ -1245,37 +1236,38 @@ int lk_preprocess_scan_dev(lk_handle* h, const lk_point* d_raw, size_t n_raw, fl
     CHECK_H(h);
     if (!d_raw || !d_out || !n_out || n_raw == 0 || !(leaf > 0.f)) return fail(h, LK_ERR_INVALID, "lk_preprocess_scan: bad argument");
     if (n_raw > 0x7fffffffu) return fail(h, LK_ERR_INVALID, "too many points");
-    int rc = pre_reserve(h, n_raw);
+    PrePool d;
+    int rc = pre_reserve(h, n_raw, d);
     if (rc) return rc;
     const int n = (int)n_raw;
     const int nb = (n + 255) / 256;
     const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
-    int* mm = reinterpret_cast<int*>(h->pre_misc);
+    int* mm = reinterpret_cast<int*>(d.misc);
     const int init[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0, 0};
     HIPCHK(h, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-    unsigned int* err = h->pre_misc + 6;
-    unsigned int* ncells_d = h->pre_misc + 7;
+    unsigned int* err = d.misc + 6;
+    unsigned int* ncells_d = d.misc + 7;
     LAUNCH(h, "pre_minmax", hipLaunchKernelGGL(lk_pre_minmax_kernel, dim3(std::min(nb, 1024)), dim3(256), 0, h->stream, d_raw, n, mm));
-    LAUNCH(h, "pre_cellidx", hipLaunchKernelGGL(lk_pre_cellidx_kernel, dim3(nb), dim3(256), 0, h->stream, d_raw, n, inv, mm, h->pre_k0,
-                                                h->pre_v0, err));
-    size_t tb = h->pre_tmp_bytes;
-    HIPCHK(h, lk_prim_sort_pairs(h->pre_tmp, tb, h->pre_k0, h->pre_k1, h->pre_v0, h->pre_v1, n_raw, 0, 32, h->stream));
-    LAUNCH(h, "pre_heads", hipLaunchKernelGGL(lk_pre_heads_kernel, dim3(nb), dim3(256), 0, h->stream, h->pre_k1, n, h->pre_flags));
-    tb = h->pre_tmp_bytes;
-    HIPCHK(h, lk_prim_exclusive_scan(h->pre_tmp, tb, h->pre_flags, h->pre_pos, n_raw, h->stream));
-    LAUNCH(h, "pre_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(nb), dim3(256), 0, h->stream, h->pre_flags, h->pre_pos, n,
-                                               h->pre_starts, ncells_d));
-    LAUNCH(h, "pre_centroid", hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(nb), dim3(256), 0, h->stream, d_raw, h->pre_v1,
-                                                 h->pre_starts, ncells_d, n, h->pre_cells, h->pre_k0, h->pre_v0));
+    LAUNCH(h, "pre_cellidx", hipLaunchKernelGGL(lk_pre_cellidx_kernel, dim3(nb), dim3(256), 0, h->stream, d_raw, n, inv, mm, d.k0,
+                                                d.v0, err));
+    size_t tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, n_raw, 0, 32, h->stream));
+    LAUNCH(h, "pre_heads", hipLaunchKernelGGL(lk_pre_heads_kernel, dim3(nb), dim3(256), 0, h->stream, d.k1, n, d.flags));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, n_raw, h->stream));
+    LAUNCH(h, "pre_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(nb), dim3(256), 0, h->stream, d.flags, d.pos, n,
+                                               d.starts, ncells_d));
+    LAUNCH(h, "pre_centroid", hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(nb), dim3(256), 0, h->stream, d_raw, d.v1,
+                                                 d.starts, ncells_d, n, d.cells, d.k0, d.v0));
     unsigned int host_misc[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(host_misc, err, sizeof(host_misc), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (host_misc[0]) return fail(h, LK_ERR_INVALID, "voxel grid leaf too small for the cloud extent (index overflow)");
     const size_t nc = host_misc[1];
-    tb = h->pre_tmp_bytes;
-    HIPCHK(h, lk_prim_sort_pairs(h->pre_tmp, tb, h->pre_k0, h->pre_k1, h->pre_v0, h->pre_v1, nc, 0, 32, h->stream));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, nc, 0, 32, h->stream));
     LAUNCH(h, "pre_gather", hipLaunchKernelGGL(lk_pre_gather_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream,
-                                               h->pre_cells, h->pre_v1, (int)nc, d_out));
+                                               d.cells, d.v1, (int)nc, d_out));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_out = nc;
     return LK_OK;
@@ -1286,59 +1278,40 @@ int lk_preprocess_scan_dev(lk_handle* h, const lk_point* d_raw, size_t n_raw, fl
 // after the centroids (per-scan overflow words and cell offsets) and at the end.  Both sorts are rocPRIM's stable segmented radix sort with one
 // segment per scan, so ties keep the order the per-scan chain's global sorts keep.
 namespace {
-struct DscPool {   // the per-call view of h->d_dsc
+struct DscPool {   // the per-call view of h->dsc
     unsigned int *flags, *pos, *sid, *k0, *k1, *v0, *v1;
     int* starts;
     lk_point *dec, *cells;
     unsigned long long* msg_off;
-    unsigned int *pt_off, *dec_off, *cell_off, *err, *misc;   // cell_off [S + 1] and err [S] of the call adjacent: one read-back
+    unsigned int *pt_off, *dec_off, *cell_off, *err, *misc;
     int* mm;
     double* first_last;
 };
-// carves the arrays out of `base` (nullptr: only counts) and returns the bytes they take
+// carves the arrays for P raw points of S messages out of `base` (nullptr: only counts) and returns the bytes they take
 size_t dsc_carve(void* base, size_t P, size_t S, DscPool& d) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* r = base ? static_cast<char*>(base) + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return r;
-    };
-    d.flags = (unsigned int*)take(4 * P), d.pos = (unsigned int*)take(4 * P), d.sid = (unsigned int*)take(4 * P);
-    d.k0 = (unsigned int*)take(4 * P), d.k1 = (unsigned int*)take(4 * P), d.v0 = (unsigned int*)take(4 * P), d.v1 = (unsigned int*)take(4 * P);
-    d.starts = (int*)take(4 * P);
-    d.dec = (lk_point*)take(sizeof(lk_point) * P), d.cells = (lk_point*)take(sizeof(lk_point) * P);
-    d.msg_off = (unsigned long long*)take(8 * S);
-    d.pt_off = (unsigned int*)take(4 * (S + 1)), d.dec_off = (unsigned int*)take(4 * (S + 1));
-    d.cell_off = (unsigned int*)take(4 * (2 * S + 1)), d.err = nullptr;   // err: set per call, right behind the call's S + 1 offsets
-    d.misc = (unsigned int*)take(4 * 8);
-    d.mm = (int*)take(4 * 6 * S);
-    d.first_last = (double*)take(8 * 2 * S);
-    return off;
+    LkCarve c(base, 256);
+    d.flags = c.take<unsigned int>(P), d.pos = c.take<unsigned int>(P), d.sid = c.take<unsigned int>(P);
+    d.k0 = c.take<unsigned int>(P), d.k1 = c.take<unsigned int>(P), d.v0 = c.take<unsigned int>(P), d.v1 = c.take<unsigned int>(P);
+    d.starts = c.take<int>(P);
+    d.dec = c.take<lk_point>(P), d.cells = c.take<lk_point>(P);
+    d.msg_off = c.take<unsigned long long>(S);
+    d.pt_off = c.take<unsigned int>(S + 1), d.dec_off = c.take<unsigned int>(S + 1);
+    d.cell_off = c.take<unsigned int>(2 * S + 1), d.err = d.cell_off ? d.cell_off + S + 1 : nullptr;   // cell_off [S + 1] | err [S] taken as ONE array: they are read back with one copy
+    d.misc = c.take<unsigned int>(8);
+    d.mm = c.take<int>(6 * S);
+    d.first_last = c.take<double>(2 * S);
+    return c.total();
 }
 }  // namespace
 
 static int dsc_reserve(lk_handle* h, size_t P, size_t S, DscPool& d) {
-    if (P > h->dsc_pt_cap || S > h->dsc_msg_cap) {
-        if (h->d_dsc) hipFree(h->d_dsc), h->d_dsc = nullptr;
-        const size_t pc = std::max(P, h->dsc_pt_cap), sc = std::max(S, h->dsc_msg_cap);
-        h->dsc_pt_cap = h->dsc_msg_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_dsc, dsc_carve(nullptr, pc, sc, d)));
-        h->dsc_pt_cap = pc, h->dsc_msg_cap = sc;
-    }
-    dsc_carve(h->d_dsc, h->dsc_pt_cap, h->dsc_msg_cap, d);
-    d.err = d.cell_off + S + 1;
+    LKCHK(reserve(h, h->dsc, dsc_carve(nullptr, P, S, d)));
+    dsc_carve(h->dsc.p, P, S, d);
     size_t t1 = 0, t2 = 0;
     HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, d.flags, d.pos, P, h->stream));
     HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)P, (unsigned int)S, d.dec_off, d.dec_off + 1, 0, 32,
                                            h->stream));
-    const size_t need = std::max(t1, t2);
-    if (need > h->dsctmp_cap) {
-        if (h->d_dsctmp) hipFree(h->d_dsctmp), h->d_dsctmp = nullptr;
-        h->dsctmp_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_dsctmp, need));
-        h->dsctmp_cap = need;
-    }
-    return LK_OK;
+    return reserve(h, h->prim_tmp, std::max(t1, t2));
 }
 
 int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const uint64_t* msg_off, const uint32_t* n_points,
@@ -1374,8 +1347,8 @@ int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const u
     HIPCHK(h, hipMemcpyAsync(d.pt_off, pt_off.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
     // 1. decode: keep flags, compaction, scatter
     LAUNCH(h, "dscan_flags", hipLaunchKernelGGL(lk_dscan_flags_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a, d.flags));
-    size_t tb = h->dsctmp_cap;
-    HIPCHK(h, lk_prim_exclusive_scan(h->d_dsctmp, tb, d.flags, d.pos, P, h->stream));
+    size_t tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, P, h->stream));
     LAUNCH(h, "dscan_scatter", hipLaunchKernelGGL(lk_dscan_scatter_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a,
                                                   d.flags, d.pos, d.dec, d.sid, d.dec_off, d.first_last, d.mm, d.err));
     std::vector<unsigned int> dec_off(S + 1);
@@ -1393,11 +1366,11 @@ int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const u
     LAUNCH(h, "dscan_minmax", hipLaunchKernelGGL(lk_dscan_minmax_kernel, dim3(Si, gy), dim3(256), 0, h->stream, d.dec, d.dec_off, d.mm));
     LAUNCH(h, "dscan_cellidx", hipLaunchKernelGGL(lk_dscan_cellidx_kernel, dim3(db), dim3(256), 0, h->stream, d.dec, D, inv, d.mm, d.sid, d.k0, d.v0,
                                                   d.err));
-    tb = h->dsctmp_cap;
-    HIPCHK(h, lk_prim_segmented_sort_pairs(h->d_dsctmp, tb, d.k0, d.k1, d.v0, d.v1, D, Si, d.dec_off, d.dec_off + 1, 0, 32, h->stream));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, D, Si, d.dec_off, d.dec_off + 1, 0, 32, h->stream));
     LAUNCH(h, "dscan_heads", hipLaunchKernelGGL(lk_dscan_heads_kernel, dim3(db), dim3(256), 0, h->stream, d.k1, d.sid, D, d.flags));
-    tb = h->dsctmp_cap;
-    HIPCHK(h, lk_prim_exclusive_scan(h->d_dsctmp, tb, d.flags, d.pos, D, h->stream));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, D, h->stream));
     unsigned int* ncells_d = d.misc;
     LAUNCH(h, "dscan_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(db), dim3(256), 0, h->stream, d.flags, d.pos, (int)D, d.starts, ncells_d));
     LAUNCH(h, "dscan_centroid", hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(db), dim3(256), 0, h->stream, d.dec, (const int*)d.v1, d.starts, ncells_d,
@@ -1413,8 +1386,8 @@ int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const u
                                                ": voxel grid leaf too small for the cloud extent (index overflow)");
     const unsigned int Cn = ce[S];
     // 3. time sort inside each scan's cells, gather into the caller's buffer
-    tb = h->dsctmp_cap;
-    HIPCHK(h, lk_prim_segmented_sort_pairs(h->d_dsctmp, tb, d.k0, d.k1, d.v0, d.v1, Cn, Si, d.cell_off, d.cell_off + 1, 0, 32, h->stream));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, Cn, Si, d.cell_off, d.cell_off + 1, 0, 32, h->stream));
     LAUNCH(h, "dscan_gather", hipLaunchKernelGGL(lk_pre_gather_kernel, dim3((Cn + 255) / 256), dim3(256), 0, h->stream, d.cells, (const int*)d.v1, (int)Cn,
                                                d_out));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1430,12 +1403,13 @@ int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const u
 int lk_preprocess_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float leaf, lk_point* out_sorted, size_t* n_out) {
     CHECK_H(h);
     if (!raw || !out_sorted || n_raw == 0) return fail(h, LK_ERR_INVALID, "lk_preprocess_scan: bad argument");
-    int rc = pre_reserve(h, n_raw);
+    PrePool d;
+    int rc = pre_reserve(h, n_raw, d);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->pre_raw, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
-    rc = lk_preprocess_scan_dev(h, h->pre_raw, n_raw, leaf, h->pre_out, n_out);
+    HIPCHK(h, hipMemcpyAsync(d.raw, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
+    rc = lk_preprocess_scan_dev(h, d.raw, n_raw, leaf, d.out, n_out);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(out_sorted, h->pre_out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_sorted, d.out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return LK_OK;
 }
@@ -1445,18 +1419,19 @@ int lk_process_raw_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float l
     CHECK_H(h);
     if (!raw || n_raw == 0) return fail(h, LK_ERR_INVALID, "empty scan");
     if (n_imu && n_kin) return fail(h, LK_ERR_INVALID, "pass either IMU or kin+IMU messages, not both");
-    int rc = pre_reserve(h, n_raw);
+    PrePool d;
+    int rc = pre_reserve(h, n_raw, d);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->pre_raw, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d.raw, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
     size_t nd = 0;
-    rc = lk_preprocess_scan_dev(h, h->pre_raw, n_raw, leaf, h->pre_out, &nd);
+    rc = lk_preprocess_scan_dev(h, d.raw, n_raw, leaf, d.out, &nd);
     if (rc) return rc;
     if (nd > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "downsampled scan exceeds max_scan_points");
     std::vector<lk_point> sorted(nd);
-    HIPCHK(h, hipMemcpyAsync(sorted.data(), h->pre_out, sizeof(lk_point) * nd, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(sorted.data(), d.out, sizeof(lk_point) * nd, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (n_down) *n_down = nd;
-    return run_scan(h, sorted.data(), h->pre_out, nd, t_begin, imus, n_imu, kins, n_kin, nullptr, out);
+    return run_scan(h, sorted.data(), d.out, nd, t_begin, imus, n_imu, kins, n_kin, nullptr, out);
 }
 
 // ------------------------------------------------------------------ batch replay against the frozen map
@@ -2001,38 +1976,37 @@ int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uin
     // every check comes before the first memset / upload / launch: a refused call leaves the filter slots untouched
     if (n_imu && biggest_bucket > (uint32_t)LK_SCAN_WAVE_MAX && !with_insert)   // (the batch with insert runs bucket by bucket: lk_rag_advance_kernel takes the messages at any bucket size)
         return fail(h, LK_ERR_INVALID, "IMU / kinematic messages between buckets are only replayed for scans whose buckets hold <= 512 points");
-    // tables: pt_off [S][ldb+1] u64 | t [S][ldb] f64 | t_begin [S] f64 | nb [S] u32, staged in pinned host memory
     size_t n_imu_total = 0;
     if (n_imu)
         for (size_t s = 0; s < S; ++s) n_imu_total += n_imu[s];
     if (n_imu_total && !imus) return fail(h, LK_ERR_INVALID, "null message array");
-    // ... | imu [n][7] f64 | nb [S] u32 | imu_off [S+1] u32
-    const size_t o_po = 0, o_t = o_po + 8 * S * (ldb + 1), o_tb = o_t + 8 * S * ldb, o_im = o_tb + 8 * S, o_nb = o_im + msg_bytes * n_imu_total,
-                 o_io = o_nb + 4 * S, bytes = o_io + 4 * (S + 1);
-    if (bytes > h->rag_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->d_rag) hipFree(h->d_rag), h->d_rag = nullptr;
-        if (h->h_rag) hipHostFree(h->h_rag), h->h_rag = nullptr;
-        h->rag_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_rag, bytes + bytes / 2));
-        HIPCHK(h, hipHostMalloc(&h->h_rag, bytes + bytes / 2, hipHostMallocDefault));
-        h->rag_cap = bytes + bytes / 2;
-    } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));  // a previous call's upload from the staging buffer has completed
-    }
-    unsigned char* stage = static_cast<unsigned char*>(h->h_rag);
-    auto* hpo = reinterpret_cast<unsigned long long*>(stage + o_po);
-    auto* ht = reinterpret_cast<double*>(stage + o_t);
-    auto* htb = reinterpret_cast<double*>(stage + o_tb);
-    auto* hnb = reinterpret_cast<unsigned int*>(stage + o_nb);
+    struct Tables {   // staged in pinned host memory, uploaded in one copy
+        unsigned long long* po;   // [S][ldb+1]
+        double *t, *tb;           // [S][ldb], [S]
+        unsigned char* im;        // the messages
+        unsigned int *nb, *io;    // [S], [S+1]
+        size_t bytes;
+    };
+    auto tables = [&](void* base) {   // one description: counted, then laid over the staging copy and over the device copy
+        LkCarve c(base);
+        Tables r;
+        r.po = c.take<unsigned long long>(S * (ldb + 1)), r.t = c.take<double>(S * ldb), r.tb = c.take<double>(S);
+        r.im = c.take<unsigned char>(msg_bytes * n_imu_total);
+        r.nb = c.take<unsigned int>(S), r.io = c.take<unsigned int>(S + 1);
+        r.bytes = c.total();
+        return r;
+    };
+    const size_t bytes = tables(nullptr).bytes;
+    LKCHK(rag_reserve(h, bytes));   // (synchronises: the previous call's upload from the staging buffer has completed)
+    const Tables hs = tables(h->rag_stage.p), dv = tables(h->rag.p);
     std::vector<int> max_n(ldb, 0);
     row_o = 0, row_t = 0;
     for (size_t s = 0; s < S; ++s) {   // pass 2: fill
         const uint32_t* bo = bucket_off + row_o;
         const double* bd = bucket_dt + row_t;
         const size_t nbs = n_buckets[s];
-        unsigned long long* po = hpo + s * (ldb + 1);
-        double* tr = ht + s * ldb;
+        unsigned long long* po = hs.po + s * (ldb + 1);
+        double* tr = hs.t + s * ldb;
         size_t k = 0;
         for (size_t b = 0; b < nbs; ++b) {
             if (bo[b + 1] == bo[b]) continue;
@@ -2043,25 +2017,23 @@ int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uin
         }
         for (size_t b = k; b <= ldb; ++b) po[b] = scan_off[s + 1];
         for (size_t b = k; b < ldb; ++b) tr[b] = 0.0;
-        htb[s] = t_begin[s];
-        hnb[s] = cnt[s];
+        hs.tb[s] = t_begin[s];
+        hs.nb[s] = cnt[s];
         row_o += nbs + 1, row_t += nbs;
     }
     if (n_imu) {
-        if (n_imu_total) memcpy(stage + o_im, imus, msg_bytes * n_imu_total);
-        auto* hio = reinterpret_cast<unsigned int*>(stage + o_io);
-        hio[0] = 0;
-        for (size_t s = 0; s < S; ++s) hio[s + 1] = hio[s] + n_imu[s];
+        if (n_imu_total) memcpy(hs.im, imus, msg_bytes * n_imu_total);
+        hs.io[0] = 0;
+        for (size_t s = 0; s < S; ++s) hs.io[s + 1] = hs.io[s] + n_imu[s];
     }
-    HIPCHK(h, hipMemcpyAsync(h->d_rag, stage, bytes, hipMemcpyHostToDevice, h->stream));
-    unsigned char* dr = static_cast<unsigned char*>(h->d_rag);
+    HIPCHK(h, hipMemcpyAsync(h->rag.p, h->rag_stage.p, bytes, hipMemcpyHostToDevice, h->stream));
     LkRagged rg;
-    rg.pt_off = reinterpret_cast<const unsigned long long*>(dr + o_po);
-    rg.t = reinterpret_cast<const double*>(dr + o_t);
-    rg.nb = reinterpret_cast<const unsigned int*>(dr + o_nb);
+    rg.pt_off = dv.po;
+    rg.t = dv.t;
+    rg.nb = dv.nb;
     rg.ldb = (int)ldb;
-    rg.imu_off = n_imu ? reinterpret_cast<const unsigned int*>(dr + o_io) : nullptr;
-    rg.imu = reinterpret_cast<const double*>(dr + o_im);
+    rg.imu_off = n_imu ? dv.io : nullptr;
+    rg.imu = reinterpret_cast<const double*>(dv.im);
     rg.msg_stride = (int)(msg_bytes / sizeof(double));
     rg.kin_noise = h->cfg.kin_meas_noise;
     rg.q_diag = h->q_diag ? 1 : 0;
@@ -2071,10 +2043,10 @@ int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uin
     if (with_insert) {
         size_t max_scan_pts = 0;
         for (size_t s = 0; s < S; ++s) max_scan_pts = std::max(max_scan_pts, (size_t)(scan_off[s + 1] - scan_off[s]));
-        return overlay_ragged_launch(h, d_pts, S, rg, reinterpret_cast<const double*>(dr + o_tb), (int)biggest_bucket, ldb, max_n.data(), max_scan_pts,
+        return overlay_ragged_launch(h, d_pts, S, rg, dv.tb, (int)biggest_bucket, ldb, max_n.data(), max_scan_pts,
                                      n_imu ? (msg_bytes == sizeof(lk_kin_imu) ? 2 : 1) : 0, out);
     }
-    return ragged_launch(h, d_pts, S, rg, reinterpret_cast<const double*>(dr + o_tb), (int)biggest_bucket, ldb, max_n.data(),
+    return ragged_launch(h, d_pts, S, rg, dv.tb, (int)biggest_bucket, ldb, max_n.data(),
                          n_imu ? (msg_bytes == sizeof(lk_kin_imu) ? 2 : 1) : 0, out);
 }
 
@@ -2139,27 +2111,24 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     if (msg_kind)
         for (size_t s = 0; s < S; ++s) n_msg_total += n_msg[s];
     if (n_msg_total && !msgs) return fail(h, LK_ERR_INVALID, "null message array");
-    // device layout: scan_off u64[S+1] | t_begin f64[S] | pt_start u64[n+1] | tb f64[n] | msgs | flag u32[n] | rank u32[n] | bstart u32[S+1]
-    //                | msg_off u32[S+1] | stats u32[4]
-    const size_t o_so = 0, o_tb0 = o_so + 8 * (S + 1), o_ps = o_tb0 + 8 * S, o_tb = o_ps + 8 * (n + 1), o_ms = o_tb + 8 * n,
-                 o_fl = o_ms + ((msg_bytes * n_msg_total + 7) & ~(size_t)7), o_rk = o_fl + 4 * n, o_bs = o_rk + 4 * n, o_mo = o_bs + 4 * (S + 1),
-                 o_st = o_mo + 4 * (S + 1), bytes = o_st + 16;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (bytes > h->ragdev_cap) {
-        if (h->d_ragdev) hipFree(h->d_ragdev), h->d_ragdev = nullptr, h->ragdev_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_ragdev, bytes + bytes / 4));
-        h->ragdev_cap = bytes + bytes / 4;
-    }
-    unsigned char* d = static_cast<unsigned char*>(h->d_ragdev);
-    auto* d_so = reinterpret_cast<unsigned long long*>(d + o_so);
-    auto* d_t0 = reinterpret_cast<double*>(d + o_tb0);
-    auto* d_ps = reinterpret_cast<unsigned long long*>(d + o_ps);
-    auto* d_tb = reinterpret_cast<double*>(d + o_tb);
-    auto* d_fl = reinterpret_cast<unsigned int*>(d + o_fl);
-    auto* d_rk = reinterpret_cast<unsigned int*>(d + o_rk);
-    auto* d_bs = reinterpret_cast<unsigned int*>(d + o_bs);
-    auto* d_mo = reinterpret_cast<unsigned int*>(d + o_mo);
-    auto* d_st = reinterpret_cast<unsigned int*>(d + o_st);
+    unsigned long long *d_so = nullptr, *d_ps = nullptr;
+    double *d_t0 = nullptr, *d_tb = nullptr;
+    unsigned char* d_ms = nullptr;
+    unsigned int *d_fl = nullptr, *d_rk = nullptr, *d_bs = nullptr, *d_mo = nullptr, *d_st = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        d_so = c.take<unsigned long long>(S + 1), d_t0 = c.take<double>(S);       // scan_off, t_begin
+        d_ps = c.take<unsigned long long>(n + 1), d_tb = c.take<double>(n);       // CSR tables: first point and time of every bucket
+        d_ms = c.take<unsigned char>(msg_bytes * n_msg_total);                    // the messages
+        d_fl = c.take<unsigned int>(n), d_rk = c.take<unsigned int>(n);           // bucket-start flags, their ranks
+        d_bs = c.take<unsigned int>(S + 1), d_mo = c.take<unsigned int>(S + 1);   // first bucket / first message of every scan
+        d_st = c.take<unsigned int>(4);                                           // stats
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->ragdev, bytes, bytes / 4));
+    carve(h->ragdev.p);
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "scan offsets are 64-bit");
     HIPCHK(h, hipMemcpyAsync(d_so, scan_off, 8 * (S + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_t0, t_begin, 8 * S, hipMemcpyHostToDevice, h->stream));
@@ -2169,20 +2138,15 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
         for (size_t s = 0; s < S; ++s) moff[s + 1] = moff[s] + n_msg[s];
         HIPCHK(h, hipMemcpyAsync(d_mo, moff.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
         if (n_msg_total)
-            HIPCHK(h, hipMemcpyAsync(d + o_ms, msgs, msg_bytes * n_msg_total, msgs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(d_ms, msgs, msg_bytes * n_msg_total, msgs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, hipMemsetAsync(d_st, 0, 16, h->stream));
     const unsigned int nblk = (unsigned int)((n + 255) / 256);
     hipLaunchKernelGGL(lk_rag_flag_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_st);
     size_t tmp_bytes = 0;
     HIPCHK(h, lk_prim_exclusive_scan(nullptr, tmp_bytes, d_fl, d_rk, n, h->stream));
-    if (tmp_bytes > h->ragtmp_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->d_ragtmp) hipFree(h->d_ragtmp), h->d_ragtmp = nullptr, h->ragtmp_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_ragtmp, tmp_bytes));
-        h->ragtmp_cap = tmp_bytes;
-    }
-    HIPCHK(h, lk_prim_exclusive_scan(h->d_ragtmp, tmp_bytes, d_fl, d_rk, n, h->stream));
+    LKCHK(reserve(h, h->prim_tmp, tmp_bytes));
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tmp_bytes, d_fl, d_rk, n, h->stream));
     hipLaunchKernelGGL(lk_rag_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_rk, d_t0,
                        d_ps, d_tb, d_bs, d_st);
     hipLaunchKernelGGL(lk_rag_stats_kernel, dim3(nblk), dim3(256), 0, h->stream, d_ps, d_bs, (int)S, d_st);
@@ -2202,7 +2166,7 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     rg.ldb = (int)most;
     rg.bstart = d_bs;
     rg.imu_off = msg_kind ? d_mo : nullptr;
-    rg.imu = reinterpret_cast<const double*>(d + o_ms);
+    rg.imu = reinterpret_cast<const double*>(d_ms);
     rg.msg_stride = (int)(msg_bytes / sizeof(double));
     rg.kin_noise = h->cfg.kin_meas_noise;
     rg.q_diag = h->q_diag ? 1 : 0;

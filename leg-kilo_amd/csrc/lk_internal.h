@@ -1,5 +1,5 @@
 // lk_internal.h - what the translation units of liblegkilo_hip.so share: the handle, the error / launch / allocation helpers, and the kernel
-// headers.  Round 6: the library is five units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
+// headers.  The library is six units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
 // kernel but the overlay's and the stream path's own), lk_stream.hip (LK_TU_STREAM: one live scan after the other with the map insert - the per-bucket
 // launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries that run them), lk_overlay.hip (LK_TU_OVERLAY: batch replay
 // WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_kin.hip (LK_TU_KIN: the leg kinematics front end - HighState decode, contact detector, scan split - and its entries, lk_kin_kernels.h), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+#include "lk_carve.h"  // one buffer carved into typed arrays
 #include "lk_prim.h"   // rocPRIM's sorts and scans, instantiated in lk_prim.hip
 
 #include "lk_device.h"
@@ -49,6 +50,15 @@ static_assert(sizeof(lk_point) == 16, "scan point must be 16 B");
 struct ProfEntry {
     uint64_t launches = 0;
     double total_ms = 0.0;
+};
+
+// Device memory that belongs to the handle, grows on demand and never shrinks (reserve() below; `pinned`: page-locked host memory instead).
+// A new scratch buffer is one DevBuf member of lk_handle and one reserve() where it is used: lk_destroy frees whatever was reserved.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;        // bytes
+    bool pinned = false;
+    bool listed = false;   // in lk_handle::grown
 };
 
 struct lk_handle {
@@ -74,13 +84,12 @@ struct lk_handle {
     unsigned char* d_valid = nullptr;
     double* d_tmp = nullptr;   // small scratch for class-surface calls (>= 18*32 doubles + 900*2)
     lk_pose* d_poses = nullptr;
-    void* d_ragdev = nullptr;     // lk_batch_replay_scans_dev: flags, ranks, CSR tables, messages (grow-only)
-    size_t ragdev_cap = 0;
-    void* d_ragtmp = nullptr;     // rocPRIM scan scratch
-    size_t ragtmp_cap = 0;
-    void* d_rag = nullptr;        // tables of lk_batch_replay_ragged_dev (device copy, pinned staging copy)
-    void* h_rag = nullptr;
-    size_t rag_cap = 0;
+    // what lk_destroy frees: the fixed pools as pool_alloc handed them out, the grow-only buffers that reserve() has allocated
+    std::vector<void*> pools;
+    std::vector<DevBuf*> grown;
+    DevBuf prim_tmp;              // temporary storage of every rocPRIM call (all of them run on `stream`)
+    DevBuf ragdev;                // lk_batch_replay_scans_dev: flags, ranks, CSR tables, messages
+    DevBuf rag, rag_stage{nullptr, 0, true};   // tables of lk_batch_replay_ragged_dev and of the resident stream kernels: device copy, pinned staging copy (rag_reserve)
     // pipelined stream path ("spec"): the insert of bucket k on its own stream beside predict + residual of bucket k+1 (enqueue_bucket)
     hipStream_t ins = nullptr;
     hipEvent_t ev_U[2] = {}, ev_D[2] = {}, ev_I = nullptr;
@@ -118,17 +127,8 @@ struct lk_handle {
     uint64_t ov_gen = 0;       // the snapshot the last overlay replay ran against (lk_overlay_export reads base blocks / planes of THAT map)
     bool grid_enable = true;   // LEGKILO_GRID=0 keeps batch replay on the hash table (A/B)
     int* d_grid_mm = nullptr;
-    // grow-only scratch of lk_preprocess_scan
-    size_t pre_cap = 0, pre_tmp_bytes = 0;
-    lk_point *pre_raw = nullptr, *pre_cells = nullptr, *pre_out = nullptr;
-    unsigned int *pre_k0 = nullptr, *pre_k1 = nullptr, *pre_flags = nullptr, *pre_pos = nullptr, *pre_misc = nullptr;
-    int *pre_v0 = nullptr, *pre_v1 = nullptr, *pre_starts = nullptr;
-    void* pre_tmp = nullptr;
-    // grow-only scratch of lk_decode_scans_dev: per-point arrays for dsc_pt_cap raw points, per-message tables for dsc_msg_cap messages
-    void* d_dsc = nullptr;
-    size_t dsc_pt_cap = 0, dsc_msg_cap = 0;
-    void* d_dsctmp = nullptr;     // rocPRIM scan / segmented sort scratch
-    size_t dsctmp_cap = 0;
+    DevBuf pre;                   // scratch of lk_decode_scan / lk_preprocess_scan (PrePool)
+    DevBuf dsc;                   // scratch of lk_decode_scans_dev (DscPool)
     // batch replay with a per-scan insert overlay (lk_overlay_kernels.h): the pools of all slots, grow-only
     LkOverlay ov = {};
     uint32_t ov_slots = 0;                                // slots the pools were allocated for
@@ -137,12 +137,9 @@ struct lk_handle {
     uint32_t ov_hw_roots = 0, ov_hw_nodes = 0, ov_hw_blocks = 0;   // high-water marks of the last replay (any slot): the next replay's pools are sized from them
     size_t ov_hw_npts = 0;                                // ... which belong to scans of this size
     size_t ov_pool_bytes = 0;                             // bytes the overlay pools hold (lk_overlay_pool_bytes)
-    LkFilter* d_ov_priors = nullptr;                      // the batch's priors, kept for the retry after a pool overflow
-    size_t ov_priors_cap = 0;
-    void* d_query = nullptr;                              // lk_match_points: inputs + outputs of a query, grown on demand
-    size_t query_cap = 0;
-    int* d_ov_res = nullptr;                              // scan-resident recorded-run replay with insert: [S] next bucket, [S] bucket with fallback items, stopped-scan counter
-    size_t ov_res_cap = 0;
+    DevBuf ov_priors;                                     // LkFilter[S]: the batch's priors, kept for the retry after a pool overflow
+    DevBuf query;                                         // lk_match_points: inputs + outputs of a query
+    DevBuf ov_res;                                        // scan-resident recorded-run replay with insert: [S] next bucket, [S] bucket with fallback items, stopped-scan counter
     unsigned int ov_res_rounds = 0;                       // launches of the scan-resident kernel in the last such replay
     unsigned int* d_ov_status = nullptr;
     // input order of device-resident batches (lk_batch_order): the batches the frozen-map batch entries have seen, with the library's voxel-ordered copy
@@ -163,14 +160,11 @@ struct lk_handle {
     uint64_t ord_tick = 0, ord_examined = 0, ord_sorted = 0, ord_stale = 0;
     int batch_order_mode = 1;              // LK_BATCH_ORDER_AUTO; LEGKILO_BATCH_ORDER=0 / lk_batch_order(h, 0): replay every batch as given
     int batch_order_after = 2;             // a batch is sorted once this many replays in a row have found the same content in its buffer (the sort pays for itself after ~10)
-    // leg kinematics front end (lk_kin.hip): configuration, the state carried from message to message, grow-only scratch
+    // leg kinematics front end (lk_kin.hip): configuration, the state carried from message to message, scratch
     bool kin_configured = false;
     lk_kin_config kin_cfg = {};
     lk_kin_frontend_state kin_fe = {};
-    void* d_kin = nullptr;        // keep flags, ranks, transition maps, their scan, status words
-    size_t kin_cap = 0;
-    void* d_kintmp = nullptr;     // rocPRIM scan scratch
-    size_t kintmp_cap = 0;
+    DevBuf kin;                   // keep flags, ranks, transition maps, their scan, status words
     bool profiling = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::map<std::string, ProfEntry> prof;
@@ -189,6 +183,12 @@ static int fail(lk_handle* h, int code, const std::string& msg) {
         hipError_t e_ = (call);                                                                       \
         if (e_ != hipSuccess)                                                                         \
             return fail(h, LK_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
+    } while (0)
+
+#define LKCHK(call)                        \
+    do {                                   \
+        const int rc_ = (call);            \
+        if (rc_ != LK_OK) return rc_;      \
     } while (0)
 
 template <typename F>
@@ -242,6 +242,39 @@ static hipError_t lk_hip_malloc(T** p, size_t bytes) {
     return lk_hip_malloc(reinterpret_cast<void**>(p), bytes);
 }
 #define hipMalloc(p, n) lk_hip_malloc((p), (n))
+
+// A fixed pool of the handle (allocated once, freed by lk_destroy).  LkMap and its like go to kernels by value and stay plain structs:
+// only the host remembers what it handed out.
+template <typename T>
+static hipError_t pool_alloc(lk_handle* h, T** out, size_t bytes) {
+    const hipError_t e = hipMalloc(out, bytes);
+    if (e == hipSuccess) h->pools.push_back(*out);
+    return e;
+}
+
+static void buf_release(DevBuf& b) {
+    if (b.p) b.pinned ? hipHostFree(b.p) : hipFree(b.p);
+    b.p = nullptr, b.cap = 0;
+}
+// Room for `bytes` in a grow-only buffer.  Large enough already: nothing happens (no synchronisation, no HIP call).  Otherwise the handle's
+// stream is waited for - every user of these buffers runs there - and the buffer is replaced by one of bytes + slack; an allocation that
+// fails leaves it empty, so the next call behaves like a first call.
+static int reserve(lk_handle* h, DevBuf& b, size_t bytes, size_t slack = 0) {
+    if (bytes <= b.cap) return LK_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    buf_release(b);
+    if (!b.listed) h->grown.push_back(&b), b.listed = true;
+    HIPCHK(h, b.pinned ? hipHostMalloc(&b.p, bytes + slack, hipHostMallocDefault) : hipMalloc(&b.p, bytes + slack));
+    b.cap = bytes + slack;
+    return LK_OK;
+}
+// The ragged tables' device copy and its pinned staging twin.  The synchronisation is unconditional and not about growth: a previous
+// call's upload out of the staging buffer must have finished before the host overwrites it.
+static int rag_reserve(lk_handle* h, size_t bytes) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    LKCHK(reserve(h, h->rag, bytes, bytes / 2));
+    return reserve(h, h->rag_stage, bytes, bytes / 2);
+}
 
 // device temporaries of one call: freed on every return path
 struct DevTemps {
@@ -350,8 +383,6 @@ int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n,
              size_t n_kin, float* xyz_world_out, lk_pose* out);          // the bucket loop of KILO::process on a sorted cloud that is in HBM (and on the host, for the bucket bounds)
 // overlay unit (lk_overlay.hip)
 void ov_free(lk_handle* h);
-// kinematics unit (lk_kin.hip)
-void kin_free(lk_handle* h);
 // lk_ovscan.hip (LK_TU_OVSCAN: the scan-resident kernel of the recorded-run replay with insert, a unit of its own for the build time): one launch of it
 int ov_scan_launch(lk_handle* h, bool xid, int S, hipStream_t st, const LkMap& fmap, const LkOverlay& ov, LkFilter* fl, const LkRagged& rg, const lk_point* d_pts, int msg_kind,
                    int* cur, int* fb_b, unsigned int* pending);

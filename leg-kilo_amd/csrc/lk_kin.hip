@@ -7,44 +7,27 @@
 static_assert(sizeof(lk_kin_config) == 64, "lk_kin_config must be 64 B");
 static_assert(sizeof(lk_kin_frontend_state) == 32, "lk_kin_frontend_state must be 32 B");
 
-static int kin_scratch(lk_handle* h, size_t bytes) {
-    if (bytes <= h->kin_cap) return LK_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_kin) hipFree(h->d_kin), h->d_kin = nullptr, h->kin_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_kin, bytes + bytes / 4));
-    h->kin_cap = bytes + bytes / 4;
-    return LK_OK;
-}
-static int kin_tmp(lk_handle* h, size_t bytes) {
-    if (bytes <= h->kintmp_cap) return LK_OK;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_kintmp) hipFree(h->d_kintmp), h->d_kintmp = nullptr, h->kintmp_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_kintmp, bytes));
-    h->kintmp_cap = bytes;
-    return LK_OK;
-}
-static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // flags -> two scans -> scatter -> check; the carried state moves only when the call succeeds
 static int kin_decode(lk_handle* h, const unsigned char* d_msgs, size_t n_sz, lk_kin_imu* d_out, size_t* n_out) {
     const unsigned int n = (unsigned int)n_sz;
-    // scratch: keep u32[n] | rank u32[n] | maps u8[n] | scanned maps u8[n] | status
-    const size_t o_keep = 0, o_rank = align16(4 * n_sz), o_map = o_rank + align16(4 * n_sz), o_cmap = o_map + align16(n_sz),
-                 o_st = o_cmap + align16(n_sz), bytes = o_st + align16(sizeof(LkKinStatus));
-    int rc = kin_scratch(h, bytes);
-    if (rc) return rc;
-    unsigned char* d = static_cast<unsigned char*>(h->d_kin);
-    auto* keep = reinterpret_cast<unsigned int*>(d + o_keep);
-    auto* rank = reinterpret_cast<unsigned int*>(d + o_rank);
-    auto* maps = d + o_map;
-    auto* cmaps = d + o_cmap;
-    auto* st = reinterpret_cast<LkKinStatus*>(d + o_st);
+    unsigned int *keep = nullptr, *rank = nullptr;
+    unsigned char *maps = nullptr, *cmaps = nullptr;   // transition maps, their scan
+    LkKinStatus* st = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        keep = c.take<unsigned int>(n_sz), rank = c.take<unsigned int>(n_sz);
+        maps = c.take<unsigned char>(n_sz), cmaps = c.take<unsigned char>(n_sz);
+        st = c.take<LkKinStatus>(1);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->kin, bytes, bytes / 4));
+    carve(h->kin.p);
     size_t b0 = 0, b1 = 0;
     HIPCHK(h, lk_prim_exclusive_scan(nullptr, b0, keep, rank, n_sz, h->stream));
     HIPCHK(h, lk_prim_compose_scan(nullptr, b1, maps, cmaps, n_sz, h->stream));
     size_t tb = std::max(b0, b1);
-    rc = kin_tmp(h, tb);
-    if (rc) return rc;
+    LKCHK(reserve(h, h->prim_tmp, tb));
     const lk_kin_config& c = h->kin_cfg;
     const lk_kin_frontend_state& fe = h->kin_fe;
     const int4 c0 = make_int4(fe.contact[0], fe.contact[1], fe.contact[2], fe.contact[3]);
@@ -53,8 +36,8 @@ static int kin_decode(lk_handle* h, const unsigned char* d_msgs, size_t n_sz, lk
     LAUNCH(h, "kin_flags", hipLaunchKernelGGL(lk_kin_flags_kernel, dim3(nb), dim3(256), 0, h->stream, d_msgs, n, fe.last_acc_z, fe.last_gyr_z,
                                               c.redundancy ? 1 : 0, c.contact_force_threshold_up, c.contact_force_threshold_down, keep, maps));
     size_t t0 = tb, t1 = tb;
-    HIPCHK(h, lk_prim_exclusive_scan(h->d_kintmp, t0, keep, rank, n_sz, h->stream));
-    HIPCHK(h, lk_prim_compose_scan(h->d_kintmp, t1, maps, cmaps, n_sz, h->stream));
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, t0, keep, rank, n_sz, h->stream));
+    HIPCHK(h, lk_prim_compose_scan(h->prim_tmp.p, t1, maps, cmaps, n_sz, h->stream));
     const unsigned int ns = (n + LK_KIN_MSGS_PER_BLOCK - 1) / LK_KIN_MSGS_PER_BLOCK;
     LAUNCH(h, "kin_scatter", hipLaunchKernelGGL(lk_kin_scatter_kernel, dim3(ns), dim3(4 * LK_KIN_MSGS_PER_BLOCK), 0, h->stream, d_msgs, n, c, c0, keep,
                                                 rank, cmaps, d_out));
@@ -80,13 +63,6 @@ static void kin_reset_frontend(lk_handle* h) {
 }
 
 extern "C" {
-
-void kin_free(lk_handle* h) {
-    if (h->d_kin) hipFree(h->d_kin);
-    if (h->d_kintmp) hipFree(h->d_kintmp);
-    h->d_kin = h->d_kintmp = nullptr;
-    h->kin_cap = h->kintmp_cap = 0;
-}
 
 int lk_kin_configure(lk_handle* h, const lk_kin_config* cfg) {
     CHECK_H(h);
@@ -165,17 +141,20 @@ int lk_kin_split_dev(lk_handle* h, const lk_kin_imu* d_kins, size_t n_kins, cons
     for (size_t s = 0; s < n_scans; ++s) n_msg[s] = 0;
     if (n_scans == 0 || n_kins == 0) return LK_OK;   // an empty cache packages nothing (ros_interface.cc:307)
     const unsigned int S = (unsigned int)n_scans, n = (unsigned int)n_kins;
-    // scratch: ends f64[S] | lb u32[S] | n_msg u32[S] | eq u8[S] | st u32[2]
-    const size_t o_end = 0, o_lb = align16(8 * n_scans), o_nm = o_lb + align16(4 * n_scans), o_eq = o_nm + align16(4 * n_scans),
-                 o_st = o_eq + align16(n_scans), bytes = o_st + 16;
-    int rc = kin_scratch(h, bytes);
-    if (rc) return rc;
-    unsigned char* d = static_cast<unsigned char*>(h->d_kin);
-    auto* ends = reinterpret_cast<double*>(d + o_end);
-    auto* lb = reinterpret_cast<unsigned int*>(d + o_lb);
-    auto* nm = reinterpret_cast<unsigned int*>(d + o_nm);
-    auto* eq = d + o_eq;
-    auto* st = reinterpret_cast<unsigned int*>(d + o_st);
+    double* ends = nullptr;
+    unsigned int *lb = nullptr, *nm = nullptr, *st = nullptr;
+    unsigned char* eq = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        ends = c.take<double>(n_scans);
+        lb = c.take<unsigned int>(n_scans), nm = c.take<unsigned int>(n_scans);   // lower bounds, messages per scan
+        eq = c.take<unsigned char>(n_scans);
+        st = c.take<unsigned int>(2);   // scans packaged, records consumed
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->kin, bytes, bytes / 4));
+    carve(h->kin.p);
     HIPCHK(h, hipMemcpyAsync(ends, scan_end, 8 * n_scans, hipMemcpyHostToDevice, h->stream));
     LAUNCH(h, "kin_lb", hipLaunchKernelGGL(lk_kin_lb_kernel, dim3((S + 255) / 256), dim3(256), 0, h->stream, d_kins, n, ends, S, lb, eq));
     LAUNCH(h, "kin_split", hipLaunchKernelGGL(lk_kin_split_kernel, dim3(1), dim3(LK_WAVE), 0, h->stream, lb, eq, S, n, nm, st));

@@ -245,7 +245,7 @@ static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t bigges
     if (e == hipSuccess) e = get(&o.base_sums, (size_t)h->map.max_nodes * sizeof(LkLeafSum));
     if (e == hipSuccess) e = get(&o.cplx, s * n.scan_cap * 2 * sizeof(int));
     if (e == hipSuccess) e = get(&o.ptroot, s * n.scan_cap * sizeof(int));
-    if (e == hipSuccess && !h->d_ov_status) e = hipMalloc(&h->d_ov_status, 8 * sizeof(unsigned int));
+    if (e == hipSuccess && !h->d_ov_status) e = pool_alloc(h, &h->d_ov_status, 8 * sizeof(unsigned int));
     if (e == hipSuccess && lk_poison_pools()) {
         // test aid: fresh pools hold 0x5a bytes instead of whatever the allocator hands out (usually zeros) - a kernel that trusts a record
         // nobody has written then faults HERE AND NOW, not in the one process whose allocation history leaves garbage there
@@ -329,12 +329,8 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
     // the batch's priors, kept for a second attempt: a scan whose overlay outgrows pools that were sized by this library (first guess, or
     // the previous replay's high-water marks) makes the pools grow and the whole batch run again - only capacities the caller has set
     // explicitly (lk_overlay_reserve) fail with LK_ERR_CAPACITY
-    if (h->ov_priors_cap < (size_t)S) {
-        if (h->d_ov_priors) hipFree(h->d_ov_priors), h->d_ov_priors = nullptr, h->ov_priors_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_ov_priors, sizeof(LkFilter) * (size_t)S));
-        h->ov_priors_cap = (size_t)S;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_ov_priors, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
+    LKCHK(reserve(h, h->ov_priors, sizeof(LkFilter) * (size_t)S));
+    HIPCHK(h, hipMemcpyAsync(h->ov_priors.p, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
     unsigned int stt[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     for (int attempt = 0;; ++attempt) {
     const LkOverlay ov = h->ov;
@@ -434,7 +430,7 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
     HIPCHK(h, hipStreamSynchronize(st));
     const bool growable = !h->ov_want_roots && !(stt[0] & ~(LK_E_HASH_FULL | LK_E_NODES_FULL | LK_E_BLOCKS_FULL)) && attempt < 4;
     if (!stt[0] || !growable) break;
-    HIPCHK(h, hipMemcpyAsync(h->d_filters, h->d_ov_priors, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
     rc = ov_reserve(h, (uint32_t)S, n_pts, biggest, fmap, stt[0]);
     if (rc) return rc;
     }   // attempts
@@ -489,13 +485,9 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
     if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
     rc = ov_reserve(h, (uint32_t)S, max_scan_pts, (size_t)biggest, fmap);
     if (rc) return rc;
-    if (h->ov_priors_cap < (size_t)S) {
-        if (h->d_ov_priors) hipFree(h->d_ov_priors), h->d_ov_priors = nullptr, h->ov_priors_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_ov_priors, sizeof(LkFilter) * (size_t)S));
-        h->ov_priors_cap = (size_t)S;
-    }
+    LKCHK(reserve(h, h->ov_priors, sizeof(LkFilter) * (size_t)S));
     hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->d_ov_priors, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->ov_priors.p, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
     const bool xid = h->pr.ext_identity && lk_xid_enabled();
     const auto res_kernel = xid ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
     unsigned int stt[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -517,12 +509,8 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
         const bool resident = rag_resident && biggest <= LK_SCAN_WAVE_MAX && !rg.bstart;
         if (resident) {
             // [S] next bucket of every scan, [S] the bucket whose fallback items wait, one counter: scans stopped by fallback items in the last launch
-            if (h->ov_res_cap < (size_t)S) {
-                if (h->d_ov_res) hipFree(h->d_ov_res), h->d_ov_res = nullptr, h->ov_res_cap = 0;
-                HIPCHK(h, hipMalloc(&h->d_ov_res, sizeof(int) * (2 * (size_t)S + 4)));
-                h->ov_res_cap = (size_t)S;
-            }
-            int* cur = h->d_ov_res;
+            LKCHK(reserve(h, h->ov_res, sizeof(int) * (2 * (size_t)S + 4)));
+            int* cur = static_cast<int*>(h->ov_res.p);
             int* fb_b = cur + S;
             unsigned int* pending = reinterpret_cast<unsigned int*>(cur + 2 * (size_t)S);
             HIPCHK(h, hipMemsetAsync(cur, 0, sizeof(int) * (2 * (size_t)S + 4), st));
@@ -580,7 +568,7 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
         HIPCHK(h, hipStreamSynchronize(st));
         const bool growable = !h->ov_want_roots && !(stt[0] & ~(LK_E_HASH_FULL | LK_E_NODES_FULL | LK_E_BLOCKS_FULL)) && attempt < 4;
         if (!stt[0] || !growable) break;
-        HIPCHK(h, hipMemcpyAsync(h->d_filters, h->d_ov_priors, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
         rc = ov_reserve(h, (uint32_t)S, max_scan_pts, (size_t)biggest, fmap, stt[0]);
         if (rc) return rc;
     }

@@ -1078,17 +1078,46 @@ int lk_process_scan(lk_handle* h, const lk_point* pts, size_t n, double t_begin,
     return run_scan(h, pts, h->d_scan, n, t_begin, imus, n_imu, kins, n_kin, xyz_world_out, out);
 }
 
-// staging buffer of the ragged / resident tables (device copy + pinned host copy, grow-only); synchronises the stream: a previous
-// call's upload from the staging buffer must have completed before it is overwritten
-static int rag_reserve(lk_handle* h, size_t bytes) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (bytes <= h->rag_cap) return LK_OK;
-    if (h->d_rag) hipFree(h->d_rag), h->d_rag = nullptr;
-    if (h->h_rag) hipHostFree(h->h_rag), h->h_rag = nullptr;
-    h->rag_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_rag, bytes + bytes / 2));
-    HIPCHK(h, hipHostMalloc(&h->h_rag, bytes + bytes / 2, hipHostMallocDefault));
-    h->rag_cap = bytes + bytes / 2;
+// Tables of one scan for the resident stream kernels: LkRagged's arrays for a single scan, the grid-resident kernel's barrier words, where a
+// launch stopped.  One description, laid over the pinned staging copy and over the device copy (rag_reserve); both kernels' scans use it, so
+// a scan-resident launch also uploads the 16 B of barrier words it does not read.
+struct ScanTables {
+    unsigned long long* po;   // [nb+1] first point of every bucket
+    double* t;                // [nb] its time
+    unsigned char* im;        // the scan's messages
+    unsigned int *nb, *io;    // { nb, 0 }, { 0, n_msg }: a batch of one scan
+    unsigned int* sync;       // [4] lk_scan_grid_kernel: barrier arrivals, abort word, XCC ids
+    LkResume* rs;
+    size_t bytes;
+};
+static ScanTables scan_tables(void* base, size_t nb, size_t msg_bytes_total) {
+    LkCarve c(base);
+    ScanTables r;
+    r.po = c.take<unsigned long long>(nb + 1), r.t = c.take<double>(nb);
+    r.im = c.take<unsigned char>(msg_bytes_total);
+    r.nb = c.take<unsigned int>(2), r.io = c.take<unsigned int>(2);
+    r.sync = c.take<unsigned int>(4);
+    r.rs = c.take<LkResume>(1);
+    r.bytes = c.total();
+    return r;
+}
+// fills the staging copy and uploads it; returns the device copy's arrays
+static int upload_scan_tables(lk_handle* h, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime, const void* msgs, size_t n_msg,
+                       size_t msg_bytes, ScanTables* dev) {
+    const size_t nb = btime.size();
+    const size_t bytes = scan_tables(nullptr, nb, msg_bytes * n_msg).bytes;
+    LKCHK(rag_reserve(h, bytes));
+    const ScanTables st = scan_tables(h->rag_stage.p, nb, msg_bytes * n_msg);
+    memcpy(st.po, bstart.data(), 8 * (nb + 1));
+    memcpy(st.t, btime.data(), 8 * nb);
+    if (n_msg) memcpy(st.im, msgs, msg_bytes * n_msg);
+    st.nb[0] = (unsigned int)nb, st.nb[1] = 0u;
+    st.io[0] = 0u, st.io[1] = (unsigned int)n_msg;
+    memset(st.sync, 0, 16);
+    memset(st.rs, 0, sizeof(LkResume));
+    st.rs->fb_bucket = -1;
+    HIPCHK(h, hipMemcpyAsync(h->rag.p, h->rag_stage.p, bytes, hipMemcpyHostToDevice, h->stream));
+    *dev = scan_tables(h->rag.p, nb, msg_bytes * n_msg);
     return LK_OK;
 }
 
@@ -1099,7 +1128,7 @@ static unsigned int resident_timeout_ms() {
 }
 // filters[0] before a scan that works on it in place (grid-resident kernel, pipelined launches): check_map_errors restores it on LK_ERR_TIMEOUT
 static int backup_filter(lk_handle* h) {
-    if (!h->d_fbackup) HIPCHK(h, hipMalloc(&h->d_fbackup, sizeof(LkFilter)));
+    if (!h->d_fbackup) HIPCHK(h, pool_alloc(h, &h->d_fbackup, sizeof(LkFilter)));
     HIPCHK(h, hipMemcpyAsync(h->d_fbackup, h->d_filters, sizeof(LkFilter), hipMemcpyDeviceToDevice, h->stream));
     h->fbackup_valid = true;
     return LK_OK;
@@ -1112,34 +1141,18 @@ static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vec
                              const void* msgs, size_t n_msg, int msg_kind, float* d_world, lk_pose* pose) {
     const size_t nb = btime.size();
     const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
-    const size_t o_po = 0, o_t = o_po + 8 * (nb + 1), o_im = o_t + 8 * nb, o_nb = o_im + msg_bytes * n_msg, o_io = o_nb + 8, o_rs = o_io + 8,
-                 bytes = o_rs + sizeof(LkResume);
-    int rc = rag_reserve(h, bytes);
+    ScanTables dv;
+    int rc = upload_scan_tables(h, bstart, btime, msgs, n_msg, msg_bytes, &dv);
     if (rc) return rc;
-    unsigned char* stage = static_cast<unsigned char*>(h->h_rag);
-    memcpy(stage + o_po, bstart.data(), 8 * (nb + 1));
-    memcpy(stage + o_t, btime.data(), 8 * nb);
-    if (n_msg) memcpy(stage + o_im, msgs, msg_bytes * n_msg);
-    const unsigned int nbu[2] = {(unsigned int)nb, 0u}, io[2] = {0u, (unsigned int)n_msg};
-    memcpy(stage + o_nb, nbu, 8);
-    memcpy(stage + o_io, io, 8);
-    {
-        LkResume r0;
-        memset(&r0, 0, sizeof(r0));
-        r0.fb_bucket = -1;
-        memcpy(stage + o_rs, &r0, sizeof(r0));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_rag, stage, bytes, hipMemcpyHostToDevice, h->stream));
-    unsigned char* dr = static_cast<unsigned char*>(h->d_rag);
-    LkResume* d_rs = reinterpret_cast<LkResume*>(dr + o_rs);
+    LkResume* d_rs = dv.rs;
     LkRagged rg;
-    rg.pt_off = reinterpret_cast<const unsigned long long*>(dr + o_po);
-    rg.t = reinterpret_cast<const double*>(dr + o_t);
-    rg.nb = reinterpret_cast<const unsigned int*>(dr + o_nb);
+    rg.pt_off = dv.po;
+    rg.t = dv.t;
+    rg.nb = dv.nb;
     rg.ldb = (int)nb;
     rg.bstart = nullptr;
-    rg.imu_off = reinterpret_cast<const unsigned int*>(dr + o_io);
-    rg.imu = reinterpret_cast<const double*>(dr + o_im);
+    rg.imu_off = dv.io;
+    rg.imu = reinterpret_cast<const double*>(dv.im);
     rg.msg_stride = (int)(msg_bytes / sizeof(double));
     rg.kin_noise = h->cfg.kin_meas_noise;
     rg.q_diag = h->q_diag ? 1 : 0;
@@ -1233,33 +1246,18 @@ static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vec
 static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime,
                          size_t biggest, float* d_world, lk_pose* pose) {
     const size_t nb = btime.size();
-    const size_t o_po = 0, o_t = o_po + 8 * (nb + 1), o_nb = o_t + 8 * nb, o_io = o_nb + 8, o_sync = o_io + 8, o_rs = o_sync + 16, bytes = o_rs + sizeof(LkResume);
-    int rc = rag_reserve(h, bytes);
+    ScanTables dv;
+    int rc = upload_scan_tables(h, bstart, btime, nullptr, 0, 0, &dv);
     if (rc) return rc;
-    unsigned char* stage = static_cast<unsigned char*>(h->h_rag);
-    memcpy(stage + o_po, bstart.data(), 8 * (nb + 1));
-    memcpy(stage + o_t, btime.data(), 8 * nb);
-    const unsigned int nbu[2] = {(unsigned int)nb, 0u}, io[2] = {0u, 0u}, zero4[4] = {0u, 0u, 0u, 0u};
-    memcpy(stage + o_nb, nbu, 8);
-    memcpy(stage + o_io, io, 8);
-    memcpy(stage + o_sync, zero4, 16);
-    {
-        LkResume r0;
-        memset(&r0, 0, sizeof(r0));
-        r0.fb_bucket = -1;
-        memcpy(stage + o_rs, &r0, sizeof(r0));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_rag, stage, bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = backup_filter(h))) return rc;
-    unsigned char* dr = static_cast<unsigned char*>(h->d_rag);
     LkRagged rg;
     memset(&rg, 0, sizeof(rg));
-    rg.pt_off = reinterpret_cast<const unsigned long long*>(dr + o_po);
-    rg.t = reinterpret_cast<const double*>(dr + o_t);
-    rg.nb = reinterpret_cast<const unsigned int*>(dr + o_nb);
+    rg.pt_off = dv.po;
+    rg.t = dv.t;
+    rg.nb = dv.nb;
     rg.ldb = (int)nb;
     rg.bstart = nullptr;
-    rg.imu_off = reinterpret_cast<const unsigned int*>(dr + o_io);
+    rg.imu_off = dv.io;
     rg.q_diag = h->q_diag ? 1 : 0;
     h->grid_valid = false;   // the map changes
     const bool xid = h->pr.ext_identity && lk_xid_enabled();
@@ -1285,13 +1283,13 @@ static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<
     // up to one workgroup per CU of an XCD: launch 8 G blocks and let only every eighth work
     const int stride = G <= 32 ? 8 : 1;
     const auto k = xid ? lk_scan_grid_kernel<true> : lk_scan_grid_kernel<false>;
-    LkResume* d_rs = reinterpret_cast<LkResume*>(dr + o_rs);
+    LkResume* d_rs = dv.rs;
     h->grid_scans += 1;
     int b0 = 0;
     for (size_t round = 0;; ++round) {
         h->fbackup_valid = true;   // the copy taken above is the pre-scan state for every launch of this scan
         LAUNCH(h, "scan_grid", hipLaunchKernelGGL(k, dim3(G * stride), dim3(LK_FB), 0, h->stream, h->map, h->pr, h->d_filters, d_pts, rg, h->d_Q, h->d_snap, d_world,
-                                                  h->d_partials, reinterpret_cast<unsigned int*>(dr + o_sync), h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, stride, b0, d_rs));
+                                                  h->d_partials, dv.sync, h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, stride, b0, d_rs));
         if ((rc = finish_scan(h, pose, d_rs))) return rc;
 #ifdef LK_DEBUG_RES
         {
@@ -1314,7 +1312,7 @@ static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<
         if (round > nb + 4 || rsm[0] <= b0) return fail(h, LK_ERR_STATE, "the grid-resident kernel does not advance");
         h->grid_relaunches += 1;
         LAUNCH(h, "resident_fallback", hipLaunchKernelGGL(lk_resident_fallback_kernel, dim3(8), dim3(LK_MB), 0, h->stream, h->map, h->pr, h->d_snap, d_pts, rg, 0u, 0, d_rs,
-                                                          reinterpret_cast<unsigned int*>(dr + o_sync)));   // (also zeroes the barrier arrivals, abort word and XCC ids for the next launch)
+                                                          dv.sync));   // (also zeroes the barrier arrivals, abort word and XCC ids for the next launch)
         b0 = rsm[0];
         if (b0 >= (int)nb) {   // they were the last bucket's
             if ((rc = finish_scan(h, pose, nullptr))) return rc;

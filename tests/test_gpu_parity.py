@@ -308,6 +308,43 @@ def test_build_single_residual_per_point(pair, scene, oracle_lib):
     scenes.compare_maps(blob, g.map_export())   # the query left the map alone
 
 
+def test_match_points_buffer_grows_and_stays_right(scene, oracle_lib, hip_lib):
+    """A few queries, many, the few again on one handle (lk_match_points): each answer equals, bit for bit, the same query's on a fresh handle."""
+    o = oracle_lib.Oracle(scene.cfg(), imu_mode_only=True)
+    blob = mature_oracle_map(o, scene, 1.0)
+    xs, _ = o.get_state()
+    o.close()
+    rng = np.random.default_rng(43)
+    pts = synth.dense_scan(scene.world, scenes.Frozen(scene.traj, 2.0), 2.0, scene.P, n=20000, n_buckets=1)
+    Rw, tw = np.asarray(xs[:9]).reshape(3, 3), np.asarray(xs[9:12])
+    pw = (scenes.xyz_of(pts).astype(np.float64) + np.asarray(scene.P["extrinsic_T"])) @ Rw.T + tw + rng.normal(0, 0.03, (len(pts), 3))
+    keys = np.array([oracle_lib.key_floor(p, float(scene.P["voxel_size"])) for p in pw], dtype=np.int32)
+    A = rng.normal(size=(len(pw), 3, 3))
+    V = A @ A.transpose(0, 2, 1) * 4e-3 + np.eye(3) * 1e-6
+
+    def handle():
+        g = hip_lib.LegKiloHip(scene.cfg())
+        g.map_import(blob)
+        return g
+
+    def run(g, n):
+        m = g.match_points(keys[:n], pw[:n], V[:n])
+        return {k: np.asarray(v).tobytes() for k, v in m.items()}, int(np.asarray(m["success"]).sum())
+
+    one = handle()
+    try:
+        for n, least in ((7, 0), (20000, 2000), (7, 0)):   # 20 000 queries: 4.2 MB, beyond the buffer's first 64 KiB
+            fresh = handle()
+            try:
+                want, n_ok = run(fresh, n)
+            finally:
+                fresh.close()
+            assert n_ok >= least, (n, n_ok)
+            assert run(one, n)[0] == want, n
+    finally:
+        one.close()
+
+
 def test_update_points_bucket_and_insert(pair, scene):
     o, g = pair
     t0 = 1.0
@@ -1881,6 +1918,52 @@ def test_batch_replay_ragged(scene, oracle_lib, hip_lib, monkeypatch):
     g.device_free(d_pts)
     g.close()
     o.close()
+
+
+@pytest.mark.parametrize("host_tables", [True, False])
+def test_ragged_replay_buffers_grow_and_stay_right(scene, oracle_lib, hip_lib, host_tables):
+    """A small batch, a large batch, the small batch again on one handle - lk_batch_replay_ragged_imu_dev with host tables, or
+    lk_batch_replay_scans_dev with the tables built on the device: poses and states equal, bit for bit, what the same batch gives on a
+    fresh handle."""
+    o = oracle_lib.Oracle(scene.cfg(), imu_mode_only=True)
+    t0 = 1.0
+    blob = mature_oracle_map(o, scene, t0)
+    o.close()
+    rng = np.random.default_rng(8120)
+
+    def batch(n, k0, cut):
+        tbs = [t0 + 1.1 + 0.1 * (k0 + k) for k in range(n)]
+        scans = [scenes.vlp_scan_input(scene, tb, 40 + k0 + k)[:cut] for k, tb in enumerate(tbs)]
+        xs = [synth.initial_state(scene.traj, tb, scene.P, rng, 0.02, 0.5) for tb in tbs]
+        imus = [synth.imu_stream(scene.traj, tb, tb + 0.1, seed=8700 + k0 + k) for k, tb in enumerate(tbs)]
+        return scans, tbs, xs, [1e-4 * np.eye(30)] * n, imus
+
+    def handle():
+        g = hip_lib.LegKiloHip(scene.cfg(n_slots=6))
+        g.map_import(blob)
+        g.init_process_cov_q()
+        g.set_acc_norm(9.81)
+        return g
+
+    def run(g, b):
+        scans, tbs, xs, Ps, imus = b
+        ps = g.batch_replay_ragged(scans, tbs, xs, Ps, imus=imus, host_tables=host_tables)
+        assert all(p.n_updates > 0 for p in ps)
+        return [bytes(p) for p in ps], [tuple(a.tobytes() for a in g.get_state(slot=s)) for s in range(len(scans))]
+
+    small, large = batch(1, 0, 1000), batch(6, 1, None)
+    assert sum(len(sc) for sc in large[0]) > 20 * len(small[0][0])
+    one = handle()
+    try:
+        for b in (small, large, small):
+            fresh = handle()
+            try:
+                want = run(fresh, b)
+            finally:
+                fresh.close()
+            assert run(one, b) == want
+    finally:
+        one.close()
 
 
 def test_batch_replay_ragged_leg_fusion(oracle_lib, hip_lib):

@@ -338,6 +338,43 @@ def test_split_parity_with_stamps_on_scan_ends(hip_lib):
 
 
 @pytest.mark.gpu
+def test_scratch_grows_and_stays_right(hip_lib):
+    """A short stream, a long one, the short one again on one handle (lk_decode_highstate_dev, then lk_kin_split_dev over what it kept, with few and
+    with many scans): records, front-end state and split equal, bit for bit, what the same input gives on a fresh handle."""
+    p = dict(config.DITER, redundancy=True)
+    short, long_ = _stream(p, n=700, seed=31), _stream(p, n=60_000, seed=32)
+
+    def run(g, msgs, n_scans):
+        g.kin_configure(p)   # (resets the carried state: every input starts like a first call)
+        d_in, d_out = g.device_malloc(msgs.nbytes), g.device_malloc(len(msgs) * synth.KIN_DTYPE.itemsize)
+        try:
+            g.h2d(d_in, msgs)
+            k = g.decode_highstate_dev(d_in, len(msgs), d_out)
+            recs = np.zeros(k, dtype=synth.KIN_DTYPE)
+            g.d2h(recs, d_out)
+            st = g.kin_get_frontend()
+            ends = np.linspace(recs["time_stamp"][0], recs["time_stamp"][-1] + 0.01, n_scans)
+            n_msg, npk, ncs = g.kin_split_dev(d_out, k, ends)
+        finally:
+            g.device_free(d_in)
+            g.device_free(d_out)
+        assert k > 20 and npk > 0 and ncs > 0
+        return recs.tobytes(), {key: np.asarray(v).tobytes() for key, v in st.items()}, n_msg.tobytes(), npk, ncs
+
+    one = _handle(hip_lib, p)
+    try:
+        for msgs, n_scans in ((short, 3), (long_, 2500), (short, 3)):
+            fresh = _handle(hip_lib, p)
+            try:
+                want = run(fresh, msgs, n_scans)
+            finally:
+                fresh.close()
+            assert run(one, msgs, n_scans) == want
+    finally:
+        one.close()
+
+
+@pytest.mark.gpu
 def test_leg_fusion_recorded_run_from_highstate_bytes(oracle_lib, hip_lib):
     """HighState bytes -> lk_decode_highstate_dev -> lk_kin_split_dev -> lk_batch_replay_scans_kin_dev, the records never leaving HBM, equals the
     oracle's process_scan fed with the restatement's records (counts exact, x to 1e-8, P to 1e-6), and lk_batch_replay_scans_dev fed with the

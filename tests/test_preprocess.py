@@ -76,6 +76,34 @@ def test_gpu_preprocess_bit_exact(scene, hip_lib, leaf):
 
 
 @pytest.mark.gpu
+def test_gpu_preprocess_scratch_grows_and_stays_right(scene, hip_lib):
+    """A small cloud, a large one, the small one again on one handle (lk_preprocess_scan): each equals, bit for bit, what the same cloud
+    gives on a fresh handle.  Then, on another handle, clouds a few points beyond what the first call's slack covers (1 000 points reserve
+    room for 1 000 + 250 + 1 024 = 2 274): the scratch and the sorts' temporary storage must follow."""
+    scan = raw_scan(scene, 1.0)
+    small = scan[:900]
+    large = synth.dense_scan(scene.world, scene.traj, 3.0, scene.P, n=100000, n_buckets=51, seed_scan=4243)
+    assert len(scan) > 2400
+    for clouds in ((small, large, small), (scan[:1000], scan[:2275], scan[:2288], scan[:2289], scan[:2400])):
+        _grow_case(scene, hip_lib, clouds)
+
+
+def _grow_case(scene, hip_lib, clouds):
+    one = hip_lib.LegKiloHip(scene.cfg())
+    try:
+        for cloud in clouds:
+            fresh = hip_lib.LegKiloHip(scene.cfg())
+            try:
+                want = fresh.preprocess_scan(cloud, 0.3)
+            finally:
+                fresh.close()
+            got = one.preprocess_scan(cloud, 0.3)
+            assert 0 < len(want) <= len(cloud) and got.tobytes() == want.tobytes()
+    finally:
+        one.close()
+
+
+@pytest.mark.gpu
 def test_gpu_raw_scan_to_pose(scene, hip_lib, oracle_lib):
     """raw cloud -> (device) voxel grid + sort -> bucket loop, against oracle preprocessing + oracle path."""
     o = oracle_lib.Oracle(scene.cfg(), imu_mode_only=True)

@@ -367,7 +367,9 @@ __device__ __forceinline__ V3 point_world(float bx, float by, float bz, const Bu
 //   n^T P_pp n
 // These are identities in exact arithmetic for ANY R / ext_R (no orthonormality is assumed); in fp64 they differ
 // from the reference's matrix route by rounding only (~1e-16 relative), ~60 flops per candidate instead of ~230 per
-// point + 12 per candidate, and ~40 fewer live VGPRs.
+// point + 12 per candidate, and ~40 fewer live VGPRs.  Checked with a tilted, not exactly orthonormal ext_R (6-decimal
+// entries) and z == 0 body points against the oracle's matrix route: tests/test_config_space.py, configurations `tilt` / `all`
+// (test_residuals_and_batch_rows: rows to 1e-9, masks exact).
 // 1 / x for the residual kernel's two divisions per point: the IEEE division.  v_rcp_f64 + two Newton steps - the same value to the
 // last bit or one ulp beside it, ~20 instructions fewer per point - measured +1.5 % (662 k vs 652 k scans/s, same box), but one match
 // of the 1024-scan batch flips (a gate within an ulp of its threshold): the oracle divides, so does the shipped build.

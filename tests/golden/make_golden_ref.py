@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generates tests/golden/ref_kilo_small.npz with the REFERENCE ITSELF: oracle/_ref = the reference's own eskf.cc,
+"""Generates tests/golden/ref_kilo_small.npz, ref_kilo_config4.npz and ref_kilo_offconfig.npz with the REFERENCE ITSELF: oracle/_ref = the reference's own eskf.cc,
 voxel_map.cc and KILO.cc compiled unmodified against oracle/shim (oracle/Makefile, target `ref`), driven through
 KILO::process by oracle_binding.ReferenceKilo.
 
@@ -21,6 +21,7 @@ import lk_pkg  # noqa: E402
 
 lk_pkg.load()
 import oracle_binding as ob  # noqa: E402
+import offconfig  # noqa: E402
 import scenes  # noqa: E402
 from legkilo_amd import config, synth  # noqa: E402
 
@@ -28,8 +29,11 @@ CAPS = dict(max_roots=1 << 14, max_nodes=1 << 15, max_point_blocks=1 << 14, max_
 
 
 def run(mode, n_scans, tmp):
+    """mode "off": configuration `all` of tests/offconfig.py (tilted 6-decimal extrinsic, voxel size 0.4, max_layer 3 with per-layer
+    thresholds, other gate constants), IMU-only, z = 0 forced on every 37th raw point."""
     use_kin = mode == "kin"
-    sc = scenes.Scene(params=dict(config.DITER, voxel_grid_resolution=0.3) if use_kin else None, **CAPS)
+    sc = offconfig.scene("all" if mode == "off" else None, use_kin, **CAPS)
+    scan_input = offconfig.ZeroZ() if mode == "off" else scenes.vlp_scan_input
     k = ob.ReferenceKilo(sc.P, not use_kin, os.path.join(tmp, f"{mode}.yaml"))
     t0 = 1.0
     x0 = scenes.init_filter(k, sc, t0)
@@ -41,7 +45,7 @@ def run(mode, n_scans, tmp):
     pts, aux, xs, ne = [], [], [], []
     for s in range(n_scans):
         tb = t0 + 0.1 * s
-        ds = scenes.vlp_scan_input(sc, tb, s)
+        ds = scan_input(sc, tb, s)
         a = synth.kin_stream(sc.traj, tb, tb + 0.1, sc.P, seed=3003 + s) if use_kin else synth.imu_stream(sc.traj, tb, tb + 0.1, seed=3003 + s)
         pose, _ = k.process_scan(ds, tb, kins=a) if use_kin else k.process_scan(ds, tb, imus=a)
         x, _ = k.get_state()
@@ -103,6 +107,12 @@ def run_config4(n_scans, tmp):
 def main():
     assert ob.build_ref() is not None and os.path.exists("/root/reference"), "needs the reference tree"
     with tempfile.TemporaryDirectory() as tmp:
+        off = run("off", 3, tmp)
+        path = os.path.join(HERE, "ref_kilo_offconfig.npz")
+        np.savez_compressed(path, **off)
+        print(path, os.path.getsize(path), "bytes; n_effect", off["off_n_effect"])
+        if "--offconfig-only" in sys.argv:
+            return
         if "--config4-only" not in sys.argv:
             d = run("imu", 3, tmp)
             d.update(run("kin", 2, tmp))

@@ -78,12 +78,13 @@ def vlp_scan_input(scene, tb, k):
     return ds
 
 
-def replay_vlp(obj, scene, t0, n_scans, use_kin=False, start=0, collect=None):  # noqa: C901
-    """Replay n_scans 10 Hz scans through obj.process_scan; returns list of (pose, x36)."""
+def replay_vlp(obj, scene, t0, n_scans, use_kin=False, start=0, collect=None, scan_input=None):  # noqa: C901
+    """Replay n_scans 10 Hz scans through obj.process_scan; returns list of (pose, x36).
+    scan_input(scene, tb, k) replaces vlp_scan_input (e.g. offconfig.ZeroZ)."""
     out = []
     for k in range(start, start + n_scans):
         tb = t0 + 0.1 * k
-        ds = vlp_scan_input(scene, tb, k)
+        ds = (scan_input or vlp_scan_input)(scene, tb, k)
         if use_kin:
             kins = synth.kin_stream(scene.traj, tb, tb + 0.1, scene.P, seed=3003 + k)
             pose, w = obj.process_scan(ds, tb, kins=kins, want_world=collect is not None)

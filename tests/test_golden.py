@@ -152,6 +152,7 @@ def synth_point_dtype():
 # ----------------------------------------------------------------------------- golden vectors made BY THE REFERENCE
 GR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_kilo_small.npz")
 GR4 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_kilo_config4.npz")
+GRO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_kilo_offconfig.npz")
 
 
 def replay_ref_golden(obj, g, mode):
@@ -166,7 +167,7 @@ def replay_ref_golden(obj, g, mode):
     ao = np.r_[0, np.cumsum(g[f"{mode}_aux_len"])]
     for k in range(len(g[f"{mode}_len"])):
         pts, aux = g[f"{mode}_pts"][po[k]:po[k + 1]], g[f"{mode}_aux"][ao[k]:ao[k + 1]]
-        kw = dict(imus=aux) if mode == "imu" else dict(kins=aux)
+        kw = dict(imus=aux) if mode in ("imu", "off") else dict(kins=aux)
         pose, _ = obj.process_scan(pts, float(g[f"{mode}_tb"][k]), **kw)
         x, _ = obj.get_state()
         yield k, pose, x
@@ -175,10 +176,13 @@ def replay_ref_golden(obj, g, mode):
 def check_ref_golden(make, tol_state, tol_cov, ptol):
     from legkilo_amd import config
 
-    for mode in ("imu", "kin", "c4"):
+    import offconfig
+
+    for mode in ("imu", "kin", "c4", "off"):
         # "c4": config 4 at its stated shape - diter.yaml as is, Ouster 64 x 1024 scans, leg fusion (make_golden_ref.py: run_config4)
-        g = np.load(GR4 if mode == "c4" else GR)
-        params = {"imu": None, "kin": dict(config.DITER, voxel_grid_resolution=0.3), "c4": config.DITER}[mode]
+        # "off": configuration `all` of tests/offconfig.py, IMU-only, z == 0 points on the path
+        g = np.load({"c4": GR4, "off": GRO}.get(mode, GR))
+        params = {"imu": None, "kin": dict(config.DITER, voxel_grid_resolution=0.3), "c4": config.DITER, "off": offconfig.params("all")}[mode]
         sc = scenes.Scene(params=params, **CAPS)
         obj = make(sc, mode)
         for k, pose, x in replay_ref_golden(obj, g, mode):
@@ -188,14 +192,14 @@ def check_ref_golden(make, tol_state, tol_cov, ptol):
         assert np.abs(P - g[f"{mode}_P"]).max() <= tol_cov * np.abs(g[f"{mode}_P"]).max(), mode
         tp, tu = obj.get_times()
         assert (tp, tu) == tuple(g[f"{mode}_times"]), mode
-        if mode == "imu":
-            scenes.compare_maps(g["imu_map_blob"], obj.map_export(), rtol=1e-5, ptol=ptol)
+        if f"{mode}_map_blob" in g.files:
+            scenes.compare_maps(g[f"{mode}_map_blob"], obj.map_export(), rtol=1e-5, ptol=ptol)
         obj.close()
 
 
 def test_oracle_reproduces_what_the_reference_computed(oracle_lib):
     """The oracle against outputs of the reference's own KILO::process (no reference tree needed to run this)."""
-    check_ref_golden(lambda sc, mode: oracle_lib.Oracle(sc.cfg(), imu_mode_only=(mode == "imu")), 1e-8, 1e-6, 1e-7)
+    check_ref_golden(lambda sc, mode: oracle_lib.Oracle(sc.cfg(), imu_mode_only=(mode in ("imu", "off"))), 1e-8, 1e-6, 1e-7)
 
 
 @pytest.mark.gpu

@@ -13,6 +13,10 @@ parity tests use as their checker:
   map (voxel_map.cc)      calcBodyCov, init_plane, BuildVoxelMap, UpdateVoxelMap / UpdateOctoTree (incl. cuts to layer 2,
                           refits, freezes), build_single_residual, mapSliding / clearMemOutOfMap
 
+Off the shipped yaml values (tests/offconfig.py: tilted 6-decimal extrinsic rotation, voxel size 0.4, max_layer 0 / 3 / 4 with per-layer
+thresholds, other gate constants) KILO::process, UpdateVoxelMap down to five levels, build_single_residual on every layer and the face
+lattice of the 0.4 m grid are pinned too: it is what makes the oracle the checker of tests/test_config_space.py.
+
 What is restated on the reference side is third-party arithmetic only (Eigen's inverse() and EigenSolver: oracle/shim
 header comment); KILO.cc's glue cannot be built here and stays pinned by the oracle's own tests.  The file is skipped
 where neither /root/reference nor a prebuilt oracle/_ref exists.
@@ -21,6 +25,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+import offconfig
 import scenes
 from legkilo_amd import abi, config, synth
 
@@ -228,31 +233,123 @@ def test_build_and_update_voxel_map_match_the_reference():
 
     assert max(depth(n) for n in cm.values()) >= 3, "the clutter must cut voxels down to layer 2"
     assert o.map_stats() == r.map_stats()
+    assert match_slide_clear(o, r, sc.P, rng, allp) > 0
+    o.close()
+    r.close()
+
+
+def match_slide_clear(o, r, P, rng, allp, centre=(5.2, 5.4, 1.0), least_ok=500, per_layer=None):
+    """build_single_residual on home and neighbouring voxels, mapSliding, clearMemOutOfMap: oracle == reference on the map both hold.
+    per_layer: dict layer -> success count, filled when given."""
     # ---- build_single_residual (voxel_map.cc:363-427) on home and neighbouring voxels
     n_ok = 0
-    q = np.concatenate([allp[:1500] + rng.normal(0, 0.02, (1500, 3)), rng.uniform(-4, 9, (500, 3))])
+    nq = min(1500, len(allp))
+    q = np.concatenate([allp[:nq] + rng.normal(0, 0.02, (nq, 3)), rng.uniform(-4, 9, (500, 3))])
+    vs_f = float(np.float32(P["voxel_size"]))       # the insert side's divisor (voxel_map.cc:337)
     for p in q:
-        key = ob.key_floor(p, float(np.float32(0.5)))
+        key = ob.key_floor(p, vs_f)
         for dk in ((0, 0, 0), (1, 0, 0), (0, -1, 0)):
             kk = tuple(int(a + b) for a, b in zip(key, dk))
             V = (np.eye(3) * 1e-4 + 2e-5).reshape(9)
-            mo, mr = o.match_voxel(kk, p, V), r.match_voxel(kk, p, V)
-            assert (mo["found"], mo["success"], mo["layer"] if mo["success"] else -1) == \
-                   (mr["found"], mr["success"], mr["layer"] if mr["success"] else -1), (p, kk)
-            if mo["success"]:
-                n_ok += 1
-                s = np.sign(np.dot(mo["normal"], mr["normal"]))
-                assert np.allclose(mo["normal"], s * mr["normal"], atol=1e-9)
-                assert np.isclose(mo["dis_to_plane"], s * mr["dis_to_plane"], rtol=1e-5, atol=1e-7)
-                assert np.isclose(mo["prob"], mr["prob"], rtol=1e-6)
-    assert n_ok > 500
+            n_ok += match_one(o, r, kk, p, V, per_layer)
+    assert n_ok > least_ok, n_ok
     # ---- sliding
-    assert o.map_slide([5.2, 5.4, 1.0], 1.0, 6) == r.map_slide([5.2, 5.4, 1.0], 1.0, 6)
+    c = np.asarray(centre, float)
+    assert o.map_slide(c, 1.0, 6) == r.map_slide(c, 1.0, 6)
     assert np.array_equal(o.get_last_slide_position(), r.get_last_slide_position())
-    assert o.map_slide([5.3, 5.4, 1.0], 1.0, 6) == r.map_slide([5.3, 5.4, 1.0], 1.0, 6) == (False, 0)
+    assert o.map_slide(c + [0.1, 0, 0], 1.0, 6) == r.map_slide(c + [0.1, 0, 0], 1.0, 6) == (False, 0)
     assert o.map_clear_outside(12, 8, 20, 9, 4, 1) == r.map_clear_outside(12, 8, 20, 9, 4, 1)
     scenes.compare_maps(o.map_export(), r.map_export(), rtol=1e-6, ptol=1e-9)
-    assert 0 < o.map_stats() == r.map_stats()
+    assert o.map_stats() == r.map_stats()
+    return o.map_stats()
+
+
+def match_one(o, r, kk, p, V, per_layer=None):
+    mo, mr = o.match_voxel(kk, p, V), r.match_voxel(kk, p, V)
+    assert (mo["found"], mo["success"], mo["layer"] if mo["success"] else -1) == \
+           (mr["found"], mr["success"], mr["layer"] if mr["success"] else -1), (p, kk)
+    if not mo["success"]:
+        return 0
+    s = np.sign(np.dot(mo["normal"], mr["normal"]))
+    assert np.allclose(mo["normal"], s * mr["normal"], atol=1e-9)
+    assert np.isclose(mo["dis_to_plane"], s * mr["dis_to_plane"], rtol=1e-5, atol=1e-7)
+    assert np.isclose(mo["prob"], mr["prob"], rtol=1e-6)
+    if per_layer is not None:
+        per_layer[mo["layer"]] = per_layer.get(mo["layer"], 0) + 1
+    return 1
+
+
+def fed_pair(P, feeds):
+    """Oracle and reference fed the same (points, variances) lists through UpdateVoxelMap in the chunk sizes of offconfig.CHUNKS;
+    compare_maps after every chunk."""
+    cfg = config.make_config(P)
+    o, r = ob.Oracle(cfg), ob.Reference(cfg)
+    for p, var in feeds:
+        for a, b in offconfig.chunks_of(len(p)):
+            for obj in (o, r):
+                obj.map_update(p[a:b], var[a:b])
+            scenes.compare_maps(o.map_export(), r.map_export(), rtol=1e-6, ptol=1e-9)
+    return o, r
+
+
+@pytest.mark.parametrize("max_layer,vs,base", [(4, 0.5, "deep4"), (3, 0.4, "deep4"), (1, 0.5, "deep4"), (0, 0.4, "deep4"), (4, 0.5, "desc4")])
+def test_update_voxel_map_uniform_box_matches_the_reference(max_layer, vs, base):
+    """UpdateVoxelMap fed 1, 1, 5, 17, 200, 1 000, 5 000, rest of 40 000 points uniform in one box, at tree depths the shipped
+    configuration never reaches: nothing is a plane, so every root is cut down to max_layer - identical at every step.  Thresholds
+    rising with depth (5 .. 9) and, `desc4`, falling (9 .. 5)."""
+    P = dict(offconfig.params(base), max_layer=max_layer, voxel_size=vs)
+    p, var = offconfig.uniform_box(seed=61)
+    o, r = fed_pair(P, [(p, var)])
+    cm = scenes.canon_map(r.map_export())
+    assert offconfig.depth(cm) == max_layer + 1
+    nodes, _ = offconfig.layer_counts(cm)
+    assert (nodes[: max_layer + 1] > 0).all() and (nodes[max_layer + 1:] == 0).all(), nodes
+    match_slide_clear(o, r, P, np.random.default_rng(62), p, centre=(4.5, 4.2, 0.7), least_ok=-1)
+    o.close()
+    r.close()
+
+
+@pytest.mark.parametrize("name", offconfig.CRAFTED)
+def test_update_voxel_map_corner_site_matches_the_reference(name):
+    """Three perpendicular thin sheets (offconfig.CornerSites): planes AND build_single_residual successes on every layer
+    1 .. max_layer of a five- / four-level tree, then matching, sliding and clearing on that deep map."""
+    P = offconfig.params(name)
+    L = P["max_layer"]
+    site = offconfig.CornerSites(seed=71)
+    p, var = site.points()
+    o, r = fed_pair(P, [(p, var)])
+    cm = scenes.canon_map(r.map_export())
+    assert offconfig.depth(cm) == L + 1
+    nodes, planes = offconfig.layer_counts(cm)
+    print(name, "nodes per layer", nodes, "planes per layer", planes)
+    assert (nodes[: L + 1] > 0).all() and (planes[1: L + 1] > 0).all(), (nodes, planes)
+    q, qv = site.fresh(1, n_per_sheet=1334)
+    vs_f = float(np.float32(P["voxel_size"]))
+    per_layer = {}
+    for pt, V in zip(q[:4000], qv[:4000]):
+        match_one(o, r, ob.key_floor(pt, vs_f), pt, V, per_layer)
+    print(name, "matches per layer", per_layer)
+    assert all(per_layer.get(l, 0) >= 100 for l in range(1, L + 1)), per_layer
+    match_slide_clear(o, r, P, np.random.default_rng(72), p, centre=(4.5, 4.2, 0.7), least_ok=100)
+    o.close()
+    r.close()
+
+
+def test_update_voxel_map_face_lattice_matches_the_reference():
+    """Points exactly on the faces of a 0.4 m grid: UpdateVoxelMap divides by the float voxel size (voxel_map.cc:337), so the
+    root keys are not floor(p / 0.4) - oracle and reference agree on them, and the double divisor would not."""
+    P = offconfig.params("vs04")
+    p, var = offconfig.face_lattice(P["voxel_size"])
+    cfg = config.make_config(P)
+    o, r = ob.Oracle(cfg), ob.Reference(cfg)
+    for obj in (o, r):
+        obj.map_update(p, var)
+    ko, kr = set(scenes.canon_map(o.map_export())), set(scenes.canon_map(r.map_export()))
+    assert ko == kr and len(ko) > 250, (len(ko), len(kr))
+    naive = offconfig.naive_keys(p, P["voxel_size"])
+    assert len(ko ^ naive) >= 10, len(ko ^ naive)
+    print("face lattice:", len(ko), "root voxels;", len(ko ^ naive), "entries differ from floor(p / 0.4)")
+    scenes.compare_maps(o.map_export(), r.map_export(), rtol=1e-6, ptol=1e-9)
     o.close()
     r.close()
 
@@ -279,13 +376,8 @@ def kilo_pair(sc, imu_only, tmp_path):
     return o, k
 
 
-@pytest.mark.parametrize("use_kin", [False, True])
-def test_kilo_process_matches_the_reference(tmp_path, use_kin):
-    """The reference's own KILO::process (KILO.cc:316-399) - time sort, bucket loop with interleaved IMU or
-    kinematic+IMU updates, predictUpdatePoint (:108-233: transform, covariances, float-truncated key, one-neighbour
-    retry with its unit mismatch, observation rows, literal N x N update, re-projection, map insert) - replays the same
-    config-1 style scans as the oracle: identical match counts every scan, states to 1e-8, identical map."""
-    sc = scenes.Scene(params=dict(config.DITER, voxel_grid_resolution=0.3) if use_kin else None)
+def kilo_process_case(tmp_path, use_kin, name=None, least_effect=500):
+    sc = offconfig.scene(name, use_kin)
     o, k = kilo_pair(sc, not use_kin, tmp_path)
     t0 = 1.0
     for obj in (o, k):
@@ -293,10 +385,11 @@ def test_kilo_process_matches_the_reference(tmp_path, use_kin):
         scenes.first_frame(obj, sc, t0, x0)
     scenes.compare_maps(o.map_export(), k.map_export(), rtol=1e-6, ptol=1e-9)
     n_scans = 4
-    ro = scenes.replay_vlp(o, sc, t0, n_scans, use_kin=use_kin)
-    rk = scenes.replay_vlp(k, sc, t0, n_scans, use_kin=use_kin)
+    zo, zk = (None, None) if name is None else (offconfig.ZeroZ(), offconfig.ZeroZ())
+    ro = scenes.replay_vlp(o, sc, t0, n_scans, use_kin=use_kin, scan_input=zo)
+    rk = scenes.replay_vlp(k, sc, t0, n_scans, use_kin=use_kin, scan_input=zk)
     for s, ((po, xo), (pk, xk)) in enumerate(zip(ro, rk)):
-        assert po.n_effect == pk.n_effect > 500, (s, po.n_effect, pk.n_effect)
+        assert po.n_effect == pk.n_effect > least_effect, (s, po.n_effect, pk.n_effect)
         assert np.allclose(xo, xk, rtol=1e-8, atol=1e-9), (s, np.abs(xo - xk).max())
     (_, Po), (_, Pk) = o.get_state(), k.get_state()
     assert np.allclose(Po, Pk, rtol=1e-6, atol=1e-12), np.abs(Po - Pk).max()
@@ -305,6 +398,31 @@ def test_kilo_process_matches_the_reference(tmp_path, use_kin):
     assert st["roots"] > 500
     o.close()
     k.close()
+    if zo is not None:
+        print(f"{name} use_kin={use_kin}: n_effect {[int(p.n_effect) for p, _ in ro]}, z == 0 path points {zo.n_zero} of {zo.n_pts}")
+        assert zo.n_zero == zk.n_zero
+        return zo.n_zero
+    return 0
+
+
+@pytest.mark.parametrize("use_kin", [False, True])
+def test_kilo_process_matches_the_reference(tmp_path, use_kin):
+    """The reference's own KILO::process (KILO.cc:316-399) - time sort, bucket loop with interleaved IMU or
+    kinematic+IMU updates, predictUpdatePoint (:108-233: transform, covariances, float-truncated key, one-neighbour
+    retry with its unit mismatch, observation rows, literal N x N update, re-projection, map insert) - replays the same
+    config-1 style scans as the oracle: identical match counts every scan, states to 1e-8, identical map."""
+    kilo_process_case(tmp_path, use_kin)
+
+
+@pytest.mark.parametrize("name", offconfig.CLOSED_LOOP)
+def test_kilo_process_matches_the_reference_off_config(tmp_path, name):
+    """The same, away from the shipped yaml files (tests/offconfig.py): tilted 6-decimal extrinsic rotation, voxel size 0.4 (the
+    residual side hashes with the double, the insert with its float cast), trees of depth 1 and 4 with per-layer thresholds,
+    other gate constants, each in IMU-only and in leg-fusion mode; z = 0 forced on every 37th raw point, so calcBodyCov's guard
+    (voxel_map.cc:23) runs on >= 1 000 path points over the two runs (~740 of ~19 500 survive the voxel grid in each).  This is what
+    makes the oracle a checker at these configurations for tests/test_config_space.py."""
+    n_zero = sum(kilo_process_case(tmp_path, use_kin, name, least_effect=300) for use_kin in (False, True))
+    assert n_zero >= 1000, n_zero
 
 
 @pytest.mark.parametrize("imu_only", [True, False])

@@ -88,7 +88,7 @@ typedef struct lk_config {
     /* device side */
     int32_t device_id;              /* HIP device ordinal */
     uint32_t n_slots;               /* filter slots (>=1); >1 only for batch replay */
-    uint32_t max_roots;             /* root voxels the hash must hold (table = next pow2 of 2x) */
+    uint32_t max_roots;             /* root voxels the hash must hold (table = next pow2 of 8x) */
     uint32_t max_nodes;             /* octree nodes (roots + children) */
     uint32_t max_point_blocks;      /* per-leaf point blocks of LK_BLOCK_PTS points */
     uint32_t max_scan_points;       /* points of the largest scan / bucket batch */
@@ -251,7 +251,10 @@ int lk_match_points(lk_handle* h, size_t n, const int32_t* keys3, const double* 
 int lk_map_stats(lk_handle* h, uint32_t* n_roots, uint32_t* n_nodes, uint32_t* n_blocks);
 int lk_map_export(lk_handle* h, void* blob, size_t* bytes);            /* blob==NULL: size query */
 int lk_map_import(lk_handle* h, const void* blob, size_t bytes);
-/* device-resident blob for the RCCL broadcast (no host staging) */
+/* device-resident blob for the RCCL broadcast (no host staging): lk_blob_header (version | 0x100) | the handle's whole root hash table
+ * (16-byte entries: key x, y, z, root node id or a negative value for a free entry) | nodes | planes | blocks, the three pools as in
+ * lk_map_export's blob.  d_blob == NULL: size query; *bytes is rounded up to a multiple of 256, and the bytes behind the last block
+ * record are padding that is not written.  Only a handle with the same max_roots can import it. */
 int lk_map_export_dev(lk_handle* h, void* d_blob, size_t* bytes);
 int lk_map_import_dev(lk_handle* h, const void* d_blob, size_t bytes);
 
@@ -275,7 +278,9 @@ int lk_process_scan_dev(lk_handle* h, const lk_point* d_pts, size_t n, double t_
 /* ---- sensor decode: LidarProcessing::{velodyne,ouster,hesai}Handler, lidar_processing.cc:25-108 ----
  * msg_data = sensor_msgs::PointCloud2::data (n_points x point_step bytes).  Keeps every filter_num-th point that is
  * outside the blind radius (lidar_processing.h:96-98), curvature = round((t - t_first) * 500) / 500 in the arithmetic
- * type of the respective handler, input order preserved.  begin/end = LidarScan::lidar_begin_time_/lidar_end_time_. */
+ * type of the respective handler, input order preserved.  begin/end = LidarScan::lidar_begin_time_/lidar_end_time_.
+ * out / d_out must hold n_points records and the first *n_out are the result.  Behind them, the host entry leaves `out` as it was; the
+ * rest of d_out's room is the device entry's to use (undefined afterwards). */
 typedef struct lk_cloud_layout {
     uint32_t point_step;
     uint32_t off_x, off_y, off_z;   /* float32 fields */

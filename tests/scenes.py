@@ -98,6 +98,14 @@ def replay_vlp(obj, scene, t0, n_scans, use_kin=False, start=0, collect=None, sc
     return out
 
 
+def mature_oracle_map(o, scene, t0, n_scans=10):
+    """The map an oracle holds after the first frame at t0 and n_scans replayed 10 Hz scans, as a blob (the filter is left where the run ended)."""
+    x0 = init_filter(o, scene, t0)
+    first_frame(o, scene, t0, x0)
+    replay_vlp(o, scene, t0, n_scans)
+    return o.map_export()
+
+
 def corner_clutter(rng, n_cells=60, per_cell=80, origin=(5.0, 5.0, 1.0)):
     """Points clustered at the 8 corners of random 0.25 m cells: per-axis variance 0.1125^2 > min_eigen_value
     (0.01), so layer-0 AND layer-1 nodes are non-planar and the octree is cut down to layer 2."""

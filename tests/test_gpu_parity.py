@@ -233,11 +233,7 @@ def test_map_update_surface(pair, scene):
 
 
 # ----------------------------------------------------------------------------- residuals (config 2, reduced)
-def mature_oracle_map(o, scene, t0, n_scans=10):
-    x0 = scenes.init_filter(o, scene, t0)
-    scenes.first_frame(o, scene, t0, x0)
-    scenes.replay_vlp(o, scene, t0, n_scans)
-    return o.map_export()
+mature_oracle_map = scenes.mature_oracle_map
 
 
 def test_residuals_on_imported_map(pair, scene):

@@ -1751,43 +1751,33 @@ __global__ void lk_set_times_kernel(LkFilter* filters, int n, double t) {
     if (s < n) filters[s].last_predict_t = t, filters[s].last_update_t = t;
 }
 
-int lk_batch_replay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, size_t n_pts, double t_begin,
-                        const uint32_t* bucket_off, const double* bucket_dt, size_t n_buckets, lk_pose* out) {
-    CHECK_H(h);
-    if (n_scans == 0 || n_scans > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_scans must be in [1, n_slots]");
-    if (n_pts == 0 || n_buckets == 0) return fail(h, LK_ERR_INVALID, "empty scans");
-    const int S = (int)n_scans;
-    LkMap fmap;
-    int rc = frozen_map(h, &fmap);
-    if (rc) return rc;
-    rc = zero_scan_counters(h, 0, (uint32_t)n_scans);
-    if (rc) return rc;
+// The frozen-map bucket chain of `sn` slots from filter slot `s0` on, all of it on stream `st`: predict -> (residual -> update + next predict) per
+// live bucket - update(k) and predict(k+1) share one launch (the map is frozen: nothing reads the state in between).  pts / alt_pts: the first
+// point of slot s0 in the caller's buffer and in the library's voxel-ordered copy (null: none); ro: what batch_ordered filled in.
+// named: through launch() as "predict" / "residual" / "update" (what lk_profile_get hands back: the one-stream synchronous path); else plain
+// launches, checked once at the end.
+static int enqueue_frozen_chain(lk_handle* h, hipStream_t st, bool named, uint32_t s0, int sn, const lk_point* pts, const lk_point* alt_pts, size_t n_pts,
+                                const std::vector<size_t>& live, const uint32_t* bucket_off, const double* bucket_dt, double t_begin, const LkMap& fmap,
+                                ResidualOut ro) {
+    const auto go = [&](const char* name, auto&& f) -> int {
+        if (named) return launch(h, name, f);
+        f();
+        return LK_OK;
+    };
     const auto res_kernel = batch_residual_kernel(h, fmap);
-    hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, h->stream, h->d_filters, S, t_begin);
-    HIPCHK(h, hipGetLastError());
-    ResidualOut ro;
-    memset(&ro, 0, sizeof(ro));
-    rc = batch_ordered(h, d_pts, 0, n_scans, n_pts, bucket_off, n_buckets, h->stream, &ro);   // the caller's buffer, or the library's voxel-ordered copy of it
-    if (rc) return rc;
-    const lk_point* const alt_base = ro.alt_pts;
-    // non-empty buckets; update(k) and predict(k+1) share one launch (the map is frozen: nothing reads the state in between)
-    std::vector<size_t> live;
-    for (size_t b = 0; b < n_buckets; ++b) {
-        if (bucket_off[b + 1] <= bucket_off[b]) continue;
-        if ((size_t)(bucket_off[b + 1] - bucket_off[b]) > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
-        live.push_back(b);
-    }
-    // Slot groups on separate HIP streams (default 3 — measured best of 1..8 on MI355X; LEGKILO_REPLAY_GROUPS=1..4 overrides): the single-workgroup update/predict kernels of one group (half of the CUs
-    // idle, latency-bound) overlap the residual kernel of the other group.  Groups touch disjoint filters / partials and
-    // only read the map.  Profiling mode (per-launch events + sync) and small batches stay on one stream.
-    const int ngroups = (!h->profiling && S >= 2 * h->replay_groups) ? h->replay_groups : 1;
-    hipStream_t streams[lk_handle::kMaxGroups];
-    streams[0] = h->stream;
-    for (int g = 1; g < lk_handle::kMaxGroups; ++g) streams[g] = h->side[g - 1];
-    if (ngroups > 1) {
-        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-        for (int g = 1; g < ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(streams[g], h->ev_fork, 0));
-    }
+    const bool wave = h->wave_update;   // the single-wave update kernel, or the 256-thread pair (LEGKILO_UPDATE_CLASSIC=1)
+    LkFilter* fl = h->d_filters + s0;
+    double* parts = h->d_partials + (size_t)s0 * h->part_stride;
+    // the update at time t over n_tiles partial sums and / or the predict to t_next.  Last argument - wave kernel: 1 update, 2 predict, 3 both;
+    // classic update kernel: 1 = predict after the update
+    const auto update = [&](int n_tiles, double t, double t_next, bool upd, bool pred) {
+        if (wave)
+            hipLaunchKernelGGL(lk_update_wave_kernel, dim3(sn), dim3(LK_WAVE), 0, st, fl, parts, n_tiles, h->part_stride, t, h->d_Q, t_next, (upd ? 1 : 0) | (pred ? 2 : 0));
+        else if (upd)
+            hipLaunchKernelGGL(lk_update_kernel, dim3(sn), dim3(LK_FB), 0, st, fl, parts, n_tiles, h->part_stride, t, h->d_Q, t_next, pred ? 1 : 0);
+        else
+            hipLaunchKernelGGL(lk_predict_kernel, dim3(sn), dim3(LK_FB), 0, st, fl, h->d_Q, t_next);
+    };
     for (size_t k = 0; k < live.size(); ++k) {
         const size_t b = live[k];
         const int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
@@ -1795,63 +1785,43 @@ int lk_batch_replay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, siz
         const bool has_next = k + 1 < live.size();
         const double t_next = has_next ? t_begin + bucket_dt[live[k + 1]] : 0.0;
         const int nblk = (nb + LK_RB - 1) / LK_RB;
-        for (int grp = 0; grp < ngroups; ++grp) {
-            const int s0 = (int)((long)S * grp / ngroups), sn = (int)((long)S * (grp + 1) / ngroups) - s0;
-            hipStream_t st = streams[grp];
-            LkFilter* fl = h->d_filters + s0;
-            double* parts = h->d_partials + (size_t)s0 * h->part_stride;
-            const lk_point* pts = d_pts + (size_t)s0 * n_pts + bucket_off[b];
-            ro.alt_pts = alt_base ? alt_base + (size_t)s0 * n_pts + bucket_off[b] : nullptr;
-            if (ngroups == 1) {
-                if (k == 0) {
-                    if (h->wave_update)
-                        LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(sn), dim3(LK_WAVE), 0, st, fl, parts, 0,
-                                                                h->part_stride, 0.0, h->d_Q, t, 2));
-                    else
-                        LAUNCH(h, "predict", hipLaunchKernelGGL(lk_predict_kernel, dim3(sn), dim3(LK_FB), 0, st, fl, h->d_Q, t));
-                }
-                const dim3 rgrid = batch_residual_grid(nblk, sn, &ro);
-                LAUNCH(h, "residual", hipLaunchKernelGGL(res_kernel, rgrid, dim3(LK_RB), 0, st, fmap, h->pr, fl,
-                                                         pts, n_pts, nb, parts, h->part_stride, ro, (size_t)0));
-                if (h->wave_update)
-                    LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(sn), dim3(LK_WAVE), 0, st, fl, parts,
-                                                           nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q, t_next, has_next ? 3 : 1));
-                else
-                    LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_kernel, dim3(sn), dim3(LK_FB), 0, st, fl, parts,
-                                                           nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q, t_next, has_next ? 1 : 0));
-            } else {
-                if (k == 0) {
-                    if (h->wave_update)
-                        hipLaunchKernelGGL(lk_update_wave_kernel, dim3(sn), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q, t, 2);
-                    else
-                        hipLaunchKernelGGL(lk_predict_kernel, dim3(sn), dim3(LK_FB), 0, st, fl, h->d_Q, t);
-                }
-                const dim3 rgrid = batch_residual_grid(nblk, sn, &ro);
-                hipLaunchKernelGGL(res_kernel, rgrid, dim3(LK_RB), 0, st, fmap, h->pr, fl, pts, n_pts, nb, parts,
-                                   h->part_stride, ro, (size_t)0);
-                if (h->wave_update)
-                    hipLaunchKernelGGL(lk_update_wave_kernel, dim3(sn), dim3(LK_WAVE), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE),
-                                       h->part_stride, t, h->d_Q, t_next, has_next ? 3 : 1);
-                else
-                    hipLaunchKernelGGL(lk_update_kernel, dim3(sn), dim3(LK_FB), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t,
-                                       h->d_Q, t_next, has_next ? 1 : 0);
-            }
-        }
+        if (k == 0) LKCHK(go("predict", [&]() { update(0, 0.0, t, false, true); }));
+        ro.alt_pts = alt_pts ? alt_pts + bucket_off[b] : nullptr;
+        const dim3 rgrid = batch_residual_grid(nblk, sn, &ro);
+        LKCHK(go("residual", [&]() { hipLaunchKernelGGL(res_kernel, rgrid, dim3(LK_RB), 0, st, fmap, h->pr, fl, pts + bucket_off[b], n_pts, nb, parts, h->part_stride, ro, (size_t)0); }));
+        LKCHK(go("update", [&]() { update(nblk * (LK_RB / LK_WAVE), t, t_next, true, has_next); }));
     }
     HIPCHK(h, hipGetLastError());
-    for (int g = 1; g < ngroups; ++g) {  // join: everything after this point on h->stream sees every group's results
-        HIPCHK(h, hipEventRecord(h->ev_join[g - 1], streams[g]));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0));
-    }
-    if (out) {
-        std::vector<lk_pose> tmp(n_scans);
-        rc = fetch_poses(h, tmp.data(), S);
-        if (rc) return rc;
-        memcpy(out, tmp.data(), sizeof(lk_pose) * n_scans);
-    } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
     return LK_OK;
+}
+
+int lk_batch_replay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, size_t n_pts, double t_begin,
+                        const uint32_t* bucket_off, const double* bucket_dt, size_t n_buckets, lk_pose* out) {
+    CHECK_H(h);
+    if (n_scans == 0 || n_scans > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_scans must be in [1, n_slots]");
+    if (n_pts == 0 || n_buckets == 0) return fail(h, LK_ERR_INVALID, "empty scans");
+    const int S = (int)n_scans;
+    std::vector<size_t> live;
+    LKCHK(live_buckets(h, bucket_off, n_buckets, live));   // all checks before the first enqueue
+    LkMap fmap;
+    LKCHK(frozen_map(h, &fmap));
+    LKCHK(zero_scan_counters(h, 0, (uint32_t)n_scans));
+    hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, h->stream, h->d_filters, S, t_begin);
+    HIPCHK(h, hipGetLastError());
+    ResidualOut ro;
+    memset(&ro, 0, sizeof(ro));
+    LKCHK(batch_ordered(h, d_pts, 0, n_scans, n_pts, bucket_off, n_buckets, h->stream, &ro));   // the caller's buffer, or the library's voxel-ordered copy of it
+    // the single-workgroup update / predict kernels of one group (half of the CUs idle, latency-bound) overlap the residual kernel of the other group
+    const SlotGroups grp(h, S, h->replay_groups, kReplayGroupSlots);
+    LKCHK(grp.fork());
+    int rc = LK_OK;
+    for (int g = 0; g < grp.n && rc == LK_OK; ++g) {
+        const size_t p0 = (size_t)grp.first(g) * n_pts;
+        rc = enqueue_frozen_chain(h, grp.stream[g], grp.n == 1, (uint32_t)grp.first(g), grp.count(g), d_pts + p0, ro.alt_pts ? ro.alt_pts + p0 : nullptr, n_pts, live,
+                                  bucket_off, bucket_dt, t_begin, fmap, ro);
+    }
+    LKCHK(grp.join(rc));
+    return fetch_poses_or_sync(h, out, S);
 }
 
 // Config 2 at bandwidth size: the residual build of KILO.cc:122-210 - transform, covariance terms, voxel lookup, plane match with the one
@@ -1881,6 +1851,15 @@ int lk_batch_residuals_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, 
                                                   h->d_partials, h->part_stride, ro, n_pts));
     HIPCHK(h, hipGetLastError());
     return LK_OK;
+}
+
+// What an LkRagged takes from the handle, whatever built its tables: the message stride, the measurement noises, the gravity scale, Q's shape.
+static void rag_from_handle(const lk_handle* h, size_t msg_bytes, LkRagged* rg) {
+    rg->msg_stride = (int)(msg_bytes / sizeof(double));
+    rg->kin_noise = h->cfg.kin_meas_noise;
+    rg->q_diag = h->q_diag ? 1 : 0;
+    rg->acc_scale = h->cfg.gravity / h->acc_norm;
+    imu_noise(h->cfg, rg->Rn);
 }
 
 // The launches of a ragged batch once its tables (padded or CSR, LkRagged) are in HBM.  msg_kind: 0 none, 1 lk_imu, 2 lk_kin_imu.
@@ -1929,13 +1908,7 @@ static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const Lk
                            (int)b);
     }
     HIPCHK(h, hipGetLastError());
-    if (out) {
-        rc = fetch_poses(h, out, (int)S);
-        if (rc) return rc;
-    } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return LK_OK;
+    return fetch_poses_or_sync(h, out, (int)S);
 }
 
 // Ragged batch replay: the scans of a recorded run differ in size, in their time buckets and in their start time.  One
@@ -2034,11 +2007,7 @@ int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uin
     rg.ldb = (int)ldb;
     rg.imu_off = n_imu ? dv.io : nullptr;
     rg.imu = reinterpret_cast<const double*>(dv.im);
-    rg.msg_stride = (int)(msg_bytes / sizeof(double));
-    rg.kin_noise = h->cfg.kin_meas_noise;
-    rg.q_diag = h->q_diag ? 1 : 0;
-    rg.acc_scale = h->cfg.gravity / h->acc_norm;
-    imu_noise(h->cfg, rg.Rn);
+    rag_from_handle(h, msg_bytes, &rg);
     rg.bstart = nullptr;
     if (with_insert) {
         size_t max_scan_pts = 0;
@@ -2167,11 +2136,7 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     rg.bstart = d_bs;
     rg.imu_off = msg_kind ? d_mo : nullptr;
     rg.imu = reinterpret_cast<const double*>(d_ms);
-    rg.msg_stride = (int)(msg_bytes / sizeof(double));
-    rg.kin_noise = h->cfg.kin_meas_noise;
-    rg.q_diag = h->q_diag ? 1 : 0;
-    rg.acc_scale = h->cfg.gravity / h->acc_norm;
-    imu_noise(h->cfg, rg.Rn);
+    rag_from_handle(h, msg_bytes, &rg);
     return ragged_launch(h, d_pts, S, rg, d_t0, (int)biggest, (size_t)most, nullptr, msg_kind, out);
 }
 
@@ -2190,14 +2155,10 @@ int lk_batch_replay_async_dev(lk_handle* h, const lk_point* d_pts, uint32_t firs
     if (!d_pts || !bucket_off || !bucket_dt) return fail(h, LK_ERR_INVALID, "null argument");
     if ((d_x36 == nullptr) != (d_P900 == nullptr)) return fail(h, LK_ERR_INVALID, "give both prior buffers or neither");
     const int S = (int)n_scans;
-    for (size_t b = 0; b < n_buckets; ++b)   // all checks before the first enqueue
-        if (bucket_off[b + 1] > bucket_off[b] && (size_t)(bucket_off[b + 1] - bucket_off[b]) > h->map.max_scan)
-            return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
+    std::vector<size_t> live;
+    LKCHK(live_buckets(h, bucket_off, n_buckets, live));   // all checks before the first enqueue
     LkMap fmap;
-    {
-        const int rc = frozen_map(h, &fmap);   // synchronises once per map snapshot (grid rebuild), otherwise free
-        if (rc) return rc;
-    }
+    LKCHK(frozen_map(h, &fmap));   // synchronises once per map snapshot (grid rebuild), otherwise free
     // batches on slot ranges 0, n, 2n, ... rotate over up to three streams (the handle's + two side streams): with three batches in
     // flight there is (almost) always a residual launch ready while the other two sit in their update / predict launches
     // The stream is a function of (first_slot, n_scans): two batches in flight on overlapping slots are ordered only if they
@@ -2213,7 +2174,6 @@ int lk_batch_replay_async_dev(lk_handle* h, const lk_point* d_pts, uint32_t firs
     const uint32_t ring = (first_slot / (uint32_t)n_scans) % 3u;
     hipStream_t st = ring == 0 ? h->stream : h->side[ring - 1];
     LkFilter* fl = h->d_filters + first_slot;
-    double* parts = h->d_partials + (size_t)first_slot * h->part_stride;
     if (st != h->stream && !d_x36) {
         // the slots' state was armed elsewhere (lk_batch_set_priors_dev is asynchronous on the MAIN stream): order this batch
         // after it.  With d_x36 / d_P900 the batch arms its own slots on its own stream and needs no such edge - which is
@@ -2229,40 +2189,8 @@ int lk_batch_replay_async_dev(lk_handle* h, const lk_point* d_pts, uint32_t firs
     hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, st, fl, S, t_begin);
     ResidualOut ro;
     memset(&ro, 0, sizeof(ro));
-    {
-        const int rc = batch_ordered(h, d_pts, first_slot, n_scans, n_pts, bucket_off, n_buckets, st, &ro);   // first sight of a batch synchronises; afterwards one small launch
-        if (rc) return rc;
-    }
-    const lk_point* const alt_base = ro.alt_pts;
-    bool first = true;
-    for (size_t b = 0; b < n_buckets; ++b) {
-        if (bucket_off[b + 1] <= bucket_off[b]) continue;
-        const int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
-        ro.alt_pts = alt_base ? alt_base + bucket_off[b] : nullptr;
-        size_t nx = b + 1;
-        while (nx < n_buckets && bucket_off[nx + 1] <= bucket_off[nx]) ++nx;
-        const bool has_next = nx < n_buckets;
-        const double t = t_begin + bucket_dt[b], t_next = has_next ? t_begin + bucket_dt[nx] : 0.0;
-        const int nblk = (nb + LK_RB - 1) / LK_RB;
-        if (first) {
-            if (h->wave_update)
-                hipLaunchKernelGGL(lk_update_wave_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q, t, 2);
-            else
-                hipLaunchKernelGGL(lk_predict_kernel, dim3(S), dim3(LK_FB), 0, st, fl, h->d_Q, t);
-        }
-        first = false;
-        const auto res_kernel = batch_residual_kernel(h, fmap);
-        const dim3 rgrid = batch_residual_grid(nblk, S, &ro);
-        hipLaunchKernelGGL(res_kernel, rgrid, dim3(LK_RB), 0, st, fmap, h->pr, fl, d_pts + bucket_off[b], n_pts, nb, parts,
-                           h->part_stride, ro, (size_t)0);
-        if (h->wave_update)
-            hipLaunchKernelGGL(lk_update_wave_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t,
-                               h->d_Q, t_next, has_next ? 3 : 1);
-        else
-            hipLaunchKernelGGL(lk_update_kernel, dim3(S), dim3(LK_FB), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q,
-                               t_next, has_next ? 1 : 0);
-    }
-    HIPCHK(h, hipGetLastError());
+    LKCHK(batch_ordered(h, d_pts, first_slot, n_scans, n_pts, bucket_off, n_buckets, st, &ro));   // first sight of a batch synchronises; afterwards one small launch
+    LKCHK(enqueue_frozen_chain(h, st, false, first_slot, S, d_pts, ro.alt_pts, n_pts, live, bucket_off, bucket_dt, t_begin, fmap, ro));
     if (host_out) {
         hipLaunchKernelGGL(lk_pose_gather_kernel, dim3((S + 63) / 64), dim3(64), 0, st, fl, h->d_poses + first_slot, S);
         HIPCHK(h, hipGetLastError());

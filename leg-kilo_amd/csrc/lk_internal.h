@@ -389,3 +389,70 @@ int ov_scan_launch(lk_handle* h, bool xid, int S, hipStream_t st, const LkMap& f
 int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const LkRagged& rg, const double* d_tbegin, int biggest, size_t ldb, const int* max_n,
                           size_t max_scan_pts, int msg_kind, lk_pose* out);
 }
+
+// The tail of a synchronous batch entry: the poses if the caller wants them (fetch_poses synchronises), else only the wait.
+static inline int fetch_poses_or_sync(lk_handle* h, lk_pose* out, int n) {
+    if (out) return fetch_poses(h, out, n);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+
+// The non-empty buckets of a uniform batch (the empty ones are skipped by every entry), none above max_scan_points; *biggest: the largest of them.
+// entry_check(b): what the calling entry asks of every bucket, empty ones included, before this bucket's size is looked at.
+template <class Check>
+static inline int live_buckets(lk_handle* h, const uint32_t* bucket_off, size_t n_buckets, std::vector<size_t>& live, size_t* biggest, Check&& entry_check) {
+    for (size_t b = 0; b < n_buckets; ++b) {
+        LKCHK(entry_check(b));
+        if (bucket_off[b + 1] <= bucket_off[b]) continue;
+        const size_t nb = (size_t)(bucket_off[b + 1] - bucket_off[b]);
+        if (nb > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
+        if (biggest) *biggest = std::max(*biggest, nb);
+        live.push_back(b);
+    }
+    return LK_OK;
+}
+static inline int live_buckets(lk_handle* h, const uint32_t* bucket_off, size_t n_buckets, std::vector<size_t>& live) {
+    return live_buckets(h, bucket_off, n_buckets, live, nullptr, [](size_t) { return LK_OK; });
+}
+
+// Slot groups of a synchronous batch replay: the batch's slots cut into `n` ranges, range g on stream g (the handle's own, then side[]).  The scans are
+// independent, so the groups touch disjoint filters, partials and pools and only read the map.  Profiling mode (per-launch events + sync on the
+// handle's stream) and small batches stay on one stream:
+//   frozen map: h->replay_groups groups (3: measured best of 1..8; LEGKILO_REPLAY_GROUPS) from kReplayGroupSlots slots per group on;
+//   overlay:    kOverlayGroups from kOverlayGroupSlots slots per group on.
+// fork() makes the side streams wait for what the handle's stream holds so far (if it fails, nothing of this call is on a side stream yet and the
+// entry just returns), join(rc) takes what the enqueue in between returned: on success the handle's stream waits for every group; on failure every
+// stream is waited for HERE - a failed launch must not leave the side streams writing filters, partials and pools behind the caller's back.
+// Nothing a caller can observe says whether a batch was split: tests/test_gpu_parity.py (OV_GROUPS, OV_GROUP_SLOTS of test_batch_replay_overlay[groups];
+// S = 6 / 7 of test_batch_replay_frozen_map) and tests/test_dev_bounds.py size their batches by these values - change them together.
+constexpr int kReplayGroupSlots = 2, kOverlayGroups = 4, kOverlayGroupSlots = 64;
+static_assert(kOverlayGroups <= lk_handle::kMaxGroups, "a stream per group");
+struct SlotGroups {
+    lk_handle* h;
+    int S, n;
+    hipStream_t stream[lk_handle::kMaxGroups];
+    SlotGroups(lk_handle* h_, int S_, int groups, int min_slots_per_group) : h(h_), S(S_), n((!h_->profiling && S_ >= min_slots_per_group * groups) ? groups : 1) {
+        stream[0] = h->stream;
+        for (int g = 1; g < lk_handle::kMaxGroups; ++g) stream[g] = h->side[g - 1];
+    }
+    int first(int g) const { return (int)((long)S * g / n); }
+    int count(int g) const { return first(g + 1) - first(g); }
+    int fork() const {
+        if (n > 1) HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+        for (int g = 1; g < n; ++g) HIPCHK(h, hipStreamWaitEvent(stream[g], h->ev_fork, 0));
+        return LK_OK;
+    }
+    int join(int rc) const {
+        if (rc == LK_OK) rc = wait_for_groups();
+        if (rc != LK_OK)
+            for (int g = 0; g < n; ++g) (void)hipStreamSynchronize(stream[g]);   // error path: nothing of this call keeps running
+        return rc;
+    }
+    int wait_for_groups() const {   // everything after this point on h->stream sees every group's results
+        for (int g = 1; g < n; ++g) {
+            HIPCHK(h, hipEventRecord(h->ev_join[g - 1], stream[g]));
+            HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0));
+        }
+        return LK_OK;
+    }
+};

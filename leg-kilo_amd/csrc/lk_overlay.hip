@@ -299,6 +299,103 @@ static LkOverlay ov_at(const LkOverlay& o, size_t s0) {
     r.ptroot += s0 * o.scan_cap;
     return r;   // frozen, base_sums, newroot, spec: shared by all slots
 }
+// ---- what the two replays with insert share (lk_batch_replay_overlay_dev, overlay_ragged_launch): the scaffold around an attempt's launches.
+// A scan whose overlay outgrows pools that were sized by this library (first guess, or the previous replay's high-water marks) makes the
+// pools grow and the whole batch run again from its priors - only capacities the caller has set explicitly (lk_overlay_reserve) fail with
+// LK_ERR_CAPACITY.
+
+// The residual pass with the overlay lookup, specialised for ext_R == I where it holds (LEGKILO_XID=0: the generic one).
+static auto ov_residual_kernel(const lk_handle* h) {
+    return (h->pr.ext_identity && lk_xid_enabled()) ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
+}
+// Before the first attempt: the frozen map with its grid, pools for S scans of n_pts_scan points, the batch's priors put aside.
+static int ov_replay_begin(lk_handle* h, int S, size_t n_pts_scan, size_t biggest, LkMap* fmap) {
+    LKCHK(join_side_streams(h));   // an asynchronous frozen-map batch may still be using the filter slots
+    LKCHK(frozen_map(h, fmap));
+    if (!fmap->grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
+    LKCHK(ov_reserve(h, (uint32_t)S, n_pts_scan, biggest, *fmap));
+    LKCHK(reserve(h, h->ov_priors, sizeof(LkFilter) * (size_t)S));
+    HIPCHK(h, hipMemcpyAsync(h->ov_priors.p, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
+    return LK_OK;
+}
+// Head of an attempt: scan counters, start times (d_tbegin: one per scan; null: t_begin for all), the frozen bits and the base map's leaf sums.
+static int ov_attempt_begin(lk_handle* h, int S, const LkMap& fmap, const double* d_tbegin, double t_begin) {
+    const LkOverlay& ov = h->ov;
+    hipStream_t st = h->stream;
+    LKCHK(zero_scan_counters(h, 0, (uint32_t)S));
+    if (d_tbegin) hipLaunchKernelGGL(lk_set_times_ragged_kernel, dim3((S + 63) / 64), dim3(64), 0, st, h->d_filters, S, d_tbegin);
+    else hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, st, h->d_filters, S, t_begin);
+    HIPCHK(h, hipMemsetAsync(ov.frozen, 0, (size_t)2 * ov.bit_words * sizeof(unsigned int), st));
+    // both bits of every cell (LkOverlay::frozen): frozen leaf, and takes the point at the root
+    LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, 1));
+    LAUNCH(h, "ov_base_sums", hipLaunchKernelGGL(lk_ov_base_sums_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, ov.base_sums));
+    return LK_OK;
+}
+// The status words of the first S slots' overlays: [0] error bits of any slot, [1..3] largest use of nodes / blocks / roots, [4] first slot with an error.  Synchronises.
+static int ov_read_status(lk_handle* h, unsigned int S, unsigned int* stt) {
+    const unsigned int init[8] = {0u, 0u, 0u, 0u, 0xffffffffu, 0u, 0u, 0u};
+    HIPCHK(h, hipMemcpyAsync(h->d_ov_status, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(lk_ov_status_kernel, dim3(std::min((S + 255u) / 256u, 64u)), dim3(256), 0, h->stream, h->ov, S, h->d_ov_status);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(stt, h->d_ov_status, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+// Tail of an attempt, from its status.  *again: pools the library sized have overflowed - they have grown, the priors are back, run the
+// attempt once more.  Otherwise the replay is over: high-water marks for the next one's pools, the poses, and the slots' errors if any.
+static int ov_attempt_end(lk_handle* h, int S, int attempt, const unsigned int* stt, size_t n_pts_scan, size_t biggest, const LkMap& fmap, lk_pose* out, bool* again) {
+    const bool growable = !h->ov_want_roots && !(stt[0] & ~(LK_E_HASH_FULL | LK_E_NODES_FULL | LK_E_BLOCKS_FULL)) && attempt < 4;
+    *again = stt[0] && growable;
+    if (*again) {
+        HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
+        return ov_reserve(h, (uint32_t)S, n_pts_scan, biggest, fmap, stt[0]);
+    }
+    if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = n_pts_scan;
+    if (out) LKCHK(fetch_poses(h, out, S));   // no wait without `out`: ov_read_status has synchronised
+    if (stt[0] & LK_E_KEY_RANGE) {
+        char buf[200];
+        snprintf(buf, sizeof(buf), "overlay replay: a point of slot %u lies in a voxel whose key is outside the +-2^20 range of the private root tables' packed keys (%.0f km from the origin at this voxel size)",
+                 stt[4], 1048576.0 * h->cfg.max_voxel_size / 1000.0);
+        return fail(h, LK_ERR_INVALID, buf);
+    }
+    if (stt[0]) {
+        const LkOverlay& ov = h->ov;
+        char buf[256];
+        snprintf(buf, sizeof(buf), "overlay pool overflow in slot %u (bits 0x%x: 1 private root table, 2 nodes, 4 point blocks, 8 work lists); largest use over the slots: %u nodes, %u blocks, %u roots; per-scan pools: %u root entries, %u child nodes, %u blocks (lk_overlay_reserve)",
+                 stt[4], stt[0], stt[1], stt[2], stt[3], ov.hash_cap, ov.nodes_cap - ov.hash_cap, ov.blocks_cap);
+        return fail(h, LK_ERR_CAPACITY, buf);
+    }
+    return LK_OK;
+}
+
+// The insert of one bucket into the overlays of Sg slots from its posterior (KILO.cc:216-233), on stream st: ov_begin ... ov_insert_apply; the
+// fallback launch behind them is the caller's.  nb: the (longest) bucket's points; S: the slots of the whole batch, which size the per-root passes.
+// Two launch shapes differ between the callers, each as measured for its entry:
+//   min_root_lane: workgroups per slot of lk_ov_root_lane_kernel at least - 4 in the uniform batch, 1 in the ragged one (as measured for this entry; not re-swept);
+//   fit_blocks:    waves per scan of the two fit passes - 12 in the uniform batch (round 6, job headers in a dense array: 6 / 8 / 12 / 16 / 24 waves
+//                  -> fit pass 1.75 / 1.92 / 1.61 / 2.12 / 1.71 ms; before: best at 6, 1.89), min(8, (nb + 63) / 64) in the ragged one (as measured
+//                  for this entry; not re-swept).
+static int ov_insert_passes(lk_handle* h, hipStream_t st, const LkMap& fmap, const LkOverlay& ov, LkFilter* fl, const LkPtSrc& src, int nb, int S, int Sg,
+                            int min_root_lane, int fit_blocks) {
+    LAUNCH(h, "ov_begin", hipLaunchKernelGGL(lk_ov_begin_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, ov));
+    LAUNCH(h, "ov_reproject", hipLaunchKernelGGL(lk_ov_reproject_kernel, dim3((nb + LK_WAVE - 1) / LK_WAVE, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
+    // per-root passes: enough waves per slot to cover its touched roots a few at a time, ~4096 workgroups per launch at least
+    const int per_slot = std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
+    // (measured at 1024 slots x 20 000-point buckets, workgroups per slot: copy-on-write 2.8 / 6.6 / 12.2 ms per batch at 4 / 16 / 32 - a wave takes 64
+    // roots, more waves only find nothing to do; root pass 12.8 / 11.0 / 11.7 - a wave works through its roots one after the other)
+    LAUNCH(h, "ov_materialise", hipLaunchKernelGGL(lk_ov_materialise_kernel<true>, dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr));
+    // root pass: one thread per point (geometry) + one lane per root (lk_ov_point_geom_kernel, lk_ov_root_lane_kernel: root leaves that append / refit /
+    // freeze), then the generic pass over what they leave - three waves per SIMD (without the fit: 184 VGPRs at 2 waves, 168 at 3) - with the
+    // leaf's plane fit only decided; then the fits, a group of lanes each
+    LAUNCH(h, "ov_point_geom", hipLaunchKernelGGL(lk_ov_point_geom_kernel, dim3((nb + 255) / 256, Sg), dim3(256), 0, st, ov, h->pr, fl, src));
+    LAUNCH(h, "ov_root_lane", hipLaunchKernelGGL(lk_ov_root_lane_kernel, dim3(std::max(min_root_lane, (nb + 16 * LK_WAVE - 1) / (16 * LK_WAVE)), Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+    LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL((lk_ov_insert_root_kernel<3, true>), dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
+    LAUNCH(h, "ov_fit_eig", hipLaunchKernelGGL(lk_ov_fit_eig_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+    LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
+    LAUNCH(h, "ov_insert_apply", hipLaunchKernelGGL(lk_ov_insert_apply_kernel, dim3(per_slot, Sg), dim3(LK_MB), 0, st, ov, h->pr, fl, src));
+    return LK_OK;
+}
+
 extern "C" {
 int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, size_t n_pts, double t_begin, const uint32_t* bucket_off,
                                 const double* bucket_dt, size_t n_buckets, lk_pose* out) {
@@ -309,155 +406,61 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
     const int S = (int)n_scans;
     std::vector<size_t> live;
     size_t biggest = 0;
-    for (size_t b = 0; b < n_buckets; ++b) {
+    // this entry's own checks, bucket by bucket ahead of the shared one: the first bad bucket decides which error the caller sees
+    LKCHK(live_buckets(h, bucket_off, n_buckets, live, &biggest, [&](size_t b) -> int {
         if (bucket_off[b + 1] < bucket_off[b] || bucket_off[b + 1] > n_pts) return fail(h, LK_ERR_INVALID, "bucket offsets must be non-decreasing and end inside the scan");
         if (!std::isfinite(bucket_dt[b]) || (b > 0 && bucket_dt[b] < bucket_dt[b - 1])) return fail(h, LK_ERR_INVALID, "bucket times must be finite and non-decreasing");
-        if (bucket_off[b + 1] == bucket_off[b]) continue;
-        if ((size_t)(bucket_off[b + 1] - bucket_off[b]) > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
-        biggest = std::max(biggest, (size_t)(bucket_off[b + 1] - bucket_off[b]));
-        live.push_back(b);
-    }
+        return LK_OK;
+    }));
     if (live.empty()) return fail(h, LK_ERR_INVALID, "empty scans");
-    int rc = join_side_streams(h);   // an asynchronous frozen-map batch may still be using the filter slots
-    if (rc) return rc;
     LkMap fmap;
-    rc = frozen_map(h, &fmap);
-    if (rc) return rc;
-    if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
-    rc = ov_reserve(h, (uint32_t)S, n_pts, biggest, fmap);
-    if (rc) return rc;
-    // the batch's priors, kept for a second attempt: a scan whose overlay outgrows pools that were sized by this library (first guess, or
-    // the previous replay's high-water marks) makes the pools grow and the whole batch run again - only capacities the caller has set
-    // explicitly (lk_overlay_reserve) fail with LK_ERR_CAPACITY
-    LKCHK(reserve(h, h->ov_priors, sizeof(LkFilter) * (size_t)S));
-    HIPCHK(h, hipMemcpyAsync(h->ov_priors.p, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
-    unsigned int stt[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    for (int attempt = 0;; ++attempt) {
-    const LkOverlay ov = h->ov;
-    hipStream_t st = h->stream;
-    rc = zero_scan_counters(h, 0, (uint32_t)S);
-    if (rc) return rc;
-    hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, st, h->d_filters, S, t_begin);
-    HIPCHK(h, hipMemsetAsync(ov.frozen, 0, (size_t)2 * ov.bit_words * sizeof(unsigned int), st));
-    // both bits of every cell (LkOverlay::frozen): frozen leaf, and takes the point at the root
-    LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, 1));
-    const auto res_kernel = (h->pr.ext_identity && lk_xid_enabled()) ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
-    // root pass: one thread per point (geometry) + one lane per root (lk_ov_point_geom_kernel, lk_ov_root_lane_kernel: root leaves that append / refit /
-    // freeze), then the generic pass over what they leave - three waves per SIMD (without the fit: 184 VGPRs at 2 waves, 168 at 3)
-    LAUNCH(h, "ov_base_sums", hipLaunchKernelGGL(lk_ov_base_sums_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, ov.base_sums));
-    const int fit_blocks = 12;   // round 6: with the job headers in a dense array 6 / 8 / 12 / 16 / 24 waves per scan -> fit pass 1.75 / 1.92 / 1.61 / 2.12 / 1.71 ms (before: best at 6, 1.89)
+    LKCHK(ov_replay_begin(h, S, n_pts, biggest, &fmap));
+    const auto res_kernel = ov_residual_kernel(h);
     // Four slot groups on separate HIP streams (round 6, same box: 15.14 / 13.48 / 13.02 / 12.74 ms with 1 / 2 / 3 / 4 groups, 14.8 / 14.2 with
-    // 6 / 8: beyond four streams the queues share hardware): the scans are independent, and the passes of a bucket are of two
-    // kinds - the root pass issues VALU work at 2.8 TB/s of HBM traffic, the others (re-projection, copy-on-write, plane fits) only move
-    // bytes - so one group's root pass runs beside the other group's memory passes.  A group is the same launches with every per-slot
-    // array offset to its first slot (ov_at).  Profiling mode (per-launch events + sync) and small batches stay on one stream.
-    const int ov_groups = 4;
-    const int ngroups = (!h->profiling && S >= 64 * ov_groups) ? ov_groups : 1;
-    hipStream_t streams[lk_handle::kMaxGroups];
-    streams[0] = h->stream;
-    for (int g = 1; g < lk_handle::kMaxGroups; ++g) streams[g] = h->side[g - 1];
-    if (ngroups > 1) {
-        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-        for (int g = 1; g < ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(streams[g], h->ev_fork, 0));
+    // 6 / 8: beyond four streams the queues share hardware): the passes of a bucket are of two kinds - the root pass issues VALU work at
+    // 2.8 TB/s of HBM traffic, the others (re-projection, copy-on-write, plane fits) only move bytes - so one group's root pass runs beside
+    // the other group's memory passes.  A group is the same launches with every per-slot array offset to its first slot (ov_at).
+    const SlotGroups grp(h, S, kOverlayGroups, kOverlayGroupSlots);
+    for (int attempt = 0;; ++attempt) {
+        LKCHK(ov_attempt_begin(h, S, fmap, nullptr, t_begin));
+        LKCHK(grp.fork());
+        const auto enqueue_all = [&]() -> int {   // bucket after bucket, every group's launches of it
+            const unsigned int per = std::max(std::max(h->ov.hash_cap, h->ov.bit_words), (unsigned int)LK_CTR_COUNT);   // root records, bitmap words, counters
+            for (int g = 0; g < grp.n; ++g)
+                LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, grp.count(g)), dim3(256), 0, grp.stream[g], ov_at(h->ov, (size_t)grp.first(g))));
+            for (size_t k = 0; k < live.size(); ++k)
+                for (int g = 0; g < grp.n; ++g) {
+                    const int s0 = grp.first(g), Sg = grp.count(g);   // this group's slots
+                    const LkOverlay ov = ov_at(h->ov, (size_t)s0);
+                    hipStream_t st = grp.stream[g];
+                    LkFilter* fl = h->d_filters + s0;
+                    double* parts = h->d_partials + (size_t)s0 * h->part_stride;
+                    const size_t b = live[k];
+                    const int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
+                    const double t = t_begin + bucket_dt[b];
+                    const int nblk = (nb + LK_RB - 1) / LK_RB;
+                    const LkPtSrc src = {d_pts + (size_t)s0 * n_pts + bucket_off[b], n_pts, nb, nullptr, nullptr, 0, 0, nullptr};
+                    if (k == 0) LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q, t, 2));
+                    LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, Sg), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, parts, h->part_stride));
+                    LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q, 0.0, 1));
+                    LKCHK(ov_insert_passes(h, st, fmap, ov, fl, src, nb, S, Sg, 4, 12));
+                    LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(Sg, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, Sg));   // (1 024 slots, workgroups 8 / 32 / 128 / 256 / 512: 0.54 / 0.26 / 0.15 / 0.17 / 0.16 ms per batch; a workgroup or more per slot: 0.34)
+                    if (k + 1 < live.size())
+                        LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q,
+                                                                t_begin + bucket_dt[live[k + 1]], 2));
+                }
+            HIPCHK(h, hipGetLastError());
+            return LK_OK;
+        };
+        LKCHK(grp.join(enqueue_all()));
+        h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;
+        unsigned int stt[8];
+        LKCHK(ov_read_status(h, (unsigned int)S, stt));
+        bool again = false;
+        const int rc = ov_attempt_end(h, S, attempt, stt, n_pts, biggest, fmap, out, &again);
+        if (!again) return rc;
+        LKCHK(rc);
     }
-    const LkOverlay ov_all = ov;
-    // the enqueue of every group's launches; whatever it returns, the side streams are joined below before this call returns (a failed
-    // launch must not leave them writing filters, partials and pools behind the caller's back)
-    auto enqueue_all = [&]() -> int {
-    for (int grp = 0; grp < ngroups; ++grp) {
-        const int s0 = (int)((long)S * grp / ngroups), sn = (int)((long)S * (grp + 1) / ngroups) - s0;
-        const unsigned int per = std::max(std::max(ov_all.hash_cap, ov_all.bit_words), (unsigned int)LK_CTR_COUNT);   // root records, bitmap words, counters
-        LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, sn), dim3(256), 0, streams[grp], ov_at(ov_all, (size_t)s0)));
-    }
-    for (size_t k = 0; k < live.size(); ++k)
-    for (int grp = 0; grp < ngroups; ++grp) {
-        const int s0 = (int)((long)S * grp / ngroups), Sg = (int)((long)S * (grp + 1) / ngroups) - s0;   // this group's slots
-        const LkOverlay ov = ov_at(ov_all, (size_t)s0);
-        hipStream_t st = streams[grp];
-        LkFilter* fl = h->d_filters + s0;
-        double* parts = h->d_partials + (size_t)s0 * h->part_stride;
-        const size_t b = live[k];
-        const int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
-        const double t = t_begin + bucket_dt[b];
-        const int nblk = (nb + LK_RB - 1) / LK_RB;
-        const lk_point* pts = d_pts + (size_t)s0 * n_pts + bucket_off[b];
-        const LkPtSrc src = {pts, n_pts, nb, nullptr, nullptr, 0, 0, nullptr};
-        if (k == 0) LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q, t, 2));
-        LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, Sg), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, parts, h->part_stride));
-        LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q, 0.0, 1));
-        // the bucket's insert into every slot's overlay, from the posterior (KILO.cc:216-233)
-        LAUNCH(h, "ov_begin", hipLaunchKernelGGL(lk_ov_begin_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, ov));
-        LAUNCH(h, "ov_reproject", hipLaunchKernelGGL(lk_ov_reproject_kernel, dim3((nb + LK_WAVE - 1) / LK_WAVE, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
-        // per-root passes: enough waves per slot to cover its touched roots a few at a time, ~4096 workgroups per launch at least
-        const int per_slot = std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
-        // (measured at 1024 slots x 20 000-point buckets, workgroups per slot: copy-on-write 2.8 / 6.6 / 12.2 ms per batch at 4 / 16 / 32 - a wave takes 64
-        // roots, more waves only find nothing to do; root pass 12.8 / 11.0 / 11.7 - a wave works through its roots one after the other)
-        LAUNCH(h, "ov_materialise", hipLaunchKernelGGL(lk_ov_materialise_kernel<true>, dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr));
-        // one WAVE per touched root (the leaf's plane fit only decided), then the fits a group of lanes each
-        LAUNCH(h, "ov_point_geom", hipLaunchKernelGGL(lk_ov_point_geom_kernel, dim3((nb + 255) / 256, Sg), dim3(256), 0, st, ov, h->pr, fl, src));
-        LAUNCH(h, "ov_root_lane", hipLaunchKernelGGL(lk_ov_root_lane_kernel, dim3(std::max(4, (nb + 16 * LK_WAVE - 1) / (16 * LK_WAVE)), Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-        LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL((lk_ov_insert_root_kernel<3, true>), dim3(std::max(1, per_slot / 2), Sg), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
-        LAUNCH(h, "ov_fit_eig", hipLaunchKernelGGL(lk_ov_fit_eig_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-        LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(fit_blocks, Sg), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-        LAUNCH(h, "ov_insert_apply", hipLaunchKernelGGL(lk_ov_insert_apply_kernel, dim3(per_slot, Sg), dim3(LK_MB), 0, st, ov, h->pr, fl, src));
-        LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(Sg, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, Sg));   // (1 024 slots, workgroups 8 / 32 / 128 / 256 / 512: 0.54 / 0.26 / 0.15 / 0.17 / 0.16 ms per batch; a workgroup or more per slot: 0.34)
-        if (k + 1 < live.size())
-            LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q,
-                                                    t_begin + bucket_dt[live[k + 1]], 2));
-    }
-    HIPCHK(h, hipGetLastError());
-    return LK_OK;
-    };
-    rc = enqueue_all();
-    for (int g = 1; g < ngroups; ++g) {  // join: everything after this point on h->stream sees every group's results
-        if (rc) {
-            (void)hipStreamSynchronize(streams[g]);   // error path: nothing of this call keeps running
-            continue;
-        }
-        HIPCHK(h, hipEventRecord(h->ev_join[g - 1], streams[g]));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0));
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(h->stream);
-        return rc;
-    }
-    h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;
-    const unsigned int init[8] = {0u, 0u, 0u, 0u, 0xffffffffu, 0u, 0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(h->d_ov_status, init, sizeof(init), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(lk_ov_status_kernel, dim3(std::min((S + 255) / 256, 64)), dim3(256), 0, st, ov, (unsigned int)S, h->d_ov_status);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(stt, h->d_ov_status, sizeof(stt), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    const bool growable = !h->ov_want_roots && !(stt[0] & ~(LK_E_HASH_FULL | LK_E_NODES_FULL | LK_E_BLOCKS_FULL)) && attempt < 4;
-    if (!stt[0] || !growable) break;
-    HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
-    rc = ov_reserve(h, (uint32_t)S, n_pts, biggest, fmap, stt[0]);
-    if (rc) return rc;
-    }   // attempts
-    const LkOverlay& ov = h->ov;
-    hipStream_t st = h->stream;
-    if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = n_pts;
-    if (out) {
-        std::vector<lk_pose> tmp(n_scans);
-        rc = fetch_poses(h, tmp.data(), S);   // synchronises
-        if (rc) return rc;
-        memcpy(out, tmp.data(), sizeof(lk_pose) * n_scans);
-    } else {
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    if (stt[0] & LK_E_KEY_RANGE) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "overlay replay: a point of slot %u lies in a voxel whose key is outside the +-2^20 range of the private root tables' packed keys (%.0f km from the origin at this voxel size)",
-                 stt[4], 1048576.0 * h->cfg.max_voxel_size / 1000.0);
-        return fail(h, LK_ERR_INVALID, buf);
-    }
-    if (stt[0]) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "overlay pool overflow in slot %u (bits 0x%x: 1 private root table, 2 nodes, 4 point blocks, 8 work lists); largest use over the slots: %u nodes, %u blocks, %u roots; per-scan pools: %u root entries, %u child nodes, %u blocks (lk_overlay_reserve)",
-                 stt[4], stt[0], stt[1], stt[2], stt[3], ov.hash_cap, ov.nodes_cap - ov.hash_cap, ov.blocks_cap);
-        return fail(h, LK_ERR_CAPACITY, buf);
-    }
-    return LK_OK;
 }
 
 int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets,
@@ -477,29 +480,15 @@ int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size
 int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const LkRagged& rg, const double* d_tbegin, int biggest, size_t ldb,
                                  const int* max_n, size_t max_scan_pts, int msg_kind, lk_pose* out) {
     const int S = (int)S_;
-    int rc = join_side_streams(h);
-    if (rc) return rc;
     LkMap fmap;
-    rc = frozen_map(h, &fmap);
-    if (rc) return rc;
-    if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
-    rc = ov_reserve(h, (uint32_t)S, max_scan_pts, (size_t)biggest, fmap);
-    if (rc) return rc;
-    LKCHK(reserve(h, h->ov_priors, sizeof(LkFilter) * (size_t)S));
+    LKCHK(ov_replay_begin(h, S, max_scan_pts, (size_t)biggest, &fmap));
     hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->ov_priors.p, h->d_filters, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
     const bool xid = h->pr.ext_identity && lk_xid_enabled();
-    const auto res_kernel = xid ? lk_ov_residual_kernel<true> : lk_ov_residual_kernel<false>;
-    unsigned int stt[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    const auto res_kernel = ov_residual_kernel(h);
     for (int attempt = 0;; ++attempt) {
         const LkOverlay ov = h->ov;
         LkFilter* fl = h->d_filters;
-        rc = zero_scan_counters(h, 0, (uint32_t)S);
-        if (rc) return rc;
-        hipLaunchKernelGGL(lk_set_times_ragged_kernel, dim3((S + 63) / 64), dim3(64), 0, st, fl, S, d_tbegin);
-        HIPCHK(h, hipMemsetAsync(ov.frozen, 0, (size_t)2 * ov.bit_words * sizeof(unsigned int), st));
-        LAUNCH(h, "ov_frozen_bits", hipLaunchKernelGGL(lk_ov_frozen_bits_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, h->pr.max_layer, ov.frozen, 1));
-        LAUNCH(h, "ov_base_sums", hipLaunchKernelGGL(lk_ov_base_sums_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, st, fmap, h->hash_cap, ov.base_sums));
+        LKCHK(ov_attempt_begin(h, S, fmap, d_tbegin, 0.0));
         {
             const unsigned int per = std::max(std::max(ov.hash_cap, ov.bit_words), (unsigned int)LK_CTR_COUNT);
             LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, S), dim3(256), 0, st, ov));
@@ -517,8 +506,7 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
             const LkPtSrc fsrc = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, 0, fb_b};
             unsigned int rounds = 0;
             for (;; ++rounds) {
-                rc = ov_scan_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending);   // lk_ovscan.hip
-                if (rc) return rc;
+                LKCHK(ov_scan_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovscan.hip
                 unsigned int n_pending = 0;
                 HIPCHK(h, hipMemcpyAsync(&n_pending, pending, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
                 HIPCHK(h, hipStreamSynchronize(st));
@@ -541,71 +529,30 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
                 LAUNCH(h, "ov_tail", hipLaunchKernelGGL(lk_ov_tail_kernel, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
             } else {
                 const int nblk = (nb + LK_RB - 1) / LK_RB;
-                const int per_slot = std::max(1, std::min((nb + 255) / 256, std::max(2, (4096 + S - 1) / S)));
-                const int fit_blocks = std::max(1, std::min(8, (nb + 63) / 64));
                 LAUNCH(h, "rag_advance", hipLaunchKernelGGL(lk_rag_advance_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_Q, rg, (int)b, msg_kind));
                 LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, S), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, h->d_partials, h->part_stride));
                 LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_partials, h->part_stride, h->d_Q, rg, (int)b, 1));
-                LAUNCH(h, "ov_begin", hipLaunchKernelGGL(lk_ov_begin_kernel, dim3(S), dim3(LK_WAVE), 0, st, ov));
-                LAUNCH(h, "ov_reproject", hipLaunchKernelGGL(lk_ov_reproject_kernel, dim3((nb + LK_WAVE - 1) / LK_WAVE, S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
-                LAUNCH(h, "ov_materialise", hipLaunchKernelGGL(lk_ov_materialise_kernel<true>, dim3(std::max(1, per_slot / 2), S), dim3(LK_MB), 0, st, fmap, ov, h->pr));
-                LAUNCH(h, "ov_point_geom", hipLaunchKernelGGL(lk_ov_point_geom_kernel, dim3((nb + 255) / 256, S), dim3(256), 0, st, ov, h->pr, fl, src));
-                LAUNCH(h, "ov_root_lane", hipLaunchKernelGGL(lk_ov_root_lane_kernel, dim3(std::max(1, (nb + 16 * LK_WAVE - 1) / (16 * LK_WAVE)), S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-                LAUNCH(h, "ov_insert_root", hipLaunchKernelGGL((lk_ov_insert_root_kernel<3, true>), dim3(std::max(1, per_slot / 2), S), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
-                LAUNCH(h, "ov_fit_eig", hipLaunchKernelGGL(lk_ov_fit_eig_kernel, dim3(fit_blocks, S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-                LAUNCH(h, "ov_fit_lane", hipLaunchKernelGGL(lk_ov_fit_group_kernel, dim3(fit_blocks, S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr));
-                LAUNCH(h, "ov_insert_apply", hipLaunchKernelGGL(lk_ov_insert_apply_kernel, dim3(per_slot, S), dim3(LK_MB), 0, st, ov, h->pr, fl, src));
+                LKCHK(ov_insert_passes(h, st, fmap, ov, fl, src, nb, S, S, 1, std::max(1, std::min(8, (nb + 63) / 64))));
             }
             LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, (int)S));
         }
         HIPCHK(h, hipGetLastError());
         h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;
-        const unsigned int init[8] = {0u, 0u, 0u, 0u, 0xffffffffu, 0u, 0u, 0u};
-        HIPCHK(h, hipMemcpyAsync(h->d_ov_status, init, sizeof(init), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(lk_ov_status_kernel, dim3(std::min((S + 255) / 256, 64)), dim3(256), 0, st, ov, (unsigned int)S, h->d_ov_status);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(stt, h->d_ov_status, sizeof(stt), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        const bool growable = !h->ov_want_roots && !(stt[0] & ~(LK_E_HASH_FULL | LK_E_NODES_FULL | LK_E_BLOCKS_FULL)) && attempt < 4;
-        if (!stt[0] || !growable) break;
-        HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, st));
-        rc = ov_reserve(h, (uint32_t)S, max_scan_pts, (size_t)biggest, fmap, stt[0]);
-        if (rc) return rc;
+        unsigned int stt[8];
+        LKCHK(ov_read_status(h, (unsigned int)S, stt));
+        bool again = false;
+        const int rc = ov_attempt_end(h, S, attempt, stt, max_scan_pts, (size_t)biggest, fmap, out, &again);
+        if (!again) return rc;
+        LKCHK(rc);
     }
-    if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = max_scan_pts;
-    if (out) {
-        std::vector<lk_pose> tmp((size_t)S);
-        rc = fetch_poses(h, tmp.data(), S);
-        if (rc) return rc;
-        memcpy(out, tmp.data(), sizeof(lk_pose) * (size_t)S);
-    }
-    if (stt[0] & LK_E_KEY_RANGE) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "overlay replay: a point of slot %u lies in a voxel whose key is outside the +-2^20 range of the private root tables' packed keys (%.0f km from the origin at this voxel size)",
-                 stt[4], 1048576.0 * h->cfg.max_voxel_size / 1000.0);
-        return fail(h, LK_ERR_INVALID, buf);
-    }
-    if (stt[0]) {
-        const LkOverlay& ov = h->ov;
-        char buf[256];
-        snprintf(buf, sizeof(buf), "overlay pool overflow in slot %u (bits 0x%x: 1 private root table, 2 nodes, 4 point blocks, 8 work lists); largest use over the slots: %u nodes, %u blocks, %u roots; per-scan pools: %u root entries, %u child nodes, %u blocks (lk_overlay_reserve)",
-                 stt[4], stt[0], stt[1], stt[2], stt[3], ov.hash_cap, ov.nodes_cap - ov.hash_cap, ov.blocks_cap);
-        return fail(h, LK_ERR_CAPACITY, buf);
-    }
-    return LK_OK;
 }
 extern "C" {
 
 int lk_overlay_stats(lk_handle* h, uint32_t* max_roots, uint32_t* max_nodes, uint32_t* max_blocks) {
     CHECK_H(h);
     if (!h->ov_last_slots || !h->ov.counters) return fail(h, LK_ERR_STATE, "no overlay replay's pools are held by this handle (none has run, or lk_overlay_reserve released them)");
-    const unsigned int init[8] = {0u, 0u, 0u, 0u, 0xffffffffu, 0u, 0u, 0u};
     unsigned int stt[8];
-    HIPCHK(h, hipMemcpyAsync(h->d_ov_status, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(lk_ov_status_kernel, dim3(std::min((h->ov_last_slots + 255u) / 256u, 64u)), dim3(256), 0, h->stream, h->ov, h->ov_last_slots, h->d_ov_status);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(stt, h->d_ov_status, sizeof(stt), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    LKCHK(ov_read_status(h, h->ov_last_slots, stt));
     if (max_nodes) *max_nodes = stt[1];
     if (max_blocks) *max_blocks = stt[2];
     if (max_roots) *max_roots = stt[3];

@@ -308,7 +308,7 @@ def _assert_replay(want, poses, states, where):
 
 
 @gpu
-@pytest.mark.parametrize("S", [7, 3])   # 7: three slot groups on three streams, split 2 / 2 / 3; 3: one stream
+@pytest.mark.parametrize("S", [7, 3])   # frozen-map replay (replay_groups = 3, from S = 6 on) - 7: three slot groups on three streams, split 2 / 2 / 3; 3: one stream
 def test_batch_replay_tile_edge_buckets(hip_lib, match, S, monkeypatch):
     """lk_batch_replay_dev and lk_batch_replay_ragged_dev over buckets of 1, 63, 64, 65, 0, 128, 1, 0, 192, 257 points against the oracle's
     process_scan per slot (counts exact; the device's n_buckets counts the non-empty buckets, as the oracle's loop does), default and

@@ -1144,7 +1144,7 @@ def test_batch_sort_by_voxel(scene, oracle_lib, hip_lib):
     o.close()
 
 
-@pytest.mark.parametrize("S", [6, 7, 3])   # 6/7: three slot groups on three HIP streams (even / ragged split); 3: single stream
+@pytest.mark.parametrize("S", [6, 7, 3])   # frozen-map replay, replay_groups = 3 from S = 6 on - 6/7: three slot groups on three HIP streams (even / ragged split); 3: single stream
 def test_batch_replay_frozen_map(scene, oracle_lib, hip_lib, S):
     n_pts, nb = 8000, 5
     o = oracle_lib.Oracle(scene.cfg(), imu_mode_only=True)
@@ -1354,6 +1354,9 @@ def test_batch_replay_overlay_follows_the_map(scene, oracle_lib, hip_lib):
     o.close()
 
 
+OV_GROUPS, OV_GROUP_SLOTS = 4, 64   # lk_batch_replay_overlay_dev: four slot groups from 64 slots per group on (kOverlayGroups, kOverlayGroupSlots)
+
+
 @pytest.mark.parametrize("case", ["scattered", "sectors", "tiny", "groups"])
 def test_batch_replay_overlay(scene, oracle_lib, hip_lib, case):
     """Batch replay WITH the map insert (lk_batch_replay_overlay_dev, SURVEY 8d config 5 "scan-local insert overlay"): every scan
@@ -1366,17 +1369,24 @@ def test_batch_replay_overlay(scene, oracle_lib, hip_lib, case):
                  matches) on a young map - the overlay lookup path of the residual pass is what decides the counts;
       sectors:   config 5's shape at full size (100 000 points, 5 azimuth sectors of 20 000);
       tiny:      12 buckets of 40..90 points, one scan of a single bucket's worth of new voxels;
-      groups:    200 such scans - from 192 on the replay splits its slots into three groups on three HIP streams (each group sees the
-                 pools offset to its first slot); the slots on both sides of the seams and at both ends are checked."""
+      groups:    256 such scans - the smallest batch the replay splits: four groups of 64 slots on four HIP streams (each group sees the
+                 pools offset to its first slot); the slots on both sides of the three seams and at both ends are checked (states and the
+                 grouped run's private voxels), and the same batch replayed on ONE stream (profiling mode, ahead of the grouped runs) gives
+                 the bits of the grouped run in every slot."""
     if case == "sectors":
         S, n_pts, nb, young = 3, 100000, 5, False
     elif case == "scattered":
         S, n_pts, nb, young = 4, 30000, 5, True
     elif case == "groups":
-        S, n_pts, nb, young = 200, 800, 12, True
+        S, n_pts, nb, young = OV_GROUPS * OV_GROUP_SLOTS, 800, 12, True
     else:
         S, n_pts, nb, young = 5, 800, 12, True
-    check_slots = list(range(S)) if S <= 8 else [0, S // 3 - 1, S // 3, 2 * S // 3 - 1, 2 * S // 3, S - 1]   # both sides of the seams of three slot groups
+    if S <= 8:
+        check_slots = list(range(S))
+    else:   # first and last slot of every group (group g starts at S * g // OV_GROUPS): both ends, and both sides of the seams
+        assert S >= OV_GROUPS * OV_GROUP_SLOTS, "the batch would run as one group"
+        check_slots = [s for grp in range(OV_GROUPS) for s in (S * grp // OV_GROUPS, S * (grp + 1) // OV_GROUPS - 1)]
+        assert check_slots == [0, 63, 64, 127, 128, 191, 192, 255]
     o = oracle_lib.Oracle(scene.cfg(), imu_mode_only=True)
     g = hip_lib.LegKiloHip(scene.cfg(n_slots=S))
     t0 = 21.0
@@ -1436,9 +1446,21 @@ def test_batch_replay_overlay(scene, oracle_lib, hip_lib, case):
         g.overlay_reserve(16384, 32768, 16384)   # a young map: a scattered 30 000-point scan touches most of its voxels
     if case == "groups":
         g.overlay_reserve(2048, 4096, 2048)
+        # the ungrouped run FIRST: profiling mode keeps the whole batch on the handle's stream.  The grouped replays follow it, so that the
+        # overlays which lk_overlay_export hands to the per-slot checks below are the grouped run's
+        g.batch_set_priors(np.array(xs), np.array(Ps))
+        g.profile_enable(1)
+        try:
+            poses1 = g.batch_replay_overlay_dev(d_pts, S, n_pts, 0.0, off, dt)
+        finally:
+            g.profile_enable(0)
+        X1, P1 = g.batch_get_states(0, S)
     g.batch_set_priors(np.array(xs), np.array(Ps))
     poses = g.batch_replay_overlay_dev(d_pts, S, n_pts, 0.0, off, dt)
     Xall, Pall = g.batch_get_states(0, S)
+    if case == "groups":   # grouped against ungrouped, every slot
+        assert np.array_equal(Xall, X1) and np.array_equal(Pall, P1)
+        assert [int(p.n_effect) for p in poses] == [int(p.n_effect) for p in poses1]
     # the shared map is untouched, and a second replay gives the same bits (the overlays start empty every time)
     assert np.array_equal(g.map_export(), np.frombuffer(blob, dtype=np.uint8)) or scenes.maps_identical(g.map_export(), blob)
     g.batch_set_priors(np.array(xs), np.array(Ps))

@@ -17,6 +17,7 @@
 #pragma once
 #include "lk_device.h"
 #include "lk_eig3.h"
+#include "lk_range_bound.h"
 
 #define LK_MB 256  // threads per block in the per-root kernels (4 waves = 4 roots in flight)
 
@@ -1741,8 +1742,10 @@ __global__ void __launch_bounds__(256) lk_grid_fill_kernel(LkMap map, unsigned i
     const int4 e = map.hash[i];
     if (e.w < 0) return;
     const size_t c = ((size_t)(e.z - map.gmin[2]) * (size_t)map.gdim[1] + (size_t)(e.y - map.gmin[1])) * (size_t)map.gdim[0] + (size_t)(e.x - map.gmin[0]);
+    // grid records carry lk_range_bound(radius) in their radius word: their only reader, match_flat, evaluates the range gate without a square root
     lk_match_rec r = map.match[e.w];
     r.pad_ = (unsigned int)e.w;
+    r.radius = lk_range_bound(r.radius);
     if (!(r.flags & LK_PLANE_IS_PLANE)) {
         // pass 1: count the plane nodes of the subtree; pass 2: copy them
         unsigned int first = 0, count = 0;
@@ -1771,6 +1774,7 @@ __global__ void __launch_bounds__(256) lk_grid_fill_kernel(LkMap map, unsigned i
                         if (pass == 1) {
                             lk_match_rec cr = map.match[node];
                             cr.pad_ = (unsigned int)node;
+                            cr.radius = lk_range_bound(cr.radius);
                             map.match[first + k] = cr;
                         }
                         ++k;

@@ -37,7 +37,9 @@ struct Match {
 struct RecTail {   // bytes 64..143 of a match record: S11 (6), w (3), s22
     double2 v0, v1, v2, v3, v4;
 };
-template <bool XID, bool PRE = false>
+// BOUND: the record is a frozen-map grid record, whose radius word holds lk_range_bound(radius) (lk_grid_fill_kernel) - the range gate is two float
+// compares, the same decision for every x as the sqrtf form that pool records keep (lk_range_bound.h).
+template <bool XID, bool PRE = false, bool BOUND = false>
 __device__ __forceinline__ void eval_plane(const lk_match_rec* __restrict__ mr, double2 q0, double2 q1, double2 q2,
                                            float pd, float pradius, int node, int layer, const PointLite& g,
                                            const BucketConst& bc, const LkParams& pr, bool& success, double& prob,
@@ -51,8 +53,13 @@ __device__ __forceinline__ void eval_plane(const lk_match_rec* __restrict__ mr, 
     float dis_to_plane = (float)fabs(sd);
     float dis_to_center = (float)((c.x - g.p_w.x) * (c.x - g.p_w.x) + (c.y - g.p_w.y) * (c.y - g.p_w.y) +
                                   (c.z - g.p_w.z) * (c.z - g.p_w.z));
-    float range_dis = sqrtf(dis_to_center - dis_to_plane * dis_to_plane);
-    if (!((double)range_dis <= 3.0 * (double)pradius)) return;  // radius_k = 3
+    const float range2 = dis_to_center - dis_to_plane * dis_to_plane;
+    if (BOUND) {
+        if (!(range2 >= 0.f && range2 <= pradius)) return;
+    } else {
+        float range_dis = sqrtf(range2);
+        if (!((double)range_dis <= 3.0 * (double)pradius)) return;  // radius_k = 3
+    }
     const V3 q = V3{g.p_w.x - c.x, g.p_w.y - c.y, g.p_w.z - c.z};
     const S3 s11 = S3{v0.x, v0.y, v1.x, v1.y, v2.x, v2.y};
     // J plane_var J^T = q^T S11 q - 2 q.w + s22   (w = S12 n, s22 = n^T S22 n precomputed per plane)
@@ -177,7 +184,7 @@ __device__ __forceinline__ bool match_flat(const LkMap& m, int cell, const Point
         const lk_match_rec* pl = &m.match[idx];
         const double2* q = reinterpret_cast<const double2*>(pl);
         double2 q0 = q[0], q1 = q[1], q2 = q[2];
-        float4 tail = *reinterpret_cast<const float4*>(&pl->d);  // d, radius, flags, node id
+        float4 tail = *reinterpret_cast<const float4*>(&pl->d);  // d, lk_range_bound(radius), flags, node id
         RecTail rt;
         rt.v0 = q[4], rt.v1 = q[5], rt.v2 = q[6], rt.v3 = q[7], rt.v4 = q[8];
         pin_chunk(q0), pin_chunk(q1), pin_chunk(q2), pin_chunk(tail);
@@ -192,7 +199,7 @@ __device__ __forceinline__ bool match_flat(const LkMap& m, int cell, const Point
                 continue;
             }
         }
-        eval_plane<XID, true>(pl, q0, q1, q2, tail.x, tail.y, 0, 0, g, bc, pr, success, prob, best, &rt);
+        eval_plane<XID, true, true>(pl, q0, q1, q2, tail.x, tail.y, 0, 0, g, bc, pr, success, prob, best, &rt);
         ++idx;
         --remaining;
     }
@@ -460,7 +467,13 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
             acc = __builtin_fma(r[a], r[b], acc);
         }
     }
-    acc += __shfl_xor(acc, 32, LK_WAVE);
+    {   // the other half's sum: v_permlane32_swap of acc's two words with copies of themselves leaves both halves' values side by side in
+        // every lane (wave_sum's first step); a + b == b + a, so either lane's view gives the bits of acc(own) + acc(other)
+        const unsigned int lo = (unsigned int)__double2loint(acc), hi = (unsigned int)__double2hiint(acc);
+        const lk_u2 l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const lk_u2 h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        acc = __hiloint2double((int)h.x, (int)l.x) + __hiloint2double((int)h.y, (int)l.y);
+    }
     return acc;
 }
 

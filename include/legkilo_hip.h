@@ -510,6 +510,66 @@ int lk_kin_split_dev(lk_handle* h, const lk_kin_imu* d_kins, size_t n_kins, cons
 int lk_batch_replay_scans_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
                                   const uint32_t* n_msg, const lk_kin_imu* d_kins, lk_pose* out);
 
+/* ---- IMU front end (only_imu_use mode): sensor_msgs/Imu -> lk_imu on the device ----
+ * What the reference runs for every IMU message before the filter sees it: RosInterface::imuCallBack (ros_interface.cc:194-219: the
+ * redundancy filter and the time check) and the IMU branch of syncPackage (ros_interface.cc:277-301) that hands the records to the scans.
+ * A message is its ROS1 serialisation; message i = the bytes [msg_off[i], msg_off[i+1]) of the buffer (msg_off: n + 1 host entries,
+ * non-decreasing, msg_off[0] may be non-zero).  With L the frame_id length the little-endian fields lie at
+ *   0 seq u32 | 4 stamp.sec u32 | 8 stamp.nsec u32 | 12 L u32 | 16 frame_id | 16+L orientation 4 f64 | 48+L its covariance 9 f64 |
+ *   120+L angular_velocity 3 f64 | 144+L its covariance 9 f64 | 216+L linear_acceleration 3 f64 | 240+L its covariance 9 f64
+ * so a message is LK_IMU_MSG_FIXED_BYTES + L bytes and, L changing from message to message, no field has any alignment.
+ * Record: stamp = (double)sec + 1e-9 * (double)nsec (ros::Time::toSec), acc = linear_acceleration, gyr = angular_velocity.
+ *   - redundancy != 0: message i is dropped when its linear_acceleration.z == the previous MESSAGE's and its angular_velocity.z == the
+ *     previous message's - kept or dropped, that one counts (ros_interface.cc:198-204) - and before the first message the carried values,
+ *     which after lk_imu_configure are the zeros of the callback's static.  An fp64 ==: -0.0 matches 0.0, NaN never matches.
+ *   - the stamps of the kept messages must not decrease, within the call or against the carried last stamp: LK_ERR_INVALID otherwise
+ *     (the reference clears its cache there, ros_interface.cc:209-212; here the call is refused, as for HighState).
+ *   - a message is valid only if msg_off[i+1] - msg_off[i] == LK_IMU_MSG_FIXED_BYTES + L (in 64 bits).  A length below
+ *     LK_IMU_MSG_FIXED_BYTES (or a decreasing msg_off) is refused on the host; a length that disagrees with L is found on the device before
+ *     anything behind byte 16 of that message is read: LK_ERR_INVALID, lk_last_error names the first offending message.  No byte outside
+ *     [msg_off[0], msg_off[n]) is ever read, whatever L claims.
+ *   - the carried state moves only when the call succeeds, and by exactly the call's messages: a stream decoded in chunks gives what one
+ *     call gives.  After a refusal the output is undefined.
+ *   - LK_ERR_STATE before lk_imu_configure; n >= 2^31 is refused; n == 0 is LK_OK with *n_out = 0.  out / d_out: room for n records. */
+#define LK_IMU_MSG_FIXED_BYTES 312
+/* What the front end carries from one message to the next: checkpoint it with lk_imu_get_frontend, resume with lk_imu_set_frontend. */
+typedef struct lk_imu_frontend_state {
+    double last_acc_z;       /* the previous message's linear_acceleration.z / angular_velocity.z, kept or not (the callback's static) */
+    double last_gyr_z;
+    double last_stamp;       /* stamp of the last kept message (-inf: none yet) */
+} lk_imu_frontend_state;
+/* Sets the redundancy flag (yaml key `redundancy`) AND resets the carried state: last acc z / gyr z 0.0, last stamp -inf. */
+int lk_imu_configure(lk_handle* h, int redundancy);
+int lk_imu_get_frontend(lk_handle* h, lk_imu_frontend_state* st);
+int lk_imu_set_frontend(lk_handle* h, const lk_imu_frontend_state* st);
+/* _dev: device input (d_msgs = byte 0 of the buffer msg_off counts in, any alignment), device output, synchronous; the host variant
+ * copies the bytes [msg_off[0], msg_off[n]) and the kept records. */
+int lk_decode_imu_dev(lk_handle* h, const void* d_msgs, size_t n, const uint64_t* msg_off, lk_imu* d_out, size_t* n_out);
+int lk_decode_imu(lk_handle* h, const void* msgs, size_t n, const uint64_t* msg_off, lk_imu* out, size_t* n_out);
+/* The IMU branch of syncPackage (ros_interface.cc:277-301) over time-sorted records (lk_decode_imu_dev's output): the rule, the arguments
+ * and the outputs of lk_kin_split_dev word for word, on lk_imu records - ready for lk_batch_replay_scans_imu_dev.  Stateless. */
+int lk_imu_split_dev(lk_handle* h, const lk_imu* d_imus, size_t n_imus, const double* scan_end, size_t n_scans, uint32_t* n_msg,
+                     size_t* n_packaged, size_t* n_consumed);
+/* lk_batch_replay_scans_dev with msg_kind 1 and the records already in HBM (d_imus: the n_msg[s] records of each scan, concatenated). */
+int lk_batch_replay_scans_imu_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
+                                  const uint32_t* n_msg, const lk_imu* d_imus, lk_pose* out);
+
+/* ---- first frame: how KILO::process starts every run (KILO.cc:332-352), on filter slot 0 ----
+ * raw / d_raw: the RAW first cloud (lk_decode_scan(_dev)'s output, not voxel-filtered: KILO.cc:336-339 uses cloud_raw), n points;
+ * msgs / d_msgs: the first package's n_msg messages - msg_kind 1: lk_imu records (StateInitialByImu, state_initial.hpp:34-72),
+ * msg_kind 2: lk_kin_imu records (StateInitialByKinImu, state_initial.hpp:79-117).  In the reference's order:
+ *   1. state: the running mean of the messages' acc / gyr in state_initial.hpp's literal order (N starts at 1, the mean starts at the
+ *      first message, which the loop visits again; mean += (cur - mean) / N); acc_norm = |mean_acc|, grav = -mean_acc / acc_norm * gravity
+ *      (divide, then multiply), bw = mean_gyr, rot = I, every other entry what a fresh ESKF holds (0), P = 1e-6 I, Q as by
+ *      lk_init_process_cov_q.  (cov_acc_ / cov_gyr_ are computed by the reference and never read: left out.)
+ *   2. cloudLidarToWorld (KILO.cc:89-106) with the state just written: fp64 rot (ext_R p + ext_T) + pos, cast to float.
+ *   3. BuildVoxelMap from the two clouds (lk_map_build's work, the clouds staying in HBM).
+ *   4. acc_norm (KILO.cc:349; lk_get_acc_norm) and both time stamps = end_time (KILO.cc:350-351; lk_get_times).
+ * Refused before anything changes: n == 0 or n_msg == 0 ("Data packet is not ready", KILO.cc:326-329) and msg_kind not 1 or 2 with
+ * LK_ERR_INVALID, a non-empty map with LK_ERR_STATE (as lk_map_build), n > max_scan_points with LK_ERR_CAPACITY.  Synchronous. */
+int lk_first_frame_dev(lk_handle* h, const lk_point* d_raw, size_t n, double end_time, int msg_kind, const void* d_msgs, size_t n_msg);
+int lk_first_frame(lk_handle* h, const lk_point* raw, size_t n, double end_time, int msg_kind, const void* msgs, size_t n_msg);
+
 /* ---- measurement hooks ---- */
 int lk_profile_enable(lk_handle* h, int on);                           /* HIP-event timing around each kernel */
 int lk_profile_get(lk_handle* h, const char* kernel, uint64_t* launches, double* total_ms);

@@ -96,6 +96,13 @@ class lk_kin_frontend_state(C.Structure):
     ]
 
 
+LK_IMU_MSG_FIXED_BYTES = 312   # a ROS1-serialised sensor_msgs/Imu is 312 + frame_id length bytes
+
+
+class lk_imu_frontend_state(C.Structure):
+    _fields_ = [("last_acc_z", C.c_double), ("last_gyr_z", C.c_double), ("last_stamp", C.c_double)]
+
+
 class lk_pose(C.Structure):
     _fields_ = [
         ("rot", C.c_double * 9),

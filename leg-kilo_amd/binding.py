@@ -24,6 +24,8 @@ EXPORTS = [
     "lk_device_malloc", "lk_device_free", "lk_memcpy_h2d", "lk_memcpy_d2h", "lk_synchronize", "lk_stream", "lk_stream_pipeline", "lk_stream_resident", "lk_stream_grid", "lk_stream_grid_placement", "lk_stream_stats", "lk_stream_resident_stats", "lk_test_stall",
     "lk_kin_configure", "lk_kin_get_frontend", "lk_kin_set_frontend", "lk_decode_highstate", "lk_decode_highstate_dev", "lk_kin_split_dev",
     "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
+    "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
+    "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev",
 ]
 
 
@@ -639,6 +641,80 @@ class LegKiloHip:
         self._chk(self.L.lk_batch_replay_scans_kin_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(so), _p(tb), _p(nm),
                                                        C.c_void_p(d_kins) if d_kins else None, poses))
         return poses
+
+    # ---- IMU front end (sensor_msgs/Imu -> lk_imu, the IMU branch of syncPackage) ----
+    def imu_configure(self, redundancy=True):
+        """Sets the yaml key `redundancy` (a bool, or a parameter dict holding it) and resets the carried state."""
+        if isinstance(redundancy, dict):
+            redundancy = redundancy.get("redundancy", True)
+        self._chk(self.L.lk_imu_configure(self.h, C.c_int(1 if redundancy else 0)))
+
+    def imu_get_frontend(self):
+        """The carried state as a dict(last_acc_z, last_gyr_z, last_stamp)."""
+        st = abi.lk_imu_frontend_state()
+        self._chk(self.L.lk_imu_get_frontend(self.h, C.byref(st)))
+        return dict(last_acc_z=st.last_acc_z, last_gyr_z=st.last_gyr_z, last_stamp=st.last_stamp)
+
+    def imu_set_frontend(self, fe):
+        st = abi.lk_imu_frontend_state(float(fe["last_acc_z"]), float(fe["last_gyr_z"]), float(fe["last_stamp"]))
+        self._chk(self.L.lk_imu_set_frontend(self.h, C.byref(st)))
+
+    def decode_imu(self, buf, msg_off):
+        """Serialized sensor_msgs/Imu messages (uint8 array; message i = buf[msg_off[i]:msg_off[i + 1]]) -> IMU_DTYPE records of the kept ones."""
+        from . import synth
+
+        data = np.ascontiguousarray(buf, dtype=np.uint8)
+        mo = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n = len(mo) - 1
+        out = np.zeros(max(n, 1), dtype=synth.IMU_DTYPE)
+        n_out = C.c_size_t(0)
+        self._chk(self.L.lk_decode_imu(self.h, _p(data), C.c_size_t(n), _p(mo), _p(out), C.byref(n_out)))
+        return out[: n_out.value]
+
+    def decode_imu_dev(self, d_msgs, msg_off, d_out):
+        """len(msg_off) - 1 messages in HBM (message i at d_msgs + msg_off[i]) -> records at the device pointer d_out (room for one per
+        message); returns the number kept."""
+        mo = np.ascontiguousarray(msg_off, dtype=np.uint64)
+        n_out = C.c_size_t(0)
+        self._chk(self.L.lk_decode_imu_dev(self.h, C.c_void_p(d_msgs), C.c_size_t(len(mo) - 1), _p(mo), C.c_void_p(d_out), C.byref(n_out)))
+        return n_out.value
+
+    def imu_split_dev(self, d_imus, n_imus, scan_end):
+        """syncPackage's IMU branch over n_imus time-sorted lk_imu records in HBM and the scans' end times -> (n_msg uint32[n_scans],
+        n_packaged, n_consumed)."""
+        ends = _f64(scan_end)
+        n_msg = np.zeros(max(len(ends), 1), dtype=np.uint32)
+        npk, ncs = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.L.lk_imu_split_dev(self.h, C.c_void_p(d_imus), C.c_size_t(n_imus), _p(ends), C.c_size_t(len(ends)), _p(n_msg), C.byref(npk),
+                                          C.byref(ncs)))
+        return n_msg[: len(ends)], npk.value, ncs.value
+
+    def batch_replay_scans_imu_dev(self, d_pts, scan_off, t_begins, n_msg, d_imus, want_poses=True):
+        """lk_batch_replay_scans_dev in IMU-only mode with the records already in HBM (d_imus: n_msg[s] records per scan, concatenated)."""
+        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
+        n_scans = len(so) - 1
+        tb = _f64(t_begins)
+        nm = np.ascontiguousarray(n_msg, dtype=np.uint32)
+        assert len(tb) == n_scans and len(nm) == n_scans
+        poses = (abi.lk_pose * n_scans)() if want_poses else None
+        self._chk(self.L.lk_batch_replay_scans_imu_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(so), _p(tb), _p(nm),
+                                                       C.c_void_p(d_imus) if d_imus else None, poses))
+        return poses
+
+    # ---- first frame (KILO.cc:332-352) ----
+    def first_frame(self, raw_pts, end_time, imus=None, kins=None):
+        """State initialisation from the first package's messages (imus: IMU_DTYPE, or kins: KIN_DTYPE), cloudLidarToWorld on the RAW first
+        cloud, BuildVoxelMap, acc_norm and the time stamps, on slot 0 (lk_first_frame)."""
+        assert (imus is None) != (kins is None)
+        raw = np.ascontiguousarray(raw_pts)
+        msgs = np.ascontiguousarray(imus if kins is None else kins)
+        self._chk(self.L.lk_first_frame(self.h, _p(raw), C.c_size_t(len(raw)), C.c_double(end_time), C.c_int(1 if kins is None else 2), _p(msgs),
+                                        C.c_size_t(len(msgs))))
+
+    def first_frame_dev(self, d_raw, n, end_time, msg_kind, d_msgs, n_msg):
+        """The same with the raw cloud (n lk_point) and the n_msg records (msg_kind 1: lk_imu, 2: lk_kin_imu) already in HBM."""
+        self._chk(self.L.lk_first_frame_dev(self.h, C.c_void_p(d_raw), C.c_size_t(n), C.c_double(end_time), C.c_int(msg_kind), C.c_void_p(d_msgs),
+                                            C.c_size_t(n_msg)))
 
     # ---- measurement / memory hooks ----
     def profile_enable(self, on):

@@ -225,8 +225,7 @@ int lk_get_Q(lk_handle* h, double* Q900) {
     return LK_OK;
 }
 // initProcessCovQ, eskf.cc:47-62 (diagonal blocks only; built on the host, it is 7 scalars)
-int lk_init_process_cov_q(lk_handle* h) {
-    CHECK_H(h);
+static int init_process_cov_q(lk_handle* h) {
     std::vector<double> Q(900, 0.0);
     auto diag3 = [&](int o, double v) {
         for (int k = 0; k < 3; ++k) Q[(o + k) * 30 + (o + k)] = v;
@@ -239,6 +238,10 @@ int lk_init_process_cov_q(lk_handle* h) {
     diag3(24, h->cfg.kin_bias_process_cov);
     diag3(27, h->cfg.contact_process_cov);
     return lk_set_Q(h, Q.data());
+}
+int lk_init_process_cov_q(lk_handle* h) {
+    CHECK_H(h);
+    return init_process_cov_q(h);
 }
 int lk_set_times(lk_handle* h, uint32_t slot, double last_predict_t, double last_update_t) {
     CHECK_H(h);
@@ -627,30 +630,28 @@ int fetch_poses(lk_handle* h, lk_pose* out, int n) {
 }
 
 // ------------------------------------------------------------------ VoxelMapManager surface
-int lk_map_build(lk_handle* h, const float* xyz_world, const float* xyz_body, size_t n) {
-    CHECK_H(h);
-    if (n == 0) return LK_OK;
+// what lk_map_build and lk_first_frame(_dev) ask before they touch anything: room for the cloud, an empty map
+static int map_build_check(lk_handle* h, size_t n) {
     if (n > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "first-frame cloud exceeds max_scan_points");
     unsigned int ctr[LK_CTR_COUNT];
     HIPCHK(h, hipMemcpy(ctr, h->map.counters, sizeof(ctr), hipMemcpyDeviceToHost));
     if (ctr[LK_CTR_NODES] != 0) return fail(h, LK_ERR_STATE, "lk_map_build needs an empty map (BuildVoxelMap runs once)");
+    return LK_OK;
+}
+// BuildVoxelMap from the two clouds in HBM (n x 3 floats each, rot / covariances of slot 0): the core of lk_map_build and lk_first_frame(_dev)
+static int map_build_dev(lk_handle* h, const float* d_w, const float* d_b, size_t n) {
     h->grid_valid = false;
-    float *d_w = nullptr, *d_b = nullptr;
     lk_pt_rec* d_bpts = nullptr;
     unsigned int *d_k0 = nullptr, *d_k1 = nullptr;
     int *d_i0 = nullptr, *d_i1 = nullptr;
     void* d_tmp = nullptr;
     size_t tmp_bytes = 0;
     DevTemps tmp;
-    HIPCHK(h, tmp.alloc(&d_w, sizeof(float) * 3 * n));
-    HIPCHK(h, tmp.alloc(&d_b, sizeof(float) * 3 * n));
     HIPCHK(h, tmp.alloc(&d_bpts, sizeof(lk_pt_rec) * n));
     HIPCHK(h, tmp.alloc(&d_k0, sizeof(unsigned int) * n));
     HIPCHK(h, tmp.alloc(&d_k1, sizeof(unsigned int) * n));
     HIPCHK(h, tmp.alloc(&d_i0, sizeof(int) * n));
     HIPCHK(h, tmp.alloc(&d_i1, sizeof(int) * n));
-    HIPCHK(h, hipMemcpyAsync(d_w, xyz_world, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_b, xyz_body, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(lk_bucket_begin_kernel, dim3(1), dim3(256), 0, h->stream, h->map);
     const int nb = (int)((n + 255) / 256);
     LAUNCH(h, "build_points", hipLaunchKernelGGL(lk_build_points_kernel, dim3(nb), dim3(256), 0, h->stream, h->map, h->pr,
@@ -665,6 +666,76 @@ int lk_map_build(lk_handle* h, const float* xyz_world, const float* xyz_body, si
     LAUNCH(h, "build_tree", hipLaunchKernelGGL(lk_build_tree_kernel, dim3(grid), dim3(LK_MB), 0, h->stream, h->map, h->pr,
                                                d_bpts, d_i1, d_i0));
     return check_map_errors(h);  // synchronises the stream; `tmp` frees the temporaries
+}
+int lk_map_build(lk_handle* h, const float* xyz_world, const float* xyz_body, size_t n) {
+    CHECK_H(h);
+    if (n == 0) return LK_OK;
+    LKCHK(map_build_check(h, n));
+    float *d_w = nullptr, *d_b = nullptr;
+    DevTemps tmp;
+    HIPCHK(h, tmp.alloc(&d_w, sizeof(float) * 3 * n));
+    HIPCHK(h, tmp.alloc(&d_b, sizeof(float) * 3 * n));
+    HIPCHK(h, hipMemcpyAsync(d_w, xyz_world, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_b, xyz_body, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
+    return map_build_dev(h, d_w, d_b, n);   // synchronises the stream before `tmp` frees the clouds
+}
+
+// ------------------------------------------------------------------ first frame (KILO.cc:332-352; lk_pre_kernels.h, lk_ff_*)
+// The raw cloud and the first package's messages are in HBM: state initialisation (one lane), cloudLidarToWorld (one thread per point),
+// BuildVoxelMap from the two clouds where they lie, then acc_norm_ and the two time stamps.
+static int first_frame_check(lk_handle* h, const void* raw, size_t n, int msg_kind, const void* msgs, size_t n_msg) {
+    if (n == 0 || n_msg == 0) return fail(h, LK_ERR_INVALID, "Data packet is not ready: the first frame needs a cloud and at least one message (KILO.cc:326-329)");
+    if (msg_kind != 1 && msg_kind != 2) return fail(h, LK_ERR_INVALID, "msg_kind must be 1 (lk_imu) or 2 (lk_kin_imu)");
+    if (!raw || !msgs) return fail(h, LK_ERR_INVALID, "null argument");
+    if (n_msg >= ((size_t)1 << 31)) return fail(h, LK_ERR_INVALID, "more than 2^31 messages");
+    return map_build_check(h, n);
+}
+static int first_frame_dev(lk_handle* h, const lk_point* d_raw, size_t n, double end_time, int msg_kind, const void* d_msgs, size_t n_msg) {
+    float *d_w = nullptr, *d_b = nullptr;
+    double* d_norm = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        d_norm = c.take<double>(1);
+        d_w = c.take<float>(3 * n), d_b = c.take<float>(3 * n);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->ff, bytes));
+    carve(h->ff.p);
+    LKCHK(init_process_cov_q(h));
+    const unsigned int stride = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
+    const unsigned int acc_off = msg_kind == 2 ? offsetof(lk_kin_imu, acc) : offsetof(lk_imu, acc);
+    static_assert(offsetof(lk_imu, gyr) == offsetof(lk_imu, acc) + 24 && offsetof(lk_kin_imu, gyr) == offsetof(lk_kin_imu, acc) + 24, "gyr lies behind acc");
+    LAUNCH(h, "ff_init", hipLaunchKernelGGL(lk_ff_init_kernel, dim3(1), dim3(256), 0, h->stream, h->d_filters, static_cast<const unsigned char*>(d_msgs),
+                                            (unsigned int)n_msg, stride, acc_off, h->cfg.gravity, end_time, d_norm));
+    LAUNCH(h, "ff_world", hipLaunchKernelGGL(lk_ff_world_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_filters, h->pr, d_raw,
+                                             (int)n, d_w, d_b));
+    LKCHK(map_build_dev(h, d_w, d_b, n));
+    double acc_norm = 0.0;
+    HIPCHK(h, hipMemcpyAsync(&acc_norm, d_norm, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->acc_norm = acc_norm;   // KILO.cc:349
+    return LK_OK;
+}
+int lk_first_frame_dev(lk_handle* h, const lk_point* d_raw, size_t n, double end_time, int msg_kind, const void* d_msgs, size_t n_msg) {
+    CHECK_H(h);
+    LKCHK(first_frame_check(h, d_raw, n, msg_kind, d_msgs, n_msg));
+    return first_frame_dev(h, d_raw, n, end_time, msg_kind, d_msgs, n_msg);
+}
+int lk_first_frame(lk_handle* h, const lk_point* raw, size_t n, double end_time, int msg_kind, const void* msgs, size_t n_msg) {
+    CHECK_H(h);
+    LKCHK(first_frame_check(h, raw, n, msg_kind, msgs, n_msg));
+    const size_t msg_bytes = n_msg * (msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu));
+    lk_point* d_raw = nullptr;
+    unsigned char* d_msgs = nullptr;
+    DevTemps tmp;
+    HIPCHK(h, tmp.alloc(&d_raw, sizeof(lk_point) * n));
+    HIPCHK(h, tmp.alloc(&d_msgs, msg_bytes));
+    HIPCHK(h, hipMemcpyAsync(d_raw, raw, sizeof(lk_point) * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_msgs, msgs, msg_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = first_frame_dev(h, d_raw, n, end_time, msg_kind, d_msgs, n_msg);
+    if (rc != LK_OK) hipStreamSynchronize(h->stream);   // (the temporaries are freed on return)
+    return rc;
 }
 
 int lk_map_update(lk_handle* h, const double* pw, const double* var9, size_t n) {
@@ -2063,7 +2134,14 @@ int lk_batch_replay_scans_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n_
     if (!n_msg) return fail(h, LK_ERR_INVALID, "null argument");
     return replay_scans(h, d_pts, n_scans, scan_off, t_begin, 2, n_msg, d_kins, true, out);
 }
-// Body of both entries: msgs is a host pointer, or a device pointer when msgs_on_device.
+// ... and the IMU records (lk_decode_imu_dev + lk_imu_split_dev).
+int lk_batch_replay_scans_imu_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
+                                  const uint32_t* n_msg, const lk_imu* d_imus, lk_pose* out) {
+    CHECK_H(h);
+    if (!n_msg) return fail(h, LK_ERR_INVALID, "null argument");
+    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, 1, n_msg, d_imus, true, out);
+}
+// Body of the three entries: msgs is a host pointer, or a device pointer when msgs_on_device.
 int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
                  const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out) {
     if (n_scans == 0 || n_scans > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_scans must be in [1, n_slots]");

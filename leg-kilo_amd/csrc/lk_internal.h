@@ -2,7 +2,7 @@
 // headers.  The library is six units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
 // kernel but the overlay's and the stream path's own), lk_stream.hip (LK_TU_STREAM: one live scan after the other with the map insert - the per-bucket
 // launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries that run them), lk_overlay.hip (LK_TU_OVERLAY: batch replay
-// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_kin.hip (LK_TU_KIN: the leg kinematics front end - HighState decode, contact detector, scan split - and its entries, lk_kin_kernels.h), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
+// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_kin.hip (LK_TU_KIN: the message front ends - HighState decode + contact detector, lk_kin_kernels.h; sensor_msgs/Imu decode, lk_imu_kernels.h; the scan split of either - and their entries), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
 // (LK_KERNELS_ELSEWHERE) and launches it through the main unit's host stub.  The overlay header's own kernels are compiled in the overlay unit only.
 #pragma once
 #if !defined(LK_TU_MAIN) && !defined(LK_TU_OVERLAY) && !defined(LK_TU_STREAM) && !defined(LK_TU_OVSCAN) && !defined(LK_TU_KIN)
@@ -164,7 +164,12 @@ struct lk_handle {
     bool kin_configured = false;
     lk_kin_config kin_cfg = {};
     lk_kin_frontend_state kin_fe = {};
-    DevBuf kin;                   // keep flags, ranks, transition maps, their scan, status words
+    DevBuf kin;                   // keep flags, ranks, transition maps, their scan, status words; the scan split's tables (either record kind)
+    // IMU front end (lk_kin.hip): the redundancy flag, the state carried from message to message, scratch
+    bool imu_configured = false, imu_redundancy = false;
+    lk_imu_frontend_state imu_fe = {};
+    DevBuf imu;                   // message offsets, keep flags, ranks, status words
+    DevBuf ff;                    // lk_first_frame(_dev): world / body clouds, acc_norm
     bool profiling = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::map<std::string, ProfEntry> prof;
@@ -372,7 +377,7 @@ int zero_scan_counters(lk_handle* h, uint32_t first_slot, uint32_t n_slots);
 int fetch_poses(lk_handle* h, lk_pose* out, int n);
 int export_map_blob(lk_handle* h, const LkMap& m, unsigned int hash_cap, void* blob, size_t* bytes);
 int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
-                 const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out);   // lk_batch_replay_scans(_kin)_dev
+                 const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out);   // lk_batch_replay_scans(_kin / _imu)_dev
 int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets, const uint32_t* bucket_off,
                   const double* bucket_dt, const double* t_begin, const uint32_t* n_imu, const void* imus, size_t msg_bytes, lk_pose* out, bool with_insert = false);
 __global__ void lk_set_times_kernel(LkFilter* filters, int n, double t);

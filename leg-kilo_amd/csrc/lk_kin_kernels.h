@@ -171,22 +171,26 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// ---- scan split (syncPackage, kin branch) ----
+// ---- scan split (syncPackage: the kin branch, ros_interface.cc:303-328, and the IMU branch, :277-301 - one rule) ----
 // One thread per scan: lb[s] = first record stamped >= scan_end[s] (n when none), eq[s] = that record is stamped exactly scan_end[s].
+// A record is `stride` bytes and starts with its stamp (lk_kin_imu::time_stamp, lk_imu::stamp).
+__device__ __forceinline__ double lk_rec_stamp(const unsigned char* __restrict__ recs, unsigned int stride, unsigned int i) {
+    return *reinterpret_cast<const double*>(recs + (size_t)i * stride);
+}
 __global__ void __launch_bounds__(256)
-    lk_kin_lb_kernel(const lk_kin_imu* __restrict__ kins, unsigned int n, const double* __restrict__ ends, unsigned int S, unsigned int* __restrict__ lb,
-                     unsigned char* __restrict__ eq) {
+    lk_kin_lb_kernel(const unsigned char* __restrict__ recs, unsigned int stride, unsigned int n, const double* __restrict__ ends, unsigned int S,
+                     unsigned int* __restrict__ lb, unsigned char* __restrict__ eq) {
     const unsigned int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     const double e = ends[s];
     unsigned int lo = 0, hi = n;
     while (lo < hi) {
         const unsigned int mid = (lo + hi) >> 1;
-        if (kins[mid].time_stamp < e) lo = mid + 1;
+        if (lk_rec_stamp(recs, stride, mid) < e) lo = mid + 1;
         else hi = mid;
     }
     lb[s] = lo;
-    eq[s] = (unsigned char)(lo < n && kins[lo].time_stamp == e);
+    eq[s] = (unsigned char)(lo < n && lk_rec_stamp(recs, stride, lo) == e);
 }
 
 // One wave carries the cursor over all scans: cursor_s = cursor_{s-1} < lb_s ? lb_s + eq_s : cursor_{s-1}.  With d_s = cursor_s - lb_s (always 0 or

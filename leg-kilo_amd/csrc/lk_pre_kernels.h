@@ -352,3 +352,52 @@ __global__ void __launch_bounds__(256)
         if (most) atomicMax(&stats[2], most);
     }
 }
+
+// ---- first frame (KILO.cc:332-352): state initialisation from the first package's messages, cloudLidarToWorld on the raw cloud ----
+// StateInitialByImu / StateInitialByKinImu (state_initial.hpp:34-117) as oracle/oracle_kilo.cc's firstFrame restates it: the running mean is
+// a serial chain over a few hundred records at most, so lane 0 runs it in plain fp64 (the unit is built with -ffp-contract=off: every
+// operation is the reference's own + - * / sqrt) while the block fills P = 1e-6 I.  msgs: n_msg records of `stride` bytes whose acc[3]
+// lies at byte acc_off and gyr[3] right behind it (lk_imu: 8, lk_kin_imu: 216).  Literal order: N starts at 1, the mean starts at message 0,
+// which the loop then visits again.  cov_acc_ / cov_gyr_ are never read by the reference and are not computed.
+__global__ void __launch_bounds__(256)
+    lk_ff_init_kernel(LkFilter* __restrict__ f, const unsigned char* __restrict__ msgs, unsigned int n_msg, unsigned int stride, unsigned int acc_off,
+                      double gravity, double end_time, double* __restrict__ acc_norm_out) {
+    for (int i = threadIdx.x; i < 900; i += 256) f->P[i] = (i / 30 == i % 30) ? 0.000001 : 0.0;
+    if (threadIdx.x != 0) return;
+    const double* m0 = reinterpret_cast<const double*>(msgs + acc_off);
+    double mean[6];   // acc, gyr
+    for (int c = 0; c < 6; ++c) mean[c] = m0[c];
+    int N = 1;
+    for (unsigned int k = 0; k < n_msg; ++k) {
+        const double* cur = reinterpret_cast<const double*>(msgs + (size_t)k * stride + acc_off);
+        for (int c = 0; c < 6; ++c) mean[c] += (cur[c] - mean[c]) / (double)N;
+        N++;
+    }
+    const double acc_norm = sqrt(mean[0] * mean[0] + mean[1] * mean[1] + mean[2] * mean[2]);
+    double* x = f->x;
+    for (int i = 0; i < LK_STATE_DOUBLES; ++i) x[i] = 0.0;   // a fresh ESKF: everything zero but rot = I (grav is set below)
+    x[0] = x[4] = x[8] = 1.0;
+    for (int c = 0; c < 3; ++c) {
+        x[18 + c] = mean[3 + c];                            // bw_ = mean_gyr
+        x[21 + c] = ((-mean[c]) / acc_norm) * gravity;      // grav_ = -mean_acc / acc_norm * gravity: divide, then multiply
+    }
+    f->last_predict_t = end_time;
+    f->last_update_t = end_time;
+    *acc_norm_out = acc_norm;
+}
+
+// pointLidarToWorld (KILO.cc:89-106) for the raw first cloud under the state lk_ff_init_kernel wrote: widen to fp64, ext_R p + ext_T,
+// rot (...) + pos with plain products and sums in the reference's order (no fused multiply-add), cast to float; the body cloud is the raw xyz.
+__global__ void __launch_bounds__(256)
+    lk_ff_world_kernel(const LkFilter* __restrict__ f, LkParams pr, const lk_point* __restrict__ raw, int n, float* __restrict__ xyz_world,
+                       float* __restrict__ xyz_body) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = reinterpret_cast<const float4*>(raw)[i];
+    const double l[3] = {(double)p.x, (double)p.y, (double)p.z};
+    double b[3], w[3];
+    for (int r = 0; r < 3; ++r) b[r] = (pr.ext_R[3 * r] * l[0] + pr.ext_R[3 * r + 1] * l[1] + pr.ext_R[3 * r + 2] * l[2]) + pr.ext_T[r];
+    for (int r = 0; r < 3; ++r) w[r] = (f->x[3 * r] * b[0] + f->x[3 * r + 1] * b[1] + f->x[3 * r + 2] * b[2]) + f->x[9 + r];
+    for (int r = 0; r < 3; ++r) xyz_world[3 * (size_t)i + r] = (float)w[r];
+    xyz_body[3 * (size_t)i] = p.x, xyz_body[3 * (size_t)i + 1] = p.y, xyz_body[3 * (size_t)i + 2] = p.z;
+}

@@ -7,6 +7,7 @@
 //                                 bucket loop of KILO::process (KILO.cc:108-399)
 //   legkilo::Kinematics        <- legkilo/src/preprocess/kinematics.h (Kinematics::processing for a batch of serialized HighState
 //                                 messages, with kinematicImuCallBack's redundancy filter) + the kin branch of syncPackage
+//   legkilo::ImuFrontend       <- RosInterface::imuCallBack for a batch of serialized sensor_msgs/Imu messages + the IMU branch of syncPackage
 //   legkilo::LidarProcessing   <- legkilo/src/preprocess/lidar_processing.h (LidarProcessing::processing for a recorded run's
 //                                 PointCloud2 messages in HBM, with the voxel grid and time sort of KILO.cc:356-370)
 //
@@ -335,12 +336,36 @@ class KiloPath {
     ESKF& eskf() { return *eskf_; }
     VoxelMapManager& map_manager() { return *map_manager_; }
     Device& device() { return *dev_; }   // the lk_handle behind both mirrors (multi-GPU helpers: legkilo_rccl.hpp)
+    std::shared_ptr<Device> device_ptr() { return dev_; }   // ... shared with the front-end mirrors (Kinematics, ImuFrontend, LidarProcessing)
     void setTimes(double last_predict, double last_update) { dev_->check(lk_set_times(dev_->h(), 0, last_predict, last_update)); }
     void setAccNorm(double a) { dev_->check(lk_set_acc_norm(dev_->h(), a)); }
     double accNorm() const {
         double a = 0.0;
         dev_->check(lk_get_acc_norm(dev_->h(), &a));
         return a;
+    }
+
+    // The first frame of KILO::process (KILO.cc:332-352) as one call (lk_first_frame): state initialisation from the first package's
+    // messages (state_initial.hpp), cloudLidarToWorld on the RAW cloud, BuildVoxelMap, acc_norm_ and both time stamps = end_time.
+    // Exactly one of the two message vectors is non-empty (only_imu_use: imus).
+    void firstFrame(const std::vector<lk_point>& cloud_raw, double end_time, const std::vector<lk_imu>& imus, const std::vector<lk_kin_imu>& kins = {}) {
+        if (imus.empty() == kins.empty()) throw std::runtime_error("firstFrame: IMU messages or kinematic + IMU messages, one of the two");
+        const bool imu_mode = !imus.empty();
+        dev_->check(lk_first_frame(dev_->h(), cloud_raw.data(), cloud_raw.size(), end_time, imu_mode ? 1 : 2,
+                                   imu_mode ? static_cast<const void*>(imus.data()) : static_cast<const void*>(kins.data()), imu_mode ? imus.size() : kins.size()));
+    }
+    // the same with the decoded cloud (lk_decode_scan_dev) and the decoded records (msg_kind 1: lk_imu, 2: lk_kin_imu) where they lie in HBM
+    void firstFrameDev(const lk_point* d_cloud_raw, size_t n, double end_time, int msg_kind, const void* d_msgs, size_t n_msg) {
+        dev_->check(lk_first_frame_dev(dev_->h(), d_cloud_raw, n, end_time, msg_kind, d_msgs, n_msg));
+    }
+    // lk_batch_replay_scans_imu_dev: recorded scans and their IMU records, both in HBM (ImuFrontend::syncPackages says how many per scan)
+    std::vector<lk_pose> replayRecordedRunImuDev(const lk_point* d_pts, const std::vector<uint64_t>& scan_off, const std::vector<double>& t_begin,
+                                                 const std::vector<uint32_t>& n_msg, const lk_imu* d_imus) {
+        const size_t S = t_begin.size();
+        if (scan_off.size() != S + 1 || n_msg.size() != S) throw std::runtime_error("replayRecordedRunImuDev: table sizes differ");
+        std::vector<lk_pose> out(S);
+        dev_->check(lk_batch_replay_scans_imu_dev(dev_->h(), d_pts, S, scan_off.data(), t_begin.data(), n_msg.data(), d_imus, out.data()));
+        return out;
     }
 
     // KILO.cc:108-233
@@ -573,6 +598,46 @@ class Kinematics {
         n_msg.assign(std::max<size_t>(scan_end.size(), 1), 0);
         size_t n_packaged = 0, consumed = 0;
         dev_->check(lk_kin_split_dev(dev_->h(), d_kins, n_kins, scan_end.data(), scan_end.size(), n_msg.data(), &n_packaged, &consumed));
+        n_msg.resize(scan_end.size());
+        if (n_consumed) *n_consumed = consumed;
+        return n_packaged;
+    }
+
+   private:
+    std::shared_ptr<Device> dev_;
+};
+
+// RosInterface::imuCallBack (ros_interface.cc:194-219) for a batch of serialized sensor_msgs/Imu messages (ROS1 serialisation, message i =
+// the bytes [msg_off[i], msg_off[i+1]) of the buffer, e.g. a recorded /imu topic): the records of the kept ones - what the callback pushes
+// into imu_cache_.  State carried across calls: the previous message's z values, the last kept stamp (frontend() / setFrontend()).
+class ImuFrontend {
+   public:
+    ImuFrontend(bool redundancy, std::shared_ptr<Device> dev) : dev_(std::move(dev)) { dev_->check(lk_imu_configure(dev_->h(), redundancy ? 1 : 0)); }
+    std::vector<lk_imu> processing(const void* msgs, const std::vector<uint64_t>& msg_off) {
+        const size_t n = msg_off.empty() ? 0 : msg_off.size() - 1;
+        std::vector<lk_imu> out(std::max<size_t>(n, 1));
+        size_t n_out = 0;
+        dev_->check(lk_decode_imu(dev_->h(), msgs, n, msg_off.data(), out.data(), &n_out));
+        out.resize(n_out);
+        return out;
+    }
+    // bytes and records in HBM (d_out: room for one record per message); returns the number kept
+    size_t processingDev(const void* d_msgs, const std::vector<uint64_t>& msg_off, lk_imu* d_out) {
+        size_t n_out = 0;
+        dev_->check(lk_decode_imu_dev(dev_->h(), d_msgs, msg_off.empty() ? 0 : msg_off.size() - 1, msg_off.data(), d_out, &n_out));
+        return n_out;
+    }
+    lk_imu_frontend_state frontend() const {
+        lk_imu_frontend_state st;
+        dev_->check(lk_imu_get_frontend(dev_->h(), &st));
+        return st;
+    }
+    void setFrontend(const lk_imu_frontend_state& st) { dev_->check(lk_imu_set_frontend(dev_->h(), &st)); }
+    // syncPackage's IMU branch (ros_interface.cc:277-301) over records already in HBM; n_msg[s] = records of packaged scan s
+    size_t syncPackages(const lk_imu* d_imus, size_t n_imus, const std::vector<double>& scan_end, std::vector<uint32_t>& n_msg, size_t* n_consumed) {
+        n_msg.assign(std::max<size_t>(scan_end.size(), 1), 0);
+        size_t n_packaged = 0, consumed = 0;
+        dev_->check(lk_imu_split_dev(dev_->h(), d_imus, n_imus, scan_end.data(), scan_end.size(), n_msg.data(), &n_packaged, &consumed));
         n_msg.resize(scan_end.size());
         if (n_consumed) *n_consumed = consumed;
         return n_packaged;

@@ -400,6 +400,21 @@ class KiloPath {
     void setAccNorm(double a) { impl_.setAccNorm(a); }                                                       // KILO.cc:349
     double accNorm() const { return impl_.accNorm(); }
 
+    // The first frame of KILO::process (KILO.cc:332-352) as one call: StateInitialByImu (imu_mode_only) or StateInitialByKinImu on the
+    // package's messages, cloudLidarToWorld on cloud_raw, BuildVoxelMap, acc_norm_ and both time stamps = end_time (lk_first_frame).
+    template <class ImuQueue, class KinQueue>
+    void firstFrame(const PointCloudType& cloud_raw, double end_time, bool imu_mode_only, const ImuQueue& imus, const KinQueue& kin_imus) {
+        std::vector<lk_point> pts(cloud_raw.points.size());
+        for (size_t i = 0; i < pts.size(); ++i) pts[i] = lk_point{cloud_raw.points[i].x, cloud_raw.points[i].y, cloud_raw.points[i].z, cloud_raw.points[i].curvature};
+        std::vector<lk_imu> li;
+        std::vector<lk_kin_imu> lk;
+        if (imu_mode_only)
+            for (const auto& m : imus) li.push_back(to_lk(*m));
+        else
+            for (const auto& k : kin_imus) lk.push_back(to_lk(k));
+        impl_.firstFrame(pts, end_time, li, lk);
+    }
+
     // KILO.cc:108-233
     bool predictUpdatePoint(double current_time, size_t idx_i, size_t idx_j, const PointCloudType& cloud_down_body, PointCloudType& cloud_down_world,
                             size_t& success_pts_size_out) {

@@ -359,6 +359,37 @@ def imu_stream(traj, t0, t1, rate=200.0, seed=3003, acc_noise=0.02, gyr_noise=0.
     return out
 
 
+IMU_MSG_FIXED_BYTES = 312   # ROS1 serialisation of sensor_msgs/Imu without its frame_id bytes
+# byte offsets of its fields for a frame_id of length 0 (everything behind frame_id moves by the frame_id's length)
+IMU_MSG_SEQ, IMU_MSG_SEC, IMU_MSG_NSEC, IMU_MSG_LEN, IMU_MSG_FRAME, IMU_MSG_GYR, IMU_MSG_ACC = 0, 4, 8, 12, 16, 120, 216
+
+
+def imu_messages(imus, frame_ids, seq0=0, seed=0):
+    """IMU_DTYPE records -> their serialized sensor_msgs/Imu messages (what a recorded /imu topic holds), back to back:
+    (buf uint8, msg_off uint64 [n + 1]).  frame_ids: one bytes / str per message (or one for all).  The stamp is written as sec / nsec
+    (nsec = the rounded fraction), so a decoded stamp is ros::Time::toSec of those two - (double)sec + 1e-9 * (double)nsec - and not the
+    record's double.  Fields the decoder does not read (orientation, the three covariances) hold random bytes."""
+    imus = np.asarray(imus)
+    n = len(imus)
+    if isinstance(frame_ids, (bytes, str)):
+        frame_ids = [frame_ids] * n
+    ids = [f.encode() if isinstance(f, str) else bytes(f) for f in frame_ids]
+    assert len(ids) == n
+    L = np.array([len(f) for f in ids], dtype=np.int64)
+    msg_off = np.r_[0, np.cumsum(IMU_MSG_FIXED_BYTES + L)].astype(np.uint64)
+    buf = np.random.default_rng(seed).integers(0, 256, size=int(msg_off[-1]), dtype=np.uint8)
+    sec = np.floor(imus["stamp"]).astype(np.int64)
+    nsec = np.round((imus["stamp"] - sec) * 1e9).astype(np.int64)
+    sec, nsec = sec + (nsec >= 1_000_000_000), np.where(nsec >= 1_000_000_000, nsec - 1_000_000_000, nsec)
+    for i in range(n):
+        o, l = int(msg_off[i]), int(L[i])
+        buf[o:o + 16] = np.array([(seq0 + i) & 0xFFFFFFFF, sec[i], nsec[i], l], dtype="<u4").view(np.uint8)
+        buf[o + 16:o + 16 + l] = np.frombuffer(ids[i], dtype=np.uint8)
+        buf[o + l + IMU_MSG_GYR:o + l + IMU_MSG_GYR + 24] = imus["gyr"][i].astype("<f8").view(np.uint8)
+        buf[o + l + IMU_MSG_ACC:o + l + IMU_MSG_ACC + 24] = imus["acc"][i].astype("<f8").view(np.uint8)
+    return buf, msg_off
+
+
 def foot_pos_vel(q, dq, p):
     """kinematics.cc:54-90 — leg order FR FL RR RL; q, dq: (4,3) hip/thigh/calf angles and rates."""
     lt, lc, d, ox, oy = p["leg_thigh_length"], p["leg_calf_length"], p["leg_thigh_offset"], p["leg_offset_x"], p["leg_offset_y"]

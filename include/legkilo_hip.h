@@ -274,6 +274,31 @@ int lk_process_scan(lk_handle* h, const lk_point* sorted_pts, size_t n, double t
  * caller: bucket b covers [bucket_off[b], bucket_off[b+1]) at time t_begin + bucket_dt[b]. */
 int lk_process_scan_dev(lk_handle* h, const lk_point* d_pts, size_t n, double t_begin, const uint32_t* bucket_off,
                         const double* bucket_dt, size_t n_buckets, lk_pose* out);
+/* A recorded run LIVE, in one call, from device-resident scans and messages (what lk_decode_scans_dev, lk_decode_imu_dev + lk_imu_split_dev or
+ * lk_decode_highstate_dev + lk_kin_split_dev leave in HBM): scan s = d_pts[scan_off[s], scan_off[s+1]), time-sorted, starting at t_begin[s], is
+ * processed on slot 0 against the handle's map WITH the map insert, s = 0 .. n_scans-1 in order - lk_process_scan on a host copy of the same
+ * points and messages, bit for bit: lk_pose (out[s]), state, covariance, time stamps, world cloud, map.  scan_off / t_begin / n_msg are host
+ * tables; scan_off[0] may be non-zero (a run's scan 0 is the first frame, lk_first_frame_dev: pass the front end's tables shifted by one) and
+ * nothing in front of it is read; n_scans is not bounded by n_slots.  msg_kind / n_msg / d_msgs as for lk_batch_replay_scans_imu_dev / _kin_dev:
+ * n_msg[s] device records per scan, concatenated (0: none).  d_world_out (may be NULL, 16-byte aligned): one 16-byte record per point, index-aligned with d_pts -
+ * cloud_down_world of every scan as x, y, z, intensity - so the run's registered cloud stays in HBM.  opt (may be NULL): after every scan,
+ * lk_map_slide(pose.pos, sliding_thresh, half_map_size); *n_slides counts the slides.  The bucket tables of all scans are built once on the
+ * device and a few words per scan are read back; every scan then takes the kernels lk_process_scan would choose for it (grid-resident,
+ * scan-resident, per-bucket launches; lk_stream_resident / lk_stream_grid / lk_stream_pipeline / profiling are honoured), and only a scan on
+ * the per-bucket launches has its table rows and messages read back.  Synchronous.
+ * Refused before anything on the handle changes, naming the scan: LK_ERR_INVALID for n_scans == 0, an empty scan, msg_kind outside 0..2 or
+ * non-zero with n_msg NULL, a scan whose curvature decreases or is not finite (the first such scan); LK_ERR_CAPACITY for a scan above
+ * max_scan_points.  An error from scan k's own launches (pool capacity, LK_ERR_TIMEOUT) ends the run: *n_done = k, out[0..k) are valid and the
+ * handle is what lk_process_scan leaves after that error in scan k of a loop. */
+typedef struct lk_run_options {
+    double  sliding_thresh;   /* lk_map_slide's arguments, applied after every scan with that scan's position */
+    int32_t half_map_size;    /* 0: never slide */
+    int32_t pad_;
+} lk_run_options;
+int lk_run_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
+                     int msg_kind, const uint32_t* n_msg, const void* d_msgs, const lk_run_options* opt /* may be NULL */,
+                     float* d_world_out /* may be NULL */, lk_pose* out /* n_scans, may be NULL */,
+                     size_t* n_done /* may be NULL */, uint32_t* n_slides /* may be NULL */);
 
 /* ---- sensor decode: LidarProcessing::{velodyne,ouster,hesai}Handler, lidar_processing.cc:25-108 ----
  * msg_data = sensor_msgs::PointCloud2::data (n_points x point_step bytes).  Keeps every filter_num-th point that is

@@ -25,7 +25,7 @@ EXPORTS = [
     "lk_kin_configure", "lk_kin_get_frontend", "lk_kin_set_frontend", "lk_decode_highstate", "lk_decode_highstate_dev", "lk_kin_split_dev",
     "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
     "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
-    "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev",
+    "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev",
 ]
 
 
@@ -285,6 +285,70 @@ class LegKiloHip:
         self._chk(self.L.lk_process_scan_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n), C.c_double(t_begin), _p(off), _p(dt),
                                              C.c_size_t(len(dt)), C.byref(pose)))
         return pose
+
+    def run_scans_dev(self, d_pts, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, slide=None, d_world=0):
+        """A recorded run live on slot 0, in one call, from device-resident scans and message records (lk_run_scans_dev): scan s =
+        d_pts[scan_off[s] : scan_off[s + 1]] (scan_off[0] may be non-zero), n_msg[s] records of msg_kind (1: lk_imu, 2: lk_kin_imu) per scan
+        at d_msgs.  slide = (sliding_thresh, half_map_size): lk_map_slide after every scan.  d_world: device room for one 16-byte record
+        per point, index-aligned with d_pts, or 0.  Returns (poses, n_slides); a LegKiloError carries n_done and the poses of the scans
+        that went through."""
+        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
+        n_scans = len(so) - 1
+        tb = _f64(t_begins)
+        assert len(tb) == max(n_scans, 0)
+        nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
+        assert nm is None or len(nm) == n_scans
+        opt = None if slide is None else abi.lk_run_options(float(slide[0]), int(slide[1]), 0)
+        poses = (abi.lk_pose * max(n_scans, 1))()
+        n_done, n_slides = C.c_size_t(0), C.c_uint32(0)
+        rc = self.L.lk_run_scans_dev(self.h, C.c_void_p(d_pts), C.c_size_t(max(n_scans, 0)), _p(so), _p(tb), C.c_int(msg_kind), _p(nm),
+                                     C.c_void_p(d_msgs) if d_msgs else None, C.byref(opt) if opt is not None else None,
+                                     C.c_void_p(d_world) if d_world else None, poses, C.byref(n_done), C.byref(n_slides))
+        try:
+            self._chk(rc)
+        except LegKiloError as e:
+            e.n_done, e.poses = n_done.value, list(poses[: n_done.value])
+            raise
+        return list(poses[:n_scans]), n_slides.value
+
+    def run_scans(self, scans, t_begins, imus=None, kins=None, slide=None, world=False):
+        """Convenience: host scans (lk_point arrays, time-sorted, any sizes) and per-scan message arrays (imus: IMU_DTYPE, or kins:
+        KIN_DTYPE) -> HBM -> run_scans_dev.  Returns (poses, worlds, n_slides): worlds = per-scan n x 3 float32 cloud_down_world
+        (world=True) or None."""
+        assert imus is None or kins is None
+        allpts = np.ascontiguousarray(np.concatenate(scans))
+        scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])].astype(np.uint64)
+        msgs = imus if imus is not None else kins
+        kind, n_msg, flat = 0, None, None
+        if msgs is not None:
+            kind = 1 if imus is not None else 2
+            n_msg = np.fromiter((len(m) for m in msgs), dtype=np.uint32, count=len(scans))
+            if n_msg.sum():
+                flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in msgs if len(m)]))
+        dptrs = []
+        try:
+            d_pts = self.device_malloc(allpts.nbytes)
+            dptrs.append(d_pts)
+            self.h2d(d_pts, allpts)
+            d_msgs = 0
+            if flat is not None:
+                d_msgs = self.device_malloc(flat.nbytes)
+                dptrs.append(d_msgs)
+                self.h2d(d_msgs, flat)
+            d_world = 0
+            if world:
+                d_world = self.device_malloc(16 * len(allpts))
+                dptrs.append(d_world)
+            poses, n_slides = self.run_scans_dev(d_pts, scan_off, t_begins, kind, n_msg, d_msgs, slide, d_world)
+            worlds = None
+            if world:
+                w = np.zeros((len(allpts), 4), dtype=np.float32)
+                self.d2h(w, d_world)
+                worlds = [np.ascontiguousarray(w[int(a):int(b), :3]) for a, b in zip(scan_off[:-1], scan_off[1:])]
+            return poses, worlds, n_slides
+        finally:
+            for d in dptrs:
+                self.device_free(d)
 
     # ---- sensor decode + preprocessing in front of the path ----
     def decode_scan(self, msg_bytes, n_points, layout, time_scale, filter_num, blind, header_stamp=0.0):

@@ -2218,6 +2218,64 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     return ragged_launch(h, d_pts, S, rg, d_t0, (int)biggest, (size_t)most, nullptr, msg_kind, out);
 }
 
+// The tables of a live run (RunTables): replay_scans' chain over the run's points - d_pts is the run's FIRST point, scan_off is counted from
+// wherever the caller counts and only its differences matter - followed by the per-scan summaries.  Nothing of the handle but scratch is touched.
+int run_tables(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, const uint32_t* n_msg, RunTables* out) {
+    const size_t S = n_scans, n = scan_off[S] - scan_off[0];
+    if (n >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 points in one run");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    unsigned long long *d_so = nullptr, *d_ps = nullptr;
+    double *d_t0 = nullptr, *d_tb = nullptr;
+    unsigned int *d_fl = nullptr, *d_rk = nullptr, *d_bs = nullptr, *d_mo = nullptr, *d_st = nullptr, *d_sum = nullptr, *d_nbp = nullptr, *d_sync = nullptr;
+    int* d_rs = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        d_so = c.take<unsigned long long>(S + 1), d_t0 = c.take<double>(S);       // scan_off, t_begin
+        d_ps = c.take<unsigned long long>(n + 1), d_tb = c.take<double>(n);       // CSR tables: first point and time of every bucket
+        d_fl = c.take<unsigned int>(n), d_rk = c.take<unsigned int>(n);           // bucket-start flags, their ranks
+        d_bs = c.take<unsigned int>(S + 1), d_mo = c.take<unsigned int>(S + 1);   // first bucket / first message of every scan
+        d_st = c.take<unsigned int>(8);                                           // stats
+        d_sum = c.take<unsigned int>(4 * S), d_nbp = c.take<unsigned int>(2 * S); // per-scan summaries, { buckets, 0 } pairs
+        d_sync = c.take<unsigned int>(4 * S), d_rs = c.take<int>(8 * S);          // per-scan barrier words, LkResume
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->ragdev, bytes, bytes / 4));
+    carve(h->ragdev.p);
+    std::vector<unsigned long long> so(S + 1);
+    for (size_t s = 0; s <= S; ++s) so[s] = scan_off[s] - scan_off[0];
+    HIPCHK(h, hipMemcpyAsync(d_so, so.data(), 8 * (S + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_t0, t_begin, 8 * S, hipMemcpyHostToDevice, h->stream));
+    std::vector<unsigned int> moff;
+    if (n_msg) {
+        moff.resize(S + 1, 0);
+        for (size_t s = 0; s < S; ++s) moff[s + 1] = moff[s] + n_msg[s];
+        HIPCHK(h, hipMemcpyAsync(d_mo, moff.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipMemsetAsync(d_st, 0, 32, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_sync, 0, 16 * S, h->stream));
+    const unsigned int nblk = (unsigned int)((n + 255) / 256);
+    hipLaunchKernelGGL(lk_rag_flag_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_st);
+    size_t tmp_bytes = 0;
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, tmp_bytes, d_fl, d_rk, n, h->stream));
+    LKCHK(reserve(h, h->prim_tmp, tmp_bytes));
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tmp_bytes, d_fl, d_rk, n, h->stream));
+    hipLaunchKernelGGL(lk_rag_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_rk, d_t0,
+                       d_ps, d_tb, d_bs, d_st);
+    hipLaunchKernelGGL(lk_rag_scan_summary_kernel, dim3((unsigned int)((S + 3) / 4)), dim3(256), 0, h->stream, d_ps, d_bs, n_msg ? d_mo : (unsigned int*)nullptr,
+                       (int)S, d_st, d_sum, d_nbp, d_rs);
+    HIPCHK(h, hipGetLastError());
+    unsigned int st[8];
+    out->bstart.resize(S + 1), out->sum.resize(4 * S);
+    HIPCHK(h, hipMemcpyAsync(st, d_st, 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out->bstart.data(), d_bs, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out->sum.data(), d_sum, 16 * S, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out->first_unsorted = st[4];
+    out->d_ps = d_ps, out->d_tb = d_tb, out->d_nbp = d_nbp, out->d_mo = n_msg ? d_mo : nullptr, out->d_sync = d_sync, out->d_resume = d_rs;
+    return LK_OK;
+}
+
 // Asynchronous, double-buffered batch replay.  The batch uses filter slots [first_slot, first_slot + n_scans); calls whose
 // slot ranges alternate (first_slot = 0, n_scans, 0, ...) run on alternate HIP streams, so the single-workgroup update /
 // predict kernels of one batch overlap the full-size residual launches of the next instead of sitting between them.

@@ -368,6 +368,21 @@ static inline void imu_noise(const lk_config& c, double* Rn) {   // diag of R of
     Rn[3] = Rn[4] = Rn[5] = c.imu_gyr_meas_noise;
 }
 
+// Tables of a live run (lk_run_scans_dev), built once per call on the device by run_tables() in h->ragdev: the CSR bucket tables of all its scans
+// (lk_rag_flag / rocPRIM scan / lk_rag_scatter, offsets counted from the run's first point) and, per scan, what a resident stream kernel wants
+// besides them.  The host gets the scans' first buckets and lk_rag_scan_summary_kernel's summaries: a few words per scan, read back once.
+struct RunTables {
+    const unsigned long long* d_ps = nullptr;   // first point of every bucket of the run (+ the end)
+    const double* d_tb = nullptr;               // its time
+    const unsigned int* d_nbp = nullptr;        // [S][2] { buckets, 0 }
+    const unsigned int* d_mo = nullptr;         // [S + 1] prefix sum of the scans' message counts (null: no messages)
+    unsigned int* d_sync = nullptr;             // [S][4] the grid-resident kernel's barrier words, zeroed
+    int* d_resume = nullptr;                    // [S] LkResume, reset
+    std::vector<unsigned int> bstart;           // [S + 1] first bucket of every scan
+    std::vector<unsigned int> sum;              // [S][4] buckets, largest bucket, smallest bucket, first message
+    unsigned int first_unsorted = 0xffffffffu;  // first scan whose curvature decreases or is not finite
+};
+
 // ---- shared between the translation units (all with C linkage: they are defined inside the units' extern "C" regions)
 extern "C" {
 // main unit (legkilo_hip.hip)
@@ -380,6 +395,7 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
                  const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out);   // lk_batch_replay_scans(_kin / _imu)_dev
 int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets, const uint32_t* bucket_off,
                   const double* bucket_dt, const double* t_begin, const uint32_t* n_imu, const void* imus, size_t msg_bytes, lk_pose* out, bool with_insert = false);
+int run_tables(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, const uint32_t* n_msg, struct RunTables* out);
 __global__ void lk_set_times_kernel(LkFilter* filters, int n, double t);
 __global__ void __launch_bounds__(LK_WAVE, 2) lk_rag_advance_kernel(LkFilter* filters, const double* __restrict__ Q, LkRagged rg, int b, int msg_kind);
 int upload_xyz_as_points(lk_handle* h, const float* xyz, size_t n);   // n x 3 floats -> h->d_scan as lk_point records

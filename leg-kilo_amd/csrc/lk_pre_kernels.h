@@ -310,10 +310,11 @@ __global__ void __launch_bounds__(256)
     const bool head = i == scan_off[s];
     const float cp = head ? c : pts[i - 1].curvature;
     flag[i] = (head || c != cp) ? 1u : 0u;
-    if (!(c >= cp) || !isfinite(c)) stats[3] = 1u;   // out of time order, NaN or +-inf (an infinite stamp would make the predict's dt infinite):
-                                                     // the caller skipped the sort of KILO.cc:367 or handed over a corrupt cloud
+    if (!(c >= cp) || !isfinite(c)) atomicMax(&stats[3], (unsigned int)(S - s));   // out of time order, NaN or +-inf (an infinite stamp would make the
+                                                     // predict's dt infinite): the caller skipped the sort of KILO.cc:367 or handed over a corrupt cloud
 }
-// stats: [0] total buckets B, [1] largest bucket (points), [2] most buckets in a scan, [3] 1: some scan is not sorted by time
+// stats: [0] total buckets B, [1] largest bucket (points), [2] most buckets in a scan, [3] non-zero: some scan is not sorted by time - S - s of
+// the FIRST such scan s (the largest S - s any offending point reports), [4] that scan's index or 0xffffffff (lk_rag_scan_summary_kernel)
 __global__ void __launch_bounds__(256)
     lk_rag_scatter_kernel(const lk_point* __restrict__ pts, unsigned long long n, const unsigned long long* __restrict__ scan_off, int S,
                           const unsigned int* __restrict__ flag, const unsigned int* __restrict__ rank, const double* __restrict__ t_begin,
@@ -351,6 +352,34 @@ __global__ void __launch_bounds__(256)
         if (big) atomicMax(&stats[1], big);
         if (most) atomicMax(&stats[2], most);
     }
+}
+// Per-scan summaries of the CSR tables for a LIVE run (lk_run_scans_dev), where every scan is a launch sequence of its own and the host picks
+// the kernel scan by scan: one wave per scan strides over the scan's buckets, wave reductions as above.  sum[s] = { buckets, largest bucket,
+// smallest bucket, first message }; nbp[s] = { buckets, 0 }, the pair a stream kernel reads through LkRagged::nb for "a batch of one scan";
+// resume[s] = that scan's LkResume (lk_stream.hip: 8 ints), reset, its message cursor at the scan's first message (msg_off: the prefix sum of
+// the scans' message counts, or null).  Scan 0's wave also turns stats[3] into the index of the first unsorted scan (stats[4]).
+__global__ void __launch_bounds__(256)
+    lk_rag_scan_summary_kernel(const unsigned long long* __restrict__ pt_start, const unsigned int* __restrict__ bstart, const unsigned int* __restrict__ msg_off,
+                               int S, unsigned int* __restrict__ stats, unsigned int* __restrict__ sum, unsigned int* __restrict__ nbp, int* __restrict__ resume) {
+    const int s = (int)((blockIdx.x * 256u + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (s >= S) return;   // (wave-uniform)
+    const unsigned int b0 = bstart[s], b1 = bstart[s + 1];
+    unsigned int big = 0u, small = 0xffffffffu;
+    for (unsigned int g = b0 + lane; g < b1; g += LK_WAVE) {
+        const unsigned int n = (unsigned int)(pt_start[g + 1] - pt_start[g]);
+        big = max(big, n), small = min(small, n);
+    }
+    for (int m = 32; m; m >>= 1) {
+        big = max(big, (unsigned int)__shfl_xor((int)big, m));
+        small = min(small, (unsigned int)__shfl_xor((int)small, m));
+    }
+    if (lane == 0) {
+        const unsigned int m0 = msg_off ? msg_off[s] : 0u;
+        sum[4 * s] = b1 - b0, sum[4 * s + 1] = big, sum[4 * s + 2] = small, sum[4 * s + 3] = m0;
+        nbp[2 * s] = b1 - b0, nbp[2 * s + 1] = 0u;
+        if (s == 0) stats[4] = stats[3] ? (unsigned int)S - stats[3] : 0xffffffffu;
+    }
+    if (lane < 8) resume[8 * s + lane] = lane == 2 ? (int)(msg_off ? msg_off[s] : 0u) : lane == 4 ? -1 : 0;   // { bf, stage1, qi, bi, fb_bucket = -1, 0, 0, 0 }
 }
 
 // ---- first frame (KILO.cc:332-352): state initialisation from the first package's messages, cloudLidarToWorld on the raw cloud ----

@@ -1101,6 +1101,19 @@ static ScanTables scan_tables(void* base, size_t nb, size_t msg_bytes_total) {
     r.bytes = c.total();
     return r;
 }
+static_assert(sizeof(LkResume) == 32 && offsetof(LkResume, qi) == 8 && offsetof(LkResume, fb_bucket) == 16, "lk_rag_scan_summary_kernel writes LkResume as eight ints");
+// What a resident stream kernel's launches read of ONE scan, wherever its tables were made: the staged upload below (a host-side bucket search),
+// or the rows of scan s in the device-built tables of a run (RunTables, lk_run_scans_dev).
+struct ScanDev {
+    const unsigned long long* po;   // [nb+1] first point of every bucket, counted from the launches' d_pts
+    const double* t;                // [nb] its time
+    const unsigned int *nb, *io;    // { nb, 0 }; io[1] = where the scan's messages end in `im` (they begin at the reset LkResume::qi)
+    const void* im;                 // message records
+    unsigned int* sync;             // [4] zeroed
+    LkResume* rs;                   // reset
+    size_t nbk;                     // nb, for the host
+    int2* ids;                      // the speculative pass's root codes, indexed like d_pts
+};
 // fills the staging copy and uploads it; returns the device copy's arrays
 static int upload_scan_tables(lk_handle* h, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime, const void* msgs, size_t n_msg,
                        size_t msg_bytes, ScanTables* dev) {
@@ -1120,6 +1133,7 @@ static int upload_scan_tables(lk_handle* h, const std::vector<unsigned long long
     *dev = scan_tables(h->rag.p, nb, msg_bytes * n_msg);
     return LK_OK;
 }
+static ScanDev scan_dev(lk_handle* h, const ScanTables& dv, size_t nb) { return ScanDev{dv.po, dv.t, dv.nb, dv.io, dv.im, dv.sync, dv.rs, nb, h->d_ids}; }
 
 // bound of the resident kernels' device-side waits (LEGKILO_RESIDENT_TIMEOUT_MS, debug aid: raise it under a profiler); read once per process
 static unsigned int resident_timeout_ms() {
@@ -1137,13 +1151,19 @@ static int backup_filter(lk_handle* h) {
 // point and absolute time of bucket k (nb buckets, bstart[nb] = n); the messages are the scan's lk_imu or lk_kin_imu records.
 // The scan's result comes back through finish_scan; a launch that stopped at fallback items is followed by lk_resident_fallback_kernel and
 // another launch from where it stopped, until the scan is through (LkResume).
+static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, int msg_kind, float* d_world, lk_pose* pose);
 static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime,
                              const void* msgs, size_t n_msg, int msg_kind, float* d_world, lk_pose* pose) {
-    const size_t nb = btime.size();
-    const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
     ScanTables dv;
-    int rc = upload_scan_tables(h, bstart, btime, msgs, n_msg, msg_bytes, &dv);
+    int rc = upload_scan_tables(h, bstart, btime, msgs, n_msg, msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu), &dv);
     if (rc) return rc;
+    return resident_rounds(h, d_pts, scan_dev(h, dv, btime.size()), msg_kind, d_world, pose);
+}
+// launch / resume until the scan is through
+static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, int msg_kind, float* d_world, lk_pose* pose) {
+    const size_t nb = dv.nbk;
+    const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
+    int rc;
     LkResume* d_rs = dv.rs;
     LkRagged rg;
     rg.pt_off = dv.po;
@@ -1180,7 +1200,7 @@ static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vec
     for (size_t round = 0;; ++round) {
         h->fbackup_valid = true;   // (finish_scan's error check ends the previous launch's claim on the copy; it is still the pre-scan state)
     LAUNCH(h, "scan_stream", hipLaunchKernelGGL(k, dim3(1), dim3((1 + LK_INS_WAVES) * LK_WAVE), 0, h->stream, h->map, h->pr, h->d_filters, d_pts, rg, h->d_Q, h->d_snap, d_world,
-                                                h->d_ids, epoch0, h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, d_rs));
+                                                dv.ids, epoch0, h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, d_rs));
 #ifdef LK_DEBUG_RES
     {
         unsigned long long hb[32];
@@ -1243,12 +1263,17 @@ static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vec
     return LK_OK;
 }
 // The bucket loop of a scan of LARGE buckets as one grid-resident launch (lk_scan_grid_kernel); same table layout as run_scan_resident.
+static int grid_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, size_t biggest, float* d_world, lk_pose* pose);
 static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime,
                          size_t biggest, float* d_world, lk_pose* pose) {
-    const size_t nb = btime.size();
     ScanTables dv;
     int rc = upload_scan_tables(h, bstart, btime, nullptr, 0, 0, &dv);
     if (rc) return rc;
+    return grid_rounds(h, d_pts, scan_dev(h, dv, btime.size()), biggest, d_world, pose);
+}
+static int grid_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, size_t biggest, float* d_world, lk_pose* pose) {
+    const size_t nb = dv.nbk;
+    int rc;
     if ((rc = backup_filter(h))) return rc;
     LkRagged rg;
     memset(&rg, 0, sizeof(rg));
@@ -1329,66 +1354,18 @@ static bool grid_takes(const lk_handle* h, size_t smallest, size_t biggest) {
     return grid_enabled(h) && smallest > (size_t)LK_SMALL_MAX && (h->gridscan_mode == 2 || biggest <= (size_t)LK_GRIDSCAN_AUTO_MAX);
 }
 
-int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n, double t_begin, const lk_imu* imus,
-             size_t n_imu, const lk_kin_imu* kins, size_t n_kin, float* xyz_world_out, lk_pose* out) {
-    int rc = zero_scan_counters(h, 0, 1);
-    if (rc) return rc;
-    if (resident_enabled(h) || grid_enabled(h)) {
-        std::vector<unsigned long long> bstart;
-        std::vector<double> btime;
-        size_t biggest = 0, smallest = n;
-        for (size_t i = 0; i < n;) {   // runs of equal curvature = buckets (KILO.cc:375-378)
-            size_t j = i + 1;
-            while (j < n && pts[i].curvature == pts[j].curvature) j++;
-            bstart.push_back(i);
-            btime.push_back(t_begin + pts[i].curvature);
-            biggest = std::max(biggest, j - i);
-            smallest = std::min(smallest, j - i);
-            i = j;
-        }
-        bstart.push_back(n);
-        if (grid_takes(h, smallest, biggest) && n_imu == 0 && n_kin == 0) {   // every bucket takes the large-bucket kernels: one grid-resident launch
-            lk_pose pose;
-            rc = run_scan_grid(h, d_pts, bstart, btime, biggest, xyz_world_out ? h->d_world : nullptr, &pose);
-            if (rc) return rc;
-            std::vector<float> w;
-            if (xyz_world_out) {
-                w.resize(4 * n);
-                HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            }
-            if (xyz_world_out)
-                for (size_t i = 0; i < n; ++i)
-                    for (int c = 0; c < 3; ++c) xyz_world_out[3 * i + c] = w[4 * i + c];
-            if (out) *out = pose;
-            return LK_OK;
-        }
-        if (resident_enabled(h) && biggest <= LK_RESIDENT_MAX) {
-            lk_pose pose;
-            rc = run_scan_resident(h, d_pts, bstart, btime, n_kin ? (const void*)kins : (const void*)imus, n_kin ? n_kin : n_imu, n_kin ? 2 : (n_imu ? 1 : 0),
-                                   xyz_world_out ? h->d_world : nullptr, &pose);
-            if (rc) return rc;
-            std::vector<float> w;
-            if (xyz_world_out) {
-                w.resize(4 * n);
-                HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            }
-            if (xyz_world_out)
-                for (size_t i = 0; i < n; ++i)
-                    for (int c = 0; c < 3; ++c) xyz_world_out[3 * i + c] = w[4 * i + c];
-            if (out) *out = pose;
-            return LK_OK;
-        }
-    }
+// The per-bucket launches of a scan (KILO.cc:375-395) from its bucket table - bstart[k] / btime[k] as for run_scan_resident, bstart counted from
+// d_pts and d_world - with the scan's messages as host records between them.  Ends with the pipelined path's inserts joined; the caller finishes the scan.
+static int run_scan_launches(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime, const lk_imu* imus,
+                             size_t n_imu, const lk_kin_imu* kins, size_t n_kin, float* d_world) {
+    int rc;
     if (h->spec_enable && (rc = backup_filter(h))) return rc;
+    const size_t nb = btime.size();
     size_t qi = 0, qk = 0;
-    size_t idx_i = 0;
     bool pre_predicted = false;
-    while (idx_i < n) {  // KILO.cc:375-395
-        double cur_point_time = t_begin + pts[idx_i].curvature;
-        size_t idx_j = idx_i + 1;
-        while (idx_j < n && pts[idx_i].curvature == pts[idx_j].curvature) idx_j++;
+    for (size_t k = 0; k < nb; ++k) {  // KILO.cc:375-395
+        const double cur_point_time = btime[k];
+        const size_t idx_i = bstart[k], idx_j = bstart[k + 1];
         while (qi < n_imu && imus[qi].stamp < cur_point_time) {
             if ((rc = enqueue_imu(h, &imus[qi]))) return rc;
             ++qi;
@@ -1399,31 +1376,135 @@ int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n,
         }
         // the next bucket's predict rides in this bucket's launch when nothing lies in between and both are large buckets
         double t_next = NAN;
-        if (idx_j < n) {
-            size_t idx_k = idx_j + 1;
-            while (idx_k < n && pts[idx_j].curvature == pts[idx_k].curvature) idx_k++;
-            const double tn = t_begin + pts[idx_j].curvature;
+        if (k + 1 < nb) {
+            const size_t idx_k = bstart[k + 2];
+            const double tn = btime[k + 1];
             const bool msg_between = (qi < n_imu && imus[qi].stamp < tn) || (qk < n_kin && kins[qk].time_stamp < tn);
             if (!msg_between && idx_k - idx_j > LK_SMALL_MAX && idx_j - idx_i > LK_SMALL_MAX) t_next = tn;
         }
-        rc = enqueue_bucket(h, d_pts + idx_i, (int)(idx_j - idx_i), cur_point_time,
-                            xyz_world_out ? h->d_world + 4 * idx_i : nullptr, true, t_next, &pre_predicted);
+        rc = enqueue_bucket(h, d_pts + idx_i, (int)(idx_j - idx_i), cur_point_time, d_world ? d_world + 4 * idx_i : nullptr, true, t_next, &pre_predicted);
         if (rc) return rc;
-        idx_i = idx_j;
     }
-    if ((rc = spec_join(h))) return rc;   // the last buckets' inserts (pipelined stream path) precede the read-backs below
-    std::vector<float> w;
-    if (xyz_world_out) {
-        w.resize(4 * n);
-        HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-    }
-    lk_pose pose;
-    rc = finish_scan(h, &pose);
+    return spec_join(h);   // the last buckets' inserts (pipelined stream path) precede the caller's read-backs
+}
+
+int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n, double t_begin, const lk_imu* imus,
+             size_t n_imu, const lk_kin_imu* kins, size_t n_kin, float* xyz_world_out, lk_pose* out) {
+    int rc = zero_scan_counters(h, 0, 1);
     if (rc) return rc;
+    std::vector<unsigned long long> bstart;
+    std::vector<double> btime;
+    size_t biggest = 0, smallest = n;
+    for (size_t i = 0; i < n;) {   // runs of equal curvature = buckets (KILO.cc:375-378)
+        size_t j = i + 1;
+        while (j < n && pts[i].curvature == pts[j].curvature) j++;
+        bstart.push_back(i);
+        btime.push_back(t_begin + pts[i].curvature);
+        biggest = std::max(biggest, j - i);
+        smallest = std::min(smallest, j - i);
+        i = j;
+    }
+    bstart.push_back(n);
+    float* const d_world = xyz_world_out ? h->d_world : nullptr;
+    lk_pose pose;
+    std::vector<float> w;
+    if (grid_takes(h, smallest, biggest) && n_imu == 0 && n_kin == 0) {   // every bucket takes the large-bucket kernels: one grid-resident launch
+        if ((rc = run_scan_grid(h, d_pts, bstart, btime, biggest, d_world, &pose))) return rc;
+        if (xyz_world_out) {
+            w.resize(4 * n);
+            HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    } else if (resident_enabled(h) && biggest <= LK_RESIDENT_MAX) {
+        rc = run_scan_resident(h, d_pts, bstart, btime, n_kin ? (const void*)kins : (const void*)imus, n_kin ? n_kin : n_imu, n_kin ? 2 : (n_imu ? 1 : 0), d_world, &pose);
+        if (rc) return rc;
+        if (xyz_world_out) {
+            w.resize(4 * n);
+            HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    } else {
+        if ((rc = run_scan_launches(h, d_pts, bstart, btime, imus, n_imu, kins, n_kin, d_world))) return rc;
+        if (xyz_world_out) {
+            w.resize(4 * n);
+            HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+        }
+        if ((rc = finish_scan(h, &pose))) return rc;
+    }
     if (xyz_world_out)
         for (size_t i = 0; i < n; ++i)
             for (int c = 0; c < 3; ++c) xyz_world_out[3 * i + c] = w[4 * i + c];
     if (out) *out = pose;
+    return LK_OK;
+}
+
+// A recorded run LIVE on slot 0 from device-resident scans and messages: run_scan for every scan in turn, with the bucket tables of the whole run
+// built once on the device (run_tables) and the kernel of every scan chosen from their per-scan summaries - run_scan's own choice.  A resident
+// launch reads its scan's rows of the tables where they lie; only a scan that takes the per-bucket launches has its rows and messages read back.
+int lk_run_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
+                     const uint32_t* n_msg, const void* d_msgs, const lk_run_options* opt, float* d_world_out, lk_pose* out, size_t* n_done,
+                     uint32_t* n_slides) {
+    CHECK_H(h);
+    if (n_done) *n_done = 0;
+    if (n_slides) *n_slides = 0;
+    if (n_scans == 0) return fail(h, LK_ERR_INVALID, "n_scans must be at least 1");
+    if (!d_pts || !scan_off || !t_begin) return fail(h, LK_ERR_INVALID, "null argument");
+    if (msg_kind < 0 || msg_kind > 2 || (msg_kind && !n_msg)) return fail(h, LK_ERR_INVALID, "msg_kind must be 0 (none), 1 (lk_imu) or 2 (lk_kin_imu) with n_msg given");
+    const size_t S = n_scans;
+    size_t n_msg_total = 0;
+    for (size_t s = 0; s < S; ++s) {
+        if (scan_off[s + 1] <= scan_off[s]) return fail(h, LK_ERR_INVALID, "scan " + std::to_string(s) + " is empty");
+        if (scan_off[s + 1] - scan_off[s] > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "scan " + std::to_string(s) + " exceeds max_scan_points");
+        if (msg_kind) n_msg_total += n_msg[s];
+    }
+    if (n_msg_total && !d_msgs) return fail(h, LK_ERR_INVALID, "null message array");
+    if (n_msg_total >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 messages in one run");
+    // everything below counts points from the run's first one: nothing in front of it is ever addressed
+    const lk_point* const pts0 = d_pts + scan_off[0];
+    float* const world0 = d_world_out ? d_world_out + 4 * scan_off[0] : nullptr;
+    RunTables rt;
+    int rc = run_tables(h, pts0, S, scan_off, t_begin, msg_kind ? n_msg : nullptr, &rt);
+    if (rc) return rc;
+    if (rt.first_unsorted != 0xffffffffu)
+        return fail(h, LK_ERR_INVALID, "scan " + std::to_string(rt.first_unsorted) + " is not sorted by time (curvature must be non-decreasing within a scan, and finite)");
+    const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
+    std::vector<unsigned long long> bstart;
+    std::vector<double> btime;
+    std::vector<unsigned char> msgs;
+    for (size_t s = 0; s < S; ++s) {
+        const size_t rel = scan_off[s] - scan_off[0], nb = rt.sum[4 * s], biggest = rt.sum[4 * s + 1], smallest = rt.sum[4 * s + 2], m0 = rt.sum[4 * s + 3];
+        const size_t nm = msg_kind ? n_msg[s] : 0;
+        const int kind = nm ? msg_kind : 0;   // (run_scan's: a scan without messages runs the kernels without them)
+        if ((rc = zero_scan_counters(h, 0, 1))) return rc;
+        ScanDev dv;
+        dv.po = rt.d_ps + rt.bstart[s], dv.t = rt.d_tb + rt.bstart[s], dv.nb = rt.d_nbp + 2 * s;
+        dv.io = rt.d_mo ? rt.d_mo + s : rt.d_nbp + 2 * s, dv.im = d_msgs;   // the cursor starts at the scan's first message (lk_rag_scan_summary_kernel), io[1] is where they end
+        dv.sync = rt.d_sync + 4 * s, dv.rs = reinterpret_cast<LkResume*>(rt.d_resume) + s, dv.nbk = nb;
+        dv.ids = h->d_ids - rel;   // d_ids holds ONE scan: the kernels index it with the run's point numbers, which start at rel in this scan
+        lk_pose pose;
+        if (grid_takes(h, smallest, biggest) && nm == 0) {
+            rc = grid_rounds(h, pts0, dv, biggest, world0, &pose);
+        } else if (resident_enabled(h) && biggest <= LK_RESIDENT_MAX) {
+            rc = resident_rounds(h, pts0, dv, kind, world0, &pose);
+        } else {   // per-bucket launches: this scan's rows of the tables and its messages drive them from the host
+            bstart.resize(nb + 1), btime.resize(nb), msgs.resize(msg_bytes * nm);
+            HIPCHK(h, hipMemcpyAsync(bstart.data(), dv.po, 8 * (nb + 1), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(btime.data(), dv.t, 8 * nb, hipMemcpyDeviceToHost, h->stream));
+            if (nm) HIPCHK(h, hipMemcpyAsync(msgs.data(), static_cast<const unsigned char*>(d_msgs) + msg_bytes * m0, msg_bytes * nm, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            rc = run_scan_launches(h, pts0, bstart, btime, kind == 1 ? reinterpret_cast<const lk_imu*>(msgs.data()) : nullptr, kind == 1 ? nm : 0,
+                                   kind == 2 ? reinterpret_cast<const lk_kin_imu*>(msgs.data()) : nullptr, kind == 2 ? nm : 0, world0);
+            if (!rc) rc = finish_scan(h, &pose);
+        }
+        if (rc) return rc;
+        if (out) out[s] = pose;
+        if (n_done) *n_done = s + 1;
+        if (opt && opt->half_map_size != 0) {   // mapSliding behind the scan, as a caller's loop does it with lk_map_slide
+            int32_t slid = 0;
+            if ((rc = lk_map_slide(h, pose.pos, opt->sliding_thresh, opt->half_map_size, &slid, nullptr))) return rc;
+            if (slid && n_slides) *n_slides += 1;
+        }
+    }
     return LK_OK;
 }
 

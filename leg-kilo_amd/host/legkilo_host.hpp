@@ -367,6 +367,24 @@ class KiloPath {
         dev_->check(lk_batch_replay_scans_imu_dev(dev_->h(), d_pts, S, scan_off.data(), t_begin.data(), n_msg.data(), d_imus, out.data()));
         return out;
     }
+    // lk_run_scans_dev: a recorded run LIVE on the handle's map (KILO::process scan after scan, the map growing), from scans and message records
+    // that lie in HBM - msg_kind 0 none, 1 lk_imu, 2 lk_kin_imu; n_msg[s] records per scan at d_msgs.  slide: mapSliding after every scan
+    // (lk_run_options), or null.  d_world_out: one 16-byte record per point of d_pts (cloud_down_world), or null.  Returns the poses of the scans
+    // that went through; an error of scan k throws with k of them in *done (when given).
+    std::vector<lk_pose> runScans(const lk_point* d_pts, const std::vector<uint64_t>& scan_off, const std::vector<double>& t_begin, int msg_kind,
+                                  const std::vector<uint32_t>& n_msg, const void* d_msgs, const lk_run_options* slide = nullptr, float* d_world_out = nullptr,
+                                  uint32_t* n_slides = nullptr, std::vector<lk_pose>* done = nullptr) {
+        const size_t S = t_begin.size();
+        if (scan_off.size() != S + 1 || (msg_kind && n_msg.size() != S)) throw std::runtime_error("runScans: table sizes differ");
+        std::vector<lk_pose> out(std::max<size_t>(S, 1));
+        size_t n_done = 0;
+        const int rc = lk_run_scans_dev(dev_->h(), d_pts, S, scan_off.data(), t_begin.data(), msg_kind, msg_kind ? n_msg.data() : nullptr, d_msgs, slide,
+                                        d_world_out, out.data(), &n_done, n_slides);
+        out.resize(n_done);
+        if (done) *done = out;
+        dev_->check(rc);
+        return out;
+    }
 
     // KILO.cc:108-233
     bool predictUpdatePoint(double current_time, size_t idx_i, size_t idx_j, const PointCloudType& cloud_down_body,

@@ -2,10 +2,15 @@
 """End to end on one MI355X, everything through the C-ABI: a synthetic recorded run of Velodyne PointCloud2 payloads is
 (1) run live - decode (lidar_processing.cc:25-108) -> voxel-grid filter + time sort (KILO.cc:356-370) -> bucket loop with IMU
     updates and map insert (KILO.cc:367-396), one scan after the other, trajectory written as a TUM file
-    (trajectory_saver.hpp:43-50);
+    (trajectory_saver.hpp:43-50); the bucket loop itself is then timed in its two forms on the same decoded scans from the same start:
+    the per-scan loop of lk_process_scan over host copies, and ONE lk_run_scans_dev call over scans and IMU records that lie in HBM
+    (ms per scan, median over --reps runs after one warm-up run, with the run-to-run spread; --json writes the figures);
 (2) replayed as ONE ragged batch against the final map, frozen: every scan re-localised from its live prior, with its own
     size / 2 ms buckets / start time / IMU messages (lk_batch_replay_ragged_imu_dev).
-Prints rates and the ATE of both trajectories against the synthetic ground truth.   Usage: replay_recorded_run.py [N_SCANS]"""
+Prints rates and the ATE of both trajectories against the synthetic ground truth.
+Usage: replay_recorded_run.py [N_SCANS] [--reps R] [--json PATH]"""
+import argparse
+import json
 import os
 import sys
 import tempfile
@@ -27,7 +32,12 @@ VELODYNE = np.dtype({"names": ["x", "y", "z", "intensity", "time", "ring"], "for
                      "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 22})
 LAYOUT = dict(point_step=22, off_x=0, off_y=4, off_z=8, off_time=16, lidar_type=1)
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+ap = argparse.ArgumentParser()
+ap.add_argument("n_scans", nargs="?", type=int, default=40)
+ap.add_argument("--reps", type=int, default=5, help="timed runs of each form of the live bucket loop (after one warm-up run)")
+ap.add_argument("--json", default="", help="write the two ms-per-scan figures here")
+args = ap.parse_args()
+N = args.n_scans
 sc = scenes.Scene()
 P, world, traj = sc.P, sc.world, sc.traj
 g = binding.LegKiloHip(sc.cfg(n_slots=max(N, 1)))
@@ -46,8 +56,19 @@ def message(k):
 x0 = scenes.init_filter(g, sc, t0)
 scenes.first_frame(g, sc, t0, x0)
 
+start = (g.map_export(), *g.get_state(), g.get_times(), g.get_last_slide_position())
+
+
+def restart():
+    """The handle as the first frame left it."""
+    g.map_import(start[0])
+    g.set_state(start[1], start[2])
+    g.set_times(*start[3])
+    g.set_last_slide_position(start[4])
+
+
 # ---- (1) live
-live_scans, live_tb, priors_x, priors_P, stamps, rots, poss = [], [], [], [], [], [], []
+live_scans, live_tb, priors_x, priors_P, stamps, rots, poss, live_poses = [], [], [], [], [], [], [], []
 msgs = [message(k) for k in range(1, N + 1)]          # the "bag": generated before the clock starts
 imu_q = [synth.imu_stream(traj, tb, tb + 0.1, seed=4200 + k) for k, (_, _, tb) in enumerate(msgs, start=1)]
 t_live = time.perf_counter()
@@ -58,11 +79,45 @@ for k in range(1, N + 1):
     x, Pm = g.get_state()
     priors_x.append(x.copy()), priors_P.append(Pm.copy()), live_scans.append(ds), live_tb.append(tb)
     pose, _ = g.process_scan(ds, tb, imus=imu_q[k - 1])
+    live_poses.append(pose)
     stamps.append(tb + float(ds["curvature"][-1])), rots.append(np.array(pose.rot).reshape(3, 3)), poss.append(np.array(pose.pos))
 t_live = time.perf_counter() - t_live
 gt = np.array([traj.pos(t) for t in stamps]).reshape(-1, 3)
 tmp = tempfile.mkdtemp()
 tum.write_tum(os.path.join(tmp, "live.txt"), stamps, rots, poss)
+
+# ---- (1b) the live bucket loop alone, per-scan loop against the one-call form: same scans, same start, same library
+all_pts = np.ascontiguousarray(np.concatenate(live_scans))
+scan_off = np.r_[0, np.cumsum([len(s) for s in live_scans])].astype(np.uint64)
+n_msg = np.array([len(m) for m in imu_q], dtype=np.uint32)
+all_imu = np.ascontiguousarray(np.concatenate(imu_q))
+d_pts, d_imu = g.device_malloc(all_pts.nbytes), g.device_malloc(all_imu.nbytes)
+g.h2d(d_pts, all_pts)
+g.h2d(d_imu, all_imu)
+
+
+def loop_form():
+    return [g.process_scan(ds, tb, imus=im)[0] for ds, tb, im in zip(live_scans, live_tb, imu_q)]
+
+
+def one_call_form():
+    return g.run_scans_dev(d_pts, scan_off, live_tb, 1, n_msg, d_imu)[0]
+
+
+ms = {}
+for name, form in (("loop", loop_form), ("one_call", one_call_form)):
+    runs = []
+    for r in range(args.reps + 1):   # run 0 warms up
+        restart()
+        t = time.perf_counter()
+        out = form()
+        runs.append((time.perf_counter() - t) / N * 1e3)
+    ms[name] = dict(median=float(np.median(runs[1:])), min=float(min(runs[1:])), max=float(max(runs[1:])), poses=out)
+g.device_free(d_pts), g.device_free(d_imu)
+same = all(bytes(a) == bytes(b) for a, b in zip(ms["loop"]["poses"], ms["one_call"]["poses"])) and \
+    all(bytes(a) == bytes(b) for a, b in zip(ms["loop"]["poses"], live_poses))
+for v in ms.values():
+    del v["poses"]
 
 # ---- (2) the same scans, with their IMU messages, as one ragged batch against the final map (frozen: no insert)
 t_b = time.perf_counter()
@@ -72,6 +127,15 @@ pb = np.array([np.array(p.pos) for p in poses])
 tum.write_tum(os.path.join(tmp, "batch.txt"), stamps, [np.array(p.rot).reshape(3, 3) for p in poses], pb)
 print(f"{N} scans, {np.mean([len(s) for s in live_scans]):.0f} points and {np.mean([p.n_buckets for p in poses]):.0f} buckets per scan after the voxel-grid filter")
 print(f"live   : {t_live / N * 1e3:7.2f} ms per scan ({N / t_live:7.1f} scans/s)   ATE vs ground truth {tum.ate(np.array(poss), gt) * 1e3:.2f} mm")
+for name, label in (("loop", "lk_process_scan per scan"), ("one_call", "one lk_run_scans_dev   ")):
+    v = ms[name]
+    print(f"bucket loop, {label}: {v['median']:7.3f} ms per scan (median of {args.reps} runs, {v['min']:.3f} .. {v['max']:.3f})")
+print(f"  poses of the two forms and of the live run bit-equal: {same}")
+if args.json:
+    with open(args.json, "w") as f:
+        json.dump(dict(tool="tools/replay_recorded_run.py", n_scans=N, reps=args.reps, points_per_scan=float(np.mean([len(s) for s in live_scans])),
+                       ms_per_scan=ms, poses_bit_equal=bool(same)), f, indent=1)
+        f.write("\n")
 print(f"batch  : {t_b / N * 1e3:7.2f} ms per scan ({N / t_b:7.1f} scans/s)   ATE vs ground truth {tum.ate(pb, gt) * 1e3:.2f} mm, "
       f"vs live {tum.ate(pb, np.array(poss)) * 1e3:.2f} mm")
 print("(only_imu_use mode: with 16 beams z is the weakly observed direction and most of the ATE is a slow z drift - the CPU oracle")

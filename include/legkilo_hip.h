@@ -416,7 +416,9 @@ int lk_batch_replay_async_dev(lk_handle* h, const lk_point* d_pts, uint32_t firs
  * copy-on-write overlay; the handle's map is not changed, and the overlays are discarded by the next replay.  Same argument meaning
  * as lk_batch_replay_dev (priors from lk_batch_set_priors(_dev); synchronous; out may be NULL).  Per slot the result equals
  * lk_process_scan_dev on a handle that holds a private copy of the map.  LK_ERR_CAPACITY when a scan's overlay outgrows its pools
- * (the message names the slot and the sizes in use). */
+ * (the message names the slot and the sizes in use); LK_ERR_INVALID when a point's voxel key lies outside +-2^20 (the packed keys of
+ * the private root tables); LK_ERR_STATE when the handle's map has no frozen-map grid (key box above 2^24 cells).  A refused replay,
+ * here and in the recorded-run form below, leaves the slots at the priors it was called with. */
 int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, size_t n_pts, double t_begin,
                                 const uint32_t* bucket_off, const double* bucket_dt, size_t n_buckets, lk_pose* out);
 /* The same for a RECORDED run's scans (config 1 / config 4 shape): every scan its own size, its own time buckets (runs of equal curvature,

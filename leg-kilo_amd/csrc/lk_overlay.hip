@@ -352,6 +352,8 @@ static int ov_attempt_end(lk_handle* h, int S, int attempt, const unsigned int* 
     }
     if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = n_pts_scan;
     if (out) LKCHK(fetch_poses(h, out, S));   // no wait without `out`: ov_read_status has synchronised
+    // a refused replay leaves the slots as the caller armed them, not at whatever the buckets before the error made of them
+    if (stt[0]) HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
     if (stt[0] & LK_E_KEY_RANGE) {
         char buf[200];
         snprintf(buf, sizeof(buf), "overlay replay: a point of slot %u lies in a voxel whose key is outside the +-2^20 range of the private root tables' packed keys (%.0f km from the origin at this voxel size)",

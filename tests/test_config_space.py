@@ -27,8 +27,9 @@ def rel_err(a, b):
     return float(np.abs(np.asarray(a) - np.asarray(b)).max() / (np.abs(np.asarray(b)).max() + 1e-300))
 
 
-def make_pair(name, oracle_lib, hip_lib, use_kin=False, **over):
-    sc = offconfig.scene(name, use_kin, **CAPS)
+def make_pair(name, oracle_lib, hip_lib, use_kin=False, scene=None, **over):
+    """scene: a ready scene (tests/placement.py) instead of the one offconfig builds from the configuration's name."""
+    sc = scene or offconfig.scene(name, use_kin, **CAPS)
     return sc, oracle_lib.Oracle(sc.cfg(**over), imu_mode_only=not use_kin), hip_lib.LegKiloHip(sc.cfg(**over))
 
 
@@ -466,11 +467,15 @@ def test_update_points_on_the_corner_sites_deep4(oracle_lib, hip_lib):
 @pytest.mark.parametrize("use_kin", [False, True])
 @pytest.mark.parametrize("name", offconfig.CLOSED_LOOP)
 def test_sequence_scan_resident_and_launches(oracle_lib, hip_lib, name, use_kin):
+    sequence_scan_resident_and_launches(oracle_lib, hip_lib, name, use_kin)
+
+
+def sequence_scan_resident_and_launches(oracle_lib, hip_lib, name, use_kin, scene=None, n_scans=6):
     """test_sequence_imu_mode / test_sequence_kin_mode / test_scan_resident_kernel_equals_per_bucket_launches: first frame + 6
     recorded-shape scans through the scan-resident kernel and through the per-bucket launches (lk_stream_resident(0)): the two
     bit-identical (state, covariance, re-projected cloud, map), both equal to the oracle - bucket / update / match counts exact on
     every scan, state to 1e-7 (IMU-only) or rtol 1e-7 / atol 1e-8 (leg fusion) as in those tests, map as in test_sequence_imu_mode."""
-    sc, o, g = make_pair(name, oracle_lib, hip_lib, use_kin=use_kin)
+    sc, o, g = make_pair(name, oracle_lib, hip_lib, use_kin=use_kin, scene=scene)
     g_pb = hip_lib.LegKiloHip(sc.cfg())
     g_pb.stream_resident(False)
     t0 = 2.0
@@ -478,7 +483,7 @@ def test_sequence_scan_resident_and_launches(oracle_lib, hip_lib, name, use_kin)
         x0 = scenes.init_filter(obj, sc, t0)
         scenes.first_frame(obj, sc, t0, x0)
     zin = offconfig.ZeroZ()
-    for k in range(6):
+    for k in range(n_scans):
         tb = t0 + 0.1 * k
         ds = zin(sc, tb, k)
         kw = dict(kins=synth.kin_stream(sc.traj, tb, tb + 0.1, sc.P, seed=3003 + k)) if use_kin else \
@@ -498,19 +503,23 @@ def test_sequence_scan_resident_and_launches(oracle_lib, hip_lib, name, use_kin)
         assert np.array_equal(wg, wp), k
     scenes.maps_identical(g.map_export(), g_pb.map_export())
     scenes.compare_maps(o.map_export(), g.map_export(), rtol=1e-5, ptol=1e-6)
-    n_scans, n_relaunch = g.stream_resident_stats()
-    print(f"{name} use_kin={use_kin}: scan-resident kernel ran {n_scans} scans, {n_relaunch} launches beyond one per scan; z == 0 path points {zin.n_zero}")
-    assert n_scans == 6 and g_pb.stream_resident_stats()[0] == 0, (n_scans, g_pb.stream_resident_stats())
+    n_res, n_relaunch = g.stream_resident_stats()
+    print(f"{name} use_kin={use_kin}: scan-resident kernel ran {n_res} scans, {n_relaunch} launches beyond one per scan; z == 0 path points {zin.n_zero}")
+    assert n_res == n_scans and g_pb.stream_resident_stats()[0] == 0, (n_res, g_pb.stream_resident_stats())
     close(g, g_pb, o)
 
 
 @pytest.mark.parametrize("nb", [5, 51])
 @pytest.mark.parametrize("name", ["tilt", "all"])
 def test_scan_grid_kernel_and_launches(oracle_lib, hip_lib, name, nb):
+    scan_grid_kernel_and_launches(oracle_lib, hip_lib, name, nb)
+
+
+def scan_grid_kernel_and_launches(oracle_lib, hip_lib, name, nb, scene=None):
     """test_scan_grid_kernel_equals_per_bucket_launches, reduced (two scans of 30 000 points in 5 buckets / 70 000 in 51 two-ms bins:
     the kernel takes scans whose smallest bucket holds more than 512 points): the grid-resident kernel against the per-bucket
     launches bit for bit, both against the oracle (counts exact, state 1e-6, same voxels)."""
-    sc, o, g = make_pair(name, oracle_lib, hip_lib)
+    sc, o, g = make_pair(name, oracle_lib, hip_lib, scene=scene)
     g_seq = hip_lib.LegKiloHip(sc.cfg())
     g.stream_grid(2)
     g_seq.stream_grid(0)
@@ -740,10 +749,14 @@ def overlay_replay_and_check(o, g, tag, blob, scans, xs, Ps, reserve, least_effe
 
 @pytest.mark.parametrize("name", ["tilt", "vs04", "layers3", "all"])
 def test_batch_replay_overlay_scattered(oracle_lib, hip_lib, name):
+    batch_replay_overlay_scattered(oracle_lib, hip_lib, name)
+
+
+def batch_replay_overlay_scattered(oracle_lib, hip_lib, name, scene=None):
     """Case `scattered` of test_batch_replay_overlay at its own size (4 slots x 30 000 points): the buckets are a random partition of the
     scan on a young map, so every bucket's insert refits / creates planes the next bucket matches."""
     S, n_pts, nb = 4, 30000, 5
-    sc, o, g = make_pair(name, oracle_lib, hip_lib, n_slots=S)
+    sc, o, g = make_pair(name, oracle_lib, hip_lib, scene=scene, n_slots=S)
     t0 = 21.0
     x0 = scenes.init_filter(o, sc, t0)
     scenes.first_frame(o, sc, t0, x0, dense=20000)
@@ -788,11 +801,15 @@ def test_batch_replay_overlay_corner_sites_deep4(oracle_lib, hip_lib):
 
 @pytest.mark.parametrize("name", ["tilt", "vs04", "layers3", "all"])
 def test_batch_replay_overlay_ragged_scan_resident_imu(oracle_lib, hip_lib, monkeypatch, name):
+    batch_replay_overlay_ragged_scan_resident_imu(oracle_lib, hip_lib, monkeypatch, name)
+
+
+def batch_replay_overlay_ragged_scan_resident_imu(oracle_lib, hip_lib, monkeypatch, name, scene=None):
     """Mode `imu` of test_batch_replay_overlay_ragged_scan_resident: lk_batch_replay_overlay_ragged_dev in its scan-resident form and
     launch by launch (LEGKILO_RAG_RESIDENT=0) on a young map - the same bits, and per slot the oracle's KILO::process on a private copy
     of the map: counts exact, state 1e-6, private voxels equal.  Shapes: config-1 scans (one with volumetric clutter), 40 buckets of
     ~150 points, a one-point scan."""
-    sc = offconfig.scene(name, **CAPS)
+    sc = scene or offconfig.scene(name, **CAPS)
     o = oracle_lib.Oracle(sc.cfg(), imu_mode_only=True)
     t0 = 2.0
     x0 = scenes.init_filter(o, sc, t0)

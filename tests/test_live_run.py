@@ -29,9 +29,10 @@ def _scene(kind):
 
 
 @functools.lru_cache(maxsize=None)
-def _config1_run(kind):
-    """4 config-1 scans (hundreds of small buckets each) with their messages: generated once, shared, never modified."""
-    sc = _scene(kind)
+def _config1_run(kind, sc=None):
+    """4 config-1 scans (hundreds of small buckets each) with their messages: generated once, shared, never modified.
+    sc: a ready scene (tests/placement.py) instead of _scene(kind)."""
+    sc = sc or _scene(kind)
     scans, tbs, msgs = [], [], []
     for k in range(4):
         tb = T0 + 0.1 * k
@@ -256,8 +257,12 @@ def test_edge_sizes_and_subrange_with_guard_bands(hip_lib):
 # ------------------------------------------------------------------ 5. sliding
 @pytest.mark.gpu
 def test_run_with_map_sliding(hip_lib):
-    sc = _scene(1)
-    scans, tbs, msgs = _config1_run(1)
+    run_with_map_sliding(hip_lib)
+
+
+def run_with_map_sliding(hip_lib, sc=None):
+    scans, tbs, msgs = _config1_run(1) if sc is None else _config1_run(1, sc)
+    sc = sc or _scene(1)
     slide = (0.05, 12)   # metres moved since the last slide; half box size in voxels: far voxels of the first frame are dropped
     g_loop, g_run = hip_lib.LegKiloHip(sc.cfg()), hip_lib.LegKiloHip(sc.cfg())
     for g in (g_loop, g_run):

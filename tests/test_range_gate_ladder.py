@@ -1,17 +1,21 @@
 """The range gate of the frozen-map grid (records carry lk_range_bound(radius), two float compares) against the gate of the pool records
 (sqrtf, LEGKILO_GRID=0) on points laid ACROSS the gate: for eight planes of an oracle map, 512 points in the plane whose distance from the
 plane's centre steps by 8e-8 (relative) through 3 * radius * (1 -+ 2e-5) - float spacing of the gated quantity on both sides of its
-threshold.  Both paths must accept exactly the points the oracle accepts, and leave the same bits in the filter."""
+threshold.  Both paths must accept exactly the points the oracle accepts, and leave the same bits in the filter.
+
+`origin` is the room as legkilo_amd.synth builds it; `negz` and `far` move room and trajectory (tests/placement.py): the gate's
+(float)(p - c) is formed from coordinates of 10 m and of 3 km, where a kernel that subtracted two floats would be wrong by metres."""
 import numpy as np
 import pytest
 
+import placement
 import scenes
 from legkilo_amd import abi, synth
 
 pytestmark = pytest.mark.gpu
 
 CAPS = dict(max_roots=1 << 16, max_nodes=1 << 17, max_point_blocks=1 << 16, max_scan_points=1 << 17)
-N_PLANES, PER_PLANE = 8, 512
+N_PLANES, PER_PLANE = 8, 512     # four root planes + four planes of the grid's flattened lists: the oracle splits eight ladders at every placement
 STEP, HALF = 8e-8, PER_PLANE // 2   # 256 * 8e-8 = 2.05e-5 on either side
 
 
@@ -57,14 +61,21 @@ def plane_candidates(blob, vs):
     return out
 
 
-def test_range_gate_ladder_grid_equals_pool_records(oracle_lib, hip_lib, monkeypatch):
-    sc = scenes.Scene(**CAPS)
+def ladder_case(oracle_lib, place):
+    """The oracle's side: scene, map blob, prior, the scan of N_PLANES ladders, its bucket table and the oracle's replay of it ->
+    (sc, blob, x0, P0, scan, off, dt, valid [N_PLANES, PER_PLANE], oracle pose)."""
+    sc = scenes.Scene(**CAPS) if place == "origin" else placement.placed_scene(place, **CAPS)
+    D = np.array(placement.PLACEMENTS[place])
     o = oracle_lib.Oracle(sc.cfg(), imu_mode_only=True)
     t0 = 1.0
     scenes.mature_oracle_map(o, sc, t0, n_scans=4)
     # clutter (corner clusters of 0.25 m cells): cut voxels, so that some ladders run through the grid's flattened lists
     centre = sc.traj.pos(t0 + 1.3)
-    clutter = scenes.corner_clutter(np.random.default_rng(77), n_cells=40, per_cell=80, origin=(centre[0] + 2.0, centre[1] - 1.0, 3.0))
+    # (moved with the room by D snapped to whole voxels: the clutter cuts the same voxels, relative to the grid, at every placement)
+    vs = float(sc.P["voxel_size"])
+    snap = np.round(D / vs) * vs - D
+    clutter = scenes.corner_clutter(np.random.default_rng(77), n_cells=40, per_cell=80,
+                                    origin=(centre[0] + 2.0 + snap[0], centre[1] - 1.0 + snap[1], 3.0 + D[2] + snap[2]))
     o.map_update(clutter, np.tile((1e-4 * np.eye(3)).reshape(1, 9), (len(clutter), 1)))
     blob = o.map_export()
     o.set_map_insert(False)
@@ -98,7 +109,14 @@ def test_range_gate_ladder_grid_equals_pool_records(oracle_lib, hip_lib, monkeyp
     o.set_times(0.0, 0.0)
     po, _ = o.process_scan(scan, 0.0)
     assert po.n_effect == int(valid.sum())
-    print("accepted per plane:", valid.sum(1).tolist(), "of", PER_PLANE)
+    print(place, "accepted per plane:", valid.sum(1).tolist(), "of", PER_PLANE)
+    o.close()
+    return sc, blob, x0, P0, scan, off, dt, valid, po
+
+
+@pytest.mark.parametrize("place", ["origin", "negz", "far"])
+def test_range_gate_ladder_grid_equals_pool_records(oracle_lib, hip_lib, monkeypatch, place):
+    sc, blob, x0, P0, scan, off, dt, valid, po = ladder_case(oracle_lib, place)
     res = {}
     for name, env in (("grid", {}), ("pool", {"LEGKILO_GRID": "0"})):
         monkeypatch.delenv("LEGKILO_GRID", raising=False)
@@ -120,4 +138,3 @@ def test_range_gate_ladder_grid_equals_pool_records(oracle_lib, hip_lib, monkeyp
     assert res["grid"][0] == res["pool"][0] == po.n_effect
     assert res["grid"][1] == res["pool"][1] == po.n_updates
     assert np.array_equal(res["grid"][2], res["pool"][2]) and np.array_equal(res["grid"][3], res["pool"][3])
-    o.close()

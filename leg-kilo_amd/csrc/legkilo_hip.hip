@@ -685,7 +685,7 @@ int lk_map_build(lk_handle* h, const float* xyz_world, const float* xyz_body, si
 // BuildVoxelMap from the two clouds where they lie, then acc_norm_ and the two time stamps.
 static int first_frame_check(lk_handle* h, const void* raw, size_t n, int msg_kind, const void* msgs, size_t n_msg) {
     if (n == 0 || n_msg == 0) return fail(h, LK_ERR_INVALID, "Data packet is not ready: the first frame needs a cloud and at least one message (KILO.cc:326-329)");
-    if (msg_kind != 1 && msg_kind != 2) return fail(h, LK_ERR_INVALID, "msg_kind must be 1 (lk_imu) or 2 (lk_kin_imu)");
+    if (msg_kind != MSG_IMU && msg_kind != MSG_KIN) return fail(h, LK_ERR_INVALID, "msg_kind must be 1 (lk_imu) or 2 (lk_kin_imu)");
     if (!raw || !msgs) return fail(h, LK_ERR_INVALID, "null argument");
     if (n_msg >= ((size_t)1 << 31)) return fail(h, LK_ERR_INVALID, "more than 2^31 messages");
     return map_build_check(h, n);
@@ -703,8 +703,8 @@ static int first_frame_dev(lk_handle* h, const lk_point* d_raw, size_t n, double
     LKCHK(reserve(h, h->ff, bytes));
     carve(h->ff.p);
     LKCHK(init_process_cov_q(h));
-    const unsigned int stride = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
-    const unsigned int acc_off = msg_kind == 2 ? offsetof(lk_kin_imu, acc) : offsetof(lk_imu, acc);
+    const unsigned int stride = (unsigned int)msg_record_bytes(msg_kind);
+    const unsigned int acc_off = msg_kind == MSG_KIN ? offsetof(lk_kin_imu, acc) : offsetof(lk_imu, acc);
     static_assert(offsetof(lk_imu, gyr) == offsetof(lk_imu, acc) + 24 && offsetof(lk_kin_imu, gyr) == offsetof(lk_kin_imu, acc) + 24, "gyr lies behind acc");
     LAUNCH(h, "ff_init", hipLaunchKernelGGL(lk_ff_init_kernel, dim3(1), dim3(256), 0, h->stream, h->d_filters, static_cast<const unsigned char*>(d_msgs),
                                             (unsigned int)n_msg, stride, acc_off, h->cfg.gravity, end_time, d_norm));
@@ -725,7 +725,7 @@ int lk_first_frame_dev(lk_handle* h, const lk_point* d_raw, size_t n, double end
 int lk_first_frame(lk_handle* h, const lk_point* raw, size_t n, double end_time, int msg_kind, const void* msgs, size_t n_msg) {
     CHECK_H(h);
     LKCHK(first_frame_check(h, raw, n, msg_kind, msgs, n_msg));
-    const size_t msg_bytes = n_msg * (msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu));
+    const size_t msg_bytes = n_msg * msg_record_bytes(msg_kind);
     lk_point* d_raw = nullptr;
     unsigned char* d_msgs = nullptr;
     DevTemps tmp;
@@ -1924,16 +1924,21 @@ int lk_batch_residuals_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, 
     return LK_OK;
 }
 
-// What an LkRagged takes from the handle, whatever built its tables: the message stride, the measurement noises, the gravity scale, Q's shape.
-static void rag_from_handle(const lk_handle* h, size_t msg_bytes, LkRagged* rg) {
-    rg->msg_stride = (int)(msg_bytes / sizeof(double));
-    rg->kin_noise = h->cfg.kin_meas_noise;
-    rg->q_diag = h->q_diag ? 1 : 0;
-    rg->acc_scale = h->cfg.gravity / h->acc_norm;
-    imu_noise(h->cfg, rg->Rn);
+#ifdef LK_DEBUG_PHASES
+// the one-wave-per-scan kernels' phase clocks (lk_sw_dbg), printed and reset
+static void dump_scan_wave_phases(hipStream_t st) {
+    unsigned long long hb[16];
+    hipStreamSynchronize(st);
+    hipMemcpyFromSymbol(hb, HIP_SYMBOL(lk_sw_dbg), sizeof(hb));
+    const char* names[6] = {"head", "predict", "bc", "residual", "update", "tail"};
+    fprintf(stderr, "[scan-wave phases] %llu buckets:", hb[15]);
+    for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.2f us;", names[k], (double)hb[k] / (double)hb[15] * 0.01);
+    fprintf(stderr, "\n");
+    memset(hb, 0, sizeof(hb));
+    hipMemcpyToSymbol(HIP_SYMBOL(lk_sw_dbg), hb, sizeof(hb));
 }
-
-// The launches of a ragged batch once its tables (padded or CSR, LkRagged) are in HBM.  msg_kind: 0 none, 1 lk_imu, 2 lk_kin_imu.
+#endif
+// The launches of a ragged batch once its tables (padded or CSR, LkRagged) are in HBM.  msg_kind: a MsgKind.
 // max_n: largest bucket of every bucket index (null: `biggest` for all of them).
 static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const LkRagged& rg, const double* d_tbegin, int biggest, size_t ldb,
                          const int* max_n, int msg_kind, lk_pose* out) {
@@ -1947,24 +1952,14 @@ static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const Lk
     hipLaunchKernelGGL(lk_set_times_ragged_kernel, dim3(((int)S + 63) / 64), dim3(64), 0, st, fl, (int)S, d_tbegin);
     if (biggest <= LK_SCAN_WAVE_MAX && (msg_kind || !getenv("LEGKILO_RAGGED_LEVELS"))) {
         // small buckets only (a real scan's 2 ms bins): each scan's whole bucket chain as one wave, one launch
-        if (msg_kind == 2)
+        if (msg_kind == MSG_KIN)
             hipLaunchKernelGGL(lk_scan_wave_kin_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fmap, h->pr, fl, d_pts, rg, h->d_Q);
-        else if (msg_kind == 1)
+        else if (msg_kind == MSG_IMU)
             hipLaunchKernelGGL(lk_scan_wave_imu_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fmap, h->pr, fl, d_pts, rg, h->d_Q);
         else
             hipLaunchKernelGGL(lk_scan_wave_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fmap, h->pr, fl, d_pts, rg, h->d_Q);
 #ifdef LK_DEBUG_PHASES
-        {
-            unsigned long long hb[16];
-            hipStreamSynchronize(st);
-            hipMemcpyFromSymbol(hb, HIP_SYMBOL(lk_sw_dbg), sizeof(hb));
-            const char* names[6] = {"head", "predict", "bc", "residual", "update", "tail"};
-            fprintf(stderr, "[scan-wave phases] %llu buckets:", hb[15]);
-            for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.2f us;", names[k], (double)hb[k] / (double)hb[15] * 0.01);
-            fprintf(stderr, "\n");
-            memset(hb, 0, sizeof(hb));
-            hipMemcpyToSymbol(HIP_SYMBOL(lk_sw_dbg), hb, sizeof(hb));
-        }
+        dump_scan_wave_phases(st);
 #endif
         ldb = 0;
     } else {
@@ -1988,7 +1983,7 @@ static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const Lk
 // a ragged batch of equally shaped scans gives the same bits.  Synchronous; priors as for lk_batch_replay_dev.
 int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off,
                          const uint32_t* n_buckets, const uint32_t* bucket_off, const double* bucket_dt,
-                         const double* t_begin, const uint32_t* n_imu, const void* imus, size_t msg_bytes, lk_pose* out, bool with_insert) {
+                         const double* t_begin, const uint32_t* n_imu, const void* imus, int msg_kind, lk_pose* out, bool with_insert) {
     CHECK_H(h);
     if (n_scans == 0 || n_scans > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_scans must be in [1, n_slots]");
     if (!d_pts || !scan_off || !n_buckets || !bucket_off || !bucket_dt || !t_begin) return fail(h, LK_ERR_INVALID, "null argument");
@@ -2024,6 +2019,7 @@ int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uin
     if (n_imu)
         for (size_t s = 0; s < S; ++s) n_imu_total += n_imu[s];
     if (n_imu_total && !imus) return fail(h, LK_ERR_INVALID, "null message array");
+    const size_t msg_bytes = msg_record_bytes(msg_kind);
     struct Tables {   // staged in pinned host memory, uploaded in one copy
         unsigned long long* po;   // [S][ldb+1]
         double *t, *tb;           // [S][ldb], [S]
@@ -2078,22 +2074,20 @@ int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uin
     rg.ldb = (int)ldb;
     rg.imu_off = n_imu ? dv.io : nullptr;
     rg.imu = reinterpret_cast<const double*>(dv.im);
-    rag_from_handle(h, msg_bytes, &rg);
+    rag_from_handle(h, msg_kind, &rg);
     rg.bstart = nullptr;
     if (with_insert) {
         size_t max_scan_pts = 0;
         for (size_t s = 0; s < S; ++s) max_scan_pts = std::max(max_scan_pts, (size_t)(scan_off[s + 1] - scan_off[s]));
-        return overlay_ragged_launch(h, d_pts, S, rg, dv.tb, (int)biggest_bucket, ldb, max_n.data(), max_scan_pts,
-                                     n_imu ? (msg_bytes == sizeof(lk_kin_imu) ? 2 : 1) : 0, out);
+        return overlay_ragged_launch(h, d_pts, S, rg, dv.tb, (int)biggest_bucket, ldb, max_n.data(), max_scan_pts, msg_kind, out);
     }
-    return ragged_launch(h, d_pts, S, rg, dv.tb, (int)biggest_bucket, ldb, max_n.data(),
-                         n_imu ? (msg_bytes == sizeof(lk_kin_imu) ? 2 : 1) : 0, out);
+    return ragged_launch(h, d_pts, S, rg, dv.tb, (int)biggest_bucket, ldb, max_n.data(), msg_kind, out);
 }
 
 int lk_batch_replay_ragged_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off,
                                const uint32_t* n_buckets, const uint32_t* bucket_off, const double* bucket_dt,
                                const double* t_begin, lk_pose* out) {
-    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, nullptr, nullptr, sizeof(lk_imu), out);
+    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, nullptr, nullptr, MSG_NONE, out);
 }
 // The same with each scan's IMU messages (only_imu_use mode, KILO.cc:379-383): n_imu[s] messages of scan s, concatenated in
 // `imus`, time-sorted per scan; a message stamped before a bucket's time is applied before that bucket, the rest of the
@@ -2103,7 +2097,7 @@ int lk_batch_replay_ragged_imu_dev(lk_handle* h, const lk_point* d_pts, size_t n
                                    const double* t_begin, const uint32_t* n_imu, const lk_imu* imus, lk_pose* out) {
     CHECK_H(h);
     if (!n_imu) return fail(h, LK_ERR_INVALID, "null argument");
-    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, n_imu, imus, sizeof(lk_imu), out);
+    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, n_imu, imus, MSG_IMU, out);
 }
 // Leg-fusion mode (only_imu_use: false, the reference's default): n_kin[s] kinematic + IMU messages of scan s, concatenated in
 // `kins`, time-sorted per scan; a message stamped before a bucket's time is applied (predictUpdateKinImu, KILO.cc:260-314:
@@ -2114,7 +2108,7 @@ int lk_batch_replay_ragged_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n
                                    const double* t_begin, const uint32_t* n_kin, const lk_kin_imu* kins, lk_pose* out) {
     CHECK_H(h);
     if (!n_kin) return fail(h, LK_ERR_INVALID, "null argument");
-    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, n_kin, kins, sizeof(lk_kin_imu), out);
+    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, n_kin, kins, MSG_KIN, out);
 }
 
 // Recorded-run replay WITHOUT host-side bucket tables: the scans lie back to back in HBM (scan s = d_pts[scan_off[s] .. scan_off[s+1]),
@@ -2132,15 +2126,56 @@ int lk_batch_replay_scans_kin_dev(lk_handle* h, const lk_point* d_pts, size_t n_
                                   const uint32_t* n_msg, const lk_kin_imu* d_kins, lk_pose* out) {
     CHECK_H(h);
     if (!n_msg) return fail(h, LK_ERR_INVALID, "null argument");
-    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, 2, n_msg, d_kins, true, out);
+    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, MSG_KIN, n_msg, d_kins, true, out);
 }
 // ... and the IMU records (lk_decode_imu_dev + lk_imu_split_dev).
 int lk_batch_replay_scans_imu_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin,
                                   const uint32_t* n_msg, const lk_imu* d_imus, lk_pose* out) {
     CHECK_H(h);
     if (!n_msg) return fail(h, LK_ERR_INVALID, "null argument");
-    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, 1, n_msg, d_imus, true, out);
+    return replay_scans(h, d_pts, n_scans, scan_off, t_begin, MSG_IMU, n_msg, d_imus, true, out);
 }
+// The CSR bucket tables of scans that lie back to back in HBM, built on the device (lk_rag_flag / rocPRIM exclusive scan / lk_rag_scatter): what the
+// batch replay of a recorded run (replay_scans) and a live run (run_tables) share.  take() names the arrays once, in the caller's carve of
+// h->ragdev - first over a null base to count, then over the buffer -; build() fills them, and the caller's own kernel reads the status words next.
+struct BucketTables {
+    unsigned long long *so, *ps;   // [S + 1] scan offsets from the first scan's first point; [n + 1] first point of every bucket
+    double *t0, *tb;               // [S] start time of every scan; [n] time of every bucket
+    unsigned int *fl, *rk;         // [n] bucket-start flags, their ranks
+    unsigned int *bs, *mo;         // [S + 1] first bucket / first message of every scan
+    unsigned int* st;              // [8] status words (lk_pre_kernels.h)
+    std::vector<unsigned long long> h_so;   // what the uploads read: alive as long as the tables
+    std::vector<unsigned int> h_mo;
+    void take(LkCarve& c, size_t n, size_t S) {
+        so = c.take<unsigned long long>(S + 1), t0 = c.take<double>(S);
+        ps = c.take<unsigned long long>(n + 1), tb = c.take<double>(n);
+        fl = c.take<unsigned int>(n), rk = c.take<unsigned int>(n);
+        bs = c.take<unsigned int>(S + 1), mo = c.take<unsigned int>(S + 1);
+        st = c.take<unsigned int>(8);
+    }
+    // d_pts: the first scan's first point (scan_off counts from wherever the caller counts: only its differences matter); n_msg: null without messages
+    int build(lk_handle* h, const lk_point* d_pts, size_t n, size_t S, const uint64_t* scan_off, const double* t_begin, const uint32_t* n_msg) {
+        h_so.resize(S + 1);
+        for (size_t s = 0; s <= S; ++s) h_so[s] = scan_off[s] - scan_off[0];
+        HIPCHK(h, hipMemcpyAsync(so, h_so.data(), 8 * (S + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(t0, t_begin, 8 * S, hipMemcpyHostToDevice, h->stream));
+        if (n_msg) {
+            h_mo.assign(S + 1, 0);
+            for (size_t s = 0; s < S; ++s) h_mo[s + 1] = h_mo[s] + n_msg[s];
+            HIPCHK(h, hipMemcpyAsync(mo, h_mo.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(h, hipMemsetAsync(st, 0, 32, h->stream));
+        const unsigned int nblk = (unsigned int)((n + 255) / 256);
+        hipLaunchKernelGGL(lk_rag_flag_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, so, (int)S, fl, st);
+        size_t tmp_bytes = 0;
+        HIPCHK(h, lk_prim_exclusive_scan(nullptr, tmp_bytes, fl, rk, n, h->stream));
+        LKCHK(reserve(h, h->prim_tmp, tmp_bytes));
+        HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tmp_bytes, fl, rk, n, h->stream));
+        hipLaunchKernelGGL(lk_rag_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, so, (int)S, fl, rk, t0, ps, tb, bs, st);
+        return LK_OK;
+    }
+};
+
 // Body of the three entries: msgs is a host pointer, or a device pointer when msgs_on_device.
 int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
                  const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out) {
@@ -2153,53 +2188,31 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
         if (scan_off[s + 1] <= scan_off[s]) return fail(h, LK_ERR_INVALID, "empty scan");
     const size_t n = scan_off[S];
     if (n >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 points in one batch");
-    const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
+    const size_t msg_bytes = msg_record_bytes(msg_kind);
     size_t n_msg_total = 0;
     if (msg_kind)
         for (size_t s = 0; s < S; ++s) n_msg_total += n_msg[s];
     if (n_msg_total && !msgs) return fail(h, LK_ERR_INVALID, "null message array");
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    unsigned long long *d_so = nullptr, *d_ps = nullptr;
-    double *d_t0 = nullptr, *d_tb = nullptr;
+    BucketTables bt;
     unsigned char* d_ms = nullptr;
-    unsigned int *d_fl = nullptr, *d_rk = nullptr, *d_bs = nullptr, *d_mo = nullptr, *d_st = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base);
-        d_so = c.take<unsigned long long>(S + 1), d_t0 = c.take<double>(S);       // scan_off, t_begin
-        d_ps = c.take<unsigned long long>(n + 1), d_tb = c.take<double>(n);       // CSR tables: first point and time of every bucket
-        d_ms = c.take<unsigned char>(msg_bytes * n_msg_total);                    // the messages
-        d_fl = c.take<unsigned int>(n), d_rk = c.take<unsigned int>(n);           // bucket-start flags, their ranks
-        d_bs = c.take<unsigned int>(S + 1), d_mo = c.take<unsigned int>(S + 1);   // first bucket / first message of every scan
-        d_st = c.take<unsigned int>(4);                                           // stats
+        bt.take(c, n, S);
+        d_ms = c.take<unsigned char>(msg_bytes * n_msg_total);   // the messages
         return c.total();
     };
     const size_t bytes = carve(nullptr);
     LKCHK(reserve(h, h->ragdev, bytes, bytes / 4));
     carve(h->ragdev.p);
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "scan offsets are 64-bit");
-    HIPCHK(h, hipMemcpyAsync(d_so, scan_off, 8 * (S + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_t0, t_begin, 8 * S, hipMemcpyHostToDevice, h->stream));
-    std::vector<unsigned int> moff;
-    if (msg_kind) {
-        moff.resize(S + 1, 0);
-        for (size_t s = 0; s < S; ++s) moff[s + 1] = moff[s] + n_msg[s];
-        HIPCHK(h, hipMemcpyAsync(d_mo, moff.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
-        if (n_msg_total)
-            HIPCHK(h, hipMemcpyAsync(d_ms, msgs, msg_bytes * n_msg_total, msgs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHK(h, hipMemsetAsync(d_st, 0, 16, h->stream));
-    const unsigned int nblk = (unsigned int)((n + 255) / 256);
-    hipLaunchKernelGGL(lk_rag_flag_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_st);
-    size_t tmp_bytes = 0;
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, tmp_bytes, d_fl, d_rk, n, h->stream));
-    LKCHK(reserve(h, h->prim_tmp, tmp_bytes));
-    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tmp_bytes, d_fl, d_rk, n, h->stream));
-    hipLaunchKernelGGL(lk_rag_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_rk, d_t0,
-                       d_ps, d_tb, d_bs, d_st);
-    hipLaunchKernelGGL(lk_rag_stats_kernel, dim3(nblk), dim3(256), 0, h->stream, d_ps, d_bs, (int)S, d_st);
+    if (n_msg_total)
+        HIPCHK(h, hipMemcpyAsync(d_ms, msgs, msg_bytes * n_msg_total, msgs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    LKCHK(bt.build(h, d_pts, n, S, scan_off, t_begin, msg_kind ? n_msg : nullptr));
+    hipLaunchKernelGGL(lk_rag_stats_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, h->stream, bt.ps, bt.bs, (int)S, bt.st);
     HIPCHK(h, hipGetLastError());
     unsigned int st[4];
-    HIPCHK(h, hipMemcpyAsync(st, d_st, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st, bt.st, 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const unsigned int biggest = st[1], most = st[2];
     if (st[3]) return fail(h, LK_ERR_INVALID, "a scan is not sorted by time (curvature must be non-decreasing within a scan, and finite)");
@@ -2207,34 +2220,29 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     if (msg_kind && biggest > (unsigned int)LK_SCAN_WAVE_MAX)
         return fail(h, LK_ERR_INVALID, "IMU / kinematic messages between buckets are only replayed for scans whose buckets hold <= 512 points");
     LkRagged rg;
-    rg.pt_off = d_ps;
-    rg.t = d_tb;
+    rg.pt_off = bt.ps;
+    rg.t = bt.tb;
     rg.nb = nullptr;
     rg.ldb = (int)most;
-    rg.bstart = d_bs;
-    rg.imu_off = msg_kind ? d_mo : nullptr;
+    rg.bstart = bt.bs;
+    rg.imu_off = msg_kind ? bt.mo : nullptr;
     rg.imu = reinterpret_cast<const double*>(d_ms);
-    rag_from_handle(h, msg_bytes, &rg);
-    return ragged_launch(h, d_pts, S, rg, d_t0, (int)biggest, (size_t)most, nullptr, msg_kind, out);
+    rag_from_handle(h, msg_kind, &rg);
+    return ragged_launch(h, d_pts, S, rg, bt.t0, (int)biggest, (size_t)most, nullptr, msg_kind, out);
 }
 
-// The tables of a live run (RunTables): replay_scans' chain over the run's points - d_pts is the run's FIRST point, scan_off is counted from
-// wherever the caller counts and only its differences matter - followed by the per-scan summaries.  Nothing of the handle but scratch is touched.
+// The tables of a live run (RunTables): the same CSR tables over the run's points - d_pts is the run's FIRST point - followed by the per-scan
+// summaries.  Nothing of the handle but scratch is touched.
 int run_tables(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, const uint32_t* n_msg, RunTables* out) {
     const size_t S = n_scans, n = scan_off[S] - scan_off[0];
     if (n >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 points in one run");
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    unsigned long long *d_so = nullptr, *d_ps = nullptr;
-    double *d_t0 = nullptr, *d_tb = nullptr;
-    unsigned int *d_fl = nullptr, *d_rk = nullptr, *d_bs = nullptr, *d_mo = nullptr, *d_st = nullptr, *d_sum = nullptr, *d_nbp = nullptr, *d_sync = nullptr;
+    BucketTables bt;
+    unsigned int *d_sum = nullptr, *d_nbp = nullptr, *d_sync = nullptr;
     int* d_rs = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base);
-        d_so = c.take<unsigned long long>(S + 1), d_t0 = c.take<double>(S);       // scan_off, t_begin
-        d_ps = c.take<unsigned long long>(n + 1), d_tb = c.take<double>(n);       // CSR tables: first point and time of every bucket
-        d_fl = c.take<unsigned int>(n), d_rk = c.take<unsigned int>(n);           // bucket-start flags, their ranks
-        d_bs = c.take<unsigned int>(S + 1), d_mo = c.take<unsigned int>(S + 1);   // first bucket / first message of every scan
-        d_st = c.take<unsigned int>(8);                                           // stats
+        bt.take(c, n, S);
         d_sum = c.take<unsigned int>(4 * S), d_nbp = c.take<unsigned int>(2 * S); // per-scan summaries, { buckets, 0 } pairs
         d_sync = c.take<unsigned int>(4 * S), d_rs = c.take<int>(8 * S);          // per-scan barrier words, LkResume
         return c.total();
@@ -2242,37 +2250,19 @@ int run_tables(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64
     const size_t bytes = carve(nullptr);
     LKCHK(reserve(h, h->ragdev, bytes, bytes / 4));
     carve(h->ragdev.p);
-    std::vector<unsigned long long> so(S + 1);
-    for (size_t s = 0; s <= S; ++s) so[s] = scan_off[s] - scan_off[0];
-    HIPCHK(h, hipMemcpyAsync(d_so, so.data(), 8 * (S + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_t0, t_begin, 8 * S, hipMemcpyHostToDevice, h->stream));
-    std::vector<unsigned int> moff;
-    if (n_msg) {
-        moff.resize(S + 1, 0);
-        for (size_t s = 0; s < S; ++s) moff[s + 1] = moff[s] + n_msg[s];
-        HIPCHK(h, hipMemcpyAsync(d_mo, moff.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHK(h, hipMemsetAsync(d_st, 0, 32, h->stream));
     HIPCHK(h, hipMemsetAsync(d_sync, 0, 16 * S, h->stream));
-    const unsigned int nblk = (unsigned int)((n + 255) / 256);
-    hipLaunchKernelGGL(lk_rag_flag_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_st);
-    size_t tmp_bytes = 0;
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, tmp_bytes, d_fl, d_rk, n, h->stream));
-    LKCHK(reserve(h, h->prim_tmp, tmp_bytes));
-    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tmp_bytes, d_fl, d_rk, n, h->stream));
-    hipLaunchKernelGGL(lk_rag_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, d_pts, (unsigned long long)n, d_so, (int)S, d_fl, d_rk, d_t0,
-                       d_ps, d_tb, d_bs, d_st);
-    hipLaunchKernelGGL(lk_rag_scan_summary_kernel, dim3((unsigned int)((S + 3) / 4)), dim3(256), 0, h->stream, d_ps, d_bs, n_msg ? d_mo : (unsigned int*)nullptr,
-                       (int)S, d_st, d_sum, d_nbp, d_rs);
+    LKCHK(bt.build(h, d_pts, n, S, scan_off, t_begin, n_msg));
+    hipLaunchKernelGGL(lk_rag_scan_summary_kernel, dim3((unsigned int)((S + 3) / 4)), dim3(256), 0, h->stream, bt.ps, bt.bs, n_msg ? bt.mo : (unsigned int*)nullptr,
+                       (int)S, bt.st, d_sum, d_nbp, d_rs);
     HIPCHK(h, hipGetLastError());
     unsigned int st[8];
     out->bstart.resize(S + 1), out->sum.resize(4 * S);
-    HIPCHK(h, hipMemcpyAsync(st, d_st, 32, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out->bstart.data(), d_bs, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st, bt.st, 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out->bstart.data(), bt.bs, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(out->sum.data(), d_sum, 16 * S, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     out->first_unsorted = st[4];
-    out->d_ps = d_ps, out->d_tb = d_tb, out->d_nbp = d_nbp, out->d_mo = n_msg ? d_mo : nullptr, out->d_sync = d_sync, out->d_resume = d_rs;
+    out->d_ps = bt.ps, out->d_tb = bt.tb, out->d_nbp = d_nbp, out->d_mo = n_msg ? bt.mo : nullptr, out->d_sync = d_sync, out->d_resume = d_rs;
     return LK_OK;
 }
 

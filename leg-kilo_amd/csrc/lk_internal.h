@@ -1,7 +1,7 @@
 // lk_internal.h - what the translation units of liblegkilo_hip.so share: the handle, the error / launch / allocation helpers, and the kernel
 // headers.  The library is six units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
 // kernel but the overlay's and the stream path's own), lk_stream.hip (LK_TU_STREAM: one live scan after the other with the map insert - the per-bucket
-// launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries that run them), lk_overlay.hip (LK_TU_OVERLAY: batch replay
+// launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries, which all run a scan through run_one_scan: one choice of its kernel), lk_overlay.hip (LK_TU_OVERLAY: batch replay
 // WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_kin.hip (LK_TU_KIN: the message front ends - HighState decode + contact detector, lk_kin_kernels.h; sensor_msgs/Imu decode, lk_imu_kernels.h; the scan split of either - and their entries), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
 // (LK_KERNELS_ELSEWHERE) and launches it through the main unit's host stub.  The overlay header's own kernels are compiled in the overlay unit only.
 #pragma once
@@ -368,9 +368,21 @@ static inline void imu_noise(const lk_config& c, double* Rn) {   // diag of R of
     Rn[3] = Rn[4] = Rn[5] = c.imu_gyr_meas_noise;
 }
 
+// The message records between a scan's buckets, under the values of the public msg_kind arguments; the size of one record (MSG_NONE: tables
+// without messages are laid out with lk_imu's stride, which nothing reads).
+enum MsgKind { MSG_NONE = 0, MSG_IMU = 1, MSG_KIN = 2 };
+static inline size_t msg_record_bytes(int kind) { return kind == MSG_KIN ? sizeof(lk_kin_imu) : sizeof(lk_imu); }
+// What an LkRagged takes from the handle, whatever built its tables: the message stride, the measurement noises, the gravity scale, Q's shape.
+static inline void rag_from_handle(const lk_handle* h, int msg_kind, LkRagged* rg) {
+    rg->msg_stride = (int)(msg_record_bytes(msg_kind) / sizeof(double));
+    rg->kin_noise = h->cfg.kin_meas_noise;
+    rg->q_diag = h->q_diag ? 1 : 0;
+    rg->acc_scale = h->cfg.gravity / h->acc_norm;
+    imu_noise(h->cfg, rg->Rn);
+}
+
 // Tables of a live run (lk_run_scans_dev), built once per call on the device by run_tables() in h->ragdev: the CSR bucket tables of all its scans
-// (lk_rag_flag / rocPRIM scan / lk_rag_scatter, offsets counted from the run's first point) and, per scan, what a resident stream kernel wants
-// besides them.  The host gets the scans' first buckets and lk_rag_scan_summary_kernel's summaries: a few words per scan, read back once.
+// (BucketTables in the main unit, offsets counted from the run's first point) and, per scan, what a resident stream kernel wants besides them.  The host gets the scans' first buckets and lk_rag_scan_summary_kernel's summaries: a few words per scan, read back once.
 struct RunTables {
     const unsigned long long* d_ps = nullptr;   // first point of every bucket of the run (+ the end)
     const double* d_tb = nullptr;               // its time
@@ -394,7 +406,7 @@ int export_map_blob(lk_handle* h, const LkMap& m, unsigned int hash_cap, void* b
 int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
                  const uint32_t* n_msg, const void* msgs, bool msgs_on_device, lk_pose* out);   // lk_batch_replay_scans(_kin / _imu)_dev
 int ragged_replay(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets, const uint32_t* bucket_off,
-                  const double* bucket_dt, const double* t_begin, const uint32_t* n_imu, const void* imus, size_t msg_bytes, lk_pose* out, bool with_insert = false);
+                  const double* bucket_dt, const double* t_begin, const uint32_t* n_imu, const void* imus, int msg_kind, lk_pose* out, bool with_insert = false);
 int run_tables(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, const uint32_t* n_msg, struct RunTables* out);
 __global__ void lk_set_times_kernel(LkFilter* filters, int n, double t);
 __global__ void __launch_bounds__(LK_WAVE, 2) lk_rag_advance_kernel(LkFilter* filters, const double* __restrict__ Q, LkRagged rg, int b, int msg_kind);

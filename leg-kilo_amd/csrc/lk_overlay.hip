@@ -471,8 +471,7 @@ int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size
     CHECK_H(h);
     if (msg_kind < 0 || msg_kind > 2) return fail(h, LK_ERR_INVALID, "msg_kind must be 0 (no messages), 1 (lk_imu) or 2 (lk_kin_imu)");
     if (msg_kind && !n_msg) return fail(h, LK_ERR_INVALID, "null argument");
-    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, msg_kind ? n_msg : nullptr, msgs,
-                         msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu), out, true);
+    return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, msg_kind ? n_msg : nullptr, msgs, msg_kind, out, true);
 }
 }  // extern "C"
 // The ragged batch WITH insert, bucket INDEX after bucket index over all scans (one launch of every pass per index, grids sized by that

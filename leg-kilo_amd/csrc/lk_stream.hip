@@ -894,7 +894,7 @@ static int enqueue_bucket(lk_handle* h, const lk_point* d_pts, int n, double t, 
     if (fuse) {
         const auto tiny_kernel = xid ? lk_tiny_bucket_kernel<true> : lk_tiny_bucket_kernel<false>;
         LAUNCH(h, "small_bucket", hipLaunchKernelGGL(tiny_kernel, dim3(1), dim3(LK_WAVE), 0, h->stream, m, h->pr, h->d_filters, h->d_Q,
-                                                     h->q_diag ? 1 : 0, t, d_pts, n, d_world, (d_world || do_insert) ? (do_insert ? 2 : 1) : 0));
+                                                     h->q_diag ? 1 : 0, t, d_pts, n, d_world, do_insert ? 2 : (d_world ? 1 : 0)));
     } else if (n <= LK_SMALL_MAX) {
         const auto small_kernel = xid ? lk_small_bucket_kernel<true> : lk_small_bucket_kernel<false>;
         LAUNCH(h, "small_bucket", hipLaunchKernelGGL(small_kernel, dim3(1), dim3(LK_FB), 0, h->stream, m, h->pr, h->d_filters,
@@ -1078,9 +1078,9 @@ int lk_process_scan(lk_handle* h, const lk_point* pts, size_t n, double t_begin,
     return run_scan(h, pts, h->d_scan, n, t_begin, imus, n_imu, kins, n_kin, xyz_world_out, out);
 }
 
-// Tables of one scan for the resident stream kernels: LkRagged's arrays for a single scan, the grid-resident kernel's barrier words, where a
-// launch stopped.  One description, laid over the pinned staging copy and over the device copy (rag_reserve); both kernels' scans use it, so
-// a scan-resident launch also uploads the 16 B of barrier words it does not read.
+// Tables of one scan for the resident stream kernels, where the scan's bucket table was made on the host: LkRagged's arrays for a single scan, the
+// grid-resident kernel's barrier words, where a launch stopped.  One description, laid over the pinned staging copy and over the device copy
+// (rag_reserve); both kernels' scans use it, so a scan-resident launch also uploads the 16 B of barrier words it does not read.
 struct ScanTables {
     unsigned long long* po;   // [nb+1] first point of every bucket
     double* t;                // [nb] its time
@@ -1102,8 +1102,9 @@ static ScanTables scan_tables(void* base, size_t nb, size_t msg_bytes_total) {
     return r;
 }
 static_assert(sizeof(LkResume) == 32 && offsetof(LkResume, qi) == 8 && offsetof(LkResume, fb_bucket) == 16, "lk_rag_scan_summary_kernel writes LkResume as eight ints");
-// What a resident stream kernel's launches read of ONE scan, wherever its tables were made: the staged upload below (a host-side bucket search),
-// or the rows of scan s in the device-built tables of a run (RunTables, lk_run_scans_dev).
+// One scan as run_one_scan takes it, whichever entry it came through.  ScanDev: its tables in HBM, as the resident kernels' launches read them - the
+// staged upload below, or the rows of scan s in the device-built tables of a run (RunTables).  ScanHost: the same bucket table on the host, as the
+// per-bucket launches read it.  An entry has one of the two; run_one_scan makes the other only for a kernel that wants it.
 struct ScanDev {
     const unsigned long long* po;   // [nb+1] first point of every bucket, counted from the launches' d_pts
     const double* t;                // [nb] its time
@@ -1111,29 +1112,48 @@ struct ScanDev {
     const void* im;                 // message records
     unsigned int* sync;             // [4] zeroed
     LkResume* rs;                   // reset
-    size_t nbk;                     // nb, for the host
     int2* ids;                      // the speculative pass's root codes, indexed like d_pts
 };
+struct ScanHost {
+    std::vector<unsigned long long> bstart;   // [nb+1] first point of every bucket (+ the end), counted from the launches' d_pts and d_world
+    std::vector<double> btime;                // [nb] its absolute time
+    std::vector<unsigned char> msgs;          // the messages of a run's scan, read back
+};
+struct ScanSum {
+    size_t nb, biggest, smallest;   // buckets (all non-empty), points of the largest and of the smallest
+};
+struct ScanMsgs {   // the scan's lk_imu or lk_kin_imu records, time-sorted: on the host beside a ScanHost, in HBM beside a ScanDev
+    int kind;       // MsgKind; MSG_NONE when n == 0
+    size_t n;
+    const void* p;
+};
 // fills the staging copy and uploads it; returns the device copy's arrays
-static int upload_scan_tables(lk_handle* h, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime, const void* msgs, size_t n_msg,
-                       size_t msg_bytes, ScanTables* dev) {
-    const size_t nb = btime.size();
-    const size_t bytes = scan_tables(nullptr, nb, msg_bytes * n_msg).bytes;
+static int upload_scan_tables(lk_handle* h, const ScanHost& ht, const ScanMsgs& m, ScanDev* dev) {
+    const size_t nb = ht.btime.size(), msg_bytes = msg_record_bytes(m.kind) * m.n;
+    const size_t bytes = scan_tables(nullptr, nb, msg_bytes).bytes;
     LKCHK(rag_reserve(h, bytes));
-    const ScanTables st = scan_tables(h->rag_stage.p, nb, msg_bytes * n_msg);
-    memcpy(st.po, bstart.data(), 8 * (nb + 1));
-    memcpy(st.t, btime.data(), 8 * nb);
-    if (n_msg) memcpy(st.im, msgs, msg_bytes * n_msg);
+    const ScanTables st = scan_tables(h->rag_stage.p, nb, msg_bytes);
+    memcpy(st.po, ht.bstart.data(), 8 * (nb + 1));
+    memcpy(st.t, ht.btime.data(), 8 * nb);
+    if (m.n) memcpy(st.im, m.p, msg_bytes);
     st.nb[0] = (unsigned int)nb, st.nb[1] = 0u;
-    st.io[0] = 0u, st.io[1] = (unsigned int)n_msg;
+    st.io[0] = 0u, st.io[1] = (unsigned int)m.n;
     memset(st.sync, 0, 16);
     memset(st.rs, 0, sizeof(LkResume));
     st.rs->fb_bucket = -1;
     HIPCHK(h, hipMemcpyAsync(h->rag.p, h->rag_stage.p, bytes, hipMemcpyHostToDevice, h->stream));
-    *dev = scan_tables(h->rag.p, nb, msg_bytes * n_msg);
+    const ScanTables dv = scan_tables(h->rag.p, nb, msg_bytes);
+    *dev = ScanDev{dv.po, dv.t, dv.nb, dv.io, dv.im, dv.sync, dv.rs, h->d_ids};
     return LK_OK;
 }
-static ScanDev scan_dev(lk_handle* h, const ScanTables& dv, size_t nb) { return ScanDev{dv.po, dv.t, dv.nb, dv.io, dv.im, dv.sync, dv.rs, nb, h->d_ids}; }
+// the "batch of one scan" a resident stream kernel reads
+static LkRagged scan_ragged(const lk_handle* h, const ScanDev& dv, size_t nb, int msg_kind) {
+    LkRagged rg;
+    rg.pt_off = dv.po, rg.t = dv.t, rg.nb = dv.nb, rg.ldb = (int)nb, rg.bstart = nullptr;
+    rg.imu_off = dv.io, rg.imu = reinterpret_cast<const double*>(dv.im);
+    rag_from_handle(h, msg_kind, &rg);
+    return rg;
+}
 
 // bound of the resident kernels' device-side waits (LEGKILO_RESIDENT_TIMEOUT_MS, debug aid: raise it under a profiler); read once per process
 static unsigned int resident_timeout_ms() {
@@ -1147,37 +1167,70 @@ static int backup_filter(lk_handle* h) {
     h->fbackup_valid = true;
     return LK_OK;
 }
-// The bucket loop of KILO::process for a scan of small buckets as ONE launch (lk_scan_stream_kernel).  bstart[k] / btime[k]: first
-// point and absolute time of bucket k (nb buckets, bstart[nb] = n); the messages are the scan's lk_imu or lk_kin_imu records.
-// The scan's result comes back through finish_scan; a launch that stopped at fallback items is followed by lk_resident_fallback_kernel and
-// another launch from where it stopped, until the scan is through (LkResume).
-static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, int msg_kind, float* d_world, lk_pose* pose);
-static int run_scan_resident(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime,
-                             const void* msgs, size_t n_msg, int msg_kind, float* d_world, lk_pose* pose) {
-    ScanTables dv;
-    int rc = upload_scan_tables(h, bstart, btime, msgs, n_msg, msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu), &dv);
-    if (rc) return rc;
-    return resident_rounds(h, d_pts, scan_dev(h, dv, btime.size()), msg_kind, d_world, pose);
+#ifdef LK_DEBUG_RES
+// the resident kernels' clocks (lk_res_dbg, lk_core_dbg, lk_res_ts), printed and reset after a launch of nb buckets
+static void dump_resident_clocks(lk_handle* h, size_t nb) {
+    unsigned long long hb[32];
+    hipStreamSynchronize(h->stream);
+    hipMemcpyFromSymbol(hb, HIP_SYMBOL(lk_res_dbg), sizeof(hb));
+    const double nbk = (double)hb[31];
+    const char* fn[8] = {"predict", "tiles", "wait-decided", "suspects(+redo)", "update", "snapshot+post", "messages", "wait-done(b-2)"};
+    const char* in[8] = {"wait-post", "begin", "reproject", "stamp", "root", "apply", "fallback+done", "-"};
+    fprintf(stderr, "[resident] %.0f buckets; filter wave (us per bucket):", nbk);
+    for (int q = 0; q < 8; ++q) fprintf(stderr, " %s %.2f;", fn[q], (double)hb[q] / nbk * 0.01);
+    fprintf(stderr, "\n[resident] insert wave 1:");
+    for (int q = 0; q < 7; ++q) fprintf(stderr, " %s %.2f;", in[q], (double)hb[8 + q] / nbk * 0.01);
+    fprintf(stderr, " buckets with fallback items %llu\n", hb[15]);
+    {
+        unsigned long long cd[16];
+        hipMemcpyFromSymbol(cd, HIP_SYMBOL(lk_core_dbg), sizeof(cd));
+        const double np_ = (double)(cd[7] ? cd[7] : 1), nu_ = (double)(cd[15] ? cd[15] : 1);
+        fprintf(stderr, "[resident] predict core (%llu calls), us: rotations %.2f; rows of Fx P %.2f; columns %.2f; Q + state %.2f\n", cd[7],
+                cd[0] / np_ * 0.01, cd[1] / np_ * 0.01, cd[2] / np_ * 0.01, cd[3] / np_ * 0.01);
+        fprintf(stderr, "[resident] update core (%llu calls), us: columns %.2f; Gauss-Jordan %.2f; X + dx %.2f; P update %.2f; rotation(s) + state %.2f\n", cd[15],
+                cd[8] / nu_ * 0.01, cd[9] / nu_ * 0.01, cd[10] / nu_ * 0.01, cd[11] / nu_ * 0.01, cd[12] / nu_ * 0.01);
+        memset(cd, 0, sizeof(cd));
+        hipMemcpyToSymbol(HIP_SYMBOL(lk_core_dbg), cd, sizeof(cd));
+    }
+    {
+        static unsigned long long ts[6][1024];
+        hipMemcpyFromSymbol(ts, HIP_SYMBOL(lk_res_ts), sizeof(ts));
+        const int nbq = (int)std::min<size_t>(nb, 1024);
+        double a01 = 0, a12 = 0, a24 = 0, a34 = 0, a25 = 0, a00 = 0;
+        int c = 0;
+        for (int b = 2; b + 2 < nbq; ++b, ++c) {
+            a01 += (double)(long long)(ts[1][b] - ts[0][b]), a12 += (double)(long long)(ts[2][b] - ts[1][b]), a24 += (double)(long long)(ts[4][b] - ts[2][b]);
+            a34 += (double)(long long)(ts[4][b] - ts[3][b]), a25 += (double)(long long)(ts[5][b] - ts[2][b]), a00 += (double)(long long)(ts[0][b + 1] - ts[0][b]);
+        }
+        if (c) fprintf(stderr, "[resident] hand-offs (us, mean over %d buckets): post -> insert sees it %.2f; -> decided posted %.2f; -> filter sees it %.2f (filter had waited %.2f); decided -> done %.2f; post to post %.2f\n",
+                       c, a01 / c * 0.01, a12 / c * 0.01, a24 / c * 0.01, a34 / c * 0.01, a25 / c * 0.01, a00 / c * 0.01);
+        for (int b = 100; b < 104 && b + 1 < nbq; ++b)
+            fprintf(stderr, "[resident]   bucket %d: post 0, seen %+.2f, decided %+.2f, filter waits from %+.2f, sees %+.2f, done %+.2f, next post %+.2f\n", b,
+                    (double)(long long)(ts[1][b] - ts[0][b]) * 0.01, (double)(long long)(ts[2][b] - ts[0][b]) * 0.01, (double)(long long)(ts[3][b] - ts[0][b]) * 0.01,
+                    (double)(long long)(ts[4][b] - ts[0][b]) * 0.01, (double)(long long)(ts[5][b] - ts[0][b]) * 0.01, (double)(long long)(ts[0][b + 1] - ts[0][b]) * 0.01);
+    }
+    memset(hb, 0, sizeof(hb));
+    hipMemcpyToSymbol(HIP_SYMBOL(lk_res_dbg), hb, sizeof(hb));
 }
-// launch / resume until the scan is through
-static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, int msg_kind, float* d_world, lk_pose* pose) {
-    const size_t nb = dv.nbk;
-    const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
+static void dump_grid_clocks(size_t nb, int G) {
+    unsigned long long hb[32];
+    hipMemcpyFromSymbol(hb, HIP_SYMBOL(lk_res_dbg), sizeof(hb));
+    const char* nm[10] = {"residual tiles", "barrier", "update+snapshot+begin (wg 0)", "barrier", "predict (wg 0; others re-project)", "barrier", "root pass (wg 0's share)", "barrier",
+                          "emitted groups (wg 0's share)", "barrier"};
+    fprintf(stderr, "[grid] %zu buckets, G = %d; workgroup 0, us per bucket:", nb, G);
+    for (int q = 0; q < 10; ++q) fprintf(stderr, " %s %.2f;", nm[q], (double)hb[16 + q] / (double)nb * 0.01);
+    fprintf(stderr, "\n");
+    memset(hb, 0, sizeof(hb));
+    hipMemcpyToSymbol(HIP_SYMBOL(lk_res_dbg), hb, sizeof(hb));
+}
+#endif
+// The bucket loop of KILO::process for a scan of small buckets as ONE launch (lk_scan_stream_kernel) over the scan's tables in HBM: launch / resume
+// until the scan is through.  The scan's result comes back through finish_scan; a launch that stopped at fallback items is followed by
+// lk_resident_fallback_kernel and another launch from where it stopped (LkResume).
+static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, size_t nb, int msg_kind, float* d_world, lk_pose* pose) {
     int rc;
     LkResume* d_rs = dv.rs;
-    LkRagged rg;
-    rg.pt_off = dv.po;
-    rg.t = dv.t;
-    rg.nb = dv.nb;
-    rg.ldb = (int)nb;
-    rg.bstart = nullptr;
-    rg.imu_off = dv.io;
-    rg.imu = reinterpret_cast<const double*>(dv.im);
-    rg.msg_stride = (int)(msg_bytes / sizeof(double));
-    rg.kin_noise = h->cfg.kin_meas_noise;
-    rg.q_diag = h->q_diag ? 1 : 0;
-    rg.acc_scale = h->cfg.gravity / h->acc_norm;
-    imu_noise(h->cfg, rg.Rn);
+    const LkRagged rg = scan_ragged(h, dv, nb, msg_kind);
     h->grid_valid = false;   // the map changes
     const bool xid = h->pr.ext_identity && lk_xid_enabled();
     if (h->epoch + (unsigned int)nb + 16u < h->epoch || h->epoch >= 0xf0000000u) {   // stamps are plain unsigned numbers: start over long before they wrap
@@ -1190,61 +1243,19 @@ static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& d
     h->spec_base = h->epoch + 1u;
     const unsigned int timeout_ms = resident_timeout_ms();
     void (*k)(LkMap, LkParams, LkFilter*, const lk_point*, LkRagged, const double*, LkFilter*, float*, int2*, unsigned int, unsigned int, LkResume*) =
-        msg_kind == 2 ? (xid ? lk_scan_stream_kernel<2, true> : lk_scan_stream_kernel<2, false>)
-      : msg_kind == 1 ? (xid ? lk_scan_stream_kernel<1, true> : lk_scan_stream_kernel<1, false>)
-                      : (xid ? lk_scan_stream_kernel<0, true> : lk_scan_stream_kernel<0, false>);
+        msg_kind == MSG_KIN ? (xid ? lk_scan_stream_kernel<2, true> : lk_scan_stream_kernel<2, false>)
+      : msg_kind == MSG_IMU ? (xid ? lk_scan_stream_kernel<1, true> : lk_scan_stream_kernel<1, false>)
+                            : (xid ? lk_scan_stream_kernel<0, true> : lk_scan_stream_kernel<0, false>);
     // a launch given up keeps the filter in LDS and returns before its write-back - but a scan that is picked up again after fallback items
     // has written it once: every scan starts with a copy, which a LK_ERR_TIMEOUT in any of its launches puts back (check_map_errors)
     if ((rc = backup_filter(h))) return rc;
     h->resident_scans += 1;
     for (size_t round = 0;; ++round) {
         h->fbackup_valid = true;   // (finish_scan's error check ends the previous launch's claim on the copy; it is still the pre-scan state)
-    LAUNCH(h, "scan_stream", hipLaunchKernelGGL(k, dim3(1), dim3((1 + LK_INS_WAVES) * LK_WAVE), 0, h->stream, h->map, h->pr, h->d_filters, d_pts, rg, h->d_Q, h->d_snap, d_world,
-                                                dv.ids, epoch0, h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, d_rs));
+        LAUNCH(h, "scan_stream", hipLaunchKernelGGL(k, dim3(1), dim3((1 + LK_INS_WAVES) * LK_WAVE), 0, h->stream, h->map, h->pr, h->d_filters, d_pts, rg, h->d_Q, h->d_snap, d_world,
+                                                    dv.ids, epoch0, h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, d_rs));
 #ifdef LK_DEBUG_RES
-    {
-        unsigned long long hb[32];
-        hipStreamSynchronize(h->stream);
-        hipMemcpyFromSymbol(hb, HIP_SYMBOL(lk_res_dbg), sizeof(hb));
-        const double nbk = (double)hb[31];
-        const char* fn[8] = {"predict", "tiles", "wait-decided", "suspects(+redo)", "update", "snapshot+post", "messages", "wait-done(b-2)"};
-        const char* in[8] = {"wait-post", "begin", "reproject", "stamp", "root", "apply", "fallback+done", "-"};
-        fprintf(stderr, "[resident] %.0f buckets; filter wave (us per bucket):", nbk);
-        for (int q = 0; q < 8; ++q) fprintf(stderr, " %s %.2f;", fn[q], (double)hb[q] / nbk * 0.01);
-        fprintf(stderr, "\n[resident] insert wave 1:");
-        for (int q = 0; q < 7; ++q) fprintf(stderr, " %s %.2f;", in[q], (double)hb[8 + q] / nbk * 0.01);
-        fprintf(stderr, " buckets with fallback items %llu\n", hb[15]);
-        {
-            unsigned long long cd[16];
-            hipMemcpyFromSymbol(cd, HIP_SYMBOL(lk_core_dbg), sizeof(cd));
-            const double np_ = (double)(cd[7] ? cd[7] : 1), nu_ = (double)(cd[15] ? cd[15] : 1);
-            fprintf(stderr, "[resident] predict core (%llu calls), us: rotations %.2f; rows of Fx P %.2f; columns %.2f; Q + state %.2f\n", cd[7],
-                    cd[0] / np_ * 0.01, cd[1] / np_ * 0.01, cd[2] / np_ * 0.01, cd[3] / np_ * 0.01);
-            fprintf(stderr, "[resident] update core (%llu calls), us: columns %.2f; Gauss-Jordan %.2f; X + dx %.2f; P update %.2f; rotation(s) + state %.2f\n", cd[15],
-                    cd[8] / nu_ * 0.01, cd[9] / nu_ * 0.01, cd[10] / nu_ * 0.01, cd[11] / nu_ * 0.01, cd[12] / nu_ * 0.01);
-            memset(cd, 0, sizeof(cd));
-            hipMemcpyToSymbol(HIP_SYMBOL(lk_core_dbg), cd, sizeof(cd));
-        }
-        {
-            static unsigned long long ts[6][1024];
-            hipMemcpyFromSymbol(ts, HIP_SYMBOL(lk_res_ts), sizeof(ts));
-            const int nbq = (int)std::min<size_t>(nb, 1024);
-            double a01 = 0, a12 = 0, a24 = 0, a34 = 0, a25 = 0, a00 = 0;
-            int c = 0;
-            for (int b = 2; b + 2 < nbq; ++b, ++c) {
-                a01 += (double)(long long)(ts[1][b] - ts[0][b]), a12 += (double)(long long)(ts[2][b] - ts[1][b]), a24 += (double)(long long)(ts[4][b] - ts[2][b]);
-                a34 += (double)(long long)(ts[4][b] - ts[3][b]), a25 += (double)(long long)(ts[5][b] - ts[2][b]), a00 += (double)(long long)(ts[0][b + 1] - ts[0][b]);
-            }
-            if (c) fprintf(stderr, "[resident] hand-offs (us, mean over %d buckets): post -> insert sees it %.2f; -> decided posted %.2f; -> filter sees it %.2f (filter had waited %.2f); decided -> done %.2f; post to post %.2f\n",
-                           c, a01 / c * 0.01, a12 / c * 0.01, a24 / c * 0.01, a34 / c * 0.01, a25 / c * 0.01, a00 / c * 0.01);
-            for (int b = 100; b < 104 && b + 1 < nbq; ++b)
-                fprintf(stderr, "[resident]   bucket %d: post 0, seen %+.2f, decided %+.2f, filter waits from %+.2f, sees %+.2f, done %+.2f, next post %+.2f\n", b,
-                        (double)(long long)(ts[1][b] - ts[0][b]) * 0.01, (double)(long long)(ts[2][b] - ts[0][b]) * 0.01, (double)(long long)(ts[3][b] - ts[0][b]) * 0.01,
-                        (double)(long long)(ts[4][b] - ts[0][b]) * 0.01, (double)(long long)(ts[5][b] - ts[0][b]) * 0.01, (double)(long long)(ts[0][b + 1] - ts[0][b]) * 0.01);
-        }
-        memset(hb, 0, sizeof(hb));
-        hipMemcpyToSymbol(HIP_SYMBOL(lk_res_dbg), hb, sizeof(hb));
-    }
+        dump_resident_clocks(h, nb);
 #endif
         if ((rc = finish_scan(h, pose, d_rs))) return rc;
         const int* rsm = h->h_result->resume;   // { filter wave's next bucket, insert team's next bucket, bucket with fallback items pending }
@@ -1262,28 +1273,11 @@ static int resident_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& d
     }
     return LK_OK;
 }
-// The bucket loop of a scan of LARGE buckets as one grid-resident launch (lk_scan_grid_kernel); same table layout as run_scan_resident.
-static int grid_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, size_t biggest, float* d_world, lk_pose* pose);
-static int run_scan_grid(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime,
-                         size_t biggest, float* d_world, lk_pose* pose) {
-    ScanTables dv;
-    int rc = upload_scan_tables(h, bstart, btime, nullptr, 0, 0, &dv);
-    if (rc) return rc;
-    return grid_rounds(h, d_pts, scan_dev(h, dv, btime.size()), biggest, d_world, pose);
-}
-static int grid_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, size_t biggest, float* d_world, lk_pose* pose) {
-    const size_t nb = dv.nbk;
+// The bucket loop of a scan of LARGE buckets as one grid-resident launch (lk_scan_grid_kernel); same tables as resident_rounds.
+static int grid_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, size_t nb, size_t biggest, float* d_world, lk_pose* pose) {
     int rc;
     if ((rc = backup_filter(h))) return rc;
-    LkRagged rg;
-    memset(&rg, 0, sizeof(rg));
-    rg.pt_off = dv.po;
-    rg.t = dv.t;
-    rg.nb = dv.nb;
-    rg.ldb = (int)nb;
-    rg.bstart = nullptr;
-    rg.imu_off = dv.io;
-    rg.q_diag = h->q_diag ? 1 : 0;
+    const LkRagged rg = scan_ragged(h, dv, nb, MSG_NONE);   // (a scan with messages never comes here: the kernel reads none of the message fields)
     h->grid_valid = false;   // the map changes
     const bool xid = h->pr.ext_identity && lk_xid_enabled();
     const unsigned int timeout_ms = resident_timeout_ms();
@@ -1317,17 +1311,7 @@ static int grid_rounds(lk_handle* h, const lk_point* d_pts, const ScanDev& dv, s
                                                   h->d_partials, dv.sync, h->test_stall_ms ? (h->test_stall_ms | 0x80000000u) : timeout_ms, stride, b0, d_rs));
         if ((rc = finish_scan(h, pose, d_rs))) return rc;
 #ifdef LK_DEBUG_RES
-        {
-            unsigned long long hb[32];
-            hipMemcpyFromSymbol(hb, HIP_SYMBOL(lk_res_dbg), sizeof(hb));
-            const char* nm[10] = {"residual tiles", "barrier", "update+snapshot+begin (wg 0)", "barrier", "predict (wg 0; others re-project)", "barrier", "root pass (wg 0's share)", "barrier",
-                                  "emitted groups (wg 0's share)", "barrier"};
-            fprintf(stderr, "[grid] %zu buckets, G = %d; workgroup 0, us per bucket:", nb, G);
-            for (int q = 0; q < 10; ++q) fprintf(stderr, " %s %.2f;", nm[q], (double)hb[16 + q] / (double)nb * 0.01);
-            fprintf(stderr, "\n");
-            memset(hb, 0, sizeof(hb));
-            hipMemcpyToSymbol(HIP_SYMBOL(lk_res_dbg), hb, sizeof(hb));
-        }
+        dump_grid_clocks(nb, G);
 #endif
         const int* rsm = h->h_result->resume;   // { next bucket, next bucket, bucket with fallback items pending }
         if (rsm[2] < 0) {
@@ -1354,13 +1338,16 @@ static bool grid_takes(const lk_handle* h, size_t smallest, size_t biggest) {
     return grid_enabled(h) && smallest > (size_t)LK_SMALL_MAX && (h->gridscan_mode == 2 || biggest <= (size_t)LK_GRIDSCAN_AUTO_MAX);
 }
 
-// The per-bucket launches of a scan (KILO.cc:375-395) from its bucket table - bstart[k] / btime[k] as for run_scan_resident, bstart counted from
-// d_pts and d_world - with the scan's messages as host records between them.  Ends with the pipelined path's inserts joined; the caller finishes the scan.
-static int run_scan_launches(lk_handle* h, const lk_point* d_pts, const std::vector<unsigned long long>& bstart, const std::vector<double>& btime, const lk_imu* imus,
-                             size_t n_imu, const lk_kin_imu* kins, size_t n_kin, float* d_world) {
+// The per-bucket launches of a scan (KILO.cc:375-395) from its bucket table on the host, with the scan's messages as host records between them.
+// Ends with the pipelined path's inserts joined; the caller finishes the scan.
+static int run_scan_launches(lk_handle* h, const lk_point* d_pts, const ScanHost& ht, const ScanMsgs& m, float* d_world) {
     int rc;
     if (h->spec_enable && (rc = backup_filter(h))) return rc;
-    const size_t nb = btime.size();
+    const std::vector<unsigned long long>& bstart = ht.bstart;
+    const std::vector<double>& btime = ht.btime;
+    const lk_imu* const imus = m.kind == MSG_IMU ? static_cast<const lk_imu*>(m.p) : nullptr;
+    const lk_kin_imu* const kins = m.kind == MSG_KIN ? static_cast<const lk_kin_imu*>(m.p) : nullptr;
+    const size_t nb = btime.size(), n_imu = imus ? m.n : 0, n_kin = kins ? m.n : 0;
     size_t qi = 0, qk = 0;
     bool pre_predicted = false;
     for (size_t k = 0; k < nb; ++k) {  // KILO.cc:375-395
@@ -1388,59 +1375,67 @@ static int run_scan_launches(lk_handle* h, const lk_point* d_pts, const std::vec
     return spec_join(h);   // the last buckets' inserts (pipelined stream path) precede the caller's read-backs
 }
 
+// ONE scan on slot 0, for every entry of the live path: the choice of its kernel, and the run.  All buckets large and no messages: one grid-resident
+// launch; all buckets small: one scan-resident launch; else a launch sequence per bucket, driven from the host.  dev: the scan's tables in HBM, or
+// null - then `ht` holds them and a resident kernel's scan is staged from there (upload_scan_tables); with dev, `ht` is scratch that the
+// per-bucket launches' read-back of the scan's rows and messages fills.
+static int run_one_scan(lk_handle* h, const lk_point* d_pts, const ScanDev* dev, ScanHost& ht, const ScanSum& sum, ScanMsgs m, float* d_world, lk_pose* pose) {
+    const bool grid = grid_takes(h, sum.smallest, sum.biggest) && m.n == 0;   // every bucket takes the large-bucket kernels
+    if (grid || (resident_enabled(h) && sum.biggest <= LK_RESIDENT_MAX)) {
+        ScanDev staged;
+        if (!dev) {
+            LKCHK(upload_scan_tables(h, ht, m, &staged));
+            dev = &staged;
+        }
+        return grid ? grid_rounds(h, d_pts, *dev, sum.nb, sum.biggest, d_world, pose) : resident_rounds(h, d_pts, *dev, sum.nb, m.kind, d_world, pose);
+    }
+    if (dev) {
+        const size_t msg_bytes = msg_record_bytes(m.kind) * m.n;
+        ht.bstart.resize(sum.nb + 1), ht.btime.resize(sum.nb), ht.msgs.resize(msg_bytes);
+        HIPCHK(h, hipMemcpyAsync(ht.bstart.data(), dev->po, 8 * (sum.nb + 1), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ht.btime.data(), dev->t, 8 * sum.nb, hipMemcpyDeviceToHost, h->stream));
+        if (m.n) HIPCHK(h, hipMemcpyAsync(ht.msgs.data(), m.p, msg_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        m.p = ht.msgs.data();
+    }
+    LKCHK(run_scan_launches(h, d_pts, ht, m, d_world));
+    return finish_scan(h, pose);
+}
+
 int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n, double t_begin, const lk_imu* imus,
              size_t n_imu, const lk_kin_imu* kins, size_t n_kin, float* xyz_world_out, lk_pose* out) {
     int rc = zero_scan_counters(h, 0, 1);
     if (rc) return rc;
-    std::vector<unsigned long long> bstart;
-    std::vector<double> btime;
-    size_t biggest = 0, smallest = n;
+    ScanHost ht;
+    ScanSum sum{0, 0, n};
     for (size_t i = 0; i < n;) {   // runs of equal curvature = buckets (KILO.cc:375-378)
         size_t j = i + 1;
         while (j < n && pts[i].curvature == pts[j].curvature) j++;
-        bstart.push_back(i);
-        btime.push_back(t_begin + pts[i].curvature);
-        biggest = std::max(biggest, j - i);
-        smallest = std::min(smallest, j - i);
+        ht.bstart.push_back(i);
+        ht.btime.push_back(t_begin + pts[i].curvature);
+        sum.biggest = std::max(sum.biggest, j - i);
+        sum.smallest = std::min(sum.smallest, j - i);
         i = j;
     }
-    bstart.push_back(n);
-    float* const d_world = xyz_world_out ? h->d_world : nullptr;
+    ht.bstart.push_back(n);
+    sum.nb = ht.btime.size();
+    const ScanMsgs m = n_kin ? ScanMsgs{MSG_KIN, n_kin, kins} : n_imu ? ScanMsgs{MSG_IMU, n_imu, imus} : ScanMsgs{MSG_NONE, 0, nullptr};
     lk_pose pose;
-    std::vector<float> w;
-    if (grid_takes(h, smallest, biggest) && n_imu == 0 && n_kin == 0) {   // every bucket takes the large-bucket kernels: one grid-resident launch
-        if ((rc = run_scan_grid(h, d_pts, bstart, btime, biggest, d_world, &pose))) return rc;
-        if (xyz_world_out) {
-            w.resize(4 * n);
-            HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-        }
-    } else if (resident_enabled(h) && biggest <= LK_RESIDENT_MAX) {
-        rc = run_scan_resident(h, d_pts, bstart, btime, n_kin ? (const void*)kins : (const void*)imus, n_kin ? n_kin : n_imu, n_kin ? 2 : (n_imu ? 1 : 0), d_world, &pose);
-        if (rc) return rc;
-        if (xyz_world_out) {
-            w.resize(4 * n);
-            HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-        }
-    } else {
-        if ((rc = run_scan_launches(h, d_pts, bstart, btime, imus, n_imu, kins, n_kin, d_world))) return rc;
-        if (xyz_world_out) {
-            w.resize(4 * n);
-            HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-        }
-        if ((rc = finish_scan(h, &pose))) return rc;
-    }
-    if (xyz_world_out)
+    if ((rc = run_one_scan(h, d_pts, nullptr, ht, sum, m, xyz_world_out ? h->d_world : nullptr, &pose))) return rc;
+    if (xyz_world_out) {
+        std::vector<float> w(4 * n);
+        HIPCHK(h, hipMemcpyAsync(w.data(), h->d_world, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
         for (size_t i = 0; i < n; ++i)
             for (int c = 0; c < 3; ++c) xyz_world_out[3 * i + c] = w[4 * i + c];
+    }
     if (out) *out = pose;
     return LK_OK;
 }
 
-// A recorded run LIVE on slot 0 from device-resident scans and messages: run_scan for every scan in turn, with the bucket tables of the whole run
-// built once on the device (run_tables) and the kernel of every scan chosen from their per-scan summaries - run_scan's own choice.  A resident
-// launch reads its scan's rows of the tables where they lie; only a scan that takes the per-bucket launches has its rows and messages read back.
+// A recorded run LIVE on slot 0 from device-resident scans and messages: run_one_scan for every scan in turn, with the bucket tables of the whole run
+// built once on the device (run_tables) and every scan's summary taken from there.  A resident launch reads its scan's rows of the tables where
+// they lie; only a scan that takes the per-bucket launches has its rows and messages read back.
 int lk_run_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const double* t_begin, int msg_kind,
                      const uint32_t* n_msg, const void* d_msgs, const lk_run_options* opt, float* d_world_out, lk_pose* out, size_t* n_done,
                      uint32_t* n_slides) {
@@ -1467,36 +1462,21 @@ int lk_run_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const 
     if (rc) return rc;
     if (rt.first_unsorted != 0xffffffffu)
         return fail(h, LK_ERR_INVALID, "scan " + std::to_string(rt.first_unsorted) + " is not sorted by time (curvature must be non-decreasing within a scan, and finite)");
-    const size_t msg_bytes = msg_kind == 2 ? sizeof(lk_kin_imu) : sizeof(lk_imu);
-    std::vector<unsigned long long> bstart;
-    std::vector<double> btime;
-    std::vector<unsigned char> msgs;
+    ScanHost ht;
     for (size_t s = 0; s < S; ++s) {
-        const size_t rel = scan_off[s] - scan_off[0], nb = rt.sum[4 * s], biggest = rt.sum[4 * s + 1], smallest = rt.sum[4 * s + 2], m0 = rt.sum[4 * s + 3];
+        const size_t rel = scan_off[s] - scan_off[0], m0 = rt.sum[4 * s + 3];
+        const ScanSum sum{rt.sum[4 * s], rt.sum[4 * s + 1], rt.sum[4 * s + 2]};
         const size_t nm = msg_kind ? n_msg[s] : 0;
-        const int kind = nm ? msg_kind : 0;   // (run_scan's: a scan without messages runs the kernels without them)
+        // a scan without messages runs the kernels without them, as through run_scan
+        const ScanMsgs m{nm ? msg_kind : MSG_NONE, nm, static_cast<const unsigned char*>(d_msgs) + msg_record_bytes(msg_kind) * m0};
         if ((rc = zero_scan_counters(h, 0, 1))) return rc;
         ScanDev dv;
         dv.po = rt.d_ps + rt.bstart[s], dv.t = rt.d_tb + rt.bstart[s], dv.nb = rt.d_nbp + 2 * s;
         dv.io = rt.d_mo ? rt.d_mo + s : rt.d_nbp + 2 * s, dv.im = d_msgs;   // the cursor starts at the scan's first message (lk_rag_scan_summary_kernel), io[1] is where they end
-        dv.sync = rt.d_sync + 4 * s, dv.rs = reinterpret_cast<LkResume*>(rt.d_resume) + s, dv.nbk = nb;
+        dv.sync = rt.d_sync + 4 * s, dv.rs = reinterpret_cast<LkResume*>(rt.d_resume) + s;
         dv.ids = h->d_ids - rel;   // d_ids holds ONE scan: the kernels index it with the run's point numbers, which start at rel in this scan
         lk_pose pose;
-        if (grid_takes(h, smallest, biggest) && nm == 0) {
-            rc = grid_rounds(h, pts0, dv, biggest, world0, &pose);
-        } else if (resident_enabled(h) && biggest <= LK_RESIDENT_MAX) {
-            rc = resident_rounds(h, pts0, dv, kind, world0, &pose);
-        } else {   // per-bucket launches: this scan's rows of the tables and its messages drive them from the host
-            bstart.resize(nb + 1), btime.resize(nb), msgs.resize(msg_bytes * nm);
-            HIPCHK(h, hipMemcpyAsync(bstart.data(), dv.po, 8 * (nb + 1), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipMemcpyAsync(btime.data(), dv.t, 8 * nb, hipMemcpyDeviceToHost, h->stream));
-            if (nm) HIPCHK(h, hipMemcpyAsync(msgs.data(), static_cast<const unsigned char*>(d_msgs) + msg_bytes * m0, msg_bytes * nm, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            rc = run_scan_launches(h, pts0, bstart, btime, kind == 1 ? reinterpret_cast<const lk_imu*>(msgs.data()) : nullptr, kind == 1 ? nm : 0,
-                                   kind == 2 ? reinterpret_cast<const lk_kin_imu*>(msgs.data()) : nullptr, kind == 2 ? nm : 0, world0);
-            if (!rc) rc = finish_scan(h, &pose);
-        }
-        if (rc) return rc;
+        if ((rc = run_one_scan(h, pts0, &dv, ht, sum, m, world0, &pose))) return rc;
         if (out) out[s] = pose;
         if (n_done) *n_done = s + 1;
         if (opt && opt->half_map_size != 0) {   // mapSliding behind the scan, as a caller's loop does it with lk_map_slide
@@ -1508,6 +1488,9 @@ int lk_run_scans_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const 
     return LK_OK;
 }
 
+// One scan that lies in HBM with a bucket table from the caller's host: the table's non-empty entries are the scan's buckets, and the scan runs as
+// through lk_process_scan (run_one_scan).  An empty entry is no neighbour: where one lies between two buckets of more than LK_SMALL_MAX points, the
+// second one's predict rides in the first one's root pass, as it does for the same scan there (same bits as a predict launched apart).
 int lk_process_scan_dev(lk_handle* h, const lk_point* d_pts, size_t n, double t_begin, const uint32_t* bucket_off,
                         const double* bucket_dt, size_t n_buckets, lk_pose* out) {
     CHECK_H(h);
@@ -1523,48 +1506,24 @@ int lk_process_scan_dev(lk_handle* h, const lk_point* d_pts, size_t n, double t_
     }
     int rc = zero_scan_counters(h, 0, 1);
     if (rc) return rc;
-    if (resident_enabled(h) || grid_enabled(h)) {
-        std::vector<unsigned long long> bstart;
-        std::vector<double> btime;
-        uint32_t biggest = 0, smallest = 0xffffffffu;
-        for (size_t b = 0; b < n_buckets; ++b) {
-            if (bucket_off[b + 1] <= bucket_off[b]) continue;
-            bstart.push_back(bucket_off[b]);
-            btime.push_back(t_begin + bucket_dt[b]);
-            biggest = std::max(biggest, bucket_off[b + 1] - bucket_off[b]);
-            smallest = std::min(smallest, bucket_off[b + 1] - bucket_off[b]);
-        }
-        bstart.push_back(bucket_off[n_buckets]);
-        if (!btime.empty() && grid_takes(h, smallest, biggest)) {
-            lk_pose pose;
-            if ((rc = run_scan_grid(h, d_pts, bstart, btime, biggest, nullptr, &pose))) return rc;
-            if (out) *out = pose;
-            return LK_OK;
-        }
-        if (!btime.empty() && resident_enabled(h) && biggest <= LK_RESIDENT_MAX) {
-            lk_pose pose;
-            if ((rc = run_scan_resident(h, d_pts, bstart, btime, nullptr, 0, 0, nullptr, &pose))) return rc;
-            if (out) *out = pose;
-            return LK_OK;
-        }
-    }
-    if (h->spec_enable && (rc = backup_filter(h))) return rc;
-    bool pre_predicted = false;
+    ScanHost ht;
+    ScanSum sum{0, 0, n};
     for (size_t b = 0; b < n_buckets; ++b) {
-        int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
-        if (nb <= 0) continue;
-        double t_next = NAN;
-        if (b + 1 < n_buckets && nb > LK_SMALL_MAX && (int)(bucket_off[b + 2] - bucket_off[b + 1]) > LK_SMALL_MAX) t_next = t_begin + bucket_dt[b + 1];
-        rc = enqueue_bucket(h, d_pts + bucket_off[b], nb, t_begin + bucket_dt[b], nullptr, true, t_next, &pre_predicted);
-        if (rc) return rc;
+        if (bucket_off[b + 1] <= bucket_off[b]) continue;
+        const size_t nb = bucket_off[b + 1] - bucket_off[b];
+        ht.bstart.push_back(bucket_off[b]);
+        ht.btime.push_back(t_begin + bucket_dt[b]);
+        sum.biggest = std::max(sum.biggest, nb);
+        sum.smallest = std::min(sum.smallest, nb);
     }
-    if ((rc = spec_join(h))) return rc;
+    ht.bstart.push_back(bucket_off[n_buckets]);
+    sum.nb = ht.btime.size();
     lk_pose pose;
-    rc = finish_scan(h, &pose);
+    // (a table of empty entries only: nothing runs, the pose is the untouched filter's)
+    rc = sum.nb ? run_one_scan(h, d_pts, nullptr, ht, sum, ScanMsgs{MSG_NONE, 0, nullptr}, nullptr, &pose) : finish_scan(h, &pose);
     if (rc) return rc;
     if (out) *out = pose;
     return LK_OK;
 }
 
 }  // extern "C"
-

@@ -201,6 +201,66 @@ def test_kernel_choice_per_scan(hip_lib, mode):
     _close(g_loop, g_run)
 
 
+# ------------------------------------------------------------------ 3b. lk_process_scan_dev: a hand-written table against process_scan
+# bucket sizes, 0 = an empty table entry: scan-resident with empty entries first, inside and last | grid-resident | an empty entry between two
+# large buckets | mixed sizes (per-bucket launches) | one large bucket
+PSD_SHAPES = [[0, 1, 64, 0, 65, 512, 0], [513, 600, 513], [513, 0, 600], [40, 513, 9], [513]]
+
+
+def _hand_table(sizes, dcurv=0.002):
+    """(bucket_off, bucket_dt) of _shaped_scan(sizes): entry k holds sizes[k] points at the float32 curvature dcurv * (k + 1); an empty entry
+    repeats its neighbour's time (the one before it, or the one behind it where it is first)."""
+    dt = [float(np.float32(dcurv * (k + 1))) if n else None for k, n in enumerate(sizes)]
+    first = next((v for v in dt if v is not None), 0.0)
+    for k in range(len(dt)):
+        if dt[k] is None:
+            dt[k] = dt[k - 1] if k else first
+    return np.r_[0, np.cumsum(sizes)].astype(np.uint32), np.array(dt)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["default", "resident-off", "grid-off"])
+def test_process_scan_dev_equals_process_scan(hip_lib, mode):
+    """Handle A: process_scan over the host copy of a scan (its buckets found from the curvatures).  Handle B: the same points in HBM and
+    process_scan_dev with a hand-written bucket table that also holds empty entries.  Same pose, same filter, same map, same kernel choice,
+    scan after scan; then a table of empty entries only: a pose with n_buckets == 0, filter and map untouched."""
+    sc = _scene(1)
+    g_a, g_b = hip_lib.LegKiloHip(sc.cfg()), hip_lib.LegKiloHip(sc.cfg())
+    for g in (g_a, g_b):
+        _start(g, sc)
+        if mode == "resident-off":
+            g.stream_resident(False)
+        if mode == "grid-off":
+            g.stream_grid(0)
+    d_pts = g_b.device_malloc(max(sum(sz) for sz in PSD_SHAPES) * PT)
+    try:
+        for k, sizes in enumerate(PSD_SHAPES):
+            tb = T0 + 0.1 * k
+            pts = _shaped_scan(sc, tb, sizes, 7700 + k)
+            off, dt = _hand_table(sizes)
+            before = [g.stream_resident_stats() for g in (g_a, g_b)]
+            pose_a, _ = g_a.process_scan(pts, tb)
+            g_b.h2d(d_pts, pts)
+            pose_b = g_b.process_scan_dev(d_pts, len(pts), tb, off, dt)
+            assert pose_a.n_buckets == sum(1 for n in sizes if n), (sizes, pose_a.n_buckets)
+            _same_pose(pose_b, pose_a, sizes)
+            _same_handle_state(g_b, g_a)
+            moved = [tuple(int(v) for v in np.subtract(g.stream_resident_stats(), b)) for g, b in zip((g_a, g_b), before)]
+            print(f"{mode} {sizes}: resident statistics moved by {moved[0]} (process_scan) {moved[1]} (process_scan_dev)")
+            assert moved[0] == moved[1], (sizes, moved)
+        # empty entries only (over a scan that has points: n == 0 is refused)
+        state, stats = _digest(g_b), g_b.stream_resident_stats()
+        pose = g_b.process_scan_dev(d_pts, len(pts), T0 + 0.1 * len(PSD_SHAPES), np.zeros(3, dtype=np.uint32), np.zeros(2))
+        assert pose.n_buckets == 0
+        after = _digest(g_b)
+        assert after[:2] == state[:2], "state changed"
+        scenes.maps_identical(after[3], state[3])
+        assert g_b.stream_resident_stats() == stats
+    finally:
+        g_b.device_free(d_pts)
+        _close(g_a, g_b)
+
+
 # ------------------------------------------------------------------ 4. edge sizes, sub-range, guard bands
 @pytest.mark.gpu
 def test_edge_sizes_and_subrange_with_guard_bands(hip_lib):

@@ -430,6 +430,21 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
 int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets,
                                        const uint32_t* bucket_off, const double* bucket_dt, const double* t_begin, const uint32_t* n_msg,
                                        const void* msgs, int msg_kind, lk_pose* out);
+/* Whole recorded RUNS with the insert, a run per filter slot: run r = the scans run_off[r] .. run_off[r+1) (run_off: n_runs + 1 scan indices, first 0;
+ * n_runs <= n_slots, n_scans = run_off[n_runs] is not bounded by n_slots), scan s = d_pts[scan_off[s] .. scan_off[s+1]) sorted by time, its messages
+ * n_msg[s] records of d_msgs (DEVICE memory; msg_kind as above) - the tables lk_decode_scans_dev and lk_kin_split_dev / lk_imu_split_dev leave.  The
+ * bucket tables are built on the device.  Per scan this is what lk_batch_replay_overlay_ragged_dev does, one KILO::process after the other: across a
+ * scan boundary the slot's state, covariance, time stamps and OVERLAY stay (KILO's members), the messages start at the next scan's first record -
+ * what a scan's package held beyond its last bucket is never applied (`measure` is a new package per call, KILO.cc:316-399), and at a scan's first
+ * bucket all of its own records below that bucket's time are.  Priors from lk_batch_set_priors(_dev); a slot's time stamps start at the t_begin of
+ * its run's first scan.  out[s] (n_scans records, may be NULL): the pose after scan s, n_effect / n_buckets / n_updates of that scan alone.
+ * Afterwards lk_batch_get_states(_dev) gives the runs' final states, lk_overlay_export(r) run r's overlay; the handle's map is untouched.
+ * Synchronous.  Buckets <= 512 points: run-resident, one wave per run (lk_overlay_resident_rounds as above); else launch by launch - same bits.
+ * LK_ERR_INVALID: n_runs 0 or above n_slots, run_off[0] != 0, an empty run or scan, a scan not sorted by time (the message names it), a voxel key
+ * outside +-2^20; LK_ERR_CAPACITY: a bucket above max_scan_points, pools set by lk_overlay_reserve that overflow (pools the library sized grow and
+ * the call runs again); LK_ERR_STATE: no frozen-map grid.  A refused call leaves the slots at their priors. */
+int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
+                                     const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

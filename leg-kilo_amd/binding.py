@@ -25,7 +25,7 @@ EXPORTS = [
     "lk_kin_configure", "lk_kin_get_frontend", "lk_kin_set_frontend", "lk_decode_highstate", "lk_decode_highstate_dev", "lk_kin_split_dev",
     "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
     "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
-    "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev",
+    "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
 ]
 
 
@@ -534,6 +534,59 @@ class LegKiloHip:
             return self.batch_replay_overlay_ragged_dev(d, tables)
         finally:
             self.device_free(d)
+
+    def batch_replay_overlay_runs_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, want_poses=True):
+        """Whole recorded runs WITH the map insert, run r on slot r (lk_batch_replay_overlay_runs_dev): run r = the scans run_off[r] : run_off[r + 1],
+        scan s = d_pts[scan_off[s] : scan_off[s + 1]] with n_msg[s] records of msg_kind (1: lk_imu, 2: lk_kin_imu) at d_msgs - all in HBM, the
+        bucket tables are built there.  State, covariance, times and overlay of a slot survive its run's scan boundaries.  Returns one pose per
+        SCAN (counters of that scan alone); batch_get_states / overlay_export(r) give a run's final state and overlay."""
+        ro = np.ascontiguousarray(run_off, dtype=np.uint32)
+        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
+        n_scans = len(so) - 1
+        tb = _f64(t_begins)
+        assert len(tb) == n_scans and len(ro) >= 1
+        nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
+        assert nm is None or len(nm) == n_scans
+        poses = (abi.lk_pose * max(n_scans, 1))() if want_poses else None
+        self._chk(self.L.lk_batch_replay_overlay_runs_dev(self.h, C.c_void_p(d_pts), C.c_size_t(len(ro) - 1), _p(ro), _p(so), _p(tb), C.c_int(msg_kind),
+                                                          _p(nm), C.c_void_p(d_msgs) if d_msgs else None, poses))
+        return list(poses[:n_scans]) if want_poses else None
+
+    def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None):
+        """Convenience: runs = a list of runs, each a list of host scans (lk_point arrays, time-sorted, any sizes); t_begins, imus / kins: the same
+        nesting (one start time, one message array per scan) -> HBM -> batch_replay_overlay_runs_dev.  Optional priors, one per run.  Returns the
+        poses run by run (a list of lists)."""
+        assert imus is None or kins is None
+        if xs is not None:
+            self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
+        scans = [sc for run in runs for sc in run]
+        run_off = np.r_[0, np.cumsum([len(run) for run in runs])].astype(np.uint32)
+        scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])].astype(np.uint64)
+        tb = [t for run in t_begins for t in run]
+        allpts = np.ascontiguousarray(np.concatenate(scans))
+        msgs = imus if imus is not None else kins
+        kind, n_msg, flat = 0, None, None
+        if msgs is not None:
+            kind = 1 if imus is not None else 2
+            per_scan = [m for run in msgs for m in run]
+            n_msg = np.fromiter((len(m) for m in per_scan), dtype=np.uint32, count=len(scans))
+            if n_msg.sum():
+                flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in per_scan if len(m)]))
+        dptrs = []
+        try:
+            d_pts = self.device_malloc(allpts.nbytes)
+            dptrs.append(d_pts)
+            self.h2d(d_pts, allpts)
+            d_msgs = 0
+            if flat is not None:
+                d_msgs = self.device_malloc(flat.nbytes)
+                dptrs.append(d_msgs)
+                self.h2d(d_msgs, flat)
+            poses = self.batch_replay_overlay_runs_dev(d_pts, run_off, scan_off, tb, kind, n_msg, d_msgs)
+            return [poses[int(a):int(b)] for a, b in zip(run_off[:-1], run_off[1:])]
+        finally:
+            for d in dptrs:
+                self.device_free(d)
 
     def overlay_reserve(self, roots_per_scan=0, nodes_per_scan=0, blocks_per_scan=0):
         self._chk(self.L.lk_overlay_reserve(self.h, C.c_uint32(roots_per_scan), C.c_uint32(nodes_per_scan), C.c_uint32(blocks_per_scan)))

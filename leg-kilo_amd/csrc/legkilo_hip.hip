@@ -457,14 +457,15 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     double t_upd = f->last_update_t, t_pred = f->last_predict_t;
     __syncthreads();
     const double tb = T[b];
+    const LkRagBucket rb = rag_bucket(rg, slot, b, msg_kind != 0);   // (runs: the messages and the look-back are the owning scan's)
     if (msg_kind) {
         const size_t mstride = msg_kind == 2 ? 33 : 7;
-        const unsigned int q0 = rg.imu_off[slot], q1 = rg.imu_off[slot + 1];
+        const unsigned int q0 = rb.q0, q1 = rb.q1;
         for (unsigned int q = q0; q < q1; ++q) {
             const double* m = rg.imu + mstride * (size_t)q;
             const double tm = m[0];
             if (!(tm < tb)) break;                  // time-sorted: the rest belongs to later buckets
-            if (b > 0 && tm < T[b - 1]) continue;   // consumed on the way to an earlier bucket
+            if (!rb.first && tm < T[b - 1]) continue;   // consumed on the way to an earlier bucket
             wave_predict_core(sm, Q, tm - t_upd, tm - t_pred, lane, rg.q_diag != 0);
             t_pred = tm;
             if (msg_kind == 2) wave_kin_update_core(sm, rows, m, rg.acc_scale, rg.Rn, rg.kin_noise, lane);
@@ -477,7 +478,10 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     __syncthreads();
     for (int e = lane; e < 900; e += LK_WAVE) f->P[e] = sm.P[e];
     if (lane < 36) f->x[lane] = sm.x[lane];
-    if (lane == 0) f->last_update_t = t_upd, f->last_predict_t = t_pred;
+    if (lane == 0) {
+        f->last_update_t = t_upd, f->last_predict_t = t_pred;
+        if (rg.run_scan && rb.first) f->n_buckets = 0u, f->n_updates = 0u, f->n_effect = 0ull;   // runs: the update behind this launch counts the scan alone
+    }
 }
 
 
@@ -2229,6 +2233,78 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     rg.imu = reinterpret_cast<const double*>(d_ms);
     rag_from_handle(h, msg_kind, &rg);
     return ragged_launch(h, d_pts, S, rg, bt.t0, (int)biggest, (size_t)most, nullptr, msg_kind, out);
+}
+
+// Batch replay WITH insert of whole recorded runs: run r = the scans run_off[r] .. run_off[r+1) on filter slot r, each scan what
+// lk_batch_replay_overlay_ragged_dev does for one - but the slot's state, covariance, times and overlay survive the scan boundary, as KILO's members do
+// from one KILO::process to the next, and the message cursor jumps to the next scan's first record (what a package left over is never applied).
+// Bucket tables: built here for all scans at once (BucketTables, CSR), in which a run is one contiguous bucket range - overlay_ragged_launch replays
+// it as one long scan whose kernels know where its scans end (LkRagged::run_scan).  out[s]: the pose after scan s, its counters that scan's alone.
+int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
+                                     const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out) {
+    CHECK_H(h);
+    if (n_runs == 0 || n_runs > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_runs must be in [1, n_slots]");
+    if (!d_pts || !run_off || !scan_off || !t_begin) return fail(h, LK_ERR_INVALID, "null argument");
+    if (msg_kind < 0 || msg_kind > 2 || (msg_kind && !n_msg)) return fail(h, LK_ERR_INVALID, "msg_kind must be 0 (none), 1 (lk_imu) or 2 (lk_kin_imu) with n_msg given");
+    const size_t R = n_runs;
+    if (run_off[0] != 0) return fail(h, LK_ERR_INVALID, "run_off[0] must be 0");
+    for (size_t r = 0; r < R; ++r)
+        if (run_off[r + 1] <= run_off[r]) return fail(h, LK_ERR_INVALID, "run " + std::to_string(r) + " is empty");
+    const size_t S = run_off[R];
+    if (scan_off[0] != 0) return fail(h, LK_ERR_INVALID, "scan_off[0] must be 0");
+    size_t n_msg_total = 0;
+    for (size_t s = 0; s < S; ++s) {
+        if (scan_off[s + 1] <= scan_off[s]) return fail(h, LK_ERR_INVALID, "scan " + std::to_string(s) + " is empty");
+        if (msg_kind) n_msg_total += n_msg[s];
+    }
+    const size_t n = scan_off[S];
+    if (n >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 points in one batch");
+    if (n_msg_total && !d_msgs) return fail(h, LK_ERR_INVALID, "null message array");
+    if (n_msg_total >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 messages in one batch");
+    size_t max_run_pts = 0;   // what sizes a slot's overlay: everything its run inserts
+    for (size_t r = 0; r < R; ++r) max_run_pts = std::max(max_run_pts, (size_t)(scan_off[run_off[r + 1]] - scan_off[run_off[r]]));
+    LkMap fmap;   // (asked here, ahead of the tables: a handle without the grid is refused before anything is built)
+    LKCHK(frozen_map(h, &fmap));
+    if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    BucketTables bt;
+    unsigned int *d_ro = nullptr, *d_rb = nullptr;
+    double* d_rt = nullptr;
+    lk_pose* d_pose = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base);
+        bt.take(c, n, S);
+        d_ro = c.take<unsigned int>(R + 1), d_rb = c.take<unsigned int>(R + 1);   // the runs' first scans, their first buckets
+        d_rt = c.take<double>(R);                                                  // their start times
+        d_pose = c.take<lk_pose>(S);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->ragdev, bytes, bytes / 4));
+    carve(h->ragdev.p);
+    HIPCHK(h, hipMemcpyAsync(d_ro, run_off, 4 * (R + 1), hipMemcpyHostToDevice, h->stream));
+    LKCHK(bt.build(h, d_pts, n, S, scan_off, t_begin, msg_kind ? n_msg : nullptr));
+    hipLaunchKernelGGL(lk_rag_stats_kernel, dim3((unsigned int)((std::max(n, S) + 255) / 256)), dim3(256), 0, h->stream, bt.ps, bt.bs, (int)S, bt.st);
+    hipLaunchKernelGGL(lk_rag_run_tables_kernel, dim3((unsigned int)((R + 256) / 256)), dim3(256), 0, h->stream, bt.bs, d_ro, bt.t0, (int)R, d_rb, d_rt, bt.st);
+    HIPCHK(h, hipGetLastError());
+    unsigned int st[8];
+    HIPCHK(h, hipMemcpyAsync(st, bt.st, 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const unsigned int biggest = st[1], most_run = st[5];
+    if (st[3])
+        return fail(h, LK_ERR_INVALID, "scan " + std::to_string(S - st[3]) + " is not sorted by time (curvature must be non-decreasing within a scan, and finite)");
+    if (biggest > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
+    LkRagged rg;
+    rg.pt_off = bt.ps;
+    rg.t = bt.tb;
+    rg.nb = nullptr;
+    rg.ldb = (int)most_run;
+    rg.bstart = d_rb;
+    rg.imu_off = msg_kind ? bt.mo : nullptr;
+    rg.imu = reinterpret_cast<const double*>(d_msgs);   // read where they lie
+    rag_from_handle(h, msg_kind, &rg);
+    rg.run_scan = d_ro, rg.scan_b = bt.bs, rg.scan_pose = d_pose;
+    return overlay_ragged_launch(h, d_pts, R, rg, d_rt, (int)biggest, (size_t)most_run, nullptr, max_run_pts, msg_kind, out, S);
 }
 
 // The tables of a live run (RunTables): the same CSR tables over the run's points - d_pts is the run's FIRST point - followed by the per-scan

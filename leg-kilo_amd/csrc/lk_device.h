@@ -167,6 +167,12 @@ struct LkRagged {
     int q_diag;                        // the process noise Q is diagonal (initProcessCovQ, eskf.cc:47-62): P += dt^2 Q touches 30 entries
     double acc_scale;                  // gravity / acc_norm (KILO.cc:246)
     double Rn[6];                      // IMU measurement noise: acc, acc, acc_z, gyr, gyr, gyr
+    // RUNS (lk_batch_replay_overlay_runs_dev; CSR form only; null: every slot is one scan, as everywhere else): slot r replays the consecutive scans
+    // run_scan[r] .. run_scan[r+1) - in the flat tables one contiguous bucket range, which is what bstart[r] .. bstart[r+1) then names - and scan s owns the
+    // flat buckets scan_b[s] .. scan_b[s+1), the messages imu_off[s] .. imu_off[s+1) (imu_off counts SCANS here) and the pose record scan_pose[s].
+    const unsigned int* run_scan = nullptr;   // [S + 1]
+    const unsigned int* scan_b = nullptr;     // [n_scans + 1]
+    lk_pose* scan_pose = nullptr;             // [n_scans]: the pose after a scan's last bucket, its counters that scan's alone
 };
 
 __device__ __forceinline__ int rag_nb(const LkRagged& rg, int slot) {
@@ -177,6 +183,44 @@ __device__ __forceinline__ const unsigned long long* rag_pt_off(const LkRagged& 
 }
 __device__ __forceinline__ const double* rag_t(const LkRagged& rg, int slot) {
     return rg.bstart ? rg.t + rg.bstart[slot] : rg.t + (size_t)slot * rg.ldb;
+}
+// Runs: the scan that owns bucket b of slot `slot` (scans are never empty: scan_b is strictly increasing).
+__device__ __forceinline__ int rag_run_scan(const LkRagged& rg, int slot, int b) {
+    const unsigned int g = rg.bstart[slot] + (unsigned int)b;
+    int lo = (int)rg.run_scan[slot], hi = (int)rg.run_scan[slot + 1];   // scan_b[lo] <= g < scan_b[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rg.scan_b[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// What is scan-aware about bucket b of a slot (KILO::process is called once per scan: `measure` is a new package every time).  q0 .. q1: the messages
+// in reach - the owning scan's; first: the scan's first bucket, where every message below the bucket's time is applied whatever the bucket before (a
+// run's: the previous scan's last) was stamped; pose: where the pose goes if this is the scan's last bucket, else null.  Without runs: the slot's scan.
+struct LkRagBucket {
+    unsigned int q0, q1;
+    bool first;
+    lk_pose* pose;
+};
+__device__ __forceinline__ LkRagBucket rag_bucket(const LkRagged& rg, int slot, int b, bool with_msgs) {
+    LkRagBucket r;
+    int s = slot;
+    r.first = b == 0, r.pose = nullptr;
+    if (rg.run_scan) {
+        s = rag_run_scan(rg, slot, b);
+        const unsigned int g = rg.bstart[slot] + (unsigned int)b;
+        r.first = g == rg.scan_b[s];
+        if (g + 1 == rg.scan_b[s + 1]) r.pose = rg.scan_pose + s;
+    }
+    r.q0 = with_msgs ? rg.imu_off[s] : 0u, r.q1 = with_msgs ? rg.imu_off[s + 1] : 0u;
+    return r;
+}
+// The pose record of a scan (runs): rotation, position, velocity = the first 15 doubles of the state, handed over lane by lane; the counters are the
+// filter record's, which count the scan alone (they are zeroed at a scan's first bucket).  Plain vector stores.
+__device__ __forceinline__ void rag_write_pose(lk_pose* p, const double* x, const LkFilter* f, int lane) {
+    if (lane < 15) reinterpret_cast<double*>(p)[lane] = x[lane];
+    if (lane == 0) p->n_effect = f->n_effect, p->n_buckets = f->n_buckets, p->n_updates = f->n_updates;
 }
 
 // ---------------------------------------------------------------- small fp64 helpers

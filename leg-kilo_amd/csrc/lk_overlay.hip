@@ -30,14 +30,15 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     double t_upd = f->last_update_t, t_pred = f->last_predict_t;
     __syncthreads();
     const double tb = T[b];
+    const LkRagBucket rb = rag_bucket(rg, slot, b, msg_kind != 0);   // (runs: the messages and the look-back are the owning scan's)
     if (msg_kind) {   // lk_rag_advance_kernel: the scan's messages stamped before this bucket that no earlier bucket has consumed (KILO.cc:379-390)
         const size_t mstride = msg_kind == 2 ? 33 : 7;
-        const unsigned int q0 = rg.imu_off[slot], q1 = rg.imu_off[slot + 1];
+        const unsigned int q0 = rb.q0, q1 = rb.q1;
         for (unsigned int q = q0; q < q1; ++q) {
             const double* m = rg.imu + mstride * (size_t)q;
             const double tm = m[0];
             if (!(tm < tb)) break;
-            if (b > 0 && tm < T[b - 1]) continue;
+            if (!rb.first && tm < T[b - 1]) continue;
             wave_predict_core(sm, Q, tm - t_upd, tm - t_pred, lane, rg.q_diag != 0);
             t_pred = tm;
             if (msg_kind == 2) wave_kin_update_core(sm, rows, m, rg.acc_scale, rg.Rn, rg.kin_noise, lane);
@@ -78,6 +79,7 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     // lk_update_wave_ragged_kernel (update_only): the posterior the insert reads
     const int N = (int)(lane_bcast<28>(totv) + 0.5);
     if (lane == 0) {
+        if (rg.run_scan && rb.first) f->n_buckets = 0u, f->n_updates = 0u, f->n_effect = 0ull;   // runs: the counters are the scan's own
         f->last_predict_t = t_pred;
         f->n_buckets += 1;
         f->last_N = N;
@@ -92,6 +94,7 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     __syncthreads();
     for (int e = lane; e < 900; e += LK_WAVE) f->P[e] = sm.P[e];
     if (lane < 36) f->x[lane] = sm.x[lane];
+    if (rb.pose) rag_write_pose(rb.pose, sm.x, f, lane);   // runs: the scan's last bucket
     // the re-projection below reads the posterior through the filter record, like every other kernel of the insert - written by THIS wave: its stores
     // have to be acknowledged before its loads go out (workgroup scope = s_waitcnt; an agent-scope fence here is an L2 write-back + invalidate per
     // wave, 1 024 of them per launch: the first version of this kernel was 6 ms SLOWER than the five launches for it)
@@ -105,6 +108,14 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     }
 }
 
+// Runs, buckets above LK_SCAN_WAVE_MAX points (the update is lk_update_wave_ragged_kernel's, which knows no scans): the pose of every scan whose last bucket
+// is bucket b of its run, from the posterior that update has just written.
+__global__ void __launch_bounds__(LK_WAVE) lk_rag_pose_tap_kernel(const LkFilter* __restrict__ filters, LkRagged rg, int b) {
+    const int slot = blockIdx.x;
+    if (b >= rag_nb(rg, slot)) return;
+    const LkRagBucket rb = rag_bucket(rg, slot, b, false);
+    if (rb.pose) rag_write_pose(rb.pose, filters[slot].x, &filters[slot], (int)threadIdx.x);
+}
 }   // extern "C++"
 
 extern "C" {
@@ -168,7 +179,8 @@ __global__ void __launch_bounds__(256) lk_ov_poison_nodes_kernel(lk_node_rec* no
 // 113 GB for 1 024 scans, where the bench's scans use 4 700 roots); else a first guess of n_pts / 18 roots.  `grow` (bits of the slots' error
 // word: 1 private root table, 2 nodes, 4 point blocks) doubles what overflowed - the replay is then run again (lk_batch_replay_overlay_dev).
 static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t biggest_bucket, const LkMap& fmap, unsigned int grow = 0) {
-    const bool hist = h->ov_hw_roots > 0 && h->ov_hw_npts == n_pts_scan;
+    // (a run and a single scan of equal point count are not the same shape: a run's overlay keeps growing over its scans)
+    const bool hist = h->ov_hw_roots > 0 && h->ov_hw_npts == n_pts_scan && h->ov_hw_runs == h->ov_runs;
     uint32_t roots, nodes_extra, blocks;
     if (h->ov_want_roots) {
         roots = h->ov_want_roots;
@@ -350,7 +362,7 @@ static int ov_attempt_end(lk_handle* h, int S, int attempt, const unsigned int* 
         HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
         return ov_reserve(h, (uint32_t)S, n_pts_scan, biggest, fmap, stt[0]);
     }
-    if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = n_pts_scan;
+    if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = n_pts_scan, h->ov_hw_runs = h->ov_runs;
     if (out) LKCHK(fetch_poses(h, out, S));   // no wait without `out`: ov_read_status has synchronised
     // a refused replay leaves the slots as the caller armed them, not at whatever the buckets before the error made of them
     if (stt[0]) HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
@@ -406,6 +418,7 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
     if (n_pts == 0 || n_buckets == 0) return fail(h, LK_ERR_INVALID, "empty scans");
     if (!d_pts || !bucket_off || !bucket_dt) return fail(h, LK_ERR_INVALID, "null argument");
     const int S = (int)n_scans;
+    h->ov_runs = false;
     std::vector<size_t> live;
     size_t biggest = 0;
     // this entry's own checks, bucket by bucket ahead of the shared one: the first bad bucket decides which error the caller sees
@@ -478,9 +491,13 @@ int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size
 // index's longest bucket; a scan that has run out of buckets leaves every launch at once): per index b - the scan's messages up to the
 // bucket's time + predict (lk_rag_advance_kernel), residual with the overlay lookup, update, then the insert passes of
 // lk_batch_replay_overlay_dev on each scan's own bucket (LkPtSrc).  One stream: a recorded run's buckets are small, the launches are what it costs.
+// Runs (rg.run_scan, CSR tables: lk_batch_replay_overlay_runs_dev): a slot is a run of scans - for addressing and time one long scan of ldb buckets at most,
+// max_scan_pts its points; the kernels know where its scans end (rag_bucket), and `out` takes the n_poses records of rg.scan_pose instead of the slots' poses.
 int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const LkRagged& rg, const double* d_tbegin, int biggest, size_t ldb,
-                                 const int* max_n, size_t max_scan_pts, int msg_kind, lk_pose* out) {
+                                 const int* max_n, size_t max_scan_pts, int msg_kind, lk_pose* out, size_t n_poses) {
     const int S = (int)S_;
+    const bool runs = rg.run_scan != nullptr;
+    h->ov_runs = runs;
     LkMap fmap;
     LKCHK(ov_replay_begin(h, S, max_scan_pts, (size_t)biggest, &fmap));
     hipStream_t st = h->stream;
@@ -496,7 +513,7 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
         }
         const bool rag_resident = getenv("LEGKILO_RAG_RESIDENT") == nullptr || atoi(getenv("LEGKILO_RAG_RESIDENT")) != 0;   // 0: launch by launch (the bit-identity reference of the tests: read at every call)
         h->ov_res_rounds = 0;
-        const bool resident = rag_resident && biggest <= LK_SCAN_WAVE_MAX && !rg.bstart;
+        const bool resident = rag_resident && biggest <= LK_SCAN_WAVE_MAX && (!rg.bstart || runs);
         if (resident) {
             // [S] next bucket of every scan, [S] the bucket whose fallback items wait, one counter: scans stopped by fallback items in the last launch
             LKCHK(reserve(h, h->ov_res, sizeof(int) * (2 * (size_t)S + 4)));
@@ -504,10 +521,11 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
             int* fb_b = cur + S;
             unsigned int* pending = reinterpret_cast<unsigned int*>(cur + 2 * (size_t)S);
             HIPCHK(h, hipMemsetAsync(cur, 0, sizeof(int) * (2 * (size_t)S + 4), st));
-            const LkPtSrc fsrc = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, 0, fb_b};
+            const LkPtSrc fsrc = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, 0, fb_b, rg.bstart};
             unsigned int rounds = 0;
             for (;; ++rounds) {
-                LKCHK(ov_scan_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovscan.hip
+                if (runs) LKCHK(ov_run_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovrun.hip
+                else LKCHK(ov_scan_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovscan.hip
                 unsigned int n_pending = 0;
                 HIPCHK(h, hipMemcpyAsync(&n_pending, pending, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
                 HIPCHK(h, hipStreamSynchronize(st));
@@ -520,7 +538,7 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
         }
         for (size_t b = 0; b < (resident ? 0 : ldb); ++b) {
             const int nb = std::max(1, max_n ? max_n[b] : biggest);
-            const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr};
+            const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr, rg.bstart};
             if (biggest <= LK_SCAN_WAVE_MAX) {
                 // buckets of <= LK_SCAN_WAVE_MAX points: three launches per bucket index (front, mid, tail); the tail at one wave per slot:
                 // 29.2 -> 26.4 ms against four (fewer waves to dispatch)
@@ -533,6 +551,7 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
                 LAUNCH(h, "rag_advance", hipLaunchKernelGGL(lk_rag_advance_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_Q, rg, (int)b, msg_kind));
                 LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, S), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, h->d_partials, h->part_stride));
                 LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_partials, h->part_stride, h->d_Q, rg, (int)b, 1));
+                if (runs) LAUNCH(h, "rag_pose_tap", hipLaunchKernelGGL(lk_rag_pose_tap_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, rg, (int)b));
                 LKCHK(ov_insert_passes(h, st, fmap, ov, fl, src, nb, S, S, 1, std::max(1, std::min(8, (nb + 63) / 64))));
             }
             LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, (int)S));
@@ -542,7 +561,11 @@ int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const 
         unsigned int stt[8];
         LKCHK(ov_read_status(h, (unsigned int)S, stt));
         bool again = false;
-        const int rc = ov_attempt_end(h, S, attempt, stt, max_scan_pts, (size_t)biggest, fmap, out, &again);
+        const int rc = ov_attempt_end(h, S, attempt, stt, max_scan_pts, (size_t)biggest, fmap, runs ? nullptr : out, &again);
+        if (!again && rc == LK_OK && runs && out) {   // the scans' poses, written where each scan ended (ov_read_status has synchronised)
+            HIPCHK(h, hipMemcpyAsync(out, rg.scan_pose, sizeof(lk_pose) * n_poses, hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+        }
         if (!again) return rc;
         LKCHK(rc);
     }

@@ -56,6 +56,7 @@ struct LkPtSrc {
     const unsigned int* nb;
     int ldb, b;
     const int* b_slot;                  // optional [S]: every slot its OWN bucket index (the scan-resident replay: a launch behind it finds the slots at different buckets); null: b
+    const unsigned int* bstart;         // optional [S + 1]: pt_off is LkRagged's CSR form (slot s owns the flat buckets bstart[s] .. bstart[s+1); nb and ldb unused); null: the padded form
 };
 __device__ __forceinline__ int ov_pt_src(const LkPtSrc& s, unsigned int slot, const lk_point** p) {
     if (!s.pt_off) {
@@ -64,8 +65,8 @@ __device__ __forceinline__ int ov_pt_src(const LkPtSrc& s, unsigned int slot, co
     }
     *p = s.pts;
     const int b = s.b_slot ? s.b_slot[slot] : s.b;
-    if (b < 0 || b >= (int)s.nb[slot]) return 0;
-    const unsigned long long* po = s.pt_off + (size_t)slot * (size_t)(s.ldb + 1);
+    if (b < 0 || b >= (s.bstart ? (int)(s.bstart[slot + 1] - s.bstart[slot]) : (int)s.nb[slot])) return 0;
+    const unsigned long long* po = s.bstart ? s.pt_off + s.bstart[slot] : s.pt_off + (size_t)slot * (size_t)(s.ldb + 1);
     *p = s.pts + po[b];
     return (int)(po[b + 1] - po[b]);
 }

@@ -21,7 +21,14 @@ extern "C++" {
 #ifndef LK_SCAN_WAVES
 #define LK_SCAN_WAVES 1   // waves per SIMD the register allocation aims at
 #endif
-template <bool XID>
+// RUN (lk_batch_replay_overlay_runs_dev; compiled in lk_ovrun.hip, which is this file with LK_OVSCAN_RUNS defined): the slot replays a RUN of consecutive scans,
+// overlay, state, covariance and times surviving the scan boundaries as KILO's members do.  In the CSR tables a run's buckets are one contiguous range and
+// their times absolute, so for addressing and time a run IS a scan (rag_nb / rag_t / rag_pt_off through rg.bstart; cur / fb_b count the run's buckets: a stop
+// behind a scan's last bucket resumes in the next scan).  Scan-aware are the message loop - the owning scan's records only, and no look-back skip at a scan's
+// first bucket: KILO::process gets a new package per call, what the last one left over is never applied - and the pose: at a scan's last bucket, behind the
+// update and before the insert (which may stop the launch: the record is written exactly once), with counters that are zeroed at a scan's first bucket.
+// Everything RUN adds is under `if constexpr`: the two instantiations without it compile to what they were.
+template <bool XID, bool RUN = false>
 __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
     lk_rag_ov_scan_kernel(LkMap base, LkOverlay ov, LkParams pr, LkFilter* filters, const double* __restrict__ Q, LkRagged rg, const lk_point* __restrict__ d_pts,
                           int msg_kind, int* __restrict__ cur, int* __restrict__ fb_b, unsigned int* __restrict__ pending) {
@@ -51,18 +58,26 @@ __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
     ovv.bits = ov.bits + (size_t)slot * ov.bit_words;
     ResidualOut ro;
     ro.h6 = nullptr, ro.z = nullptr, ro.R = nullptr, ro.valid = nullptr, ro.world = nullptr, ro.ids = nullptr;
+    int sc = 0;               // RUN: the scan that owns bucket b ...
+    unsigned int g0 = 0u;     // ... and the run's first flat bucket
+    if constexpr (RUN) sc = rag_run_scan(rg, slot, b), g0 = rg.bstart[slot];
 #pragma unroll 1
     for (; b < nbk; ++b) {
         // ---- front (lk_rag_ov_front_kernel)
         const double tb = T[b];
+        bool first = b == 0, last = false;
+        if constexpr (RUN) {
+            if (g0 + (unsigned int)b >= rg.scan_b[sc + 1]) ++sc;   // (no scan is empty: one step at most)
+            first = g0 + (unsigned int)b == rg.scan_b[sc], last = g0 + (unsigned int)b + 1u == rg.scan_b[sc + 1];
+        }
         if (msg_kind) {
             const size_t mstride = msg_kind == 2 ? 33 : 7;
-            const unsigned int q0 = rg.imu_off[slot], q1 = rg.imu_off[slot + 1];
+            const unsigned int q0 = rg.imu_off[RUN ? sc : slot], q1 = rg.imu_off[(RUN ? sc : slot) + 1];
             for (unsigned int q = q0; q < q1; ++q) {
                 const double* m = rg.imu + mstride * (size_t)q;
                 const double tm = m[0];
                 if (!(tm < tb)) break;
-                if (b > 0 && tm < T[b - 1]) continue;
+                if ((RUN ? !first : b > 0) && tm < T[b - 1]) continue;   // (spelled as it was where RUN is off: `first` there costs two accumulator registers)
                 wave_predict_core(sm, Q, tm - t_upd, tm - t_pred, lane, rg.q_diag != 0);
                 t_pred = tm;
                 if (msg_kind == 2) wave_kin_update_core(sm, rows, m, rg.acc_scale, rg.Rn, rg.kin_noise, lane);
@@ -92,6 +107,8 @@ __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
         }
         const int N = (int)(lane_bcast<28>(totv) + 0.5);
         if (lane == 0) {
+            if constexpr (RUN)
+                if (first) f->n_buckets = 0u, f->n_updates = 0u, f->n_effect = 0ull;   // the counters are the scan's own
             f->last_predict_t = t_pred;
             f->n_buckets += 1;
             f->last_N = N;
@@ -114,6 +131,8 @@ __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
             f->P[e] = sm.P[e];
         }
         if (lane < 36) f->x[lane] = sm.x[lane];
+        if constexpr (RUN)
+            if (last) rag_write_pose(rg.scan_pose + sc, sm.x, f, lane);
         LK_SCAN_PHASE_SYNC();
         dev_bucket_begin_wave(pm);
         for (int i = lane; i < n; i += LK_WAVE) {
@@ -122,7 +141,7 @@ __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
         }
         LK_SCAN_PHASE_SYNC();
         // ---- middle (lk_ov_mid_kernel<true>)
-        const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, b, nullptr};
+        const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, b, nullptr, RUN ? rg.bstart : nullptr};
         ov_materialise_body<true>(base, ov, pr, (unsigned int)slot, 0, 1, lane, LK_WAVE);
         LK_SCAN_PHASE_SYNC();
         for (int i0 = 0; i0 < n; i0 += LK_WAVE) ov_point_geom_body(ov, pr, filters, src, (unsigned int)slot, (i0 + lane) >> 8, (i0 + lane) & 255);
@@ -162,9 +181,18 @@ __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
 }
 }   // extern "C++"
 
+#ifndef LK_OVSCAN_RUNS
 extern "C" int ov_scan_launch(lk_handle* h, bool xid, int S, hipStream_t st, const LkMap& fmap, const LkOverlay& ov, LkFilter* fl, const LkRagged& rg, const lk_point* d_pts,
                               int msg_kind, int* cur, int* fb_b, unsigned int* pending) {
     const auto scan_kernel = xid ? lk_rag_ov_scan_kernel<true> : lk_rag_ov_scan_kernel<false>;
     LAUNCH(h, "rag_ov_scan", hipLaunchKernelGGL(scan_kernel, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, h->d_Q, rg, d_pts, msg_kind, cur, fb_b, pending));
     return LK_OK;
 }
+#else
+extern "C" int ov_run_launch(lk_handle* h, bool xid, int S, hipStream_t st, const LkMap& fmap, const LkOverlay& ov, LkFilter* fl, const LkRagged& rg, const lk_point* d_pts,
+                             int msg_kind, int* cur, int* fb_b, unsigned int* pending) {
+    const auto run_kernel = xid ? lk_rag_ov_scan_kernel<true, true> : lk_rag_ov_scan_kernel<false, true>;
+    LAUNCH(h, "rag_ov_run", hipLaunchKernelGGL(run_kernel, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, h->d_Q, rg, d_pts, msg_kind, cur, fb_b, pending));
+    return LK_OK;
+}
+#endif

@@ -353,6 +353,20 @@ __global__ void __launch_bounds__(256)
         if (most) atomicMax(&stats[2], most);
     }
 }
+// Runs of consecutive scans as slots (lk_batch_replay_overlay_runs_dev): run r = the scans run_off[r] .. run_off[r+1), in the CSR tables the contiguous bucket
+// range run_b[r] .. run_b[r+1); its start time is its first scan's.  stats[5] = most buckets in a run.
+__global__ void __launch_bounds__(256)
+    lk_rag_run_tables_kernel(const unsigned int* __restrict__ bstart, const unsigned int* __restrict__ run_off, const double* __restrict__ t0, int R,
+                             unsigned int* __restrict__ run_b, double* __restrict__ run_t0, unsigned int* __restrict__ stats) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r > R) return;
+    const unsigned int b0 = bstart[run_off[r]];
+    run_b[r] = b0;
+    if (r < R) {
+        run_t0[r] = t0[run_off[r]];
+        atomicMax(&stats[5], bstart[run_off[r + 1]] - b0);
+    }
+}
 // Per-scan summaries of the CSR tables for a LIVE run (lk_run_scans_dev), where every scan is a launch sequence of its own and the host picks
 // the kernel scan by scan: one wave per scan strides over the scan's buckets, wave reductions as above.  sum[s] = { buckets, largest bucket,
 // smallest bucket, first message }; nbp[s] = { buckets, 0 }, the pair a stream kernel reads through LkRagged::nb for "a batch of one scan";

@@ -367,6 +367,20 @@ class KiloPath {
         dev_->check(lk_batch_replay_scans_imu_dev(dev_->h(), d_pts, S, scan_off.data(), t_begin.data(), n_msg.data(), d_imus, out.data()));
         return out;
     }
+    // lk_batch_replay_overlay_runs_dev: whole recorded runs WITH the map insert, run r = the scans run_off[r] .. run_off[r+1) on filter slot r, each
+    // scan one KILO::process - state, covariance, times and the slot's copy-on-write overlay carried across the scan boundaries, the map itself
+    // untouched.  Scans and message records (msg_kind 0 none, 1 lk_imu, 2 lk_kin_imu; n_msg[s] per scan) lie in HBM, as the front ends leave
+    // them.  Priors: lk_batch_set_priors.  Returns one pose per SCAN, its counters that scan's alone.
+    std::vector<lk_pose> replayRunsWithInsertDev(const lk_point* d_pts, const std::vector<uint32_t>& run_off, const std::vector<uint64_t>& scan_off,
+                                                 const std::vector<double>& t_begin, int msg_kind, const std::vector<uint32_t>& n_msg, const void* d_msgs) {
+        const size_t S = t_begin.size();
+        if (run_off.size() < 2 || run_off.back() != S || scan_off.size() != S + 1 || (msg_kind && n_msg.size() != S))
+            throw std::runtime_error("replayRunsWithInsertDev: table sizes differ");
+        std::vector<lk_pose> out(S);
+        dev_->check(lk_batch_replay_overlay_runs_dev(dev_->h(), d_pts, run_off.size() - 1, run_off.data(), scan_off.data(), t_begin.data(), msg_kind,
+                                                     msg_kind ? n_msg.data() : nullptr, d_msgs, out.data()));
+        return out;
+    }
     // lk_run_scans_dev: a recorded run LIVE on the handle's map (KILO::process scan after scan, the map growing), from scans and message records
     // that lie in HBM - msg_kind 0 none, 1 lk_imu, 2 lk_kin_imu; n_msg[s] records per scan at d_msgs.  slide: mapSliding after every scan
     // (lk_run_options), or null.  d_world_out: one 16-byte record per point of d_pts (cloud_down_world), or null.  Returns the poses of the scans

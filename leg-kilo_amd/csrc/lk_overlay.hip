@@ -156,16 +156,65 @@ int lk_overlay_export(lk_handle* h, uint32_t slot, void* blob, size_t* bytes) {
 // ------------------------------------------------------------------ batch replay with a per-scan insert overlay
 // (lk_overlay_kernels.h) KILO::process for every scan of the batch - predict, residual, update AND map insert per bucket (KILO.cc:108-233,
 // :375-395) - each scan on its own copy-on-write overlay of the handle's map, which itself stays untouched.
+
+// The overlay arrays, one entry per pointer of LkOverlay in the order they are allocated: where the pointer lives, whether every slot owns a range of the
+// array or all slots share it, and the BYTES a slot owns (shared: the bytes of the whole array) under the handle's capacities.  The one
+// host-side description of the pools: ov_reserve allocates from it, ov_free releases, ov_at offsets.  The kernels' description of the same layout is ov_slot_map.
+struct OvPool { size_t at; bool shared; size_t (*bytes)(const lk_handle* h); };   // at: offsetof(LkOverlay, the pointer)
+#define OV_POOL(field, shared, ...) {offsetof(LkOverlay, field), shared, [](const lk_handle* h) -> size_t { const LkOverlay& c = h->ov; (void)c; return __VA_ARGS__; }}
+constexpr bool kPerSlot = false, kShared = true;
+static const OvPool kOvPools[] = {
+    OV_POOL(keys, kPerSlot, sizeof(unsigned long long) * c.hash_cap),
+    OV_POOL(planes, kPerSlot, sizeof(lk_plane_rec) * c.nodes_cap), OV_POOL(match, kPerSlot, sizeof(lk_match_rec) * c.nodes_cap), OV_POOL(nodes, kPerSlot, sizeof(lk_node_rec) * c.nodes_cap),
+    OV_POOL(blocks, kPerSlot, sizeof(lk_block_rec) * c.blocks_cap),
+    OV_POOL(counters, kPerSlot, sizeof(unsigned int) * LK_CTR_COUNT),
+    OV_POOL(touched, kPerSlot, sizeof(int) * c.scan_cap), OV_POOL(next, kPerSlot, sizeof(int) * c.scan_cap), OV_POOL(scratch, kPerSlot, sizeof(int) * c.scan_cap), OV_POOL(gidx, kPerSlot, sizeof(int) * c.scan_cap),
+    OV_POOL(groups, kPerSlot, sizeof(LkGroup) * 2 * c.scan_cap),
+    OV_POOL(slots, kPerSlot, sizeof(float4) * LK_SLOTS * c.hash_cap),
+    OV_POOL(free_list, kPerSlot, sizeof(int) * c.blocks_cap), OV_POOL(freed_next, kPerSlot, sizeof(int) * c.blocks_cap),
+    OV_POOL(dirty, kPerSlot, sizeof(unsigned int) * c.hash_cap),
+    OV_POOL(newroot, kShared, sizeof(unsigned int) * (LK_NEWROOT_MASK + 1)), OV_POOL(spec, kShared, sizeof(unsigned int) * LK_SPEC_WORDS),
+    OV_POOL(bits, kPerSlot, sizeof(unsigned int) * c.bit_words),
+    OV_POOL(frozen, kShared, sizeof(unsigned int) * 2 * c.bit_words),
+    OV_POOL(jobs, kPerSlot, sizeof(LkFitJob) * LK_INLINE_GROUPS * c.hash_cap), OV_POOL(jobhdr, kPerSlot, sizeof(int4) * LK_INLINE_GROUPS * c.hash_cap),
+    OV_POOL(sums, kPerSlot, sizeof(LkLeafSum) * c.hash_cap),
+    OV_POOL(base_sums, kShared, sizeof(LkLeafSum) * h->map.max_nodes),
+    OV_POOL(cplx, kPerSlot, sizeof(int) * 2 * c.scan_cap), OV_POOL(ptroot, kPerSlot, sizeof(int) * c.scan_cap),
+};
+#undef OV_POOL
+static_assert(std::is_standard_layout<LkOverlay>::value && sizeof(LkOverlay) == (sizeof(kOvPools) / sizeof(kOvPools[0]) + 3) * sizeof(void*),
+              "25 pointers and five capacities (24 B with the padding): an array added to LkOverlay needs its row in kOvPools");
+// (the pointers are of 25 types: read and written as bytes)
+static char* ov_pool_ptr(const LkOverlay& o, const OvPool& p) { char* q; memcpy(&q, reinterpret_cast<const char*>(&o) + p.at, sizeof(q)); return q; }
+static void ov_pool_set(LkOverlay& o, const OvPool& p, void* q) { memcpy(reinterpret_cast<char*>(&o) + p.at, &q, sizeof(q)); }
+
 void ov_free(lk_handle* h) {
-    LkOverlay& o = h->ov;
-    void* ptrs[] = {o.keys, o.planes, o.match, o.nodes, o.blocks, o.counters, o.touched, o.next, o.scratch, o.gidx, o.groups, o.slots,
-                    o.free_list, o.freed_next, o.dirty, o.newroot, o.spec, o.bits, o.jobs, o.jobhdr, o.frozen, o.sums, o.base_sums, o.cplx, o.ptroot};
-    for (void* q : ptrs)
-        if (q) hipFree(q);
-    memset(&o, 0, sizeof(o));
+    for (const OvPool& p : kOvPools)
+        if (char* q = ov_pool_ptr(h->ov, p)) hipFree(q);
+    memset(&h->ov, 0, sizeof(h->ov));
     h->ov_slots = 0;
     h->ov_pool_bytes = 0;
     h->ov_last_slots = 0;   // nothing of the last replay is left to export / count (lk_overlay_export, lk_overlay_stats)
+}
+// the overlay pools as a group of slots starting at slot s0 sees them: every per-slot array advanced by s0 slots (the kernels index by blockIdx.y)
+static LkOverlay ov_at(const lk_handle* h, size_t s0) {
+    LkOverlay r = h->ov;
+    for (const OvPool& p : kOvPools)
+        if (!p.shared) ov_pool_set(r, p, ov_pool_ptr(r, p) + s0 * p.bytes(h));
+    return r;
+}
+// The table against the kernels' view (ov_slot_map), for fresh pools of S slots: slot b of the group that starts at slot a is slot a + b of the pools, in
+// every array ov_slot_map addresses.  (keys, bits, jobs, jobhdr, sums, ptroot: the kernels index them by hand; the table and LkOverlay's comments are the record.)
+static int ov_check_layout(lk_handle* h, uint32_t S) {
+    const char* bad = nullptr;
+    for (const uint32_t a : {S / 2, S - 1}) {
+        const LkMap x = ov_slot_map(ov_at(h, a), S - 1 - a), y = ov_slot_map(h->ov, S - 1);
+#define OV_SAME(f) if (x.f != y.f) bad = #f;
+        OV_SAME(planes) OV_SAME(match) OV_SAME(nodes) OV_SAME(blocks) OV_SAME(counters) OV_SAME(touched) OV_SAME(heavy) OV_SAME(next) OV_SAME(slots)
+        OV_SAME(scratch) OV_SAME(groups) OV_SAME(gidx) OV_SAME(free_list) OV_SAME(freed_next) OV_SAME(dirty) OV_SAME(newroot) OV_SAME(spec)
+#undef OV_SAME
+    }
+    return bad ? fail(h, LK_ERR_STATE, std::string("overlay pools: the host's table (ov_at) and ov_slot_map disagree on LkMap::") + bad) : LK_OK;
 }
 // LEGKILO_POISON_POOLS (test aid): node records that look plausible - a few points, no children - and point at a block far outside any pool
 __global__ void __launch_bounds__(256) lk_ov_poison_nodes_kernel(lk_node_rec* nodes, size_t n) {
@@ -177,7 +226,7 @@ __global__ void __launch_bounds__(256) lk_ov_poison_nodes_kernel(lk_node_rec* no
 // Per-scan capacities.  lk_overlay_reserve's numbers if given; else, when an earlier replay of scans of this size has left its
 // high-water marks, those + 25 % (pools more than twice that are released and re-made: round 4 reserved n_pts / 6 roots = 110 MB per scan,
 // 113 GB for 1 024 scans, where the bench's scans use 4 700 roots); else a first guess of n_pts / 18 roots.  `grow` (bits of the slots' error
-// word: 1 private root table, 2 nodes, 4 point blocks) doubles what overflowed - the replay is then run again (lk_batch_replay_overlay_dev).
+// word: 1 private root table, 2 nodes, 4 point blocks) doubles what overflowed - the replay is then run again (ov_replay).
 static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t biggest_bucket, const LkMap& fmap, unsigned int grow = 0) {
     // (a run and a single scan of equal point count are not the same shape: a run's overlay keeps growing over its scans)
     const bool hist = h->ov_hw_roots > 0 && h->ov_hw_npts == n_pts_scan && h->ov_hw_runs == h->ov_runs;
@@ -227,36 +276,14 @@ static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t bigges
     h->ov = n;
     const size_t s = S2;
     size_t total = 0;
-    auto get = [&](auto** q, size_t bytes) -> hipError_t {
-        total += bytes;
-        return hipMalloc((void**)q, bytes);
-    };
     hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = get(&o.keys, s * n.hash_cap * sizeof(unsigned long long));
-    if (e == hipSuccess) e = get(&o.planes, s * n.nodes_cap * sizeof(lk_plane_rec));
-    if (e == hipSuccess) e = get(&o.match, s * n.nodes_cap * sizeof(lk_match_rec));
-    if (e == hipSuccess) e = get(&o.nodes, s * n.nodes_cap * sizeof(lk_node_rec));
-    if (e == hipSuccess) e = get(&o.blocks, s * n.blocks_cap * sizeof(lk_block_rec));
-    if (e == hipSuccess) e = get(&o.counters, s * LK_CTR_COUNT * sizeof(unsigned int));
-    if (e == hipSuccess) e = get(&o.touched, s * n.scan_cap * sizeof(int));
-    if (e == hipSuccess) e = get(&o.next, s * n.scan_cap * sizeof(int));
-    if (e == hipSuccess) e = get(&o.scratch, s * n.scan_cap * sizeof(int));
-    if (e == hipSuccess) e = get(&o.gidx, s * n.scan_cap * sizeof(int));
-    if (e == hipSuccess) e = get(&o.groups, s * n.scan_cap * 2 * sizeof(LkGroup));
-    if (e == hipSuccess) e = get(&o.slots, s * n.hash_cap * LK_SLOTS * sizeof(float4));
-    if (e == hipSuccess) e = get(&o.free_list, s * n.blocks_cap * sizeof(int));
-    if (e == hipSuccess) e = get(&o.freed_next, s * n.blocks_cap * sizeof(int));
-    if (e == hipSuccess) e = get(&o.dirty, s * n.hash_cap * sizeof(unsigned int));
-    if (e == hipSuccess) e = get(&o.newroot, (size_t)(LK_NEWROOT_MASK + 1) * sizeof(unsigned int));
-    if (e == hipSuccess) e = get(&o.spec, LK_SPEC_WORDS * sizeof(unsigned int));
-    if (e == hipSuccess) e = get(&o.bits, s * n.bit_words * sizeof(unsigned int));
-    if (e == hipSuccess) e = get(&o.frozen, (size_t)2 * n.bit_words * sizeof(unsigned int));
-    if (e == hipSuccess) e = get(&o.jobs, s * n.hash_cap * LK_INLINE_GROUPS * sizeof(LkFitJob));
-    if (e == hipSuccess) e = get(&o.jobhdr, s * n.hash_cap * LK_INLINE_GROUPS * sizeof(int4));
-    if (e == hipSuccess) e = get(&o.sums, s * n.hash_cap * sizeof(LkLeafSum));
-    if (e == hipSuccess) e = get(&o.base_sums, (size_t)h->map.max_nodes * sizeof(LkLeafSum));
-    if (e == hipSuccess) e = get(&o.cplx, s * n.scan_cap * 2 * sizeof(int));
-    if (e == hipSuccess) e = get(&o.ptroot, s * n.scan_cap * sizeof(int));
+    for (const OvPool& p : kOvPools) {
+        const size_t bytes = (p.shared ? 1 : s) * p.bytes(h);
+        void* q = nullptr;
+        total += bytes;
+        if ((e = hipMalloc(&q, bytes)) != hipSuccess) break;
+        ov_pool_set(o, p, q);
+    }
     if (e == hipSuccess && !h->d_ov_status) e = pool_alloc(h, &h->d_ov_status, 8 * sizeof(unsigned int));
     if (e == hipSuccess && lk_poison_pools()) {
         // test aid: fresh pools hold 0x5a bytes instead of whatever the allocator hands out (usually zeros) - a kernel that trusts a record
@@ -270,6 +297,10 @@ static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t bigges
         snprintf(buf, sizeof(buf), "overlay pools for %u scans (%u root entries / %u child nodes / %u point blocks each) do not fit: %s (lk_overlay_reserve sets smaller per-scan capacities)",
                  S2, n.hash_cap, n.nodes_cap - n.hash_cap, n.blocks_cap, hipGetErrorString(e));
         return fail(h, LK_ERR_CAPACITY, buf);
+    }
+    if (const int rc = ov_check_layout(h, S2)) {   // pools that the kernels would address differently are not kept: the next call fails here again
+        ov_free(h);
+        return rc;
     }
     h->ov_slots = S2;
     h->ov_pool_bytes = total;
@@ -291,27 +322,7 @@ int lk_overlay_reserve(lk_handle* h, uint32_t roots_per_scan, uint32_t nodes_per
 }
 
 }  // extern "C"
-// the overlay pools as a group of slots starting at slot s0 sees them: every per-slot array advanced by s0 slots (the kernels index by blockIdx.y)
-static LkOverlay ov_at(const LkOverlay& o, size_t s0) {
-    LkOverlay r = o;
-    r.keys += s0 * o.hash_cap;
-    r.planes += s0 * o.nodes_cap, r.match += s0 * o.nodes_cap, r.nodes += s0 * o.nodes_cap;
-    r.blocks += s0 * o.blocks_cap;
-    r.counters += s0 * LK_CTR_COUNT;
-    r.touched += s0 * o.scan_cap, r.next += s0 * o.scan_cap, r.scratch += s0 * o.scan_cap, r.gidx += s0 * o.scan_cap;
-    r.groups += s0 * o.scan_cap * 32;
-    r.slots += s0 * o.hash_cap * LK_SLOTS * 4;
-    r.free_list += s0 * o.blocks_cap, r.freed_next += s0 * o.blocks_cap;
-    r.dirty += s0 * o.hash_cap;
-    r.bits += s0 * o.bit_words;
-    r.jobs += s0 * o.hash_cap * LK_INLINE_GROUPS;
-    r.jobhdr += s0 * o.hash_cap * LK_INLINE_GROUPS;
-    r.sums += s0 * o.hash_cap;
-    r.cplx += s0 * o.scan_cap * 2;
-    r.ptroot += s0 * o.scan_cap;
-    return r;   // frozen, base_sums, newroot, spec: shared by all slots
-}
-// ---- what the two replays with insert share (lk_batch_replay_overlay_dev, overlay_ragged_launch): the scaffold around an attempt's launches.
+// ---- what the replays with insert share (lk_batch_replay_overlay_dev, overlay_ragged_launch): ov_replay, the scaffold around an attempt's launches.
 // A scan whose overlay outgrows pools that were sized by this library (first guess, or the previous replay's high-water marks) makes the
 // pools grow and the whole batch run again from its priors - only capacities the caller has set explicitly (lk_overlay_reserve) fail with
 // LK_ERR_CAPACITY.
@@ -358,14 +369,12 @@ static int ov_read_status(lk_handle* h, unsigned int S, unsigned int* stt) {
 static int ov_attempt_end(lk_handle* h, int S, int attempt, const unsigned int* stt, size_t n_pts_scan, size_t biggest, const LkMap& fmap, lk_pose* out, bool* again) {
     const bool growable = !h->ov_want_roots && !(stt[0] & ~(LK_E_HASH_FULL | LK_E_NODES_FULL | LK_E_BLOCKS_FULL)) && attempt < 4;
     *again = stt[0] && growable;
-    if (*again) {
-        HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
-        return ov_reserve(h, (uint32_t)S, n_pts_scan, biggest, fmap, stt[0]);
-    }
     if (!stt[0]) h->ov_hw_roots = stt[3], h->ov_hw_nodes = stt[1], h->ov_hw_blocks = stt[2], h->ov_hw_npts = n_pts_scan, h->ov_hw_runs = h->ov_runs;
-    if (out) LKCHK(fetch_poses(h, out, S));   // no wait without `out`: ov_read_status has synchronised
-    // a refused replay leaves the slots as the caller armed them, not at whatever the buckets before the error made of them
+    if (out && !*again) LKCHK(fetch_poses(h, out, S));   // no wait without `out`: ov_read_status has synchronised
+    // the priors are back whenever a slot has reported an error: the next attempt starts from them, and a refused replay leaves the slots as the
+    // caller armed them, not at whatever the buckets before the error made of them
     if (stt[0]) HIPCHK(h, hipMemcpyAsync(h->d_filters, h->ov_priors.p, sizeof(LkFilter) * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
+    if (*again) return ov_reserve(h, (uint32_t)S, n_pts_scan, biggest, fmap, stt[0]);
     if (stt[0] & LK_E_KEY_RANGE) {
         char buf[200];
         snprintf(buf, sizeof(buf), "overlay replay: a point of slot %u lies in a voxel whose key is outside the +-2^20 range of the private root tables' packed keys (%.0f km from the origin at this voxel size)",
@@ -379,6 +388,30 @@ static int ov_attempt_end(lk_handle* h, int S, int attempt, const unsigned int* 
                  stt[4], stt[0], stt[1], stt[2], stt[3], ov.hash_cap, ov.nodes_cap - ov.hash_cap, ov.blocks_cap);
         return fail(h, LK_ERR_CAPACITY, buf);
     }
+    return LK_OK;
+}
+
+// A whole replay with insert: the attempt loop around `enqueue(fmap)`, which puts ONE attempt's launches behind ov_attempt_begin's - reset of the
+// overlays included - and returns once they are enqueued (an error: the replay returns it, no status is read).  The entries differ in nothing else.
+template <class Enqueue>
+static int ov_replay(lk_handle* h, int S, size_t n_pts_scan, size_t biggest, const double* d_tbegin, double t_begin, lk_pose* out, Enqueue&& enqueue) {
+    LkMap fmap;
+    LKCHK(ov_replay_begin(h, S, n_pts_scan, biggest, &fmap));
+    for (int attempt = 0;; ++attempt) {
+        LKCHK(ov_attempt_begin(h, S, fmap, d_tbegin, t_begin));
+        LKCHK(enqueue(fmap));
+        h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;
+        unsigned int stt[8];
+        LKCHK(ov_read_status(h, (unsigned int)S, stt));
+        bool again = false;
+        const int rc = ov_attempt_end(h, S, attempt, stt, n_pts_scan, biggest, fmap, out, &again);
+        if (!again) return rc;
+        LKCHK(rc);
+    }
+}
+static int ov_reset(lk_handle* h, hipStream_t st, const LkOverlay& ov, int Sg) {
+    const unsigned int per = std::max(std::max(ov.hash_cap, ov.bit_words), (unsigned int)LK_CTR_COUNT);   // root records, bitmap words, counters
+    LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, Sg), dim3(256), 0, st, ov));
     return LK_OK;
 }
 
@@ -410,6 +443,40 @@ static int ov_insert_passes(lk_handle* h, hipStream_t st, const LkMap& fmap, con
     return LK_OK;
 }
 
+// An attempt's launches of the uniform batch: bucket after bucket, every slot group's launches of it on the group's stream.
+// Four slot groups on separate HIP streams (round 6, same box: 15.14 / 13.48 / 13.02 / 12.74 ms with 1 / 2 / 3 / 4 groups, 14.8 / 14.2 with
+// 6 / 8: beyond four streams the queues share hardware): the passes of a bucket are of two kinds - the root pass issues VALU work at
+// 2.8 TB/s of HBM traffic, the others (re-projection, copy-on-write, plane fits) only move bytes - so one group's root pass runs beside
+// the other group's memory passes.  A group is the same launches with every per-slot array offset to its first slot (ov_at).
+static int ov_uniform_launches(lk_handle* h, const SlotGroups& grp, const LkMap& fmap, const lk_point* d_pts, size_t n_pts, double t_begin, const uint32_t* bucket_off,
+                               const double* bucket_dt, const std::vector<size_t>& live) {
+    const auto res_kernel = ov_residual_kernel(h);
+    for (int g = 0; g < grp.n; ++g) LKCHK(ov_reset(h, grp.stream[g], ov_at(h, (size_t)grp.first(g)), grp.count(g)));
+    for (size_t k = 0; k < live.size(); ++k)
+        for (int g = 0; g < grp.n; ++g) {
+            const int s0 = grp.first(g), Sg = grp.count(g);   // this group's slots
+            const LkOverlay ov = ov_at(h, (size_t)s0);
+            hipStream_t st = grp.stream[g];
+            LkFilter* fl = h->d_filters + s0;
+            double* parts = h->d_partials + (size_t)s0 * h->part_stride;
+            const size_t b = live[k];
+            const int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
+            const double t = t_begin + bucket_dt[b];
+            const int nblk = (nb + LK_RB - 1) / LK_RB;
+            const LkPtSrc src = {d_pts + (size_t)s0 * n_pts + bucket_off[b], n_pts, nb, nullptr, nullptr, 0, 0, nullptr};
+            if (k == 0) LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q, t, 2));
+            LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, Sg), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, parts, h->part_stride));
+            LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q, 0.0, 1));
+            LKCHK(ov_insert_passes(h, st, fmap, ov, fl, src, nb, grp.S, Sg, 4, 12));
+            LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(Sg, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, Sg));   // (1 024 slots, workgroups 8 / 32 / 128 / 256 / 512: 0.54 / 0.26 / 0.15 / 0.17 / 0.16 ms per batch; a workgroup or more per slot: 0.34)
+            if (k + 1 < live.size())
+                LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q,
+                                                        t_begin + bucket_dt[live[k + 1]], 2));
+        }
+    HIPCHK(h, hipGetLastError());
+    return LK_OK;
+}
+
 extern "C" {
 int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, size_t n_pts, double t_begin, const uint32_t* bucket_off,
                                 const double* bucket_dt, size_t n_buckets, lk_pose* out) {
@@ -428,54 +495,11 @@ int lk_batch_replay_overlay_dev(lk_handle* h, const lk_point* d_pts, size_t n_sc
         return LK_OK;
     }));
     if (live.empty()) return fail(h, LK_ERR_INVALID, "empty scans");
-    LkMap fmap;
-    LKCHK(ov_replay_begin(h, S, n_pts, biggest, &fmap));
-    const auto res_kernel = ov_residual_kernel(h);
-    // Four slot groups on separate HIP streams (round 6, same box: 15.14 / 13.48 / 13.02 / 12.74 ms with 1 / 2 / 3 / 4 groups, 14.8 / 14.2 with
-    // 6 / 8: beyond four streams the queues share hardware): the passes of a bucket are of two kinds - the root pass issues VALU work at
-    // 2.8 TB/s of HBM traffic, the others (re-projection, copy-on-write, plane fits) only move bytes - so one group's root pass runs beside
-    // the other group's memory passes.  A group is the same launches with every per-slot array offset to its first slot (ov_at).
     const SlotGroups grp(h, S, kOverlayGroups, kOverlayGroupSlots);
-    for (int attempt = 0;; ++attempt) {
-        LKCHK(ov_attempt_begin(h, S, fmap, nullptr, t_begin));
+    return ov_replay(h, S, n_pts, biggest, nullptr, t_begin, out, [&](const LkMap& fmap) -> int {
         LKCHK(grp.fork());
-        const auto enqueue_all = [&]() -> int {   // bucket after bucket, every group's launches of it
-            const unsigned int per = std::max(std::max(h->ov.hash_cap, h->ov.bit_words), (unsigned int)LK_CTR_COUNT);   // root records, bitmap words, counters
-            for (int g = 0; g < grp.n; ++g)
-                LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, grp.count(g)), dim3(256), 0, grp.stream[g], ov_at(h->ov, (size_t)grp.first(g))));
-            for (size_t k = 0; k < live.size(); ++k)
-                for (int g = 0; g < grp.n; ++g) {
-                    const int s0 = grp.first(g), Sg = grp.count(g);   // this group's slots
-                    const LkOverlay ov = ov_at(h->ov, (size_t)s0);
-                    hipStream_t st = grp.stream[g];
-                    LkFilter* fl = h->d_filters + s0;
-                    double* parts = h->d_partials + (size_t)s0 * h->part_stride;
-                    const size_t b = live[k];
-                    const int nb = (int)(bucket_off[b + 1] - bucket_off[b]);
-                    const double t = t_begin + bucket_dt[b];
-                    const int nblk = (nb + LK_RB - 1) / LK_RB;
-                    const LkPtSrc src = {d_pts + (size_t)s0 * n_pts + bucket_off[b], n_pts, nb, nullptr, nullptr, 0, 0, nullptr};
-                    if (k == 0) LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q, t, 2));
-                    LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, Sg), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, parts, h->part_stride));
-                    LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, nblk * (LK_RB / LK_WAVE), h->part_stride, t, h->d_Q, 0.0, 1));
-                    LKCHK(ov_insert_passes(h, st, fmap, ov, fl, src, nb, S, Sg, 4, 12));
-                    LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(Sg, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, Sg));   // (1 024 slots, workgroups 8 / 32 / 128 / 256 / 512: 0.54 / 0.26 / 0.15 / 0.17 / 0.16 ms per batch; a workgroup or more per slot: 0.34)
-                    if (k + 1 < live.size())
-                        LAUNCH(h, "predict", hipLaunchKernelGGL(lk_update_wave_kernel, dim3(Sg), dim3(LK_WAVE), 0, st, fl, parts, 0, h->part_stride, 0.0, h->d_Q,
-                                                                t_begin + bucket_dt[live[k + 1]], 2));
-                }
-            HIPCHK(h, hipGetLastError());
-            return LK_OK;
-        };
-        LKCHK(grp.join(enqueue_all()));
-        h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;
-        unsigned int stt[8];
-        LKCHK(ov_read_status(h, (unsigned int)S, stt));
-        bool again = false;
-        const int rc = ov_attempt_end(h, S, attempt, stt, n_pts, biggest, fmap, out, &again);
-        if (!again) return rc;
-        LKCHK(rc);
-    }
+        return grp.join(ov_uniform_launches(h, grp, fmap, d_pts, n_pts, t_begin, bucket_off, bucket_dt, live));
+    });
 }
 
 int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64_t* scan_off, const uint32_t* n_buckets,
@@ -487,91 +511,91 @@ int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size
     return ragged_replay(h, d_pts, n_scans, scan_off, n_buckets, bucket_off, bucket_dt, t_begin, msg_kind ? n_msg : nullptr, msgs, msg_kind, out, true);
 }
 }  // extern "C"
-// The ragged batch WITH insert, bucket INDEX after bucket index over all scans (one launch of every pass per index, grids sized by that
-// index's longest bucket; a scan that has run out of buckets leaves every launch at once): per index b - the scan's messages up to the
-// bucket's time + predict (lk_rag_advance_kernel), residual with the overlay lookup, update, then the insert passes of
-// lk_batch_replay_overlay_dev on each scan's own bucket (LkPtSrc).  One stream: a recorded run's buckets are small, the launches are what it costs.
-// Runs (rg.run_scan, CSR tables: lk_batch_replay_overlay_runs_dev): a slot is a run of scans - for addressing and time one long scan of ldb buckets at most,
-// max_scan_pts its points; the kernels know where its scans end (rag_bucket), and `out` takes the n_poses records of rg.scan_pose instead of the slots' poses.
+// The ragged batch WITH insert on one stream (a recorded run's buckets are small, the launches are what it costs): behind the reset of the overlays an
+// attempt's launches go one of three ways.  Runs (rg.run_scan, CSR tables: lk_batch_replay_overlay_runs_dev): a slot is a run of scans - for addressing and
+// time one long scan of ldb buckets at most, max_scan_pts its points; the kernels know where its scans end (rag_bucket), and `out` takes the n_poses
+// records of rg.scan_pose instead of the slots' poses.
+// 1. Buckets of <= LK_SCAN_WAVE_MAX points, scan-resident: one wave per scan (run) works through its buckets in ONE launch (lk_ovscan.hip, lk_ovrun.hip) and
+// stops where a bucket leaves fallback items; those run as a launch of their own, then the resident kernel picks every stopped scan up again.
+static int ov_rag_resident_rounds(lk_handle* h, int S, const LkMap& fmap, const LkRagged& rg, const lk_point* d_pts, int msg_kind, size_t ldb) {
+    hipStream_t st = h->stream;
+    const bool xid = h->pr.ext_identity && lk_xid_enabled(), runs = rg.run_scan != nullptr;
+    // [S] next bucket of every scan, [S] the bucket whose fallback items wait, one counter: scans stopped by fallback items in the last launch
+    LKCHK(reserve(h, h->ov_res, sizeof(int) * (2 * (size_t)S + 4)));
+    int* cur = static_cast<int*>(h->ov_res.p);
+    int* fb_b = cur + S;
+    unsigned int* pending = reinterpret_cast<unsigned int*>(cur + 2 * (size_t)S);
+    HIPCHK(h, hipMemsetAsync(cur, 0, sizeof(int) * (2 * (size_t)S + 4), st));
+    const LkPtSrc fsrc = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, 0, fb_b, rg.bstart};
+    unsigned int rounds = 0;
+    for (;; ++rounds) {
+        if (runs) LKCHK(ov_run_launch(h, xid, S, st, fmap, h->ov, h->d_filters, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovrun.hip
+        else LKCHK(ov_scan_launch(h, xid, S, st, fmap, h->ov, h->d_filters, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovscan.hip
+        unsigned int n_pending = 0;
+        HIPCHK(h, hipMemcpyAsync(&n_pending, pending, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (!n_pending) break;
+        if (rounds > ldb + 1) return fail(h, LK_ERR_STATE, "scan-resident overlay replay: more fallback rounds than buckets");
+        HIPCHK(h, hipMemsetAsync(pending, 0, sizeof(unsigned int), st));
+        LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(S, 128)), dim3(LK_MB), 0, st, h->ov, h->pr, h->d_filters, fsrc, S));
+    }
+    h->ov_res_rounds = rounds + 1;
+    return LK_OK;
+}
+// 2. The same buckets launch by launch, bucket INDEX after bucket index over all scans (a scan that has run out of buckets leaves every launch at once): front
+// (the scan's messages up to the bucket's time, predict, residual, update, re-projection), mid, tail - at one wave per slot: 29.2 -> 26.4 ms against four launches.
+static int ov_rag_small_launches(lk_handle* h, int S, const LkMap& fmap, const LkRagged& rg, const lk_point* d_pts, int msg_kind, size_t ldb) {
+    const LkOverlay& ov = h->ov;
+    const auto front = (h->pr.ext_identity && lk_xid_enabled()) ? lk_rag_ov_front_kernel<true> : lk_rag_ov_front_kernel<false>;
+    for (size_t b = 0; b < ldb; ++b) {
+        const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr, rg.bstart};
+        LAUNCH(h, "rag_ov_front", hipLaunchKernelGGL(front, dim3(S), dim3(LK_WAVE), 0, h->stream, fmap, ov, h->pr, h->d_filters, h->d_Q, rg, d_pts, (int)b, msg_kind));
+        LAUNCH(h, "ov_mid", hipLaunchKernelGGL(lk_ov_mid_kernel<true>, dim3(S), dim3(LK_MB), 0, h->stream, fmap, ov, h->pr, h->d_filters, src));
+        LAUNCH(h, "ov_tail", hipLaunchKernelGGL(lk_ov_tail_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, fmap, ov, h->pr, h->d_filters, src));
+        LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(S, 128)), dim3(LK_MB), 0, h->stream, ov, h->pr, h->d_filters, src, S));
+    }
+    return LK_OK;
+}
+// 3. Larger buckets, index after index: lk_rag_advance_kernel, then the chain of lk_batch_replay_overlay_dev on each scan's own bucket (LkPtSrc), grids sized
+// by that index's longest bucket (max_n; null: `biggest` for all); runs: the pose tap behind the update.
+static int ov_rag_large_launches(lk_handle* h, int S, const LkMap& fmap, const LkRagged& rg, const lk_point* d_pts, int msg_kind, size_t ldb, const int* max_n, int biggest) {
+    const LkOverlay& ov = h->ov;
+    const auto res_kernel = ov_residual_kernel(h);
+    for (size_t b = 0; b < ldb; ++b) {
+        const int nb = std::max(1, max_n ? max_n[b] : biggest);
+        const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr, rg.bstart};
+        const int nblk = (nb + LK_RB - 1) / LK_RB;
+        LAUNCH(h, "rag_advance", hipLaunchKernelGGL(lk_rag_advance_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, h->d_Q, rg, (int)b, msg_kind));
+        LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, S), dim3(LK_RB), 0, h->stream, fmap, ov, h->pr, h->d_filters, src, h->d_partials, h->part_stride));
+        LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, h->d_partials, h->part_stride, h->d_Q, rg, (int)b, 1));
+        if (rg.run_scan) LAUNCH(h, "rag_pose_tap", hipLaunchKernelGGL(lk_rag_pose_tap_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, rg, (int)b));
+        LKCHK(ov_insert_passes(h, h->stream, fmap, ov, h->d_filters, src, nb, S, S, 1, std::max(1, std::min(8, (nb + 63) / 64))));
+        LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(S, 128)), dim3(LK_MB), 0, h->stream, ov, h->pr, h->d_filters, src, S));
+    }
+    return LK_OK;
+}
 int overlay_ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S_, const LkRagged& rg, const double* d_tbegin, int biggest, size_t ldb,
                                  const int* max_n, size_t max_scan_pts, int msg_kind, lk_pose* out, size_t n_poses) {
     const int S = (int)S_;
-    const bool runs = rg.run_scan != nullptr;
+    const bool runs = rg.run_scan != nullptr, small = biggest <= LK_SCAN_WAVE_MAX;
     h->ov_runs = runs;
-    LkMap fmap;
-    LKCHK(ov_replay_begin(h, S, max_scan_pts, (size_t)biggest, &fmap));
-    hipStream_t st = h->stream;
-    const bool xid = h->pr.ext_identity && lk_xid_enabled();
-    const auto res_kernel = ov_residual_kernel(h);
-    for (int attempt = 0;; ++attempt) {
-        const LkOverlay ov = h->ov;
-        LkFilter* fl = h->d_filters;
-        LKCHK(ov_attempt_begin(h, S, fmap, d_tbegin, 0.0));
-        {
-            const unsigned int per = std::max(std::max(ov.hash_cap, ov.bit_words), (unsigned int)LK_CTR_COUNT);
-            LAUNCH(h, "ov_reset", hipLaunchKernelGGL(lk_ov_reset_kernel, dim3((per + 255) / 256, S), dim3(256), 0, st, ov));
-        }
+    LKCHK(ov_replay(h, S, max_scan_pts, (size_t)biggest, d_tbegin, 0.0, runs ? nullptr : out, [&](const LkMap& fmap) -> int {
+        LKCHK(ov_reset(h, h->stream, h->ov, S));
         const bool rag_resident = getenv("LEGKILO_RAG_RESIDENT") == nullptr || atoi(getenv("LEGKILO_RAG_RESIDENT")) != 0;   // 0: launch by launch (the bit-identity reference of the tests: read at every call)
         h->ov_res_rounds = 0;
-        const bool resident = rag_resident && biggest <= LK_SCAN_WAVE_MAX && (!rg.bstart || runs);
-        if (resident) {
-            // [S] next bucket of every scan, [S] the bucket whose fallback items wait, one counter: scans stopped by fallback items in the last launch
-            LKCHK(reserve(h, h->ov_res, sizeof(int) * (2 * (size_t)S + 4)));
-            int* cur = static_cast<int*>(h->ov_res.p);
-            int* fb_b = cur + S;
-            unsigned int* pending = reinterpret_cast<unsigned int*>(cur + 2 * (size_t)S);
-            HIPCHK(h, hipMemsetAsync(cur, 0, sizeof(int) * (2 * (size_t)S + 4), st));
-            const LkPtSrc fsrc = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, 0, fb_b, rg.bstart};
-            unsigned int rounds = 0;
-            for (;; ++rounds) {
-                if (runs) LKCHK(ov_run_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovrun.hip
-                else LKCHK(ov_scan_launch(h, xid, S, st, fmap, ov, fl, rg, d_pts, msg_kind, cur, fb_b, pending));   // lk_ovscan.hip
-                unsigned int n_pending = 0;
-                HIPCHK(h, hipMemcpyAsync(&n_pending, pending, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-                HIPCHK(h, hipStreamSynchronize(st));
-                if (!n_pending) break;
-                if (rounds > ldb + 1) return fail(h, LK_ERR_STATE, "scan-resident overlay replay: more fallback rounds than buckets");
-                HIPCHK(h, hipMemsetAsync(pending, 0, sizeof(unsigned int), st));
-                LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, fsrc, (int)S));
-            }
-            h->ov_res_rounds = rounds + 1;
-        }
-        for (size_t b = 0; b < (resident ? 0 : ldb); ++b) {
-            const int nb = std::max(1, max_n ? max_n[b] : biggest);
-            const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr, rg.bstart};
-            if (biggest <= LK_SCAN_WAVE_MAX) {
-                // buckets of <= LK_SCAN_WAVE_MAX points: three launches per bucket index (front, mid, tail); the tail at one wave per slot:
-                // 29.2 -> 26.4 ms against four (fewer waves to dispatch)
-                const auto front = xid ? lk_rag_ov_front_kernel<true> : lk_rag_ov_front_kernel<false>;
-                LAUNCH(h, "rag_ov_front", hipLaunchKernelGGL(front, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, h->d_Q, rg, d_pts, (int)b, msg_kind));
-                LAUNCH(h, "ov_mid", hipLaunchKernelGGL(lk_ov_mid_kernel<true>, dim3(S), dim3(LK_MB), 0, st, fmap, ov, h->pr, fl, src));
-                LAUNCH(h, "ov_tail", hipLaunchKernelGGL(lk_ov_tail_kernel, dim3(S), dim3(LK_WAVE), 0, st, fmap, ov, h->pr, fl, src));
-            } else {
-                const int nblk = (nb + LK_RB - 1) / LK_RB;
-                LAUNCH(h, "rag_advance", hipLaunchKernelGGL(lk_rag_advance_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_Q, rg, (int)b, msg_kind));
-                LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, S), dim3(LK_RB), 0, st, fmap, ov, h->pr, fl, src, h->d_partials, h->part_stride));
-                LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, h->d_partials, h->part_stride, h->d_Q, rg, (int)b, 1));
-                if (runs) LAUNCH(h, "rag_pose_tap", hipLaunchKernelGGL(lk_rag_pose_tap_kernel, dim3(S), dim3(LK_WAVE), 0, st, fl, rg, (int)b));
-                LKCHK(ov_insert_passes(h, st, fmap, ov, fl, src, nb, S, S, 1, std::max(1, std::min(8, (nb + 63) / 64))));
-            }
-            LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min((int)S, 128)), dim3(LK_MB), 0, st, ov, h->pr, fl, src, (int)S));
-        }
+        if (rag_resident && small && (!rg.bstart || runs)) LKCHK(ov_rag_resident_rounds(h, S, fmap, rg, d_pts, msg_kind, ldb));
+        else if (small) LKCHK(ov_rag_small_launches(h, S, fmap, rg, d_pts, msg_kind, ldb));
+        else LKCHK(ov_rag_large_launches(h, S, fmap, rg, d_pts, msg_kind, ldb, max_n, biggest));
         HIPCHK(h, hipGetLastError());
-        h->ov_last_slots = (uint32_t)S, h->ov_gen = h->map_gen;
-        unsigned int stt[8];
-        LKCHK(ov_read_status(h, (unsigned int)S, stt));
-        bool again = false;
-        const int rc = ov_attempt_end(h, S, attempt, stt, max_scan_pts, (size_t)biggest, fmap, runs ? nullptr : out, &again);
-        if (!again && rc == LK_OK && runs && out) {   // the scans' poses, written where each scan ended (ov_read_status has synchronised)
-            HIPCHK(h, hipMemcpyAsync(out, rg.scan_pose, sizeof(lk_pose) * n_poses, hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipStreamSynchronize(st));
-        }
-        if (!again) return rc;
-        LKCHK(rc);
+        return LK_OK;
+    }));
+    if (runs && out) {   // the scans' poses, written where each scan ended (the replay has synchronised)
+        HIPCHK(h, hipMemcpyAsync(out, rg.scan_pose, sizeof(lk_pose) * n_poses, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+    return LK_OK;
 }
 extern "C" {
-
 int lk_overlay_stats(lk_handle* h, uint32_t* max_roots, uint32_t* max_nodes, uint32_t* max_blocks) {
     CHECK_H(h);
     if (!h->ov_last_slots || !h->ov.counters) return fail(h, LK_ERR_STATE, "no overlay replay's pools are held by this handle (none has run, or lk_overlay_reserve released them)");
@@ -597,6 +621,4 @@ int lk_overlay_pool_bytes(lk_handle* h, uint64_t* bytes, uint32_t* root_entries,
     if (blocks) *blocks = h->ov.blocks_cap;
     return LK_OK;
 }
-
-
 }  // extern "C"

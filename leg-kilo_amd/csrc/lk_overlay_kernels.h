@@ -71,7 +71,7 @@ __device__ __forceinline__ int ov_pt_src(const LkPtSrc& s, unsigned int slot, co
     return (int)(po[b + 1] - po[b]);
 }
 
-// The overlay pools of all slots, passed by value.  Slot s owns element range [s * cap, (s + 1) * cap) of every array.
+// The overlay pools of all slots, passed by value.  Slot s owns element range [s * cap, (s + 1) * cap) of every [S][cap] array; the host allocates and offsets them from ONE table (kOvPools, lk_overlay.hip), which ov_slot_map below is checked against.
 // Private root table of a slot: open addressing over PACKED 64-bit keys (3 x 21 bits), and the root's node id IS its table index -
 // node records [0, hash_cap) of the slot are its roots, children are allocated from hash_cap upwards.  A key is claimed with ONE
 // relaxed 64-bit compare-and-swap and nothing has to be published to the other lanes: no lock word, no fences (an agent-scope
@@ -79,22 +79,22 @@ __device__ __forceinline__ int ov_pt_src(const LkPtSrc& s, unsigned int slot, co
 // pass spun on one per point and took 14 ms per launch where this one takes a fraction of a millisecond).
 struct LkOverlay {
     unsigned long long* keys;    // [S][hash_cap]
-    lk_plane_rec* planes;
-    lk_match_rec* match;
+    lk_plane_rec* planes;        // [S][nodes_cap]
+    lk_match_rec* match;         // [S][nodes_cap]
     lk_node_rec* nodes;          // [S][nodes_cap], nodes_cap = hash_cap + children
-    lk_block_rec* blocks;
+    lk_block_rec* blocks;        // [S][blocks_cap]
     unsigned int* counters;      // [S][LK_CTR_COUNT]
     int* touched;                // [S][scan_cap]
     int* next;                   // [S][scan_cap]
     int* scratch;                // [S][scan_cap]
     int* gidx;                   // [S][scan_cap]
-    int* groups;                 // [S][2 * scan_cap * 16]  (LkGroup = 16 ints)
+    int* groups;                 // [S][2 * scan_cap] x LkGroup (16 ints)
     int* slots;                  // [S][hash_cap][LK_SLOTS] x float4 {x, y, z, index}: the points queued on a root in the current bucket (only roots queue points)
     int* free_list;              // [S][blocks_cap]
     int* freed_next;             // [S][blocks_cap]
     unsigned int* dirty;         // [S][hash_cap] (roots only; epoch 0)
-    unsigned int* newroot;       // one shared dummy table (epoch 0: only ever written with 0)
-    unsigned int* spec;          // one shared dummy
+    unsigned int* newroot;       // [LK_NEWROOT_MASK + 1], shared: one dummy table (epoch 0: only ever written with 0)
+    unsigned int* spec;          // [LK_SPEC_WORDS], shared: one dummy
     unsigned int* bits;          // [S][bit_words]: bit c = the slot has a private root at base grid cell c
     unsigned int* frozen;        // [2 * bit_words], shared by all slots: TWO bits per grid cell c of the BASE map (lk_ov_frozen_bits_kernel): bit 0 = its voxel is a
                                  // frozen leaf (UpdateOctoTree ignores the point), bit 1 = its voxel takes the point AT THE ROOT (a live leaf, or not initialised

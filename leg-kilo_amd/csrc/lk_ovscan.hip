@@ -1,6 +1,6 @@
 // lk_ovscan.hip - the scan-resident kernel of the recorded-run batch replay WITH insert (lk_batch_replay_overlay_ragged_dev, small buckets), a translation
 // unit of its own: its two instantiations take as long to compile as the rest of the overlay unit (see lk_internal.h; the host loop around it -
-// rounds, fallback launches - is overlay_ragged_launch in lk_overlay.hip).
+// rounds, fallback launches - is ov_rag_resident_rounds in lk_overlay.hip).
 #define LK_TU_OVSCAN 1
 #include "lk_internal.h"
 

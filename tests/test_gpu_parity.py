@@ -1493,6 +1493,93 @@ def test_batch_replay_overlay(scene, oracle_lib, hip_lib, case):
     o.close()
 
 
+def test_overlay_pool_capacities(scene, oracle_lib, hip_lib):
+    """How the overlay pools are sized and laid out, on test_batch_replay_overlay's `tiny` batch (5 slots x 800 points, 12 buckets, young map), as
+    lk_overlay_pool_bytes reports it - (bytes, root-table entries, child nodes, point blocks per scan):
+      (a) first replay on a fresh handle - the first guess: roots = min(max(2048, n / 18), max(1024, n)) = 1024, table = next_pow2(roots + roots / 4),
+          children = roots / 2, blocks = roots;
+      (b) the same replay again - the history rule on (a)'s high-water marks (lk_overlay_stats): roots = hw + hw / 4 + 64, children = c + c / 4 + 256
+          with c = nodes - roots, blocks = hw + hw / 4 + 64; pools more than twice that (table), or 2 x + 1024 (blocks), are replaced by exactly those
+          values, else every capacity is max(old, new);
+      (c) after lk_overlay_reserve(2048, 4096, 2048): table 4096, children 4096 - 2048, blocks 2048;
+      (d) the pools' bytes are affine in the slot count: handles of 1, 2 and 3 slots with the same explicit reserve differ by one slot's bytes each.
+    States, covariances and poses of (b) and (c) are bit-equal to (a)'s: what a scan computes does not depend on where its pools lie."""
+    S, n_pts, nb = 5, 800, 12
+    o = oracle_lib.Oracle(scene.cfg(), imu_mode_only=True)
+    t0 = 21.0
+    scenes.first_frame(o, scene, t0, scenes.init_filter(o, scene, t0), dense=20000)
+    o.map_import(o.map_export())
+    blob = o.map_export()
+    o.close()
+    rng = np.random.default_rng(515151)
+    xs, Ps, scans = [], [], []
+    for s in range(S):
+        tb = t0 + 0.5 + 0.21 * s
+        pts = synth.dense_scan(scene.world, scene.traj, tb, scene.P, n=n_pts, n_buckets=nb, seed_scan=7005 + s, seed_noise=7106 + s)
+        curv = pts["curvature"].copy()
+        pts = pts[rng.permutation(len(pts))]
+        pts["curvature"] = curv
+        scans.append(pts)
+        xs.append(synth.initial_state(scene.traj, tb, scene.P, rng, 0.02, 0.5))
+        Ps.append(1e-4 * np.eye(30))
+    off, dt = synth.buckets_of(scans[0])
+    allpts = np.concatenate(scans)
+
+    def replay(g, d_pts, n):
+        g.batch_set_priors(np.array(xs[:n]), np.array(Ps[:n]))
+        poses = g.batch_replay_overlay_dev(d_pts, n, n_pts, 0.0, off, dt)
+        X, P = g.batch_get_states(0, n)
+        return X, P, bytes(poses)
+
+    def same_bits(a, b):
+        return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+
+    def next_pow2(v):
+        return 1 << max(0, int(v) - 1).bit_length()
+
+    g = hip_lib.LegKiloHip(scene.cfg(n_slots=S))
+    g.map_import(blob)
+    g.init_process_cov_q()
+    d_pts = g.device_malloc(allpts.nbytes)
+    g.h2d(d_pts, allpts)
+    first = replay(g, d_pts, S)
+    caps_a = g.overlay_pool_bytes()[1:]
+    hw_roots, hw_nodes, hw_blocks = g.overlay_stats()
+    print("overlay pools (a) first guess:", g.overlay_pool_bytes(), "high-water marks (roots, nodes, blocks):", (hw_roots, hw_nodes, hw_blocks))
+    assert caps_a == (2048, 512, 1024)
+    second = replay(g, d_pts, S)
+    roots = hw_roots + hw_roots // 4 + 64
+    child = max(hw_nodes - hw_roots, 0)
+    new = (next_pow2(roots + roots // 4), child + child // 4 + 256, hw_blocks + hw_blocks // 4 + 64)
+    oversized = caps_a[0] > 2 * new[0] or caps_a[2] > 2 * new[2] + 1024
+    want_b = new if oversized else tuple(max(x, y) for x, y in zip(caps_a, new))
+    print("overlay pools (b) history rule:", g.overlay_pool_bytes(), "rule:", new, "replaced" if oversized else "kept / grown")
+    assert g.overlay_pool_bytes()[1:] == want_b
+    assert same_bits(first, second)
+    g.overlay_reserve(2048, 4096, 2048)
+    third = replay(g, d_pts, S)
+    print("overlay pools (c) explicit:", g.overlay_pool_bytes())
+    assert g.overlay_pool_bytes()[1:] == (4096, 2048, 2048)
+    assert same_bits(first, third)
+    g.device_free(d_pts)
+    g.close()
+    total = []
+    for n in (1, 2, 3):
+        g = hip_lib.LegKiloHip(scene.cfg(n_slots=n))
+        g.map_import(blob)
+        g.init_process_cov_q()
+        g.overlay_reserve(2048, 4096, 2048)
+        d_pts = g.device_malloc(allpts.nbytes)
+        g.h2d(d_pts, allpts)
+        replay(g, d_pts, n)
+        assert g.overlay_pool_bytes()[1:] == (4096, 2048, 2048)
+        total.append(g.overlay_pool_bytes()[0])
+        g.device_free(d_pts)
+        g.close()
+    print("overlay pools (d) bytes for 1, 2, 3 slots:", total)
+    assert total[1] - total[0] == total[2] - total[1] > 0, total
+
+
 @pytest.mark.parametrize("mode", ["plain", "imu", "kin"])
 def test_batch_replay_overlay_ragged_scan_resident(scene, oracle_lib, hip_lib, mode, monkeypatch):
     """The scan-resident form of lk_batch_replay_overlay_ragged_dev (every bucket <= 512 points: ONE launch carries a scan through its whole bucket

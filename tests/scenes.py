@@ -34,6 +34,15 @@ class Scene:
         return config.make_config(self.P, **caps)
 
 
+def rand_spd(rng, scale=1e-4):
+    A = rng.normal(size=(30, 30))
+    return scale * (A @ A.T / 30 + 0.1 * np.eye(30))
+
+
+def rel_err(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / (np.abs(np.asarray(b)).max() + 1e-300))
+
+
 def xyz_of(pts):
     return np.stack([pts["x"], pts["y"], pts["z"]], axis=1).astype(np.float32)
 

@@ -10,19 +10,11 @@ import pytest
 
 import scenes
 from legkilo_amd import abi, config, synth
+from scenes import rand_spd, rel_err
 
 pytestmark = pytest.mark.gpu
 
 CAPS = dict(max_roots=1 << 16, max_nodes=1 << 17, max_point_blocks=1 << 16, max_scan_points=1 << 17)
-
-
-def rand_spd(rng, scale=1e-4):
-    A = rng.normal(size=(30, 30))
-    return scale * (A @ A.T / 30 + 0.1 * np.eye(30))
-
-
-def rel_err(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / (np.abs(np.asarray(b)).max() + 1e-300))
 
 
 @pytest.fixture(scope="module")
@@ -2076,7 +2068,7 @@ def test_batch_replay_ragged_leg_fusion(oracle_lib, hip_lib):
     IMU messages are applied between its time buckets (predictUpdateKinImu, KILO.cc:260-314; updateByKinImu, eskf.cc:137-145:
     6 IMU rows + 3 rows per foot in contact, 6..18 rows) inside the one-wave-per-scan kernel (wave_kin_update_core).  diter.yaml
     parameters.  Each scan equals the oracle's process_scan(..., kins=) on that scan alone: counts exact, x to 1e-8, P to 1e-6;
-    the message mix covers 0..4 contacts (M = 6..18)."""
+    the message mix covers 0..4 contacts (M = 6, 9, 12, 15, 18)."""
     sc = scenes.Scene(params=dict(config.DITER, voxel_grid_resolution=0.3), **CAPS)
     o = oracle_lib.Oracle(sc.cfg(), imu_mode_only=False)
     t0 = 2.0
@@ -2101,9 +2093,10 @@ def test_batch_replay_ragged_leg_fusion(oracle_lib, hip_lib):
         if s == 2:
             k["contact"][::4] = 0          # flight phase: IMU rows only (M = 6)
             k["contact"][1::4] = [1, 0, 0, 0]
+            k["contact"][2::4] = [0, 1, 1, 1]   # three feet down (M = 15): FL's rows are block 0
         seen_m |= set(int(6 + 3 * c.sum()) for c in (k["contact"] != 0))
         kins.append(k)
-    assert seen_m >= {6, 9, 12, 18}, seen_m
+    assert seen_m == {6, 9, 12, 15, 18}, seen_m
     g = hip_lib.LegKiloHip(sc.cfg(n_slots=S))
     g.map_import(blob)
     g.init_process_cov_q()

@@ -24,6 +24,7 @@ where neither /root/reference nor a prebuilt oracle/_ref exists.
 import numpy as np
 import pytest
 
+import msgcases
 import oracle_binding as ob
 import offconfig
 import scenes
@@ -142,6 +143,22 @@ def test_update_by_imu_and_kin_imu(pair):
         (xo, Po), (xr, Pr) = o.get_state(), r.get_state()
         assert np.allclose(xo, xr, rtol=1e-9, atol=1e-12), (trial, np.abs(xo - xr).max())
         assert np.allclose(Po, Pr, rtol=1e-7, atol=1e-13), (trial, np.abs(Po - Pr).max())
+    # the rows KILO.cc:267-309 builds, for every contact mask: M = 6, 9, 12, 15, 18, a contact's row block at its rank among the feet in contact
+    sc = msgcases.scene()
+    seen_m = set()
+    for mask, rec in enumerate(msgcases.one_message_per_mask(sc, 1.0)):
+        x, P = rand_state(rng), rand_cov(rng, 1e-4)
+        kh, kz, kR = msgcases.kin_rows(x, rec, sc.P)
+        assert len(kz) == 6 + 3 * bin(mask).count("1")
+        seen_m.add(len(kz))
+        for obj in pair:
+            obj.set_state(x, P)
+            obj.update_by_kin_imu(kh, kz, kR)
+        (xo, Po), (xr, Pr) = o.get_state(), r.get_state()
+        assert np.allclose(xo, xr, rtol=1e-9, atol=1e-12), (mask, np.abs(xo - xr).max())
+        assert np.allclose(Po, Pr, rtol=1e-7, atol=1e-13), (mask, np.abs(Po - Pr).max())
+        assert np.abs(xo - x).max() > 1e-6, mask
+    assert seen_m == {6, 9, 12, 15, 18}
 
 
 # ----------------------------------------------------------------------------- keys
@@ -412,6 +429,37 @@ def test_kilo_process_matches_the_reference(tmp_path, use_kin):
     retry with its unit mismatch, observation rows, literal N x N update, re-projection, map insert) - replays the same
     config-1 style scans as the oracle: identical match counts every scan, states to 1e-8, identical map."""
     kilo_process_case(tmp_path, use_kin)
+
+
+@pytest.mark.parametrize("when", ["t1", "epoch"])
+@pytest.mark.parametrize("kind", ["kin", "imu"])
+def test_kilo_process_matches_the_reference_on_message_edges(tmp_path, kind, when):
+    """KILO::process on the crafted message streams of tests/msgcases.py - all 16 contact masks with set bits written 1, 2, -1, 256, every second
+    stamp exactly on a bucket time (the queue pops while stamp < cur_point_time, KILO.cc:379-390), a pair of equal stamps, and the same at
+    stamps of 1.7e9 s where consecutive buckets share one absolute time: the oracle equals the reference scan after scan (match counts,
+    state 1e-8, covariance 1e-6, both time stamps, map).  It is what makes the oracle the checker of tests/test_message_edges.py."""
+    c = msgcases.live_case(kind, when == "epoch")
+    msgcases.assert_conditions(c, 1e-8)
+    o = ob.Oracle(c.sc.cfg(), imu_mode_only=kind != "kin")
+    k = ob.ReferenceKilo(c.sc.P, kind != "kin", tmp_path / "ref.yaml")
+    for obj in (o, k):
+        msgcases.start(obj, c)
+    scenes.compare_maps(o.map_export(), k.map_export(), rtol=1e-6, ptol=1e-9)
+    for s, scan in enumerate(c.scans):
+        kw = {"kins" if kind == "kin" else "imus": scan["msgs"]}
+        po, _ = o.process_scan(scan["ds"], scan["tb"], **kw)
+        pk, _ = k.process_scan(scan["ds"], scan["tb"], **kw)
+        (xo, Po), (xk, Pk) = o.get_state(), k.get_state()
+        print(f"{kind} {when} scan {s}: n_effect {int(po.n_effect)} / {int(pk.n_effect)}, max |dx| {np.abs(xo - xk).max():.2e}, max |dP| {np.abs(Po - Pk).max():.2e}")
+        assert po.n_effect == pk.n_effect > 500, (s, po.n_effect, pk.n_effect)
+        assert np.allclose(xo, xk, rtol=1e-8, atol=1e-9), (s, np.abs(xo - xk).max())
+        assert np.allclose(Po, Pk, rtol=1e-6, atol=1e-12), (s, np.abs(Po - Pk).max())
+        assert o.get_times() == k.get_times() == c.oracle[s][2] and o.get_times()[0] == scan["T"][-1], s
+        assert (po.n_buckets, po.n_updates, int(po.n_effect)) == c.oracle[s][0] and np.array_equal(xo, c.oracle[s][1]), s   # the shared oracle run is this run
+    st = scenes.compare_maps(o.map_export(), k.map_export(), rtol=1e-6, ptol=1e-7)
+    assert st["roots"] > 500
+    o.close()
+    k.close()
 
 
 @pytest.mark.parametrize("name", offconfig.CLOSED_LOOP)

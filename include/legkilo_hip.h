@@ -445,6 +445,26 @@ int lk_batch_replay_overlay_ragged_dev(lk_handle* h, const lk_point* d_pts, size
  * the call runs again); LK_ERR_STATE: no frozen-map grid.  A refused call leaves the slots at their priors. */
 int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
                                      const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out);
+/* The same runs on the FROZEN map - localisation against a finished prior map: arguments as for lk_batch_replay_overlay_runs_dev, run r on slot r, but no
+ * insert, no overlay pool, and the handle's map unchanged.  Per scan this is what lk_batch_replay_scans_dev does for one scan (frozen-map grid if there
+ * is one, hash table otherwise); across a scan boundary the slot's state, covariance and both time stamps stay, the message cursor jumps to the next
+ * scan's first record (what a package held beyond its scan's last bucket is never applied), and at a scan's first bucket all of its own records below
+ * that bucket's time are applied, one stamped before the previous scan's last bucket included.  out[s] (n_scans records, may be NULL): the pose after
+ * scan s, n_effect / n_buckets / n_updates of that scan alone; afterwards lk_batch_get_states(_dev) gives the runs' final states, and the slots'
+ * counters are their last scans'.  Synchronous.
+ * flags == 0: priors from lk_batch_set_priors(_dev), a slot's time stamps start at the t_begin of its run's first scan.
+ * LK_RUNS_CONTINUE: slot r goes on from the state, covariance and time stamps it HOLDS - on a frozen map the filter record is all a run carries, so a
+ * run split at any scan boundary into consecutive calls (the first with flags 0) gives the same bits as one call, and a run's length is unbounded.
+ * Nothing marks a slot as "in a run": the caller must not have used slots 0 .. n_runs-1 in between (any other batch or class-surface call on them,
+ * lk_batch_set_priors, lk_set_times), or the run continues from whatever that left.
+ * Buckets <= 512 points: run-resident, one wave per run; larger buckets without messages: launch by launch, same bits; larger buckets WITH messages
+ * are refused, as by the other frozen-map entries.
+ * LK_ERR_INVALID: n_runs 0 or above n_slots, run_off[0] != 0, an empty run or scan (the message names it), a scan not sorted by time (the message names
+ * it), a bad msg_kind, null arguments, unknown flag bits, messages with a bucket above 512 points; LK_ERR_CAPACITY: a bucket above max_scan_points,
+ * 2^32 points or messages or more.  Every check comes before the first write to a slot: a refused call leaves the slots as they were. */
+#define LK_RUNS_CONTINUE 1u
+int lk_batch_replay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin,
+                             int msg_kind, const uint32_t* n_msg, const void* d_msgs, uint32_t flags, lk_pose* out);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

@@ -26,6 +26,7 @@ EXPORTS = [
     "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
     "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
     "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
+    "lk_batch_replay_runs_dev",
 ]
 
 
@@ -68,6 +69,32 @@ def lib():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+LK_RUNS_CONTINUE = 1
+
+
+def flatten_runs(runs, t_begins, imus=None, kins=None):
+    """The flat tables of the run entries (lk_batch_replay_overlay_runs_dev, lk_batch_replay_runs_dev) from nested host inputs: runs = a list of
+    runs, each a list of scans (lk_point arrays); t_begins, imus / kins: the same nesting (one start time, one message array per scan).  Pure:
+    touches no device.  Returns a dict: run_off uint32 [R + 1], scan_off uint64 [S + 1], t_begin float64 [S], pts (all points, contiguous),
+    msg_kind 0 / 1 (imus) / 2 (kins), n_msg uint32 [S] or None, msgs (all records, contiguous) or None when there is none."""
+    assert imus is None or kins is None
+    scans = [sc for run in runs for sc in run]
+    run_off = np.r_[0, np.cumsum([len(run) for run in runs])].astype(np.uint32)
+    scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])].astype(np.uint64)
+    tb = np.array([t for run in t_begins for t in run], dtype=np.float64)
+    assert len(tb) == len(scans), "one start time per scan"
+    msgs = imus if imus is not None else kins
+    kind, n_msg, flat = 0, None, None
+    if msgs is not None:
+        kind = 1 if imus is not None else 2
+        per_scan = [m for run in msgs for m in run]
+        assert len(per_scan) == len(scans), "one message array per scan"
+        n_msg = np.fromiter((len(m) for m in per_scan), dtype=np.uint32, count=len(scans))
+        if n_msg.sum():
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in per_scan if len(m)]))
+    return dict(run_off=run_off, scan_off=scan_off, t_begin=tb, pts=np.ascontiguousarray(np.concatenate(scans)), msg_kind=kind, n_msg=n_msg, msgs=flat)
 
 
 def _f64(a):
@@ -552,41 +579,56 @@ class LegKiloHip:
                                                           _p(nm), C.c_void_p(d_msgs) if d_msgs else None, poses))
         return list(poses[:n_scans]) if want_poses else None
 
+    def _replay_runs_staged(self, entry, runs, t_begins, xs, Ps, imus, kins, **kw):
+        """What the two run conveniences share: priors, flatten_runs, points and messages -> HBM, entry(...), the poses run by run."""
+        if xs is not None:
+            self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
+        t = flatten_runs(runs, t_begins, imus, kins)
+        dptrs = []
+        try:
+            d_pts = self.device_malloc(t["pts"].nbytes)
+            dptrs.append(d_pts)
+            self.h2d(d_pts, t["pts"])
+            d_msgs = 0
+            if t["msgs"] is not None:
+                d_msgs = self.device_malloc(t["msgs"].nbytes)
+                dptrs.append(d_msgs)
+                self.h2d(d_msgs, t["msgs"])
+            poses = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, **kw)
+            return [poses[int(a):int(b)] for a, b in zip(t["run_off"][:-1], t["run_off"][1:])]
+        finally:
+            for d in dptrs:
+                self.device_free(d)
+
     def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None):
         """Convenience: runs = a list of runs, each a list of host scans (lk_point arrays, time-sorted, any sizes); t_begins, imus / kins: the same
         nesting (one start time, one message array per scan) -> HBM -> batch_replay_overlay_runs_dev.  Optional priors, one per run.  Returns the
         poses run by run (a list of lists)."""
-        assert imus is None or kins is None
-        if xs is not None:
-            self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
-        scans = [sc for run in runs for sc in run]
-        run_off = np.r_[0, np.cumsum([len(run) for run in runs])].astype(np.uint32)
-        scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])].astype(np.uint64)
-        tb = [t for run in t_begins for t in run]
-        allpts = np.ascontiguousarray(np.concatenate(scans))
-        msgs = imus if imus is not None else kins
-        kind, n_msg, flat = 0, None, None
-        if msgs is not None:
-            kind = 1 if imus is not None else 2
-            per_scan = [m for run in msgs for m in run]
-            n_msg = np.fromiter((len(m) for m in per_scan), dtype=np.uint32, count=len(scans))
-            if n_msg.sum():
-                flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in per_scan if len(m)]))
-        dptrs = []
-        try:
-            d_pts = self.device_malloc(allpts.nbytes)
-            dptrs.append(d_pts)
-            self.h2d(d_pts, allpts)
-            d_msgs = 0
-            if flat is not None:
-                d_msgs = self.device_malloc(flat.nbytes)
-                dptrs.append(d_msgs)
-                self.h2d(d_msgs, flat)
-            poses = self.batch_replay_overlay_runs_dev(d_pts, run_off, scan_off, tb, kind, n_msg, d_msgs)
-            return [poses[int(a):int(b)] for a, b in zip(run_off[:-1], run_off[1:])]
-        finally:
-            for d in dptrs:
-                self.device_free(d)
+        return self._replay_runs_staged(self.batch_replay_overlay_runs_dev, runs, t_begins, xs, Ps, imus, kins)
+
+    def batch_replay_runs_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, cont=False, want_poses=True, flags=None):
+        """Whole recorded runs on the FROZEN map, run r on slot r (lk_batch_replay_runs_dev): arguments as for batch_replay_overlay_runs_dev; no insert,
+        the handle's map is unchanged.  State, covariance and both time stamps of a slot survive its run's scan boundaries.  cont: LK_RUNS_CONTINUE -
+        the slots go on from what they hold (the caller has not used them since the previous call), so a run may be fed in chunks of scans.
+        Returns one pose per SCAN (counters of that scan alone); batch_get_states gives the runs' final states."""
+        ro = np.ascontiguousarray(run_off, dtype=np.uint32)
+        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
+        n_scans = len(so) - 1
+        tb = _f64(t_begins)
+        assert len(tb) == n_scans and len(ro) >= 1
+        nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
+        assert nm is None or len(nm) == n_scans
+        poses = (abi.lk_pose * max(n_scans, 1))() if want_poses else None
+        fl = (LK_RUNS_CONTINUE if cont else 0) if flags is None else int(flags)
+        self._chk(self.L.lk_batch_replay_runs_dev(self.h, C.c_void_p(d_pts), C.c_size_t(len(ro) - 1), _p(ro), _p(so), _p(tb), C.c_int(msg_kind),
+                                                  _p(nm), C.c_void_p(d_msgs) if d_msgs else None, C.c_uint32(fl), poses))
+        return list(poses[:n_scans]) if want_poses else None
+
+    def batch_replay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cont=False):
+        """Convenience: the nested host inputs of batch_replay_overlay_runs -> HBM -> batch_replay_runs_dev (frozen map).  Optional priors, one per
+        run (not with cont: a continued run goes on from what its slot holds).  Returns the poses run by run (a list of lists)."""
+        assert not (cont and xs is not None), "a continued run keeps its slot's state: no priors"
+        return self._replay_runs_staged(self.batch_replay_runs_dev, runs, t_begins, xs, Ps, imus, kins, cont=cont)
 
     def overlay_reserve(self, roots_per_scan=0, nodes_per_scan=0, blocks_per_scan=0):
         self._chk(self.L.lk_overlay_reserve(self.h, C.c_uint32(roots_per_scan), C.c_uint32(nodes_per_scan), C.c_uint32(blocks_per_scan)))

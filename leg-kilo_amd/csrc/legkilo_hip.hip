@@ -352,6 +352,15 @@ __device__ unsigned long long lk_sw_dbg[16];   // DEBUG BUILD ONLY: s_memtime de
 #else
 #define SW_STAMP(k) do { } while (0)
 #endif
+// RUN (lk_batch_replay_runs_dev; the lk_run_wave kernels below): the slot replays a RUN of consecutive scans on the frozen map, state, covariance and both
+// time stamps surviving the scan boundaries as KILO's members do from one KILO::process to the next.  In the CSR tables a run's buckets are one contiguous
+// range and their times absolute, so for addressing and time a run IS a scan (rag_nb / rag_t / rag_pt_off through rg.bstart).  Scan-aware are the message
+// cursor - behind a scan's last bucket it jumps to the next scan's first record: what a package leaves over is never applied, and at the next scan's first
+// bucket every record of ITS package below the bucket's time is (the two rules of rag_bucket()) -, the three per-scan counters, zeroed at the same place,
+// and the pose record, written behind the update of a scan's last bucket.  Everything RUN adds is under `if constexpr`: the three kernels without it
+// compile to what they were.
+extern "C++" {
+template <bool RUN = false>
 __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& pr, LkFilter* filters, const lk_point* __restrict__ pts,
                                               const LkRagged& rg, const double* __restrict__ Q, WaveSmem& sm, double* rows, const int MSG) {
     const bool WITH_IMU = MSG != 0;   // 1: lk_imu messages (only_imu_use), 2: lk_kin_imu messages (leg fusion, KILO.cc:384-390)
@@ -369,7 +378,15 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
     int last_N = f->last_N, updated = f->updated;
     __syncthreads();
     unsigned int qi = 0, qn = 0;   // this scan's IMU messages (KILO.cc:379-383: those stamped before the bucket come first)
-    if (WITH_IMU) qi = rg.imu_off[slot], qn = rg.imu_off[slot + 1];
+    if constexpr (!RUN)
+        if (WITH_IMU) qi = rg.imu_off[slot], qn = rg.imu_off[slot + 1];
+    int sc = 0;                // RUN: the scan that owns bucket b ...
+    unsigned int b_end = 0u;   // ... and the slot's bucket index behind that scan's last one
+    if constexpr (RUN) {
+        sc = rag_run_scan(rg, slot, 0);
+        b_end = rg.scan_b[sc + 1] - rg.bstart[slot];
+        if (WITH_IMU) qi = rg.imu_off[sc], qn = rg.imu_off[sc + 1];
+    }
     ResidualOut ro;
     ro.h6 = nullptr, ro.z = nullptr, ro.R = nullptr, ro.valid = nullptr, ro.world = nullptr;
 #ifdef LK_DEBUG_PHASES
@@ -425,6 +442,19 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
         SW_STAMP(4);
         __syncthreads();
         ++b;
+        if constexpr (RUN) {
+            if ((unsigned int)b == b_end) {   // that was the scan's last bucket: its pose, its counters (plain vector stores, as rag_write_pose's)
+                lk_pose* p = rg.scan_pose + sc;
+                if (lane < 15) reinterpret_cast<double*>(p)[lane] = sm.x[lane];
+                if (lane == 0) p->n_effect = n_effect, p->n_buckets = n_buckets, p->n_updates = n_updates;
+                if (b < nbk) {   // the next scan (no scan is empty): its own package from the first record on, counters of its own
+                    ++sc;
+                    b_end = rg.scan_b[sc + 1] - rg.bstart[slot];
+                    if (WITH_IMU) qi = rg.imu_off[sc], qn = rg.imu_off[sc + 1];
+                    n_effect = 0ull, n_updates = 0u, n_buckets = 0u;
+                }
+            }
+        }
         SW_STAMP(5);
     }
 #ifdef LK_DEBUG_PHASES
@@ -441,6 +471,7 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
         f->n_effect = n_effect, f->n_updates = n_updates, f->n_buckets = n_buckets, f->last_N = last_N, f->updated = updated;
     }
 }
+}   // extern "C++"
 // Ragged batch WITH insert, the way to bucket b of every scan that has one: the scan's messages stamped before the bucket's time that no
 // earlier bucket has consumed (KILO.cc:379-390: predictUpdateImu / predictUpdateKinImu one after the other), then the predict to the bucket's
 // time (KILO.cc:111-115) - dev_scan_wave's event loop between two buckets, as a launch of its own (one wave per scan).
@@ -505,6 +536,45 @@ __global__ void __launch_bounds__(LK_WAVE, 2)
     __shared__ WaveSmem sm;
     __shared__ double rows[64 * LK_ROW2];
     dev_scan_wave(map, pr, filters, pts, rg, Q, sm, rows, 2);
+}
+// The same three for runs of scans (dev_scan_wave<true>: lk_batch_replay_runs_dev), one wave per run.
+__global__ void __launch_bounds__(LK_WAVE, 2)
+    lk_run_wave_kernel(LkMap map, LkParams pr, LkFilter* filters, const lk_point* __restrict__ pts, LkRagged rg,
+                       const double* __restrict__ Q) {
+    __shared__ WaveSmem sm;
+    __shared__ double rows[64 * LK_ROW2];
+    dev_scan_wave<true>(map, pr, filters, pts, rg, Q, sm, rows, 0);
+}
+__global__ void __launch_bounds__(LK_WAVE, 2)
+    lk_run_wave_imu_kernel(LkMap map, LkParams pr, LkFilter* filters, const lk_point* __restrict__ pts, LkRagged rg,
+                           const double* __restrict__ Q) {
+    __shared__ WaveSmem sm;
+    __shared__ double rows[64 * LK_ROW2];
+    dev_scan_wave<true>(map, pr, filters, pts, rg, Q, sm, rows, 1);
+}
+__global__ void __launch_bounds__(LK_WAVE, 2)
+    lk_run_wave_kin_kernel(LkMap map, LkParams pr, LkFilter* filters, const lk_point* __restrict__ pts, LkRagged rg,
+                           const double* __restrict__ Q) {
+    __shared__ WaveSmem sm;
+    __shared__ double rows[64 * LK_ROW2];
+    dev_scan_wave<true>(map, pr, filters, pts, rg, Q, sm, rows, 2);
+}
+// Runs launch by launch (plain mode with a bucket above LK_SCAN_WAVE_MAX points, or LEGKILO_RAGGED_LEVELS): behind the update of bucket index b
+// (lk_update_wave_ragged_kernel, update only) the pose of every scan that ends there - then that slot's three counters are zeroed for the next scan -
+// and the predict to the slot's next bucket, which in plain mode is what KILO::process does across a scan boundary as well.
+__global__ void __launch_bounds__(LK_WAVE, LK_UPD_WAVES)
+    lk_run_tap_predict_kernel(LkFilter* filters, const double* __restrict__ Q, LkRagged rg, int b) {
+    __shared__ WaveSmem sm;
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    const int nbk = rag_nb(rg, slot);
+    if (b >= nbk) return;
+    LkFilter* f = &filters[slot];
+    const LkRagBucket rb = rag_bucket(rg, slot, b, false);
+    if (rb.pose) {
+        rag_write_pose(rb.pose, f->x, f, lane);
+        if (lane == 0 && b + 1 < nbk) f->n_buckets = 0u, f->n_updates = 0u, f->n_effect = 0ull;
+    }
+    if (b + 1 < nbk) dev_update_wave(f, sm, nullptr, 0, 0.0, Q, rag_t(rg, slot)[b + 1], 2);
 }
 
 // The map as the batch-replay kernels see it: with the dense root grid when it can be built (LkMap::grid).  The grid is derived
@@ -1943,9 +2013,12 @@ static void dump_scan_wave_phases(hipStream_t st) {
 }
 #endif
 // The launches of a ragged batch once its tables (padded or CSR, LkRagged) are in HBM.  msg_kind: a MsgKind.
-// max_n: largest bucket of every bucket index (null: `biggest` for all of them).
+// max_n: largest bucket of every bucket index (null: `biggest` for all of them).  d_tbegin: the slots' start times, or null - they go on from the
+// time stamps they hold (LK_RUNS_CONTINUE).  Runs (rg.run_scan, CSR tables: lk_batch_replay_runs_dev): a slot is a run of scans - for addressing and
+// time one long scan of ldb buckets at most; the kernels know where its scans end, and `out` takes the n_poses records of rg.scan_pose instead of
+// the slots' poses.
 static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const LkRagged& rg, const double* d_tbegin, int biggest, size_t ldb,
-                         const int* max_n, int msg_kind, lk_pose* out) {
+                         const int* max_n, int msg_kind, lk_pose* out, size_t n_poses = 0) {
     LkMap fmap;
     int rc = frozen_map(h, &fmap);
     if (rc) return rc;
@@ -1953,10 +2026,14 @@ static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const Lk
     if (rc) return rc;
     hipStream_t st = h->stream;
     LkFilter* fl = h->d_filters;
-    hipLaunchKernelGGL(lk_set_times_ragged_kernel, dim3(((int)S + 63) / 64), dim3(64), 0, st, fl, (int)S, d_tbegin);
+    const bool runs = rg.run_scan != nullptr;
+    if (d_tbegin) hipLaunchKernelGGL(lk_set_times_ragged_kernel, dim3(((int)S + 63) / 64), dim3(64), 0, st, fl, (int)S, d_tbegin);
     if (biggest <= LK_SCAN_WAVE_MAX && (msg_kind || !getenv("LEGKILO_RAGGED_LEVELS"))) {
-        // small buckets only (a real scan's 2 ms bins): each scan's whole bucket chain as one wave, one launch
-        if (msg_kind == MSG_KIN)
+        // small buckets only (a real scan's 2 ms bins): each scan's (run's) whole bucket chain as one wave, one launch
+        if (runs) {
+            const auto run_kernel = msg_kind == MSG_KIN ? lk_run_wave_kin_kernel : msg_kind == MSG_IMU ? lk_run_wave_imu_kernel : lk_run_wave_kernel;
+            hipLaunchKernelGGL(run_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fmap, h->pr, fl, d_pts, rg, h->d_Q);
+        } else if (msg_kind == MSG_KIN)
             hipLaunchKernelGGL(lk_scan_wave_kin_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fmap, h->pr, fl, d_pts, rg, h->d_Q);
         else if (msg_kind == MSG_IMU)
             hipLaunchKernelGGL(lk_scan_wave_imu_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fmap, h->pr, fl, d_pts, rg, h->d_Q);
@@ -1974,10 +2051,16 @@ static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const Lk
         const auto rag_kernel = fmap.grid_on ? lk_residual_ragged_kernel<1> : lk_residual_ragged_kernel<0>;
         hipLaunchKernelGGL(rag_kernel, dim3(nblk, (unsigned)S), dim3(LK_RB), 0, st, fmap, h->pr, fl, d_pts, rg, (int)b, h->d_partials,
                            h->part_stride);
+        // runs: the update alone, then the pose tap and the predict to the next bucket (lk_run_tap_predict_kernel) - the same arithmetic in two launches
         hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fl, h->d_partials, h->part_stride, h->d_Q, rg,
-                           (int)b);
+                           (int)b, runs ? 1 : 0);
+        if (runs) hipLaunchKernelGGL(lk_run_tap_predict_kernel, dim3((unsigned)S), dim3(LK_WAVE), 0, st, fl, h->d_Q, rg, (int)b);
     }
     HIPCHK(h, hipGetLastError());
+    if (runs && out) {   // the scans' poses, written where each scan ended
+        HIPCHK(h, hipMemcpyAsync(out, rg.scan_pose, sizeof(lk_pose) * n_poses, hipMemcpyDeviceToHost, st));
+        out = nullptr;
+    }
     return fetch_poses_or_sync(h, out, (int)S);
 }
 
@@ -2235,14 +2318,21 @@ int replay_scans(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint
     return ragged_launch(h, d_pts, S, rg, bt.t0, (int)biggest, (size_t)most, nullptr, msg_kind, out);
 }
 
-// Batch replay WITH insert of whole recorded runs: run r = the scans run_off[r] .. run_off[r+1) on filter slot r, each scan what
-// lk_batch_replay_overlay_ragged_dev does for one - but the slot's state, covariance, times and overlay survive the scan boundary, as KILO's members do
-// from one KILO::process to the next, and the message cursor jumps to the next scan's first record (what a package left over is never applied).
-// Bucket tables: built here for all scans at once (BucketTables, CSR), in which a run is one contiguous bucket range - overlay_ragged_launch replays
-// it as one long scan whose kernels know where its scans end (LkRagged::run_scan).  out[s]: the pose after scan s, its counters that scan's alone.
-int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
-                                     const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out) {
-    CHECK_H(h);
+// Whole recorded runs, a run per filter slot (lk_batch_replay_overlay_runs_dev with the insert, lk_batch_replay_runs_dev on the frozen map): run r = the
+// scans run_off[r] .. run_off[r+1) on slot r.  Bucket tables: built for all scans at once (BucketTables, CSR), in which a run is one contiguous bucket
+// range - the launches replay it as one long scan whose kernels know where its scans end (LkRagged::run_scan).  What the two entries share comes in two
+// halves, so that an entry can put checks of its own between them: runs_check() is everything the host can refuse from the arguments alone,
+// RunBatch::build() the tables on the device and what they say about the scans.  Nothing here writes to a filter slot.
+struct RunBatch {
+    size_t R = 0, S = 0, n = 0, max_run_pts = 0;   // runs, scans, points; the most points of a run
+    LkRagged rg;                                   // the runs' tables: bstart = the runs' first buckets, ldb = most buckets of a run
+    const double* d_rt = nullptr;                  // [R] the runs' start times
+    unsigned int biggest = 0, most_run = 0;        // largest bucket (points), most buckets of a run
+    int build(lk_handle* h, const lk_point* d_pts, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin, int msg_kind, const uint32_t* n_msg,
+              const void* d_msgs);
+};
+static int runs_check(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin, int msg_kind,
+                      const uint32_t* n_msg, const void* d_msgs, RunBatch* rb) {
     if (n_runs == 0 || n_runs > h->cfg.n_slots) return fail(h, LK_ERR_INVALID, "n_runs must be in [1, n_slots]");
     if (!d_pts || !run_off || !scan_off || !t_begin) return fail(h, LK_ERR_INVALID, "null argument");
     if (msg_kind < 0 || msg_kind > 2 || (msg_kind && !n_msg)) return fail(h, LK_ERR_INVALID, "msg_kind must be 0 (none), 1 (lk_imu) or 2 (lk_kin_imu) with n_msg given");
@@ -2261,21 +2351,22 @@ int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t
     if (n >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 points in one batch");
     if (n_msg_total && !d_msgs) return fail(h, LK_ERR_INVALID, "null message array");
     if (n_msg_total >= ((size_t)1 << 32)) return fail(h, LK_ERR_CAPACITY, "more than 2^32 messages in one batch");
-    size_t max_run_pts = 0;   // what sizes a slot's overlay: everything its run inserts
-    for (size_t r = 0; r < R; ++r) max_run_pts = std::max(max_run_pts, (size_t)(scan_off[run_off[r + 1]] - scan_off[run_off[r]]));
-    LkMap fmap;   // (asked here, ahead of the tables: a handle without the grid is refused before anything is built)
-    LKCHK(frozen_map(h, &fmap));
-    if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
+    rb->R = R, rb->S = S, rb->n = n, rb->max_run_pts = 0;
+    for (size_t r = 0; r < R; ++r) rb->max_run_pts = std::max(rb->max_run_pts, (size_t)(scan_off[run_off[r + 1]] - scan_off[run_off[r]]));
+    return LK_OK;
+}
+int RunBatch::build(lk_handle* h, const lk_point* d_pts, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin, int msg_kind, const uint32_t* n_msg,
+                    const void* d_msgs) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     BucketTables bt;
     unsigned int *d_ro = nullptr, *d_rb = nullptr;
-    double* d_rt = nullptr;
+    double* rt = nullptr;
     lk_pose* d_pose = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base);
         bt.take(c, n, S);
         d_ro = c.take<unsigned int>(R + 1), d_rb = c.take<unsigned int>(R + 1);   // the runs' first scans, their first buckets
-        d_rt = c.take<double>(R);                                                  // their start times
+        rt = c.take<double>(R);                                                    // their start times
         d_pose = c.take<lk_pose>(S);
         return c.total();
     };
@@ -2285,16 +2376,15 @@ int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t
     HIPCHK(h, hipMemcpyAsync(d_ro, run_off, 4 * (R + 1), hipMemcpyHostToDevice, h->stream));
     LKCHK(bt.build(h, d_pts, n, S, scan_off, t_begin, msg_kind ? n_msg : nullptr));
     hipLaunchKernelGGL(lk_rag_stats_kernel, dim3((unsigned int)((std::max(n, S) + 255) / 256)), dim3(256), 0, h->stream, bt.ps, bt.bs, (int)S, bt.st);
-    hipLaunchKernelGGL(lk_rag_run_tables_kernel, dim3((unsigned int)((R + 256) / 256)), dim3(256), 0, h->stream, bt.bs, d_ro, bt.t0, (int)R, d_rb, d_rt, bt.st);
+    hipLaunchKernelGGL(lk_rag_run_tables_kernel, dim3((unsigned int)((R + 256) / 256)), dim3(256), 0, h->stream, bt.bs, d_ro, bt.t0, (int)R, d_rb, rt, bt.st);
     HIPCHK(h, hipGetLastError());
     unsigned int st[8];
     HIPCHK(h, hipMemcpyAsync(st, bt.st, 32, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const unsigned int biggest = st[1], most_run = st[5];
+    biggest = st[1], most_run = st[5];
     if (st[3])
         return fail(h, LK_ERR_INVALID, "scan " + std::to_string(S - st[3]) + " is not sorted by time (curvature must be non-decreasing within a scan, and finite)");
     if (biggest > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
-    LkRagged rg;
     rg.pt_off = bt.ps;
     rg.t = bt.tb;
     rg.nb = nullptr;
@@ -2304,7 +2394,40 @@ int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t
     rg.imu = reinterpret_cast<const double*>(d_msgs);   // read where they lie
     rag_from_handle(h, msg_kind, &rg);
     rg.run_scan = d_ro, rg.scan_b = bt.bs, rg.scan_pose = d_pose;
-    return overlay_ragged_launch(h, d_pts, R, rg, d_rt, (int)biggest, (size_t)most_run, nullptr, max_run_pts, msg_kind, out, S);
+    d_rt = rt;
+    return LK_OK;
+}
+
+// Batch replay WITH insert of whole recorded runs: run r = the scans run_off[r] .. run_off[r+1) on filter slot r, each scan what
+// lk_batch_replay_overlay_ragged_dev does for one - but the slot's state, covariance, times and overlay survive the scan boundary, as KILO's members do
+// from one KILO::process to the next, and the message cursor jumps to the next scan's first record (what a package left over is never applied).
+// out[s]: the pose after scan s, its counters that scan's alone.
+int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
+                                     const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out) {
+    CHECK_H(h);
+    RunBatch rb;
+    LKCHK(runs_check(h, d_pts, n_runs, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs, &rb));
+    LkMap fmap;   // (asked here, ahead of the tables: a handle without the grid is refused before anything is built)
+    LKCHK(frozen_map(h, &fmap));
+    if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
+    LKCHK(rb.build(h, d_pts, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs));
+    return overlay_ragged_launch(h, d_pts, rb.R, rb.rg, rb.d_rt, (int)rb.biggest, (size_t)rb.most_run, nullptr, rb.max_run_pts, msg_kind, out, rb.S);
+}
+
+// The same runs on the FROZEN map - no insert, no overlay, the handle's map unchanged: per scan what lk_batch_replay_scans_dev does for one (grid if
+// there is one, hash otherwise), state, covariance and both time stamps carried across the scan boundaries, the message cursor as above.  On a frozen
+// map a slot's filter record is the whole carried state: with LK_RUNS_CONTINUE the slots go on from what they hold (no reset of the times), so a run
+// split at any scan boundary into consecutive calls gives the bits of one call.  Every check comes before the first write to a slot.
+int lk_batch_replay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin,
+                             int msg_kind, const uint32_t* n_msg, const void* d_msgs, uint32_t flags, lk_pose* out) {
+    CHECK_H(h);
+    if (flags & ~LK_RUNS_CONTINUE) return fail(h, LK_ERR_INVALID, "unknown flag bits (LK_RUNS_CONTINUE is the only one)");
+    RunBatch rb;
+    LKCHK(runs_check(h, d_pts, n_runs, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs, &rb));
+    LKCHK(rb.build(h, d_pts, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs));
+    if (msg_kind && rb.biggest > (unsigned int)LK_SCAN_WAVE_MAX)
+        return fail(h, LK_ERR_INVALID, "IMU / kinematic messages between buckets are only replayed for scans whose buckets hold <= 512 points");
+    return ragged_launch(h, d_pts, rb.R, rb.rg, (flags & LK_RUNS_CONTINUE) ? nullptr : rb.d_rt, (int)rb.biggest, (size_t)rb.most_run, nullptr, msg_kind, out, rb.S);
 }
 
 // The tables of a live run (RunTables): the same CSR tables over the run's points - d_pts is the run's FIRST point - followed by the per-scan

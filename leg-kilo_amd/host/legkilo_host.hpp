@@ -381,6 +381,20 @@ class KiloPath {
                                                      msg_kind ? n_msg.data() : nullptr, d_msgs, out.data()));
         return out;
     }
+    // lk_batch_replay_runs_dev: the same runs on the FROZEN map (localisation against a finished map: no insert, no overlay, the map untouched) -
+    // state, covariance and both time stamps carried across the scan boundaries.  cont (LK_RUNS_CONTINUE): the slots go on from what they hold, so
+    // a run may be fed in chunks of scans, the first chunk with cont = false; the caller has not used the slots in between.  Tables as above.
+    std::vector<lk_pose> replayRunsDev(const lk_point* d_pts, const std::vector<uint32_t>& run_off, const std::vector<uint64_t>& scan_off,
+                                       const std::vector<double>& t_begin, int msg_kind, const std::vector<uint32_t>& n_msg, const void* d_msgs,
+                                       bool cont = false) {
+        const size_t S = t_begin.size();
+        if (run_off.size() < 2 || run_off.back() != S || scan_off.size() != S + 1 || (msg_kind && n_msg.size() != S))
+            throw std::runtime_error("replayRunsDev: table sizes differ");
+        std::vector<lk_pose> out(S);
+        dev_->check(lk_batch_replay_runs_dev(dev_->h(), d_pts, run_off.size() - 1, run_off.data(), scan_off.data(), t_begin.data(), msg_kind,
+                                             msg_kind ? n_msg.data() : nullptr, d_msgs, cont ? LK_RUNS_CONTINUE : 0u, out.data()));
+        return out;
+    }
     // lk_run_scans_dev: a recorded run LIVE on the handle's map (KILO::process scan after scan, the map growing), from scans and message records
     // that lie in HBM - msg_kind 0 none, 1 lk_imu, 2 lk_kin_imu; n_msg[s] records per scan at d_msgs.  slide: mapSliding after every scan
     // (lk_run_options), or null.  d_world_out: one 16-byte record per point of d_pts (cloud_down_world), or null.  Returns the poses of the scans

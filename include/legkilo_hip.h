@@ -476,6 +476,22 @@ int lk_overlay_reserve(lk_handle* h, uint32_t roots_per_scan, uint32_t nodes_per
  * BEFORE the map is changed.  After lk_process_scan / lk_update_points / lk_map_update / lk_map_build / lk_map_import / lk_map_slide /
  * lk_map_clear_outside the call fails with LK_ERR_STATE. */
 int lk_overlay_export(lk_handle* h, uint32_t slot, void* blob, size_t* bytes);
+/* Slot `slot`'s overlay of the LAST overlay replay becomes part of the handle's map, without the map leaving HBM: afterwards the handle's map is the
+ * map a private handle would hold after KILO::process of that slot's scans on a copy of the base map.  Every root voxel the slot holds privately
+ * replaces the base voxel of that key as a whole octree, a private root voxel of a key the base map lacks is added, every other voxel stays bit for
+ * bit; records are moved, not recomputed, and get new ids (the ranks of a prefix sum: the same call on the same state gives the same ids).
+ * Synchronous.  With lk_batch_get_states(_dev) -> lk_batch_set_priors(_dev) this makes windowed mapping of any length out of the replays with
+ * insert: replay a window on all slots, choose a slot, commit it, lk_map_slide if wanted, replay the next window.
+ * The call commits ONE slot.  The reference has no answer for a voxel two slots changed; the other slots' overlays are stale afterwards, as after any
+ * map change: lk_overlay_export and a second lk_overlay_commit answer LK_ERR_STATE until the next replay with insert, and the frozen-map grid is
+ * rebuilt by the next batch replay.
+ * flags == 0: no filter slot is touched.  LK_COMMIT_ADOPT_FILTER: the whole filter record of `slot` (state, covariance, both time stamps, counters)
+ * is also copied to slot 0, device to device, so that lk_process_scan / lk_run_scans_dev go on live from the committed map.
+ * LK_ERR_STATE: no overlay pools, or the map has changed since the replay (lk_overlay_export's conditions); LK_ERR_INVALID: slot was not part of the
+ * last replay, unknown flag bits; LK_ERR_CAPACITY: surviving + private records exceed max_nodes / max_point_blocks, or twice the root voxels the
+ * root table (lk_map_import's rule) - the message gives the counts.  Every refusal comes before the first write: the map is byte-equal afterwards. */
+#define LK_COMMIT_ADOPT_FILTER 1u
+int lk_overlay_commit(lk_handle* h, uint32_t slot, uint32_t flags);
 /* Largest private root / node / point-block count any scan of the last overlay replay reached (any pointer may be NULL). */
 int lk_overlay_stats(lk_handle* h, uint32_t* max_roots, uint32_t* max_nodes, uint32_t* max_blocks);
 /* What the overlay pools hold right now: total bytes in HBM and the per-scan capacities (root-table entries = root node records,

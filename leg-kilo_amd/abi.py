@@ -13,6 +13,8 @@ LK_NODE_UPDATE_ENABLE = 2
 LK_NODE_OCTO_STATE = 4
 LK_NODE_PTS_DROPPED = 8
 
+LK_COMMIT_ADOPT_FILTER = 1   # lk_overlay_commit: the committed slot's filter record also goes to slot 0
+
 
 class lk_config(C.Structure):
     _fields_ = [

@@ -26,7 +26,7 @@ EXPORTS = [
     "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
     "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
     "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
-    "lk_batch_replay_runs_dev",
+    "lk_batch_replay_runs_dev", "lk_overlay_commit",
 ]
 
 
@@ -640,6 +640,13 @@ class LegKiloHip:
         buf = np.zeros(nbytes.value, dtype=np.uint8)
         self._chk(self.L.lk_overlay_export(self.h, C.c_uint32(slot), _p(buf), C.byref(nbytes)))
         return buf
+
+    def overlay_commit(self, slot, adopt_filter=False, flags=None):
+        """Slot `slot`'s overlay of the last replay with insert becomes part of the handle's map, on the device (lk_overlay_commit): the map
+        KILO::process of that slot's scans would have left on a private copy.  The replay's overlays are stale afterwards.  adopt_filter: the slot's
+        filter record (state, covariance, time stamps, counters) is also copied to slot 0.  flags: the raw flag word instead."""
+        fl = (abi.LK_COMMIT_ADOPT_FILTER if adopt_filter else 0) if flags is None else int(flags)
+        self._chk(self.L.lk_overlay_commit(self.h, C.c_uint32(slot), C.c_uint32(fl)))
 
     def overlay_stats(self):
         """(max roots, max nodes, max point blocks) any scan's overlay reached in the last overlay replay."""

@@ -920,87 +920,127 @@ int lk_match_points(lk_handle* h, size_t n, const int32_t* keys3, const double* 
     return LK_OK;
 }
 
-// clearMemOutOfMap (voxel_map.cc:571-594) as a pool compaction; see lk_map_kernels.h
-static int clear_outside(lk_handle* h, const LkSlideBox& box, uint32_t* n_removed) {
-    if (n_removed) *n_removed = 0;
-    h->grid_valid = false;
+// clearMemOutOfMap (voxel_map.cc:571-594) as a pool compaction; see lk_map_kernels.h.  The steps (MapCompact, lk_internal.h) are shared with
+// lk_overlay_commit.
+__global__ void lk_validate_ids_kernel(LkMap map, unsigned int n_nodes, unsigned int n_blocks, unsigned int hash_cap);
+int compact_begin(lk_handle* h, MapCompact* mc, unsigned int x_nodes, unsigned int x_blocks, unsigned int x_roots) {
     unsigned int ctr[LK_CTR_COUNT];
     HIPCHK(h, hipMemcpyAsync(ctr, h->map.counters, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const unsigned int n_nodes = std::min(ctr[LK_CTR_NODES], h->map.max_nodes), n_blocks = std::min(ctr[LK_CTR_BLOCKS], h->map.max_blocks),
-                       n_roots = ctr[LK_CTR_ROOTS];
-    if (n_roots == 0) return LK_OK;
-    struct Scratch {  // freed on every exit path
-        std::vector<void*> p;
-        ~Scratch() {
-            for (void* q : p) hipFree(q);
-        }
-        void* get(size_t bytes) {
-            void* q = nullptr;
-            if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-            p.push_back(q);
-            return q;
-        }
-    } sc;
-    unsigned int* alive_node = (unsigned int*)sc.get(sizeof(unsigned int) * n_nodes);
-    unsigned int* alive_block = (unsigned int*)sc.get(sizeof(unsigned int) * std::max(n_blocks, 1u));
-    unsigned int* new_node = (unsigned int*)sc.get(sizeof(unsigned int) * n_nodes);
-    unsigned int* new_block = (unsigned int*)sc.get(sizeof(unsigned int) * std::max(n_blocks, 1u));
-    lk_root_rec* kept = (lk_root_rec*)sc.get(sizeof(lk_root_rec) * n_roots);
-    unsigned int* cnt = (unsigned int*)sc.get(sizeof(unsigned int) * 2);
-    if (!alive_node || !alive_block || !new_node || !new_block || !kept || !cnt) return fail(h, LK_ERR_HIP, "map slide: out of device memory");
-    HIPCHK(h, hipMemsetAsync(alive_node, 0, sizeof(unsigned int) * n_nodes, h->stream));
-    HIPCHK(h, hipMemsetAsync(alive_block, 0, sizeof(unsigned int) * std::max(n_blocks, 1u), h->stream));
-    HIPCHK(h, hipMemsetAsync(cnt, 0, sizeof(unsigned int) * 2, h->stream));
-    hipLaunchKernelGGL(lk_slide_mark_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, h->stream, h->map, box, h->hash_cap,
-                       alive_node, alive_block, kept, cnt);
-    unsigned int hc[2];
-    HIPCHK(h, hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (hc[0] + hc[1] != n_roots) return fail(h, LK_ERR_STATE, "hash table and root counter disagree");
-    if (n_removed) *n_removed = hc[1];
-    if (hc[1] == 0) return LK_OK;
-    // dense new ids
-    size_t t1 = 0, t2 = 0;
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, alive_node, new_node, n_nodes, h->stream));
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t2, alive_block, new_block, std::max(n_blocks, 1u), h->stream));
-    void* tmp = sc.get(std::max(t1, t2));
-    if (!tmp) return fail(h, LK_ERR_HIP, "map slide: out of device memory");
-    HIPCHK(h, lk_prim_exclusive_scan(tmp, t1, alive_node, new_node, n_nodes, h->stream));
-    if (n_blocks)
-        HIPCHK(h, lk_prim_exclusive_scan(tmp, t2, alive_block, new_block, n_blocks, h->stream));
-    unsigned int last[4] = {0, 0, 0, 0};  // new_node[n-1], alive_node[n-1], new_block[n-1], alive_block[n-1]
-    HIPCHK(h, hipMemcpyAsync(&last[0], new_node + n_nodes - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last[1], alive_node + n_nodes - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-    if (n_blocks) {
-        HIPCHK(h, hipMemcpyAsync(&last[2], new_block + n_blocks - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&last[3], alive_block + n_blocks - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    mc->n_nodes = std::min(ctr[LK_CTR_NODES], h->map.max_nodes), mc->n_blocks = std::min(ctr[LK_CTR_BLOCKS], h->map.max_blocks), mc->n_roots = ctr[LK_CTR_ROOTS];
+    mc->x_nodes = x_nodes, mc->x_blocks = x_blocks, mc->x_roots = x_roots;
+    if (mc->n_roots + x_roots == 0) return LK_OK;   // nothing to compact: no scratch
+    const size_t N = (size_t)mc->n_nodes + x_nodes, B = std::max<size_t>((size_t)mc->n_blocks + x_blocks, 1);
+    const auto flags = [&](void* base) {   // one allocation, one memset
+        LkCarve c(base);
+        mc->alive_node = c.take<unsigned int>(N), mc->alive_block = c.take<unsigned int>(B), mc->drop = c.take<unsigned int>(std::max(mc->n_nodes, 1u));
+        mc->cnt = c.take<unsigned int>(4);
+        return c.total();
+    };
+    const auto ranks = [&](void* base) {
+        LkCarve c(base);
+        mc->new_node = c.take<unsigned int>(N), mc->new_block = c.take<unsigned int>(B);
+        return c.total();
+    };
+    void *fb = nullptr, *rb = nullptr;
+    const size_t fbytes = flags(nullptr);
+    if (mc->tmp.alloc(&fb, fbytes) != hipSuccess || mc->tmp.alloc(&rb, ranks(nullptr)) != hipSuccess ||
+        mc->tmp.alloc(&mc->kept, sizeof(lk_root_rec) * ((size_t)mc->n_roots + x_roots)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, LK_ERR_HIP, "map compaction: out of device memory");
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const unsigned int live_nodes = last[0] + last[1], live_blocks = last[2] + last[3];
-    lk_node_rec* tn = (lk_node_rec*)sc.get(sizeof(lk_node_rec) * live_nodes);
-    lk_plane_rec* tp = (lk_plane_rec*)sc.get(sizeof(lk_plane_rec) * live_nodes);
-    lk_match_rec* tm = (lk_match_rec*)sc.get(sizeof(lk_match_rec) * live_nodes);
-    lk_block_rec* tb = (lk_block_rec*)sc.get(sizeof(lk_block_rec) * std::max(live_blocks, 1u));
-    if (!tn || !tp || !tm || !tb) return fail(h, LK_ERR_HIP, "map slide: out of device memory");
-    hipLaunchKernelGGL(lk_slide_move_nodes_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, h->stream, h->map, n_nodes, alive_node,
-                       new_node, new_block, tn, tp, tm);
-    if (n_blocks)
-        hipLaunchKernelGGL(lk_slide_move_blocks_kernel, dim3(n_blocks), dim3(64), 0, h->stream, h->map, alive_block, new_block, tb);
+    flags(fb), ranks(rb);
+    HIPCHK(h, hipMemsetAsync(fb, 0, fbytes, h->stream));
+    return LK_OK;
+}
+int compact_mark(lk_handle* h, MapCompact* mc, const LkSlideBox& box, bool with_drop) {
+    hipLaunchKernelGGL(lk_slide_mark_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, h->stream, h->map, box, h->hash_cap,
+                       mc->alive_node, mc->alive_block, mc->kept, mc->cnt, with_drop ? mc->drop : nullptr);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->map.nodes, tn, sizeof(lk_node_rec) * live_nodes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->map.planes, tp, sizeof(lk_plane_rec) * live_nodes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->map.match, tm, sizeof(lk_match_rec) * live_nodes, hipMemcpyDeviceToDevice, h->stream));
+    unsigned int hc[2];
+    HIPCHK(h, hipMemcpyAsync(hc, mc->cnt, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hc[0] + hc[1] != mc->n_roots) return fail(h, LK_ERR_STATE, "hash table and root counter disagree");
+    mc->kept_roots = hc[0], mc->removed_roots = hc[1];
+    return LK_OK;
+}
+int compact_count(lk_handle* h, MapCompact* mc) {   // dense new ids
+    const size_t N = (size_t)mc->n_nodes + mc->x_nodes, B = (size_t)mc->n_blocks + mc->x_blocks;
+    size_t t1 = 0, t2 = 0;
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, mc->alive_node, mc->new_node, N, h->stream));
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t2, mc->alive_block, mc->new_block, std::max<size_t>(B, 1), h->stream));
+    LKCHK(reserve(h, h->prim_tmp, std::max(t1, t2)));
+    t1 = t2 = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, t1, mc->alive_node, mc->new_node, N, h->stream));
+    if (B) HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, t2, mc->alive_block, mc->new_block, B, h->stream));
+    unsigned int last[6] = {0, 0, 0, 0, 0, 0};  // new_node[N-1], alive_node[N-1], new_block[B-1], alive_block[B-1]; new_node / new_block at the second pool's first record
+    HIPCHK(h, hipMemcpyAsync(&last[0], mc->new_node + N - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last[1], mc->alive_node + N - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    if (B) {
+        HIPCHK(h, hipMemcpyAsync(&last[2], mc->new_block + B - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&last[3], mc->alive_block + B - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (mc->x_nodes) HIPCHK(h, hipMemcpyAsync(&last[4], mc->new_node + mc->n_nodes, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    if (mc->x_blocks) HIPCHK(h, hipMemcpyAsync(&last[5], mc->new_block + mc->n_blocks, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    mc->all_nodes = last[0] + last[1], mc->all_blocks = last[2] + last[3];
+    mc->live_nodes = mc->x_nodes ? last[4] : mc->all_nodes, mc->live_blocks = mc->x_blocks ? last[5] : mc->all_blocks;
+    return LK_OK;
+}
+int compact_move(lk_handle* h, MapCompact* mc) {
+    h->grid_valid = false;
+    const unsigned int live_nodes = mc->live_nodes, live_blocks = mc->live_blocks;
+    lk_node_rec* tn = nullptr;
+    lk_plane_rec* tp = nullptr;
+    lk_match_rec* tm = nullptr;
+    lk_block_rec* tb = nullptr;
+    if (mc->tmp.alloc(&tn, sizeof(lk_node_rec) * std::max(live_nodes, 1u)) != hipSuccess || mc->tmp.alloc(&tp, sizeof(lk_plane_rec) * std::max(live_nodes, 1u)) != hipSuccess ||
+        mc->tmp.alloc(&tm, sizeof(lk_match_rec) * std::max(live_nodes, 1u)) != hipSuccess || mc->tmp.alloc(&tb, sizeof(lk_block_rec) * std::max(live_blocks, 1u)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, LK_ERR_HIP, "map compaction: out of device memory");
+    }
+    if (mc->n_nodes)
+        hipLaunchKernelGGL(lk_slide_move_nodes_kernel, dim3((mc->n_nodes + 255) / 256), dim3(256), 0, h->stream, h->map, mc->n_nodes, mc->alive_node,
+                           mc->new_node, mc->new_block, tn, tp, tm, 0);
+    if (mc->n_blocks)
+        hipLaunchKernelGGL(lk_slide_move_blocks_kernel, dim3(mc->n_blocks), dim3(64), 0, h->stream, h->map, mc->alive_block, mc->new_block, tb);
+    HIPCHK(h, hipGetLastError());
+    if (live_nodes) {
+        HIPCHK(h, hipMemcpyAsync(h->map.nodes, tn, sizeof(lk_node_rec) * live_nodes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->map.planes, tp, sizeof(lk_plane_rec) * live_nodes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->map.match, tm, sizeof(lk_match_rec) * live_nodes, hipMemcpyDeviceToDevice, h->stream));
+    }
     if (live_blocks)
         HIPCHK(h, hipMemcpyAsync(h->map.blocks, tb, sizeof(lk_block_rec) * live_blocks, hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(lk_slide_hash_clear_kernel, dim3((h->hash_cap + 255) / 256), dim3(256), 0, h->stream, h->map, h->hash_cap);
-    if (hc[0]) {
-        hipLaunchKernelGGL(lk_slide_remap_roots_kernel, dim3((hc[0] + 255) / 256), dim3(256), 0, h->stream, kept, hc[0], new_node);
-        hipLaunchKernelGGL(lk_hash_insert_kernel, dim3((hc[0] + 255) / 256), dim3(256), 0, h->stream, h->map, h->pr, kept, (int)hc[0]);
+    if (mc->kept_roots)
+        hipLaunchKernelGGL(lk_slide_remap_roots_kernel, dim3((mc->kept_roots + 255) / 256), dim3(256), 0, h->stream, mc->kept, mc->kept_roots, mc->new_node);
+    HIPCHK(h, hipGetLastError());
+    return LK_OK;
+}
+int compact_finish(lk_handle* h, MapCompact* mc, unsigned int n_nodes, unsigned int n_blocks, unsigned int n_roots, bool validate_ids) {
+    if (n_roots)
+        hipLaunchKernelGGL(lk_hash_insert_kernel, dim3((n_roots + 255) / 256), dim3(256), 0, h->stream, h->map, h->pr, mc->kept, (int)n_roots);
+    hipLaunchKernelGGL(lk_slide_counters_kernel, dim3(1), dim3(1), 0, h->stream, h->map, n_nodes, n_blocks, n_roots);
+    if (validate_ids) {   // as lk_map_import_dev: a dangling id is an error now, not a walk later
+        const unsigned int nv = std::max(n_nodes, h->hash_cap);
+        hipLaunchKernelGGL(lk_validate_ids_kernel, dim3((nv + 255) / 256), dim3(256), 0, h->stream, h->map, n_nodes, n_blocks, h->hash_cap);
     }
-    hipLaunchKernelGGL(lk_slide_counters_kernel, dim3(1), dim3(1), 0, h->stream, h->map, live_nodes, live_blocks, hc[0]);
     HIPCHK(h, hipGetLastError());
     return check_map_errors(h);  // synchronises: the scratch buffers may be released after this
+}
+static int clear_outside(lk_handle* h, const LkSlideBox& box, uint32_t* n_removed) {
+    if (n_removed) *n_removed = 0;
+    h->grid_valid = false;
+    MapCompact mc;
+    LKCHK(compact_begin(h, &mc, 0, 0, 0));
+    if (mc.n_roots == 0) return LK_OK;
+    LKCHK(compact_mark(h, &mc, box, false));
+    if (n_removed) *n_removed = mc.removed_roots;
+    if (mc.removed_roots == 0) return LK_OK;
+    LKCHK(compact_count(h, &mc));
+    LKCHK(compact_move(h, &mc));
+    return compact_finish(h, &mc, mc.live_nodes, mc.live_blocks, mc.kept_roots, false);
 }
 
 int lk_map_clear_outside(lk_handle* h, int32_t x_max, int32_t x_min, int32_t y_max, int32_t y_min, int32_t z_max, int32_t z_min,

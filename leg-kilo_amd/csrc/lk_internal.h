@@ -2,7 +2,7 @@
 // headers.  The library is seven units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
 // kernel but the overlay's and the stream path's own), lk_stream.hip (LK_TU_STREAM: one live scan after the other with the map insert - the per-bucket
 // launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries, which all run a scan through run_one_scan: one choice of its kernel), lk_overlay.hip (LK_TU_OVERLAY: batch replay
-// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_ovrun.hip (the same file's run-resident instantiations), lk_kin.hip (LK_TU_KIN: the message front ends - HighState decode + contact detector, lk_kin_kernels.h; sensor_msgs/Imu decode, lk_imu_kernels.h; the scan split of either - and their entries), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
+// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them, lk_overlay_commit among them: its compaction steps, MapCompact below, are the main unit's), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_ovrun.hip (the same file's run-resident instantiations), lk_kin.hip (LK_TU_KIN: the message front ends - HighState decode + contact detector, lk_kin_kernels.h; sensor_msgs/Imu decode, lk_imu_kernels.h; the scan split of either - and their entries), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
 // (LK_KERNELS_ELSEWHERE) and launches it through the main unit's host stub.  The overlay header's own kernels are compiled in the overlay unit only.
 #pragma once
 #if !defined(LK_TU_MAIN) && !defined(LK_TU_OVERLAY) && !defined(LK_TU_STREAM) && !defined(LK_TU_OVSCAN) && !defined(LK_TU_KIN)
@@ -299,6 +299,26 @@ struct DevTemps {
     }
 };
 
+// The pool compaction of lk_map_slide / lk_map_clear_outside (lk_map_kernels.h), in steps, so that lk_overlay_commit (overlay unit) can put its own
+// between them: begin - the map's counters, the flag and rank arrays, zeroed; x_* > 0: room for the records of a second pool (a slot's overlay)
+// flagged BEHIND the map's, so that one scan ranks the survivors first and those records behind them; mark - lk_slide_mark_kernel (box, and `drop`
+// if asked for); count - the exclusive scans and their totals, nothing of the map written so far; move - survivors to their ranks, the root table
+// cleared, the kept roots renumbered; finish - the table rebuilt from kept[0 .. n_roots), the counters set, the error word read.  The functions are
+// the main unit's.
+struct MapCompact {
+    DevTemps tmp;                                                // freed on every exit path
+    unsigned int n_nodes = 0, n_blocks = 0, n_roots = 0;         // the map's counters at begin()
+    unsigned int x_nodes = 0, x_blocks = 0, x_roots = 0;         // the second pool's records
+    unsigned int *alive_node = nullptr, *alive_block = nullptr;  // [n_nodes + x_nodes], [n_blocks + x_blocks]
+    unsigned int *new_node = nullptr, *new_block = nullptr;      // their exclusive scans
+    unsigned int *drop = nullptr;                                // [n_nodes]: roots to remove whatever the box says
+    unsigned int *cnt = nullptr;                                 // [4]: kept, removed, two words of the caller's
+    lk_root_rec* kept = nullptr;                                 // [n_roots + x_roots]
+    unsigned int kept_roots = 0, removed_roots = 0;              // mark()
+    unsigned int live_nodes = 0, live_blocks = 0;                // count(): the map's survivors ...
+    unsigned int all_nodes = 0, all_blocks = 0;                  // ... and with the second pool's flagged records
+};
+
 // LEGKILO_XID=0: the generic residual kernels instead of those specialised for ext_R == I (the tests' reference); read once per process
 static bool lk_xid_enabled() {
     static const bool v = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
@@ -412,6 +432,11 @@ int run_tables(lk_handle* h, const lk_point* d_pts, size_t n_scans, const uint64
 __global__ void lk_set_times_kernel(LkFilter* filters, int n, double t);
 __global__ void __launch_bounds__(LK_WAVE, 2) lk_rag_advance_kernel(LkFilter* filters, const double* __restrict__ Q, LkRagged rg, int b, int msg_kind);
 int upload_xyz_as_points(lk_handle* h, const float* xyz, size_t n);   // n x 3 floats -> h->d_scan as lk_point records
+int compact_begin(lk_handle* h, MapCompact* mc, unsigned int x_nodes, unsigned int x_blocks, unsigned int x_roots);
+int compact_mark(lk_handle* h, MapCompact* mc, const LkSlideBox& box, bool with_drop);
+int compact_count(lk_handle* h, MapCompact* mc);
+int compact_move(lk_handle* h, MapCompact* mc);
+int compact_finish(lk_handle* h, MapCompact* mc, unsigned int n_nodes, unsigned int n_blocks, unsigned int n_roots, bool validate_ids);
 // stream unit (lk_stream.hip)
 int run_scan(lk_handle* h, const lk_point* pts, const lk_point* d_pts, size_t n, double t_begin, const lk_imu* imus, size_t n_imu, const lk_kin_imu* kins,
              size_t n_kin, float* xyz_world_out, lk_pose* out);          // the bucket loop of KILO::process on a sorted cloud that is in HBM (and on the host, for the bucket bounds)

@@ -1851,41 +1851,28 @@ __global__ void __launch_bounds__(256) lk_hash_insert_kernel(LkMap map, LkParams
 //   lk_slide_hash_clear + lk_slide_remap_roots + lk_hash_insert_kernel   rebuild the table from the kept roots
 // Nothing on the per-bucket path changes: allocation stays a bump pointer (+ the point-block free list, which is
 // emptied here because retired blocks are not alive).
+// lk_overlay_commit (lk_overlay.hip) runs the same compaction under a second predicate - `drop`: a flag per node id, set for the base roots whose key
+// one slot's overlay holds privately - and with that slot's private records flagged behind the map's own in the same arrays, so that one scan
+// ranks survivors first and the appended records behind them (MapCompact, lk_internal.h).
 struct LkSlideBox {
     int x_max, x_min, y_max, y_min, z_max, z_min;
 };
 
-#ifdef LK_KERNELS_ELSEWHERE
-__global__ void __launch_bounds__(256)
-    lk_slide_mark_kernel(LkMap map, LkSlideBox box, unsigned int n_hash, unsigned int* __restrict__ alive_node,
-                         unsigned int* __restrict__ alive_block, lk_root_rec* __restrict__ kept,
-                         unsigned int* __restrict__ cnt /* [0] kept, [1] removed */);
-#else
-__global__ void __launch_bounds__(256)
-    lk_slide_mark_kernel(LkMap map, LkSlideBox box, unsigned int n_hash, unsigned int* __restrict__ alive_node,
-                         unsigned int* __restrict__ alive_block, lk_root_rec* __restrict__ kept,
-                         unsigned int* __restrict__ cnt /* [0] kept, [1] removed */) {
-    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_hash) return;
-    const int4 e = map.hash[i];
-    if (e.w < 0) return;
-    const bool should_remove = e.x > box.x_max || e.x < box.x_min || e.y > box.y_max || e.y < box.y_min ||
-                               e.z > box.z_max || e.z < box.z_min;  // voxel_map.cc:578-579
-    if (should_remove) {
-        atomicAdd(&cnt[1], 1u);
-        return;
-    }
-    const unsigned int k = atomicAdd(&cnt[0], 1u);
-    kept[k].key[0] = e.x, kept[k].key[1] = e.y, kept[k].key[2] = e.z;
-    kept[k].node = e.w;
-    // pre-order walk of the subtree (depth <= LK_MAX_LAYER)
+// Flags the nodes and point blocks of the octree below `root` (pre-order walk, depth <= LK_MAX_LAYER).  An id at or above n_nodes / n_blocks is not
+// followed and makes the result false.
+__device__ __forceinline__ bool dev_mark_subtree(const LkMap& map, int root, unsigned int n_nodes, unsigned int n_blocks,
+                                                 unsigned int* __restrict__ alive_node, unsigned int* __restrict__ alive_block) {
     int st_node[LK_MAX_LAYER + 2], st_ci[LK_MAX_LAYER + 2];
     int depth = 0;
-    st_node[0] = e.w, st_ci[0] = 0;
-    alive_node[e.w] = 1u;
+    bool ok = true;
+    st_node[0] = root, st_ci[0] = 0;
+    alive_node[root] = 1u;
     {
-        const int b = map.nodes[e.w].block;
-        if (b >= 0) alive_block[b] = 1u;
+        const int b = map.nodes[root].block;
+        if (b >= 0) {
+            if ((unsigned int)b < n_blocks) alive_block[b] = 1u;
+            else ok = false;
+        }
     }
     while (depth >= 0) {
         const int ci = st_ci[depth];
@@ -1896,14 +1883,49 @@ __global__ void __launch_bounds__(256)
         st_ci[depth] = ci + 1;
         const int child = map.nodes[st_node[depth]].child[ci];
         if (child < 0) continue;
+        if ((unsigned int)child >= n_nodes) {
+            ok = false;
+            continue;
+        }
         alive_node[child] = 1u;
         const int b = map.nodes[child].block;
-        if (b >= 0) alive_block[b] = 1u;
+        if (b >= 0) {
+            if ((unsigned int)b < n_blocks) alive_block[b] = 1u;
+            else ok = false;
+        }
         if (depth + 1 < LK_MAX_LAYER + 2) {
             ++depth;
             st_node[depth] = child, st_ci[depth] = 0;
         }
     }
+    return ok;
+}
+
+#ifdef LK_KERNELS_ELSEWHERE
+__global__ void __launch_bounds__(256)
+    lk_slide_mark_kernel(LkMap map, LkSlideBox box, unsigned int n_hash, unsigned int* __restrict__ alive_node,
+                         unsigned int* __restrict__ alive_block, lk_root_rec* __restrict__ kept,
+                         unsigned int* __restrict__ cnt /* [0] kept, [1] removed */, const unsigned int* __restrict__ drop /* per node id, or null */);
+#else
+__global__ void __launch_bounds__(256)
+    lk_slide_mark_kernel(LkMap map, LkSlideBox box, unsigned int n_hash, unsigned int* __restrict__ alive_node,
+                         unsigned int* __restrict__ alive_block, lk_root_rec* __restrict__ kept,
+                         unsigned int* __restrict__ cnt /* [0] kept, [1] removed */, const unsigned int* __restrict__ drop /* per node id, or null */) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_hash) return;
+    const int4 e = map.hash[i];
+    if (e.w < 0) return;
+    const bool should_remove = e.x > box.x_max || e.x < box.x_min || e.y > box.y_max || e.y < box.y_min ||
+                               e.z > box.z_max || e.z < box.z_min ||  // voxel_map.cc:578-579
+                               (drop && drop[e.w]);
+    if (should_remove) {
+        atomicAdd(&cnt[1], 1u);
+        return;
+    }
+    const unsigned int k = atomicAdd(&cnt[0], 1u);
+    kept[k].key[0] = e.x, kept[k].key[1] = e.y, kept[k].key[2] = e.z;
+    kept[k].node = e.w;
+    dev_mark_subtree(map, e.w, 0x7fffffffu, 0x7fffffffu, alive_node, alive_block);   // (the map's own ids: checked when they came in)
 }
 #endif
 
@@ -1911,12 +1933,12 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(256)
     lk_slide_move_nodes_kernel(LkMap map, unsigned int n_nodes, const unsigned int* __restrict__ alive_node,
                                const unsigned int* __restrict__ new_node, const unsigned int* __restrict__ new_block,
-                               lk_node_rec* __restrict__ tn, lk_plane_rec* __restrict__ tp, lk_match_rec* __restrict__ tm);
+                               lk_node_rec* __restrict__ tn, lk_plane_rec* __restrict__ tp, lk_match_rec* __restrict__ tm, int from_overlay);
 #else
 __global__ void __launch_bounds__(256)
     lk_slide_move_nodes_kernel(LkMap map, unsigned int n_nodes, const unsigned int* __restrict__ alive_node,
                                const unsigned int* __restrict__ new_node, const unsigned int* __restrict__ new_block,
-                               lk_node_rec* __restrict__ tn, lk_plane_rec* __restrict__ tp, lk_match_rec* __restrict__ tm) {
+                               lk_node_rec* __restrict__ tn, lk_plane_rec* __restrict__ tp, lk_match_rec* __restrict__ tm, int from_overlay) {
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_nodes || !alive_node[i]) return;
     const unsigned int j = new_node[i];
@@ -1927,6 +1949,10 @@ __global__ void __launch_bounds__(256)
     if (r.block >= 0) r.block = (int)new_block[r.block];
     r.list_head = -1;  // bucket-local queue state is not carried across a slide
     r.pad_[0] = 0;
+    if (from_overlay) {   // a private root's overlay-only words (LK_PAD_LIVE, _BASE, _COWBLK, _SPLIT, _SUMSRC): a root the live insert makes has zeros there
+#pragma unroll
+        for (int c = 1; c < 8; ++c) r.pad_[c] = 0;
+    }
     tn[j] = r;
     tp[j] = map.planes[i];
     tm[j] = map.match[i];

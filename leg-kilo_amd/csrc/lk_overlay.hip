@@ -120,19 +120,31 @@ __global__ void __launch_bounds__(LK_WAVE) lk_rag_pose_tap_kernel(const LkFilter
 
 extern "C" {
 
+// What lk_overlay_export and lk_overlay_commit ask before they read an overlay: the pools of a replay are there, and the handle's map still is the
+// one that replay ran against.
+static int ov_readable(lk_handle* h, const char* verb) {
+    if (!h->ov.counters || !h->ov_last_slots) return fail(h, LK_ERR_STATE, "no overlay replay's pools are held by this handle (none has run, or lk_overlay_reserve released them)");
+    // an overlay is not self-contained: split leaves keep their first points in the BASE map's blocks, lazily copied voxels their plane in the base
+    // map's plane records.  Once the handle's map has changed (lk_process_scan, lk_map_update, lk_map_slide, lk_map_import, lk_overlay_commit, ...)
+    // those ids may name other voxels: refuse instead of reading them
+    if (!h->grid_valid || h->ov_gen != h->map_gen)
+        return fail(h, LK_ERR_STATE, std::string("the handle's map has changed since the overlay replay: its overlays can no longer be ") + verb +
+                                         " (export before the map is updated, slid or imported, or replay again)");
+    return LK_OK;
+}
+// leaves the fast root pass left split (old points still in the handle's blocks) and lazily copied plane records are made whole
+static int ov_make_whole(lk_handle* h, uint32_t slot) {
+    hipLaunchKernelGGL(lk_ov_merge_split_kernel, dim3(64), dim3(LK_MB), 0, h->stream, h->map, h->ov, slot);
+    HIPCHK(h, hipGetLastError());
+    return LK_OK;
+}
+
 int lk_overlay_export(lk_handle* h, uint32_t slot, void* blob, size_t* bytes) {
     CHECK_H(h);
-    if (!h->ov.counters || !h->ov_last_slots) return fail(h, LK_ERR_STATE, "no overlay replay's pools are held by this handle (none has run, or lk_overlay_reserve released them)");
+    LKCHK(ov_readable(h, "exported"));
     if (slot >= h->ov_last_slots) return fail(h, LK_ERR_INVALID, "slot was not part of the last overlay replay");
-    // an overlay is not self-contained: split leaves keep their first points in the BASE map's blocks, lazily copied voxels their plane in the base
-    // map's plane records.  Once the handle's map has changed (lk_process_scan, lk_map_update, lk_map_slide, lk_map_import, ...) those ids may
-    // name other voxels: refuse instead of exporting them
-    if (!h->grid_valid || h->ov_gen != h->map_gen)
-        return fail(h, LK_ERR_STATE, "the handle's map has changed since the overlay replay: its overlays can no longer be exported (export before the map is updated, slid or imported, or replay again)");
     const LkOverlay& ov = h->ov;
-    // leaves the fast root pass left split (old points still in the handle's blocks) are made whole first
-    hipLaunchKernelGGL(lk_ov_merge_split_kernel, dim3(64), dim3(LK_MB), 0, h->stream, h->map, ov, slot);
-    HIPCHK(h, hipGetLastError());
+    LKCHK(ov_make_whole(h, slot));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<unsigned long long> keys(ov.hash_cap);
     HIPCHK(h, hipMemcpy(keys.data(), ov.keys + (size_t)slot * ov.hash_cap, sizeof(unsigned long long) * ov.hash_cap, hipMemcpyDeviceToHost));
@@ -151,6 +163,66 @@ int lk_overlay_export(lk_handle* h, uint32_t slot, void* blob, size_t* bytes) {
     HIPCHK(h, tmp.alloc(&m.hash, sizeof(int4) * ov.hash_cap));
     HIPCHK(h, hipMemcpy(m.hash, table.data(), sizeof(int4) * ov.hash_cap, hipMemcpyHostToDevice));
     return export_map_blob(h, m, ov.hash_cap, blob, bytes);
+}
+
+// Slot `slot`'s overlay becomes part of the handle's map, in HBM: the compaction of the map slide (MapCompact) with the base voxels the slot holds
+// privately as the ones to remove, and the slot's private records ranked behind the survivors by the same scans.  Every refusal comes before
+// compact_move, the first write to the map.
+int lk_overlay_commit(lk_handle* h, uint32_t slot, uint32_t flags) {
+    CHECK_H(h);
+    LKCHK(ov_readable(h, "committed"));
+    if (slot >= h->ov_last_slots) return fail(h, LK_ERR_INVALID, "slot was not part of the last overlay replay");
+    if (flags & ~LK_COMMIT_ADOPT_FILTER) return fail(h, LK_ERR_INVALID, "unknown flag bits (LK_COMMIT_ADOPT_FILTER is the only flag)");
+    LKCHK(join_side_streams(h));
+    const LkOverlay& ov = h->ov;
+    const LkMap pm = ov_slot_map(ov, slot);
+    LKCHK(ov_make_whole(h, slot));
+    unsigned int octr[LK_CTR_COUNT];
+    HIPCHK(h, hipMemcpyAsync(octr, pm.counters, sizeof(octr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (octr[LK_CTR_ERR]) return fail(h, LK_ERR_STATE, "the slot's overlay carries an error word: the replay that made it was refused");
+    const unsigned int pn = std::min(octr[LK_CTR_NODES], ov.nodes_cap), pb = std::min(octr[LK_CTR_BLOCKS], ov.blocks_cap);   // used ranges of the private pools (pn >= hash_cap: the root entries)
+    if (pn < ov.hash_cap) return fail(h, LK_ERR_STATE, "the slot's node counter lies below its root entries");   // (the flag arrays are sized by it)
+    MapCompact mc;
+    LKCHK(compact_begin(h, &mc, pn, pb, ov.hash_cap));
+    unsigned int* xa_node = mc.alive_node + mc.n_nodes;   // the private records' part of the flag and rank arrays
+    unsigned int* xa_block = mc.alive_block + mc.n_blocks;
+    const unsigned int* xn_node = mc.new_node + mc.n_nodes;
+    const unsigned int* xn_block = mc.new_block + mc.n_blocks;
+    const unsigned int root_grid = (ov.hash_cap + 255) / 256;
+    LAUNCH(h, "ov_commit_mark", hipLaunchKernelGGL(lk_ov_commit_mark_kernel, dim3(root_grid), dim3(256), 0, h->stream, h->map, ov, slot, pn, pb, mc.drop, xa_node, xa_block, mc.cnt + 2));
+    LKCHK(compact_mark(h, &mc, LkSlideBox{INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN}, true));   // (a box that holds every key)
+    LKCHK(compact_count(h, &mc));
+    unsigned int bad = 0, behind_roots = mc.all_nodes;   // new id of the first private CHILD record (none: the end)
+    HIPCHK(h, hipMemcpyAsync(&bad, mc.cnt + 2, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    if (pn > ov.hash_cap) HIPCHK(h, hipMemcpyAsync(&behind_roots, xn_node + ov.hash_cap, sizeof(behind_roots), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const unsigned int x_roots = behind_roots - mc.live_nodes, n_roots = mc.kept_roots + x_roots;
+    if (bad || x_roots != octr[LK_CTR_ROOTS]) return fail(h, LK_ERR_STATE, "the slot's overlay is not a whole map (an id outside its pools, or a root that was claimed and never made)");
+    if (mc.all_nodes > h->map.max_nodes || mc.all_blocks > h->map.max_blocks || 2 * (size_t)n_roots > h->hash_cap) {
+        char buf[320];
+        snprintf(buf, sizeof(buf), "the committed map needs %u nodes (%u of the map's stay, %u private), %u point blocks (%u + %u) and %u root voxels (%u + %u): the handle has max_nodes %u, max_point_blocks %u and room for %u roots",
+                 mc.all_nodes, mc.live_nodes, mc.all_nodes - mc.live_nodes, mc.all_blocks, mc.live_blocks, mc.all_blocks - mc.live_blocks, n_roots, mc.kept_roots, x_roots,
+                 h->map.max_nodes, h->map.max_blocks, h->hash_cap / 2);
+        return fail(h, LK_ERR_CAPACITY, buf);
+    }
+    LKCHK(compact_move(h, &mc));   // from here on the map changes: the grid is invalid, the replay's overlays are stale (ov_readable)
+    // the private records behind the survivors, ids renumbered by the ranks, a private root's overlay-only words cleared; a wave per block
+    LAUNCH(h, "ov_commit_nodes", hipLaunchKernelGGL(lk_slide_move_nodes_kernel, dim3((pn + 255) / 256), dim3(256), 0, h->stream, pm, pn, xa_node, xn_node, xn_block,
+                                                    h->map.nodes, h->map.planes, h->map.match, 1));
+    if (pb) LAUNCH(h, "ov_commit_blocks", hipLaunchKernelGGL(lk_slide_move_blocks_kernel, dim3(pb), dim3(64), 0, h->stream, pm, xa_block, xn_block, h->map.blocks));
+    LAUNCH(h, "ov_commit_roots", hipLaunchKernelGGL(lk_ov_commit_roots_kernel, dim3(root_grid), dim3(256), 0, h->stream, ov, slot, xa_node, xn_node, mc.live_nodes, mc.kept + mc.kept_roots));
+    if (mc.all_nodes > mc.live_nodes) {   // a lazily copied voxel's match record never was private: all appended ones are derived, as an import does
+        LkMap app = h->map;
+        app.planes += mc.live_nodes, app.match += mc.live_nodes;
+        LAUNCH(h, "derive_match", hipLaunchKernelGGL(lk_derive_match_kernel, dim3((mc.all_nodes - mc.live_nodes + 255) / 256), dim3(256), 0, h->stream, app, (int)(mc.all_nodes - mc.live_nodes)));
+    }
+    LKCHK(compact_finish(h, &mc, mc.all_nodes, mc.all_blocks, n_roots, true));
+    if ((flags & LK_COMMIT_ADOPT_FILTER) && slot != 0) {
+        HIPCHK(h, hipMemcpyAsync(h->d_filters, h->d_filters + slot, sizeof(LkFilter), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return LK_OK;
 }
 
 // ------------------------------------------------------------------ batch replay with a per-scan insert overlay

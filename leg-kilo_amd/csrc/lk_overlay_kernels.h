@@ -883,6 +883,42 @@ __global__ void __launch_bounds__(LK_MB) lk_ov_merge_split_kernel(LkMap base, Lk
 }
 #endif
 
+// ---------------------------------------------------------------- lk_overlay_commit: one slot's overlay becomes part of the handle's map
+// The compaction of the map slide (lk_map_kernels.h, MapCompact in lk_internal.h) under another predicate.  One thread per entry of the slot's key
+// table, behind lk_ov_merge_split_kernel: the base root of the same key, if there is one, is flagged in `drop` (lk_slide_mark_kernel then leaves
+// its whole subtree dead), and the private tree below the entry is flagged alive - in the part of the flag arrays that lies BEHIND the base map's
+// records (the pointers come offset), so that the scan over both parts ranks the survivors first and the private records behind them: the rank IS
+// the new id, no counter is involved.  Only what the roots reach is flagged: a private pool also holds retired blocks and its free list.
+// bad[0]: a private id outside the pools' used range was met (it is not followed).
+#ifdef LK_TU_OVERLAY   // compiled in the overlay unit only (lk_internal.h)
+__global__ void __launch_bounds__(256) lk_ov_commit_mark_kernel(LkMap base, LkOverlay ov, unsigned int slot, unsigned int n_nodes, unsigned int n_blocks,
+                                                                unsigned int* __restrict__ drop, unsigned int* __restrict__ alive_node,
+                                                                unsigned int* __restrict__ alive_block, unsigned int* __restrict__ bad) {
+    const unsigned int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= ov.hash_cap) return;
+    const unsigned long long pk = ov.keys[(size_t)slot * ov.hash_cap + r];
+    if (pk == LK_OV_EMPTY) return;
+    const LkMap pm = ov_slot_map(ov, slot);
+    if (pm.nodes[r].pad_[LK_PAD_LIVE] == 0) return;   // claimed, never made: not a root of the slot's map (the host compares the count with the slot's counter)
+    int k3[3];
+    ov_unpack_key(pk, k3);
+    const int b = hash_find(base, k3[0], k3[1], k3[2]);
+    if (b >= 0) drop[b] = 1u;
+    if (!dev_mark_subtree(pm, (int)r, n_nodes, n_blocks, alive_node, alive_block)) bad[0] = 1u;
+}
+// Behind the scan: the private roots as root records for lk_hash_insert_kernel.  The root entries are the first hash_cap node ids of a slot's pool
+// and only roots are flagged among them, so new_node[r] - first is the rank of root r among the private roots: out[rank] = {key, new id}.
+__global__ void __launch_bounds__(256) lk_ov_commit_roots_kernel(LkOverlay ov, unsigned int slot, const unsigned int* __restrict__ alive_node,
+                                                                 const unsigned int* __restrict__ new_node, unsigned int first, lk_root_rec* __restrict__ out) {
+    const unsigned int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= ov.hash_cap || !alive_node[r]) return;
+    lk_root_rec rec;
+    ov_unpack_key(ov.keys[(size_t)slot * ov.hash_cap + r], rec.key);
+    rec.node = (int)new_node[r];
+    out[new_node[r] - first] = rec;
+}
+#endif
+
 // moment sums of the BASE map's root leaves that can still take points, once per replay: one thread per entry of the root table
 #ifdef LK_TU_OVERLAY   // compiled in the overlay unit only (lk_internal.h)
 __global__ void __launch_bounds__(256) lk_ov_base_sums_kernel(LkMap base, unsigned int n_hash, LkLeafSum* __restrict__ out) {

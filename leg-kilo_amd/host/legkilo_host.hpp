@@ -381,6 +381,13 @@ class KiloPath {
                                                      msg_kind ? n_msg.data() : nullptr, d_msgs, out.data()));
         return out;
     }
+    // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
+    // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
+    // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with
+    // insert on all slots, commit the chosen one, arm the next window's priors from lk_batch_get_states_dev.
+    void commitOverlay(uint32_t slot, bool adopt_filter = false) {
+        dev_->check(lk_overlay_commit(dev_->h(), slot, adopt_filter ? LK_COMMIT_ADOPT_FILTER : 0u));
+    }
     // lk_batch_replay_runs_dev: the same runs on the FROZEN map (localisation against a finished map: no insert, no overlay, the map untouched) -
     // state, covariance and both time stamps carried across the scan boundaries.  cont (LK_RUNS_CONTINUE): the slots go on from what they hold, so
     // a run may be fed in chunks of scans, the first chunk with cont = false; the caller has not used the slots in between.  Tables as above.

@@ -128,6 +128,15 @@ typedef struct lk_pose {
     uint32_t n_updates;  /* buckets whose N>0 */
 } lk_pose;
 
+/* one time bucket of a replayed run (lk_batch_replay_runs_cloud_dev, lk_batch_replay_overlay_runs_cloud_dev) */
+typedef struct lk_bucket_pose {      /* 144 bytes */
+    double   rot[9], pos[3], vel[3]; /* first 15 doubles of the state after the bucket: the posterior if
+                                        it updated, else the state predicted to the bucket's time */
+    double   t;                      /* the bucket's absolute time, t_begin + curvature (KILO.cc:376) */
+    uint64_t first_point;            /* index into d_pts of the bucket's first point */
+    uint32_t n_points, n_effect;     /* n_effect = matched points; 0 means no update, intensity 0 */
+} lk_bucket_pose;
+
 /* ---- map blob (lk_map_export / lk_map_import; also the RCCL broadcast payload) ----
  * blob = lk_blob_header | roots[n_roots] | nodes[n_nodes] | planes[n_nodes] | blocks[n_blocks]
  * All little-endian PODs below; node ids index nodes[]/planes[]; block ids index blocks[]. */
@@ -465,6 +474,26 @@ int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t
 #define LK_RUNS_CONTINUE 1u
 int lk_batch_replay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin,
                              int msg_kind, const uint32_t* n_msg, const void* d_msgs, uint32_t flags, lk_pose* out);
+/* The two run replays with what KILO::process returns beside the pose: the state after EVERY time bucket and the scans registered into the world
+ * frame, every bucket's points under that bucket's own state (KILO.cc:130-133, :219-223 - the placement that removes the motion distortion inside a
+ * scan).  Arguments, refusals and messages of lk_batch_replay_runs_dev / lk_batch_replay_overlay_runs_dev, which ARE these entries with both outputs
+ * NULL; slots, out[] and overlays are left bit for bit as those leave them.
+ * d_world_out (DEVICE, may be NULL, 16-byte aligned): one x y z intensity record per point, index-aligned with d_pts (lk_run_scans_dev's layout) -
+ * (float)(R_b (ext_R p + ext_t) + p_b) under the state after the point's bucket, intensity 255.0f where that bucket updated (n_effect > 0), else 0.0f.
+ * scan_bucket_off (HOST, n_scans + 1 words, may be NULL): scan s owns the records scan_bucket_off[s] .. scan_bucket_off[s+1) of the bucket table.
+ * The bucket table (one lk_bucket_pose per time bucket, in d_pts order) is the library's: with either output given the call records it, and
+ * lk_runs_bucket_poses(_dev) copy records first_bucket .. first_bucket + n out of it until the handle's next batch replay of ANY kind.  A call with
+ * LK_RUNS_CONTINUE records its own chunk only.  With both outputs NULL nothing is recorded.
+ * LK_ERR_INVALID: d_world_out not 16-byte aligned (before the first write to a slot), a record range past the table's count; LK_ERR_STATE from the
+ * getters: the handle's last batch replay recorded nothing. */
+int lk_batch_replay_runs_cloud_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
+                                   const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, uint32_t flags, lk_pose* out,
+                                   float* d_world_out, uint32_t* scan_bucket_off);
+int lk_batch_replay_overlay_runs_cloud_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
+                                           const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out,
+                                           float* d_world_out, uint32_t* scan_bucket_off);
+int lk_runs_bucket_poses_dev(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* d_out);
+int lk_runs_bucket_poses(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* out);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

@@ -123,6 +123,27 @@ def pose_dtype():
     return np.dtype([("rot", "<f8", 9), ("pos", "<f8", 3), ("vel", "<f8", 3), ("n_effect", "<u8"), ("n_buckets", "<u4"), ("n_updates", "<u4")])
 
 
+class lk_bucket_pose(C.Structure):
+    _fields_ = [
+        ("rot", C.c_double * 9),
+        ("pos", C.c_double * 3),
+        ("vel", C.c_double * 3),
+        ("t", C.c_double),
+        ("first_point", C.c_uint64),
+        ("n_points", C.c_uint32),
+        ("n_effect", C.c_uint32),
+    ]
+
+
+def bucket_pose_dtype():
+    """numpy view of lk_bucket_pose (144 B): the records of lk_runs_bucket_poses."""
+    import numpy as np
+
+    dt = np.dtype([("rot", "<f8", 9), ("pos", "<f8", 3), ("vel", "<f8", 3), ("t", "<f8"), ("first_point", "<u8"), ("n_points", "<u4"), ("n_effect", "<u4")])
+    assert dt.itemsize == C.sizeof(lk_bucket_pose) == 144
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

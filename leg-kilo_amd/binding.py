@@ -27,6 +27,7 @@ EXPORTS = [
     "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
     "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
     "lk_batch_replay_runs_dev", "lk_overlay_commit",
+    "lk_batch_replay_runs_cloud_dev", "lk_batch_replay_overlay_runs_cloud_dev", "lk_runs_bucket_poses_dev", "lk_runs_bucket_poses",
 ]
 
 
@@ -579,8 +580,54 @@ class LegKiloHip:
                                                           _p(nm), C.c_void_p(d_msgs) if d_msgs else None, poses))
         return list(poses[:n_scans]) if want_poses else None
 
-    def _replay_runs_staged(self, entry, runs, t_begins, xs, Ps, imus, kins, **kw):
-        """What the two run conveniences share: priors, flatten_runs, points and messages -> HBM, entry(...), the poses run by run."""
+    def _runs_cloud_call(self, overlay, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, flags, want_poses, d_world, want_offsets):
+        """The two _cloud entries' call: (poses or None, scan_bucket_off uint32 [n_scans + 1] or None)."""
+        ro = np.ascontiguousarray(run_off, dtype=np.uint32)
+        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
+        n_scans = len(so) - 1
+        tb = _f64(t_begins)
+        assert len(tb) == n_scans and len(ro) >= 1
+        nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
+        assert nm is None or len(nm) == n_scans
+        poses = (abi.lk_pose * max(n_scans, 1))() if want_poses else None
+        sbo = np.zeros(n_scans + 1, dtype=np.uint32) if want_offsets else None
+        head = (self.h, C.c_void_p(d_pts), C.c_size_t(len(ro) - 1), _p(ro), _p(so), _p(tb), C.c_int(msg_kind), _p(nm), C.c_void_p(d_msgs) if d_msgs else None)
+        tail = (poses, C.c_void_p(d_world) if d_world else None, _p(sbo))
+        if overlay:
+            self._chk(self.L.lk_batch_replay_overlay_runs_cloud_dev(*head, *tail))
+        else:
+            self._chk(self.L.lk_batch_replay_runs_cloud_dev(*head, C.c_uint32(flags), *tail))
+        return (list(poses[:n_scans]) if want_poses else None), sbo
+
+    def batch_replay_runs_cloud_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, cont=False, want_poses=True, flags=None,
+                                    d_world=0, want_offsets=True):
+        """batch_replay_runs_dev with what KILO::process returns beside the pose (lk_batch_replay_runs_cloud_dev): d_world - device pointer (16-byte
+        aligned, 0: none) to one x y z intensity float record per point of d_pts, each point under the state after ITS time bucket, intensity 255 where
+        that bucket updated; want_offsets: the scans' record ranges in the handle's bucket table (runs_bucket_poses).  Either output makes the call
+        record the table; with neither this is batch_replay_runs_dev.  Returns (poses, scan_bucket_off or None)."""
+        fl = (LK_RUNS_CONTINUE if cont else 0) if flags is None else int(flags)
+        return self._runs_cloud_call(False, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, fl, want_poses, d_world, want_offsets)
+
+    def batch_replay_overlay_runs_cloud_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, want_poses=True, d_world=0,
+                                            want_offsets=True):
+        """batch_replay_overlay_runs_dev with the registered cloud and the bucket table (lk_batch_replay_overlay_runs_cloud_dev): outputs as for
+        batch_replay_runs_cloud_dev.  Returns (poses, scan_bucket_off or None)."""
+        return self._runs_cloud_call(True, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, 0, want_poses, d_world, want_offsets)
+
+    def runs_bucket_poses_dev(self, first_bucket, n, d_out):
+        """Records first_bucket : first_bucket + n of the last _cloud run replay's bucket table -> device memory at d_out (lk_runs_bucket_poses_dev)."""
+        self._chk(self.L.lk_runs_bucket_poses_dev(self.h, C.c_uint64(first_bucket), C.c_size_t(n), C.c_void_p(d_out) if d_out else None))
+
+    def runs_bucket_poses(self, first_bucket, n):
+        """The same records as a numpy array of abi.bucket_pose_dtype() (lk_runs_bucket_poses)."""
+        out = np.zeros(n, dtype=abi.bucket_pose_dtype())
+        self._chk(self.L.lk_runs_bucket_poses(self.h, C.c_uint64(first_bucket), C.c_size_t(n), _p(out)))
+        return out
+
+    def _replay_runs_staged(self, entry, runs, t_begins, xs, Ps, imus, kins, cloud=False, bucket_poses=False, **kw):
+        """What the two run conveniences share: priors, flatten_runs, points and messages -> HBM, entry(...), the poses run by run.  cloud /
+        bucket_poses: `entry` is the _cloud form; returns (poses run by run, dict) with "cloud" (float32 [n, 4], in the order of the flattened
+        points) and / or "bucket_poses" (all records) + "scan_bucket_off"."""
         if xs is not None:
             self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
         t = flatten_runs(runs, t_begins, imus, kins)
@@ -594,16 +641,34 @@ class LegKiloHip:
                 d_msgs = self.device_malloc(t["msgs"].nbytes)
                 dptrs.append(d_msgs)
                 self.h2d(d_msgs, t["msgs"])
-            poses = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, **kw)
-            return [poses[int(a):int(b)] for a, b in zip(t["run_off"][:-1], t["run_off"][1:])]
+            extra = None
+            if cloud or bucket_poses:
+                extra = {}
+                d_world = 0
+                if cloud:
+                    d_world = self.device_malloc(16 * len(t["pts"]))
+                    dptrs.append(d_world)
+                poses, sbo = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, d_world=d_world, **kw)
+                if cloud:
+                    extra["cloud"] = np.zeros((len(t["pts"]), 4), dtype=np.float32)
+                    self.d2h(extra["cloud"], d_world)
+                if bucket_poses:
+                    extra["bucket_poses"], extra["scan_bucket_off"] = self.runs_bucket_poses(0, int(sbo[-1])), sbo
+            else:
+                poses = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, **kw)
+            by_run = [poses[int(a):int(b)] for a, b in zip(t["run_off"][:-1], t["run_off"][1:])]
+            return by_run if extra is None else (by_run, extra)
         finally:
             for d in dptrs:
                 self.device_free(d)
 
-    def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None):
+    def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cloud=False, bucket_poses=False):
         """Convenience: runs = a list of runs, each a list of host scans (lk_point arrays, time-sorted, any sizes); t_begins, imus / kins: the same
         nesting (one start time, one message array per scan) -> HBM -> batch_replay_overlay_runs_dev.  Optional priors, one per run.  Returns the
-        poses run by run (a list of lists)."""
+        poses run by run (a list of lists); with cloud / bucket_poses: (those, dict) - the registered cloud and / or the bucket table of
+        batch_replay_overlay_runs_cloud_dev (_replay_runs_staged)."""
+        if cloud or bucket_poses:
+            return self._replay_runs_staged(self.batch_replay_overlay_runs_cloud_dev, runs, t_begins, xs, Ps, imus, kins, cloud=cloud, bucket_poses=bucket_poses)
         return self._replay_runs_staged(self.batch_replay_overlay_runs_dev, runs, t_begins, xs, Ps, imus, kins)
 
     def batch_replay_runs_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, cont=False, want_poses=True, flags=None):
@@ -624,10 +689,13 @@ class LegKiloHip:
                                                   _p(nm), C.c_void_p(d_msgs) if d_msgs else None, C.c_uint32(fl), poses))
         return list(poses[:n_scans]) if want_poses else None
 
-    def batch_replay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cont=False):
+    def batch_replay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cont=False, cloud=False, bucket_poses=False):
         """Convenience: the nested host inputs of batch_replay_overlay_runs -> HBM -> batch_replay_runs_dev (frozen map).  Optional priors, one per
-        run (not with cont: a continued run goes on from what its slot holds).  Returns the poses run by run (a list of lists)."""
+        run (not with cont: a continued run goes on from what its slot holds).  Returns the poses run by run (a list of lists); with cloud /
+        bucket_poses: (those, dict), as batch_replay_overlay_runs."""
         assert not (cont and xs is not None), "a continued run keeps its slot's state: no priors"
+        if cloud or bucket_poses:
+            return self._replay_runs_staged(self.batch_replay_runs_cloud_dev, runs, t_begins, xs, Ps, imus, kins, cloud=cloud, bucket_poses=bucket_poses, cont=cont)
         return self._replay_runs_staged(self.batch_replay_runs_dev, runs, t_begins, xs, Ps, imus, kins, cont=cont)
 
     def overlay_reserve(self, roots_per_scan=0, nodes_per_scan=0, blocks_per_scan=0):

@@ -1,6 +1,7 @@
 // legkilo_hip.hip - the main translation unit of liblegkilo_hip.so (see lk_internal.h)
 #define LK_TU_MAIN 1
 #include "lk_internal.h"
+#include "lk_cloud_layout.h"
 
 thread_local std::string g_err;
 
@@ -443,6 +444,8 @@ __device__ __forceinline__ void dev_scan_wave(const LkMap& map, const LkParams& 
         __syncthreads();
         ++b;
         if constexpr (RUN) {
+            if (rg.bucket_pose)   // (the _cloud entries: the state behind this bucket, updated or not; its time and points read again from the tables - nothing more is kept alive over the update)
+                rag_write_bucket(rg.bucket_pose + rg.bstart[slot] + (unsigned int)(b - 1), sm.x, T[b - 1], po[b - 1], (unsigned int)(po[b] - po[b - 1]), (unsigned int)last_N, lane);
             if ((unsigned int)b == b_end) {   // that was the scan's last bucket: its pose, its counters (plain vector stores, as rag_write_pose's)
                 lk_pose* p = rg.scan_pose + sc;
                 if (lane < 15) reinterpret_cast<double*>(p)[lane] = sm.x[lane];
@@ -570,11 +573,74 @@ __global__ void __launch_bounds__(LK_WAVE, LK_UPD_WAVES)
     if (b >= nbk) return;
     LkFilter* f = &filters[slot];
     const LkRagBucket rb = rag_bucket(rg, slot, b, false);
+    if (rg.run_scan && rg.bucket_pose) {   // (the _cloud entries: the state the update has left behind this bucket)
+        const unsigned long long* po = rag_pt_off(rg, slot);
+        rag_write_bucket(rg.bucket_pose + rg.bstart[slot] + (unsigned int)b, f->x, rag_t(rg, slot)[b], po[b], (unsigned int)(po[b + 1] - po[b]), (unsigned int)f->last_N, lane);
+    }
     if (rb.pose) {
         rag_write_pose(rb.pose, f->x, f, lane);
         if (lane == 0 && b + 1 < nbk) f->n_buckets = 0u, f->n_updates = 0u, f->n_effect = 0ull;
     }
     if (b + 1 < nbk) dev_update_wave(f, sm, nullptr, 0, 0.0, Q, rag_t(rg, slot)[b + 1], 2);
+}
+
+// Registration of replayed runs (the _cloud entries): point i of d_pts under the state behind ITS bucket - x y z as floats, intensity 255 where that bucket
+// updated, else 0 (KILO.cc:130-133, :219-223; lk_run_scans_dev's record).  16 B in, 16 B out per point; what has to be found is the point's bucket.  Points
+// lie in bucket order and no bucket is empty, so the LK_REG_TILE points of a workgroup from point p0 on lie in the buckets g0 .. g0 + LK_REG_TILE - 1 at
+// most, g0 = the bucket of p0: ONE search of the flat pt_off table per workgroup (the same in each of its waves, 64 probes a round), then that window's offsets and - for the
+// buckets that do begin inside the tile - the 12 pose doubles and n_effect of their records go to LDS, and every lane searches the window there.
+__global__ void __launch_bounds__(LK_REG_TILE)
+    lk_register_cloud_kernel(const lk_point* __restrict__ pts, unsigned long long n, const unsigned long long* __restrict__ pt_off, unsigned int B,
+                             const lk_bucket_pose* __restrict__ rec, LkParams pr, float* __restrict__ world) {
+    typedef float lk_f4v __attribute__((ext_vector_type(4)));
+    __shared__ unsigned long long s_off[LK_REG_TILE + 1];
+    __shared__ double s_pose[LK_REG_TILE * 12];
+    __shared__ unsigned int s_ne[LK_REG_TILE];
+    const unsigned int tid = threadIdx.x;
+    const unsigned long long p0 = (unsigned long long)blockIdx.x * LK_REG_TILE;
+    if (p0 >= n || B == 0u) return;
+    const unsigned int np = (unsigned int)((n - p0 < (unsigned long long)LK_REG_TILE) ? n - p0 : (unsigned long long)LK_REG_TILE);
+    // (the point itself does not wait for its bucket: its load goes out first)
+    lk_f4v p = {0.f, 0.f, 0.f, 0.f};
+    if (tid < np) p = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(pts) + p0 + tid);
+    // the search, the same in every wave: 64 probes a round, one per lane, at even steps through what is left - offsets increase, so the probes at or below
+    // p0 are a prefix and their number names the interval: four dependent loads at 1.5 M buckets where a bisection makes 21
+    unsigned int g0 = 0u, hi = B;   // pt_off[g0] <= p0 < pt_off[hi]  (pt_off[0] = 0, pt_off[B] = n)
+    while (hi - g0 > 1u) {
+        const unsigned int step = (hi - g0 + LK_WAVE - 1) / LK_WAVE;
+        const unsigned long long at = (unsigned long long)g0 + (unsigned long long)((tid & (LK_WAVE - 1)) + 1u) * step;
+        const unsigned int below = (unsigned int)__popcll(__ballot(at < hi && pt_off[at] <= p0));
+        const unsigned long long next = (unsigned long long)g0 + (unsigned long long)(below + 1u) * step;
+        g0 += below * step;
+        if (next < hi) hi = (unsigned int)next;
+    }
+    for (unsigned int k = tid; k <= np; k += LK_REG_TILE) s_off[k] = pt_off[(g0 + k < B) ? g0 + k : B];
+    __syncthreads();
+    // the window's buckets that hold a point of this tile: bucket g0, and those that begin below p0 + np (offsets increase: the count is their number)
+    const unsigned int nbw = (unsigned int)__syncthreads_count(tid < np && g0 + tid < B && s_off[tid] < p0 + np);
+    for (unsigned int e = tid; e < nbw * 12u; e += LK_REG_TILE) {
+        const unsigned int k = e / 12u;
+        s_pose[e] = reinterpret_cast<const double*>(rec + g0 + k)[e - 12u * k];   // rot, pos: the record's first 12 doubles
+    }
+    if (tid < nbw) s_ne[tid] = rec[g0 + tid].n_effect;
+    __syncthreads();
+    if (tid >= np) return;
+    const unsigned long long i = p0 + tid;
+    unsigned int lo = 0u, up = nbw;   // s_off[lo] <= i < s_off[up]
+    while (up - lo > 1u) {
+        const unsigned int mid = (lo + up) >> 1;
+        if (s_off[mid] <= i) lo = mid;
+        else up = mid;
+    }
+    BucketConst bc;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) bc.R[j] = s_pose[12u * lo + j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) bc.p[j] = s_pose[12u * lo + 9 + j];
+    const V3 w = point_world(p.x, p.y, p.z, bc, pr);
+    lk_f4v o;
+    o.x = (float)w.x, o.y = (float)w.y, o.z = (float)w.z, o.w = s_ne[lo] ? 255.0f : 0.0f;
+    __builtin_nontemporal_store(o, reinterpret_cast<lk_f4v*>(world) + i);
 }
 
 // The map as the batch-replay kernels see it: with the dense root grid when it can be built (LkMap::grid).  The grid is derived
@@ -1990,6 +2056,7 @@ int lk_batch_replay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, siz
     LKCHK(live_buckets(h, bucket_off, n_buckets, live));   // all checks before the first enqueue
     LkMap fmap;
     LKCHK(frozen_map(h, &fmap));
+    h->bucket_n = 0;   // (a batch replay that records no buckets: lk_runs_bucket_poses)
     LKCHK(zero_scan_counters(h, 0, (uint32_t)n_scans));
     hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, h->stream, h->d_filters, S, t_begin);
     HIPCHK(h, hipGetLastError());
@@ -2062,6 +2129,7 @@ static int ragged_launch(lk_handle* h, const lk_point* d_pts, size_t S, const Lk
     LkMap fmap;
     int rc = frozen_map(h, &fmap);
     if (rc) return rc;
+    h->bucket_n = 0;   // (the _cloud entry sets it behind its replay)
     rc = zero_scan_counters(h, 0, (uint32_t)S);
     if (rc) return rc;
     hipStream_t st = h->stream;
@@ -2368,6 +2436,10 @@ struct RunBatch {
     LkRagged rg;                                   // the runs' tables: bstart = the runs' first buckets, ldb = most buckets of a run
     const double* d_rt = nullptr;                  // [R] the runs' start times
     unsigned int biggest = 0, most_run = 0;        // largest bucket (points), most buckets of a run
+    unsigned int n_buckets = 0;                    // flat buckets of the batch
+    std::vector<uint32_t> h_bs;                    // the scans' first flat buckets, [S + 1] (record(): the _cloud entries)
+    int record(lk_handle* h, bool on);
+    int finish(lk_handle* h, const lk_point* d_pts, float* d_world_out, uint32_t* scan_bucket_off);
     int build(lk_handle* h, const lk_point* d_pts, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin, int msg_kind, const uint32_t* n_msg,
               const void* d_msgs);
 };
@@ -2421,7 +2493,7 @@ int RunBatch::build(lk_handle* h, const lk_point* d_pts, const uint32_t* run_off
     unsigned int st[8];
     HIPCHK(h, hipMemcpyAsync(st, bt.st, 32, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    biggest = st[1], most_run = st[5];
+    biggest = st[1], most_run = st[5], n_buckets = st[0];
     if (st[3])
         return fail(h, LK_ERR_INVALID, "scan " + std::to_string(S - st[3]) + " is not sorted by time (curvature must be non-decreasing within a scan, and finite)");
     if (biggest > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "bucket exceeds max_scan_points");
@@ -2437,6 +2509,35 @@ int RunBatch::build(lk_handle* h, const lk_point* d_pts, const uint32_t* run_off
     d_rt = rt;
     return LK_OK;
 }
+// The _cloud entries, ahead of the launches (and behind every refusal the host can make): room for the batch's bucket records in the handle's table, which
+// the kernels then fill (LkRagged::bucket_pose), and the scans' first buckets for scan_bucket_off.  A table that has to grow loses its old records.
+int RunBatch::record(lk_handle* h, bool on) {
+    if (!on) return LK_OK;
+    const size_t bytes = lk_cloud_table_bytes(n_buckets, sizeof(lk_bucket_pose));
+    if (bytes > h->bucket_tab.cap) h->bucket_n = 0;
+    LKCHK(reserve(h, h->bucket_tab, bytes, bytes / 4));
+    rg.bucket_pose = static_cast<lk_bucket_pose*>(h->bucket_tab.p);
+    h_bs.resize(S + 1);
+    HIPCHK(h, hipMemcpyAsync(h_bs.data(), rg.scan_b, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+// ... and behind a replay that has succeeded: the table is the handle's last recording, the scans' ranges in it go to the caller, and the cloud - every
+// point under its bucket's record - is one launch on the handle's stream (not made without d_world_out).
+int RunBatch::finish(lk_handle* h, const lk_point* d_pts, float* d_world_out, uint32_t* scan_bucket_off) {
+    if (!rg.bucket_pose) return LK_OK;
+    if (lk_cloud_scan_offsets(h_bs.data(), S, scan_bucket_off) != (uint64_t)n_buckets) return fail(h, LK_ERR_STATE, "bucket tables: the scans' first buckets do not add up");
+    h->bucket_n = n_buckets;
+    if (!d_world_out) return LK_OK;
+    LAUNCH(h, "register_cloud", hipLaunchKernelGGL(lk_register_cloud_kernel, dim3(lk_cloud_tiles(n)), dim3(LK_REG_TILE), 0, h->stream, d_pts, (unsigned long long)n,
+                                                   rg.pt_off, n_buckets, rg.bucket_pose, h->pr, d_world_out));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+static int cloud_args_check(lk_handle* h, const float* d_world_out) {
+    if ((uintptr_t)d_world_out & 15u) return fail(h, LK_ERR_INVALID, "d_world_out must be 16-byte aligned");
+    return LK_OK;
+}
 
 // Batch replay WITH insert of whole recorded runs: run r = the scans run_off[r] .. run_off[r+1) on filter slot r, each scan what
 // lk_batch_replay_overlay_ragged_dev does for one - but the slot's state, covariance, times and overlay survive the scan boundary, as KILO's members do
@@ -2444,14 +2545,24 @@ int RunBatch::build(lk_handle* h, const lk_point* d_pts, const uint32_t* run_off
 // out[s]: the pose after scan s, its counters that scan's alone.
 int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
                                      const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out) {
+    return lk_batch_replay_overlay_runs_cloud_dev(h, d_pts, n_runs, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs, out, nullptr, nullptr);
+}
+// ... with the state behind every bucket recorded in the handle's bucket table (either output given) and the scans registered under those states
+// (d_world_out): RunBatch::record / finish.  With both NULL this is the entry above, kernel for kernel.
+int lk_batch_replay_overlay_runs_cloud_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off,
+                                           const double* t_begin, int msg_kind, const uint32_t* n_msg, const void* d_msgs, lk_pose* out,
+                                           float* d_world_out, uint32_t* scan_bucket_off) {
     CHECK_H(h);
+    LKCHK(cloud_args_check(h, d_world_out));
     RunBatch rb;
     LKCHK(runs_check(h, d_pts, n_runs, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs, &rb));
     LkMap fmap;   // (asked here, ahead of the tables: a handle without the grid is refused before anything is built)
     LKCHK(frozen_map(h, &fmap));
     if (!fmap.grid_on) return fail(h, LK_ERR_STATE, "overlay replay needs the frozen-map grid (root keys' bounding box too large, LEGKILO_GRID=0, or out of device memory)");
     LKCHK(rb.build(h, d_pts, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs));
-    return overlay_ragged_launch(h, d_pts, rb.R, rb.rg, rb.d_rt, (int)rb.biggest, (size_t)rb.most_run, nullptr, rb.max_run_pts, msg_kind, out, rb.S);
+    LKCHK(rb.record(h, d_world_out || scan_bucket_off));
+    LKCHK(overlay_ragged_launch(h, d_pts, rb.R, rb.rg, rb.d_rt, (int)rb.biggest, (size_t)rb.most_run, nullptr, rb.max_run_pts, msg_kind, out, rb.S));
+    return rb.finish(h, d_pts, d_world_out, scan_bucket_off);
 }
 
 // The same runs on the FROZEN map - no insert, no overlay, the handle's map unchanged: per scan what lk_batch_replay_scans_dev does for one (grid if
@@ -2460,14 +2571,40 @@ int lk_batch_replay_overlay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t
 // split at any scan boundary into consecutive calls gives the bits of one call.  Every check comes before the first write to a slot.
 int lk_batch_replay_runs_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin,
                              int msg_kind, const uint32_t* n_msg, const void* d_msgs, uint32_t flags, lk_pose* out) {
+    return lk_batch_replay_runs_cloud_dev(h, d_pts, n_runs, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs, flags, out, nullptr, nullptr);
+}
+int lk_batch_replay_runs_cloud_dev(lk_handle* h, const lk_point* d_pts, size_t n_runs, const uint32_t* run_off, const uint64_t* scan_off, const double* t_begin,
+                                   int msg_kind, const uint32_t* n_msg, const void* d_msgs, uint32_t flags, lk_pose* out, float* d_world_out,
+                                   uint32_t* scan_bucket_off) {
     CHECK_H(h);
+    LKCHK(cloud_args_check(h, d_world_out));
     if (flags & ~LK_RUNS_CONTINUE) return fail(h, LK_ERR_INVALID, "unknown flag bits (LK_RUNS_CONTINUE is the only one)");
     RunBatch rb;
     LKCHK(runs_check(h, d_pts, n_runs, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs, &rb));
     LKCHK(rb.build(h, d_pts, run_off, scan_off, t_begin, msg_kind, n_msg, d_msgs));
     if (msg_kind && rb.biggest > (unsigned int)LK_SCAN_WAVE_MAX)
         return fail(h, LK_ERR_INVALID, "IMU / kinematic messages between buckets are only replayed for scans whose buckets hold <= 512 points");
-    return ragged_launch(h, d_pts, rb.R, rb.rg, (flags & LK_RUNS_CONTINUE) ? nullptr : rb.d_rt, (int)rb.biggest, (size_t)rb.most_run, nullptr, msg_kind, out, rb.S);
+    LKCHK(rb.record(h, d_world_out || scan_bucket_off));
+    LKCHK(ragged_launch(h, d_pts, rb.R, rb.rg, (flags & LK_RUNS_CONTINUE) ? nullptr : rb.d_rt, (int)rb.biggest, (size_t)rb.most_run, nullptr, msg_kind, out, rb.S));
+    return rb.finish(h, d_pts, d_world_out, scan_bucket_off);
+}
+// Records first_bucket .. first_bucket + n of the table the handle's last batch replay recorded (a _cloud run replay; anything else records nothing).
+static int bucket_poses_copy(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* out, hipMemcpyKind kind) {
+    if (!h->bucket_n) return fail(h, LK_ERR_STATE, "the handle's last batch replay recorded no bucket poses (lk_batch_replay_runs_cloud_dev / lk_batch_replay_overlay_runs_cloud_dev do)");
+    if (!lk_cloud_range_ok(first_bucket, n, h->bucket_n)) return fail(h, LK_ERR_INVALID, "bucket range ends past the " + std::to_string(h->bucket_n) + " records of the table");
+    if (n == 0) return LK_OK;
+    if (!out) return fail(h, LK_ERR_INVALID, "null argument");
+    HIPCHK(h, hipMemcpyAsync(out, static_cast<const lk_bucket_pose*>(h->bucket_tab.p) + first_bucket, sizeof(lk_bucket_pose) * n, kind, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+int lk_runs_bucket_poses_dev(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* d_out) {
+    CHECK_H(h);
+    return bucket_poses_copy(h, first_bucket, n, d_out, hipMemcpyDeviceToDevice);
+}
+int lk_runs_bucket_poses(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* out) {
+    CHECK_H(h);
+    return bucket_poses_copy(h, first_bucket, n, out, hipMemcpyDeviceToHost);
 }
 
 // The tables of a live run (RunTables): the same CSR tables over the run's points - d_pts is the run's FIRST point - followed by the per-scan
@@ -2536,6 +2673,7 @@ int lk_batch_replay_async_dev(lk_handle* h, const lk_point* d_pts, uint32_t firs
             if (h->side[i]) HIPCHK(h, hipStreamSynchronize(h->side[i]));
     }
     h->async_n = n_scans;
+    h->bucket_n = 0;
     const uint32_t ring = (first_slot / (uint32_t)n_scans) % 3u;
     hipStream_t st = ring == 0 ? h->stream : h->side[ring - 1];
     LkFilter* fl = h->d_filters + first_slot;

@@ -173,6 +173,7 @@ struct LkRagged {
     const unsigned int* run_scan = nullptr;   // [S + 1]
     const unsigned int* scan_b = nullptr;     // [n_scans + 1]
     lk_pose* scan_pose = nullptr;             // [n_scans]: the pose after a scan's last bucket, its counters that scan's alone
+    lk_bucket_pose* bucket_pose = nullptr;    // optional [flat buckets] (the _cloud entries): the state after bucket b of slot r at bstart[r] + b
 };
 
 __device__ __forceinline__ int rag_nb(const LkRagged& rg, int slot) {
@@ -221,6 +222,12 @@ __device__ __forceinline__ LkRagBucket rag_bucket(const LkRagged& rg, int slot, 
 __device__ __forceinline__ void rag_write_pose(lk_pose* p, const double* x, const LkFilter* f, int lane) {
     if (lane < 15) reinterpret_cast<double*>(p)[lane] = x[lane];
     if (lane == 0) p->n_effect = f->n_effect, p->n_buckets = f->n_buckets, p->n_updates = f->n_updates;
+}
+// The record of one bucket of a run (rg.bucket_pose): the same 15 doubles behind the bucket's update or non-update, then the bucket's time, its
+// first point, its points and its matches (N: 0 = no update) as the words of one lane.  Plain vector stores.
+__device__ __forceinline__ void rag_write_bucket(lk_bucket_pose* r, const double* x, double t, unsigned long long first, unsigned int n, unsigned int N, int lane) {
+    if (lane < 15) reinterpret_cast<double*>(r)[lane] = x[lane];
+    if (lane == 0) r->t = t, r->first_point = first, r->n_points = n, r->n_effect = N;
 }
 
 // ---------------------------------------------------------------- small fp64 helpers

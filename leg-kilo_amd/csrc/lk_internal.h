@@ -46,6 +46,7 @@ static_assert(sizeof(lk_plane_rec) == 256, "plane record must be 256 B");
 static_assert(sizeof(lk_node_rec) == 128, "node record must be 128 B");
 static_assert(sizeof(lk_pt_rec) == 72, "point record must be 72 B");
 static_assert(sizeof(lk_point) == 16, "scan point must be 16 B");
+static_assert(sizeof(lk_bucket_pose) == 144, "bucket record must be 144 B");
 
 struct ProfEntry {
     uint64_t launches = 0;
@@ -142,6 +143,8 @@ struct lk_handle {
     DevBuf query;                                         // lk_match_points: inputs + outputs of a query
     DevBuf ov_res;                                        // scan-resident recorded-run replay with insert: [S] next bucket, [S] bucket with fallback items, stopped-scan counter
     unsigned int ov_res_rounds = 0;                       // launches of the scan-resident kernel in the last such replay
+    DevBuf bucket_tab;                                    // lk_bucket_pose[flat buckets] of the last _cloud run replay (lk_runs_bucket_poses)
+    size_t bucket_n = 0;                                  // its records; 0: the handle's last batch replay recorded nothing
     unsigned int* d_ov_status = nullptr;
     // input order of device-resident batches (lk_batch_order): the batches the frozen-map batch entries have seen, with the library's voxel-ordered copy
     struct OrdEntry {

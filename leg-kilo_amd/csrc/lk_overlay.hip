@@ -116,6 +116,16 @@ __global__ void __launch_bounds__(LK_WAVE) lk_rag_pose_tap_kernel(const LkFilter
     const LkRagBucket rb = rag_bucket(rg, slot, b, false);
     if (rb.pose) rag_write_pose(rb.pose, filters[slot].x, &filters[slot], (int)threadIdx.x);
 }
+// Runs launch by launch, small buckets and large (the _cloud entries only): the record of bucket b of every run that has one, from the filter record
+// as the update (lk_rag_ov_front_kernel's, lk_update_wave_ragged_kernel's) has just left it - the insert behind it reads that record and changes none of it.
+__global__ void __launch_bounds__(LK_WAVE) lk_rag_bucket_tap_kernel(const LkFilter* __restrict__ filters, LkRagged rg, int b) {
+    const int slot = blockIdx.x;
+    if (!(rg.run_scan && rg.bucket_pose) || b >= rag_nb(rg, slot)) return;
+    const LkFilter* f = &filters[slot];
+    const unsigned long long* po = rag_pt_off(rg, slot);
+    rag_write_bucket(rg.bucket_pose + rg.bstart[slot] + (unsigned int)b, f->x, rag_t(rg, slot)[b], po[b], (unsigned int)(po[b + 1] - po[b]), (unsigned int)f->last_N,
+                     (int)threadIdx.x);
+}
 }   // extern "C++"
 
 extern "C" {
@@ -469,6 +479,7 @@ template <class Enqueue>
 static int ov_replay(lk_handle* h, int S, size_t n_pts_scan, size_t biggest, const double* d_tbegin, double t_begin, lk_pose* out, Enqueue&& enqueue) {
     LkMap fmap;
     LKCHK(ov_replay_begin(h, S, n_pts_scan, biggest, &fmap));
+    h->bucket_n = 0;   // (the _cloud entry sets it behind its replay)
     for (int attempt = 0;; ++attempt) {
         LKCHK(ov_attempt_begin(h, S, fmap, d_tbegin, t_begin));
         LKCHK(enqueue(fmap));
@@ -622,6 +633,7 @@ static int ov_rag_small_launches(lk_handle* h, int S, const LkMap& fmap, const L
     for (size_t b = 0; b < ldb; ++b) {
         const LkPtSrc src = {d_pts, 0, 0, rg.pt_off, rg.nb, rg.ldb, (int)b, nullptr, rg.bstart};
         LAUNCH(h, "rag_ov_front", hipLaunchKernelGGL(front, dim3(S), dim3(LK_WAVE), 0, h->stream, fmap, ov, h->pr, h->d_filters, h->d_Q, rg, d_pts, (int)b, msg_kind));
+        if (rg.run_scan && rg.bucket_pose) LAUNCH(h, "rag_bucket_tap", hipLaunchKernelGGL(lk_rag_bucket_tap_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, rg, (int)b));
         LAUNCH(h, "ov_mid", hipLaunchKernelGGL(lk_ov_mid_kernel<true>, dim3(S), dim3(LK_MB), 0, h->stream, fmap, ov, h->pr, h->d_filters, src));
         LAUNCH(h, "ov_tail", hipLaunchKernelGGL(lk_ov_tail_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, fmap, ov, h->pr, h->d_filters, src));
         LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(S, 128)), dim3(LK_MB), 0, h->stream, ov, h->pr, h->d_filters, src, S));
@@ -641,6 +653,7 @@ static int ov_rag_large_launches(lk_handle* h, int S, const LkMap& fmap, const L
         LAUNCH(h, "ov_residual", hipLaunchKernelGGL(res_kernel, dim3(nblk, S), dim3(LK_RB), 0, h->stream, fmap, ov, h->pr, h->d_filters, src, h->d_partials, h->part_stride));
         LAUNCH(h, "update", hipLaunchKernelGGL(lk_update_wave_ragged_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, h->d_partials, h->part_stride, h->d_Q, rg, (int)b, 1));
         if (rg.run_scan) LAUNCH(h, "rag_pose_tap", hipLaunchKernelGGL(lk_rag_pose_tap_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, rg, (int)b));
+        if (rg.run_scan && rg.bucket_pose) LAUNCH(h, "rag_bucket_tap", hipLaunchKernelGGL(lk_rag_bucket_tap_kernel, dim3(S), dim3(LK_WAVE), 0, h->stream, h->d_filters, rg, (int)b));
         LKCHK(ov_insert_passes(h, h->stream, fmap, ov, h->d_filters, src, nb, S, S, 1, std::max(1, std::min(8, (nb + 63) / 64))));
         LAUNCH(h, "ov_insert_fallback", hipLaunchKernelGGL(lk_ov_insert_fallback_kernel, dim3(std::min(S, 128)), dim3(LK_MB), 0, h->stream, ov, h->pr, h->d_filters, src, S));
     }

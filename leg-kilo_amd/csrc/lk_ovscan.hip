@@ -131,8 +131,11 @@ __global__ void __launch_bounds__(LK_WAVE, LK_SCAN_WAVES)
             f->P[e] = sm.P[e];
         }
         if (lane < 36) f->x[lane] = sm.x[lane];
-        if constexpr (RUN)
+        if constexpr (RUN) {
             if (last) rag_write_pose(rg.scan_pose + sc, sm.x, f, lane);
+            // (the _cloud entries) the bucket's record, ahead of the insert like the pose: a launch that stops behind this bucket resumes at the next
+            if (rg.bucket_pose) rag_write_bucket(rg.bucket_pose + g0 + (unsigned int)b, sm.x, tb, po[b], (unsigned int)n, (unsigned int)N, lane);
+        }
         LK_SCAN_PHASE_SYNC();
         dev_bucket_begin_wave(pm);
         for (int i = lane; i < n; i += LK_WAVE) {

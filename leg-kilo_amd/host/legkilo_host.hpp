@@ -371,15 +371,30 @@ class KiloPath {
     // scan one KILO::process - state, covariance, times and the slot's copy-on-write overlay carried across the scan boundaries, the map itself
     // untouched.  Scans and message records (msg_kind 0 none, 1 lk_imu, 2 lk_kin_imu; n_msg[s] per scan) lie in HBM, as the front ends leave
     // them.  Priors: lk_batch_set_priors.  Returns one pose per SCAN, its counters that scan's alone.
+    // d_world_out / bucket_poses (lk_batch_replay_overlay_runs_cloud_dev; both optional): the scans registered into the world frame, one 16-byte x y z
+    // intensity record per point of d_pts under the state after the point's time bucket (cloud_down_world_out of KILO::process), and the state after
+    // every bucket - scan s owns (*scan_bucket_off)[s] .. [s+1] of *bucket_poses.  Without them this is lk_batch_replay_overlay_runs_dev.
     std::vector<lk_pose> replayRunsWithInsertDev(const lk_point* d_pts, const std::vector<uint32_t>& run_off, const std::vector<uint64_t>& scan_off,
-                                                 const std::vector<double>& t_begin, int msg_kind, const std::vector<uint32_t>& n_msg, const void* d_msgs) {
+                                                 const std::vector<double>& t_begin, int msg_kind, const std::vector<uint32_t>& n_msg, const void* d_msgs,
+                                                 float* d_world_out = nullptr, std::vector<lk_bucket_pose>* bucket_poses = nullptr,
+                                                 std::vector<uint32_t>* scan_bucket_off = nullptr) {
         const size_t S = t_begin.size();
         if (run_off.size() < 2 || run_off.back() != S || scan_off.size() != S + 1 || (msg_kind && n_msg.size() != S))
             throw std::runtime_error("replayRunsWithInsertDev: table sizes differ");
         std::vector<lk_pose> out(S);
-        dev_->check(lk_batch_replay_overlay_runs_dev(dev_->h(), d_pts, run_off.size() - 1, run_off.data(), scan_off.data(), t_begin.data(), msg_kind,
-                                                     msg_kind ? n_msg.data() : nullptr, d_msgs, out.data()));
+        std::vector<uint32_t> sbo(bucket_poses || scan_bucket_off ? S + 1 : 0);
+        dev_->check(lk_batch_replay_overlay_runs_cloud_dev(dev_->h(), d_pts, run_off.size() - 1, run_off.data(), scan_off.data(), t_begin.data(), msg_kind,
+                                                           msg_kind ? n_msg.data() : nullptr, d_msgs, out.data(), d_world_out, sbo.empty() ? nullptr : sbo.data()));
+        fetchBucketPoses(sbo, bucket_poses, scan_bucket_off);
         return out;
+    }
+    // what the two run replays share behind a _cloud call: the whole bucket table (lk_runs_bucket_poses) and the scans' ranges in it
+    void fetchBucketPoses(std::vector<uint32_t>& sbo, std::vector<lk_bucket_pose>* bucket_poses, std::vector<uint32_t>* scan_bucket_off) {
+        if (bucket_poses) {
+            bucket_poses->resize(sbo.back());
+            dev_->check(lk_runs_bucket_poses(dev_->h(), 0, bucket_poses->size(), bucket_poses->data()));
+        }
+        if (scan_bucket_off) scan_bucket_off->swap(sbo);
     }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
@@ -391,15 +406,20 @@ class KiloPath {
     // lk_batch_replay_runs_dev: the same runs on the FROZEN map (localisation against a finished map: no insert, no overlay, the map untouched) -
     // state, covariance and both time stamps carried across the scan boundaries.  cont (LK_RUNS_CONTINUE): the slots go on from what they hold, so
     // a run may be fed in chunks of scans, the first chunk with cont = false; the caller has not used the slots in between.  Tables as above.
+    // d_world_out / bucket_poses / scan_bucket_off: as for replayRunsWithInsertDev (lk_batch_replay_runs_cloud_dev); a continued call records its chunk.
     std::vector<lk_pose> replayRunsDev(const lk_point* d_pts, const std::vector<uint32_t>& run_off, const std::vector<uint64_t>& scan_off,
                                        const std::vector<double>& t_begin, int msg_kind, const std::vector<uint32_t>& n_msg, const void* d_msgs,
-                                       bool cont = false) {
+                                       bool cont = false, float* d_world_out = nullptr, std::vector<lk_bucket_pose>* bucket_poses = nullptr,
+                                       std::vector<uint32_t>* scan_bucket_off = nullptr) {
         const size_t S = t_begin.size();
         if (run_off.size() < 2 || run_off.back() != S || scan_off.size() != S + 1 || (msg_kind && n_msg.size() != S))
             throw std::runtime_error("replayRunsDev: table sizes differ");
         std::vector<lk_pose> out(S);
-        dev_->check(lk_batch_replay_runs_dev(dev_->h(), d_pts, run_off.size() - 1, run_off.data(), scan_off.data(), t_begin.data(), msg_kind,
-                                             msg_kind ? n_msg.data() : nullptr, d_msgs, cont ? LK_RUNS_CONTINUE : 0u, out.data()));
+        std::vector<uint32_t> sbo(bucket_poses || scan_bucket_off ? S + 1 : 0);
+        dev_->check(lk_batch_replay_runs_cloud_dev(dev_->h(), d_pts, run_off.size() - 1, run_off.data(), scan_off.data(), t_begin.data(), msg_kind,
+                                                   msg_kind ? n_msg.data() : nullptr, d_msgs, cont ? LK_RUNS_CONTINUE : 0u, out.data(), d_world_out,
+                                                   sbo.empty() ? nullptr : sbo.data()));
+        fetchBucketPoses(sbo, bucket_poses, scan_bucket_off);
         return out;
     }
     // lk_run_scans_dev: a recorded run LIVE on the handle's map (KILO::process scan after scan, the map growing), from scans and message records

@@ -494,6 +494,30 @@ int lk_batch_replay_overlay_runs_cloud_dev(lk_handle* h, const lk_point* d_pts, 
                                            float* d_world_out, uint32_t* scan_bucket_off);
 int lk_runs_bucket_poses_dev(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* d_out);
 int lk_runs_bucket_poses(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* out);
+/* Downsampled map clouds from registered points, many files per call: PcdSaver::downsampleAndSave (common/pcd_saver.hpp:114-121) up to and excluding
+ * savePCDFileBinaryCompressed - pcl::VoxelGrid<PointXYZINormal> at `leaf` over each file's buffer of frames.
+ * File f = the 16-byte x y z intensity records file_off[f] .. file_off[f+1) of d_world (DEVICE, 16-byte aligned, the layout of d_world_out; consecutive
+ * frames of a run are contiguous there, so a file is one range).  file_off: HOST, n_files + 1 entries, not decreasing; file_off[0] may be non-zero and
+ * nothing in front of it is read.  d_out (DEVICE, 16-byte aligned, room for file_off[n_files] - file_off[0] records, not overlapping the input): file
+ * f's result is the records out_off[f] .. out_off[f+1) of it, out_off[0] == 0 (HOST, n_files + 1 entries); nothing behind out_off[n_files] records is
+ * written.  Synchronous; the input is not modified, the filter slots and the map are not touched.
+ * Per file (oracle/preprocess_oracle.py::voxel_grid_centroid with intensity in the place of curvature): inv = 1.0f / leaf in float, bounds over the
+ * file's own points, ijk = floor(p * inv) - min_b, idx = i0 + i1 div0 + i2 div0 div1; one record per occupied cell in ascending idx, each of x y z
+ * intensity the float32 sum of the cell's points in INPUT order (frame after frame, point after point) divided by the float count.  Equal idx in two
+ * files are two cells.  (The normal and curvature members of cloud_down_world are zero in the reference and stay zero under a centroid.)
+ * Index overflow: when div0 div1 div2 > INT32_MAX pcl::VoxelGrid warns "Leaf size is too small for the input dataset" and hands the input on - that
+ * file comes out as its input, record for record in input order, and unfiltered[f] = 1 (HOST, n_files bytes, may be NULL; 0 otherwise).  At 0.1 m that
+ * is a cloud from about 129 m of extent per axis on: an ordinary run, not an error, and the other files are unaffected.
+ * LK_ERR_INVALID before anything is launched: n_files == 0, leaf not finite or <= 0, null tables or pointers, a misaligned d_world or d_out, input and
+ * output overlapping, file_off decreasing, an empty file (the message names it: PcdSaver never writes one), more than 0x7fffffff points in all.
+ * LK_ERR_INVALID found on the device: a file with a non-finite coordinate or with |p * inv| >= 2^30 (the message names the first such file); d_out is
+ * then undefined and the handle stays usable.
+ * lk_downsample_clouds: the same from and to HOST memory (world: the records file_off[0] .. file_off[n_files) are uploaded; out: room as for d_out,
+ * out_off[n_files] records are written, what lies behind them is left as it was). */
+int lk_downsample_clouds_dev(lk_handle* h, const float* d_world, size_t n_files, const uint64_t* file_off, float leaf, float* d_out, uint64_t* out_off,
+                             uint8_t* unfiltered);
+int lk_downsample_clouds(lk_handle* h, const float* world, size_t n_files, const uint64_t* file_off, float leaf, float* out, uint64_t* out_off,
+                         uint8_t* unfiltered);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

@@ -28,6 +28,7 @@ EXPORTS = [
     "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
     "lk_batch_replay_runs_dev", "lk_overlay_commit",
     "lk_batch_replay_runs_cloud_dev", "lk_batch_replay_overlay_runs_cloud_dev", "lk_runs_bucket_poses_dev", "lk_runs_bucket_poses",
+    "lk_downsample_clouds_dev", "lk_downsample_clouds",
 ]
 
 
@@ -96,6 +97,26 @@ def flatten_runs(runs, t_begins, imus=None, kins=None):
         if n_msg.sum():
             flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in per_scan if len(m)]))
     return dict(run_off=run_off, scan_off=scan_off, t_begin=tb, pts=np.ascontiguousarray(np.concatenate(scans)), msg_kind=kind, n_msg=n_msg, msgs=flat)
+
+
+def pcd_file_offsets(run_off, scan_off, frames_per_file=100):
+    """Which registered points go into which map file - the counting of PcdSaver::workerLoop over the run entries' tables (csrc/lk_pcd_files.h is the
+    C++ twin): a file is cut after every frames_per_file scans of a run (<= 0: 100) and at each run's end for the remainder; a scan without points is
+    skipped and not counted.  Returns (file_off uint64 [n_files + 1], file_run uint32 [n_files]): file f = the records file_off[f] : file_off[f + 1]
+    of the run replays' d_world_out and belongs to run file_run[f].  Pure: touches no device."""
+    ro = np.asarray(run_off, dtype=np.int64)
+    so = np.asarray(scan_off, dtype=np.uint64)
+    fpf = int(frames_per_file) if int(frames_per_file) > 0 else 100
+    ends, runs = [], []
+    for r in range(len(ro) - 1):
+        full = np.flatnonzero(so[ro[r] + 1:ro[r + 1] + 1] != so[ro[r]:ro[r + 1]]) + ro[r]   # the run's scans that hold points
+        cut = list(full[fpf - 1::fpf])                                                      # every fpf-th of them closes a file ...
+        if len(full) % fpf:
+            cut.append(full[-1])                                                            # ... and the run's end the remainder
+        ends += [so[s + 1] for s in cut]
+        runs += [r] * len(cut)
+    first = so[ro[0]] if len(ro) else 0
+    return np.array([first] + ends, dtype=np.uint64), np.array(runs, dtype=np.uint32)
 
 
 def _f64(a):
@@ -624,10 +645,56 @@ class LegKiloHip:
         self._chk(self.L.lk_runs_bucket_poses(self.h, C.c_uint64(first_bucket), C.c_size_t(n), _p(out)))
         return out
 
-    def _replay_runs_staged(self, entry, runs, t_begins, xs, Ps, imus, kins, cloud=False, bucket_poses=False, **kw):
+    def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
+        """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
+        file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at
+        `leaf` per file -> d_out (device, room for file_off[-1] - file_off[0] records).  Returns (out_off uint64 [n_files + 1], unfiltered uint8
+        [n_files]): file f's cloud is d_out[out_off[f] : out_off[f + 1]]; unfiltered[f] = 1 where the grid would overflow and the file is its input."""
+        fo = np.ascontiguousarray(file_off, dtype=np.uint64)
+        n_files = max(len(fo) - 1, 0)
+        out_off = np.zeros(n_files + 1, dtype=np.uint64)
+        unf = np.zeros(max(n_files, 1), dtype=np.uint8)
+        self._chk(self.L.lk_downsample_clouds_dev(self.h, C.c_void_p(d_world) if d_world else None, C.c_size_t(n_files), _p(fo), C.c_float(leaf),
+                                                  C.c_void_p(d_out) if d_out else None, _p(out_off), _p(unf)))
+        return out_off, unf[:n_files]
+
+    def downsample_clouds(self, world, file_off, leaf, with_flags=False):
+        """The same from host memory (lk_downsample_clouds): world float32 [n, 4] -> a list of (n_f, 4) float32 arrays, one per file; with_flags:
+        (that list, unfiltered)."""
+        w = np.ascontiguousarray(world, dtype=np.float32)
+        fo = np.ascontiguousarray(file_off, dtype=np.uint64)
+        n_files = len(fo) - 1
+        out = np.zeros((int(fo[-1] - fo[0]), 4), dtype=np.float32)
+        out_off = np.zeros(n_files + 1, dtype=np.uint64)
+        unf = np.zeros(n_files, dtype=np.uint8)
+        self._chk(self.L.lk_downsample_clouds(self.h, _p(w), C.c_size_t(n_files), _p(fo), C.c_float(leaf), _p(out), _p(out_off), _p(unf)))
+        clouds = [out[int(a):int(b)].copy() for a, b in zip(out_off[:-1], out_off[1:])]
+        return (clouds, unf) if with_flags else clouds
+
+    def _map_clouds_staged(self, d_world, run_off, scan_off, frames_per_file, leaf):
+        """d_world_out of a run replay -> the map files' downsampled clouds, on the device but for the result: a dict with "clouds" (a list of (n_f, 4)
+        float32 arrays), "file_off", "file_run", "unfiltered"."""
+        file_off, file_run = pcd_file_offsets(run_off, scan_off, frames_per_file)
+        res = dict(clouds=[], file_off=file_off, file_run=file_run, unfiltered=np.zeros(0, dtype=np.uint8))
+        if len(file_run) == 0:
+            return res
+        n = int(file_off[-1] - file_off[0])
+        d_out = self.device_malloc(16 * n)
+        try:
+            out_off, res["unfiltered"] = self.downsample_clouds_dev(d_world, file_off, leaf, d_out)
+            out = np.zeros((int(out_off[-1]), 4), dtype=np.float32)
+            if len(out):
+                self.d2h(out, d_out)
+        finally:
+            self.device_free(d_out)
+        res["clouds"] = [out[int(a):int(b)].copy() for a, b in zip(out_off[:-1], out_off[1:])]
+        return res
+
+    def _replay_runs_staged(self, entry, runs, t_begins, xs, Ps, imus, kins, cloud=False, bucket_poses=False, map_clouds=None, **kw):
         """What the two run conveniences share: priors, flatten_runs, points and messages -> HBM, entry(...), the poses run by run.  cloud /
-        bucket_poses: `entry` is the _cloud form; returns (poses run by run, dict) with "cloud" (float32 [n, 4], in the order of the flattened
-        points) and / or "bucket_poses" (all records) + "scan_bucket_off"."""
+        bucket_poses / map_clouds: `entry` is the _cloud form; returns (poses run by run, dict) with "cloud" (float32 [n, 4], in the order of the
+        flattened points) and / or "bucket_poses" (all records) + "scan_bucket_off" and / or "map_clouds" (map_clouds = (frames_per_file, leaf):
+        _map_clouds_staged on the registered cloud while it is in HBM)."""
         if xs is not None:
             self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
         t = flatten_runs(runs, t_begins, imus, kins)
@@ -642,10 +709,10 @@ class LegKiloHip:
                 dptrs.append(d_msgs)
                 self.h2d(d_msgs, t["msgs"])
             extra = None
-            if cloud or bucket_poses:
+            if cloud or bucket_poses or map_clouds is not None:
                 extra = {}
                 d_world = 0
-                if cloud:
+                if cloud or map_clouds is not None:
                     d_world = self.device_malloc(16 * len(t["pts"]))
                     dptrs.append(d_world)
                 poses, sbo = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, d_world=d_world, **kw)
@@ -654,6 +721,8 @@ class LegKiloHip:
                     self.d2h(extra["cloud"], d_world)
                 if bucket_poses:
                     extra["bucket_poses"], extra["scan_bucket_off"] = self.runs_bucket_poses(0, int(sbo[-1])), sbo
+                if map_clouds is not None:
+                    extra["map_clouds"] = self._map_clouds_staged(d_world, t["run_off"], t["scan_off"], *map_clouds)
             else:
                 poses = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, **kw)
             by_run = [poses[int(a):int(b)] for a, b in zip(t["run_off"][:-1], t["run_off"][1:])]
@@ -662,13 +731,15 @@ class LegKiloHip:
             for d in dptrs:
                 self.device_free(d)
 
-    def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cloud=False, bucket_poses=False):
+    def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cloud=False, bucket_poses=False, map_clouds=None):
         """Convenience: runs = a list of runs, each a list of host scans (lk_point arrays, time-sorted, any sizes); t_begins, imus / kins: the same
         nesting (one start time, one message array per scan) -> HBM -> batch_replay_overlay_runs_dev.  Optional priors, one per run.  Returns the
         poses run by run (a list of lists); with cloud / bucket_poses: (those, dict) - the registered cloud and / or the bucket table of
-        batch_replay_overlay_runs_cloud_dev (_replay_runs_staged)."""
-        if cloud or bucket_poses:
-            return self._replay_runs_staged(self.batch_replay_overlay_runs_cloud_dev, runs, t_begins, xs, Ps, imus, kins, cloud=cloud, bucket_poses=bucket_poses)
+        batch_replay_overlay_runs_cloud_dev (_replay_runs_staged); map_clouds = (frames_per_file, leaf): also the map files' downsampled clouds
+        (pcd_file_offsets + downsample_clouds_dev on the registered cloud, chained on the device) under "map_clouds"."""
+        if cloud or bucket_poses or map_clouds is not None:
+            return self._replay_runs_staged(self.batch_replay_overlay_runs_cloud_dev, runs, t_begins, xs, Ps, imus, kins, cloud=cloud, bucket_poses=bucket_poses,
+                                            map_clouds=map_clouds)
         return self._replay_runs_staged(self.batch_replay_overlay_runs_dev, runs, t_begins, xs, Ps, imus, kins)
 
     def batch_replay_runs_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, cont=False, want_poses=True, flags=None):
@@ -689,13 +760,14 @@ class LegKiloHip:
                                                   _p(nm), C.c_void_p(d_msgs) if d_msgs else None, C.c_uint32(fl), poses))
         return list(poses[:n_scans]) if want_poses else None
 
-    def batch_replay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cont=False, cloud=False, bucket_poses=False):
+    def batch_replay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cont=False, cloud=False, bucket_poses=False, map_clouds=None):
         """Convenience: the nested host inputs of batch_replay_overlay_runs -> HBM -> batch_replay_runs_dev (frozen map).  Optional priors, one per
         run (not with cont: a continued run goes on from what its slot holds).  Returns the poses run by run (a list of lists); with cloud /
-        bucket_poses: (those, dict), as batch_replay_overlay_runs."""
+        bucket_poses / map_clouds: (those, dict), as batch_replay_overlay_runs."""
         assert not (cont and xs is not None), "a continued run keeps its slot's state: no priors"
-        if cloud or bucket_poses:
-            return self._replay_runs_staged(self.batch_replay_runs_cloud_dev, runs, t_begins, xs, Ps, imus, kins, cloud=cloud, bucket_poses=bucket_poses, cont=cont)
+        if cloud or bucket_poses or map_clouds is not None:
+            return self._replay_runs_staged(self.batch_replay_runs_cloud_dev, runs, t_begins, xs, Ps, imus, kins, cloud=cloud, bucket_poses=bucket_poses,
+                                            map_clouds=map_clouds, cont=cont)
         return self._replay_runs_staged(self.batch_replay_runs_dev, runs, t_begins, xs, Ps, imus, kins, cont=cont)
 
     def overlay_reserve(self, roots_per_scan=0, nodes_per_scan=0, blocks_per_scan=0):

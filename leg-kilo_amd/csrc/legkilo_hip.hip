@@ -1651,6 +1651,141 @@ int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const u
     return LK_OK;
 }
 
+// ------------------------------------------------------------------ map clouds: the voxel grid over files of registered points (lk_mapcloud_kernels.h)
+// Two host round trips per call, none per file: after the per-file grids (status and overflow words: a bad file is refused before the sort) and at
+// the end (the files' cell offsets).  The sort is rocPRIM's stable segmented radix sort with a segment per file - ties keep the input order, which is
+// the order of the sums; a single file goes through the device-wide stable sort instead (a segment is sorted by ONE workgroup).
+namespace {
+struct MclPool {   // the per-call view of h->mcl
+    unsigned int *k0, *k1, *v0, *v1;   // keys / indices before and after the sort; k0 / v0 hold the head flags and their ranks afterwards
+    int* starts;
+    float4* sorted;
+    unsigned int *file_off, *cell_off, *status, *misc;
+    int *mm, *grid;
+    float4 *io_in, *io_out;            // lk_downsample_clouds' device copies (n_io records each; the device entry carves none)
+};
+// carves the arrays for N points of F files out of `base` (nullptr: only counts) and returns the bytes they take; the host entry's staging arrays
+// come last, so that the device entry's view of the same buffer is the same but for them
+size_t mcl_carve(void* base, size_t N, size_t F, size_t n_io, MclPool& d) {
+    LkCarve c(base, 256);
+    d.k0 = c.take<unsigned int>(N), d.k1 = c.take<unsigned int>(N), d.v0 = c.take<unsigned int>(N), d.v1 = c.take<unsigned int>(N);
+    d.starts = c.take<int>(N);
+    d.sorted = c.take<float4>(N);
+    d.file_off = c.take<unsigned int>(F + 1), d.cell_off = c.take<unsigned int>(F + 1);
+    d.status = c.take<unsigned int>(F);
+    d.misc = c.take<unsigned int>(8);
+    d.mm = c.take<int>(6 * F);
+    d.grid = c.take<int>(LK_MC_GRID_WORDS * F);
+    d.io_in = c.take<float4>(n_io), d.io_out = c.take<float4>(n_io);
+    return c.total();
+}
+}  // namespace
+
+static int mcl_reserve(lk_handle* h, size_t N, size_t F, size_t n_io, MclPool& d) {
+    LKCHK(reserve(h, h->mcl, mcl_carve(nullptr, N, F, n_io, d)));
+    mcl_carve(h->mcl.p, N, F, n_io, d);
+    size_t t1 = 0, t2 = 0;
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, d.k0, d.v0, N, h->stream));
+    if (F > 1)
+        HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)N, (unsigned int)F, d.file_off, d.file_off + 1, 0, 31,
+                                               h->stream));
+    else
+        HIPCHK(h, lk_prim_sort_pairs(nullptr, t2, d.k0, d.k1, (const int*)d.v0, (int*)d.v1, N, 0, 31, h->stream));
+    return reserve(h, h->prim_tmp, std::max(t1, t2));
+}
+
+// what both entries refuse before anything is launched; *n_pts: file_off[n_files] - file_off[0]
+static int mcl_check_tables(lk_handle* h, const char* who, const void* in, size_t n_files, const uint64_t* file_off, float leaf, const void* out,
+                            const uint64_t* out_off, size_t* n_pts) {
+    const std::string w = std::string(who) + ": ";
+    if (!in || !file_off || !out || !out_off) return fail(h, LK_ERR_INVALID, w + "null argument");
+    if (n_files == 0) return fail(h, LK_ERR_INVALID, w + "n_files is 0");
+    if (!std::isfinite(leaf) || !(leaf > 0.f)) return fail(h, LK_ERR_INVALID, w + "leaf must be finite and above 0");
+    if (((uintptr_t)in & 15u) || ((uintptr_t)out & 15u)) return fail(h, LK_ERR_INVALID, w + "the input and output clouds must be 16-byte aligned");
+    for (size_t f = 0; f < n_files; ++f) {
+        if (file_off[f + 1] < file_off[f]) return fail(h, LK_ERR_INVALID, w + "file_off decreases at file " + std::to_string(f));
+        if (file_off[f + 1] == file_off[f]) return fail(h, LK_ERR_INVALID, w + "file " + std::to_string(f) + " is empty");
+        if (file_off[f + 1] - file_off[0] > 0x7fffffffull)
+            return fail(h, LK_ERR_INVALID, w + "more than 0x7fffffff points from file " + std::to_string(f) + " on: split the call");
+    }
+    *n_pts = (size_t)(file_off[n_files] - file_off[0]);
+    const uintptr_t a = (uintptr_t)in + 16u * (uintptr_t)file_off[0], b = (uintptr_t)out, len = 16u * (uintptr_t)*n_pts;
+    if (a < b + len && b < a + len) return fail(h, LK_ERR_INVALID, w + "the output overlaps the input");
+    return LK_OK;
+}
+
+int lk_downsample_clouds_dev(lk_handle* h, const float* d_world, size_t n_files, const uint64_t* file_off, float leaf, float* d_out, uint64_t* out_off,
+                             uint8_t* unfiltered) {
+    CHECK_H(h);
+    size_t N = 0;
+    LKCHK(mcl_check_tables(h, "lk_downsample_clouds_dev", d_world, n_files, file_off, leaf, d_out, out_off, &N));
+    const size_t F = n_files;
+    MclPool d;
+    LKCHK(mcl_reserve(h, N, F, 0, d));
+    std::vector<unsigned int> foff(F + 1);
+    size_t biggest = 0;
+    for (size_t f = 0; f <= F; ++f) foff[f] = (unsigned int)(file_off[f] - file_off[0]);
+    for (size_t f = 0; f < F; ++f) biggest = std::max(biggest, (size_t)(foff[f + 1] - foff[f]));
+    const float4* pts = reinterpret_cast<const float4*>(d_world) + file_off[0];
+    const unsigned int n = (unsigned int)N, nb = (n + 255) / 256, Fi = (unsigned int)F, fb = (Fi + 255) / 256;
+    const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
+    HIPCHK(h, hipMemcpyAsync(d.file_off, foff.data(), 4 * (F + 1), hipMemcpyHostToDevice, h->stream));
+    // 1. per-file bounds with the non-finite / range words, the files' grids
+    const unsigned int gy = (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / F)), std::max<size_t>(1, biggest / 4096));
+    LAUNCH(h, "mc_init", hipLaunchKernelGGL(lk_mc_init_kernel, dim3(fb), dim3(256), 0, h->stream, d.mm, d.status, (int)Fi));
+    LAUNCH(h, "mc_bounds", hipLaunchKernelGGL(lk_mc_bounds_kernel, dim3(Fi, gy), dim3(256), 0, h->stream, pts, d.file_off, inv, d.mm, d.status));
+    LAUNCH(h, "mc_grid", hipLaunchKernelGGL(lk_mc_grid_kernel, dim3(fb), dim3(256), 0, h->stream, d.mm, d.status, inv, (int)Fi, d.grid));
+    std::vector<int> grid(LK_MC_GRID_WORDS * F);
+    HIPCHK(h, hipMemcpyAsync(grid.data(), d.grid, sizeof(int) * grid.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t f = 0; f < F; ++f)
+        if (const int st = grid[LK_MC_GRID_WORDS * f + 7])
+            return fail(h, LK_ERR_INVALID, "lk_downsample_clouds_dev: file " + std::to_string(f) +
+                                               ((st & LK_MC_BAD_NONFINITE) ? " holds a coordinate that is not finite" : " holds a coordinate with |p / leaf| >= 2^30"));
+    // 2. a cell key per point, a stable sort by key inside each file, cells (a new one at every file boundary), their first points
+    LAUNCH(h, "mc_keys", hipLaunchKernelGGL(lk_mc_keys_kernel, dim3(nb), dim3(256), 0, h->stream, pts, n, d.file_off, (int)Fi, inv, d.grid, d.k0, d.v0));
+    size_t tb = h->prim_tmp.cap;
+    if (F > 1)
+        HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, n, Fi, d.file_off, d.file_off + 1, 0, 31, h->stream));
+    else
+        HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, (const int*)d.v0, (int*)d.v1, N, 0, 31, h->stream));
+    unsigned int *flags = d.k0, *pos = d.v0, *ncells_d = d.misc;
+    LAUNCH(h, "mc_heads", hipLaunchKernelGGL(lk_mc_heads_kernel, dim3(nb), dim3(256), 0, h->stream, d.k1, n, d.file_off, (int)Fi, flags));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, flags, pos, N, h->stream));
+    LAUNCH(h, "mc_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(nb), dim3(256), 0, h->stream, flags, pos, (int)n, d.starts, ncells_d));
+    LAUNCH(h, "mc_celloff", hipLaunchKernelGGL(lk_dscan_celloff_kernel, dim3((Fi + 1 + 255) / 256), dim3(256), 0, h->stream, d.file_off, pos, ncells_d, (int)Fi,
+                                               d.cell_off));
+    // 3. the records into cell order, one centroid per cell
+    LAUNCH(h, "mc_gather", hipLaunchKernelGGL(lk_mc_gather_kernel, dim3(nb), dim3(256), 0, h->stream, pts, d.v1, n, d.sorted));
+    LAUNCH(h, "mc_centroid", hipLaunchKernelGGL(lk_mc_centroid_kernel, dim3(nb), dim3(256), 0, h->stream, d.sorted, d.starts, ncells_d, n, d.file_off, (int)Fi,
+                                                d.grid, reinterpret_cast<float4*>(d_out)));
+    std::vector<unsigned int> co(F + 1);
+    HIPCHK(h, hipMemcpyAsync(co.data(), d.cell_off, 4 * (F + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t f = 0; f <= F; ++f) out_off[f] = co[f];
+    if (unfiltered)
+        for (size_t f = 0; f < F; ++f) unfiltered[f] = grid[LK_MC_GRID_WORDS * f + 6] ? 1 : 0;
+    return LK_OK;
+}
+
+int lk_downsample_clouds(lk_handle* h, const float* world, size_t n_files, const uint64_t* file_off, float leaf, float* out, uint64_t* out_off,
+                         uint8_t* unfiltered) {
+    CHECK_H(h);
+    size_t N = 0;
+    LKCHK(mcl_check_tables(h, "lk_downsample_clouds", world, n_files, file_off, leaf, out, out_off, &N));
+    MclPool d;
+    LKCHK(mcl_reserve(h, N, n_files, N, d));
+    HIPCHK(h, hipMemcpyAsync(d.io_in, world + 4 * file_off[0], 16 * N, hipMemcpyHostToDevice, h->stream));
+    std::vector<uint64_t> rel(n_files + 1);
+    for (size_t f = 0; f <= n_files; ++f) rel[f] = file_off[f] - file_off[0];
+    LKCHK(lk_downsample_clouds_dev(h, reinterpret_cast<const float*>(d.io_in), n_files, rel.data(), leaf, reinterpret_cast<float*>(d.io_out), out_off,
+                                   unfiltered));
+    HIPCHK(h, hipMemcpyAsync(out, d.io_out, 16 * (size_t)out_off[n_files], hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+
 int lk_preprocess_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float leaf, lk_point* out_sorted, size_t* n_out) {
     CHECK_H(h);
     if (!raw || !out_sorted || n_raw == 0) return fail(h, LK_ERR_INVALID, "lk_preprocess_scan: bad argument");

@@ -39,6 +39,7 @@
 #ifdef LK_TU_MAIN
 #include "lk_pre_kernels.h"   // decode / voxel grid / ragged tables: launched by the main unit only
 #include "lk_query_kernels.h" // per-point build_single_residual: launched by the main unit only
+#include "lk_mapcloud_kernels.h" // voxel grid over files of registered points (lk_downsample_clouds_dev): launched by the main unit only
 #endif
 #include "lk_overlay_kernels.h"
 
@@ -130,6 +131,7 @@ struct lk_handle {
     int* d_grid_mm = nullptr;
     DevBuf pre;                   // scratch of lk_decode_scan / lk_preprocess_scan (PrePool)
     DevBuf dsc;                   // scratch of lk_decode_scans_dev (DscPool)
+    DevBuf mcl;                   // scratch of lk_downsample_clouds(_dev) (MclPool)
     // batch replay with a per-scan insert overlay (lk_overlay_kernels.h): the pools of all slots, grow-only
     LkOverlay ov = {};
     uint32_t ov_slots = 0;                                // slots the pools were allocated for

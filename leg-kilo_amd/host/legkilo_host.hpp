@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "legkilo_hip.h"
+#include "../csrc/lk_pcd_files.h"   // pcd_file_offsets: PcdSaver::workerLoop's counting over the run replays' tables (plain C++)
 
 // The mirror lives in namespace legkilo, like the classes it stands in for.  Inside the reference's own tree that namespace already
 // holds the Eigen typedefs of common/eigen_types.hpp (Vec3D, Mat3D, ...): there legkilo_host_eigen.hpp includes this header under
@@ -421,6 +422,26 @@ class KiloPath {
                                                    sbo.empty() ? nullptr : sbo.data()));
         fetchBucketPoses(sbo, bucket_poses, scan_bucket_off);
         return out;
+    }
+    // lk_downsample_clouds_dev behind a run replay's d_world_out: what PcdSaver (pcd_saver.hpp, defaults 100 frames per file, leaf 0.1 m) makes of the
+    // registered frames up to the file container - a file after every frames_per_file non-empty scans of a run and at each run's end, pcl::VoxelGrid at
+    // `leaf` per file.  d_out: room for scan_off.back() - scan_off[run_off[0]] records.  File f's cloud is d_out[(*out_off)[f] .. (*out_off)[f+1]) and
+    // belongs to run (*file_run)[f]; (*unfiltered)[f] = 1 where the grid would overflow an int and the file is its input.  Returns the number of files.
+    size_t downsampleCloudsDev(const float* d_world, const std::vector<uint32_t>& run_off, const std::vector<uint64_t>& scan_off, float* d_out,
+                               std::vector<uint64_t>* out_off, std::vector<uint32_t>* file_run = nullptr, std::vector<uint8_t>* unfiltered = nullptr,
+                               int frames_per_file = 100, float leaf = 0.1f) {
+        if (run_off.size() < 2 || scan_off.size() != (size_t)run_off.back() + 1) throw std::runtime_error("downsampleCloudsDev: table sizes differ");
+        const size_t R = run_off.size() - 1;
+        std::vector<uint64_t> file_off(scan_off.size()), off(scan_off.size());
+        std::vector<uint32_t> runs(scan_off.size());
+        const size_t F = pcd_file_offsets(run_off.data(), R, scan_off.data(), frames_per_file, file_off.data(), runs.data());
+        std::vector<uint8_t> unf(F);
+        if (F) dev_->check(lk_downsample_clouds_dev(dev_->h(), d_world, F, file_off.data(), leaf, d_out, off.data(), unf.data()));
+        off.resize(F + 1), runs.resize(F);
+        if (out_off) out_off->swap(off);
+        if (file_run) file_run->swap(runs);
+        if (unfiltered) unfiltered->swap(unf);
+        return F;
     }
     // lk_run_scans_dev: a recorded run LIVE on the handle's map (KILO::process scan after scan, the map growing), from scans and message records
     // that lie in HBM - msg_kind 0 none, 1 lk_imu, 2 lk_kin_imu; n_msg[s] records per scan at d_msgs.  slide: mapSliding after every scan

@@ -88,6 +88,16 @@ typedef struct lk_config {
     /* device side */
     int32_t device_id;              /* HIP device ordinal */
     uint32_t n_slots;               /* filter slots (>=1); >1 only for batch replay */
+    /* max_roots and the root table.  The table has T = next_pow2(8 * max_roots) slots (at least 128: max_roots >= 16) and is probed linearly.
+     * Up to T / 2 root voxels - 4 * max_roots when max_roots is a power of two - everything works: lk_map_build / lk_map_update / the scan
+     * entries create roots, every lookup finds them, lk_map_export writes them and lk_map_import, lk_map_clear_outside, lk_map_slide and
+     * lk_overlay_commit rebuild the table from them.  A map made ON THE DEVICE may go on to T roots: creation and lookup still work (a lookup
+     * of an absent key in a full table ends after one circle of the table) and lk_map_export still writes it - but lk_map_import and
+     * lk_overlay_commit refuse more than T / 2 roots with LK_ERR_CAPACITY and leave the handle's map as it was, so such a map cannot be
+     * restored from its own host blob by a handle of the same max_roots.  The (T + 1)-th root voxel is LK_ERR_CAPACITY "device pool overflow
+     * (bits 0x1 ...)" from a bounded loop: the voxels that exist are still found, the map may hold a part of the refused insert, and the
+     * handle goes on once lk_map_import has put a map in.  Size max_roots for the load, not for the limit: probe chains grow quickly
+     * above T / 4. */
     uint32_t max_roots;             /* root voxels the hash must hold (table = next pow2 of 8x) */
     uint32_t max_nodes;             /* octree nodes (roots + children) */
     uint32_t max_point_blocks;      /* per-leaf point blocks of LK_BLOCK_PTS points */
@@ -521,7 +531,13 @@ int lk_downsample_clouds(lk_handle* h, const float* world, size_t n_files, const
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the
- * caller's word: overflowing them fails the replay with LK_ERR_CAPACITY.  Releases pools of another shape. */
+ * caller's word: overflowing them fails the replay with LK_ERR_CAPACITY.  Releases pools of another shape.
+ * The private root table of a scan has next_pow2(roots + roots / 4) entries and takes keys until every entry is used (100 roots: 128 entries,
+ * the 129th voxel overflows).  Growth is bounded: a replay runs again at most four times, each time with what overflowed doubled - a root
+ * table that doubles takes point blocks for 4/5 of its entries and half as many child nodes with it - so library-sized pools reach 16 times
+ * their root entries.  A scan that needs more (2 200 voxels behind replays of 10-voxel scans of the same size: 128 entries, 2 048 after four
+ * doublings) fails with LK_ERR_CAPACITY "overlay pool overflow" like an explicit reserve, the slots back at their priors and the handle
+ * usable; an explicit reserve, or a first replay of representative scans, avoids it. */
 int lk_overlay_reserve(lk_handle* h, uint32_t roots_per_scan, uint32_t nodes_per_scan, uint32_t blocks_per_scan);
 /* The voxels scan `slot` of the LAST overlay replay holds privately - every root voxel its inserts touched or created, whole octrees -
  * as a map blob (lk_map_export's format; blob == NULL: size query).  Voxels not in it are the handle's, unchanged.

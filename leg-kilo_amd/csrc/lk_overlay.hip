@@ -331,7 +331,15 @@ static int ov_reserve(lk_handle* h, uint32_t S, size_t n_pts_scan, size_t bigges
     LkOverlay& o = h->ov;
     if (grow) {   // never below what is there; what overflowed is doubled
         hash_cap = std::max(hash_cap, o.hash_cap), nodes_extra = std::max(nodes_extra, o.nodes_cap - o.hash_cap), blocks = std::max(blocks, o.blocks_cap);
-        if (grow & LK_E_HASH_FULL) hash_cap *= 2;
+        if (grow & LK_E_HASH_FULL) {
+            // A scan that cannot claim its roots stops there: the blocks and child nodes of the roots it did not get are never asked for, so an
+            // attempt whose table overflows reports the table alone.  Doubling one pool per attempt spent the four attempts on the table and left
+            // none for the point blocks (history-sized pools of a 10-voxel scan, then a 600-voxel scan: LK_ERR_CAPACITY at 1024 entries / 152 blocks).
+            // The first guess's proportions go with the table instead: roots = 4/5 of its entries, a block per root, a child node per two.
+            hash_cap *= 2;
+            const uint32_t r = hash_cap / 5 * 4;
+            blocks = std::max(blocks, r), nodes_extra = std::max(nodes_extra, r / 2);
+        }
         if (grow & LK_E_NODES_FULL) nodes_extra = nodes_extra * 2 + 256;
         if (grow & LK_E_BLOCKS_FULL) blocks *= 2;
     }

@@ -440,20 +440,32 @@ struct PointLite {
     double alpha_n, beta;  // alpha / |pb|^2, beta
     float gz;              // 1e-4 when calcBodyCov's z == 0 guard fired (voxel_map.cc:23), else 0
 };
+// point_lite in two parts, so that a caller can put work between them (residual_tile's frozen-grid order: lk_point_kernels.h).
+// The position part: p_i, p_w - what the voxel key, and with it the address of the point's cell record, depends on.
 template <bool XID = false>
-__device__ __forceinline__ PointLite point_lite(float bx, float by, float bz, const BucketConst& bc, const LkParams& pr) {
-    PointLite g;
+__device__ __forceinline__ void point_lite_pos(float bx, float by, float bz, const BucketConst& bc, const LkParams& pr, PointLite& g) {
     V3 pb = V3{(double)bx, (double)by, (double)bz};
     V3 e = XID ? pb : mat3_mul_v(pr.ext_R, pb);   // XID: ext_R is exactly I, and 1 * x + 0 * y + 0 * z == x bit for bit
     g.p_i = V3{e.x + pr.ext_T[0], e.y + pr.ext_T[1], e.z + pr.ext_T[2]};
     V3 w = mat3_mul_v(bc.R, g.p_i);
     g.p_w = V3{w.x + bc.p[0], w.y + bc.p[1], w.z + bc.p[2]};
+}
+// The terms part: gz, beta, alpha_n - functions of the body point alone (an fp64 square root and an IEEE division, both serial
+// chains); no address depends on them.
+__device__ __forceinline__ void point_lite_terms(float bx, float by, float bz, const LkParams& pr, PointLite& g) {
+    V3 pb = V3{(double)bx, (double)by, (double)bz};
     g.gz = 0.f;
     if (pb.z == 0) pb.z = 0.0001, g.gz = 0.0001f;
     const double n2 = dot3(pb.x, pb.x, pb.y, pb.y, pb.z, pb.z);
     const double r = (double)(float)sqrt(n2);            // float range, voxel_map.cc:24
     g.beta = (r * r) * pr.dir_var;
     g.alpha_n = ((double)pr.range_var - g.beta) * lk_inv(n2);
+}
+template <bool XID = false>
+__device__ __forceinline__ PointLite point_lite(float bx, float by, float bz, const BucketConst& bc, const LkParams& pr) {
+    PointLite g;
+    point_lite_pos<XID>(bx, by, bz, bc, pr, g);
+    point_lite_terms(bx, by, bz, pr, g);
     return g;
 }
 struct PlaneTerms {  // per (point, candidate normal)

@@ -11,7 +11,14 @@
 // HBM-bound by design (arithmetic intensity ~2 flop/B): one thread per point, lk_point loaded as one
 // 16-B float4 per lane (coalesced 1 KiB per wave), plane records are 256-B aligned and read with
 // 16-B vector loads, the gate data (first 64 B) before the 6x6 plane covariance (next 168 B).
-// grid = (ceil(n/256), n_slots): blockIdx.y selects the filter slot (batch replay).
+// grid = (ceil(n/64), n_slots), one wave per workgroup (LK_RB): blockIdx.y selects the filter slot (batch replay).
+//
+// Order of a lane's first look-up.  Everywhere but on the frozen grid: point_lite (position AND point-only terms), key, root, then the
+// matcher requests the root's record.  Frozen grid (GRID == 1: lk_residual_kernel<*, 1, *, *>, lk_residual_ragged_kernel<1>): position part
+// of point_lite, key, cell - then the cell's record is REQUESTED (rec_request: nine 16-B loads, no pin), then the point-only terms
+// (point_lite_terms: an fp64 square root and an IEEE division, ~50 serial VALU no address depends on) are computed while the record travels,
+// and match_flat<XID, true> pins and evaluates the pieces where they landed.  Same expressions, same bits; the wave's second memory trip
+// starts that much earlier.
 #pragma once
 #include "lk_device.h"
 
@@ -37,6 +44,19 @@ struct Match {
 struct RecTail {   // bytes 64..143 of a match record: S11 (6), w (3), s22
     double2 v0, v1, v2, v3, v4;
 };
+// A whole match record as its nine 16-B pieces in registers.  rec_request only issues the nine loads; the pieces are NOT pinned
+// (pin_chunk is a use, and a use is where the compiler waits for the load): whoever consumes them pins them first.
+struct RecRegs {
+    double2 q0, q1, q2;   // center, normal
+    float4 tail;          // d, radius, flags, pad_
+    RecTail rt;
+};
+__device__ __forceinline__ void rec_request(const lk_match_rec* pl, RecRegs& r) {
+    const double2* q = reinterpret_cast<const double2*>(pl);
+    r.q0 = q[0], r.q1 = q[1], r.q2 = q[2];
+    r.rt.v0 = q[4], r.rt.v1 = q[5], r.rt.v2 = q[6], r.rt.v3 = q[7], r.rt.v4 = q[8];
+    r.tail = *reinterpret_cast<const float4*>(&pl->d);   // d, radius, flags, pad_ (grid cells: node id)
+}
 // BOUND: the record is a frozen-map grid record, whose radius word holds lk_range_bound(radius) (lk_grid_fill_kernel) - the range gate is two float
 // compares, the same decision for every x as the sqrtf form that pool records keep (lk_range_bound.h).
 template <bool XID, bool PRE = false, bool BOUND = false>
@@ -175,18 +195,21 @@ __device__ __forceinline__ bool match_root(const LkMap& m, int root, const bool 
 // Matcher of the FROZEN map (grid cells, LkMap::grid_base): the root's cell is a plane record, or the header of the flattened
 // list of its subtree's planes (LK_GRID_LIST) - a counted loop over consecutive records, candidates in the reference's
 // pre-order, one copy of the plane evaluation.  Returns whether a root voxel exists at the cell.
-template <bool XID>
+// PRE: the caller has already REQUESTED the cell's own record into `rec` (rec_request, not pinned) - the header iteration takes
+// those registers as they are, later iterations load into the same ones.
+template <bool XID, bool PRE = false>
 __device__ __forceinline__ bool match_flat(const LkMap& m, int cell, const PointLite& g, const BucketConst& bc, const LkParams& pr,
-                                           bool& success, double& prob, Match& best) {
+                                           bool& success, double& prob, Match& best, RecRegs* rec = nullptr) {
     int idx = cell, remaining = 1;
     bool header = true;   // the record at idx is the cell itself
+    RecRegs own;
+    RecRegs& r = PRE ? *rec : own;
+    double2 &q0 = r.q0, &q1 = r.q1, &q2 = r.q2;
+    float4& tail = r.tail;    // d, lk_range_bound(radius), flags, node id
+    RecTail& rt = r.rt;
     while (remaining > 0) {
         const lk_match_rec* pl = &m.match[idx];
-        const double2* q = reinterpret_cast<const double2*>(pl);
-        double2 q0 = q[0], q1 = q[1], q2 = q[2];
-        float4 tail = *reinterpret_cast<const float4*>(&pl->d);  // d, lk_range_bound(radius), flags, node id
-        RecTail rt;
-        rt.v0 = q[4], rt.v1 = q[5], rt.v2 = q[6], rt.v3 = q[7], rt.v4 = q[8];
+        if (!PRE || !header) rec_request(pl, r);
         pin_chunk(q0), pin_chunk(q1), pin_chunk(q2), pin_chunk(tail);
         pin_chunk(rt.v0), pin_chunk(rt.v1), pin_chunk(rt.v2), pin_chunk(rt.v3), pin_chunk(rt.v4);
         const unsigned int fl = __float_as_uint(tail.z);
@@ -332,10 +355,22 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
     {
         PointLite g;
         int root = -1, nroot = -1;
+        // Frozen grid (GRID == 1): the home cell's record is requested the moment its address is known, and the point-only terms of
+        // point_lite - an fp64 square root and an IEEE division, serial chains that no address depends on - are computed while it travels.
+        // Request, terms and match sit in ONE region (root >= 0 implies i < n): the loaded pieces reach match_flat's pins without crossing a
+        // join of control flow - across one, the compiler copies them into other registers and waits for every piece in front of the terms.
+        // Lanes without a home cell skip the terms: nothing reads them there (no match, no neighbour retry).
+        constexpr bool REC_FIRST = GRID == 1;
+        bool success = false;
+        double prob = 0;
+        Match best;
+        best.row = rows + lane * LK_ROW2;
+        bool home = false;
         if (i < n) {
             typedef float lk_f4v __attribute__((ext_vector_type(4)));
             const lk_f4v p = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(spts) + i);   // read once: keep it from displacing plane records in L2 (round 6: 1.560 -> 1.537 ms per step, same bits)
-            g = point_lite<XID>(p.x, p.y, p.z, bc, pr);
+            if (REC_FIRST) point_lite_pos<XID>(p.x, p.y, p.z, bc, pr, g);
+            else g = point_lite<XID>(p.x, p.y, p.z, bc, pr);
             if (out.world) {
                 float4 w = make_float4((float)g.p_w.x, (float)g.p_w.y, (float)g.p_w.z, 0.f);
                 reinterpret_cast<float4*>(out.world + out_base * 4)[i] = w;
@@ -349,17 +384,19 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
                 if (out.ids_lane) *out.ids_lane = make_int2(spec_code(root, key), LK_SPEC_NONE);
                 else out.ids[out_base + i] = make_int2(spec_code(root, key), LK_SPEC_NONE);
             }
+            if (REC_FIRST && root >= 0) {   // lanes beyond n or outside the grid request nothing
+                RecRegs home_rec;
+                rec_request(&map.match[root], home_rec);
+                point_lite_terms(p.x, p.y, p.z, pr, g);
+                home = match_flat<XID, true>(map, root, g, bc, pr, success, prob, best, &home_rec);
+            }
         }
-        // K2: home voxel first (the root's 144-B record is fetched in one round trip inside match_root)
-        bool success = false;
-        double prob = 0;
-        Match best;
-        best.row = rows + lane * LK_ROW2;
+        // K2: home voxel first (the root's 144-B record is fetched in one round trip: inside match_root / match_flat, or just above)
         const bool grid_cell = GRID == 1 || GRID == 3 || (GRID == 2 && map.grid_on != 0);
-        bool home = false;
         LkMap pmv = {};   // GRID == 3: the slot's private pools (match_root reads match[] and nodes[].child only)
         if (GRID == 3) pmv.match = const_cast<lk_match_rec*>(ovv->match), pmv.nodes = const_cast<lk_node_rec*>(ovv->nodes);
-        if (root >= 0) home = grid_cell ? match_flat<XID>(map, root, g, bc, pr, success, prob, best) : match_root<XID>(map, root, false, g, bc, pr, success, prob, best);
+        if (REC_FIRST) {}   // matched above
+        else if (root >= 0) home = grid_cell ? match_flat<XID>(map, root, g, bc, pr, success, prob, best) : match_root<XID>(map, root, false, g, bc, pr, success, prob, best);
         else if (GRID == 3 && root <= -2) home = match_root<XID>(pmv, -2 - root, false, g, bc, pr, success, prob, best);
         // the one-neighbour retry (KILO.cc:156-178): only when the home voxel EXISTS (the lookup at KILO.cc:149 found a tree)
         if (home && !success) {

@@ -384,9 +384,13 @@ int lk_batch_sort_by_voxel_dev(lk_handle* h, const lk_point* d_in, lk_point* d_o
  * a library-owned copy unless every bucket already is in voxel order under the slots' priors (the work of lk_batch_sort_by_voxel_dev: 5.6 ms and 16 B per
  * point for 1 024 x 100 000 points; that call synchronises), and the later replays of that batch read the copy: the same scans in another legal order,
  * equal to the replay of the buffer as given up to the order of floating-point sums.  The caller's buffer is never written.  A batch replayed once or
- * twice (new scans streamed through a staging buffer) is never sorted.  New content in a sorted batch's buffer is noticed by the same stamp: that replay
- * reads the buffer as given and the count starts again; after an in-place edit too small for the sample, call lk_batch_changed.  The two most recently
- * used batches are kept.
+ * twice (new scans streamed through a staging buffer) is never sorted.  New content in a sorted batch's buffer is noticed by the same stamp: the stamp
+ * the copy was made from is kept in a word of its own, and a replay reads the copy only if ITS stamp equals that word - so that replay, and every other
+ * replay of the new content that was enqueued before the host heard of the change (lk_batch_replay_async_dev never waits), reads the buffer as given; the
+ * count starts again.  Each of the three streams the asynchronous entry rotates over has its own decision word per batch: replays of one buffer in flight
+ * on several streams do not decide for each other.  After an in-place edit too small for the sample, call lk_batch_changed.  The two most recently used
+ * batches are kept.  (The count is read by the host without waiting; only at the replay that could be the one to sort does the host wait, once per
+ * content, for the replays of that batch still in flight - the sort waits for them anyway.)
  * LK_BATCH_ORDER_AS_GIVEN: every batch is replayed where it lies, no copy, no stamp (also: LEGKILO_BATCH_ORDER=0).
  * The entries WITH insert (lk_batch_replay_overlay*_dev) and the ragged entries always replay as given: with the map insert the order inside a bucket
  * decides which points a voxel holds when it is fitted, and the caller's order is the one its checker knows. */
@@ -395,7 +399,8 @@ int lk_batch_sort_by_voxel_dev(lk_handle* h, const lk_point* d_in, lk_point* d_o
 int lk_batch_order(lk_handle* h, int mode);
 int lk_batch_changed(lk_handle* h);
 /* For a caller who KNOWS a batch will be replayed many times: examine it and make the voxel-ordered copy now, under the priors of slots [0, n_scans)
- * (lk_batch_set_priors(_dev) first), instead of at its third replay.  Synchronous; once per loaded batch (works in either mode). */
+ * (lk_batch_set_priors(_dev) first), instead of at its third replay.  Synchronous; once per loaded batch.  In LK_BATCH_ORDER_AS_GIVEN no replay would
+ * read the copy: the call then returns LK_OK without examining or copying anything (and nothing is remembered for a later LK_BATCH_ORDER_AUTO). */
 int lk_batch_prepare_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, size_t n_pts, const uint32_t* bucket_off, size_t n_buckets);
 /* out3 = { batches examined (replayed unchanged often enough), of those sorted into a copy, sorted batches whose buffer later held other content } since lk_create */
 int lk_batch_order_stats(lk_handle* h, uint64_t* out3);

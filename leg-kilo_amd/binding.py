@@ -499,7 +499,8 @@ class LegKiloHip:
         self._chk(self.L.lk_batch_order(self.h, int(mode)))
 
     def batch_prepare_dev(self, d_pts, n_scans, n_pts, bucket_off):
-        """Make the voxel-ordered copy of a batch NOW (priors armed first) instead of at its third replay (lk_batch_prepare_dev)."""
+        """Make the voxel-ordered copy of a batch NOW (priors armed first) instead of at its third replay (lk_batch_prepare_dev); does nothing
+        under batch_order(0), where no replay would read it."""
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
         self._chk(self.L.lk_batch_prepare_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), C.c_size_t(n_pts), _p(off), C.c_size_t(len(off) - 1)))
 

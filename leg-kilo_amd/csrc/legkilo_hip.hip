@@ -1,6 +1,7 @@
 // legkilo_hip.hip - the main translation unit of liblegkilo_hip.so (see lk_internal.h)
 #define LK_TU_MAIN 1
 #include "lk_internal.h"
+#include "lk_batch_stamp.h"
 #include "lk_cloud_layout.h"
 
 thread_local std::string g_err;
@@ -1919,7 +1920,9 @@ static int sort_by_voxel(lk_handle* h, const lk_point* d_in, lk_point* d_out, ui
 // of the reference's sort of equal time stamps (KILO.cc:369), so the copy is a batch of the same scans.  A batch that is replayed once or twice - new
 // scans streamed through one staging buffer - is never sorted; new content in a sorted batch's buffer is noticed by the same kernel, which tells the
 // residual kernel to read the caller's buffer (ResidualOut::alt_use) and starts the count again.  (An in-place edit that changes none of the sampled
-// points is not noticed: lk_batch_changed.)
+// points is not noticed: lk_batch_changed.)  The host picks the kernel's mode from a count that lags behind the replays in flight, so the device side
+// is safe under ANY order of modes and stamps: the copy is read only by a replay that carries the stamp the copy was made from, which has a word of its
+// own, and every ring stream of the asynchronous entry has its own decision word (lk_batch_stamp.h; tests/test_batch_stamp.py enumerates the orders).
 __global__ void __launch_bounds__(256) lk_sort_check_kernel(LkParams pr, const LkFilter* __restrict__ filters, const lk_point* __restrict__ pts, size_t n_pts,
                                                             unsigned int* __restrict__ unsorted) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1936,57 +1939,50 @@ __global__ void __launch_bounds__(256) lk_sort_check_kernel(LkParams pr, const L
     const unsigned int sb = (((unsigned int)kb[2] & 1023u) << 20) | (((unsigned int)kb[1] & 1023u) << 10) | ((unsigned int)kb[0] & 1023u);
     if (sb < sa) atomicAdd(unsorted, 1u);
 }
-// Stamp of 4 096 points spread over the batch, compared on the device with the stamp of the replay before (ref[0]); ref[1] = which buffer THIS replay's
-// residual launches read (1: the library's copy); *seen (host-mapped) = how many replays in a row have found the same stamp (LK_ORD_SORTED once a copy
-// of this very content exists).  mode LK_ORD_SET: the copy has just been made from the buffer.
-#define LK_ORD_PROBE 0     // no copy (yet): count how often the content repeats
-#define LK_ORD_CHECK 1     // a copy exists: use it if the buffer still holds what it was made from
-#define LK_ORD_SET 2
-#define LK_ORD_SORTED 1000000u
-__global__ void __launch_bounds__(256) lk_batch_stamp_kernel(const lk_point* __restrict__ pts, size_t total, unsigned long long* __restrict__ ref,
-                                                             unsigned int* __restrict__ seen, int mode) {
+// Stamp of 4 096 points spread over the batch, taken ahead of a replay's residual launches on the replay's own stream, and the replay's decision
+// (lk_batch_stamp.h: lk_stamp_decide).  w: the batch's words - w[LK_ORDW_COPY] the stamp its copy was made from, written by LK_ORD_SET alone, apart
+// from w[LK_ORDW_LAST], the stamp of the replay before, which only counts repeats.  use: the pair of the ring stream this replay runs on; use[1] = which
+// buffer THIS replay's residual launches read (1: the library's copy, only if this replay's stamp is the copy's own) - a word per stream, so that no
+// other stream's stamp kernel rewrites it under them.  *seen (host-mapped, atomic) = how many replays in a row have found the same stamp
+// (LK_ORD_SORTED while a copy of this very content exists).
+__global__ void __launch_bounds__(256) lk_batch_stamp_kernel(const lk_point* __restrict__ pts, size_t total, unsigned long long* __restrict__ w,
+                                                             unsigned long long* __restrict__ use, unsigned int* __restrict__ seen, int mode) {
     __shared__ unsigned long long acc;
     if (threadIdx.x == 0) acc = 0ull;
     __syncthreads();
-    const size_t stride = total / 4096 ? total / 4096 : 1;
+    const size_t stride = lk_stamp_stride(total);
     unsigned long long hsh = 0ull;
-    for (int k = 0; k < 16; ++k) {
-        const size_t idx = ((size_t)threadIdx.x * 16 + k) * stride;
+    for (int k = 0; k < LK_STAMP_SAMPLES / 256; ++k) {
+        const size_t idx = ((size_t)threadIdx.x * (LK_STAMP_SAMPLES / 256) + k) * stride;
         if (idx >= total) break;
         const uint4 v = reinterpret_cast<const uint4*>(pts)[idx];
-        unsigned long long m = ((unsigned long long)v.x | ((unsigned long long)v.y << 32)) ^ (0x9E3779B97F4A7C15ull * (idx + 1));
-        m = (m ^ (m >> 31)) * 0xBF58476D1CE4E5B9ull;
-        m ^= ((unsigned long long)v.z | ((unsigned long long)v.w << 32)) * 0x94D049BB133111EBull;
-        m = (m ^ (m >> 29)) * 0xC2B2AE3D27D4EB4Full;
-        hsh += m ^ (m >> 32);   // a sum: the order the threads arrive in does not matter
+        hsh += lk_stamp_mix(v.x, v.y, v.z, v.w, idx);
     }
     atomicAdd(&acc, hsh);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long st = acc | 1ull;   // never 0: ref[0] == 0 means "no stamp yet"
-        if (mode == LK_ORD_SET) {
-            ref[0] = st, ref[1] = 1ull, *seen = LK_ORD_SORTED;
-        } else if (st == ref[0]) {
-            ref[1] = mode == LK_ORD_CHECK ? 1ull : 0ull;
-            if (mode == LK_ORD_PROBE) *seen = *seen + 1u;
-        } else {   // other content than last time: this replay reads the caller's buffer, and the count starts again
-            ref[0] = st, ref[1] = 0ull, *seen = 1u;
-        }
-    }
+    if (threadIdx.x == 0) lk_stamp_decide(mode, lk_stamp_finish(acc), w, use, seen);
 }
 static uint64_t hash_offsets(const uint32_t* off, size_t n) {
     uint64_t x = 1469598103934665603ull;
     for (size_t i = 0; i <= n; ++i) x = (x ^ off[i]) * 1099511628211ull;
     return x;
 }
-// Which buffer the residual launches of a frozen-map batch replay read.  `st`: the stream the slots' priors were armed on and the batch will run on.
+// Which buffer the residual launches of a frozen-map batch replay read.  `st`: the stream the slots' priors were armed on and the batch will run on;
+// `ring`: which of the LK_ORD_RINGS decision pairs of the batch's words this replay owns - the asynchronous entry's ring stream.  The synchronous
+// entry passes 0 and makes this call on h->stream BEFORE its slot groups fork: all groups of one call read one pair, written before any of them starts.
 // Fills ro->alt_pts / alt_use (null: the caller's buffer as given).  One small launch per call; the call that makes the copy synchronises.
 static int batch_ordered(lk_handle* h, const lk_point* d_pts, uint32_t first_slot, size_t n_scans, size_t n_pts, const uint32_t* bucket_off, size_t n_buckets,
-                         hipStream_t st, ResidualOut* ro, bool now = false) {
+                         hipStream_t st, uint32_t ring, ResidualOut* ro, bool now = false) {
     ResidualOut none;
     if (!ro) ro = &none;
     ro->alt_pts = nullptr, ro->alt_use = nullptr;
-    if ((h->batch_order_mode == 0 && !now) || n_scans * n_pts < 4096 || n_scans * n_pts >= ((size_t)1 << 32)) return LK_OK;
+    if (h->batch_order_mode == 0 || n_scans * n_pts < LK_STAMP_SAMPLES || n_scans * n_pts >= ((size_t)1 << 32)) return LK_OK;
+    const auto drain = [&]() -> int {   // replays in flight on any stream read and write the entries' words
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < lk_handle::kMaxGroups - 1; ++i)
+            if (h->side[i]) HIPCHK(h, hipStreamSynchronize(h->side[i]));
+        return LK_OK;
+    };
     const uint64_t oh = hash_offsets(bucket_off, n_buckets);
     lk_handle::OrdEntry* e = nullptr;
     for (auto& c : h->ord)
@@ -1994,41 +1990,47 @@ static int batch_ordered(lk_handle* h, const lk_point* d_pts, uint32_t first_slo
     if (!e) {   // a batch not seen before (or forgotten): the least recently used entry goes; nothing is examined yet, only its stamp is taken
         e = h->ord[0].tick <= h->ord[1].tick ? &h->ord[0] : &h->ord[1];
         if (!e->d_ref) {
-            HIPCHK(h, hipMalloc(&e->d_ref, 2 * sizeof(unsigned long long)));
+            HIPCHK(h, hipMalloc(&e->d_ref, LK_ORDW_COUNT * sizeof(unsigned long long)));
             HIPCHK(h, hipHostMalloc(&e->h_seen, sizeof(unsigned int), hipHostMallocMapped));
             HIPCHK(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&e->d_seen), e->h_seen, 0));
         } else {
-            HIPCHK(h, hipStreamSynchronize(h->stream));   // replays of the entry's former batch may still be using its stamp words
-            for (int i = 0; i < lk_handle::kMaxGroups - 1; ++i)
-                if (h->side[i]) HIPCHK(h, hipStreamSynchronize(h->side[i]));
+            LKCHK(drain());   // replays of the entry's former batch may still be using its words
         }
         *reinterpret_cast<volatile unsigned int*>(e->h_seen) = 0u;
-        HIPCHK(h, hipMemsetAsync(e->d_ref, 0, 2 * sizeof(unsigned long long), st));
+        HIPCHK(h, hipMemsetAsync(e->d_ref, 0, LK_ORDW_COUNT * sizeof(unsigned long long), st));
         e->src = d_pts, e->n_scans = n_scans, e->n_pts = n_pts, e->n_buckets = n_buckets, e->off_hash = oh;
         e->as_given = false, e->have_copy = false;
+        e->probes = 0, e->waited = false;
     }
     e->tick = ++h->ord_tick;
     if (e->as_given) return LK_OK;
-    const unsigned int seen = *reinterpret_cast<volatile unsigned int*>(e->h_seen);   // written by the device; may lag behind the replays still in flight
+    const auto count = [&]() { return *reinterpret_cast<volatile unsigned int*>(e->h_seen); };   // written by the device; may lag behind the replays still in flight
+    unsigned int seen = count();
     if (e->have_copy && seen < LK_ORD_SORTED) {   // a replay found other content in the caller's buffer: the copy is of no use any more
         e->have_copy = false;
+        e->probes = 1, e->waited = false;         // (that replay was the new content's first)
         ++h->ord_stale;
     }
+    if (!e->have_copy && !now && !e->waited && e->probes >= (unsigned int)h->batch_order_after && seen < (unsigned int)h->batch_order_after) {
+        // enough replays are enqueued for the count to be there, but it is not (yet): this may be the replay that sorts.  Wait for the ones in flight,
+        // once per content - the sort would wait for them anyway; a buffer whose content keeps changing pays this a single time
+        LKCHK(drain());
+        e->waited = true;
+        seen = count();
+    }
+    unsigned long long* use = e->d_ref + LK_ORDW_USE + 2 * ring;
     if (!e->have_copy && (now || seen >= (unsigned int)h->batch_order_after) && seen < LK_ORD_SORTED) {
         // the same content has been replayed often enough to be worth 5.6 ms: examine it, and unless it already is in voxel order, sort it into the copy
         ++h->ord_examined;
         HIPCHK(h, hipStreamSynchronize(st));   // the priors are armed
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int i = 0; i < lk_handle::kMaxGroups - 1; ++i)   // (replays in flight on the other streams write the entry's stamp words)
-            if (h->side[i]) HIPCHK(h, hipStreamSynchronize(h->side[i]));
-        unsigned int* d_uns = reinterpret_cast<unsigned int*>(e->d_ref + 1);   // (borrowed: ref[1] is written again by the stamp kernel below)
+        LKCHK(drain());
+        unsigned int* d_uns = reinterpret_cast<unsigned int*>(e->d_ref + LK_ORDW_SCRATCH);
         HIPCHK(h, hipMemsetAsync(d_uns, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(lk_sort_check_kernel, dim3((unsigned int)((n_pts + 255) / 256), (unsigned int)n_scans), dim3(256), 0, st, h->pr, h->d_filters + first_slot, d_pts, n_pts, d_uns);
         HIPCHK(h, hipGetLastError());
         unsigned int uns = 0;
         HIPCHK(h, hipMemcpyAsync(&uns, d_uns, sizeof(uns), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        HIPCHK(h, hipMemsetAsync(d_uns, 0, sizeof(unsigned long long), st));
         bool sort_it = uns != 0;
         if (sort_it) {
             const size_t bytes = sizeof(lk_point) * n_scans * n_pts;
@@ -2051,14 +2053,15 @@ static int batch_ordered(lk_handle* h, const lk_point* d_pts, uint32_t first_slo
         if (rc) return rc;
         ++h->ord_sorted;
         e->have_copy = true;
-        hipLaunchKernelGGL(lk_batch_stamp_kernel, dim3(1), dim3(256), 0, st, d_pts, n_scans * n_pts, e->d_ref, e->d_seen, LK_ORD_SET);
+        hipLaunchKernelGGL(lk_batch_stamp_kernel, dim3(1), dim3(256), 0, st, d_pts, n_scans * n_pts, e->d_ref, use, e->d_seen, LK_ORD_SET);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipStreamSynchronize(st));
     } else {
-        hipLaunchKernelGGL(lk_batch_stamp_kernel, dim3(1), dim3(256), 0, st, d_pts, n_scans * n_pts, e->d_ref, e->d_seen, e->have_copy ? LK_ORD_CHECK : LK_ORD_PROBE);
+        hipLaunchKernelGGL(lk_batch_stamp_kernel, dim3(1), dim3(256), 0, st, d_pts, n_scans * n_pts, e->d_ref, use, e->d_seen, e->have_copy ? LK_ORD_CHECK : LK_ORD_PROBE);
         HIPCHK(h, hipGetLastError());
+        if (!e->have_copy) ++e->probes;
     }
-    if (e->have_copy) ro->alt_pts = e->copy, ro->alt_use = e->d_ref;
+    if (e->have_copy) ro->alt_pts = e->copy, ro->alt_use = use;
     return LK_OK;
 }
 
@@ -2088,9 +2091,10 @@ int lk_batch_prepare_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, si
     if (!d_pts || !bucket_off) return fail(h, LK_ERR_INVALID, "null argument");
     if (n_scans == 0 || n_scans > h->cfg.n_slots || n_pts == 0 || n_buckets == 0) return fail(h, LK_ERR_INVALID, "empty batch, or n_scans exceeds n_slots");
     if (bucket_off[0] != 0 || bucket_off[n_buckets] != n_pts) return fail(h, LK_ERR_INVALID, "bucket_off must cover the scan: bucket_off[0] == 0, bucket_off[n_buckets] == n_pts");
+    if (h->batch_order_mode == 0) return LK_OK;   // LK_BATCH_ORDER_AS_GIVEN: no replay would read the copy
     int rc = join_side_streams(h);
     if (rc) return rc;
-    rc = batch_ordered(h, d_pts, 0, n_scans, n_pts, bucket_off, n_buckets, h->stream, nullptr, true);
+    rc = batch_ordered(h, d_pts, 0, n_scans, n_pts, bucket_off, n_buckets, h->stream, 0, nullptr, true);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return LK_OK;
@@ -2197,7 +2201,7 @@ int lk_batch_replay_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, siz
     HIPCHK(h, hipGetLastError());
     ResidualOut ro;
     memset(&ro, 0, sizeof(ro));
-    LKCHK(batch_ordered(h, d_pts, 0, n_scans, n_pts, bucket_off, n_buckets, h->stream, &ro));   // the caller's buffer, or the library's voxel-ordered copy of it
+    LKCHK(batch_ordered(h, d_pts, 0, n_scans, n_pts, bucket_off, n_buckets, h->stream, 0, &ro));   // the caller's buffer, or the library's voxel-ordered copy of it: decided on h->stream, before the groups fork
     // the single-workgroup update / predict kernels of one group (half of the CUs idle, latency-bound) overlap the residual kernel of the other group
     const SlotGroups grp(h, S, h->replay_groups, kReplayGroupSlots);
     LKCHK(grp.fork());
@@ -2827,7 +2831,7 @@ int lk_batch_replay_async_dev(lk_handle* h, const lk_point* d_pts, uint32_t firs
     hipLaunchKernelGGL(lk_set_times_kernel, dim3((S + 63) / 64), dim3(64), 0, st, fl, S, t_begin);
     ResidualOut ro;
     memset(&ro, 0, sizeof(ro));
-    LKCHK(batch_ordered(h, d_pts, first_slot, n_scans, n_pts, bucket_off, n_buckets, st, &ro));   // first sight of a batch synchronises; afterwards one small launch
+    LKCHK(batch_ordered(h, d_pts, first_slot, n_scans, n_pts, bucket_off, n_buckets, st, ring, &ro));   // first sight of a batch synchronises; afterwards one small launch
     LKCHK(enqueue_frozen_chain(h, st, false, first_slot, S, d_pts, ro.alt_pts, n_pts, live, bucket_off, bucket_dt, t_begin, fmap, ro));
     if (host_out) {
         hipLaunchKernelGGL(lk_pose_gather_kernel, dim3((S + 63) / 64), dim3(64), 0, st, fl, h->d_poses + first_slot, S);

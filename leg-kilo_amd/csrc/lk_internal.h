@@ -156,10 +156,12 @@ struct lk_handle {
         bool as_given = false;             // the batch already was in voxel order: replayed where it lies, no copy, no stamp
         lk_point* copy = nullptr;          // voxel-ordered copy (every bucket of every scan sorted by root-voxel key under the priors of the first sight)
         size_t copy_bytes = 0;
-        unsigned long long* d_ref = nullptr;   // device: [0] content stamp of src at the replay before, [1] 1 = this replay reads the copy
+        unsigned long long* d_ref = nullptr;   // device, LK_ORDW_COUNT words (lk_batch_stamp.h): the stamp the copy was made from, the stamp of the replay before, a decision pair per ring stream
         bool have_copy = false;            // the copy holds the buffer's content as of the last sort (as far as the host knows: h_seen says what the device found)
         unsigned int* h_seen = nullptr;    // host-mapped, written by the device: replays in a row that found the same content stamp; LK_ORD_SORTED while the copy is current
         unsigned int* d_seen = nullptr;
+        unsigned int probes = 0;           // counting replays enqueued for the content at hand (h_seen may not show them yet)
+        bool waited = false;               // ... and the replays in flight have been waited for once, when h_seen lagged behind that number
         uint64_t tick = 0;
     };
     OrdEntry ord[2];

@@ -2244,6 +2244,16 @@ int lk_batch_residuals_dev(lk_handle* h, const lk_point* d_pts, size_t n_scans, 
     return LK_OK;
 }
 
+#ifdef LK_DEBUG_PROLOGUE
+// DEBUG BUILD ONLY: the batch residual kernel's phase clocks (lk_res_phase_dbg, lk_point_kernels.h) of this translation unit's launches - the
+// frozen-map batch entries - since the last call, in ticks of 10 ns; reset behind the read.  Not declared in include/legkilo_hip.h.
+extern "C" int lk_debug_res_phases(unsigned long long* out8) {
+    if (hipDeviceSynchronize() != hipSuccess) return LK_ERR_HIP;
+    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(lk_res_phase_dbg), 8 * sizeof(unsigned long long)) != hipSuccess) return LK_ERR_HIP;
+    const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    return hipMemcpyToSymbol(HIP_SYMBOL(lk_res_phase_dbg), zero, sizeof(zero)) == hipSuccess ? LK_OK : LK_ERR_HIP;
+}
+#endif
 #ifdef LK_DEBUG_PHASES
 // the one-wave-per-scan kernels' phase clocks (lk_sw_dbg), printed and reset
 static void dump_scan_wave_phases(hipStream_t st) {

@@ -19,6 +19,13 @@
 // (point_lite_terms: an fp64 square root and an IEEE division, ~50 serial VALU no address depends on) are computed while the record travels,
 // and match_flat<XID, true> pins and evaluates the pieces where they landed.  Same expressions, same bits; the wave's second memory trip
 // starts that much earlier.
+//
+// Order of the batch kernel's prologue (lk_residual_kernel<*, 1, *, *>): slot and tile (XCD-aware decode; workgroups beyond the grid leave before any
+// load), the one word alt_use[1] that names the buffer, the lane's non-temporal point load (lanes with i >= n load nothing), and only THEN the
+// bucket constants out of the slot's filter record - their scalar loads are in flight together under the point's HBM trip, and the first wait
+// behind the point's load is the one in front of the transform.  residual_tile<..., PRELOADED = true> takes the point by value.  Every other
+// caller of residual_tile (verify, ragged, small-bucket, stream, overlay, scan-resident kernels) and the hash-table instantiations of the batch
+// kernel load constants first and the point inside residual_tile, as before.
 #pragma once
 #include "lk_device.h"
 
@@ -338,6 +345,39 @@ __device__ __forceinline__ bool spec_suspect(const LkMap& m, int code, unsigned 
 #else
 #define LK_RES_BOUNDS __launch_bounds__(LK_RB)
 #endif
+#ifdef LK_DEBUG_PROLOGUE
+// DEBUG BUILD ONLY (make EXTRA=-DLK_DEBUG_PROLOGUE; with -DLK_PROLOGUE_OLD_ORDER the batch kernel keeps the order it had before the point load moved
+// into its prologue): where a wave of lk_residual_kernel spends its life.  Lane 0 stamps wall_clock64() (100 MHz) into six words of LDS - 0 entry,
+// 1 point load issued, 2 point and bucket constants arrived, 3 home cell's record arrived, 4 start of K3, 5 end - and every 64th workgroup adds the
+// five differences to lk_res_phase_dbg[0..4]; [6] = sampled waves whose lane 0 requested no record, [7] = sampled waves.  "Arrived" is made a fact
+// by an empty asm that takes the loaded registers as inputs: the compiler has to wait for them in front of it (in the shipped order it waits piece
+// by piece, further down).  Read and reset by lk_debug_res_phases (legkilo_hip.hip).  The other callers of residual_tile pass no stamp memory.
+static __device__ unsigned long long lk_res_phase_dbg[8];
+#define LK_PHASE_PARAM , unsigned long long* ph = nullptr
+#define LK_PHASE(k)                                    \
+    do {                                               \
+        if (ph) {                                      \
+            const unsigned long long t_ = wall_clock64(); \
+            if (lane == 0) ph[k] = t_;                 \
+        }                                              \
+    } while (0)
+#define LK_PHASE_ARRIVED(k, p, bc)                                                                                                      \
+    do {                                                                                                                                \
+        if (ph) asm volatile("" ::"v"(p.x), "v"(p.y), "v"(p.z), "s"(bc.R[0]), "s"(bc.p[2]), "s"(bc.Prr.xx), "s"(bc.Ppp.zz) : "memory"); \
+        LK_PHASE(k);                                                                                                                    \
+    } while (0)
+#define LK_PHASE_RECORD(k, r)                                                                                                                       \
+    do {                                                                                                                                            \
+        if (ph) asm volatile("" ::"v"(r.q0.x), "v"(r.q1.x), "v"(r.q2.x), "v"(r.tail.x), "v"(r.rt.v0.x), "v"(r.rt.v1.x), "v"(r.rt.v2.x), "v"(r.rt.v3.x), \
+                             "v"(r.rt.v4.x) : "memory");                                                                                            \
+        LK_PHASE(k);                                                                                                                                \
+    } while (0)
+#else
+#define LK_PHASE_PARAM
+#define LK_PHASE(k) ((void)0)
+#define LK_PHASE_ARRIVED(k, p, bc) ((void)0)
+#define LK_PHASE_RECORD(k, r) ((void)0)
+#endif
 // One 64-point tile of the residual pass, executed by one wave: K1 (transform + covariance terms), K2 (home voxel, one
 // neighbour retry), the observation row, and K3 for the tile.  `rows` is the wave's private LDS region (64 x LK_ROW2
 // doubles).  Returns, in lane (q, half) = (lane & 31, lane >> 5), component q of [A(21) b(6) sumR count] summed over the
@@ -346,10 +386,14 @@ __device__ __forceinline__ bool spec_suspect(const LkMap& m, int code, unsigned 
 // SHORT (the small-bucket kernels, where a tile usually holds a handful of points): the sums run over the rows that hold points,
 // rounded up to eight - the rows behind them are zero rows, and fma(0, 0, acc) == acc for every acc this loop can hold (it starts
 // at +0 and can never become -0), so the bits are those of the full loop.
-template <bool EMIT_ROWS, int GRID = 2, bool XID = false, bool SHORT = false, bool SPEC = false>
+// PRELOADED (lk_residual_kernel): `pre` is point i of spts, loaded by the caller ahead of the bucket constants (lanes with i >= n: anything);
+// every other caller loads it here.
+typedef float lk_f4v __attribute__((ext_vector_type(4)));
+template <bool EMIT_ROWS, int GRID = 2, bool XID = false, bool SHORT = false, bool SPEC = false, bool PRELOADED = false>
 __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams& pr, const BucketConst& bc,
                                                 const float4* __restrict__ spts, int i, int n, double* rows, int lane,
-                                                const ResidualOut& out, size_t out_base, const LkOvView* ovv = nullptr) {
+                                                const ResidualOut& out, size_t out_base, const LkOvView* ovv = nullptr,
+                                                lk_f4v pre = lk_f4v{0.f, 0.f, 0.f, 0.f} LK_PHASE_PARAM) {
     bool ok = false;
     double h[6] = {0, 0, 0, 0, 0, 0}, z = 0, R = 0;
     {
@@ -367,8 +411,11 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
         best.row = rows + lane * LK_ROW2;
         bool home = false;
         if (i < n) {
-            typedef float lk_f4v __attribute__((ext_vector_type(4)));
-            const lk_f4v p = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(spts) + i);   // read once: keep it from displacing plane records in L2 (round 6: 1.560 -> 1.537 ms per step, same bits)
+            lk_f4v p;
+            if (PRELOADED) p = pre;
+            else p = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(spts) + i);   // read once: keep it from displacing plane records in L2 (round 6: 1.560 -> 1.537 ms per step, same bits)
+            if (!PRELOADED) LK_PHASE(1);
+            LK_PHASE_ARRIVED(2, p, bc);
             if (REC_FIRST) point_lite_pos<XID>(p.x, p.y, p.z, bc, pr, g);
             else g = point_lite<XID>(p.x, p.y, p.z, bc, pr);
             if (out.world) {
@@ -388,6 +435,7 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
                 RecRegs home_rec;
                 rec_request(&map.match[root], home_rec);
                 point_lite_terms(p.x, p.y, p.z, pr, g);
+                LK_PHASE_RECORD(3, home_rec);
                 home = match_flat<XID, true>(map, root, g, bc, pr, success, prob, best, &home_rec);
             }
         }
@@ -427,6 +475,7 @@ __device__ __forceinline__ double residual_tile(const LkMap& map, const LkParams
     // of [A(21) b(6) sumR count] over the 32 rows of its half, in row order, branch-free and with ONE fma per row
     // (ds_read_b64 broadcasts, all loads independent of the arithmetic); the two halves are combined with one
     // cross-lane read.
+    LK_PHASE(4);
     if (!ok) {   // matched lanes wrote their final row when they took their plane
         double* r = rows + lane * LK_ROW2;
 #pragma unroll
@@ -533,15 +582,54 @@ __global__ void LK_RES_BOUNDS
     }
     const int tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
+    const int i = bx * LK_RB + tid;
+#ifdef LK_DEBUG_PROLOGUE
+    __shared__ unsigned long long ph_[8];
+    unsigned long long* const ph = ph_;
+    if (lane == 0) ph[1] = ph[2] = ph[3] = ph[4] = 0ull;
+    LK_PHASE(0);
+#endif
+    // The lane's point is requested FIRST: its address needs kernel arguments, the workgroup's id and the one word alt_use[1], nothing of the slot's
+    // filter record.  The ten scalar loads of load_bucket_const - R, p and two blocks of P out of a 7 560-B record that lk_update_wave_kernel has
+    // just written, read about once per CU: scalar-cache misses - then travel under the point's HBM trip instead of in front of it (the scalar
+    // counter cannot tell loads apart: with the alt_use word among them, the point's load waited for the whole record).  The empty asm keeps the
+    // compiler from hoisting the constants' loads back over the point's; it pins no pointer (pinned through "+s" operands, the filter reads
+    // became vector loads and scratch went from 12 to 176 B).  Same loads, same arithmetic, same bits.
+    // Frozen-grid instantiations only (GRID == 1: what the batch entries launch unless LEGKILO_GRID=0).  The hash-table ones keep constants first:
+    // with the point first <false, 0, true, false> went from 48 to 52 B of scratch and <true, 0, false, false> from 44 to 52 B.
+#ifdef LK_PROLOGUE_OLD_ORDER
+    constexpr bool POINT_FIRST = false;
+#else
+    constexpr bool POINT_FIRST = GRID == 1;
+#endif
     BucketConst bc;
-    load_bucket_const<false>(&filters[slot], pr, bc);
+    if (!POINT_FIRST) load_bucket_const<false>(&filters[slot], pr, bc);
     if (out.alt_use && out.alt_use[1] != 0ull) pts = out.alt_pts;   // wave-uniform (scalar load): the voxel-ordered copy of the same scans
-    const double acc = residual_tile<EMIT_ROWS, GRID, XID, false, SPEC>(map, pr, bc, reinterpret_cast<const float4*>(pts + (size_t)slot * pts_slot_stride),
-                                                bx * LK_RB + tid, n, &stage[wv][0], lane, out, (size_t)slot * out_slot_stride);
+    const float4* spts = reinterpret_cast<const float4*>(pts + (size_t)slot * pts_slot_stride);
+    lk_f4v p0 = lk_f4v{0.f, 0.f, 0.f, 0.f};
+    if (POINT_FIRST) {
+        if (i < n) p0 = __builtin_nontemporal_load(reinterpret_cast<const lk_f4v*>(spts) + i);   // lanes beyond the bucket's end load nothing
+        asm volatile("" ::: "memory");
+        LK_PHASE(1);
+        load_bucket_const<false>(&filters[slot], pr, bc);
+    }
+#ifdef LK_DEBUG_PROLOGUE
+    const double acc = residual_tile<EMIT_ROWS, GRID, XID, false, SPEC, POINT_FIRST>(map, pr, bc, spts, i, n, &stage[wv][0], lane, out, (size_t)slot * out_slot_stride, nullptr, p0, ph);
+#else
+    const double acc = residual_tile<EMIT_ROWS, GRID, XID, false, SPEC, POINT_FIRST>(map, pr, bc, spts, i, n, &stage[wv][0], lane, out, (size_t)slot * out_slot_stride, nullptr, p0);
+#endif
     if (!EMIT_ROWS && lane < LK_NPART) {
         const size_t wave_id = (size_t)bx * (LK_RB / LK_WAVE) + wv;
         partials[(size_t)slot * part_slot_stride + wave_id * LK_NPART + lane] = (lane < 29) ? acc : 0.0;
     }
+#ifdef LK_DEBUG_PROLOGUE
+    LK_PHASE(5);
+    if (lane == 0 && ((blockIdx.x + blockIdx.y * gridDim.x) & 63u) == 0u && ph[2] != 0ull) {   // (ph[2] == 0: lane 0 lies beyond the bucket's end)
+        if (ph[3] == 0ull) ph[3] = ph[2], atomicAdd(&lk_res_phase_dbg[6], 1ull);   // lane 0 had no home cell (or no point): no record trip
+        for (int k = 0; k < 5; ++k) atomicAdd(&lk_res_phase_dbg[k], ph[k + 1] - ph[k]);
+        atomicAdd(&lk_res_phase_dbg[7], 1ull);
+    }
+#endif
 }
 
 // ---------------------------------------------------------------- pipelined stream path: verify pass

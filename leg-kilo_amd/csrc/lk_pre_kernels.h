@@ -102,6 +102,7 @@ __global__ void __launch_bounds__(256)
     const float4 o = make_float4(sx / cnt, sy / cnt, sz / cnt, sc / cnt);
     reinterpret_cast<float4*>(cells)[c] = o;
     unsigned int u = __float_as_uint(o.w);
+    if (u == 0x80000000u) u = 0u;  // -0.0 (a sum of negative denormals that underflows in the division) and +0.0 are ONE time: a tie, kept in cell order
     tkeys[c] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving image of the float time stamp
     tvals[c] = c;
 }

@@ -157,7 +157,7 @@ def test_decode_oracle_matches_vectorised_host_version(scene):
     host = synth.preprocess_velodyne(synth.vlp16_scan(scene.world, scene.traj, 1.0, scene.P)[:3000], 3, 1.5)
     assert len(got) == len(host) > 500
     for f in got.dtype.names:
-        assert np.array_equal(got[f], host[f]), f
+        assert got[f].tobytes() == host[f].tobytes(), f   # bits: == cannot tell -0.0 from +0.0
     assert abs(tb - (100.0 + float(raw["time"][0]))) < 1e-9 and te > tb
     # 2 ms bins (lidar_processing.cc:48)
     assert np.allclose(got["curvature"] * 500.0, np.round(got["curvature"] * 500.0), atol=1e-4)
@@ -173,7 +173,7 @@ def test_decode_vectorised_equals_the_loop(scene, lidar_type):
     b, bb, be = po.decode_vec(raw, lidar_type, scale, 3, 1.5, header_stamp=7.0)
     assert len(a) == len(b) > 800 and (ab, ae) == (bb, be)
     for f in a.dtype.names:
-        assert np.array_equal(a[f], b[f]), f
+        assert a[f].tobytes() == b[f].tobytes(), f
 
 
 @pytest.mark.gpu
@@ -186,7 +186,7 @@ def test_gpu_decode_bit_exact(scene, hip_lib, lidar_type):
     got, gb, ge = g.decode_scan(raw.tobytes(), len(raw), layout, scale, 3, 1.5, header_stamp=50.0)
     assert len(got) == len(want) > 1000
     for f in want.dtype.names:
-        assert np.array_equal(got[f], want[f]), (f, int((got[f] != want[f]).sum()))
+        assert got[f].tobytes() == want[f].tobytes(), (f, int((got[f].view(np.uint32) != want[f].view(np.uint32)).sum()))
     assert gb == tb and ge == te
     # decode -> voxel grid -> time sort, all on the device, equals the oracle chain
     full, layout, scale = raw_message(scene, 2.0, lidar_type)
@@ -195,5 +195,5 @@ def test_gpu_decode_bit_exact(scene, hip_lib, lidar_type):
     assert np.all(np.diff(ds["curvature"]) >= 0) and 1000 < len(ds) < len(dec)
     want_ds = po.preprocess(dec, 0.3)
     for f in want_ds.dtype.names:
-        assert np.array_equal(ds[f], want_ds[f]), f
+        assert ds[f].tobytes() == want_ds[f].tobytes(), f
     g.close()

@@ -509,6 +509,49 @@ int lk_batch_replay_overlay_runs_cloud_dev(lk_handle* h, const lk_point* d_pts, 
                                            float* d_world_out, uint32_t* scan_bucket_off);
 int lk_runs_bucket_poses_dev(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* d_out);
 int lk_runs_bucket_poses(lk_handle* h, uint64_t first_bucket, size_t n, lk_bucket_pose* out);
+/* Absolute trajectory error of n_traj trajectories against ground truth, in HBM: time association, optional closed-form rigid alignment, RMSE / mean /
+ * max of the position errors - leg-kilo_amd/tum.py's associate + ate per trajectory, one small record each for the host.  What a caller of the run
+ * replays chooses a slot with, and what a localisation sweep over many priors is ranked by.
+ * Layout: d_*_t and d_*_pos are DEVICE pointers (8-byte aligned) to the first sample's stamp and to its three position doubles; sample k lies
+ * k * stride BYTES further on, one stride for both pointers of a side (a multiple of 8, >= 8 for the stamps and >= 24 for the positions).  A packed
+ * [t x y z] table has stride 32; an lk_bucket_pose table has stride 144 with &rec[0].t and &rec[0].pos[0].
+ * est_off, gt_off: HOST tables of n_traj + 1 entries, not decreasing; trajectory r owns the samples off[r] .. off[r+1]) of its side.  A range may be
+ * empty, off[0] need not be 0, nothing outside the ranges is read.  A trajectory holds fewer than 2^32 - 1 samples on either side.
+ * Association: estimate sample i is paired with the ground-truth sample j(i) of the same trajectory that minimises fabs(t_est[i] - t_gt[j]), the
+ * EARLIEST j on equal distance (equal ground-truth stamps are allowed), and the pair counts when that fabs(..) - one double subtraction - is
+ * <= max_dt.  Every estimate sample decides alone, so a ground-truth sample may serve several estimate samples.  Whenever consecutive stamps of BOTH
+ * trajectories lie more than 2 * max_dt apart, these are exactly the pairs of tum.associate.
+ * Error: e_i = |g_i - (R p_i + t)| over the pairs (g ground truth, p estimate).  LK_ATE_ALIGN: R, t minimise sum e_i^2 over proper rotations
+ * (det R = +1) - tum.ate(pa = gt, pb = est, align=True); one pair gives e = 0; for collinear or coincident pairs R is not unique and any minimiser is
+ * returned (the error figures are unique).  Without the flag R = I, t = 0 and e_i = |g_i - p_i|, exactly.
+ * out: HOST, n_traj records, every byte written.  Synchronous; no filter slot, no map and no bucket table is touched, the inputs are not modified.
+ * A sum is taken in an order that depends on the trajectory's own samples only: a trajectory's record has the same bits whatever else the call holds.
+ * LK_ERR_INVALID before anything is launched: n_traj == 0 (or >= 2^31), null pointers or tables, a misaligned pointer, a bad stride, decreasing
+ * offsets, 2^32 - 1 samples or more in one trajectory, max_dt not finite or below 0, unknown flag bits.
+ * LK_ERR_INVALID found on the device: a trajectory whose stamps, on either side, decrease or are not finite (the message names the first such
+ * trajectory and the side); out is then undefined and the handle stays usable.  A non-finite POSITION is not an error of the call - a diverged filter
+ * scores NaN and does not abort a sweep: a trajectory with one in a PAIRED sample gets status LK_ATE_NONFINITE, NaN figures, R = I, t = 0, worst = 0
+ * and its n_pairs; the other trajectories are unaffected, and positions of unpaired samples are never read.  n_pairs == 0: NaN figures, status 0. */
+typedef struct lk_ate {          /* 136 bytes */
+    double   rmse, mean, max;    /* of e_i = |g_i - (R p_i + t)| over the pairs; NaN when n_pairs == 0 or LK_ATE_NONFINITE */
+    double   rot[9], trans[3];   /* row-major R and t, estimate -> ground truth; identity and 0 without LK_ATE_ALIGN */
+    uint64_t n_pairs;
+    uint32_t worst;              /* index, within the trajectory's estimate, of the pair with the largest e_i (first on ties) */
+    uint32_t status;             /* 0, or LK_ATE_NONFINITE: a PAIRED position was not finite */
+} lk_ate;
+#define LK_ATE_ALIGN     1u
+#define LK_ATE_NONFINITE 1u
+int lk_traj_ate_dev(lk_handle* h, size_t n_traj,
+                    const double* d_est_t, const double* d_est_pos, size_t est_stride, const uint64_t* est_off,
+                    const double* d_gt_t,  const double* d_gt_pos,  size_t gt_stride,  const uint64_t* gt_off,
+                    double max_dt, uint32_t flags, lk_ate* out);
+/* The same evaluation with the estimate read where it lies: the bucket table the handle's last _cloud run replay recorded (t and pos of its
+ * lk_bucket_pose records, no copy).  Run r is the records run_bucket_off[r] .. run_bucket_off[r+1]) (HOST, n_runs + 1 entries, not decreasing) - with
+ * the replay's tables, scan_bucket_off[run_off[r]].  LK_ERR_STATE when the handle's last batch replay recorded nothing (the getters' condition),
+ * LK_ERR_INVALID for a range past the table's records; otherwise as lk_traj_ate_dev.  The table, the slots and the overlays are left as they are. */
+int lk_runs_ate_dev(lk_handle* h, size_t n_runs, const uint64_t* run_bucket_off,
+                    const double* d_gt_t, const double* d_gt_pos, size_t gt_stride, const uint64_t* gt_off,
+                    double max_dt, uint32_t flags, lk_ate* out);
 /* Downsampled map clouds from registered points, many files per call: PcdSaver::downsampleAndSave (common/pcd_saver.hpp:114-121) up to and excluding
  * savePCDFileBinaryCompressed - pcl::VoxelGrid<PointXYZINormal> at `leaf` over each file's buffer of frames.
  * File f = the 16-byte x y z intensity records file_off[f] .. file_off[f+1) of d_world (DEVICE, 16-byte aligned, the layout of d_world_out; consecutive
@@ -555,7 +598,7 @@ int lk_overlay_export(lk_handle* h, uint32_t slot, void* blob, size_t* bytes);
  * replaces the base voxel of that key as a whole octree, a private root voxel of a key the base map lacks is added, every other voxel stays bit for
  * bit; records are moved, not recomputed, and get new ids (the ranks of a prefix sum: the same call on the same state gives the same ids).
  * Synchronous.  With lk_batch_get_states(_dev) -> lk_batch_set_priors(_dev) this makes windowed mapping of any length out of the replays with
- * insert: replay a window on all slots, choose a slot, commit it, lk_map_slide if wanted, replay the next window.
+ * insert: replay a window on all slots, choose a slot (with ground truth: lk_runs_ate_dev), commit it, lk_map_slide if wanted, replay the next window.
  * The call commits ONE slot.  The reference has no answer for a voxel two slots changed; the other slots' overlays are stale afterwards, as after any
  * map change: lk_overlay_export and a second lk_overlay_commit answer LK_ERR_STATE until the next replay with insert, and the frozen-map grid is
  * rebuilt by the next batch replay.

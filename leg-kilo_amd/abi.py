@@ -144,6 +144,32 @@ def bucket_pose_dtype():
     return dt
 
 
+class lk_ate(C.Structure):
+    _fields_ = [
+        ("rmse", C.c_double),
+        ("mean", C.c_double),
+        ("max", C.c_double),
+        ("rot", C.c_double * 9),
+        ("trans", C.c_double * 3),
+        ("n_pairs", C.c_uint64),
+        ("worst", C.c_uint32),
+        ("status", C.c_uint32),
+    ]
+
+
+LK_ATE_ALIGN = 1       # lk_traj_ate_dev / lk_runs_ate_dev flag: remove the best rigid motion estimate -> ground truth first
+LK_ATE_NONFINITE = 1   # lk_ate.status: a paired position was not finite
+
+
+def ate_dtype():
+    """numpy view of lk_ate (136 B): the records of lk_traj_ate_dev / lk_runs_ate_dev."""
+    import numpy as np
+
+    dt = np.dtype([("rmse", "<f8"), ("mean", "<f8"), ("max", "<f8"), ("rot", "<f8", 9), ("trans", "<f8", 3), ("n_pairs", "<u8"), ("worst", "<u4"), ("status", "<u4")])
+    assert dt.itemsize == C.sizeof(lk_ate) == 136
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

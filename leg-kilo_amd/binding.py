@@ -28,7 +28,7 @@ EXPORTS = [
     "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
     "lk_batch_replay_runs_dev", "lk_overlay_commit",
     "lk_batch_replay_runs_cloud_dev", "lk_batch_replay_overlay_runs_cloud_dev", "lk_runs_bucket_poses_dev", "lk_runs_bucket_poses",
-    "lk_downsample_clouds_dev", "lk_downsample_clouds",
+    "lk_downsample_clouds_dev", "lk_downsample_clouds", "lk_traj_ate_dev", "lk_runs_ate_dev",
 ]
 
 
@@ -645,6 +645,47 @@ class LegKiloHip:
         out = np.zeros(n, dtype=abi.bucket_pose_dtype())
         self._chk(self.L.lk_runs_bucket_poses(self.h, C.c_uint64(first_bucket), C.c_size_t(n), _p(out)))
         return out
+
+    def traj_ate_dev(self, d_est_t, d_est_pos, est_stride, est_off, d_gt_t, d_gt_pos, gt_stride, gt_off, max_dt, align=False, flags=None, out=None):
+        """Absolute trajectory error of len(est_off) - 1 trajectories against ground truth, all in device memory (lk_traj_ate_dev): d_*_t / d_*_pos -
+        device pointers to the first sample's stamp and position, sample k `stride` bytes further on; est_off / gt_off - the trajectories' sample
+        ranges.  Pairs by nearest stamp within max_dt, align: the best rigid motion removed first.  Returns abi.ate_dtype() records, one per
+        trajectory (out: an array of that dtype to write into instead - n_traj records of it are written)."""
+        eo = np.ascontiguousarray(est_off, dtype=np.uint64)
+        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
+        n = max(len(eo) - 1, 0)
+        assert len(go) == len(eo)
+        res = np.zeros(max(n, 1), dtype=abi.ate_dtype()) if out is None else out
+        fl = (abi.LK_ATE_ALIGN if align else 0) if flags is None else int(flags)
+        ptr = lambda d: C.c_void_p(d) if d else None   # noqa: E731
+        self._chk(self.L.lk_traj_ate_dev(self.h, C.c_size_t(n), ptr(d_est_t), ptr(d_est_pos), C.c_size_t(est_stride), _p(eo), ptr(d_gt_t), ptr(d_gt_pos),
+                                         C.c_size_t(gt_stride), _p(go), C.c_double(max_dt), C.c_uint32(fl), _p(res)))
+        return res[:n]
+
+    def runs_ate_dev(self, run_bucket_off, d_gt_t, d_gt_pos, gt_stride, gt_off, max_dt, align=False, flags=None):
+        """The same with the estimate read from the bucket table of the last _cloud run replay (lk_runs_ate_dev): run r = the records
+        run_bucket_off[r] : run_bucket_off[r + 1] (scan_bucket_off[run_off]); the ground truth in device memory."""
+        ro = np.ascontiguousarray(run_bucket_off, dtype=np.uint64)
+        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
+        n = max(len(ro) - 1, 0)
+        assert len(go) == len(ro)
+        res = np.zeros(max(n, 1), dtype=abi.ate_dtype())
+        fl = (abi.LK_ATE_ALIGN if align else 0) if flags is None else int(flags)
+        self._chk(self.L.lk_runs_ate_dev(self.h, C.c_size_t(n), _p(ro), C.c_void_p(d_gt_t) if d_gt_t else None, C.c_void_p(d_gt_pos) if d_gt_pos else None,
+                                         C.c_size_t(gt_stride), _p(go), C.c_double(max_dt), C.c_uint32(fl), _p(res)))
+        return res[:n]
+
+    def runs_ate(self, run_bucket_off, gt_t, gt_pos, gt_off, max_dt, align=False):
+        """runs_ate_dev with the ground truth taken from the host: gt_t [m], gt_pos [m, 3] are uploaded as one packed [t x y z] table (stride 32) for
+        the call.  What the windowed-mapping recipe chooses a slot with: replay, runs_ate, overlay_commit(argmin rmse)."""
+        gt = np.ascontiguousarray(np.concatenate([_f64(gt_t).reshape(-1, 1), _f64(gt_pos).reshape(-1, 3)], axis=1))
+        d_gt = self.device_malloc(max(gt.nbytes, 32))
+        try:
+            if gt.nbytes:
+                self.h2d(d_gt, gt)
+            return self.runs_ate_dev(run_bucket_off, d_gt, d_gt + 8, 32, gt_off, max_dt, align)
+        finally:
+            self.device_free(d_gt)
 
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records

@@ -397,6 +397,28 @@ class KiloPath {
         }
         if (scan_bucket_off) scan_bucket_off->swap(sbo);
     }
+    // lk_runs_ate_dev: every run of the last _cloud replay scored against ground truth where its bucket table lies - nearest stamp within max_dt,
+    // align: the best rigid motion removed first (tum.py's associate + ate).  Run r = the records run_bucket_off[r] .. [r+1]) of the table
+    // (scan_bucket_off[run_off[r]]); ground truth in HBM, sample k gt_stride bytes behind d_gt_t / d_gt_pos, trajectory r the samples gt_off[r] ..
+    // [r+1]).  One lk_ate per run: "choose a slot" is the run with the smallest rmse among those with status 0 and n_pairs > 0.
+    std::vector<lk_ate> runsAteDev(const std::vector<uint64_t>& run_bucket_off, const double* d_gt_t, const double* d_gt_pos, size_t gt_stride,
+                                   const std::vector<uint64_t>& gt_off, double max_dt, bool align = false) {
+        if (run_bucket_off.size() < 2 || gt_off.size() != run_bucket_off.size()) throw std::runtime_error("runsAteDev: table sizes differ");
+        std::vector<lk_ate> out(run_bucket_off.size() - 1);
+        dev_->check(lk_runs_ate_dev(dev_->h(), out.size(), run_bucket_off.data(), d_gt_t, d_gt_pos, gt_stride, gt_off.data(), max_dt,
+                                    align ? LK_ATE_ALIGN : 0u, out.data()));
+        return out;
+    }
+    // lk_traj_ate_dev: the same over trajectories the caller holds in HBM (strided tables on both sides)
+    std::vector<lk_ate> trajAteDev(const double* d_est_t, const double* d_est_pos, size_t est_stride, const std::vector<uint64_t>& est_off,
+                                   const double* d_gt_t, const double* d_gt_pos, size_t gt_stride, const std::vector<uint64_t>& gt_off, double max_dt,
+                                   bool align = false) {
+        if (est_off.size() < 2 || gt_off.size() != est_off.size()) throw std::runtime_error("trajAteDev: table sizes differ");
+        std::vector<lk_ate> out(est_off.size() - 1);
+        dev_->check(lk_traj_ate_dev(dev_->h(), out.size(), d_est_t, d_est_pos, est_stride, est_off.data(), d_gt_t, d_gt_pos, gt_stride, gt_off.data(),
+                                    max_dt, align ? LK_ATE_ALIGN : 0u, out.data()));
+        return out;
+    }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
     // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with

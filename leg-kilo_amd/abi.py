@@ -1,5 +1,8 @@
-"""ctypes mirrors of the PODs in include/legkilo_hip.h (keep field order identical)."""
+"""ctypes mirrors of the PODs in include/legkilo_hip.h (keep field order identical) and the C signatures of its prototypes."""
 import ctypes as C
+import functools
+import os
+import re
 
 LK_DIM_STATE = 30
 LK_STATE_DOUBLES = 36
@@ -14,6 +17,49 @@ LK_NODE_OCTO_STATE = 4
 LK_NODE_PTS_DROPPED = 8
 
 LK_COMMIT_ADOPT_FILTER = 1   # lk_overlay_commit: the committed slot's filter record also goes to slot 0
+
+
+class LegKiloError(RuntimeError):
+    pass
+
+
+_HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "legkilo_hip.h")
+_PROTOTYPE = re.compile(r"^([A-Za-z_][\w \*]*?)\b(lk_\w+)\s*\(([^;{]*?)\)\s*;", re.M)
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "unsigned int": C.c_uint32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "double": C.c_double, "float": C.c_float}
+
+
+def _ctype(decl, name, is_return=False):
+    """The ctypes type of one C type as the header writes it; `name`: the prototype, for the error."""
+    t = " ".join(decl.replace("*", " * ").split())
+    if t.endswith("*"):
+        return C.c_char_p if t == "const char *" else C.c_void_p
+    if is_return and t == "void":
+        return None
+    if t not in _SCALARS:
+        raise LegKiloError(f"include/legkilo_hip.h: {name}: no ctypes type for {'return type' if is_return else 'parameter'} '{decl.strip()}'")
+    return _SCALARS[t]
+
+
+def parse_signatures(header_text):
+    """{name: (restype, [argtypes])} of every lk_* prototype in the text of a header.  Nothing is guessed: a type outside the closed map
+    of _ctype, or an `lk_*(` that is not a prototype this reads, raises a LegKiloError that names it."""
+    text = re.sub(r"/\*.*?\*/", "", header_text, flags=re.S)
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        params = [p.strip() for p in params.split(",")] if params.strip() != "void" else []
+        sigs[name] = (_ctype(ret, name, True), [_ctype(re.sub(r"\w+$", "", p), name) for p in params])   # a parameter = its type, then its name
+    unread = sorted(set(re.findall(r"\b(lk_\w+)\s*\(", text)) - set(sigs))
+    if unread:
+        raise LegKiloError(f"include/legkilo_hip.h: cannot read the prototype of {', '.join(unread)}")
+    return sigs
+
+
+@functools.lru_cache(maxsize=None)
+def signatures():
+    """parse_signatures of include/legkilo_hip.h: what binding.lib() sets as restype / argtypes, and binding.EXPORTS."""
+    with open(_HEADER) as f:
+        return parse_signatures(f.read())
 
 
 class lk_config(C.Structure):
@@ -120,7 +166,7 @@ def pose_dtype():
     """numpy view of lk_pose (136 B) for vectorised access to pose buffers."""
     import numpy as np
 
-    return np.dtype([("rot", "<f8", 9), ("pos", "<f8", 3), ("vel", "<f8", 3), ("n_effect", "<u8"), ("n_buckets", "<u4"), ("n_updates", "<u4")])
+    return np.dtype(lk_pose)
 
 
 class lk_bucket_pose(C.Structure):
@@ -139,7 +185,7 @@ def bucket_pose_dtype():
     """numpy view of lk_bucket_pose (144 B): the records of lk_runs_bucket_poses."""
     import numpy as np
 
-    dt = np.dtype([("rot", "<f8", 9), ("pos", "<f8", 3), ("vel", "<f8", 3), ("t", "<f8"), ("first_point", "<u8"), ("n_points", "<u4"), ("n_effect", "<u4")])
+    dt = np.dtype(lk_bucket_pose)
     assert dt.itemsize == C.sizeof(lk_bucket_pose) == 144
     return dt
 
@@ -165,7 +211,7 @@ def ate_dtype():
     """numpy view of lk_ate (136 B): the records of lk_traj_ate_dev / lk_runs_ate_dev."""
     import numpy as np
 
-    dt = np.dtype([("rmse", "<f8"), ("mean", "<f8"), ("max", "<f8"), ("rot", "<f8", 9), ("trans", "<f8", 3), ("n_pairs", "<u8"), ("worst", "<u4"), ("status", "<u4")])
+    dt = np.dtype(lk_ate)
     assert dt.itemsize == C.sizeof(lk_ate) == 136
     return dt
 
@@ -198,8 +244,7 @@ def blob_header_dtype():
     """numpy view of lk_blob_header (48 B)."""
     import numpy as np
 
-    dt = np.dtype([("magic", "<u4"), ("version", "<u4"), ("n_roots", "<u4"), ("n_nodes", "<u4"), ("n_blocks", "<u4"), ("block_pts", "<u4"),
-                   ("voxel_size", "<f8"), ("max_layer", "<i4"), ("max_points_num", "<i4"), ("bytes", "<u8")])
+    dt = np.dtype(lk_blob_header)
     assert dt.itemsize == C.sizeof(lk_blob_header)
     return dt
 

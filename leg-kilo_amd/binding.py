@@ -3,37 +3,20 @@
 There is no fallback: if the shared library is missing or no gfx950 device is visible the
 constructor raises.  Nothing here imports oracle/.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 
-from . import abi
+from . import abi, synth
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LEGKILO_HIP_LIB", os.path.join(_HERE, "liblegkilo_hip.so"))  # override: A/B builds
 
-EXPORTS = [
-    "lk_abi_version", "lk_create", "lk_destroy", "lk_last_error", "lk_set_state", "lk_get_state", "lk_set_Q", "lk_get_Q",
-    "lk_init_process_cov_q", "lk_set_times", "lk_get_times", "lk_set_acc_norm", "lk_get_acc_norm", "lk_get_fx", "lk_get_function_f",
-    "lk_predict", "lk_update_by_points", "lk_update_by_imu", "lk_update_by_kin_imu", "lk_map_build", "lk_map_update",
-    "lk_residuals", "lk_match_points", "lk_map_slide", "lk_map_clear_outside", "lk_map_slide_position", "lk_map_stats", "lk_map_export", "lk_map_import", "lk_map_export_dev", "lk_map_import_dev",
-    "lk_update_points", "lk_update_imu", "lk_update_kin_imu", "lk_process_scan", "lk_process_scan_dev",
-    "lk_decode_scan", "lk_decode_scan_dev", "lk_preprocess_scan", "lk_preprocess_scan_dev", "lk_process_raw_scan", "lk_batch_set_priors", "lk_batch_set_priors_dev", "lk_batch_get_states", "lk_batch_get_states_dev", "lk_batch_residuals_dev", "lk_batch_order", "lk_batch_changed", "lk_batch_prepare_dev", "lk_batch_order_stats", "lk_batch_replay_dev", "lk_batch_sort_by_voxel_dev", "lk_batch_replay_async_dev", "lk_batch_replay_ragged_dev", "lk_batch_replay_ragged_imu_dev", "lk_batch_replay_ragged_kin_dev", "lk_batch_replay_scans_dev", "lk_batch_replay_overlay_dev", "lk_batch_replay_overlay_ragged_dev", "lk_overlay_reserve", "lk_overlay_export", "lk_overlay_stats", "lk_overlay_pool_bytes", "lk_overlay_resident_rounds", "lk_profile_enable", "lk_profile_get", "lk_profile_reset",
-    "lk_device_malloc", "lk_device_free", "lk_memcpy_h2d", "lk_memcpy_d2h", "lk_synchronize", "lk_stream", "lk_stream_pipeline", "lk_stream_resident", "lk_stream_grid", "lk_stream_grid_placement", "lk_stream_stats", "lk_stream_resident_stats", "lk_test_stall",
-    "lk_kin_configure", "lk_kin_get_frontend", "lk_kin_set_frontend", "lk_decode_highstate", "lk_decode_highstate_dev", "lk_kin_split_dev",
-    "lk_batch_replay_scans_kin_dev", "lk_decode_scans_dev",
-    "lk_imu_configure", "lk_imu_get_frontend", "lk_imu_set_frontend", "lk_decode_imu", "lk_decode_imu_dev", "lk_imu_split_dev",
-    "lk_batch_replay_scans_imu_dev", "lk_first_frame", "lk_first_frame_dev", "lk_run_scans_dev", "lk_batch_replay_overlay_runs_dev",
-    "lk_batch_replay_runs_dev", "lk_overlay_commit",
-    "lk_batch_replay_runs_cloud_dev", "lk_batch_replay_overlay_runs_cloud_dev", "lk_runs_bucket_poses_dev", "lk_runs_bucket_poses",
-    "lk_downsample_clouds_dev", "lk_downsample_clouds", "lk_traj_ate_dev", "lk_runs_ate_dev",
-]
-
-
-class LegKiloError(RuntimeError):
-    pass
+EXPORTS = sorted(abi.signatures())   # every lk_* prototype of include/legkilo_hip.h
+LegKiloError = abi.LegKiloError
 
 
 def build(force=False):
@@ -62,15 +45,28 @@ def lib():
         if torch is not None and torch.cuda.is_available():
             torch.cuda.init()
         L = C.CDLL(LIB_PATH)
-        L.lk_last_error.restype = C.c_char_p
-        L.lk_last_error.argtypes = [C.c_void_p]
-        L.lk_stream.restype = C.c_void_p
+        for name, (restype, argtypes) in abi.signatures().items():   # the header's types: ctypes converts and checks every argument of every call
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _messages(imus, kins, n_scans):
+    """Per-scan message arrays, imus (lk_imu records) or kins (lk_kin_imu), one array per scan -> (msg_kind 0 / 1 (imus) / 2 (kins), n_msg
+    uint32 [n_scans] or None, all records contiguous or None when there is none)."""
+    assert imus is None or kins is None
+    msgs = imus if imus is not None else kins
+    if msgs is None:
+        return 0, None, None
+    assert len(msgs) == n_scans, "one message array per scan"
+    n_msg = np.fromiter((len(m) for m in msgs), dtype=np.uint32, count=n_scans)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in msgs if len(m)])) if n_msg.sum() else None
+    return (1 if imus is not None else 2), n_msg, flat
 
 
 LK_RUNS_CONTINUE = 1
@@ -87,15 +83,8 @@ def flatten_runs(runs, t_begins, imus=None, kins=None):
     scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])].astype(np.uint64)
     tb = np.array([t for run in t_begins for t in run], dtype=np.float64)
     assert len(tb) == len(scans), "one start time per scan"
-    msgs = imus if imus is not None else kins
-    kind, n_msg, flat = 0, None, None
-    if msgs is not None:
-        kind = 1 if imus is not None else 2
-        per_scan = [m for run in msgs for m in run]
-        assert len(per_scan) == len(scans), "one message array per scan"
-        n_msg = np.fromiter((len(m) for m in per_scan), dtype=np.uint32, count=len(scans))
-        if n_msg.sum():
-            flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in per_scan if len(m)]))
+    per_scan = lambda nested: None if nested is None else [m for run in nested for m in run]   # noqa: E731
+    kind, n_msg, flat = _messages(per_scan(imus), per_scan(kins), len(scans))
     return dict(run_off=run_off, scan_off=scan_off, t_begin=tb, pts=np.ascontiguousarray(np.concatenate(scans)), msg_kind=kind, n_msg=n_msg, msgs=flat)
 
 
@@ -150,15 +139,39 @@ class LegKiloHip:
         except Exception:
             pass
 
+    @contextlib.contextmanager
+    def _staged(self, *items):
+        """Device memory for the length of a `with` body: per item an uploaded copy of a numpy array, or that many bytes left unwritten (an
+        int), or nothing (None -> 0).  Yields the device pointers in the items' order and frees them on exit, also when the body raises."""
+        dptrs = []
+        try:
+            for it in items:
+                dptrs.append(0 if it is None else self.device_malloc(it.nbytes if isinstance(it, np.ndarray) else it))
+                if isinstance(it, np.ndarray):
+                    self.h2d(dptrs[-1], it)
+            yield dptrs
+        finally:
+            for d in dptrs:
+                if d:
+                    self.device_free(d)
+
+    def _export_blob(self, fn, *head):
+        """The two calls of a blob export fn(*head, blob, &bytes): the size query with blob == NULL, then the blob."""
+        nbytes = C.c_size_t(0)
+        self._chk(fn(*head, None, C.byref(nbytes)))
+        buf = np.zeros(nbytes.value, dtype=np.uint8)
+        self._chk(fn(*head, _p(buf), C.byref(nbytes)))
+        return buf
+
     # ---- ESKF surface ----
     def set_state(self, x36=None, P=None, slot=0):
         x36 = None if x36 is None else _f64(x36).reshape(36)
         P = None if P is None else _f64(P).reshape(900)
-        self._chk(self.L.lk_set_state(self.h, C.c_uint32(slot), _p(x36), _p(P)))
+        self._chk(self.L.lk_set_state(self.h, slot, _p(x36), _p(P)))
 
     def get_state(self, slot=0):
         x, P = np.zeros(36), np.zeros(900)
-        self._chk(self.L.lk_get_state(self.h, C.c_uint32(slot), _p(x), _p(P)))
+        self._chk(self.L.lk_get_state(self.h, slot, _p(x), _p(P)))
         return x, P.reshape(30, 30)
 
     def set_Q(self, Q):
@@ -174,15 +187,15 @@ class LegKiloHip:
         self._chk(self.L.lk_init_process_cov_q(self.h))
 
     def set_times(self, last_predict_t, last_update_t, slot=0):
-        self._chk(self.L.lk_set_times(self.h, C.c_uint32(slot), C.c_double(last_predict_t), C.c_double(last_update_t)))
+        self._chk(self.L.lk_set_times(self.h, slot, last_predict_t, last_update_t))
 
     def get_times(self, slot=0):
         a, b = C.c_double(), C.c_double()
-        self._chk(self.L.lk_get_times(self.h, C.c_uint32(slot), C.byref(a), C.byref(b)))
+        self._chk(self.L.lk_get_times(self.h, slot, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def set_acc_norm(self, a):
-        self._chk(self.L.lk_set_acc_norm(self.h, C.c_double(a)))
+        self._chk(self.L.lk_set_acc_norm(self.h, a))
 
     def get_acc_norm(self):
         a = C.c_double()
@@ -191,44 +204,44 @@ class LegKiloHip:
 
     def get_fx(self, dt, slot=0):
         F = np.zeros(900)
-        self._chk(self.L.lk_get_fx(self.h, C.c_uint32(slot), C.c_double(dt), _p(F)))
+        self._chk(self.L.lk_get_fx(self.h, slot, dt, _p(F)))
         return F.reshape(30, 30)
 
     def get_function_f(self, dt, slot=0):
         f = np.zeros(30)
-        self._chk(self.L.lk_get_function_f(self.h, C.c_uint32(slot), C.c_double(dt), _p(f)))
+        self._chk(self.L.lk_get_function_f(self.h, slot, dt, _p(f)))
         return f
 
     def predict(self, dt, prop_state, prop_cov, slot=0):
-        self._chk(self.L.lk_predict(self.h, C.c_uint32(slot), C.c_double(dt), int(prop_state), int(prop_cov)))
+        self._chk(self.L.lk_predict(self.h, slot, dt, int(prop_state), int(prop_cov)))
 
     def update_by_points(self, h6, z, R, slot=0):
         h6, z, R = _f64(h6), _f64(z), _f64(R)
-        self._chk(self.L.lk_update_by_points(self.h, C.c_uint32(slot), _p(h6), _p(z), _p(R), C.c_size_t(len(z))))
+        self._chk(self.L.lk_update_by_points(self.h, slot, _p(h6), _p(z), _p(R), len(z)))
 
     def update_by_imu(self, z6, R6, slot=0):
         z6, R6 = _f64(z6), _f64(R6)
-        self._chk(self.L.lk_update_by_imu(self.h, C.c_uint32(slot), _p(z6), _p(R6)))
+        self._chk(self.L.lk_update_by_imu(self.h, slot, _p(z6), _p(R6)))
 
     def update_by_kin_imu(self, ki_h, ki_z, ki_R, slot=0):
         ki_h, ki_z, ki_R = _f64(ki_h), _f64(ki_z), _f64(ki_R)
-        self._chk(self.L.lk_update_by_kin_imu(self.h, C.c_uint32(slot), _p(ki_h), _p(ki_z), _p(ki_R), C.c_size_t(len(ki_z))))
+        self._chk(self.L.lk_update_by_kin_imu(self.h, slot, _p(ki_h), _p(ki_z), _p(ki_R), len(ki_z)))
 
     # ---- VoxelMapManager surface ----
     def map_build(self, xyz_world, xyz_body):
         w = np.ascontiguousarray(xyz_world, dtype=np.float32)
         b = np.ascontiguousarray(xyz_body, dtype=np.float32)
-        self._chk(self.L.lk_map_build(self.h, _p(w), _p(b), C.c_size_t(len(w))))
+        self._chk(self.L.lk_map_build(self.h, _p(w), _p(b), len(w)))
 
     def map_update(self, pw, var9):
         pw, var9 = _f64(pw), _f64(var9)
-        self._chk(self.L.lk_map_update(self.h, _p(pw), _p(var9), C.c_size_t(len(pw))))
+        self._chk(self.L.lk_map_update(self.h, _p(pw), _p(var9), len(pw)))
 
     def residuals(self, xyz_body):
         b = np.ascontiguousarray(xyz_body, dtype=np.float32)
         n = len(b)
         h6, z, R, valid = np.zeros((n, 6)), np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint8)
-        self._chk(self.L.lk_residuals(self.h, _p(b), C.c_size_t(n), _p(h6), _p(z), _p(R), _p(valid)))
+        self._chk(self.L.lk_residuals(self.h, _p(b), n, _p(h6), _p(z), _p(R), _p(valid)))
         return h6, z, R, valid
 
     def match_points(self, keys, pw, var):
@@ -240,7 +253,7 @@ class LegKiloHip:
         found, ok = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
         prob, d, dis, layer = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
         normal, center = np.zeros((n, 3)), np.zeros((n, 3))
-        self._chk(self.L.lk_match_points(self.h, C.c_size_t(n), _p(keys), _p(pw), _p(var), _p(found), _p(ok), _p(prob), _p(normal), _p(center),
+        self._chk(self.L.lk_match_points(self.h, n, _p(keys), _p(pw), _p(var), _p(found), _p(ok), _p(prob), _p(normal), _p(center),
                                          _p(d), _p(dis), _p(layer)))
         return dict(found=found.astype(bool), success=ok.astype(bool), prob=prob, normal=normal, center=center, d=d, dis_to_plane=dis, layer=layer)
 
@@ -254,35 +267,29 @@ class LegKiloHip:
         """VoxelMapManager::mapSliding with position_last_ = position -> (slid, n_removed)."""
         pos = _f64(position)
         slid, nrem = C.c_int32(0), C.c_uint32(0)
-        self._chk(self.L.lk_map_slide(self.h, _p(pos), C.c_double(sliding_thresh), C.c_int32(int(half_map_size)),
-                                      C.byref(slid), C.byref(nrem)))
+        self._chk(self.L.lk_map_slide(self.h, _p(pos), sliding_thresh, int(half_map_size), C.byref(slid), C.byref(nrem)))
         return bool(slid.value), int(nrem.value)
 
     def map_clear_outside(self, x_max, x_min, y_max, y_min, z_max, z_min):
         nrem = C.c_uint32(0)
-        self._chk(self.L.lk_map_clear_outside(self.h, *(C.c_int32(int(v)) for v in (x_max, x_min, y_max, y_min, z_max, z_min)),
-                                              C.byref(nrem)))
+        self._chk(self.L.lk_map_clear_outside(self.h, *(int(v) for v in (x_max, x_min, y_max, y_min, z_max, z_min)), C.byref(nrem)))
         return int(nrem.value)
 
     def get_last_slide_position(self):
         out = np.zeros(3)
-        self._chk(self.L.lk_map_slide_position(self.h, C.c_int32(0), _p(out)))
+        self._chk(self.L.lk_map_slide_position(self.h, 0, _p(out)))
         return out
 
     def set_last_slide_position(self, p):
         p = _f64(p).copy()
-        self._chk(self.L.lk_map_slide_position(self.h, C.c_int32(1), _p(p)))
+        self._chk(self.L.lk_map_slide_position(self.h, 1, _p(p)))
 
     def map_export(self):
-        nbytes = C.c_size_t(0)
-        self._chk(self.L.lk_map_export(self.h, None, C.byref(nbytes)))
-        buf = np.zeros(nbytes.value, dtype=np.uint8)
-        self._chk(self.L.lk_map_export(self.h, _p(buf), C.byref(nbytes)))
-        return buf
+        return self._export_blob(self.L.lk_map_export, self.h)
 
     def map_import(self, blob):
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        self._chk(self.L.lk_map_import(self.h, _p(blob), C.c_size_t(blob.size)))
+        self._chk(self.L.lk_map_import(self.h, _p(blob), blob.size))
 
     def map_export_dev_size(self):
         nbytes = C.c_size_t(0)
@@ -291,11 +298,11 @@ class LegKiloHip:
 
     def map_export_dev(self, d_ptr, nbytes):
         nb = C.c_size_t(nbytes)
-        self._chk(self.L.lk_map_export_dev(self.h, C.c_void_p(d_ptr), C.byref(nb)))
+        self._chk(self.L.lk_map_export_dev(self.h, d_ptr, C.byref(nb)))
         return nb.value
 
     def map_import_dev(self, d_ptr, nbytes):
-        self._chk(self.L.lk_map_import_dev(self.h, C.c_void_p(d_ptr), C.c_size_t(nbytes)))
+        self._chk(self.L.lk_map_import_dev(self.h, d_ptr, nbytes))
 
     # ---- KILO path ----
     def update_points(self, t, xyz_body):
@@ -304,7 +311,7 @@ class LegKiloHip:
         w = np.zeros((n, 3), dtype=np.float32)
         inten = np.zeros(n, dtype=np.float32)
         ne = C.c_size_t(0)
-        self._chk(self.L.lk_update_points(self.h, C.c_double(t), _p(b), C.c_size_t(n), _p(w), _p(inten), C.byref(ne)))
+        self._chk(self.L.lk_update_points(self.h, t, _p(b), n, _p(w), _p(inten), C.byref(ne)))
         return w, inten, ne.value
 
     def update_imu(self, imu_rec):
@@ -323,16 +330,14 @@ class LegKiloHip:
         kins = None if kins is None else np.ascontiguousarray(kins)
         w = np.zeros((len(pts), 3), dtype=np.float32) if want_world else None
         pose = abi.lk_pose()
-        self._chk(self.L.lk_process_scan(self.h, _p(pts), C.c_size_t(len(pts)), C.c_double(t_begin), _p(imus), C.c_size_t(ni),
-                                         _p(kins), C.c_size_t(nk), _p(w), C.byref(pose)))
+        self._chk(self.L.lk_process_scan(self.h, _p(pts), len(pts), t_begin, _p(imus), ni, _p(kins), nk, _p(w), C.byref(pose)))
         return pose, w
 
     def process_scan_dev(self, d_pts, n, t_begin, bucket_off, bucket_dt):
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
         dt = _f64(bucket_dt)
         pose = abi.lk_pose()
-        self._chk(self.L.lk_process_scan_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n), C.c_double(t_begin), _p(off), _p(dt),
-                                             C.c_size_t(len(dt)), C.byref(pose)))
+        self._chk(self.L.lk_process_scan_dev(self.h, d_pts, n, t_begin, _p(off), _p(dt), len(dt), C.byref(pose)))
         return pose
 
     def run_scans_dev(self, d_pts, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, slide=None, d_world=0):
@@ -350,9 +355,8 @@ class LegKiloHip:
         opt = None if slide is None else abi.lk_run_options(float(slide[0]), int(slide[1]), 0)
         poses = (abi.lk_pose * max(n_scans, 1))()
         n_done, n_slides = C.c_size_t(0), C.c_uint32(0)
-        rc = self.L.lk_run_scans_dev(self.h, C.c_void_p(d_pts), C.c_size_t(max(n_scans, 0)), _p(so), _p(tb), C.c_int(msg_kind), _p(nm),
-                                     C.c_void_p(d_msgs) if d_msgs else None, C.byref(opt) if opt is not None else None,
-                                     C.c_void_p(d_world) if d_world else None, poses, C.byref(n_done), C.byref(n_slides))
+        rc = self.L.lk_run_scans_dev(self.h, d_pts, max(n_scans, 0), _p(so), _p(tb), msg_kind, _p(nm), d_msgs,
+                                     C.byref(opt) if opt is not None else None, d_world, poses, C.byref(n_done), C.byref(n_slides))
         try:
             self._chk(rc)
         except LegKiloError as e:
@@ -364,30 +368,10 @@ class LegKiloHip:
         """Convenience: host scans (lk_point arrays, time-sorted, any sizes) and per-scan message arrays (imus: IMU_DTYPE, or kins:
         KIN_DTYPE) -> HBM -> run_scans_dev.  Returns (poses, worlds, n_slides): worlds = per-scan n x 3 float32 cloud_down_world
         (world=True) or None."""
-        assert imus is None or kins is None
         allpts = np.ascontiguousarray(np.concatenate(scans))
         scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])].astype(np.uint64)
-        msgs = imus if imus is not None else kins
-        kind, n_msg, flat = 0, None, None
-        if msgs is not None:
-            kind = 1 if imus is not None else 2
-            n_msg = np.fromiter((len(m) for m in msgs), dtype=np.uint32, count=len(scans))
-            if n_msg.sum():
-                flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in msgs if len(m)]))
-        dptrs = []
-        try:
-            d_pts = self.device_malloc(allpts.nbytes)
-            dptrs.append(d_pts)
-            self.h2d(d_pts, allpts)
-            d_msgs = 0
-            if flat is not None:
-                d_msgs = self.device_malloc(flat.nbytes)
-                dptrs.append(d_msgs)
-                self.h2d(d_msgs, flat)
-            d_world = 0
-            if world:
-                d_world = self.device_malloc(16 * len(allpts))
-                dptrs.append(d_world)
+        kind, n_msg, flat = _messages(imus, kins, len(scans))
+        with self._staged(allpts, flat, 16 * len(allpts) if world else None) as (d_pts, d_msgs, d_world):
             poses, n_slides = self.run_scans_dev(d_pts, scan_off, t_begins, kind, n_msg, d_msgs, slide, d_world)
             worlds = None
             if world:
@@ -395,27 +379,24 @@ class LegKiloHip:
                 self.d2h(w, d_world)
                 worlds = [np.ascontiguousarray(w[int(a):int(b), :3]) for a, b in zip(scan_off[:-1], scan_off[1:])]
             return poses, worlds, n_slides
-        finally:
-            for d in dptrs:
-                self.device_free(d)
 
     # ---- sensor decode + preprocessing in front of the path ----
     def decode_scan(self, msg_bytes, n_points, layout, time_scale, filter_num, blind, header_stamp=0.0):
         """layout = dict(point_step, off_x, off_y, off_z, off_time, lidar_type)."""
         data = np.ascontiguousarray(np.frombuffer(msg_bytes, dtype=np.uint8))
         lay = abi.lk_cloud_layout(**layout)
-        out = np.zeros(n_points, dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("curvature", "<f4")]))
+        out = np.zeros(n_points, dtype=synth.POINT_DTYPE)
         n_out, tb, te = C.c_size_t(0), C.c_double(0), C.c_double(0)
-        self._chk(self.L.lk_decode_scan(self.h, _p(data), C.c_size_t(n_points), C.byref(lay), C.c_double(time_scale), int(filter_num),
-                                        C.c_float(blind), C.c_double(header_stamp), _p(out), C.byref(n_out), C.byref(tb), C.byref(te)))
+        self._chk(self.L.lk_decode_scan(self.h, _p(data), n_points, C.byref(lay), time_scale, int(filter_num),
+                                        blind, header_stamp, _p(out), C.byref(n_out), C.byref(tb), C.byref(te)))
         return out[: n_out.value], tb.value, te.value
 
     def decode_scan_dev(self, d_msg, n_points, layout, time_scale, filter_num, blind, header_stamp, d_out):
         """One message in HBM -> its decoded points at the device pointer d_out (room for n_points); returns (n_out, t_begin, t_end)."""
         lay = abi.lk_cloud_layout(**layout)
         n_out, tb, te = C.c_size_t(0), C.c_double(0), C.c_double(0)
-        self._chk(self.L.lk_decode_scan_dev(self.h, C.c_void_p(d_msg), C.c_size_t(n_points), C.byref(lay), C.c_double(time_scale), int(filter_num),
-                                            C.c_float(blind), C.c_double(header_stamp), C.c_void_p(d_out), C.byref(n_out), C.byref(tb), C.byref(te)))
+        self._chk(self.L.lk_decode_scan_dev(self.h, d_msg, n_points, C.byref(lay), time_scale, int(filter_num),
+                                            blind, header_stamp, d_out, C.byref(n_out), C.byref(tb), C.byref(te)))
         return n_out.value, tb.value, te.value
 
     def decode_scans_dev(self, d_msgs, msg_off, n_points, header_stamps, layout, time_scale, filter_num, blind, leaf, d_out):
@@ -430,21 +411,20 @@ class LegKiloHip:
         lay = abi.lk_cloud_layout(**layout)
         so = np.zeros(S + 1, dtype=np.uint64)
         tb, te = np.zeros(S), np.zeros(S)
-        self._chk(self.L.lk_decode_scans_dev(self.h, C.c_void_p(d_msgs), C.c_size_t(S), _p(mo), _p(npts), _p(hs), C.byref(lay), C.c_double(time_scale),
-                                             int(filter_num), C.c_float(blind), C.c_float(leaf), C.c_void_p(d_out), _p(so), _p(tb), _p(te)))
+        self._chk(self.L.lk_decode_scans_dev(self.h, d_msgs, S, _p(mo), _p(npts), _p(hs), C.byref(lay), time_scale,
+                                             int(filter_num), blind, leaf, d_out, _p(so), _p(tb), _p(te)))
         return so, tb, te
 
     def preprocess_scan(self, raw_pts, leaf):
         raw = np.ascontiguousarray(raw_pts)
         out = np.zeros(len(raw), dtype=raw.dtype)
         n_out = C.c_size_t(0)
-        self._chk(self.L.lk_preprocess_scan(self.h, _p(raw), C.c_size_t(len(raw)), C.c_float(leaf), _p(out), C.byref(n_out)))
+        self._chk(self.L.lk_preprocess_scan(self.h, _p(raw), len(raw), leaf, _p(out), C.byref(n_out)))
         return out[: n_out.value]
 
     def preprocess_scan_dev(self, d_raw, n_raw, leaf, d_out):
         n_out = C.c_size_t(0)
-        self._chk(self.L.lk_preprocess_scan_dev(self.h, C.c_void_p(d_raw), C.c_size_t(n_raw), C.c_float(leaf), C.c_void_p(d_out),
-                                                C.byref(n_out)))
+        self._chk(self.L.lk_preprocess_scan_dev(self.h, d_raw, n_raw, leaf, d_out, C.byref(n_out)))
         return n_out.value
 
     def process_raw_scan(self, raw_pts, leaf, t_begin, imus=None, kins=None):
@@ -455,8 +435,7 @@ class LegKiloHip:
         kins = None if kins is None else np.ascontiguousarray(kins)
         pose = abi.lk_pose()
         nd = C.c_size_t(0)
-        self._chk(self.L.lk_process_raw_scan(self.h, _p(raw), C.c_size_t(len(raw)), C.c_float(leaf), C.c_double(t_begin), _p(imus),
-                                             C.c_size_t(ni), _p(kins), C.c_size_t(nk), C.byref(nd), C.byref(pose)))
+        self._chk(self.L.lk_process_raw_scan(self.h, _p(raw), len(raw), leaf, t_begin, _p(imus), ni, _p(kins), nk, C.byref(nd), C.byref(pose)))
         return pose, nd.value
 
     # ---- batch replay ----
@@ -464,35 +443,34 @@ class LegKiloHip:
         x36 = _f64(x36).reshape(-1, 36)
         P900 = _f64(P900).reshape(-1, 900)
         assert len(x36) == len(P900)
-        self._chk(self.L.lk_batch_set_priors(self.h, _p(x36), _p(P900), C.c_size_t(len(x36))))
+        self._chk(self.L.lk_batch_set_priors(self.h, _p(x36), _p(P900), len(x36)))
 
     def batch_set_priors_dev(self, d_x36, d_P900, n_scans):
         """Priors already in HBM (device pointers to n_scans x 36 and n_scans x 900 doubles); asynchronous."""
-        self._chk(self.L.lk_batch_set_priors_dev(self.h, C.c_void_p(d_x36), C.c_void_p(d_P900), C.c_size_t(n_scans)))
+        self._chk(self.L.lk_batch_set_priors_dev(self.h, d_x36, d_P900, n_scans))
 
     def batch_get_states(self, first_slot, n, want_P=True):
         """State [n, 36] and covariance [n, 30, 30] of the filter slots first_slot .. first_slot + n (one gather kernel)."""
         x = np.zeros((n, 36))
         P = np.zeros((n, 900)) if want_P else None
-        self._chk(self.L.lk_batch_get_states(self.h, C.c_uint32(first_slot), C.c_size_t(n), _p(x), _p(P)))
+        self._chk(self.L.lk_batch_get_states(self.h, first_slot, n, _p(x), _p(P)))
         return x, (P.reshape(n, 30, 30) if want_P else None)
 
     def batch_get_states_dev(self, first_slot, n, d_x36, d_P900):
         """The same into device buffers (pointers or 0), asynchronous on the handle's stream."""
-        self._chk(self.L.lk_batch_get_states_dev(self.h, C.c_uint32(first_slot), C.c_size_t(n), C.c_void_p(d_x36 or None), C.c_void_p(d_P900 or None)))
+        self._chk(self.L.lk_batch_get_states_dev(self.h, first_slot, n, d_x36, d_P900))
 
     def batch_replay_dev(self, d_pts, n_scans, n_pts, t_begin, bucket_off, bucket_dt, want_poses=True):
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
         dt = _f64(bucket_dt)
         poses = (abi.lk_pose * n_scans)() if want_poses else None
-        self._chk(self.L.lk_batch_replay_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), C.c_size_t(n_pts),
-                                             C.c_double(t_begin), _p(off), _p(dt), C.c_size_t(len(dt)), poses))
+        self._chk(self.L.lk_batch_replay_dev(self.h, d_pts, n_scans, n_pts, t_begin, _p(off), _p(dt), len(dt), poses))
         return poses
 
     def batch_residuals_dev(self, d_pts, n_scans, n_pts, d_rows8, d_valid):
         """Config 2 for a device-resident batch (lk_batch_residuals_dev): residual rows of n_scans x n_pts points, scan s under the current state of
         slot s, written to the device buffers d_rows8 [n][8] float64 = (h0..h5, z, R) per point and d_valid (uint8).  Asynchronous on the handle's stream."""
-        self._chk(self.L.lk_batch_residuals_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), C.c_size_t(n_pts), C.c_void_p(d_rows8), C.c_void_p(d_valid)))
+        self._chk(self.L.lk_batch_residuals_dev(self.h, d_pts, n_scans, n_pts, d_rows8, d_valid))
 
     def batch_order(self, mode):
         """0: replay every device-resident batch as given; 1 (default): the frozen-map batch entries keep a voxel-ordered copy of a batch they see (lk_batch_order)."""
@@ -502,7 +480,7 @@ class LegKiloHip:
         """Make the voxel-ordered copy of a batch NOW (priors armed first) instead of at its third replay (lk_batch_prepare_dev); does nothing
         under batch_order(0), where no replay would read it."""
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
-        self._chk(self.L.lk_batch_prepare_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), C.c_size_t(n_pts), _p(off), C.c_size_t(len(off) - 1)))
+        self._chk(self.L.lk_batch_prepare_dev(self.h, d_pts, n_scans, n_pts, _p(off), len(off) - 1))
 
     def batch_changed(self):
         self._chk(self.L.lk_batch_changed(self.h))
@@ -517,8 +495,7 @@ class LegKiloHip:
         """Every bucket of every scan of a device-resident batch into root-voxel order under the slots' prior poses (lk_batch_sort_by_voxel_dev):
         d_out = the same scans, a residual wave's points a handful of voxels apart.  Priors first (batch_set_priors(_dev))."""
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
-        self._chk(self.L.lk_batch_sort_by_voxel_dev(self.h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_size_t(n_scans), C.c_size_t(n_pts), _p(off),
-                                                    C.c_size_t(len(off) - 1)))
+        self._chk(self.L.lk_batch_sort_by_voxel_dev(self.h, d_in, d_out, n_scans, n_pts, _p(off), len(off) - 1))
 
     def batch_replay_async_dev(self, d_pts, first_slot, n_scans, n_pts, t_begin, bucket_off, bucket_dt, d_x36=None, d_P900=None,
                                host_out_ptr=None):
@@ -527,18 +504,15 @@ class LegKiloHip:
         batch's stream gets there (synchronize() waits for everything)."""
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
         dt = _f64(bucket_dt)
-        self._chk(self.L.lk_batch_replay_async_dev(self.h, C.c_void_p(d_pts), C.c_uint32(first_slot), C.c_size_t(n_scans),
-                                                   C.c_size_t(n_pts), C.c_double(t_begin), _p(off), _p(dt), C.c_size_t(len(dt)),
-                                                   C.c_void_p(d_x36) if d_x36 else None, C.c_void_p(d_P900) if d_P900 else None,
-                                                   C.c_void_p(host_out_ptr) if host_out_ptr else None))
+        self._chk(self.L.lk_batch_replay_async_dev(self.h, d_pts, first_slot, n_scans, n_pts, t_begin, _p(off), _p(dt), len(dt), d_x36, d_P900,
+                                                   host_out_ptr))
 
     def batch_replay_overlay_dev(self, d_pts, n_scans, n_pts, t_begin, bucket_off, bucket_dt, want_poses=True):
         """Batch replay WITH the map insert: every scan on its own copy-on-write overlay of the handle's map (lk_batch_replay_overlay_dev)."""
         off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
         dt = _f64(bucket_dt)
         poses = (abi.lk_pose * n_scans)() if want_poses else None
-        self._chk(self.L.lk_batch_replay_overlay_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), C.c_size_t(n_pts),
-                                                     C.c_double(t_begin), _p(off), _p(dt), C.c_size_t(len(dt)), poses))
+        self._chk(self.L.lk_batch_replay_overlay_dev(self.h, d_pts, n_scans, n_pts, t_begin, _p(off), _p(dt), len(dt), poses))
         return poses
 
     def batch_replay_overlay(self, scans, t_begin, bucket_off, bucket_dt):
@@ -547,12 +521,8 @@ class LegKiloHip:
         allpts = np.ascontiguousarray(np.concatenate(scans))
         n_pts = len(scans[0])
         assert all(len(sc) == n_pts for sc in scans), "the overlay batch entry takes equally shaped scans (ragged: lk_batch_replay_overlay_ragged_dev)"
-        d = self.device_malloc(allpts.nbytes)
-        try:
-            self.h2d(d, allpts)
+        with self._staged(allpts) as (d,):
             return self.batch_replay_overlay_dev(d, len(scans), n_pts, t_begin, bucket_off, bucket_dt)
-        finally:
-            self.device_free(d)
 
     def batch_replay_overlay_ragged_dev(self, d_pts, tables, want_poses=True):
         """Ragged batch WITH the map insert on slots [0, n_scans): `tables` from ragged_tables() (with imus= or kins= for the messages between
@@ -560,36 +530,33 @@ class LegKiloHip:
         t = tables
         n_scans = t["n_scans"]
         poses = (abi.lk_pose * n_scans)() if want_poses else None
-        kind, n_msg, msgs = (2, t["n_kin"], t["kins"]) if "n_kin" in t else (1, t["n_imu"], t["imus"]) if "n_imu" in t else (0, None, None)
-        self._chk(self.L.lk_batch_replay_overlay_ragged_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(t["scan_off"]), _p(t["n_buckets"]),
-                                                            _p(t["bucket_off"]), _p(t["bucket_dt"]), _p(t["t_begin"]),
-                                                            _p(n_msg) if n_msg is not None else None, _p(msgs) if msgs is not None else None,
-                                                            C.c_int(kind), poses))
+        kind, n_msg, msgs = self._ragged_messages(t)
+        self._chk(self.L.lk_batch_replay_overlay_ragged_dev(self.h, d_pts, n_scans, _p(t["scan_off"]), _p(t["n_buckets"]), _p(t["bucket_off"]),
+                                                            _p(t["bucket_dt"]), _p(t["t_begin"]), _p(n_msg), _p(msgs), kind, poses))
         return poses
 
     def batch_replay_overlay_ragged(self, scans, t_begins, xs=None, Ps=None, imus=None, kins=None):
         """Convenience: host scans (lk_point arrays, time-sorted, any sizes) -> HBM, buckets = runs of equal curvature (KILO.cc:375-378),
         optional priors and per-scan messages, ragged replay WITH insert.  Returns the poses."""
-        from . import synth
-
         if xs is not None:
             self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
         allpts = np.ascontiguousarray(np.concatenate(scans))
         scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])]
         tabs = [synth.buckets_of(sc) for sc in scans]
         tables = self.ragged_tables(scan_off, [t[0] for t in tabs], [t[1] for t in tabs], t_begins, imus, kins)
-        d = self.device_malloc(allpts.nbytes)
-        try:
-            self.h2d(d, allpts)
+        with self._staged(allpts) as (d,):
             return self.batch_replay_overlay_ragged_dev(d, tables)
-        finally:
-            self.device_free(d)
 
     def batch_replay_overlay_runs_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, want_poses=True):
         """Whole recorded runs WITH the map insert, run r on slot r (lk_batch_replay_overlay_runs_dev): run r = the scans run_off[r] : run_off[r + 1],
         scan s = d_pts[scan_off[s] : scan_off[s + 1]] with n_msg[s] records of msg_kind (1: lk_imu, 2: lk_kin_imu) at d_msgs - all in HBM, the
         bucket tables are built there.  State, covariance, times and overlay of a slot survive its run's scan boundaries.  Returns one pose per
         SCAN (counters of that scan alone); batch_get_states / overlay_export(r) give a run's final state and overlay."""
+        return self._runs_call(self.L.lk_batch_replay_overlay_runs_dev, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, want_poses)
+
+    def _runs_call(self, fn, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, want_poses, flags=(), tail=()):
+        """What the four run exports share - the run tables (run_off uint32, scan_off uint64, t_begin float64, n_msg uint32 or None) and the pose
+        array: fn(handle, points, tables, messages, *flags, poses, *tail).  Returns the poses, one per scan, or None."""
         ro = np.ascontiguousarray(run_off, dtype=np.uint32)
         so = np.ascontiguousarray(scan_off, dtype=np.uint64)
         n_scans = len(so) - 1
@@ -598,28 +565,14 @@ class LegKiloHip:
         nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
         assert nm is None or len(nm) == n_scans
         poses = (abi.lk_pose * max(n_scans, 1))() if want_poses else None
-        self._chk(self.L.lk_batch_replay_overlay_runs_dev(self.h, C.c_void_p(d_pts), C.c_size_t(len(ro) - 1), _p(ro), _p(so), _p(tb), C.c_int(msg_kind),
-                                                          _p(nm), C.c_void_p(d_msgs) if d_msgs else None, poses))
+        self._chk(fn(self.h, d_pts, len(ro) - 1, _p(ro), _p(so), _p(tb), msg_kind, _p(nm), d_msgs, *flags, poses, *tail))
         return list(poses[:n_scans]) if want_poses else None
 
     def _runs_cloud_call(self, overlay, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, flags, want_poses, d_world, want_offsets):
         """The two _cloud entries' call: (poses or None, scan_bucket_off uint32 [n_scans + 1] or None)."""
-        ro = np.ascontiguousarray(run_off, dtype=np.uint32)
-        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
-        n_scans = len(so) - 1
-        tb = _f64(t_begins)
-        assert len(tb) == n_scans and len(ro) >= 1
-        nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
-        assert nm is None or len(nm) == n_scans
-        poses = (abi.lk_pose * max(n_scans, 1))() if want_poses else None
-        sbo = np.zeros(n_scans + 1, dtype=np.uint32) if want_offsets else None
-        head = (self.h, C.c_void_p(d_pts), C.c_size_t(len(ro) - 1), _p(ro), _p(so), _p(tb), C.c_int(msg_kind), _p(nm), C.c_void_p(d_msgs) if d_msgs else None)
-        tail = (poses, C.c_void_p(d_world) if d_world else None, _p(sbo))
-        if overlay:
-            self._chk(self.L.lk_batch_replay_overlay_runs_cloud_dev(*head, *tail))
-        else:
-            self._chk(self.L.lk_batch_replay_runs_cloud_dev(*head, C.c_uint32(flags), *tail))
-        return (list(poses[:n_scans]) if want_poses else None), sbo
+        sbo = np.zeros(len(scan_off), dtype=np.uint32) if want_offsets else None
+        fn, fl = (self.L.lk_batch_replay_overlay_runs_cloud_dev, ()) if overlay else (self.L.lk_batch_replay_runs_cloud_dev, (flags,))
+        return self._runs_call(fn, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, want_poses, fl, (d_world, _p(sbo))), sbo
 
     def batch_replay_runs_cloud_dev(self, d_pts, run_off, scan_off, t_begins, msg_kind=0, n_msg=None, d_msgs=0, cont=False, want_poses=True, flags=None,
                                     d_world=0, want_offsets=True):
@@ -638,12 +591,12 @@ class LegKiloHip:
 
     def runs_bucket_poses_dev(self, first_bucket, n, d_out):
         """Records first_bucket : first_bucket + n of the last _cloud run replay's bucket table -> device memory at d_out (lk_runs_bucket_poses_dev)."""
-        self._chk(self.L.lk_runs_bucket_poses_dev(self.h, C.c_uint64(first_bucket), C.c_size_t(n), C.c_void_p(d_out) if d_out else None))
+        self._chk(self.L.lk_runs_bucket_poses_dev(self.h, first_bucket, n, d_out))
 
     def runs_bucket_poses(self, first_bucket, n):
         """The same records as a numpy array of abi.bucket_pose_dtype() (lk_runs_bucket_poses)."""
         out = np.zeros(n, dtype=abi.bucket_pose_dtype())
-        self._chk(self.L.lk_runs_bucket_poses(self.h, C.c_uint64(first_bucket), C.c_size_t(n), _p(out)))
+        self._chk(self.L.lk_runs_bucket_poses(self.h, first_bucket, n, _p(out)))
         return out
 
     def traj_ate_dev(self, d_est_t, d_est_pos, est_stride, est_off, d_gt_t, d_gt_pos, gt_stride, gt_off, max_dt, align=False, flags=None, out=None):
@@ -657,9 +610,7 @@ class LegKiloHip:
         assert len(go) == len(eo)
         res = np.zeros(max(n, 1), dtype=abi.ate_dtype()) if out is None else out
         fl = (abi.LK_ATE_ALIGN if align else 0) if flags is None else int(flags)
-        ptr = lambda d: C.c_void_p(d) if d else None   # noqa: E731
-        self._chk(self.L.lk_traj_ate_dev(self.h, C.c_size_t(n), ptr(d_est_t), ptr(d_est_pos), C.c_size_t(est_stride), _p(eo), ptr(d_gt_t), ptr(d_gt_pos),
-                                         C.c_size_t(gt_stride), _p(go), C.c_double(max_dt), C.c_uint32(fl), _p(res)))
+        self._chk(self.L.lk_traj_ate_dev(self.h, n, d_est_t, d_est_pos, est_stride, _p(eo), d_gt_t, d_gt_pos, gt_stride, _p(go), max_dt, fl, _p(res)))
         return res[:n]
 
     def runs_ate_dev(self, run_bucket_off, d_gt_t, d_gt_pos, gt_stride, gt_off, max_dt, align=False, flags=None):
@@ -671,21 +622,15 @@ class LegKiloHip:
         assert len(go) == len(ro)
         res = np.zeros(max(n, 1), dtype=abi.ate_dtype())
         fl = (abi.LK_ATE_ALIGN if align else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_runs_ate_dev(self.h, C.c_size_t(n), _p(ro), C.c_void_p(d_gt_t) if d_gt_t else None, C.c_void_p(d_gt_pos) if d_gt_pos else None,
-                                         C.c_size_t(gt_stride), _p(go), C.c_double(max_dt), C.c_uint32(fl), _p(res)))
+        self._chk(self.L.lk_runs_ate_dev(self.h, n, _p(ro), d_gt_t, d_gt_pos, gt_stride, _p(go), max_dt, fl, _p(res)))
         return res[:n]
 
     def runs_ate(self, run_bucket_off, gt_t, gt_pos, gt_off, max_dt, align=False):
         """runs_ate_dev with the ground truth taken from the host: gt_t [m], gt_pos [m, 3] are uploaded as one packed [t x y z] table (stride 32) for
         the call.  What the windowed-mapping recipe chooses a slot with: replay, runs_ate, overlay_commit(argmin rmse)."""
         gt = np.ascontiguousarray(np.concatenate([_f64(gt_t).reshape(-1, 1), _f64(gt_pos).reshape(-1, 3)], axis=1))
-        d_gt = self.device_malloc(max(gt.nbytes, 32))
-        try:
-            if gt.nbytes:
-                self.h2d(d_gt, gt)
+        with self._staged(gt if gt.nbytes else 32) as (d_gt,):   # an empty table still gets a pointer the entry accepts
             return self.runs_ate_dev(run_bucket_off, d_gt, d_gt + 8, 32, gt_off, max_dt, align)
-        finally:
-            self.device_free(d_gt)
 
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
@@ -696,8 +641,7 @@ class LegKiloHip:
         n_files = max(len(fo) - 1, 0)
         out_off = np.zeros(n_files + 1, dtype=np.uint64)
         unf = np.zeros(max(n_files, 1), dtype=np.uint8)
-        self._chk(self.L.lk_downsample_clouds_dev(self.h, C.c_void_p(d_world) if d_world else None, C.c_size_t(n_files), _p(fo), C.c_float(leaf),
-                                                  C.c_void_p(d_out) if d_out else None, _p(out_off), _p(unf)))
+        self._chk(self.L.lk_downsample_clouds_dev(self.h, d_world, n_files, _p(fo), leaf, d_out, _p(out_off), _p(unf)))
         return out_off, unf[:n_files]
 
     def downsample_clouds(self, world, file_off, leaf, with_flags=False):
@@ -709,7 +653,7 @@ class LegKiloHip:
         out = np.zeros((int(fo[-1] - fo[0]), 4), dtype=np.float32)
         out_off = np.zeros(n_files + 1, dtype=np.uint64)
         unf = np.zeros(n_files, dtype=np.uint8)
-        self._chk(self.L.lk_downsample_clouds(self.h, _p(w), C.c_size_t(n_files), _p(fo), C.c_float(leaf), _p(out), _p(out_off), _p(unf)))
+        self._chk(self.L.lk_downsample_clouds(self.h, _p(w), n_files, _p(fo), leaf, _p(out), _p(out_off), _p(unf)))
         clouds = [out[int(a):int(b)].copy() for a, b in zip(out_off[:-1], out_off[1:])]
         return (clouds, unf) if with_flags else clouds
 
@@ -721,14 +665,11 @@ class LegKiloHip:
         if len(file_run) == 0:
             return res
         n = int(file_off[-1] - file_off[0])
-        d_out = self.device_malloc(16 * n)
-        try:
+        with self._staged(16 * n) as (d_out,):
             out_off, res["unfiltered"] = self.downsample_clouds_dev(d_world, file_off, leaf, d_out)
             out = np.zeros((int(out_off[-1]), 4), dtype=np.float32)
             if len(out):
                 self.d2h(out, d_out)
-        finally:
-            self.device_free(d_out)
         res["clouds"] = [out[int(a):int(b)].copy() for a, b in zip(out_off[:-1], out_off[1:])]
         return res
 
@@ -740,23 +681,11 @@ class LegKiloHip:
         if xs is not None:
             self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
         t = flatten_runs(runs, t_begins, imus, kins)
-        dptrs = []
-        try:
-            d_pts = self.device_malloc(t["pts"].nbytes)
-            dptrs.append(d_pts)
-            self.h2d(d_pts, t["pts"])
-            d_msgs = 0
-            if t["msgs"] is not None:
-                d_msgs = self.device_malloc(t["msgs"].nbytes)
-                dptrs.append(d_msgs)
-                self.h2d(d_msgs, t["msgs"])
+        world_bytes = 16 * len(t["pts"]) if cloud or map_clouds is not None else None
+        with self._staged(t["pts"], t["msgs"], world_bytes) as (d_pts, d_msgs, d_world):
             extra = None
             if cloud or bucket_poses or map_clouds is not None:
                 extra = {}
-                d_world = 0
-                if cloud or map_clouds is not None:
-                    d_world = self.device_malloc(16 * len(t["pts"]))
-                    dptrs.append(d_world)
                 poses, sbo = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, d_world=d_world, **kw)
                 if cloud:
                     extra["cloud"] = np.zeros((len(t["pts"]), 4), dtype=np.float32)
@@ -769,9 +698,6 @@ class LegKiloHip:
                 poses = entry(d_pts, t["run_off"], t["scan_off"], t["t_begin"], t["msg_kind"], t["n_msg"], d_msgs, **kw)
             by_run = [poses[int(a):int(b)] for a, b in zip(t["run_off"][:-1], t["run_off"][1:])]
             return by_run if extra is None else (by_run, extra)
-        finally:
-            for d in dptrs:
-                self.device_free(d)
 
     def batch_replay_overlay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cloud=False, bucket_poses=False, map_clouds=None):
         """Convenience: runs = a list of runs, each a list of host scans (lk_point arrays, time-sorted, any sizes); t_begins, imus / kins: the same
@@ -789,18 +715,8 @@ class LegKiloHip:
         the handle's map is unchanged.  State, covariance and both time stamps of a slot survive its run's scan boundaries.  cont: LK_RUNS_CONTINUE -
         the slots go on from what they hold (the caller has not used them since the previous call), so a run may be fed in chunks of scans.
         Returns one pose per SCAN (counters of that scan alone); batch_get_states gives the runs' final states."""
-        ro = np.ascontiguousarray(run_off, dtype=np.uint32)
-        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
-        n_scans = len(so) - 1
-        tb = _f64(t_begins)
-        assert len(tb) == n_scans and len(ro) >= 1
-        nm = None if n_msg is None else np.ascontiguousarray(n_msg, dtype=np.uint32)
-        assert nm is None or len(nm) == n_scans
-        poses = (abi.lk_pose * max(n_scans, 1))() if want_poses else None
         fl = (LK_RUNS_CONTINUE if cont else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_batch_replay_runs_dev(self.h, C.c_void_p(d_pts), C.c_size_t(len(ro) - 1), _p(ro), _p(so), _p(tb), C.c_int(msg_kind),
-                                                  _p(nm), C.c_void_p(d_msgs) if d_msgs else None, C.c_uint32(fl), poses))
-        return list(poses[:n_scans]) if want_poses else None
+        return self._runs_call(self.L.lk_batch_replay_runs_dev, d_pts, run_off, scan_off, t_begins, msg_kind, n_msg, d_msgs, want_poses, (fl,))
 
     def batch_replay_runs(self, runs, t_begins, xs=None, Ps=None, imus=None, kins=None, cont=False, cloud=False, bucket_poses=False, map_clouds=None):
         """Convenience: the nested host inputs of batch_replay_overlay_runs -> HBM -> batch_replay_runs_dev (frozen map).  Optional priors, one per
@@ -813,22 +729,18 @@ class LegKiloHip:
         return self._replay_runs_staged(self.batch_replay_runs_dev, runs, t_begins, xs, Ps, imus, kins, cont=cont)
 
     def overlay_reserve(self, roots_per_scan=0, nodes_per_scan=0, blocks_per_scan=0):
-        self._chk(self.L.lk_overlay_reserve(self.h, C.c_uint32(roots_per_scan), C.c_uint32(nodes_per_scan), C.c_uint32(blocks_per_scan)))
+        self._chk(self.L.lk_overlay_reserve(self.h, roots_per_scan, nodes_per_scan, blocks_per_scan))
 
     def overlay_export(self, slot):
         """Map blob of the voxels scan `slot` of the last overlay replay holds privately."""
-        nbytes = C.c_size_t(0)
-        self._chk(self.L.lk_overlay_export(self.h, C.c_uint32(slot), None, C.byref(nbytes)))
-        buf = np.zeros(nbytes.value, dtype=np.uint8)
-        self._chk(self.L.lk_overlay_export(self.h, C.c_uint32(slot), _p(buf), C.byref(nbytes)))
-        return buf
+        return self._export_blob(self.L.lk_overlay_export, self.h, slot)
 
     def overlay_commit(self, slot, adopt_filter=False, flags=None):
         """Slot `slot`'s overlay of the last replay with insert becomes part of the handle's map, on the device (lk_overlay_commit): the map
         KILO::process of that slot's scans would have left on a private copy.  The replay's overlays are stale afterwards.  adopt_filter: the slot's
         filter record (state, covariance, time stamps, counters) is also copied to slot 0.  flags: the raw flag word instead."""
         fl = (abi.LK_COMMIT_ADOPT_FILTER if adopt_filter else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_overlay_commit(self.h, C.c_uint32(slot), C.c_uint32(fl)))
+        self._chk(self.L.lk_overlay_commit(self.h, slot, fl))
 
     def overlay_stats(self):
         """(max roots, max nodes, max point blocks) any scan's overlay reached in the last overlay replay."""
@@ -873,22 +785,20 @@ class LegKiloHip:
             assert tab["kins"].nbytes == 264 * int(tab["n_kin"].sum())
         return tab
 
+    @staticmethod
+    def _ragged_messages(t):
+        """(msg_kind, n_msg, records) of a ragged_tables() dict: its kins (2), its imus (1), or (0, None, None)."""
+        return (2, t["n_kin"], t["kins"]) if "n_kin" in t else (1, t["n_imu"], t["imus"]) if "n_imu" in t else (0, None, None)
+
     def batch_replay_ragged_dev(self, d_pts, tables, want_poses=True):
         """Ragged batch on slots [0, n_scans): `tables` from ragged_tables()."""
         t = tables
         n_scans = t["n_scans"]
         poses = (abi.lk_pose * n_scans)() if want_poses else None
-        if "n_kin" in t:
-            self._chk(self.L.lk_batch_replay_ragged_kin_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(t["scan_off"]),
-                                                            _p(t["n_buckets"]), _p(t["bucket_off"]), _p(t["bucket_dt"]), _p(t["t_begin"]),
-                                                            _p(t["n_kin"]), _p(t["kins"]), poses))
-        elif "n_imu" in t:
-            self._chk(self.L.lk_batch_replay_ragged_imu_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(t["scan_off"]),
-                                                            _p(t["n_buckets"]), _p(t["bucket_off"]), _p(t["bucket_dt"]), _p(t["t_begin"]),
-                                                            _p(t["n_imu"]), _p(t["imus"]), poses))
-        else:
-            self._chk(self.L.lk_batch_replay_ragged_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(t["scan_off"]), _p(t["n_buckets"]),
-                                                        _p(t["bucket_off"]), _p(t["bucket_dt"]), _p(t["t_begin"]), poses))
+        kind, n_msg, msgs = self._ragged_messages(t)
+        fn = (self.L.lk_batch_replay_ragged_dev, self.L.lk_batch_replay_ragged_imu_dev, self.L.lk_batch_replay_ragged_kin_dev)[kind]
+        self._chk(fn(self.h, d_pts, n_scans, _p(t["scan_off"]), _p(t["n_buckets"]), _p(t["bucket_off"]), _p(t["bucket_dt"]), _p(t["t_begin"]),
+                     *((_p(n_msg), _p(msgs)) if kind else ()), poses))
         return poses
 
     def batch_replay_scans_dev(self, d_pts, scan_off, t_begins, imus=None, kins=None, want_poses=True):
@@ -897,16 +807,10 @@ class LegKiloHip:
         so = np.ascontiguousarray(scan_off, dtype=np.uint64)
         n_scans = len(so) - 1
         tb = _f64(t_begins)
-        assert len(tb) == n_scans and not (imus is not None and kins is not None)
-        kind, n_msg, flat = 0, None, None
-        msgs = imus if imus is not None else kins
-        if msgs is not None:
-            kind = 1 if imus is not None else 2
-            n_msg = np.fromiter((len(m) for m in msgs), dtype=np.uint32, count=n_scans)
-            flat = np.ascontiguousarray(np.concatenate([np.asarray(m) for m in msgs])) if n_msg.sum() else np.zeros(1, dtype=np.float64)
+        assert len(tb) == n_scans
+        kind, n_msg, flat = _messages(imus, kins, n_scans)   # flat None when no scan has a message: the entry asks for the array only if one has
         poses = (abi.lk_pose * n_scans)() if want_poses else None
-        self._chk(self.L.lk_batch_replay_scans_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(so), _p(tb), C.c_int(kind), _p(n_msg),
-                                                   _p(flat), poses))
+        self._chk(self.L.lk_batch_replay_scans_dev(self.h, d_pts, n_scans, _p(so), _p(tb), kind, _p(n_msg), _p(flat), poses))
         return poses
 
     def batch_replay_ragged(self, scans, t_begins, xs=None, Ps=None, imus=None, kins=None, host_tables=False):
@@ -914,21 +818,15 @@ class LegKiloHip:
         (KILO.cc:375-378), optional priors, ragged replay.  Returns the poses.  The bucket tables are built on the device
         (lk_batch_replay_scans_dev); host_tables=True builds them here and goes through lk_batch_replay_ragged(_imu/_kin)_dev
         (same results, bit for bit)."""
-        from . import synth
-
         if xs is not None:
             self.batch_set_priors(np.asarray(xs), np.asarray(Ps))
         allpts = np.ascontiguousarray(np.concatenate(scans))
         scan_off = np.r_[0, np.cumsum([len(sc) for sc in scans])]
-        d = self.device_malloc(allpts.nbytes)
-        try:
-            self.h2d(d, allpts)
+        with self._staged(allpts) as (d,):
             if not host_tables:
                 return self.batch_replay_scans_dev(d, scan_off, t_begins, imus=imus, kins=kins)
             tabs = [synth.buckets_of(sc) for sc in scans]
             return self.batch_replay_ragged_dev(d, self.ragged_tables(scan_off, [t[0] for t in tabs], [t[1] for t in tabs], t_begins, imus, kins))
-        finally:
-            self.device_free(d)
 
     # ---- leg kinematics front end (HighState -> lk_kin_imu, the kin branch of syncPackage) ----
     def kin_configure(self, params=None):
@@ -952,42 +850,46 @@ class LegKiloHip:
 
     def decode_highstate(self, msgs):
         """Serialized HighState messages (bytes / uint8 array, n x LK_HIGHSTATE_BYTES) -> KIN_DTYPE records of the kept ones."""
-        from . import synth
-
         data = np.ascontiguousarray(np.frombuffer(bytes(msgs) if not isinstance(msgs, np.ndarray) else msgs.tobytes(), dtype=np.uint8))
         assert data.size % abi.LK_HIGHSTATE_BYTES == 0
         n = data.size // abi.LK_HIGHSTATE_BYTES
         out = np.zeros(max(n, 1), dtype=synth.KIN_DTYPE)
         n_out = C.c_size_t(0)
-        self._chk(self.L.lk_decode_highstate(self.h, _p(data), C.c_size_t(n), _p(out), C.byref(n_out)))
+        self._chk(self.L.lk_decode_highstate(self.h, _p(data), n, _p(out), C.byref(n_out)))
         return out[: n_out.value]
 
     def decode_highstate_dev(self, d_msgs, n, d_out):
         """n messages in HBM -> records at the device pointer d_out (room for n); returns the number kept."""
         n_out = C.c_size_t(0)
-        self._chk(self.L.lk_decode_highstate_dev(self.h, C.c_void_p(d_msgs), C.c_size_t(n), C.c_void_p(d_out), C.byref(n_out)))
+        self._chk(self.L.lk_decode_highstate_dev(self.h, d_msgs, n, d_out, C.byref(n_out)))
         return n_out.value
 
     def kin_split_dev(self, d_kins, n_kins, scan_end):
         """syncPackage's kin branch over n_kins time-sorted records in HBM and the scans' end times -> (n_msg uint32[n_scans], n_packaged,
         n_consumed)."""
+        return self._split_dev(self.L.lk_kin_split_dev, d_kins, n_kins, scan_end)
+
+    def _split_dev(self, fn, d_msgs, n, scan_end):
+        """The body of kin_split_dev / imu_split_dev: fn = the export of the record kind at d_msgs."""
         ends = _f64(scan_end)
         n_msg = np.zeros(max(len(ends), 1), dtype=np.uint32)
         npk, ncs = C.c_size_t(0), C.c_size_t(0)
-        self._chk(self.L.lk_kin_split_dev(self.h, C.c_void_p(d_kins), C.c_size_t(n_kins), _p(ends), C.c_size_t(len(ends)), _p(n_msg), C.byref(npk),
-                                          C.byref(ncs)))
+        self._chk(fn(self.h, d_msgs, n, _p(ends), len(ends), _p(n_msg), C.byref(npk), C.byref(ncs)))
         return n_msg[: len(ends)], npk.value, ncs.value
 
     def batch_replay_scans_kin_dev(self, d_pts, scan_off, t_begins, n_msg, d_kins, want_poses=True):
         """lk_batch_replay_scans_dev in leg-fusion mode with the records already in HBM (d_kins: n_msg[s] records per scan, concatenated)."""
+        return self._replay_scans_msgs_dev(self.L.lk_batch_replay_scans_kin_dev, d_pts, scan_off, t_begins, n_msg, d_kins, want_poses)
+
+    def _replay_scans_msgs_dev(self, fn, d_pts, scan_off, t_begins, n_msg, d_msgs, want_poses):
+        """The body of batch_replay_scans_kin_dev / _imu_dev: fn = the export of the record kind at d_msgs."""
         so = np.ascontiguousarray(scan_off, dtype=np.uint64)
         n_scans = len(so) - 1
         tb = _f64(t_begins)
         nm = np.ascontiguousarray(n_msg, dtype=np.uint32)
         assert len(tb) == n_scans and len(nm) == n_scans
         poses = (abi.lk_pose * n_scans)() if want_poses else None
-        self._chk(self.L.lk_batch_replay_scans_kin_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(so), _p(tb), _p(nm),
-                                                       C.c_void_p(d_kins) if d_kins else None, poses))
+        self._chk(fn(self.h, d_pts, n_scans, _p(so), _p(tb), _p(nm), d_msgs, poses))
         return poses
 
     # ---- IMU front end (sensor_msgs/Imu -> lk_imu, the IMU branch of syncPackage) ----
@@ -995,7 +897,7 @@ class LegKiloHip:
         """Sets the yaml key `redundancy` (a bool, or a parameter dict holding it) and resets the carried state."""
         if isinstance(redundancy, dict):
             redundancy = redundancy.get("redundancy", True)
-        self._chk(self.L.lk_imu_configure(self.h, C.c_int(1 if redundancy else 0)))
+        self._chk(self.L.lk_imu_configure(self.h, 1 if redundancy else 0))
 
     def imu_get_frontend(self):
         """The carried state as a dict(last_acc_z, last_gyr_z, last_stamp)."""
@@ -1009,14 +911,12 @@ class LegKiloHip:
 
     def decode_imu(self, buf, msg_off):
         """Serialized sensor_msgs/Imu messages (uint8 array; message i = buf[msg_off[i]:msg_off[i + 1]]) -> IMU_DTYPE records of the kept ones."""
-        from . import synth
-
         data = np.ascontiguousarray(buf, dtype=np.uint8)
         mo = np.ascontiguousarray(msg_off, dtype=np.uint64)
         n = len(mo) - 1
         out = np.zeros(max(n, 1), dtype=synth.IMU_DTYPE)
         n_out = C.c_size_t(0)
-        self._chk(self.L.lk_decode_imu(self.h, _p(data), C.c_size_t(n), _p(mo), _p(out), C.byref(n_out)))
+        self._chk(self.L.lk_decode_imu(self.h, _p(data), n, _p(mo), _p(out), C.byref(n_out)))
         return out[: n_out.value]
 
     def decode_imu_dev(self, d_msgs, msg_off, d_out):
@@ -1024,30 +924,17 @@ class LegKiloHip:
         message); returns the number kept."""
         mo = np.ascontiguousarray(msg_off, dtype=np.uint64)
         n_out = C.c_size_t(0)
-        self._chk(self.L.lk_decode_imu_dev(self.h, C.c_void_p(d_msgs), C.c_size_t(len(mo) - 1), _p(mo), C.c_void_p(d_out), C.byref(n_out)))
+        self._chk(self.L.lk_decode_imu_dev(self.h, d_msgs, len(mo) - 1, _p(mo), d_out, C.byref(n_out)))
         return n_out.value
 
     def imu_split_dev(self, d_imus, n_imus, scan_end):
         """syncPackage's IMU branch over n_imus time-sorted lk_imu records in HBM and the scans' end times -> (n_msg uint32[n_scans],
         n_packaged, n_consumed)."""
-        ends = _f64(scan_end)
-        n_msg = np.zeros(max(len(ends), 1), dtype=np.uint32)
-        npk, ncs = C.c_size_t(0), C.c_size_t(0)
-        self._chk(self.L.lk_imu_split_dev(self.h, C.c_void_p(d_imus), C.c_size_t(n_imus), _p(ends), C.c_size_t(len(ends)), _p(n_msg), C.byref(npk),
-                                          C.byref(ncs)))
-        return n_msg[: len(ends)], npk.value, ncs.value
+        return self._split_dev(self.L.lk_imu_split_dev, d_imus, n_imus, scan_end)
 
     def batch_replay_scans_imu_dev(self, d_pts, scan_off, t_begins, n_msg, d_imus, want_poses=True):
         """lk_batch_replay_scans_dev in IMU-only mode with the records already in HBM (d_imus: n_msg[s] records per scan, concatenated)."""
-        so = np.ascontiguousarray(scan_off, dtype=np.uint64)
-        n_scans = len(so) - 1
-        tb = _f64(t_begins)
-        nm = np.ascontiguousarray(n_msg, dtype=np.uint32)
-        assert len(tb) == n_scans and len(nm) == n_scans
-        poses = (abi.lk_pose * n_scans)() if want_poses else None
-        self._chk(self.L.lk_batch_replay_scans_imu_dev(self.h, C.c_void_p(d_pts), C.c_size_t(n_scans), _p(so), _p(tb), _p(nm),
-                                                       C.c_void_p(d_imus) if d_imus else None, poses))
-        return poses
+        return self._replay_scans_msgs_dev(self.L.lk_batch_replay_scans_imu_dev, d_pts, scan_off, t_begins, n_msg, d_imus, want_poses)
 
     # ---- first frame (KILO.cc:332-352) ----
     def first_frame(self, raw_pts, end_time, imus=None, kins=None):
@@ -1056,13 +943,11 @@ class LegKiloHip:
         assert (imus is None) != (kins is None)
         raw = np.ascontiguousarray(raw_pts)
         msgs = np.ascontiguousarray(imus if kins is None else kins)
-        self._chk(self.L.lk_first_frame(self.h, _p(raw), C.c_size_t(len(raw)), C.c_double(end_time), C.c_int(1 if kins is None else 2), _p(msgs),
-                                        C.c_size_t(len(msgs))))
+        self._chk(self.L.lk_first_frame(self.h, _p(raw), len(raw), end_time, 1 if kins is None else 2, _p(msgs), len(msgs)))
 
     def first_frame_dev(self, d_raw, n, end_time, msg_kind, d_msgs, n_msg):
         """The same with the raw cloud (n lk_point) and the n_msg records (msg_kind 1: lk_imu, 2: lk_kin_imu) already in HBM."""
-        self._chk(self.L.lk_first_frame_dev(self.h, C.c_void_p(d_raw), C.c_size_t(n), C.c_double(end_time), C.c_int(msg_kind), C.c_void_p(d_msgs),
-                                            C.c_size_t(n_msg)))
+        self._chk(self.L.lk_first_frame_dev(self.h, d_raw, n, end_time, msg_kind, d_msgs, n_msg))
 
     # ---- measurement / memory hooks ----
     def profile_enable(self, on):
@@ -1078,19 +963,19 @@ class LegKiloHip:
 
     def device_malloc(self, nbytes):
         p = C.c_void_p()
-        self._chk(self.L.lk_device_malloc(self.h, C.byref(p), C.c_size_t(nbytes)))
+        self._chk(self.L.lk_device_malloc(self.h, C.byref(p), nbytes))
         return p.value
 
     def device_free(self, ptr):
-        self._chk(self.L.lk_device_free(self.h, C.c_void_p(ptr)))
+        self._chk(self.L.lk_device_free(self.h, ptr))
 
     def h2d(self, d_ptr, arr):
         arr = np.ascontiguousarray(arr)
-        self._chk(self.L.lk_memcpy_h2d(self.h, C.c_void_p(d_ptr), _p(arr), C.c_size_t(arr.nbytes)))
+        self._chk(self.L.lk_memcpy_h2d(self.h, d_ptr, _p(arr), arr.nbytes))
 
     def d2h(self, arr, d_ptr):
         assert arr.flags["C_CONTIGUOUS"]
-        self._chk(self.L.lk_memcpy_d2h(self.h, _p(arr), C.c_void_p(d_ptr), C.c_size_t(arr.nbytes)))
+        self._chk(self.L.lk_memcpy_d2h(self.h, _p(arr), d_ptr, arr.nbytes))
 
     def synchronize(self):
         self._chk(self.L.lk_synchronize(self.h))
@@ -1100,15 +985,15 @@ class LegKiloHip:
 
     def stream_pipeline(self, on):
         """Pipelined stream path on / off (lk_stream_pipeline)."""
-        self._chk(self.L.lk_stream_pipeline(self.h, C.c_int(1 if on else 0)))
+        self._chk(self.L.lk_stream_pipeline(self.h, 1 if on else 0))
 
     def stream_resident(self, on):
         """Scan-resident stream kernel on / off (lk_stream_resident)."""
-        self._chk(self.L.lk_stream_resident(self.h, C.c_int(1 if on else 0)))
+        self._chk(self.L.lk_stream_resident(self.h, 1 if on else 0))
 
     def stream_grid(self, mode):
         """Grid-resident stream kernel for scans of large buckets (lk_stream_grid): 0 / False never, 1 / True buckets up to 4096 points, 2 any size."""
-        self._chk(self.L.lk_stream_grid(self.h, C.c_int(int(mode))))
+        self._chk(self.L.lk_stream_grid(self.h, int(mode)))
 
     def stream_grid_placement(self):
         """Bit mask of the XCC ids the working blocks of the last one-XCD grid-resident launch ran on (lk_stream_grid_placement)."""
@@ -1118,7 +1003,7 @@ class LegKiloHip:
 
     def test_stall(self, bound_ms):
         """Fault injection for the LK_ERR_TIMEOUT path of the resident stream kernels (include/legkilo_hip.h: lk_test_stall); 0 = off."""
-        self._chk(self.L.lk_test_stall(self.h, C.c_uint(int(bound_ms))))
+        self._chk(self.L.lk_test_stall(self.h, int(bound_ms)))
 
     def stream_resident_stats(self):
         """(scans through the scan-resident kernel, launches beyond one per scan: its fallback rounds)."""

@@ -552,6 +552,55 @@ int lk_traj_ate_dev(lk_handle* h, size_t n_traj,
 int lk_runs_ate_dev(lk_handle* h, size_t n_runs, const uint64_t* run_bucket_off,
                     const double* d_gt_t, const double* d_gt_pos, size_t gt_stride, const uint64_t* gt_off,
                     double max_dt, uint32_t flags, lk_ate* out);
+/* Relative pose error of n_traj trajectories against ground truth, in HBM: drift per step, in translation AND rotation - the second metric beside the
+ * ATE, and the one that reads the rotations.  leg-kilo_amd/tum.py's rpe per trajectory, one small record each for the host.
+ * Layout: lk_traj_ate_dev's with a third pointer per side.  d_*_rot points at the first sample's nine row-major doubles, body -> world; one stride
+ * serves all three pointers of a side (a multiple of 8, >= 72).  A packed [t x y z r00 .. r22] table has stride 104; an lk_bucket_pose table has
+ * stride 144 with &rec[0].t, &rec[0].pos[0], &rec[0].rot[0].  Offsets tables, their rules, out (HOST, n_traj records, every byte written) and
+ * synchronous completion as for lk_traj_ate_dev; no filter slot, no map and no bucket table is touched, the inputs are not modified.
+ * Partner: estimate sample i has the ground-truth partner j(i) exactly as in lk_traj_ate_dev - the minimiser of fabs(t_est[i] - t_gt[j]), the
+ * earliest on equal distance, kept when that one rounded subtraction is <= max_dt.  n_pairs counts the samples that have one.
+ * Step: in seconds mode target = t_est[i] + delta (one rounded addition) and k(i) is the first index in (i, n_est) with t_est[k] >= target: the search
+ * starts behind i, so with duplicate stamps, or a delta the addition swallows, k is still a later sample - never i itself or an earlier equal stamp.
+ * With LK_RPE_INDEX k(i) = i + (uint64)delta.  No such k below n_est: sample i gives no term.  There is NO bound on how far t_est[k] lies behind
+ * target: on a gappy estimate a step is longer than asked.
+ * Term: sample i gives one when i and k(i) both have partners, a = j(i) and b = j(k).  a == b is allowed: against a ground truth sparser than delta
+ * the term scores the estimate's own motion.  With (R, p) the estimate and (Q, g) the ground truth:
+ *     dRe = R_i^T R_k,  dpe = R_i^T (p_k - p_i),  dRg = Q_a^T Q_b,  dpg = Q_a^T (g_b - g_a),
+ *     e_t = |dpe - dpg|,
+ *     E = dRg^T dRe,  s = 0.5 |(E21 - E12, E02 - E20, E10 - E01)|,  c = 0.5 (E00 + E11 + E22 - 1),  e_r = atan2(s, c).
+ * The matrices are used as given, without re-orthonormalisation: the figure is this formula on those bits (atan2, not acos: at 1e-9 rad acos gives 0
+ * or 1.5e-8).  Both motions are in the first pose's own frame, so one fixed rigid transform of a whole trajectory does not change its figures; an
+ * estimate equal to its ground truth scores exactly 0.0 in all six.
+ * Figures: RMSE, mean and max of e_t (metres) and of e_r (radians) over the terms; worst_* = the i of the largest term, the first on ties.
+ * n_terms == 0: NaN figures, worst_* = 0, status 0.  A sum is taken in an order that depends on the trajectory's own samples only: a trajectory's
+ * record has the same bits whatever else the call holds.
+ * LK_ERR_INVALID before anything is launched: lk_traj_ate_dev's cases, a null or misaligned rot pointer, a stride below 72 (the message names the
+ * side), delta not finite or <= 0, with LK_RPE_INDEX a delta that is no whole number in 1 .. 2^32 - 2, unknown flag bits.
+ * LK_ERR_INVALID found on the device: stamps that decrease or are not finite, as for lk_traj_ate_dev.  A non-finite POSE is not an error of the call:
+ * a trajectory with a non-finite value in any of the four positions or rotations of a TERM gets status LK_RPE_NONFINITE, NaN figures, worst_* = 0 and
+ * its n_pairs / n_terms; the other trajectories are unaffected, and poses of samples that take part in no term are never read. */
+typedef struct lk_rpe {              /* 80 bytes */
+    double   trans_rmse, trans_mean, trans_max;   /* metres; NaN when n_terms == 0 or LK_RPE_NONFINITE */
+    double   rot_rmse,   rot_mean,   rot_max;     /* radians */
+    uint64_t n_terms;                /* steps that were scored */
+    uint64_t n_pairs;                /* estimate samples that found a ground-truth partner (lk_ate's n_pairs) */
+    uint32_t worst_trans, worst_rot; /* index i, within the trajectory's estimate, of the first sample of the worst step (first on ties) */
+    uint32_t status;                 /* 0, or LK_RPE_NONFINITE: a pose of a term was not finite */
+    uint32_t reserved;               /* written 0 */
+} lk_rpe;
+#define LK_RPE_INDEX     1u   /* delta counts estimate samples instead of seconds */
+#define LK_RPE_NONFINITE 1u
+int lk_traj_rpe_dev(lk_handle* h, size_t n_traj,
+                    const double* d_est_t, const double* d_est_pos, const double* d_est_rot, size_t est_stride, const uint64_t* est_off,
+                    const double* d_gt_t,  const double* d_gt_pos,  const double* d_gt_rot,  size_t gt_stride,  const uint64_t* gt_off,
+                    double max_dt, double delta, uint32_t flags, lk_rpe* out);
+/* The same with the estimate read where it lies: t, pos and rot of the bucket table of the handle's last _cloud run replay, run r = the records
+ * run_bucket_off[r] .. run_bucket_off[r+1]) as for lk_runs_ate_dev.  LK_ERR_STATE when the last batch replay recorded nothing, LK_ERR_INVALID for a
+ * range past the table's records; otherwise as lk_traj_rpe_dev.  The table, the slots and the overlays are left as they are. */
+int lk_runs_rpe_dev(lk_handle* h, size_t n_runs, const uint64_t* run_bucket_off,
+                    const double* d_gt_t, const double* d_gt_pos, const double* d_gt_rot, size_t gt_stride, const uint64_t* gt_off,
+                    double max_dt, double delta, uint32_t flags, lk_rpe* out);
 /* Downsampled map clouds from registered points, many files per call: PcdSaver::downsampleAndSave (common/pcd_saver.hpp:114-121) up to and excluding
  * savePCDFileBinaryCompressed - pcl::VoxelGrid<PointXYZINormal> at `leaf` over each file's buffer of frames.
  * File f = the 16-byte x y z intensity records file_off[f] .. file_off[f+1) of d_world (DEVICE, 16-byte aligned, the layout of d_world_out; consecutive

@@ -216,6 +216,36 @@ def ate_dtype():
     return dt
 
 
+class lk_rpe(C.Structure):
+    _fields_ = [
+        ("trans_rmse", C.c_double),
+        ("trans_mean", C.c_double),
+        ("trans_max", C.c_double),
+        ("rot_rmse", C.c_double),
+        ("rot_mean", C.c_double),
+        ("rot_max", C.c_double),
+        ("n_terms", C.c_uint64),
+        ("n_pairs", C.c_uint64),
+        ("worst_trans", C.c_uint32),
+        ("worst_rot", C.c_uint32),
+        ("status", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+LK_RPE_INDEX = 1       # lk_traj_rpe_dev / lk_runs_rpe_dev flag: delta counts estimate samples instead of seconds
+LK_RPE_NONFINITE = 1   # lk_rpe.status: a pose of a term was not finite
+
+
+def rpe_dtype():
+    """numpy view of lk_rpe (80 B): the records of lk_traj_rpe_dev / lk_runs_rpe_dev."""
+    import numpy as np
+
+    dt = np.dtype(lk_rpe)
+    assert dt.itemsize == C.sizeof(lk_rpe) == 80
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

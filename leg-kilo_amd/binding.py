@@ -632,6 +632,34 @@ class LegKiloHip:
         with self._staged(gt if gt.nbytes else 32) as (d_gt,):   # an empty table still gets a pointer the entry accepts
             return self.runs_ate_dev(run_bucket_off, d_gt, d_gt + 8, 32, gt_off, max_dt, align)
 
+    def traj_rpe_dev(self, d_est_t, d_est_pos, d_est_rot, est_stride, est_off, d_gt_t, d_gt_pos, d_gt_rot, gt_stride, gt_off, max_dt, delta, by_index=False,
+                     flags=None, out=None):
+        """Relative pose error of len(est_off) - 1 trajectories against ground truth, all in device memory (lk_traj_rpe_dev): traj_ate_dev's tables
+        with a third pointer per side, d_*_rot - the first sample's nine row-major doubles, body to world.  A step reaches from sample i to the
+        first later sample at least `delta` seconds on (by_index: `delta` samples on); it is scored when both ends pair within max_dt.  Returns
+        abi.rpe_dtype() records, one per trajectory (out: an array of that dtype to write into instead)."""
+        eo = np.ascontiguousarray(est_off, dtype=np.uint64)
+        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
+        n = max(len(eo) - 1, 0)
+        assert len(go) == len(eo)
+        res = np.zeros(max(n, 1), dtype=abi.rpe_dtype()) if out is None else out
+        fl = (abi.LK_RPE_INDEX if by_index else 0) if flags is None else int(flags)
+        self._chk(self.L.lk_traj_rpe_dev(self.h, n, d_est_t, d_est_pos, d_est_rot, est_stride, _p(eo), d_gt_t, d_gt_pos, d_gt_rot, gt_stride, _p(go), max_dt,
+                                         delta, fl, _p(res)))
+        return res[:n]
+
+    def runs_rpe_dev(self, run_bucket_off, d_gt_t, d_gt_pos, d_gt_rot, gt_stride, gt_off, max_dt, delta, by_index=False, flags=None):
+        """The same with the estimate read from the bucket table of the last _cloud run replay (lk_runs_rpe_dev): run r = the records
+        run_bucket_off[r] : run_bucket_off[r + 1] (scan_bucket_off[run_off]); the ground truth in device memory."""
+        ro = np.ascontiguousarray(run_bucket_off, dtype=np.uint64)
+        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
+        n = max(len(ro) - 1, 0)
+        assert len(go) == len(ro)
+        res = np.zeros(max(n, 1), dtype=abi.rpe_dtype())
+        fl = (abi.LK_RPE_INDEX if by_index else 0) if flags is None else int(flags)
+        self._chk(self.L.lk_runs_rpe_dev(self.h, n, _p(ro), d_gt_t, d_gt_pos, d_gt_rot, gt_stride, _p(go), max_dt, delta, fl, _p(res)))
+        return res[:n]
+
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
         file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at

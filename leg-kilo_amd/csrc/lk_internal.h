@@ -182,7 +182,7 @@ struct lk_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::map<std::string, ProfEntry> prof;
     std::string err;
-    DevBuf traj;                  // lk_traj_ate_dev / lk_runs_ate_dev (lk_traj.hip): offset tables, partner words, the records, the refusal word
+    DevBuf traj;                  // lk_traj_ate_dev / lk_runs_ate_dev and the _rpe_ pair (lk_traj.hip): offset tables, partner words, the records, the refusal word
 };
 
 extern thread_local std::string g_err;   // defined in legkilo_hip.hip (lk_last_error(NULL) reads it)

@@ -1,5 +1,6 @@
 // lk_traj_kernels.h - absolute trajectory error of many trajectories against ground truth, on the device (lk_traj_ate_dev, lk_runs_ate_dev):
-// tum.associate + tum.ate of leg-kilo_amd/tum.py without the trip of the trajectories to the host.  Compiled in lk_traj.hip only.
+// tum.associate + tum.ate of leg-kilo_amd/tum.py without the trip of the trajectories to the host - and, further down, their relative pose error
+// (lk_traj_rpe_dev, lk_runs_rpe_dev: tum.rpe).  Compiled in lk_traj.hip only.
 //
 // One workgroup of one wave per trajectory; lane l owns the estimate samples l, l + 64, l + 128, ... in every pass, so a sum is the lanes' partial
 // sums (each in ascending sample order) added by wave_sum / wave_sum_n: an order that depends on the trajectory's own samples alone - not on n_traj,
@@ -15,6 +16,7 @@
 // Without LK_ATE_ALIGN only pair and residual run, with e_i = |g_i - p_i| on the values as they lie.
 #pragma once
 #include "lk_horn.h"
+#include "lk_relpose.h"
 
 #define LK_TRAJ_NONE 0xffffffffu   // partner word of an estimate sample without a pair
 
@@ -215,4 +217,145 @@ __global__ void __launch_bounds__(LK_WAVE) lk_traj_ate_kernel(LkTraj a) {
     for (int o = 32; o > 0; o >>= 1) wmax = fmax(wmax, __shfl_xor(wmax, o, LK_WAVE));
     const unsigned long long worst = traj_wave_min_u64(emax == wmax ? imax : ~0ull);
     if (lane == 0) traj_write(&a.out[r], sqrt(s2 * inv_n), s1 * inv_n, wmax, R, tr, n_pairs, (unsigned int)worst, 0);
+}
+
+// ---- relative pose error (lk_traj_rpe_dev, lk_runs_rpe_dev): the same launch shape, lane ownership and helpers; the per-term arithmetic is lk_relpose.h.
+// The passes of one launch:
+//   stamps     as above;
+//   pair       partner words to scratch, n_pairs counted (no pose is read here: a sample's pose is touched only by a term it takes part in);
+//   -- __syncthreads(): the term pass reads the partner word of sample k(i), which ANOTHER lane wrote.  One wave is the whole workgroup, so the
+//      workgroup barrier with its workgroup-scope fence orders that store before the load (both lanes sit on one CU and share its L1: no agent scope)
+//   terms      k(i): in seconds mode the first sample behind i with t_est[k] >= t_est[i] + delta (traj_lower_bound over the samples behind i - never i
+//              itself or an earlier equal stamp), in index mode i + step; a term when i and k both have partners.  The estimate's two poses are
+//              loaded and reduced to their motion (12 doubles) before the ground truth's two are loaded: at most two poses are live beside a motion;
+//   combine    wave_sum of the lanes' sums (each in ascending i), the maxima by shuffles, the worst index by traj_wave_min_u64 over the lanes that hold
+//              the maximum - the ATE kernel's idiom, once per figure.
+struct LkTrajRpe {
+    const unsigned char *est_t, *est_p, *est_r, *gt_t, *gt_p, *gt_r;   // first sample's stamp / position / rotation of either side
+    unsigned long long est_stride, gt_stride;
+    const unsigned long long *est_off, *gt_off;
+    unsigned long long part_base;
+    unsigned int* partner;
+    lk_rpe* out;
+    unsigned int* bad;
+    double max_dt, delta;
+    unsigned long long step;   // LK_RPE_INDEX: (uint64)delta
+    unsigned int flags;
+};
+
+__device__ __forceinline__ void traj_rpe_write(lk_rpe* o, const double* fig, unsigned long long n_terms, unsigned long long n_pairs, unsigned int worst_t,
+                                               unsigned int worst_r, unsigned int status) {
+    o->trans_rmse = fig[0], o->trans_mean = fig[1], o->trans_max = fig[2];
+    o->rot_rmse = fig[3], o->rot_mean = fig[4], o->rot_max = fig[5];
+    o->n_terms = n_terms, o->n_pairs = n_pairs;
+    o->worst_trans = worst_t, o->worst_rot = worst_r, o->status = status, o->reserved = 0;
+}
+
+// one pose: 3 position and 9 rotation doubles; false when one of them is not finite
+__device__ __forceinline__ bool traj_ld_pose(const unsigned char* p, const unsigned char* r, unsigned long long stride, unsigned long long k, double* pos, double* rot) {
+    bool fin = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pos[c] = traj_ld(p, stride, k, c), fin = fin && traj_finite(pos[c]);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) rot[c] = traj_ld(r, stride, k, c), fin = fin && traj_finite(rot[c]);
+    return fin;
+}
+
+__device__ __forceinline__ double traj_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, LK_WAVE));
+    return v;
+}
+
+__global__ void __launch_bounds__(LK_WAVE) lk_traj_rpe_kernel(LkTrajRpe a) {
+    const unsigned int r = blockIdx.x;
+    const int lane = threadIdx.x;
+    const unsigned long long e0 = a.est_off[r], ne = a.est_off[r + 1] - e0, g0 = a.gt_off[r], ng = a.gt_off[r + 1] - g0;
+    const unsigned long long se = a.est_stride, sg = a.gt_stride;
+    const unsigned char *et = a.est_t + e0 * se, *ep = a.est_p + e0 * se, *er = a.est_r + e0 * se;
+    const unsigned char *gt = a.gt_t + g0 * sg, *gp = a.gt_p + g0 * sg, *gr = a.gt_r + g0 * sg;
+    unsigned int* part = a.partner + (e0 - a.part_base);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double fig[6] = {nan, nan, nan, nan, nan, nan};
+
+    // ---- stamps
+    const bool ok_e = traj_stamps_ok(et, se, ne, lane), ok_g = traj_stamps_ok(gt, sg, ng, lane);
+    if (!ok_e || !ok_g) {
+        if (lane == 0) {
+            atomicMin(a.bad, 2u * r + (ok_e ? 1u : 0u));
+            traj_rpe_write(&a.out[r], fig, 0, 0, 0, 0, 0);
+        }
+        return;
+    }
+
+    // ---- pair
+    unsigned long long cnt = 0;
+    for (unsigned long long i = lane; i < ne; i += LK_WAVE) {
+        unsigned int w = LK_TRAJ_NONE;
+        if (ng) {
+            double d;
+            const unsigned long long j = traj_partner(gt, sg, ng, traj_ld(et, se, i), &d);
+            if (d <= a.max_dt) w = (unsigned int)j;
+        }
+        part[i] = w;
+        cnt += w != LK_TRAJ_NONE;
+    }
+    const unsigned long long n_pairs = traj_wave_sum_u64(cnt);
+    __syncthreads();   // part[k(i)] below is another lane's word (the exit above is uniform: every lane of the wave arrives)
+
+    // ---- terms
+    unsigned long long terms = 0, imax_t = ~0ull, imax_r = ~0ull;
+    double t2 = 0.0, t1 = 0.0, tmax = -1.0, r2 = 0.0, r1 = 0.0, rmax = -1.0;
+    bool nonfinite = false;
+    for (unsigned long long i = lane; i < ne; i += LK_WAVE) {
+        unsigned long long k;
+        if (a.flags & LK_RPE_INDEX) {
+            k = i + a.step;
+        } else {
+            const double target = traj_ld(et, se, i) + a.delta;
+            k = (i + 1) + traj_lower_bound(et + (i + 1) * se, se, ne - (i + 1), target);
+        }
+        if (k >= ne) continue;
+        const unsigned int wa = part[i], wb = part[k];
+        if (wa == LK_TRAJ_NONE || wb == LK_TRAJ_NONE) continue;
+        ++terms;
+        double dRe[9], dpe[3], dRg[9], dpg[3], e_t, s, c;
+        bool fin;
+        {
+            double p0[3], R0[9], p1[3], R1[9];
+            fin = traj_ld_pose(ep, er, se, i, p0, R0);
+            fin = traj_ld_pose(ep, er, se, k, p1, R1) && fin;
+            lk_relpose_motion(R0, p0, R1, p1, dRe, dpe);
+        }
+        {
+            double p0[3], R0[9], p1[3], R1[9];
+            fin = traj_ld_pose(gp, gr, sg, wa, p0, R0) && fin;
+            fin = traj_ld_pose(gp, gr, sg, wb, p1, R1) && fin;
+            lk_relpose_motion(R0, p0, R1, p1, dRg, dpg);
+        }
+        if (!fin) {
+            nonfinite = true;
+            continue;
+        }
+        lk_relpose_term(dRe, dpe, dRg, dpg, &e_t, &s, &c);
+        const double e_r = atan2(s, c);
+        t2 += e_t * e_t, t1 += e_t;
+        r2 += e_r * e_r, r1 += e_r;
+        if (e_t > tmax) tmax = e_t, imax_t = i;   // (ascending i: the lane's first of equal maxima)
+        if (e_r > rmax) rmax = e_r, imax_r = i;
+    }
+    const unsigned long long n_terms = traj_wave_sum_u64(terms);
+    if (n_terms == 0 || __ballot(nonfinite) != 0) {
+        if (lane == 0) traj_rpe_write(&a.out[r], fig, n_terms, n_pairs, 0, 0, n_terms ? LK_RPE_NONFINITE : 0u);
+        return;
+    }
+
+    // ---- combine
+    const double inv_n = 1.0 / (double)n_terms;
+    t2 = wave_sum(t2), t1 = wave_sum(t1), r2 = wave_sum(r2), r1 = wave_sum(r1);
+    const double wt = traj_wave_max(tmax), wr = traj_wave_max(rmax);
+    const unsigned long long worst_t = traj_wave_min_u64(tmax == wt ? imax_t : ~0ull), worst_r = traj_wave_min_u64(rmax == wr ? imax_r : ~0ull);
+    fig[0] = sqrt(t2 * inv_n), fig[1] = t1 * inv_n, fig[2] = wt;
+    fig[3] = sqrt(r2 * inv_n), fig[4] = r1 * inv_n, fig[5] = wr;
+    if (lane == 0) traj_rpe_write(&a.out[r], fig, n_terms, n_pairs, (unsigned int)worst_t, (unsigned int)worst_r, 0);
 }

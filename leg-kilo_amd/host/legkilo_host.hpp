@@ -419,6 +419,28 @@ class KiloPath {
                                     max_dt, align ? LK_ATE_ALIGN : 0u, out.data()));
         return out;
     }
+    // lk_runs_rpe_dev: every run of the last _cloud replay scored by its drift per step, translation and rotation, where its bucket table lies (t, pos
+    // AND rot of the records; tum.py's rpe).  A step reaches from bucket i to the first later one at least `delta` seconds on (by_index: `delta`
+    // buckets on) and counts when both ends find a ground-truth partner within max_dt; d_gt_rot: nine row-major doubles per sample, body -> world.
+    // One lk_rpe per run; worst_trans / worst_rot name the first bucket of the worst step.
+    std::vector<lk_rpe> runsRpeDev(const std::vector<uint64_t>& run_bucket_off, const double* d_gt_t, const double* d_gt_pos, const double* d_gt_rot,
+                                   size_t gt_stride, const std::vector<uint64_t>& gt_off, double max_dt, double delta, bool by_index = false) {
+        if (run_bucket_off.size() < 2 || gt_off.size() != run_bucket_off.size()) throw std::runtime_error("runsRpeDev: table sizes differ");
+        std::vector<lk_rpe> out(run_bucket_off.size() - 1);
+        dev_->check(lk_runs_rpe_dev(dev_->h(), out.size(), run_bucket_off.data(), d_gt_t, d_gt_pos, d_gt_rot, gt_stride, gt_off.data(), max_dt, delta,
+                                    by_index ? LK_RPE_INDEX : 0u, out.data()));
+        return out;
+    }
+    // lk_traj_rpe_dev: the same over trajectories the caller holds in HBM (strided tables on both sides)
+    std::vector<lk_rpe> trajRpeDev(const double* d_est_t, const double* d_est_pos, const double* d_est_rot, size_t est_stride,
+                                   const std::vector<uint64_t>& est_off, const double* d_gt_t, const double* d_gt_pos, const double* d_gt_rot,
+                                   size_t gt_stride, const std::vector<uint64_t>& gt_off, double max_dt, double delta, bool by_index = false) {
+        if (est_off.size() < 2 || gt_off.size() != est_off.size()) throw std::runtime_error("trajRpeDev: table sizes differ");
+        std::vector<lk_rpe> out(est_off.size() - 1);
+        dev_->check(lk_traj_rpe_dev(dev_->h(), out.size(), d_est_t, d_est_pos, d_est_rot, est_stride, est_off.data(), d_gt_t, d_gt_pos, d_gt_rot,
+                                    gt_stride, gt_off.data(), max_dt, delta, by_index ? LK_RPE_INDEX : 0u, out.data()));
+        return out;
+    }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
     // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with

@@ -625,6 +625,56 @@ int lk_downsample_clouds_dev(lk_handle* h, const float* d_world, size_t n_files,
                              uint8_t* unfiltered);
 int lk_downsample_clouds(lk_handle* h, const float* world, size_t n_files, const uint64_t* file_off, float leaf, float* out, uint64_t* out_off,
                          uint8_t* unfiltered);
+/* Cloud-to-cloud nearest-neighbour distance (C2C) of many pairs of clouds in one call: how far the points of a query cloud lie from a reference
+ * cloud - accuracy against a survey, completeness with the sides exchanged, slot against slot with both sides the same buffer.  The map metric
+ * beside lk_runs_ate_dev / lk_runs_rpe_dev: one small record per pair for the host.  leg-kilo_amd/cloudmetrics.py's c2c is the numpy statement.
+ * Layout: both sides are 16-byte x y z w float records (d_world_out's and lk_downsample_clouds_dev's d_out), DEVICE, 16-byte aligned; w is never
+ * read.  Cloud c of a side = its records off[c] .. off[c+1]) (q_off / r_off: HOST, n_clouds + 1 entries, not decreasing; ranges may be empty,
+ * off[0] need not be 0, nothing outside the ranges is read).  d_query and d_ref may be the same buffer or overlap: both are only read.
+ * Pair k scores query cloud pair_q[k] against reference cloud pair_r[k] (HOST, n_pairs entries each); a cloud may serve any number of pairs or none.
+ * The search structure of a reference cloud is built once per call.
+ * Result, for query point q and reference point r, in float64 from the float32 coordinates and without fused multiply-add:
+ *     dx = (double)q.x - (double)r.x (dy, dz likewise),  d2 = (dx*dx + dy*dy) + dz*dz,
+ * j(i) = the reference index that minimises (d2, j) lexicographically - the smallest index on equal d2.  Point i is MATCHED when
+ * d2_i <= max_dist * max_dist (one rounded product), d_i = sqrt(d2_i).  Every decision - matched, j(i), n_within, worst - is taken on d2.  This
+ * is a definition by brute force: the grid the library searches is not part of it (its cell edge is max_dist, doubled until the reference
+ * cloud's grid holds fewer than 2^31 cells, so clouds kilometres apart under a small max_dist are an ordinary input).
+ * d_nn_idx, d_nn_d2 (DEVICE, both or neither): pair k's query point i has its j(i) and d2_i at entry nn_off[k] + i; an unmatched point has
+ * 0xffffffff and +inf.  nn_off: HOST, n_pairs + 1 entries, written by the call, nn_off[0] = 0; required with the two outputs, optional without.
+ * Nothing behind nn_off[n_pairs] entries is written.
+ * out: HOST, n_pairs records, every byte written.  rmse = sqrt(sum d2_i / n_matched), mean = sum d_i / n_matched, max = the largest d_i, over the
+ * matched points; n_within[k] counts the matched points with d2_i <= thr[k] * thr[k] (k < n_thr <= 4, thr: HOST).  A sum is taken in an order that
+ * depends on the pair's own two clouds only: a pair's record has the same bits whatever else the call holds.
+ * A pair with a non-finite coordinate in either cloud gets LK_C2C_NONFINITE, one with |p / max_dist| >= 2^30 in either cloud LK_C2C_RANGE: NaN
+ * figures, zero counts, worst 0, its n_query, and 0xffffffff / +inf in its nn entries; the other pairs are unaffected (a diverged slot scores NaN
+ * and does not abort a sweep).  Synchronous; no filter slot, map, overlay or bucket table is touched.
+ * LK_ERR_INVALID before anything is launched, the message naming the argument: n_pairs == 0, a null table or pointer but for the optional outputs,
+ * one of d_nn_idx / d_nn_d2 without the other or both without nn_off, a misaligned pointer, decreasing offsets, a pair index past its side's cloud
+ * count, max_dist not finite or <= 0, n_thr > 4, n_thr > 0 with thr NULL, a thr[k] not finite, < 0 or > max_dist, an nn buffer that overlaps an
+ * input or the other nn buffer.  LK_ERR_CAPACITY: 2^31 or more reference records in all, a query cloud of 2^32 - 1 records or more, 2^32 or more
+ * query points over all pairs.  A refused call writes nothing.
+ * lk_clouds_c2c: the same with query, ref, nn_idx and nn_d2 in HOST memory (4- and 8-byte alignment); the two ranges are uploaded for the call. */
+typedef struct lk_c2c {            /* 80 bytes */
+    double   rmse, mean, max;      /* of d_i over the MATCHED query points; NaN when n_matched == 0 or status != 0 */
+    uint64_t n_query, n_matched;
+    uint64_t n_within[4];          /* matched points with d2_i <= thr[k] * thr[k]; entries k >= n_thr written 0 */
+    uint32_t worst;                /* index within the query cloud of the largest d2_i, the first on ties; 0 when n_matched == 0 */
+    uint32_t status;               /* 0, LK_C2C_NONFINITE, LK_C2C_RANGE (bits) */
+} lk_c2c;
+#define LK_C2C_NONFINITE 1u
+#define LK_C2C_RANGE     2u
+int lk_clouds_c2c_dev(lk_handle* h,
+                      const float* d_query, size_t n_qclouds, const uint64_t* q_off,
+                      const float* d_ref,   size_t n_rclouds, const uint64_t* r_off,
+                      size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
+                      double max_dist, const double* thr, uint32_t n_thr,
+                      lk_c2c* out, uint32_t* d_nn_idx, double* d_nn_d2, uint64_t* nn_off);
+int lk_clouds_c2c(lk_handle* h,
+                  const float* query, size_t n_qclouds, const uint64_t* q_off,
+                  const float* ref,   size_t n_rclouds, const uint64_t* r_off,
+                  size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
+                  double max_dist, const double* thr, uint32_t n_thr,
+                  lk_c2c* out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

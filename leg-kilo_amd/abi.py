@@ -246,6 +246,33 @@ def rpe_dtype():
     return dt
 
 
+class lk_c2c(C.Structure):
+    _fields_ = [
+        ("rmse", C.c_double),
+        ("mean", C.c_double),
+        ("max", C.c_double),
+        ("n_query", C.c_uint64),
+        ("n_matched", C.c_uint64),
+        ("n_within", C.c_uint64 * 4),
+        ("worst", C.c_uint32),
+        ("status", C.c_uint32),
+    ]
+
+
+LK_C2C_NONFINITE = 1   # lk_c2c.status: a coordinate of either cloud of the pair was not finite
+LK_C2C_RANGE = 2       # lk_c2c.status: |p / max_dist| >= 2^30 in either cloud of the pair
+LK_C2C_NO_MATCH = 0xFFFFFFFF   # nn_idx of an unmatched query point (its nn_d2 is +inf)
+
+
+def c2c_dtype():
+    """numpy view of lk_c2c (80 B): the records of lk_clouds_c2c_dev / lk_clouds_c2c."""
+    import numpy as np
+
+    dt = np.dtype(lk_c2c)
+    assert dt.itemsize == C.sizeof(lk_c2c) == 80
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

@@ -660,6 +660,43 @@ class LegKiloHip:
         self._chk(self.L.lk_runs_rpe_dev(self.h, n, _p(ro), d_gt_t, d_gt_pos, d_gt_rot, gt_stride, _p(go), max_dt, delta, fl, _p(res)))
         return res[:n]
 
+    def _c2c_call(self, fn, query, q_off, ref, r_off, pairs, max_dist, thr, nn_idx, nn_d2, want_nn_off):
+        """What the two C2C exports share - the host tables and the records: fn(handle, query, tables, ref, tables, pairs, max_dist, thr, records,
+        nn arrays).  Returns (records, nn_off or None)."""
+        qo = np.ascontiguousarray(q_off, dtype=np.uint64)
+        ro = np.ascontiguousarray(r_off, dtype=np.uint64)
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        pq, pref = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        th = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+        res = np.zeros(max(len(pr), 1), dtype=abi.c2c_dtype())
+        nn_off = np.zeros(len(pr) + 1, dtype=np.uint64) if want_nn_off else None
+        self._chk(fn(self.h, query, max(len(qo) - 1, 0), _p(qo), ref, max(len(ro) - 1, 0), _p(ro), len(pr), _p(pq), _p(pref), max_dist,
+                     _p(th) if len(th) else None, len(th), _p(res), nn_idx, nn_d2, _p(nn_off)))
+        return res[:len(pr)], nn_off
+
+    def clouds_c2c_dev(self, d_query, q_off, d_ref, r_off, pairs, max_dist, thr=(), d_nn_idx=0, d_nn_d2=0):
+        """Cloud-to-cloud nearest-neighbour distance of many pairs of clouds in device memory (lk_clouds_c2c_dev): cloud c of a side = the 16-byte
+        x y z w records off[c] : off[c + 1] at its device pointer (a run replay's d_world, downsample_clouds_dev's d_out with its out_off - both
+        sides may be the same buffer); pairs [n, 2] = (query cloud, reference cloud).  A query point is matched when its nearest reference point
+        lies within max_dist; thr: up to four thresholds <= max_dist counted in n_within.  d_nn_idx / d_nn_d2: device pointers (0: none) that take
+        the neighbour's index in its cloud and the squared distance per pair and query point.  Returns (abi.c2c_dtype() records, one per pair,
+        nn_off uint64 [n + 1]: pair k's entries are nn_off[k] : nn_off[k + 1]); cloudmetrics.c2c is the numpy statement, cloudmetrics.fscore
+        combines the two directions."""
+        return self._c2c_call(self.L.lk_clouds_c2c_dev, d_query, q_off, d_ref, r_off, pairs, max_dist, thr, d_nn_idx or None, d_nn_d2 or None, True)
+
+    def clouds_c2c(self, query, q_off, ref, r_off, pairs, max_dist, thr=(), want_nn=False):
+        """The same with both sides in host memory (lk_clouds_c2c): query, ref float32 [n, 4] (x y z w records).  Returns (records, nn_off), with
+        want_nn (records, nn_off, nn_idx uint32, nn_d2 float64)."""
+        q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1, 4)
+        r = np.ascontiguousarray(ref, dtype=np.float32).reshape(-1, 4)
+        if not want_nn:
+            return self._c2c_call(self.L.lk_clouds_c2c, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, None, None, True)
+        qo = np.asarray(q_off, dtype=np.uint64)
+        total = int(sum(int(qo[a + 1] - qo[a]) for a in np.asarray(pairs, dtype=np.int64).reshape(-1, 2)[:, 0]))
+        idx, d2 = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.float64)
+        res, nn_off = self._c2c_call(self.L.lk_clouds_c2c, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, _p(idx), _p(d2), True)
+        return res, nn_off, idx[:total], d2[:total]
+
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
         file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at

@@ -1,0 +1,234 @@
+// lk_c2c.hip - the map-cloud metric unit of liblegkilo_hip.so (see lk_internal.h): cloud-to-cloud nearest-neighbour distance of many pairs of clouds
+// in one call (lk_c2c_kernels.h, arithmetic in lk_c2c.h) and the two C-ABI entries around it - lk_clouds_c2c_dev over clouds in HBM (a run replay's
+// d_world_out, lk_downsample_clouds_dev's d_out), lk_clouds_c2c over clouds in host memory.
+// Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
+#define LK_TU_C2C 1
+#include "lk_internal.h"
+#include "lk_c2c_kernels.h"
+
+static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
+static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
+
+namespace {
+struct C2cArgs {   // the arguments both entries share, as the caller gave them
+    const float *query, *ref;
+    size_t n_q, n_r, n_pairs;
+    const uint64_t *q_off, *r_off;
+    const uint32_t *pair_q, *pair_r;
+    double max_dist;
+    const double* thr;
+    uint32_t n_thr;
+    lk_c2c* out;
+    uint32_t* nn_idx;
+    double* nn_d2;
+    uint64_t* nn_off;
+};
+bool overlaps(uintptr_t a, size_t alen, uintptr_t b, size_t blen) { return alen && blen && a < b + blen && b < a + alen; }
+}  // namespace
+
+// what both entries refuse before anything is launched; cloud_align: 16 for device clouds, 4 for host ones.  *total: query points over all pairs
+static int c2c_check(lk_handle* h, const char* who, const C2cArgs& a, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    if (a.n_pairs == 0) return fail(h, LK_ERR_INVALID, w + "n_pairs is 0");
+    if (!a.query) return fail(h, LK_ERR_INVALID, w + "null argument (query)");
+    if (!a.ref) return fail(h, LK_ERR_INVALID, w + "null argument (ref)");
+    if (!a.q_off) return fail(h, LK_ERR_INVALID, w + "null argument (q_off)");
+    if (!a.r_off) return fail(h, LK_ERR_INVALID, w + "null argument (r_off)");
+    if (!a.pair_q) return fail(h, LK_ERR_INVALID, w + "null argument (pair_q)");
+    if (!a.pair_r) return fail(h, LK_ERR_INVALID, w + "null argument (pair_r)");
+    if (!a.out) return fail(h, LK_ERR_INVALID, w + "null argument (out)");
+    if (!a.nn_idx != !a.nn_d2) return fail(h, LK_ERR_INVALID, w + (a.nn_idx ? "nn_idx without nn_d2" : "nn_d2 without nn_idx") + ": both or neither");
+    if (a.nn_idx && !a.nn_off) return fail(h, LK_ERR_INVALID, w + "nn_idx and nn_d2 need nn_off");
+    if ((uintptr_t)a.query & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "query must be " + std::to_string(cloud_align) + "-byte aligned");
+    if ((uintptr_t)a.ref & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "ref must be " + std::to_string(cloud_align) + "-byte aligned");
+    if ((uintptr_t)a.nn_idx & 3) return fail(h, LK_ERR_INVALID, w + "nn_idx must be 4-byte aligned");
+    if ((uintptr_t)a.nn_d2 & 7) return fail(h, LK_ERR_INVALID, w + "nn_d2 must be 8-byte aligned");
+    if (!std::isfinite(a.max_dist) || !(a.max_dist > 0.0)) return fail(h, LK_ERR_INVALID, w + "max_dist must be finite and above 0");
+    if (a.n_thr > 4) return fail(h, LK_ERR_INVALID, w + "n_thr is " + std::to_string(a.n_thr) + ": at most 4 thresholds");
+    if (a.n_thr && !a.thr) return fail(h, LK_ERR_INVALID, w + "null argument (thr) with n_thr above 0");
+    for (uint32_t k = 0; k < a.n_thr; ++k)
+        if (!std::isfinite(a.thr[k]) || a.thr[k] < 0.0 || a.thr[k] > a.max_dist)
+            return fail(h, LK_ERR_INVALID, w + "thr[" + std::to_string(k) + "] must be finite and in 0 .. max_dist");
+    for (size_t c = 0; c < a.n_q; ++c)
+        if (a.q_off[c + 1] < a.q_off[c]) return fail(h, LK_ERR_INVALID, w + "q_off decreases at cloud " + std::to_string(c));
+    for (size_t c = 0; c < a.n_r; ++c)
+        if (a.r_off[c + 1] < a.r_off[c]) return fail(h, LK_ERR_INVALID, w + "r_off decreases at cloud " + std::to_string(c));
+    for (size_t k = 0; k < a.n_pairs; ++k) {
+        if (a.pair_q[k] >= a.n_q) return fail(h, LK_ERR_INVALID, w + "pair_q[" + std::to_string(k) + "] is past the " + std::to_string(a.n_q) + " query clouds");
+        if (a.pair_r[k] >= a.n_r) return fail(h, LK_ERR_INVALID, w + "pair_r[" + std::to_string(k) + "] is past the " + std::to_string(a.n_r) + " reference clouds");
+    }
+    // (pairs exist, so both sides hold a cloud and both tables an entry 0)
+    if (a.n_pairs >= 0xffffffffull || a.n_q >= 0xffffffffull || a.n_r >= 0x7fffffffull) return fail(h, LK_ERR_CAPACITY, w + "2^32 - 1 pairs or clouds or more");
+    if (a.r_off[a.n_r] - a.r_off[0] >= (1ull << 31)) return fail(h, LK_ERR_CAPACITY, w + "ref holds 2^31 records or more in all: split the call");
+    unsigned long long sum = 0;
+    for (size_t k = 0; k < a.n_pairs; ++k) {
+        const uint64_t n = a.q_off[a.pair_q[k] + 1] - a.q_off[a.pair_q[k]];
+        if (n >= 0xffffffffull) return fail(h, LK_ERR_CAPACITY, w + "query cloud " + std::to_string(a.pair_q[k]) + " holds 2^32 - 1 records or more");
+        sum += n;
+        if (sum >= (1ull << 32)) return fail(h, LK_ERR_CAPACITY, w + "the pairs' query clouds hold 2^32 records or more in all: split the call");
+    }
+    *total = (size_t)sum;
+    if (a.nn_idx) {
+        const uintptr_t qa = (uintptr_t)a.query + 16u * (uintptr_t)a.q_off[0], ra = (uintptr_t)a.ref + 16u * (uintptr_t)a.r_off[0];
+        const size_t ql = 16u * (size_t)(a.q_off[a.n_q] - a.q_off[0]), rl = 16u * (size_t)(a.r_off[a.n_r] - a.r_off[0]);
+        const uintptr_t ia = (uintptr_t)a.nn_idx, da = (uintptr_t)a.nn_d2;
+        if (overlaps(ia, 4 * *total, qa, ql) || overlaps(ia, 4 * *total, ra, rl)) return fail(h, LK_ERR_INVALID, w + "nn_idx overlaps an input cloud");
+        if (overlaps(da, 8 * *total, qa, ql) || overlaps(da, 8 * *total, ra, rl)) return fail(h, LK_ERR_INVALID, w + "nn_d2 overlaps an input cloud");
+        if (overlaps(ia, 4 * *total, da, 8 * *total)) return fail(h, LK_ERR_INVALID, w + "nn_idx overlaps nn_d2");
+    }
+    return LK_OK;
+}
+
+// the clouds of one side that a pair names, in ascending order
+static std::vector<unsigned int> used_clouds(const uint32_t* pair, size_t n_pairs, size_t n_clouds) {
+    std::vector<unsigned char> seen(n_clouds, 0);
+    for (size_t k = 0; k < n_pairs; ++k) seen[pair[k]] = 1;
+    std::vector<unsigned int> u;
+    for (size_t c = 0; c < n_clouds; ++c)
+        if (seen[c]) u.push_back((unsigned int)c);
+    return u;
+}
+
+// the call behind c2c_check, on DEVICE clouds and DEVICE nn arrays (null: the library's own)
+static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
+    const size_t NQ = a.n_q, NR = a.n_r, P = a.n_pairs, N = (size_t)(a.r_off[NR] - a.r_off[0]);
+    const std::vector<unsigned int> uq = used_clouds(a.pair_q, P, NQ), ur = used_clouds(a.pair_r, P, NR);
+    LkC2cQuery q = {};
+    unsigned long long *d_qoff = nullptr, *d_roff64 = nullptr, *d_nnoff = nullptr;
+    unsigned int *d_roff = nullptr, *d_pq = nullptr, *d_pr = nullptr, *d_uq = nullptr, *d_ur = nullptr, *q_status = nullptr, *r_status = nullptr;
+    unsigned int *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr, *own_idx = nullptr;
+    int *q_mm = nullptr, *r_mm = nullptr;
+    LkC2cGrid* grid = nullptr;
+    LkC2cRec* recs = nullptr;
+    double* own_d2 = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        d_qoff = c.take<unsigned long long>(NQ + 1), d_roff64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
+        d_roff = c.take<unsigned int>(NR + 1), d_pq = c.take<unsigned int>(P), d_pr = c.take<unsigned int>(P);
+        d_uq = c.take<unsigned int>(uq.size()), d_ur = c.take<unsigned int>(ur.size());
+        q_status = c.take<unsigned int>(NQ), r_status = c.take<unsigned int>(NR);
+        q_mm = c.take<int>(6 * NQ), r_mm = c.take<int>(6 * NR);
+        grid = c.take<LkC2cGrid>(NR);
+        k0 = c.take<unsigned int>(N), k1 = c.take<unsigned int>(N), v0 = c.take<unsigned int>(N), v1 = c.take<unsigned int>(N);
+        recs = c.take<LkC2cRec>(N);
+        own_idx = c.take<unsigned int>(a.nn_idx ? 0 : total), own_d2 = c.take<double>(a.nn_idx ? 0 : total);
+        q.out = c.take<lk_c2c>(P);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
+    carve(h->c2c.p);
+    if (N) {
+        size_t tb = 0;
+        if (NR > 1) HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, tb, k0, k1, v0, v1, (unsigned int)N, (unsigned int)NR, d_roff, d_roff + 1, 0, 31, h->stream));
+        else HIPCHK(h, lk_prim_sort_pairs(nullptr, tb, k0, k1, (const int*)v0, (int*)v1, N, 0, 31, h->stream));
+        LKCHK(reserve(h, h->prim_tmp, tb));
+    }
+    // the host tables: offsets (the reference side's also counted from its first record, 32 bits), pairs, the clouds in use, the nn offsets
+    std::vector<unsigned int> roff(NR + 1);
+    std::vector<unsigned long long> nnoff(P + 1, 0ull);
+    for (size_t c = 0; c <= NR; ++c) roff[c] = (unsigned int)(a.r_off[c] - a.r_off[0]);
+    size_t big_q = 0, big_r = 0;
+    for (size_t k = 0; k < P; ++k) nnoff[k + 1] = nnoff[k] + (a.q_off[a.pair_q[k] + 1] - a.q_off[a.pair_q[k]]);
+    for (unsigned int c : uq) big_q = std::max(big_q, (size_t)(a.q_off[c + 1] - a.q_off[c]));
+    for (unsigned int c : ur) big_r = std::max(big_r, (size_t)(a.r_off[c + 1] - a.r_off[c]));
+    HIPCHK(h, hipMemcpyAsync(d_qoff, a.q_off, 8 * (NQ + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_roff64, a.r_off, 8 * (NR + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_nnoff, nnoff.data(), 8 * (P + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_roff, roff.data(), 4 * (NR + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_pq, a.pair_q, 4 * P, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_pr, a.pair_r, 4 * P, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_uq, uq.data(), 4 * uq.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_ur, ur.data(), 4 * ur.size(), hipMemcpyHostToDevice, h->stream));
+    const float4* qpts = reinterpret_cast<const float4*>(a.query);
+    const float4* rpts = reinterpret_cast<const float4*>(a.ref);
+    auto blocks = [](size_t n) { return dim3((unsigned int)((n + 255) / 256)); };
+    auto stride_blocks = [](size_t clouds, size_t biggest) {
+        return (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / clouds)), std::max<size_t>(1, biggest / 4096));
+    };
+    // 1. bounds and status of the clouds in use, the reference clouds' grids
+    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, blocks(NQ), dim3(256), 0, h->stream, q_mm, q_status, (unsigned int)NQ));
+    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, blocks(NR), dim3(256), 0, h->stream, r_mm, r_status, (unsigned int)NR));
+    LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)uq.size(), stride_blocks(uq.size(), big_q)), dim3(256), 0, h->stream, qpts,
+                                               d_qoff, d_uq, a.max_dist, q_mm, q_status));
+    LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)ur.size(), stride_blocks(ur.size(), big_r)), dim3(256), 0, h->stream, rpts,
+                                               d_roff64, d_ur, a.max_dist, r_mm, r_status));
+    LAUNCH(h, "c2c_grid", hipLaunchKernelGGL(lk_c2c_grid_kernel, blocks(NR), dim3(256), 0, h->stream, r_mm, r_status, a.max_dist, (unsigned int)NR, grid));
+    // 2. a cell key per reference record, a stable sort by key inside each cloud, the records into that order
+    if (N) {
+        const float4* rfirst = rpts + a.r_off[0];
+        LAUNCH(h, "c2c_keys", hipLaunchKernelGGL(lk_c2c_keys_kernel, blocks(N), dim3(256), 0, h->stream, rfirst, (unsigned int)N, d_roff, (unsigned int)NR, grid,
+                                                 r_status, r_mm, k0, v0));
+        size_t tb = h->prim_tmp.cap;
+        if (NR > 1) HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, k0, k1, v0, v1, (unsigned int)N, (unsigned int)NR, d_roff, d_roff + 1, 0, 31, h->stream));
+        else HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, k0, k1, (const int*)v0, (int*)v1, N, 0, 31, h->stream));
+        LAUNCH(h, "c2c_gather", hipLaunchKernelGGL(lk_c2c_gather_kernel, blocks(N), dim3(256), 0, h->stream, rfirst, v1, (unsigned int)N, d_roff, (unsigned int)NR,
+                                                   r_status, r_mm, recs));
+    }
+    // 3. (j, d2) per pair and query point, one record per pair
+    q.q_pts = qpts, q.q_off = d_qoff, q.r_off = d_roff, q.pair_q = d_pq, q.pair_r = d_pr, q.nn_off = d_nnoff;
+    q.q_status = q_status, q.r_status = r_status, q.grid = grid, q.keys = k1, q.recs = recs;
+    q.nn_idx = a.nn_idx ? a.nn_idx : own_idx, q.nn_d2 = a.nn_idx ? a.nn_d2 : own_d2;
+    q.reach2 = lk_c2c_reach2(a.max_dist);
+    for (uint32_t k = 0; k < 4; ++k) q.thr2[k] = k < a.n_thr ? a.thr[k] * a.thr[k] : 0.0;
+    q.n_pairs = (unsigned int)P, q.n_thr = a.n_thr;
+    if (total) LAUNCH(h, "c2c_query", hipLaunchKernelGGL(lk_c2c_query_kernel, blocks(total), dim3(256), 0, h->stream, q, (unsigned long long)total));
+    LAUNCH(h, "c2c_reduce", hipLaunchKernelGGL(lk_c2c_reduce_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, q));
+    std::vector<lk_c2c> rec(P);
+    HIPCHK(h, hipMemcpyAsync(rec.data(), q.out, sizeof(lk_c2c) * P, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(a.out, rec.data(), sizeof(lk_c2c) * P);
+    if (a.nn_off)
+        for (size_t k = 0; k <= P; ++k) a.nn_off[k] = nnoff[k];
+    return LK_OK;
+}
+
+extern "C" {
+
+int lk_clouds_c2c_dev(lk_handle* h, const float* d_query, size_t n_qclouds, const uint64_t* q_off, const float* d_ref, size_t n_rclouds, const uint64_t* r_off,
+                      size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r, double max_dist, const double* thr, uint32_t n_thr, lk_c2c* out,
+                      uint32_t* d_nn_idx, double* d_nn_d2, uint64_t* nn_off) {
+    CHECK_H(h);
+    const C2cArgs a = {d_query, d_ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, out, d_nn_idx, d_nn_d2, nn_off};
+    size_t total = 0;
+    LKCHK(c2c_check(h, "lk_clouds_c2c_dev", a, 16, &total));
+    return c2c_run(h, a, total);
+}
+
+int lk_clouds_c2c(lk_handle* h, const float* query, size_t n_qclouds, const uint64_t* q_off, const float* ref, size_t n_rclouds, const uint64_t* r_off,
+                  size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r, double max_dist, const double* thr, uint32_t n_thr, lk_c2c* out, uint32_t* nn_idx,
+                  double* nn_d2, uint64_t* nn_off) {
+    CHECK_H(h);
+    C2cArgs a = {query, ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, out, nn_idx, nn_d2, nn_off};
+    size_t total = 0;
+    LKCHK(c2c_check(h, "lk_clouds_c2c", a, 4, &total));
+    // device copies of the two ranges and of the nn arrays; the offsets counted from each side's first record
+    const size_t nq = (size_t)(q_off[n_qclouds] - q_off[0]), nr = (size_t)(r_off[n_rclouds] - r_off[0]);
+    float4 *dq = nullptr, *dr = nullptr;
+    uint32_t* di = nullptr;
+    double* dd = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        dq = c.take<float4>(nq + 1), dr = c.take<float4>(nr + 1);   // (+ 1: an empty side still has an address of its own)
+        di = c.take<uint32_t>(nn_idx ? total + 1 : 0), dd = c.take<double>(nn_idx ? total + 1 : 0);
+        return c.total();
+    };
+    LKCHK(reserve(h, h->c2c_io, carve(nullptr)));
+    carve(h->c2c_io.p);
+    if (nq) HIPCHK(h, hipMemcpyAsync(dq, query + 4 * q_off[0], 16 * nq, hipMemcpyHostToDevice, h->stream));
+    if (nr) HIPCHK(h, hipMemcpyAsync(dr, ref + 4 * r_off[0], 16 * nr, hipMemcpyHostToDevice, h->stream));
+    std::vector<uint64_t> qo(n_qclouds + 1), ro(n_rclouds + 1);
+    for (size_t c = 0; c <= n_qclouds; ++c) qo[c] = q_off[c] - q_off[0];
+    for (size_t c = 0; c <= n_rclouds; ++c) ro[c] = r_off[c] - r_off[0];
+    a.query = reinterpret_cast<const float*>(dq), a.ref = reinterpret_cast<const float*>(dr), a.q_off = qo.data(), a.r_off = ro.data();
+    a.nn_idx = nn_idx ? di : nullptr, a.nn_d2 = nn_idx ? dd : nullptr;
+    LKCHK(c2c_run(h, a, total));
+    if (nn_idx && total) {
+        HIPCHK(h, hipMemcpyAsync(nn_idx, di, 4 * total, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nn_d2, dd, 8 * total, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return LK_OK;
+}
+
+}  // extern "C"

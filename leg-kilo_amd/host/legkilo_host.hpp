@@ -24,6 +24,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "legkilo_hip.h"
@@ -439,6 +440,24 @@ class KiloPath {
         std::vector<lk_rpe> out(est_off.size() - 1);
         dev_->check(lk_traj_rpe_dev(dev_->h(), out.size(), d_est_t, d_est_pos, d_est_rot, est_stride, est_off.data(), d_gt_t, d_gt_pos, d_gt_rot,
                                     gt_stride, gt_off.data(), max_dt, delta, by_index ? LK_RPE_INDEX : 0u, out.data()));
+        return out;
+    }
+    // lk_clouds_c2c_dev: map clouds scored against a reference cloud where they lie - cloud c of a side = the 16-byte x y z w records
+    // off[c] .. off[c + 1]) at its device pointer (a replay's d_world_out, downsampleCloudsDev's output and offsets; both sides may be one buffer),
+    // pairs[k] = (query cloud, reference cloud).  A query point is matched when its nearest reference point lies within max_dist; thr (up to four,
+    // each <= max_dist) are counted in n_within.  One lk_c2c per pair.  d_nn_idx / d_nn_d2 (both or neither) take the neighbour and the squared
+    // distance per pair and query point, pair k's from entry (*nn_off)[k] on.  (No Eigen mirror: the reference has no type this would fit.)
+    std::vector<lk_c2c> cloudsC2cDev(const float* d_query, const std::vector<uint64_t>& q_off, const float* d_ref, const std::vector<uint64_t>& r_off,
+                                     const std::vector<std::pair<uint32_t, uint32_t>>& pairs, double max_dist, const std::vector<double>& thr = {},
+                                     uint32_t* d_nn_idx = nullptr, double* d_nn_d2 = nullptr, std::vector<uint64_t>* nn_off = nullptr) {
+        if (q_off.size() < 2 || r_off.size() < 2 || pairs.empty()) throw std::runtime_error("cloudsC2cDev: an offset table or the pairs are empty");
+        std::vector<uint32_t> pq(pairs.size()), pr(pairs.size());
+        for (size_t k = 0; k < pairs.size(); ++k) pq[k] = pairs[k].first, pr[k] = pairs[k].second;
+        std::vector<lk_c2c> out(pairs.size());
+        std::vector<uint64_t> off(pairs.size() + 1);
+        dev_->check(lk_clouds_c2c_dev(dev_->h(), d_query, q_off.size() - 1, q_off.data(), d_ref, r_off.size() - 1, r_off.data(), pairs.size(), pq.data(),
+                                      pr.data(), max_dist, thr.empty() ? nullptr : thr.data(), (uint32_t)thr.size(), out.data(), d_nn_idx, d_nn_d2, off.data()));
+        if (nn_off) *nn_off = off;
         return out;
     }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process

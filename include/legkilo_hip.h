@@ -675,6 +675,51 @@ int lk_clouds_c2c(lk_handle* h,
                   size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
                   double max_dist, const double* thr, uint32_t n_thr,
                   lk_c2c* out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off);
+/* Map scores that need NO reference, of many clouds in one call: mean map entropy (MME) and mean plane variance (MPV) over a map cloud itself -
+ * both lower for a crisper map.  What a recorded run without ground truth or survey ranks its slots by; beside lk_clouds_c2c_dev, one small record
+ * per cloud for the host.  leg-kilo_amd/cloudmetrics.py's mme is the numpy statement.
+ * Layout: a cloud is a range of 16-byte x y z w float records (d_world_out's, lk_downsample_clouds_dev's d_out with its out_off as they are), DEVICE,
+ * 16-byte aligned; w is never read.  Cloud c = the records off[c] .. off[c+1]) (off: HOST, n_clouds + 1 entries, not decreasing; empty clouds are
+ * allowed, off[0] need not be 0, nothing outside the ranges is read).
+ * Definition, for point i of a cloud, `radius` r and min_pts; all arithmetic in float64 from the float32 coordinates, without fused multiply-add:
+ *   neighbourhood  N_i = { j in the same cloud : d2(i, j) <= r * r }, d2 exactly lk_clouds_c2c_dev's ((dx*dx + dy*dy) + dz*dz), r * r one rounded
+ *                  product.  i itself is a member, so n_i = |N_i| >= 1; duplicates are separate points.  The decision is taken on d2: the grid
+ *                  that finds the neighbours (cell edge r, doubled as for C2C) is not part of the definition.
+ *   offsets        u_j = (double)p_j - (double)p_i per axis, ABOUT THE QUERY POINT: bounded by r, so the sums below carry rounding of order
+ *                  2^-53 r^2 wherever the cloud lies (about the origin they would lose |p|^2 / r^2 of that).  s = sum u_j (3 terms),
+ *                  M = sum u_j u_j^T (6 terms) over N_i, in an order of the library's that depends on the cloud's own records (and r) only.
+ *   classes        DENSE when n_i >= min_pts, else SPARSE.  Dense: C = (M - s s^T / n_i) / (n_i - 1), tr = C00 + C11 + C22, det = the cofactor
+ *                  expansion along the first row.  FLAT when det <= 2^-30 * (tr / 3)^3 (tr == 0, all duplicates, included): below that floor
+ *                  det is rounding noise of the float32 storage (a tilted wall at 50 m gives 1e-11 .. 8e-11), whose ln must not be averaged.
+ *                  A dense point that is not flat is SCORED.
+ *   figures        h_i = 0.5 * (3 * ln(2 pi e) + ln det) for a scored point; lmin_i = max(0, smallest eigenvalue of C) for every dense point,
+ *                  flat ones included (closed form, absolute error a few ulp of the largest eigenvalue).
+ * out: HOST, n_clouds records, every byte written.  mme = mean h_i over the scored points, mpv = mean lmin_i over the dense points, h_max = the
+ * largest h_i, worst = its index in the cloud (the first on ties, 0 when none), n_pairs = sum of n_i over all points.  A figure with nothing to
+ * average is NaN.  A cloud's sums are taken in an order that depends on that cloud only: its record has the same bits whatever else the call holds.
+ * d_n, d_h, d_lmin (DEVICE, each independently optional): record off[c] + i has its n_i, h_i, lmin_i at entry off[c] - off[0] + i; d_h is NaN where
+ * the point is not scored, d_lmin NaN where it is sparse.  Nothing behind off[n_clouds] - off[0] entries is written.
+ * A cloud with a non-finite coordinate gets LK_MME_NONFINITE, one with |p / radius| >= 2^30 LK_MME_RANGE: NaN figures, zero counts, its n_points,
+ * and n = 0 / NaN in its per-point entries; the other clouds of the call are unaffected.  Synchronous; no filter slot, map, overlay or bucket table
+ * is touched.
+ * LK_ERR_INVALID before anything is launched, the message naming the argument: n_clouds == 0, a null d_clouds, off or out, a misaligned pointer
+ * (16 bytes for the clouds, 4 for d_n, 8 for d_h and d_lmin), decreasing offsets, radius not finite or <= 0, min_pts < 4 (below four points det is
+ * 0 by rank), an output that overlaps the input or another output.  LK_ERR_CAPACITY: 2^31 or more records in all (the sort's key count, as in
+ * C2C), a cloud of 2^32 - 1 records or more.  A refused call writes nothing.
+ * lk_clouds_mme: the same with clouds, n, hh and lmin in HOST memory (4- and 8-byte alignment); the range is uploaded for the call and the
+ * per-point arrays are copied back. */
+typedef struct lk_mme {            /* 64 bytes */
+    double   mme, mpv, h_max;      /* mean h over the scored points, mean lmin over the dense ones, the largest h; NaN with nothing to average */
+    uint64_t n_points, n_dense, n_scored, n_pairs;
+    uint32_t worst;                /* index within the cloud of the largest h_i, the first on ties; 0 when n_scored == 0 */
+    uint32_t status;               /* 0, LK_MME_NONFINITE, LK_MME_RANGE (bits) */
+} lk_mme;
+#define LK_MME_NONFINITE 1u
+#define LK_MME_RANGE     2u
+int lk_clouds_mme_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts,
+                      lk_mme* out, uint32_t* d_n, double* d_h, double* d_lmin);
+int lk_clouds_mme(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts,
+                  lk_mme* out, uint32_t* n, double* hh, double* lmin);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

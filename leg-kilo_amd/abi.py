@@ -273,6 +273,33 @@ def c2c_dtype():
     return dt
 
 
+class lk_mme(C.Structure):
+    _fields_ = [
+        ("mme", C.c_double),
+        ("mpv", C.c_double),
+        ("h_max", C.c_double),
+        ("n_points", C.c_uint64),
+        ("n_dense", C.c_uint64),
+        ("n_scored", C.c_uint64),
+        ("n_pairs", C.c_uint64),
+        ("worst", C.c_uint32),
+        ("status", C.c_uint32),
+    ]
+
+
+LK_MME_NONFINITE = 1   # lk_mme.status: a coordinate of the cloud was not finite
+LK_MME_RANGE = 2       # lk_mme.status: |p / radius| >= 2^30 in the cloud
+
+
+def mme_dtype():
+    """numpy view of lk_mme (64 B): the records of lk_clouds_mme_dev / lk_clouds_mme."""
+    import numpy as np
+
+    dt = np.dtype(lk_mme)
+    assert dt.itemsize == C.sizeof(lk_mme) == 64
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

@@ -697,6 +697,34 @@ class LegKiloHip:
         res, nn_off = self._c2c_call(self.L.lk_clouds_c2c, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, _p(idx), _p(d2), True)
         return res, nn_off, idx[:total], d2[:total]
 
+    def clouds_mme_dev(self, d_clouds, off, radius, min_pts=5, d_n=0, d_h=0, d_lmin=0):
+        """Mean map entropy and mean plane variance of many clouds in device memory, no reference needed (lk_clouds_mme_dev): cloud c = the 16-byte
+        x y z w records off[c] : off[c + 1] at the device pointer d_clouds (a run replay's d_world, downsample_clouds_dev's d_out with its out_off).
+        A point's neighbourhood is every record of its cloud within `radius`, itself included; with at least min_pts (>= 4) of them it is dense and
+        gets lmin, and h unless its covariance is flat.  d_n / d_h / d_lmin: device pointers (0: none, each on its own) that take n_i uint32, h_i and
+        lmin_i float64 per record, entry off[c] - off[0] + i.  Returns abi.mme_dtype() records, one per cloud; cloudmetrics.mme is the numpy
+        statement."""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.mme_dtype())
+        self._chk(self.L.lk_clouds_mme_dev(self.h, d_clouds, n, _p(o), radius, min_pts, _p(res), d_n or None, d_h or None, d_lmin or None))
+        return res[:n]
+
+    def clouds_mme(self, clouds, off, radius, min_pts=5, want_points=False):
+        """The same with the clouds in host memory (lk_clouds_mme): clouds float32 [n, 4] (x y z w records).  Returns the records, with want_points
+        (records, n uint32, h float64, lmin float64), entry off[c] - off[0] + i for record off[c] + i."""
+        c = np.ascontiguousarray(clouds, dtype=np.float32).reshape(-1, 4)
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.mme_dtype())
+        if not want_points:
+            self._chk(self.L.lk_clouds_mme(self.h, _p(c), n, _p(o), radius, min_pts, _p(res), None, None, None))
+            return res[:n]
+        total = int(o[-1] - o[0]) if len(o) else 0
+        cnt, hh, lm = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1)), np.zeros(max(total, 1))
+        self._chk(self.L.lk_clouds_mme(self.h, _p(c), n, _p(o), radius, min_pts, _p(res), _p(cnt), _p(hh), _p(lm)))
+        return res[:n], cnt[:total], hh[:total], lm[:total]
+
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
         file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at

@@ -1,12 +1,15 @@
 // lk_c2c.hip - the map-cloud metric unit of liblegkilo_hip.so (see lk_internal.h): cloud-to-cloud nearest-neighbour distance of many pairs of clouds
 // in one call (lk_c2c_kernels.h, arithmetic in lk_c2c.h) and the two C-ABI entries around it - lk_clouds_c2c_dev over clouds in HBM (a run replay's
-// d_world_out, lk_downsample_clouds_dev's d_out), lk_clouds_c2c over clouds in host memory.
+// d_world_out, lk_downsample_clouds_dev's d_out), lk_clouds_c2c over clouds in host memory - and, on the same search structure (c2c_index), the
+// scores that need no reference: mean map entropy and mean plane variance (lk_mme_kernels.h, arithmetic in lk_mme.h), lk_clouds_mme_dev / lk_clouds_mme.
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
 #define LK_TU_C2C 1
 #include "lk_internal.h"
 #include "lk_c2c_kernels.h"
+#include "lk_mme_kernels.h"
 
 static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
+static_assert(sizeof(lk_mme) == 64, "lk_mme must be 64 B");
 static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
 
 namespace {
@@ -89,28 +92,82 @@ static std::vector<unsigned int> used_clouds(const uint32_t* pair, size_t n_pair
     return u;
 }
 
+// The search structure of one side's clouds (steps 1 and 2 of a call), shared by lk_clouds_c2c(_dev) and lk_clouds_mme(_dev): the device tables, carved
+// by the caller out of its own scratch.  N = off[n] - off[0] records in all.
+struct C2cIndex {
+    unsigned long long* d_off64;   // [n + 1], as given
+    unsigned int* d_off;           // [n + 1], counted from the first record
+    unsigned int* d_used;          // [used.size()]
+    unsigned int* status;          // [n]
+    int* mm;                       // [6 n]
+    LkC2cGrid* grid;               // [n]
+    unsigned int *k0, *k1, *v0, *v1;   // [N]: k1 = the sorted keys
+    LkC2cRec* recs;                // [N], in that order
+    std::vector<unsigned int> h_off;   // the host copy of d_off: alive until the caller has synchronised
+};
+static dim3 c2c_blocks(size_t n) { return dim3((unsigned int)((n + 255) / 256)); }
+static unsigned int c2c_stride_blocks(size_t clouds, size_t biggest) {
+    return (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / clouds)), std::max<size_t>(1, biggest / 4096));
+}
+static int c2c_sort(lk_handle* h, void* tmp, size_t& tb, const C2cIndex& x, size_t N, size_t n) {
+    if (n > 1) HIPCHK(h, lk_prim_segmented_sort_pairs(tmp, tb, x.k0, x.k1, x.v0, x.v1, (unsigned int)N, (unsigned int)n, x.d_off, x.d_off + 1, 0, 31, h->stream));
+    else HIPCHK(h, lk_prim_sort_pairs(tmp, tb, x.k0, x.k1, (const int*)x.v0, (int*)x.v1, N, 0, 31, h->stream));
+    return LK_OK;
+}
+// 1. bounds and status of the clouds in use and every cloud's grid at edge `reach` (doubling as lk_c2c_grid says); 2. a cell key per record, a stable
+// sort by key inside each cloud, the records into that order
+static int c2c_index(lk_handle* h, const float4* pts, const uint64_t* off, size_t n, const std::vector<unsigned int>& used, double reach, C2cIndex& x) {
+    const size_t N = (size_t)(off[n] - off[0]);
+    if (N) {
+        size_t tb = 0;
+        LKCHK(c2c_sort(h, nullptr, tb, x, N, n));
+        LKCHK(reserve(h, h->prim_tmp, tb));
+    }
+    std::vector<unsigned int>& roff = x.h_off;
+    roff.resize(n + 1);
+    for (size_t c = 0; c <= n; ++c) roff[c] = (unsigned int)(off[c] - off[0]);
+    size_t big = 0;
+    for (unsigned int c : used) big = std::max(big, (size_t)(off[c + 1] - off[c]));
+    HIPCHK(h, hipMemcpyAsync(x.d_off64, off, 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(x.d_off, roff.data(), 4 * (n + 1), hipMemcpyHostToDevice, h->stream));
+    if (!used.empty()) HIPCHK(h, hipMemcpyAsync(x.d_used, used.data(), 4 * used.size(), hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, c2c_blocks(n), dim3(256), 0, h->stream, x.mm, x.status, (unsigned int)n));
+    if (!used.empty())
+        LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)used.size(), c2c_stride_blocks(used.size(), big)), dim3(256), 0, h->stream,
+                                                   pts, x.d_off64, x.d_used, reach, x.mm, x.status));
+    LAUNCH(h, "c2c_grid", hipLaunchKernelGGL(lk_c2c_grid_kernel, c2c_blocks(n), dim3(256), 0, h->stream, x.mm, x.status, reach, (unsigned int)n, x.grid));
+    if (N) {
+        const float4* first = pts + off[0];
+        LAUNCH(h, "c2c_keys", hipLaunchKernelGGL(lk_c2c_keys_kernel, c2c_blocks(N), dim3(256), 0, h->stream, first, (unsigned int)N, x.d_off, (unsigned int)n, x.grid,
+                                                 x.status, x.mm, x.k0, x.v0));
+        size_t tb = h->prim_tmp.cap;
+        LKCHK(c2c_sort(h, h->prim_tmp.p, tb, x, N, n));
+        LAUNCH(h, "c2c_gather", hipLaunchKernelGGL(lk_c2c_gather_kernel, c2c_blocks(N), dim3(256), 0, h->stream, first, x.v1, (unsigned int)N, x.d_off, (unsigned int)n,
+                                                   x.status, x.mm, x.recs));
+    }
+    return LK_OK;
+}
+
 // the call behind c2c_check, on DEVICE clouds and DEVICE nn arrays (null: the library's own)
 static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     const size_t NQ = a.n_q, NR = a.n_r, P = a.n_pairs, N = (size_t)(a.r_off[NR] - a.r_off[0]);
     const std::vector<unsigned int> uq = used_clouds(a.pair_q, P, NQ), ur = used_clouds(a.pair_r, P, NR);
     LkC2cQuery q = {};
-    unsigned long long *d_qoff = nullptr, *d_roff64 = nullptr, *d_nnoff = nullptr;
-    unsigned int *d_roff = nullptr, *d_pq = nullptr, *d_pr = nullptr, *d_uq = nullptr, *d_ur = nullptr, *q_status = nullptr, *r_status = nullptr;
-    unsigned int *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr, *own_idx = nullptr;
-    int *q_mm = nullptr, *r_mm = nullptr;
-    LkC2cGrid* grid = nullptr;
-    LkC2cRec* recs = nullptr;
+    C2cIndex x = {};
+    unsigned long long *d_qoff = nullptr, *d_nnoff = nullptr;
+    unsigned int *d_pq = nullptr, *d_pr = nullptr, *d_uq = nullptr, *q_status = nullptr, *own_idx = nullptr;
+    int* q_mm = nullptr;
     double* own_d2 = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base, 256);
-        d_qoff = c.take<unsigned long long>(NQ + 1), d_roff64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
-        d_roff = c.take<unsigned int>(NR + 1), d_pq = c.take<unsigned int>(P), d_pr = c.take<unsigned int>(P);
-        d_uq = c.take<unsigned int>(uq.size()), d_ur = c.take<unsigned int>(ur.size());
-        q_status = c.take<unsigned int>(NQ), r_status = c.take<unsigned int>(NR);
-        q_mm = c.take<int>(6 * NQ), r_mm = c.take<int>(6 * NR);
-        grid = c.take<LkC2cGrid>(NR);
-        k0 = c.take<unsigned int>(N), k1 = c.take<unsigned int>(N), v0 = c.take<unsigned int>(N), v1 = c.take<unsigned int>(N);
-        recs = c.take<LkC2cRec>(N);
+        d_qoff = c.take<unsigned long long>(NQ + 1), x.d_off64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
+        x.d_off = c.take<unsigned int>(NR + 1), d_pq = c.take<unsigned int>(P), d_pr = c.take<unsigned int>(P);
+        d_uq = c.take<unsigned int>(uq.size()), x.d_used = c.take<unsigned int>(ur.size());
+        q_status = c.take<unsigned int>(NQ), x.status = c.take<unsigned int>(NR);
+        q_mm = c.take<int>(6 * NQ), x.mm = c.take<int>(6 * NR);
+        x.grid = c.take<LkC2cGrid>(NR);
+        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
+        x.recs = c.take<LkC2cRec>(N);
         own_idx = c.take<unsigned int>(a.nn_idx ? 0 : total), own_d2 = c.take<double>(a.nn_idx ? 0 : total);
         q.out = c.take<lk_c2c>(P);
         return c.total();
@@ -118,53 +175,27 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     const size_t bytes = carve(nullptr);
     LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
     carve(h->c2c.p);
-    if (N) {
-        size_t tb = 0;
-        if (NR > 1) HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, tb, k0, k1, v0, v1, (unsigned int)N, (unsigned int)NR, d_roff, d_roff + 1, 0, 31, h->stream));
-        else HIPCHK(h, lk_prim_sort_pairs(nullptr, tb, k0, k1, (const int*)v0, (int*)v1, N, 0, 31, h->stream));
-        LKCHK(reserve(h, h->prim_tmp, tb));
-    }
-    // the host tables: offsets (the reference side's also counted from its first record, 32 bits), pairs, the clouds in use, the nn offsets
-    std::vector<unsigned int> roff(NR + 1);
+    // the host tables of the query side and of the pairs
     std::vector<unsigned long long> nnoff(P + 1, 0ull);
-    for (size_t c = 0; c <= NR; ++c) roff[c] = (unsigned int)(a.r_off[c] - a.r_off[0]);
-    size_t big_q = 0, big_r = 0;
+    size_t big_q = 0;
     for (size_t k = 0; k < P; ++k) nnoff[k + 1] = nnoff[k] + (a.q_off[a.pair_q[k] + 1] - a.q_off[a.pair_q[k]]);
     for (unsigned int c : uq) big_q = std::max(big_q, (size_t)(a.q_off[c + 1] - a.q_off[c]));
-    for (unsigned int c : ur) big_r = std::max(big_r, (size_t)(a.r_off[c + 1] - a.r_off[c]));
     HIPCHK(h, hipMemcpyAsync(d_qoff, a.q_off, 8 * (NQ + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_roff64, a.r_off, 8 * (NR + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_nnoff, nnoff.data(), 8 * (P + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_roff, roff.data(), 4 * (NR + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_pq, a.pair_q, 4 * P, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_pr, a.pair_r, 4 * P, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_uq, uq.data(), 4 * uq.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_ur, ur.data(), 4 * ur.size(), hipMemcpyHostToDevice, h->stream));
     const float4* qpts = reinterpret_cast<const float4*>(a.query);
     const float4* rpts = reinterpret_cast<const float4*>(a.ref);
-    auto blocks = [](size_t n) { return dim3((unsigned int)((n + 255) / 256)); };
-    auto stride_blocks = [](size_t clouds, size_t biggest) {
-        return (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / clouds)), std::max<size_t>(1, biggest / 4096));
-    };
-    // 1. bounds and status of the clouds in use, the reference clouds' grids
+    auto blocks = c2c_blocks;
+    // bounds and status of the query clouds in use; steps 1 and 2 for the reference side
     LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, blocks(NQ), dim3(256), 0, h->stream, q_mm, q_status, (unsigned int)NQ));
-    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, blocks(NR), dim3(256), 0, h->stream, r_mm, r_status, (unsigned int)NR));
-    LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)uq.size(), stride_blocks(uq.size(), big_q)), dim3(256), 0, h->stream, qpts,
+    LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)uq.size(), c2c_stride_blocks(uq.size(), big_q)), dim3(256), 0, h->stream, qpts,
                                                d_qoff, d_uq, a.max_dist, q_mm, q_status));
-    LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)ur.size(), stride_blocks(ur.size(), big_r)), dim3(256), 0, h->stream, rpts,
-                                               d_roff64, d_ur, a.max_dist, r_mm, r_status));
-    LAUNCH(h, "c2c_grid", hipLaunchKernelGGL(lk_c2c_grid_kernel, blocks(NR), dim3(256), 0, h->stream, r_mm, r_status, a.max_dist, (unsigned int)NR, grid));
-    // 2. a cell key per reference record, a stable sort by key inside each cloud, the records into that order
-    if (N) {
-        const float4* rfirst = rpts + a.r_off[0];
-        LAUNCH(h, "c2c_keys", hipLaunchKernelGGL(lk_c2c_keys_kernel, blocks(N), dim3(256), 0, h->stream, rfirst, (unsigned int)N, d_roff, (unsigned int)NR, grid,
-                                                 r_status, r_mm, k0, v0));
-        size_t tb = h->prim_tmp.cap;
-        if (NR > 1) HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, k0, k1, v0, v1, (unsigned int)N, (unsigned int)NR, d_roff, d_roff + 1, 0, 31, h->stream));
-        else HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, k0, k1, (const int*)v0, (int*)v1, N, 0, 31, h->stream));
-        LAUNCH(h, "c2c_gather", hipLaunchKernelGGL(lk_c2c_gather_kernel, blocks(N), dim3(256), 0, h->stream, rfirst, v1, (unsigned int)N, d_roff, (unsigned int)NR,
-                                                   r_status, r_mm, recs));
-    }
+    LKCHK(c2c_index(h, rpts, a.r_off, NR, ur, a.max_dist, x));
+    unsigned int *d_roff = x.d_off, *r_status = x.status, *k1 = x.k1;
+    LkC2cGrid* grid = x.grid;
+    LkC2cRec* recs = x.recs;
     // 3. (j, d2) per pair and query point, one record per pair
     q.q_pts = qpts, q.q_off = d_qoff, q.r_off = d_roff, q.pair_q = d_pq, q.pair_r = d_pr, q.nn_off = d_nnoff;
     q.q_status = q_status, q.r_status = r_status, q.grid = grid, q.keys = k1, q.recs = recs;
@@ -226,6 +257,135 @@ int lk_clouds_c2c(lk_handle* h, const float* query, size_t n_qclouds, const uint
     if (nn_idx && total) {
         HIPCHK(h, hipMemcpyAsync(nn_idx, di, 4 * total, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(nn_d2, dd, 8 * total, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return LK_OK;
+}
+
+}  // extern "C"
+
+namespace {
+struct MmeArgs {   // the arguments both entries share, as the caller gave them
+    const float* clouds;
+    size_t n_clouds;
+    const uint64_t* off;
+    double radius;
+    uint32_t min_pts;
+    lk_mme* out;
+    uint32_t* n;
+    double *hh, *lmin;
+};
+}  // namespace
+
+// what both entries refuse before anything is launched; cloud_align: 16 for device clouds, 4 for host ones.  *total: records in all
+static int mme_check(lk_handle* h, const char* who, const MmeArgs& a, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    if (a.n_clouds == 0) return fail(h, LK_ERR_INVALID, w + "n_clouds is 0");
+    if (!a.clouds) return fail(h, LK_ERR_INVALID, w + "null argument (clouds)");
+    if (!a.off) return fail(h, LK_ERR_INVALID, w + "null argument (off)");
+    if (!a.out) return fail(h, LK_ERR_INVALID, w + "null argument (out)");
+    if ((uintptr_t)a.clouds & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "clouds must be " + std::to_string(cloud_align) + "-byte aligned");
+    if ((uintptr_t)a.n & 3) return fail(h, LK_ERR_INVALID, w + "n must be 4-byte aligned");
+    if ((uintptr_t)a.hh & 7) return fail(h, LK_ERR_INVALID, w + "h must be 8-byte aligned");
+    if ((uintptr_t)a.lmin & 7) return fail(h, LK_ERR_INVALID, w + "lmin must be 8-byte aligned");
+    if (!std::isfinite(a.radius) || !(a.radius > 0.0)) return fail(h, LK_ERR_INVALID, w + "radius must be finite and above 0");
+    if (a.min_pts < 4) return fail(h, LK_ERR_INVALID, w + "min_pts is " + std::to_string(a.min_pts) + ": at least 4 (below four points det is 0 by rank)");
+    for (size_t c = 0; c < a.n_clouds; ++c)
+        if (a.off[c + 1] < a.off[c]) return fail(h, LK_ERR_INVALID, w + "off decreases at cloud " + std::to_string(c));
+    if (a.n_clouds >= 0x7fffffffull) return fail(h, LK_ERR_CAPACITY, w + "2^31 - 1 clouds or more");
+    if (a.off[a.n_clouds] - a.off[0] >= (1ull << 31)) return fail(h, LK_ERR_CAPACITY, w + "the clouds hold 2^31 records or more in all: split the call");
+    for (size_t c = 0; c < a.n_clouds; ++c)   // (cannot happen under the bound above; the header states both)
+        if (a.off[c + 1] - a.off[c] >= 0xffffffffull) return fail(h, LK_ERR_CAPACITY, w + "cloud " + std::to_string(c) + " holds 2^32 - 1 records or more");
+    *total = (size_t)(a.off[a.n_clouds] - a.off[0]);
+    const uintptr_t ca = (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0];
+    const size_t cl = 16u * *total;
+    const uintptr_t p[3] = {(uintptr_t)a.n, (uintptr_t)a.hh, (uintptr_t)a.lmin};
+    const size_t len[3] = {4 * *total, 8 * *total, 8 * *total};
+    const char* name[3] = {"n", "h", "lmin"};
+    for (int i = 0; i < 3; ++i) {
+        if (!p[i]) continue;
+        if (overlaps(p[i], len[i], ca, cl)) return fail(h, LK_ERR_INVALID, w + name[i] + " overlaps the input clouds");
+        for (int j = i + 1; j < 3; ++j)
+            if (p[j] && overlaps(p[i], len[i], p[j], len[j])) return fail(h, LK_ERR_INVALID, w + name[i] + " overlaps " + name[j]);
+    }
+    return LK_OK;
+}
+
+// the call behind mme_check, on DEVICE clouds and DEVICE per-point arrays (null: the library's own)
+static int mme_run(lk_handle* h, const MmeArgs& a, size_t N) {
+    const size_t NC = a.n_clouds;
+    std::vector<unsigned int> used;   // every non-empty cloud
+    for (size_t c = 0; c < NC; ++c)
+        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+    C2cIndex x = {};
+    LkMmeCall m = {};
+    unsigned int* own_n = nullptr;
+    double *own_h = nullptr, *own_l = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
+        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
+        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
+        x.recs = c.take<LkC2cRec>(N);
+        own_n = c.take<unsigned int>(a.n ? 0 : N), own_h = c.take<double>(a.hh ? 0 : N), own_l = c.take<double>(a.lmin ? 0 : N);
+        m.out = c.take<lk_mme>(NC);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
+    carve(h->c2c.p);
+    LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.radius, x));
+    m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
+    m.n = a.n ? a.n : own_n, m.h = a.hh ? a.hh : own_h, m.lmin = a.lmin ? a.lmin : own_l;
+    m.reach2 = lk_c2c_reach2(a.radius);
+    m.n_clouds = (unsigned int)NC, m.min_pts = a.min_pts, m.total = (unsigned int)N;
+    if (N) LAUNCH(h, "mme_point", hipLaunchKernelGGL(lk_mme_point_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+    LAUNCH(h, "mme_reduce", hipLaunchKernelGGL(lk_mme_reduce_kernel, dim3((unsigned int)NC), dim3(256), 0, h->stream, m));
+    std::vector<lk_mme> rec(NC);
+    HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_mme) * NC, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(a.out, rec.data(), sizeof(lk_mme) * NC);
+    return LK_OK;
+}
+
+extern "C" {
+
+int lk_clouds_mme_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, lk_mme* out, uint32_t* d_n,
+                      double* d_h, double* d_lmin) {
+    CHECK_H(h);
+    const MmeArgs a = {d_clouds, n_clouds, off, radius, min_pts, out, d_n, d_h, d_lmin};
+    size_t total = 0;
+    LKCHK(mme_check(h, "lk_clouds_mme_dev", a, 16, &total));
+    return mme_run(h, a, total);
+}
+
+int lk_clouds_mme(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, lk_mme* out, uint32_t* n, double* hh,
+                  double* lmin) {
+    CHECK_H(h);
+    MmeArgs a = {clouds, n_clouds, off, radius, min_pts, out, n, hh, lmin};
+    size_t total = 0;
+    LKCHK(mme_check(h, "lk_clouds_mme", a, 4, &total));
+    float4* dc = nullptr;
+    uint32_t* dn = nullptr;
+    double *dh = nullptr, *dl = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        dc = c.take<float4>(total + 1);   // (+ 1: an empty range still has an address of its own)
+        dn = c.take<uint32_t>(n ? total + 1 : 0), dh = c.take<double>(hh ? total + 1 : 0), dl = c.take<double>(lmin ? total + 1 : 0);
+        return c.total();
+    };
+    LKCHK(reserve(h, h->c2c_io, carve(nullptr)));
+    carve(h->c2c_io.p);
+    if (total) HIPCHK(h, hipMemcpyAsync(dc, clouds + 4 * off[0], 16 * total, hipMemcpyHostToDevice, h->stream));
+    std::vector<uint64_t> o(n_clouds + 1);
+    for (size_t c = 0; c <= n_clouds; ++c) o[c] = off[c] - off[0];
+    a.clouds = reinterpret_cast<const float*>(dc), a.off = o.data();
+    a.n = n ? dn : nullptr, a.hh = hh ? dh : nullptr, a.lmin = lmin ? dl : nullptr;
+    LKCHK(mme_run(h, a, total));
+    if (total && (n || hh || lmin)) {
+        if (n) HIPCHK(h, hipMemcpyAsync(n, dn, 4 * total, hipMemcpyDeviceToHost, h->stream));
+        if (hh) HIPCHK(h, hipMemcpyAsync(hh, dh, 8 * total, hipMemcpyDeviceToHost, h->stream));
+        if (lmin) HIPCHK(h, hipMemcpyAsync(lmin, dl, 8 * total, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return LK_OK;

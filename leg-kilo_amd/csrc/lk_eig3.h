@@ -154,3 +154,58 @@ LK_HD void lk_eig_sym3(const double* Ain, double* ev, double* V) {
     lk_eig_sym3_cols(Ain, ev, v0, v1, v2);
     for (int k = 0; k < 3; ++k) V[3 * k + 0] = v0[k], V[3 * k + 1] = v1[k], V[3 * k + 2] = v2[k];
 }
+
+// Eigenvalues only, ev[3] ascending (to rounding, as above), for callers that need no basis (lk_mme.h: the smallest eigenvalue of a point's
+// neighbourhood covariance).  The trigonometric roots alone lose half the digits when two of them nearly coincide, so they only CHOOSE: the isolated
+// eigenvalue's vector comes from lk_eig3_vec0 and gives its Rayleigh quotient; the other two are the roots of the 2 x 2 restriction of A to that
+// vector's orthogonal complement, in the closed form that does not cancel (mean -+ hypot).  Absolute error: a few ulp of the largest |eigenvalue|.
+LK_HD void lk_eig_sym3_vals(const double* Ain, double* ev) {
+    double a00 = Ain[0], a01 = Ain[1], a02 = Ain[2], a11 = Ain[3], a12 = Ain[4], a22 = Ain[5];
+    double mx = fmax(fmax(fabs(a00), fabs(a01)), fmax(fabs(a02), fabs(a11)));
+    mx = fmax(mx, fmax(fabs(a12), fabs(a22)));
+    if (!(mx > 0.0)) {
+        ev[0] = ev[1] = ev[2] = (mx == 0.0) ? 0.0 : mx;
+        return;
+    }
+    const double inv = 1.0 / mx;
+    a00 *= inv, a01 *= inv, a02 *= inv, a11 *= inv, a12 *= inv, a22 *= inv;
+    const double nrm = a01 * a01 + a02 * a02 + a12 * a12;
+    double e0, e1, e2;
+    if (nrm > 0.0) {
+        const double q = (a00 + a11 + a22) / 3.0;
+        const double b00 = a00 - q, b11 = a11 - q, b22 = a22 - q;
+        const double p = sqrt((b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * nrm) / 6.0);
+        const double c00 = b11 * b22 - a12 * a12, c01 = a01 * b22 - a12 * a02, c02 = a01 * a12 - b11 * a02;
+        const double det = (b00 * c00 - a01 * c01 + a02 * c02) / (p * p * p);
+        const double hd = fmin(fmax(0.5 * det, -1.0), 1.0);
+        const double ang = acos(hd) / 3.0;
+        const bool top = hd >= 0.0;
+        const double iso_ev = q + p * 2.0 * cos(top ? ang : ang + 2.09439510239319549);
+        double w[3];
+        lk_eig3_vec0(a00, a01, a02, a11, a12, a22, iso_ev, w);
+        double ux, uy, uz;   // orthonormal basis u, t of the complement of w (as lk_eig3_vec1 builds it)
+        if (fabs(w[0]) > fabs(w[1])) {
+            const double s = 1.0 / sqrt(w[0] * w[0] + w[2] * w[2]);
+            ux = -w[2] * s, uy = 0.0, uz = w[0] * s;
+        } else {
+            const double s = 1.0 / sqrt(w[1] * w[1] + w[2] * w[2]);
+            ux = 0.0, uy = w[2] * s, uz = -w[1] * s;
+        }
+        const double tx = w[1] * uz - w[2] * uy, ty = w[2] * ux - w[0] * uz, tz = w[0] * uy - w[1] * ux;
+        const double awx = a00 * w[0] + a01 * w[1] + a02 * w[2], awy = a01 * w[0] + a11 * w[1] + a12 * w[2], awz = a02 * w[0] + a12 * w[1] + a22 * w[2];
+        const double aux = a00 * ux + a01 * uy + a02 * uz, auy = a01 * ux + a11 * uy + a12 * uz, auz = a02 * ux + a12 * uy + a22 * uz;
+        const double atx = a00 * tx + a01 * ty + a02 * tz, aty = a01 * tx + a11 * ty + a12 * tz, atz = a02 * tx + a12 * ty + a22 * tz;
+        const double iso = w[0] * awx + w[1] * awy + w[2] * awz;
+        const double m00 = ux * aux + uy * auy + uz * auz, m01 = ux * atx + uy * aty + uz * atz, m11 = tx * atx + ty * aty + tz * atz;
+        const double mean = 0.5 * (m00 + m11), half = 0.5 * (m00 - m11), rad = sqrt(half * half + m01 * m01);
+        const double lo = mean - rad, hi = mean + rad;
+        e0 = top ? lo : iso, e1 = top ? hi : lo, e2 = top ? iso : hi;
+    } else {
+        double d0 = a00, d1 = a11, d2 = a22;
+        if (d0 > d1) { double u = d0; d0 = d1; d1 = u; }
+        if (d1 > d2) { double u = d1; d1 = d2; d2 = u; }
+        if (d0 > d1) { double u = d0; d0 = d1; d1 = u; }
+        e0 = d0, e1 = d1, e2 = d2;
+    }
+    ev[0] = e0 * mx, ev[1] = e1 * mx, ev[2] = e2 * mx;
+}

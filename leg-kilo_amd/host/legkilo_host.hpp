@@ -460,6 +460,17 @@ class KiloPath {
         if (nn_off) *nn_off = off;
         return out;
     }
+    // lk_clouds_mme_dev: map clouds scored WITHOUT a reference where they lie - mean map entropy and mean plane variance, both lower for a crisper
+    // map.  Cloud c = the 16-byte x y z w records off[c] .. off[c + 1]) at d_clouds (a replay's d_world_out, downsampleCloudsDev's output and
+    // offsets).  A point's neighbourhood is every record of its cloud within `radius`, itself included; min_pts (>= 4) of them make it dense.  One
+    // lk_mme per cloud.  d_n / d_h / d_lmin (each optional) take n_i, h_i and lmin_i per record, entry off[c] - off[0] + i.
+    std::vector<lk_mme> cloudsMmeDev(const float* d_clouds, const std::vector<uint64_t>& off, double radius, uint32_t min_pts = 5, uint32_t* d_n = nullptr,
+                                     double* d_h = nullptr, double* d_lmin = nullptr) {
+        if (off.size() < 2) throw std::runtime_error("cloudsMmeDev: the offset table is empty");
+        std::vector<lk_mme> out(off.size() - 1);
+        dev_->check(lk_clouds_mme_dev(dev_->h(), d_clouds, off.size() - 1, off.data(), radius, min_pts, out.data(), d_n, d_h, d_lmin));
+        return out;
+    }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
     // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with

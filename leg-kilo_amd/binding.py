@@ -599,31 +599,31 @@ class LegKiloHip:
         self._chk(self.L.lk_runs_bucket_poses(self.h, first_bucket, n, _p(out)))
         return out
 
+    def _traj_call(self, fn, dtype, est, est_off, gt, gt_off, tail, bit, on, flags, out=None):
+        """What the four trajectory exports share - both offset tables, the flag rule (`bit` when `on`, unless `flags` states the word itself) and
+        the records: fn(handle, n, *est, est_off, *gt, gt_off, *tail, flags, records).  Returns the n records."""
+        eo = np.ascontiguousarray(est_off, dtype=np.uint64)
+        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
+        n = max(len(eo) - 1, 0)
+        assert len(go) == len(eo)
+        res = np.zeros(max(n, 1), dtype=dtype) if out is None else out
+        fl = (bit if on else 0) if flags is None else int(flags)
+        self._chk(fn(self.h, n, *est, _p(eo), *gt, _p(go), *tail, fl, _p(res)))
+        return res[:n]
+
     def traj_ate_dev(self, d_est_t, d_est_pos, est_stride, est_off, d_gt_t, d_gt_pos, gt_stride, gt_off, max_dt, align=False, flags=None, out=None):
         """Absolute trajectory error of len(est_off) - 1 trajectories against ground truth, all in device memory (lk_traj_ate_dev): d_*_t / d_*_pos -
         device pointers to the first sample's stamp and position, sample k `stride` bytes further on; est_off / gt_off - the trajectories' sample
         ranges.  Pairs by nearest stamp within max_dt, align: the best rigid motion removed first.  Returns abi.ate_dtype() records, one per
         trajectory (out: an array of that dtype to write into instead - n_traj records of it are written)."""
-        eo = np.ascontiguousarray(est_off, dtype=np.uint64)
-        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
-        n = max(len(eo) - 1, 0)
-        assert len(go) == len(eo)
-        res = np.zeros(max(n, 1), dtype=abi.ate_dtype()) if out is None else out
-        fl = (abi.LK_ATE_ALIGN if align else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_traj_ate_dev(self.h, n, d_est_t, d_est_pos, est_stride, _p(eo), d_gt_t, d_gt_pos, gt_stride, _p(go), max_dt, fl, _p(res)))
-        return res[:n]
+        return self._traj_call(self.L.lk_traj_ate_dev, abi.ate_dtype(), (d_est_t, d_est_pos, est_stride), est_off, (d_gt_t, d_gt_pos, gt_stride), gt_off,
+                               (max_dt,), abi.LK_ATE_ALIGN, align, flags, out)
 
     def runs_ate_dev(self, run_bucket_off, d_gt_t, d_gt_pos, gt_stride, gt_off, max_dt, align=False, flags=None):
         """The same with the estimate read from the bucket table of the last _cloud run replay (lk_runs_ate_dev): run r = the records
         run_bucket_off[r] : run_bucket_off[r + 1] (scan_bucket_off[run_off]); the ground truth in device memory."""
-        ro = np.ascontiguousarray(run_bucket_off, dtype=np.uint64)
-        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
-        n = max(len(ro) - 1, 0)
-        assert len(go) == len(ro)
-        res = np.zeros(max(n, 1), dtype=abi.ate_dtype())
-        fl = (abi.LK_ATE_ALIGN if align else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_runs_ate_dev(self.h, n, _p(ro), d_gt_t, d_gt_pos, gt_stride, _p(go), max_dt, fl, _p(res)))
-        return res[:n]
+        return self._traj_call(self.L.lk_runs_ate_dev, abi.ate_dtype(), (), run_bucket_off, (d_gt_t, d_gt_pos, gt_stride), gt_off, (max_dt,),
+                               abi.LK_ATE_ALIGN, align, flags)
 
     def runs_ate(self, run_bucket_off, gt_t, gt_pos, gt_off, max_dt, align=False):
         """runs_ate_dev with the ground truth taken from the host: gt_t [m], gt_pos [m, 3] are uploaded as one packed [t x y z] table (stride 32) for
@@ -638,27 +638,14 @@ class LegKiloHip:
         with a third pointer per side, d_*_rot - the first sample's nine row-major doubles, body to world.  A step reaches from sample i to the
         first later sample at least `delta` seconds on (by_index: `delta` samples on); it is scored when both ends pair within max_dt.  Returns
         abi.rpe_dtype() records, one per trajectory (out: an array of that dtype to write into instead)."""
-        eo = np.ascontiguousarray(est_off, dtype=np.uint64)
-        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
-        n = max(len(eo) - 1, 0)
-        assert len(go) == len(eo)
-        res = np.zeros(max(n, 1), dtype=abi.rpe_dtype()) if out is None else out
-        fl = (abi.LK_RPE_INDEX if by_index else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_traj_rpe_dev(self.h, n, d_est_t, d_est_pos, d_est_rot, est_stride, _p(eo), d_gt_t, d_gt_pos, d_gt_rot, gt_stride, _p(go), max_dt,
-                                         delta, fl, _p(res)))
-        return res[:n]
+        return self._traj_call(self.L.lk_traj_rpe_dev, abi.rpe_dtype(), (d_est_t, d_est_pos, d_est_rot, est_stride), est_off,
+                               (d_gt_t, d_gt_pos, d_gt_rot, gt_stride), gt_off, (max_dt, delta), abi.LK_RPE_INDEX, by_index, flags, out)
 
     def runs_rpe_dev(self, run_bucket_off, d_gt_t, d_gt_pos, d_gt_rot, gt_stride, gt_off, max_dt, delta, by_index=False, flags=None):
         """The same with the estimate read from the bucket table of the last _cloud run replay (lk_runs_rpe_dev): run r = the records
         run_bucket_off[r] : run_bucket_off[r + 1] (scan_bucket_off[run_off]); the ground truth in device memory."""
-        ro = np.ascontiguousarray(run_bucket_off, dtype=np.uint64)
-        go = np.ascontiguousarray(gt_off, dtype=np.uint64)
-        n = max(len(ro) - 1, 0)
-        assert len(go) == len(ro)
-        res = np.zeros(max(n, 1), dtype=abi.rpe_dtype())
-        fl = (abi.LK_RPE_INDEX if by_index else 0) if flags is None else int(flags)
-        self._chk(self.L.lk_runs_rpe_dev(self.h, n, _p(ro), d_gt_t, d_gt_pos, d_gt_rot, gt_stride, _p(go), max_dt, delta, fl, _p(res)))
-        return res[:n]
+        return self._traj_call(self.L.lk_runs_rpe_dev, abi.rpe_dtype(), (), run_bucket_off, (d_gt_t, d_gt_pos, d_gt_rot, gt_stride), gt_off, (max_dt, delta),
+                               abi.LK_RPE_INDEX, by_index, flags)
 
     def _c2c_call(self, fn, query, q_off, ref, r_off, pairs, max_dist, thr, nn_idx, nn_d2, want_nn_off):
         """What the two C2C exports share - the host tables and the records: fn(handle, query, tables, ref, tables, pairs, max_dist, thr, records,
@@ -697,6 +684,15 @@ class LegKiloHip:
         res, nn_off = self._c2c_call(self.L.lk_clouds_c2c, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, _p(idx), _p(d2), True)
         return res, nn_off, idx[:total], d2[:total]
 
+    def _mme_call(self, fn, clouds, off, radius, min_pts, n_arr, h_arr, lmin_arr):
+        """What the two MME exports share - the offset table and the records: fn(handle, clouds, table, radius, min_pts, records, per-point arrays).
+        Returns the records."""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.mme_dtype())
+        self._chk(fn(self.h, clouds, n, _p(o), radius, min_pts, _p(res), n_arr, h_arr, lmin_arr))
+        return res[:n]
+
     def clouds_mme_dev(self, d_clouds, off, radius, min_pts=5, d_n=0, d_h=0, d_lmin=0):
         """Mean map entropy and mean plane variance of many clouds in device memory, no reference needed (lk_clouds_mme_dev): cloud c = the 16-byte
         x y z w records off[c] : off[c + 1] at the device pointer d_clouds (a run replay's d_world, downsample_clouds_dev's d_out with its out_off).
@@ -704,26 +700,19 @@ class LegKiloHip:
         gets lmin, and h unless its covariance is flat.  d_n / d_h / d_lmin: device pointers (0: none, each on its own) that take n_i uint32, h_i and
         lmin_i float64 per record, entry off[c] - off[0] + i.  Returns abi.mme_dtype() records, one per cloud; cloudmetrics.mme is the numpy
         statement."""
-        o = np.ascontiguousarray(off, dtype=np.uint64)
-        n = max(len(o) - 1, 0)
-        res = np.zeros(max(n, 1), dtype=abi.mme_dtype())
-        self._chk(self.L.lk_clouds_mme_dev(self.h, d_clouds, n, _p(o), radius, min_pts, _p(res), d_n or None, d_h or None, d_lmin or None))
-        return res[:n]
+        return self._mme_call(self.L.lk_clouds_mme_dev, d_clouds, off, radius, min_pts, d_n or None, d_h or None, d_lmin or None)
 
     def clouds_mme(self, clouds, off, radius, min_pts=5, want_points=False):
         """The same with the clouds in host memory (lk_clouds_mme): clouds float32 [n, 4] (x y z w records).  Returns the records, with want_points
         (records, n uint32, h float64, lmin float64), entry off[c] - off[0] + i for record off[c] + i."""
         c = np.ascontiguousarray(clouds, dtype=np.float32).reshape(-1, 4)
-        o = np.ascontiguousarray(off, dtype=np.uint64)
-        n = max(len(o) - 1, 0)
-        res = np.zeros(max(n, 1), dtype=abi.mme_dtype())
         if not want_points:
-            self._chk(self.L.lk_clouds_mme(self.h, _p(c), n, _p(o), radius, min_pts, _p(res), None, None, None))
-            return res[:n]
+            return self._mme_call(self.L.lk_clouds_mme, _p(c), off, radius, min_pts, None, None, None)
+        o = np.asarray(off, dtype=np.uint64)
         total = int(o[-1] - o[0]) if len(o) else 0
         cnt, hh, lm = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1)), np.zeros(max(total, 1))
-        self._chk(self.L.lk_clouds_mme(self.h, _p(c), n, _p(o), radius, min_pts, _p(res), _p(cnt), _p(hh), _p(lm)))
-        return res[:n], cnt[:total], hh[:total], lm[:total]
+        res = self._mme_call(self.L.lk_clouds_mme, _p(c), off, radius, min_pts, _p(cnt), _p(hh), _p(lm))
+        return res, cnt[:total], hh[:total], lm[:total]
 
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records

@@ -2,6 +2,8 @@
 // in one call (lk_c2c_kernels.h, arithmetic in lk_c2c.h) and the two C-ABI entries around it - lk_clouds_c2c_dev over clouds in HBM (a run replay's
 // d_world_out, lk_downsample_clouds_dev's d_out), lk_clouds_c2c over clouds in host memory - and, on the same search structure (c2c_index), the
 // scores that need no reference: mean map entropy and mean plane variance (lk_mme_kernels.h, arithmetic in lk_mme.h), lk_clouds_mme_dev / lk_clouds_mme.
+// What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
+// use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
 #define LK_TU_C2C 1
 #include "lk_internal.h"
@@ -26,8 +28,35 @@ struct C2cArgs {   // the arguments both entries share, as the caller gave them
     double* nn_d2;
     uint64_t* nn_off;
 };
-bool overlaps(uintptr_t a, size_t alen, uintptr_t b, size_t blen) { return alen && blen && a < b + blen && b < a + alen; }
+struct C2cSpan {   // a named range of bytes (p = 0: not given)
+    const char* name;
+    uintptr_t p;
+    size_t len;
+};
+bool overlaps(const C2cSpan& a, const C2cSpan& b) { return a.len && b.len && a.p < b.p + b.len && b.p < a.p + a.len; }
 }  // namespace
+
+// an offset table does not decrease
+static int c2c_offsets_check(lk_handle* h, const std::string& w, const char* name, const uint64_t* off, size_t n) {
+    for (size_t c = 0; c < n; ++c)
+        if (off[c + 1] < off[c]) return fail(h, LK_ERR_INVALID, w + name + " decreases at cloud " + std::to_string(c));
+    return LK_OK;
+}
+// one named output against the input ranges (reported as `in_what`), then against the outputs in `rest`
+static int c2c_overlap_check(lk_handle* h, const std::string& w, const C2cSpan& o, const C2cSpan* in, size_t n_in, const char* in_what, const C2cSpan* rest, size_t n_rest) {
+    if (!o.p) return LK_OK;
+    for (size_t k = 0; k < n_in; ++k)
+        if (overlaps(o, in[k])) return fail(h, LK_ERR_INVALID, w + o.name + " overlaps " + in_what);
+    for (size_t k = 0; k < n_rest; ++k)
+        if (rest[k].p && overlaps(o, rest[k])) return fail(h, LK_ERR_INVALID, w + o.name + " overlaps " + rest[k].name);
+    return LK_OK;
+}
+// in a carve: the caller's array, or `total` elements of our own
+template <typename T>
+static T* c2c_or_own(LkCarve& c, T* given, size_t total) {
+    T* own = c.take<T>(given ? 0 : total);
+    return given ? given : own;
+}
 
 // what both entries refuse before anything is launched; cloud_align: 16 for device clouds, 4 for host ones.  *total: query points over all pairs
 static int c2c_check(lk_handle* h, const char* who, const C2cArgs& a, unsigned int cloud_align, size_t* total) {
@@ -52,10 +81,8 @@ static int c2c_check(lk_handle* h, const char* who, const C2cArgs& a, unsigned i
     for (uint32_t k = 0; k < a.n_thr; ++k)
         if (!std::isfinite(a.thr[k]) || a.thr[k] < 0.0 || a.thr[k] > a.max_dist)
             return fail(h, LK_ERR_INVALID, w + "thr[" + std::to_string(k) + "] must be finite and in 0 .. max_dist");
-    for (size_t c = 0; c < a.n_q; ++c)
-        if (a.q_off[c + 1] < a.q_off[c]) return fail(h, LK_ERR_INVALID, w + "q_off decreases at cloud " + std::to_string(c));
-    for (size_t c = 0; c < a.n_r; ++c)
-        if (a.r_off[c + 1] < a.r_off[c]) return fail(h, LK_ERR_INVALID, w + "r_off decreases at cloud " + std::to_string(c));
+    LKCHK(c2c_offsets_check(h, w, "q_off", a.q_off, a.n_q));
+    LKCHK(c2c_offsets_check(h, w, "r_off", a.r_off, a.n_r));
     for (size_t k = 0; k < a.n_pairs; ++k) {
         if (a.pair_q[k] >= a.n_q) return fail(h, LK_ERR_INVALID, w + "pair_q[" + std::to_string(k) + "] is past the " + std::to_string(a.n_q) + " query clouds");
         if (a.pair_r[k] >= a.n_r) return fail(h, LK_ERR_INVALID, w + "pair_r[" + std::to_string(k) + "] is past the " + std::to_string(a.n_r) + " reference clouds");
@@ -71,15 +98,12 @@ static int c2c_check(lk_handle* h, const char* who, const C2cArgs& a, unsigned i
         if (sum >= (1ull << 32)) return fail(h, LK_ERR_CAPACITY, w + "the pairs' query clouds hold 2^32 records or more in all: split the call");
     }
     *total = (size_t)sum;
-    if (a.nn_idx) {
-        const uintptr_t qa = (uintptr_t)a.query + 16u * (uintptr_t)a.q_off[0], ra = (uintptr_t)a.ref + 16u * (uintptr_t)a.r_off[0];
-        const size_t ql = 16u * (size_t)(a.q_off[a.n_q] - a.q_off[0]), rl = 16u * (size_t)(a.r_off[a.n_r] - a.r_off[0]);
-        const uintptr_t ia = (uintptr_t)a.nn_idx, da = (uintptr_t)a.nn_d2;
-        if (overlaps(ia, 4 * *total, qa, ql) || overlaps(ia, 4 * *total, ra, rl)) return fail(h, LK_ERR_INVALID, w + "nn_idx overlaps an input cloud");
-        if (overlaps(da, 8 * *total, qa, ql) || overlaps(da, 8 * *total, ra, rl)) return fail(h, LK_ERR_INVALID, w + "nn_d2 overlaps an input cloud");
-        if (overlaps(ia, 4 * *total, da, 8 * *total)) return fail(h, LK_ERR_INVALID, w + "nn_idx overlaps nn_d2");
-    }
-    return LK_OK;
+    const C2cSpan in[2] = {{"query", (uintptr_t)a.query + 16u * (uintptr_t)a.q_off[0], 16u * (size_t)(a.q_off[a.n_q] - a.q_off[0])},
+                           {"ref", (uintptr_t)a.ref + 16u * (uintptr_t)a.r_off[0], 16u * (size_t)(a.r_off[a.n_r] - a.r_off[0])}};
+    const C2cSpan idx = {"nn_idx", (uintptr_t)a.nn_idx, 4 * *total}, d2 = {"nn_d2", (uintptr_t)a.nn_d2, 8 * *total};
+    LKCHK(c2c_overlap_check(h, w, idx, in, 2, "an input cloud", nullptr, 0));
+    LKCHK(c2c_overlap_check(h, w, d2, in, 2, "an input cloud", nullptr, 0));
+    return c2c_overlap_check(h, w, idx, nullptr, 0, "", &d2, 1);
 }
 
 // the clouds of one side that a pair names, in ascending order
@@ -114,7 +138,18 @@ static int c2c_sort(lk_handle* h, void* tmp, size_t& tb, const C2cIndex& x, size
     else HIPCHK(h, lk_prim_sort_pairs(tmp, tb, x.k0, x.k1, (const int*)x.v0, (int*)x.v1, N, 0, 31, h->stream));
     return LK_OK;
 }
-// 1. bounds and status of the clouds in use and every cloud's grid at edge `reach` (doubling as lk_c2c_grid says); 2. a cell key per record, a stable
+// bounds and status of one side's clouds in use (d_off64, d_used: the device copies of off and used, already on their way)
+static int c2c_bounds(lk_handle* h, const float4* pts, const uint64_t* off, size_t n, const std::vector<unsigned int>& used, const unsigned long long* d_off64,
+                      const unsigned int* d_used, double reach, int* mm, unsigned int* status) {
+    size_t big = 0;
+    for (unsigned int c : used) big = std::max(big, (size_t)(off[c + 1] - off[c]));
+    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, c2c_blocks(n), dim3(256), 0, h->stream, mm, status, (unsigned int)n));
+    if (!used.empty())
+        LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)used.size(), c2c_stride_blocks(used.size(), big)), dim3(256), 0, h->stream,
+                                                   pts, d_off64, d_used, reach, mm, status));
+    return LK_OK;
+}
+// 1. bounds and status of the clouds in use (c2c_bounds) and every cloud's grid at edge `reach` (doubling as lk_c2c_grid says); 2. a cell key per record, a stable
 // sort by key inside each cloud, the records into that order
 static int c2c_index(lk_handle* h, const float4* pts, const uint64_t* off, size_t n, const std::vector<unsigned int>& used, double reach, C2cIndex& x) {
     const size_t N = (size_t)(off[n] - off[0]);
@@ -126,15 +161,10 @@ static int c2c_index(lk_handle* h, const float4* pts, const uint64_t* off, size_
     std::vector<unsigned int>& roff = x.h_off;
     roff.resize(n + 1);
     for (size_t c = 0; c <= n; ++c) roff[c] = (unsigned int)(off[c] - off[0]);
-    size_t big = 0;
-    for (unsigned int c : used) big = std::max(big, (size_t)(off[c + 1] - off[c]));
     HIPCHK(h, hipMemcpyAsync(x.d_off64, off, 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(x.d_off, roff.data(), 4 * (n + 1), hipMemcpyHostToDevice, h->stream));
     if (!used.empty()) HIPCHK(h, hipMemcpyAsync(x.d_used, used.data(), 4 * used.size(), hipMemcpyHostToDevice, h->stream));
-    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, c2c_blocks(n), dim3(256), 0, h->stream, x.mm, x.status, (unsigned int)n));
-    if (!used.empty())
-        LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)used.size(), c2c_stride_blocks(used.size(), big)), dim3(256), 0, h->stream,
-                                                   pts, x.d_off64, x.d_used, reach, x.mm, x.status));
+    LKCHK(c2c_bounds(h, pts, off, n, used, x.d_off64, x.d_used, reach, x.mm, x.status));
     LAUNCH(h, "c2c_grid", hipLaunchKernelGGL(lk_c2c_grid_kernel, c2c_blocks(n), dim3(256), 0, h->stream, x.mm, x.status, reach, (unsigned int)n, x.grid));
     if (N) {
         const float4* first = pts + off[0];
@@ -155,9 +185,8 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     LkC2cQuery q = {};
     C2cIndex x = {};
     unsigned long long *d_qoff = nullptr, *d_nnoff = nullptr;
-    unsigned int *d_pq = nullptr, *d_pr = nullptr, *d_uq = nullptr, *q_status = nullptr, *own_idx = nullptr;
+    unsigned int *d_pq = nullptr, *d_pr = nullptr, *d_uq = nullptr, *q_status = nullptr;
     int* q_mm = nullptr;
-    double* own_d2 = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base, 256);
         d_qoff = c.take<unsigned long long>(NQ + 1), x.d_off64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
@@ -168,7 +197,7 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
         x.grid = c.take<LkC2cGrid>(NR);
         x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
         x.recs = c.take<LkC2cRec>(N);
-        own_idx = c.take<unsigned int>(a.nn_idx ? 0 : total), own_d2 = c.take<double>(a.nn_idx ? 0 : total);
+        q.nn_idx = c2c_or_own(c, a.nn_idx, total), q.nn_d2 = c2c_or_own(c, a.nn_d2, total);   // (c2c_check: both or neither)
         q.out = c.take<lk_c2c>(P);
         return c.total();
     };
@@ -177,9 +206,7 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     carve(h->c2c.p);
     // the host tables of the query side and of the pairs
     std::vector<unsigned long long> nnoff(P + 1, 0ull);
-    size_t big_q = 0;
     for (size_t k = 0; k < P; ++k) nnoff[k + 1] = nnoff[k] + (a.q_off[a.pair_q[k] + 1] - a.q_off[a.pair_q[k]]);
-    for (unsigned int c : uq) big_q = std::max(big_q, (size_t)(a.q_off[c + 1] - a.q_off[c]));
     HIPCHK(h, hipMemcpyAsync(d_qoff, a.q_off, 8 * (NQ + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_nnoff, nnoff.data(), 8 * (P + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_pq, a.pair_q, 4 * P, hipMemcpyHostToDevice, h->stream));
@@ -187,23 +214,16 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     HIPCHK(h, hipMemcpyAsync(d_uq, uq.data(), 4 * uq.size(), hipMemcpyHostToDevice, h->stream));
     const float4* qpts = reinterpret_cast<const float4*>(a.query);
     const float4* rpts = reinterpret_cast<const float4*>(a.ref);
-    auto blocks = c2c_blocks;
     // bounds and status of the query clouds in use; steps 1 and 2 for the reference side
-    LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, blocks(NQ), dim3(256), 0, h->stream, q_mm, q_status, (unsigned int)NQ));
-    LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)uq.size(), c2c_stride_blocks(uq.size(), big_q)), dim3(256), 0, h->stream, qpts,
-                                               d_qoff, d_uq, a.max_dist, q_mm, q_status));
+    LKCHK(c2c_bounds(h, qpts, a.q_off, NQ, uq, d_qoff, d_uq, a.max_dist, q_mm, q_status));
     LKCHK(c2c_index(h, rpts, a.r_off, NR, ur, a.max_dist, x));
-    unsigned int *d_roff = x.d_off, *r_status = x.status, *k1 = x.k1;
-    LkC2cGrid* grid = x.grid;
-    LkC2cRec* recs = x.recs;
     // 3. (j, d2) per pair and query point, one record per pair
-    q.q_pts = qpts, q.q_off = d_qoff, q.r_off = d_roff, q.pair_q = d_pq, q.pair_r = d_pr, q.nn_off = d_nnoff;
-    q.q_status = q_status, q.r_status = r_status, q.grid = grid, q.keys = k1, q.recs = recs;
-    q.nn_idx = a.nn_idx ? a.nn_idx : own_idx, q.nn_d2 = a.nn_idx ? a.nn_d2 : own_d2;
+    q.q_pts = qpts, q.q_off = d_qoff, q.r_off = x.d_off, q.pair_q = d_pq, q.pair_r = d_pr, q.nn_off = d_nnoff;
+    q.q_status = q_status, q.r_status = x.status, q.grid = x.grid, q.keys = x.k1, q.recs = x.recs;
     q.reach2 = lk_c2c_reach2(a.max_dist);
     for (uint32_t k = 0; k < 4; ++k) q.thr2[k] = k < a.n_thr ? a.thr[k] * a.thr[k] : 0.0;
     q.n_pairs = (unsigned int)P, q.n_thr = a.n_thr;
-    if (total) LAUNCH(h, "c2c_query", hipLaunchKernelGGL(lk_c2c_query_kernel, blocks(total), dim3(256), 0, h->stream, q, (unsigned long long)total));
+    if (total) LAUNCH(h, "c2c_query", hipLaunchKernelGGL(lk_c2c_query_kernel, c2c_blocks(total), dim3(256), 0, h->stream, q, (unsigned long long)total));
     LAUNCH(h, "c2c_reduce", hipLaunchKernelGGL(lk_c2c_reduce_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, q));
     std::vector<lk_c2c> rec(P);
     HIPCHK(h, hipMemcpyAsync(rec.data(), q.out, sizeof(lk_c2c) * P, hipMemcpyDeviceToHost, h->stream));
@@ -213,6 +233,44 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
         for (size_t k = 0; k <= P; ++k) a.nn_off[k] = nnoff[k];
     return LK_OK;
 }
+
+// The host entries' trip through c2c_io: every range of host records and every host per-point array that was asked for gets a device twin (+ 1 element:
+// an empty one still has an address of its own); the records go up, their offsets are rebased to each range's first record; after the run fetch()
+// copies the arrays back and synchronises once
+namespace {
+struct C2cStage {
+    struct In { const float* host; const uint64_t* off; size_t n_clouds; float4* dev; std::vector<uint64_t> rel; };   // rel = off - off[0]
+    struct Out { void* host; size_t elem, count; void* dev; };                                                        // host null: not asked for, dev null
+    std::vector<In> in;
+    std::vector<Out> out;
+    int upload(lk_handle* h) {
+        auto carve = [&](void* base) {
+            LkCarve c(base, 256);
+            for (In& i : in) i.dev = c.take<float4>((size_t)(i.off[i.n_clouds] - i.off[0]) + 1);
+            for (Out& o : out) o.dev = o.host ? c.take<unsigned char>(o.elem * (o.count + 1)) : nullptr;
+            return c.total();
+        };
+        LKCHK(reserve(h, h->c2c_io, carve(nullptr)));
+        carve(h->c2c_io.p);
+        for (In& i : in) {
+            const size_t n = (size_t)(i.off[i.n_clouds] - i.off[0]);
+            if (n) HIPCHK(h, hipMemcpyAsync(i.dev, i.host + 4 * i.off[0], 16 * n, hipMemcpyHostToDevice, h->stream));
+            for (size_t c = 0; c <= i.n_clouds; ++c) i.rel.push_back(i.off[c] - i.off[0]);
+        }
+        return LK_OK;
+    }
+    int fetch(lk_handle* h) {
+        bool any = false;
+        for (const Out& o : out) {
+            if (!o.host || !o.count) continue;
+            HIPCHK(h, hipMemcpyAsync(o.host, o.dev, o.elem * o.count, hipMemcpyDeviceToHost, h->stream));
+            any = true;
+        }
+        if (any) HIPCHK(h, hipStreamSynchronize(h->stream));
+        return LK_OK;
+    }
+};
+}  // namespace
 
 extern "C" {
 
@@ -233,33 +291,15 @@ int lk_clouds_c2c(lk_handle* h, const float* query, size_t n_qclouds, const uint
     C2cArgs a = {query, ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, out, nn_idx, nn_d2, nn_off};
     size_t total = 0;
     LKCHK(c2c_check(h, "lk_clouds_c2c", a, 4, &total));
-    // device copies of the two ranges and of the nn arrays; the offsets counted from each side's first record
-    const size_t nq = (size_t)(q_off[n_qclouds] - q_off[0]), nr = (size_t)(r_off[n_rclouds] - r_off[0]);
-    float4 *dq = nullptr, *dr = nullptr;
-    uint32_t* di = nullptr;
-    double* dd = nullptr;
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        dq = c.take<float4>(nq + 1), dr = c.take<float4>(nr + 1);   // (+ 1: an empty side still has an address of its own)
-        di = c.take<uint32_t>(nn_idx ? total + 1 : 0), dd = c.take<double>(nn_idx ? total + 1 : 0);
-        return c.total();
-    };
-    LKCHK(reserve(h, h->c2c_io, carve(nullptr)));
-    carve(h->c2c_io.p);
-    if (nq) HIPCHK(h, hipMemcpyAsync(dq, query + 4 * q_off[0], 16 * nq, hipMemcpyHostToDevice, h->stream));
-    if (nr) HIPCHK(h, hipMemcpyAsync(dr, ref + 4 * r_off[0], 16 * nr, hipMemcpyHostToDevice, h->stream));
-    std::vector<uint64_t> qo(n_qclouds + 1), ro(n_rclouds + 1);
-    for (size_t c = 0; c <= n_qclouds; ++c) qo[c] = q_off[c] - q_off[0];
-    for (size_t c = 0; c <= n_rclouds; ++c) ro[c] = r_off[c] - r_off[0];
-    a.query = reinterpret_cast<const float*>(dq), a.ref = reinterpret_cast<const float*>(dr), a.q_off = qo.data(), a.r_off = ro.data();
-    a.nn_idx = nn_idx ? di : nullptr, a.nn_d2 = nn_idx ? dd : nullptr;
+    C2cStage st;
+    st.in = {{query, q_off, n_qclouds}, {ref, r_off, n_rclouds}};
+    st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
+    LKCHK(st.upload(h));
+    a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
+    a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
+    a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
     LKCHK(c2c_run(h, a, total));
-    if (nn_idx && total) {
-        HIPCHK(h, hipMemcpyAsync(nn_idx, di, 4 * total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(nn_d2, dd, 8 * total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return LK_OK;
+    return st.fetch(h);
 }
 
 }  // extern "C"
@@ -290,24 +330,15 @@ static int mme_check(lk_handle* h, const char* who, const MmeArgs& a, unsigned i
     if ((uintptr_t)a.lmin & 7) return fail(h, LK_ERR_INVALID, w + "lmin must be 8-byte aligned");
     if (!std::isfinite(a.radius) || !(a.radius > 0.0)) return fail(h, LK_ERR_INVALID, w + "radius must be finite and above 0");
     if (a.min_pts < 4) return fail(h, LK_ERR_INVALID, w + "min_pts is " + std::to_string(a.min_pts) + ": at least 4 (below four points det is 0 by rank)");
-    for (size_t c = 0; c < a.n_clouds; ++c)
-        if (a.off[c + 1] < a.off[c]) return fail(h, LK_ERR_INVALID, w + "off decreases at cloud " + std::to_string(c));
+    LKCHK(c2c_offsets_check(h, w, "off", a.off, a.n_clouds));
     if (a.n_clouds >= 0x7fffffffull) return fail(h, LK_ERR_CAPACITY, w + "2^31 - 1 clouds or more");
     if (a.off[a.n_clouds] - a.off[0] >= (1ull << 31)) return fail(h, LK_ERR_CAPACITY, w + "the clouds hold 2^31 records or more in all: split the call");
     for (size_t c = 0; c < a.n_clouds; ++c)   // (cannot happen under the bound above; the header states both)
         if (a.off[c + 1] - a.off[c] >= 0xffffffffull) return fail(h, LK_ERR_CAPACITY, w + "cloud " + std::to_string(c) + " holds 2^32 - 1 records or more");
     *total = (size_t)(a.off[a.n_clouds] - a.off[0]);
-    const uintptr_t ca = (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0];
-    const size_t cl = 16u * *total;
-    const uintptr_t p[3] = {(uintptr_t)a.n, (uintptr_t)a.hh, (uintptr_t)a.lmin};
-    const size_t len[3] = {4 * *total, 8 * *total, 8 * *total};
-    const char* name[3] = {"n", "h", "lmin"};
-    for (int i = 0; i < 3; ++i) {
-        if (!p[i]) continue;
-        if (overlaps(p[i], len[i], ca, cl)) return fail(h, LK_ERR_INVALID, w + name[i] + " overlaps the input clouds");
-        for (int j = i + 1; j < 3; ++j)
-            if (p[j] && overlaps(p[i], len[i], p[j], len[j])) return fail(h, LK_ERR_INVALID, w + name[i] + " overlaps " + name[j]);
-    }
+    const C2cSpan in = {"clouds", (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0], 16u * *total};
+    const C2cSpan o[3] = {{"n", (uintptr_t)a.n, 4 * *total}, {"h", (uintptr_t)a.hh, 8 * *total}, {"lmin", (uintptr_t)a.lmin, 8 * *total}};
+    for (int i = 0; i < 3; ++i) LKCHK(c2c_overlap_check(h, w, o[i], &in, 1, "the input clouds", o + i + 1, 2 - i));
     return LK_OK;
 }
 
@@ -319,15 +350,13 @@ static int mme_run(lk_handle* h, const MmeArgs& a, size_t N) {
         if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
     C2cIndex x = {};
     LkMmeCall m = {};
-    unsigned int* own_n = nullptr;
-    double *own_h = nullptr, *own_l = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base, 256);
         x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
         x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
         x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
         x.recs = c.take<LkC2cRec>(N);
-        own_n = c.take<unsigned int>(a.n ? 0 : N), own_h = c.take<double>(a.hh ? 0 : N), own_l = c.take<double>(a.lmin ? 0 : N);
+        m.n = c2c_or_own(c, a.n, N), m.h = c2c_or_own(c, a.hh, N), m.lmin = c2c_or_own(c, a.lmin, N);
         m.out = c.take<lk_mme>(NC);
         return c.total();
     };
@@ -336,7 +365,6 @@ static int mme_run(lk_handle* h, const MmeArgs& a, size_t N) {
     carve(h->c2c.p);
     LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.radius, x));
     m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
-    m.n = a.n ? a.n : own_n, m.h = a.hh ? a.hh : own_h, m.lmin = a.lmin ? a.lmin : own_l;
     m.reach2 = lk_c2c_reach2(a.radius);
     m.n_clouds = (unsigned int)NC, m.min_pts = a.min_pts, m.total = (unsigned int)N;
     if (N) LAUNCH(h, "mme_point", hipLaunchKernelGGL(lk_mme_point_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
@@ -365,30 +393,14 @@ int lk_clouds_mme(lk_handle* h, const float* clouds, size_t n_clouds, const uint
     MmeArgs a = {clouds, n_clouds, off, radius, min_pts, out, n, hh, lmin};
     size_t total = 0;
     LKCHK(mme_check(h, "lk_clouds_mme", a, 4, &total));
-    float4* dc = nullptr;
-    uint32_t* dn = nullptr;
-    double *dh = nullptr, *dl = nullptr;
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        dc = c.take<float4>(total + 1);   // (+ 1: an empty range still has an address of its own)
-        dn = c.take<uint32_t>(n ? total + 1 : 0), dh = c.take<double>(hh ? total + 1 : 0), dl = c.take<double>(lmin ? total + 1 : 0);
-        return c.total();
-    };
-    LKCHK(reserve(h, h->c2c_io, carve(nullptr)));
-    carve(h->c2c_io.p);
-    if (total) HIPCHK(h, hipMemcpyAsync(dc, clouds + 4 * off[0], 16 * total, hipMemcpyHostToDevice, h->stream));
-    std::vector<uint64_t> o(n_clouds + 1);
-    for (size_t c = 0; c <= n_clouds; ++c) o[c] = off[c] - off[0];
-    a.clouds = reinterpret_cast<const float*>(dc), a.off = o.data();
-    a.n = n ? dn : nullptr, a.hh = hh ? dh : nullptr, a.lmin = lmin ? dl : nullptr;
+    C2cStage st;
+    st.in = {{clouds, off, n_clouds}};
+    st.out = {{n, 4, total}, {hh, 8, total}, {lmin, 8, total}};
+    LKCHK(st.upload(h));
+    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
+    a.n = static_cast<uint32_t*>(st.out[0].dev), a.hh = static_cast<double*>(st.out[1].dev), a.lmin = static_cast<double*>(st.out[2].dev);
     LKCHK(mme_run(h, a, total));
-    if (total && (n || hh || lmin)) {
-        if (n) HIPCHK(h, hipMemcpyAsync(n, dn, 4 * total, hipMemcpyDeviceToHost, h->stream));
-        if (hh) HIPCHK(h, hipMemcpyAsync(hh, dh, 8 * total, hipMemcpyDeviceToHost, h->stream));
-        if (lmin) HIPCHK(h, hipMemcpyAsync(lmin, dl, 8 * total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return LK_OK;
+    return st.fetch(h);
 }
 
 }  // extern "C"

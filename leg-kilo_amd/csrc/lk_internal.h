@@ -2,7 +2,7 @@
 // headers.  The library is nine units compiled side by side - legkilo_hip.hip (LK_TU_MAIN: the C-ABI but for the overlay entries, and every
 // kernel but the overlay's and the stream path's own), lk_stream.hip (LK_TU_STREAM: one live scan after the other with the map insert - the per-bucket
 // launches, the scan-resident / grid-resident / pipelined kernels, and the KILO-path entries, which all run a scan through run_one_scan: one choice of its kernel), lk_overlay.hip (LK_TU_OVERLAY: batch replay
-// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them, lk_overlay_commit among them: its compaction steps, MapCompact below, are the main unit's), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_ovrun.hip (the same file's run-resident instantiations), lk_kin.hip (LK_TU_KIN: the message front ends - HighState decode + contact detector, lk_kin_kernels.h; sensor_msgs/Imu decode, lk_imu_kernels.h; the scan split of either - and their entries), lk_traj.hip (LK_TU_TRAJ: trajectory error against ground truth, lk_traj_kernels.h, and its two entries), lk_c2c.hip (LK_TU_C2C: the map-cloud scores - cloud-to-cloud distance, lk_c2c_kernels.h, and map entropy / plane variance, lk_mme_kernels.h, both compiled in that unit only - and their four entries), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
+// WITH insert - lk_overlay_kernels.h's kernels and the entries that launch them, lk_overlay_commit among them: its compaction steps, MapCompact below, are the main unit's), lk_ovscan.hip (LK_TU_OVSCAN: that replay's scan-resident kernel for small buckets), lk_ovrun.hip (the same file's run-resident instantiations), lk_kin.hip (LK_TU_KIN: the message front ends - HighState decode + contact detector, lk_kin_kernels.h; sensor_msgs/Imu decode, lk_imu_kernels.h; the scan split of either - and their entries), lk_traj.hip (LK_TU_TRAJ: trajectory error against ground truth, absolute and relative, lk_traj_kernels.h, and its four entries behind one host path), lk_c2c.hip (LK_TU_C2C: the map-cloud scores - cloud-to-cloud distance, lk_c2c_kernels.h, and map entropy / plane variance, lk_mme_kernels.h, both compiled in that unit only - and their four entries, the host ones through one staging helper), lk_prim.hip (rocPRIM).  A non-template kernel of a shared header is DEFINED in the main unit; the overlay unit sees its prototype
 // (LK_KERNELS_ELSEWHERE) and launches it through the main unit's host stub.  The overlay header's own kernels are compiled in the overlay unit only.
 #pragma once
 #if !defined(LK_TU_MAIN) && !defined(LK_TU_OVERLAY) && !defined(LK_TU_STREAM) && !defined(LK_TU_OVSCAN) && !defined(LK_TU_KIN) && !defined(LK_TU_TRAJ) && !defined(LK_TU_C2C)

@@ -5,7 +5,7 @@
 // One workgroup of one wave per trajectory; lane l owns the estimate samples l, l + 64, l + 128, ... in every pass, so a sum is the lanes' partial
 // sums (each in ascending sample order) added by wave_sum / wave_sum_n: an order that depends on the trajectory's own samples alone - not on n_traj,
 // not on where the trajectory stands in the call.  The passes of one launch:
-//   stamps     both sides finite and not decreasing, else the trajectory is reported through LkTraj::bad and left out;
+//   stamps     both sides finite and not decreasing, else the trajectory is reported through LkTrajTab::bad and left out;
 //   pair       partner j(i) = the ground-truth sample that minimises fabs(t_est[i] - t_gt[j]), the earliest on equal distance (a lower bound over the
 //              sorted stamps, the two neighbours compared, then the first sample that is as close as the winner); kept when that distance is
 //              <= max_dt; the partner index goes to scratch (4 bytes per sample, re-read by the lane that wrote it), the later passes do not search again;
@@ -20,15 +20,18 @@
 
 #define LK_TRAJ_NONE 0xffffffffu   // partner word of an estimate sample without a pair
 
-struct LkTraj {
+struct LkTrajTab {   // what both kernels read the same way (LkTraj, LkTrajRpe: this and their own members)
     const unsigned char *est_t, *est_p, *gt_t, *gt_p;   // first sample's stamp / position of either side
     unsigned long long est_stride, gt_stride;           // bytes from sample to sample
     const unsigned long long *est_off, *gt_off;         // [n_traj + 1] sample ranges (device copies of the caller's tables)
     unsigned long long part_base;                       // est_off[0]: partner[] starts at the call's first estimate sample
     unsigned int* partner;                              // [est_off[n_traj] - est_off[0]]
-    lk_ate* out;                                        // [n_traj]
     unsigned int* bad;                                  // min over the refused trajectories of 2 r + side (0 estimate, 1 ground truth); 0xffffffff: none
     double max_dt;
+};
+struct LkTraj {
+    LkTrajTab t;
+    lk_ate* out;   // [n_traj]
     unsigned int flags;
 };
 
@@ -48,6 +51,13 @@ __device__ __forceinline__ unsigned long long traj_wave_min_u64(unsigned long lo
     }
     return v;
 }
+__device__ __forceinline__ double traj_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, LK_WAVE));
+    return v;
+}
+// the first index that holds the wave's maximum: v, i - the lane's own maximum and its first index (~0: none), wmax - traj_wave_max(v)
+__device__ __forceinline__ unsigned long long traj_wave_first_max(double v, double wmax, unsigned long long i) { return traj_wave_min_u64(v == wmax ? i : ~0ull); }
 __device__ __forceinline__ bool traj_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
 
 // stamps of one side: finite and not decreasing (whole wave; the answer is uniform)
@@ -96,6 +106,32 @@ __device__ __forceinline__ unsigned long long traj_partner(const unsigned char* 
     return lo;
 }
 
+// ---- the prologue both kernels share
+struct LkTrajRange {   // trajectory r of a call: its sample counts and strides, its first sample on either side, its partner words
+    unsigned long long e0, ne, g0, ng, se, sg;
+    const unsigned char *et, *ep, *gt, *gp;
+    unsigned int* part;
+};
+__device__ __forceinline__ LkTrajRange traj_range(const LkTrajTab& t, unsigned int r) {
+    const unsigned long long e0 = t.est_off[r], g0 = t.gt_off[r], se = t.est_stride, sg = t.gt_stride;
+    return {e0, t.est_off[r + 1] - e0, g0, t.gt_off[r + 1] - g0, se, sg, t.est_t + e0 * se, t.est_p + e0 * se, t.gt_t + g0 * sg, t.gt_p + g0 * sg,
+            t.partner + (e0 - t.part_base)};
+}
+// the stamps pass; false (uniform): refused through LkTrajTab::bad - the caller writes its empty record from lane 0 and leaves
+__device__ __forceinline__ bool traj_stamps(const LkTrajTab& t, const LkTrajRange& v, unsigned int r, int lane) {
+    const bool ok_e = traj_stamps_ok(v.et, v.se, v.ne, lane), ok_g = traj_stamps_ok(v.gt, v.sg, v.ng, lane);
+    if (ok_e && ok_g) return true;
+    if (lane == 0) atomicMin(t.bad, 2u * r + (ok_e ? 1u : 0u));
+    return false;
+}
+// the partner word of estimate sample i: traj_partner, kept when it lies within max_dt
+__device__ __forceinline__ unsigned int traj_partner_word(const LkTrajRange& v, double max_dt, unsigned long long i) {
+    if (!v.ng) return LK_TRAJ_NONE;
+    double d;
+    const unsigned long long j = traj_partner(v.gt, v.sg, v.ng, traj_ld(v.et, v.se, i), &d);
+    return d <= max_dt ? (unsigned int)j : LK_TRAJ_NONE;
+}
+
 __device__ __forceinline__ void traj_write(lk_ate* o, double rmse, double mean, double mx, const double* R, const double* tr, unsigned long long n_pairs,
                                            unsigned int worst, unsigned int status) {
     o->rmse = rmse, o->mean = mean, o->max = mx;
@@ -109,20 +145,16 @@ __device__ __forceinline__ void traj_write(lk_ate* o, double rmse, double mean, 
 __global__ void __launch_bounds__(LK_WAVE) lk_traj_ate_kernel(LkTraj a) {
     const unsigned int r = blockIdx.x;
     const int lane = threadIdx.x;
-    const unsigned long long e0 = a.est_off[r], ne = a.est_off[r + 1] - e0, g0 = a.gt_off[r], ng = a.gt_off[r + 1] - g0;
-    const unsigned long long se = a.est_stride, sg = a.gt_stride;
-    const unsigned char *et = a.est_t + e0 * se, *ep = a.est_p + e0 * se, *gt = a.gt_t + g0 * sg, *gp = a.gt_p + g0 * sg;
-    unsigned int* part = a.partner + (e0 - a.part_base);
+    const LkTrajRange v = traj_range(a.t, r);
+    const unsigned long long ne = v.ne, se = v.se, sg = v.sg;
+    const unsigned char *ep = v.ep, *gp = v.gp;
+    unsigned int* part = v.part;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, tr[3] = {0.0, 0.0, 0.0};
 
     // ---- stamps
-    const bool ok_e = traj_stamps_ok(et, se, ne, lane), ok_g = traj_stamps_ok(gt, sg, ng, lane);
-    if (!ok_e || !ok_g) {
-        if (lane == 0) {
-            atomicMin(a.bad, 2u * r + (ok_e ? 1u : 0u));
-            traj_write(&a.out[r], nan, nan, nan, R, tr, 0, 0, 0);
-        }
+    if (!traj_stamps(a.t, v, r, lane)) {
+        if (lane == 0) traj_write(&a.out[r], nan, nan, nan, R, tr, 0, 0, 0);
         return;
     }
 
@@ -131,12 +163,7 @@ __global__ void __launch_bounds__(LK_WAVE) lk_traj_ate_kernel(LkTraj a) {
     bool nonfinite = false;
     double fg[3] = {0.0, 0.0, 0.0}, fp[3] = {0.0, 0.0, 0.0};
     for (unsigned long long i = lane; i < ne; i += LK_WAVE) {
-        unsigned int w = LK_TRAJ_NONE;
-        if (ng) {
-            double d;
-            const unsigned long long j = traj_partner(gt, sg, ng, traj_ld(et, se, i), &d);
-            if (d <= a.max_dt) w = (unsigned int)j;
-        }
+        const unsigned int w = traj_partner_word(v, a.t.max_dt, i);
         part[i] = w;
         if (w != LK_TRAJ_NONE) {
             double g[3], p[3];
@@ -212,10 +239,8 @@ __global__ void __launch_bounds__(LK_WAVE) lk_traj_ate_kernel(LkTraj a) {
         if (e > emax) emax = e, imax = i;   // (ascending i: the lane's first of equal maxima)
     }
     s2 = wave_sum(s2), s1 = wave_sum(s1);
-    double wmax = emax;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wmax = fmax(wmax, __shfl_xor(wmax, o, LK_WAVE));
-    const unsigned long long worst = traj_wave_min_u64(emax == wmax ? imax : ~0ull);
+    const double wmax = traj_wave_max(emax);
+    const unsigned long long worst = traj_wave_first_max(emax, wmax, imax);
     if (lane == 0) traj_write(&a.out[r], sqrt(s2 * inv_n), s1 * inv_n, wmax, R, tr, n_pairs, (unsigned int)worst, 0);
 }
 
@@ -228,17 +253,13 @@ __global__ void __launch_bounds__(LK_WAVE) lk_traj_ate_kernel(LkTraj a) {
 //   terms      k(i): in seconds mode the first sample behind i with t_est[k] >= t_est[i] + delta (traj_lower_bound over the samples behind i - never i
 //              itself or an earlier equal stamp), in index mode i + step; a term when i and k both have partners.  The estimate's two poses are
 //              loaded and reduced to their motion (12 doubles) before the ground truth's two are loaded: at most two poses are live beside a motion;
-//   combine    wave_sum of the lanes' sums (each in ascending i), the maxima by shuffles, the worst index by traj_wave_min_u64 over the lanes that hold
-//              the maximum - the ATE kernel's idiom, once per figure.
+//   combine    wave_sum of the lanes' sums (each in ascending i), the maxima by shuffles, the worst index by traj_wave_first_max - the ATE kernel's idiom, once
+//              per figure.
 struct LkTrajRpe {
-    const unsigned char *est_t, *est_p, *est_r, *gt_t, *gt_p, *gt_r;   // first sample's stamp / position / rotation of either side
-    unsigned long long est_stride, gt_stride;
-    const unsigned long long *est_off, *gt_off;
-    unsigned long long part_base;
-    unsigned int* partner;
-    lk_rpe* out;
-    unsigned int* bad;
-    double max_dt, delta;
+    LkTrajTab t;
+    const unsigned char *est_r, *gt_r;   // first sample's rotation of either side
+    lk_rpe* out;                         // [n_traj]
+    double delta;
     unsigned long long step;   // LK_RPE_INDEX: (uint64)delta
     unsigned int flags;
 };
@@ -261,42 +282,26 @@ __device__ __forceinline__ bool traj_ld_pose(const unsigned char* p, const unsig
     return fin;
 }
 
-__device__ __forceinline__ double traj_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, LK_WAVE));
-    return v;
-}
-
 __global__ void __launch_bounds__(LK_WAVE) lk_traj_rpe_kernel(LkTrajRpe a) {
     const unsigned int r = blockIdx.x;
     const int lane = threadIdx.x;
-    const unsigned long long e0 = a.est_off[r], ne = a.est_off[r + 1] - e0, g0 = a.gt_off[r], ng = a.gt_off[r + 1] - g0;
-    const unsigned long long se = a.est_stride, sg = a.gt_stride;
-    const unsigned char *et = a.est_t + e0 * se, *ep = a.est_p + e0 * se, *er = a.est_r + e0 * se;
-    const unsigned char *gt = a.gt_t + g0 * sg, *gp = a.gt_p + g0 * sg, *gr = a.gt_r + g0 * sg;
-    unsigned int* part = a.partner + (e0 - a.part_base);
+    const LkTrajRange v = traj_range(a.t, r);
+    const unsigned long long ne = v.ne, se = v.se, sg = v.sg;
+    const unsigned char *et = v.et, *ep = v.ep, *er = a.est_r + v.e0 * se, *gp = v.gp, *gr = a.gt_r + v.g0 * sg;
+    unsigned int* part = v.part;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     double fig[6] = {nan, nan, nan, nan, nan, nan};
 
     // ---- stamps
-    const bool ok_e = traj_stamps_ok(et, se, ne, lane), ok_g = traj_stamps_ok(gt, sg, ng, lane);
-    if (!ok_e || !ok_g) {
-        if (lane == 0) {
-            atomicMin(a.bad, 2u * r + (ok_e ? 1u : 0u));
-            traj_rpe_write(&a.out[r], fig, 0, 0, 0, 0, 0);
-        }
+    if (!traj_stamps(a.t, v, r, lane)) {
+        if (lane == 0) traj_rpe_write(&a.out[r], fig, 0, 0, 0, 0, 0);
         return;
     }
 
     // ---- pair
     unsigned long long cnt = 0;
     for (unsigned long long i = lane; i < ne; i += LK_WAVE) {
-        unsigned int w = LK_TRAJ_NONE;
-        if (ng) {
-            double d;
-            const unsigned long long j = traj_partner(gt, sg, ng, traj_ld(et, se, i), &d);
-            if (d <= a.max_dt) w = (unsigned int)j;
-        }
+        const unsigned int w = traj_partner_word(v, a.t.max_dt, i);
         part[i] = w;
         cnt += w != LK_TRAJ_NONE;
     }
@@ -354,7 +359,7 @@ __global__ void __launch_bounds__(LK_WAVE) lk_traj_rpe_kernel(LkTrajRpe a) {
     const double inv_n = 1.0 / (double)n_terms;
     t2 = wave_sum(t2), t1 = wave_sum(t1), r2 = wave_sum(r2), r1 = wave_sum(r1);
     const double wt = traj_wave_max(tmax), wr = traj_wave_max(rmax);
-    const unsigned long long worst_t = traj_wave_min_u64(tmax == wt ? imax_t : ~0ull), worst_r = traj_wave_min_u64(rmax == wr ? imax_r : ~0ull);
+    const unsigned long long worst_t = traj_wave_first_max(tmax, wt, imax_t), worst_r = traj_wave_first_max(rmax, wr, imax_r);
     fig[0] = sqrt(t2 * inv_n), fig[1] = t1 * inv_n, fig[2] = wt;
     fig[3] = sqrt(r2 * inv_n), fig[4] = r1 * inv_n, fig[5] = wr;
     if (lane == 0) traj_rpe_write(&a.out[r], fig, n_terms, n_pairs, (unsigned int)worst_t, (unsigned int)worst_r, 0);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Measurement on one MI355X, everything through the C-ABI: what scoring map clouds against a reference cloud costs (lk_clouds_c2c_dev), on the
-workload of tools/map_clouds.py - R runs of K consecutive config-1 scans replayed on the frozen map with d_world_out, cut into one file per run and
-downsampled (lk_downsample_clouds_dev); its d_out / out_off are the map clouds and stay in HBM.  The reference cloud ("survey") is the union of the
+workload of tools/runs_workload.py as tools/map_clouds.py uses it - R runs of K consecutive config-1 scans replayed on the frozen map with
+d_world_out, cut into one file per run and downsampled (lk_downsample_clouds_dev); its d_out / out_off are the map clouds and stay in HBM.  The reference cloud ("survey") is the union of the
 first --ref-files map clouds downsampled once more as one file.  Forms, at every max_dist of --max-dist:
   accuracy      pairs (f, 0): every map cloud as query against the survey;
   completeness  pairs (0, f): the survey as query against every map cloud (the sides exchanged: R search structures, one segment each).
@@ -13,100 +13,37 @@ imports (a tree per reference cloud, wall clock, over the first --host-files fil
 same way; the matched counts of those files are compared with the device's and the largest difference is recorded.
 The run replay and lk_downsample_clouds_dev are timed before and after the C2C calls (tools/runs_cloud.py's and tools/map_clouds.py's figures).
 Usage: map_c2c.py [--runs R] [--scans K] [--distinct D] [--leaf M] [--max-dist LIST] [--ref-files F] [--reps N] [--warmup W] [--host-files F] [--commit TEXT] [--json PATH]"""
-import argparse
-import ctypes as C
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))    # scenes.py: the synthetic room / trajectory / first-frame helpers the tests use
-import lk_pkg  # noqa: E402
-
-lk_pkg.load()
-import scenes  # noqa: E402
-from legkilo_amd import binding, cloudmetrics, synth  # noqa: E402
+import runs_workload as rw
+from runs_workload import binding, both, stats
+from legkilo_amd import cloudmetrics  # noqa: E402
 
 try:
     from scipy.spatial import cKDTree
 except ImportError:
     cKDTree = None
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--runs", type=int, default=1024)
-ap.add_argument("--scans", type=int, default=4, help="scans per run")
-ap.add_argument("--distinct", type=int, default=8, help="different trajectory segments among the runs")
+ap = rw.parser()
 ap.add_argument("--leaf", type=float, default=0.1)
 ap.add_argument("--max-dist", default="0.25,0.05")
 ap.add_argument("--ref-files", type=int, default=8, help="map clouds whose union, downsampled once more, is the reference cloud")
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--host-files", type=int, default=16, help="files of the host baseline")
-ap.add_argument("--map-scans", type=int, default=3, help="scans replayed live behind the first frame before the map is frozen")
-ap.add_argument("--commit", default="", help="recorded in the JSON")
-ap.add_argument("--json", default="")
 args = ap.parse_args()
-R, K, D = args.runs, args.scans, min(args.distinct, args.runs)
 
-sc = scenes.Scene()
-g = binding.LegKiloHip(sc.cfg(n_slots=R))
-t0 = 1.0
-x0 = scenes.init_filter(g, sc, t0)
-scenes.first_frame(g, sc, t0, x0)
-scenes.replay_vlp(g, sc, t0, args.map_scans)
-seg_scans, seg_tb, seg_imu = [], [], []
-for d in range(D):
-    tbs = [t0 + 0.1 * (args.map_scans + 1) + 0.37 * d + 0.1 * j for j in range(K)]
-    seg_scans.append([scenes.vlp_scan_input(sc, tb, 500 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_imu.append([synth.imu_stream(sc.traj, tb, tb + 0.1, seed=6000 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_tb.append(tbs)
-rng = np.random.default_rng(2468)
-seg_of = [r % D for r in range(R)]
-t = binding.flatten_runs([seg_scans[seg_of[r]] for r in range(R)], [seg_tb[seg_of[r]] for r in range(R)], imus=[seg_imu[seg_of[r]] for r in range(R)])
-run_off, scan_off, tb, n_msg = t["run_off"], t["scan_off"], t["t_begin"], t["n_msg"]
-n_pts = len(t["pts"])
-d_pts, d_imu, d_world, d_out, d_ref = (g.device_malloc(v) for v in (t["pts"].nbytes, t["msgs"].nbytes, 16 * n_pts, 16 * n_pts, 16 * n_pts))
-g.h2d(d_pts, t["pts"])
-g.h2d(d_imu, t["msgs"])
-x_run = np.array([synth.initial_state(sc.traj, tb[r * K], sc.P, rng, 0.02, 0.5) for r in range(R)])
-P_run = np.tile((1e-4 * np.eye(30)).reshape(1, 900), (R, 1))
+w = rw.Workload(args)
+R, K, D, g, d_pts, d_imu, n_pts, x_run, P_run = w.R, w.K, w.D, w.g, w.d_pts, w.d_imu, w.n_pts, w.x, w.P
+run_off, scan_off, tb, n_msg = w.run_off, w.scan_off, w.tb, w.n_msg
+d_world, d_out, d_ref = (g.device_malloc(16 * n_pts) for _ in range(3))
 file_off, _ = binding.pcd_file_offsets(run_off, scan_off, K)
 F = len(file_off) - 1
 
-hip, stream = g.L, C.c_void_p(g.stream())
-ev = [C.c_void_p(), C.c_void_p()]
-for e in ev:
-    assert hip.hipEventCreate(C.byref(e)) == 0
-
-
-def timed(call, before=None):
-    """[(event ms, wall ms)] of the timed calls."""
-    res = []
-    for _ in range(args.warmup + args.reps):
-        if before:
-            before()
-        assert hip.hipEventRecord(ev[0], stream) == 0
-        t1 = time.perf_counter()
-        call()
-        wall = time.perf_counter() - t1
-        ms = C.c_float()
-        assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0 and hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-        res.append((float(ms.value), wall * 1e3))
-    return res[args.warmup:]
-
-
-def stats(v):
-    return dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
-
-
-def both(res):
-    return dict(event_ms=stats([a for a, _ in res]), wall_ms=stats([b for _, b in res]))
-
-
+timer = rw.EventTimer(g, args)
+timed = timer.timed
 last = {}
 
 
@@ -139,17 +76,7 @@ for md in [float(v) for v in args.max_dist.split(",")]:
             last[name] = g.clouds_c2c_dev(*call_args, md, thr)[0]
 
         res = timed(call)
-        g.profile_reset()
-        g.profile_enable(True)
-        per = {k: [] for k in LAUNCHES}
-        try:
-            for _ in range(args.reps):
-                g.profile_reset()
-                call()
-                for k in LAUNCHES:
-                    per[k].append(g.profile_get(k)[1])
-        finally:
-            g.profile_enable(False)
+        per = rw.per_launch(g, call, LAUNCHES, args.reps)
         rec = last[name]
         build = [sum(per[k][i] for k in LAUNCHES[:5]) for i in range(args.reps)]
         forms[f"{name}_{md:g}"] = dict(max_dist=md, thr=thr, pairs=F, query_points=int(rec["n_query"].sum()), reference_points=n_ref if name == "accuracy" else n_map,
@@ -214,8 +141,5 @@ if args.json:
                        reps=args.reps, warmup=args.warmup, registered_points=n_pts, map_clouds=F, map_points=n_map, survey_points=n_ref, ref_files=args.ref_files,
                        forms=forms, baseline=baseline, chain_before=before, chain_after=after), f, indent=1)
         f.write("\n")
-for e in ev:
-    hip.hipEventDestroy(e)
-for d in (d_pts, d_imu, d_world, d_out, d_ref):
-    g.device_free(d)
-g.close()
+timer.close()
+w.close(d_world, d_out, d_ref)

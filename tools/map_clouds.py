@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Measurement on one MI355X, everything through the C-ABI: what the downsampled map clouds cost (lk_downsample_clouds_dev), on the workload of
-tools/runs_cloud.py - R runs of K consecutive config-1 scans replayed on the frozen map with d_world_out (lk_batch_replay_runs_cloud_dev), which is
-the input here and stays in HBM.  Forms:
+tools/runs_workload.py - R runs of K consecutive config-1 scans replayed on the frozen map with d_world_out (lk_batch_replay_runs_cloud_dev), which
+is the input here and stays in HBM.  Forms:
   files_<n>   pcd_file_offsets(..., frames_per_file = n) for every n of --frames-per-file: R * ceil(K / n) files in one call, leaf --leaf;
   one_file    the same points as ONE file (the skewed shape: a single file takes the device-wide sort instead of a segment per file);
   d2h         what the parent commit offers, first half: lk_memcpy_d2h of the whole registered cloud;
@@ -12,8 +12,6 @@ ms per call: median over --reps timed calls after --warmup untimed ones, with mi
 (the call is synchronous, the events bracket it) and by the host's wall clock.  Bandwidth: the chain's own byte count of DESIGN.md section 4i,
 132 B per point + 24 B per cell, over the event time.
 Usage: map_clouds.py [--runs R] [--scans K] [--distinct D] [--frames-per-file LIST] [--leaf M] [--reps N] [--warmup W] [--numpy-files F] [--commit TEXT] [--json PATH]"""
-import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -21,84 +19,29 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))    # scenes.py: the synthetic room / trajectory / first-frame helpers the tests use
-sys.path.insert(0, os.path.join(ROOT, "oracle"))   # preprocess_oracle.py: the numpy definition the baseline runs (measurement only)
-import lk_pkg  # noqa: E402
+import runs_workload as rw
+from runs_workload import binding, stats
 
-lk_pkg.load()
+sys.path.insert(0, os.path.join(rw.ROOT, "oracle"))   # preprocess_oracle.py: the numpy definition the baseline runs (measurement only)
 import preprocess_oracle as po  # noqa: E402
-import scenes  # noqa: E402
-from legkilo_amd import binding, synth  # noqa: E402
 
 BYTES_PER_POINT, BYTES_PER_CELL = 132, 24   # DESIGN.md section 4i
 COPY_CEILING_TBS = 6.29                     # DESIGN.md: the measured device-to-device copy rate of this card
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--runs", type=int, default=1024)
-ap.add_argument("--scans", type=int, default=4, help="scans per run")
-ap.add_argument("--distinct", type=int, default=8, help="different trajectory segments among the runs")
+ap = rw.parser()
 ap.add_argument("--frames-per-file", default="4,2")
 ap.add_argument("--leaf", type=float, default=0.1)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--numpy-files", type=int, default=32, help="files of the host baseline (it costs ~10 ms per file)")
-ap.add_argument("--map-scans", type=int, default=3, help="scans replayed live behind the first frame before the map is frozen")
-ap.add_argument("--commit", default="", help="recorded in the JSON")
-ap.add_argument("--json", default="")
 args = ap.parse_args()
-R, K, D = args.runs, args.scans, min(args.distinct, args.runs)
 
-sc = scenes.Scene()
-g = binding.LegKiloHip(sc.cfg(n_slots=R))
-t0 = 1.0
-x0 = scenes.init_filter(g, sc, t0)
-scenes.first_frame(g, sc, t0, x0)
-scenes.replay_vlp(g, sc, t0, args.map_scans)
-seg_scans, seg_tb, seg_imu = [], [], []
-for d in range(D):
-    tbs = [t0 + 0.1 * (args.map_scans + 1) + 0.37 * d + 0.1 * j for j in range(K)]
-    seg_scans.append([scenes.vlp_scan_input(sc, tb, 500 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_imu.append([synth.imu_stream(sc.traj, tb, tb + 0.1, seed=6000 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_tb.append(tbs)
-rng = np.random.default_rng(2468)
-seg_of = [r % D for r in range(R)]
-t = binding.flatten_runs([seg_scans[seg_of[r]] for r in range(R)], [seg_tb[seg_of[r]] for r in range(R)], imus=[seg_imu[seg_of[r]] for r in range(R)])
-run_off, scan_off, tb, n_msg = t["run_off"], t["scan_off"], t["t_begin"], t["n_msg"]
-n_pts = len(t["pts"])
-d_pts, d_imu, d_world, d_out = g.device_malloc(t["pts"].nbytes), g.device_malloc(t["msgs"].nbytes), g.device_malloc(16 * n_pts), g.device_malloc(16 * n_pts)
-g.h2d(d_pts, t["pts"])
-g.h2d(d_imu, t["msgs"])
-x_run = np.array([synth.initial_state(sc.traj, tb[r * K], sc.P, rng, 0.02, 0.5) for r in range(R)])
-g.batch_set_priors(x_run, np.tile((1e-4 * np.eye(30)).reshape(1, 900), (R, 1)))
+w = rw.Workload(args)
+R, K, D, g, d_pts, d_imu, n_pts, run_off, scan_off, tb, n_msg = w.R, w.K, w.D, w.g, w.d_pts, w.d_imu, w.n_pts, w.run_off, w.scan_off, w.tb, w.n_msg
+d_world, d_out = g.device_malloc(16 * n_pts), g.device_malloc(16 * n_pts)
+g.batch_set_priors(w.x, w.P)
 g.batch_replay_runs_cloud_dev(d_pts, run_off, scan_off, tb, 1, n_msg, d_imu, want_poses=False, d_world=d_world)   # the input: the registered cloud
 
-# HIP events of the runtime the library itself is linked against (its symbols resolve through the library's handle), on the handle's stream
-hip, stream = g.L, C.c_void_p(g.stream())
-ev = [C.c_void_p(), C.c_void_p()]
-for e in ev:
-    assert hip.hipEventCreate(C.byref(e)) == 0
-
-
-def timed(call):
-    """[(event ms, wall ms)] of the timed calls."""
-    res = []
-    for _ in range(args.warmup + args.reps):
-        assert hip.hipEventRecord(ev[0], stream) == 0
-        t1 = time.perf_counter()
-        call()
-        wall = time.perf_counter() - t1
-        ms = C.c_float()
-        assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0 and hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-        res.append((float(ms.value), wall * 1e3))
-    return res[args.warmup:]
-
-
-def stats(v):
-    return dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
-
-
+timer = rw.EventTimer(g, args)
+timed = timer.timed
 forms, last = {}, {}
 
 
@@ -158,8 +101,5 @@ if args.json:
                        leaf=args.leaf, reps=args.reps, warmup=args.warmup, map_scans=args.map_scans, points_per_scan=pps, bytes_per_point=BYTES_PER_POINT,
                        bytes_per_cell=BYTES_PER_CELL, copy_ceiling_tb_per_s=COPY_CEILING_TBS, forms=forms), f, indent=1)
         f.write("\n")
-for e in ev:
-    hip.hipEventDestroy(e)
-for d in (d_pts, d_imu, d_world, d_out):
-    g.device_free(d)
-g.close()
+timer.close()
+w.close(d_world, d_out)

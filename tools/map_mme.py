@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Measurement on one MI355X, everything through the C-ABI: what scoring map clouds WITHOUT a reference costs (lk_clouds_mme_dev: mean map entropy and
-mean plane variance), on the workload of tools/map_c2c.py - R runs of K consecutive config-1 scans replayed on the frozen map with d_world_out, cut
-into one file per run and downsampled (lk_downsample_clouds_dev); its d_out / out_off are the map clouds and stay in HBM.  One call scores all of them,
-at every radius of --radius.
+mean plane variance), on the workload of tools/runs_workload.py as tools/map_c2c.py uses it - R runs of K consecutive config-1 scans replayed on the
+frozen map with d_world_out, cut into one file per run and downsampled (lk_downsample_clouds_dev); its d_out / out_off are the map clouds and stay in
+HBM.  One call scores all of them, at every radius of --radius.
 ms per call: median over --reps timed calls after --warmup untimed ones, with min .. max, between two HIP events on the handle's stream (the call is
 synchronous, the events bracket it) and by the host's wall clock; then, in profiling mode (every launch between its own events), the grid build
 (bounds, grid, keys, gather - the sort is not a launch of the library's and is the remainder), the point kernel and the reduce on their own.
@@ -15,102 +15,38 @@ largest difference is recorded (the tree decides on distances, not on d2).
 The run replay, lk_downsample_clouds_dev and the C2C accuracy pass at 0.25 m are timed before and after the MME calls (tools/runs_cloud.py's,
 tools/map_clouds.py's and tools/map_c2c.py's figures).
 Usage: map_mme.py [--runs R] [--scans K] [--distinct D] [--leaf M] [--radius LIST] [--min-pts N] [--reps N] [--warmup W] [--host-files F] [--commit TEXT] [--json PATH]"""
-import argparse
-import ctypes as C
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))    # scenes.py: the synthetic room / trajectory / first-frame helpers the tests use
-import lk_pkg  # noqa: E402
-
-lk_pkg.load()
-import scenes  # noqa: E402
-from legkilo_amd import binding, synth  # noqa: E402
+import runs_workload as rw
+from runs_workload import binding, both, stats
 
 try:
     from scipy.spatial import cKDTree
 except ImportError:
     cKDTree = None
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--runs", type=int, default=1024)
-ap.add_argument("--scans", type=int, default=4, help="scans per run")
-ap.add_argument("--distinct", type=int, default=8, help="different trajectory segments among the runs")
+ap = rw.parser()
 ap.add_argument("--leaf", type=float, default=0.1)
 ap.add_argument("--radius", default="0.3,0.5")
 ap.add_argument("--min-pts", type=int, default=5)
 ap.add_argument("--ref-files", type=int, default=8, help="map clouds whose union, downsampled once more, is the C2C pass's reference cloud")
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--host-files", type=int, default=16, help="files of the host baseline")
-ap.add_argument("--map-scans", type=int, default=3, help="scans replayed live behind the first frame before the map is frozen")
-ap.add_argument("--commit", default="", help="recorded in the JSON")
-ap.add_argument("--json", default="")
 args = ap.parse_args()
-R, K, D = args.runs, args.scans, min(args.distinct, args.runs)
 HAS_MME = hasattr(binding.LegKiloHip, "clouds_mme_dev")   # (the tool also times the untouched paths on a library without the entry)
 
-sc = scenes.Scene()
-g = binding.LegKiloHip(sc.cfg(n_slots=R))
-t0 = 1.0
-x0 = scenes.init_filter(g, sc, t0)
-scenes.first_frame(g, sc, t0, x0)
-scenes.replay_vlp(g, sc, t0, args.map_scans)
-seg_scans, seg_tb, seg_imu = [], [], []
-for d in range(D):
-    tbs = [t0 + 0.1 * (args.map_scans + 1) + 0.37 * d + 0.1 * j for j in range(K)]
-    seg_scans.append([scenes.vlp_scan_input(sc, tb, 500 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_imu.append([synth.imu_stream(sc.traj, tb, tb + 0.1, seed=6000 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_tb.append(tbs)
-rng = np.random.default_rng(2468)
-seg_of = [r % D for r in range(R)]
-t = binding.flatten_runs([seg_scans[seg_of[r]] for r in range(R)], [seg_tb[seg_of[r]] for r in range(R)], imus=[seg_imu[seg_of[r]] for r in range(R)])
-run_off, scan_off, tb, n_msg = t["run_off"], t["scan_off"], t["t_begin"], t["n_msg"]
-n_pts = len(t["pts"])
-d_pts, d_imu, d_world, d_out, d_ref = (g.device_malloc(v) for v in (t["pts"].nbytes, t["msgs"].nbytes, 16 * n_pts, 16 * n_pts, 16 * n_pts))
-g.h2d(d_pts, t["pts"])
-g.h2d(d_imu, t["msgs"])
-x_run = np.array([synth.initial_state(sc.traj, tb[r * K], sc.P, rng, 0.02, 0.5) for r in range(R)])
-P_run = np.tile((1e-4 * np.eye(30)).reshape(1, 900), (R, 1))
+w = rw.Workload(args)
+R, K, D, g, d_pts, d_imu, n_pts, x_run, P_run = w.R, w.K, w.D, w.g, w.d_pts, w.d_imu, w.n_pts, w.x, w.P
+run_off, scan_off, tb, n_msg = w.run_off, w.scan_off, w.tb, w.n_msg
+d_world, d_out, d_ref = (g.device_malloc(16 * n_pts) for _ in range(3))
 file_off, _ = binding.pcd_file_offsets(run_off, scan_off, K)
 F = len(file_off) - 1
 
-hip, stream = g.L, C.c_void_p(g.stream())
-ev = [C.c_void_p(), C.c_void_p()]
-for e in ev:
-    assert hip.hipEventCreate(C.byref(e)) == 0
-
-
-def timed(call, before=None):
-    """[(event ms, wall ms)] of the timed calls."""
-    res = []
-    for _ in range(args.warmup + args.reps):
-        if before:
-            before()
-        assert hip.hipEventRecord(ev[0], stream) == 0
-        t1 = time.perf_counter()
-        call()
-        wall = time.perf_counter() - t1
-        ms = C.c_float()
-        assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0 and hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-        res.append((float(ms.value), wall * 1e3))
-    return res[args.warmup:]
-
-
-def stats(v):
-    return dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
-
-
-def both(res):
-    return dict(event_ms=stats([a for a, _ in res]), wall_ms=stats([b for _, b in res]))
-
-
+timer = rw.EventTimer(g, args)
+timed = timer.timed
 last = {}
 
 
@@ -180,17 +116,7 @@ for radius in radii:
         last["mme"] = g.clouds_mme_dev(d_out, out_off, radius, args.min_pts)
 
     res = timed(call)
-    g.profile_reset()
-    g.profile_enable(True)
-    per = {k: [] for k in BUILD + ("mme_point", "mme_reduce")}
-    try:
-        for _ in range(args.reps):
-            g.profile_reset()
-            call()
-            for k in per:
-                per[k].append(g.profile_get(k)[1])
-    finally:
-        g.profile_enable(False)
+    per = rw.per_launch(g, call, BUILD + ("mme_point", "mme_reduce"), args.reps)
     rec = last["mme"]
     build = [sum(per[k][i] for k in BUILD) for i in range(args.reps)]
     seen = sum(looked_at(maps[int(out_off[f]):int(out_off[f + 1]), :3].astype(np.float64), radius) for f in range(nf))
@@ -231,8 +157,5 @@ if args.json:
                        reps=args.reps, warmup=args.warmup, registered_points=n_pts, map_clouds=F, map_points=n_map, forms=forms, baseline=baseline,
                        chain_before=before, chain_after=after), f, indent=1)
         f.write("\n")
-for e in ev:
-    hip.hipEventDestroy(e)
-for d in (d_pts, d_imu, d_world, d_out, d_ref):
-    g.device_free(d)
-g.close()
+timer.close()
+w.close(d_world, d_out, d_ref)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Measurement on one MI355X, everything through the C-ABI: R runs of K consecutive config-1 scans (only_imu_use: each scan with its IMU records)
-replayed on the FROZEN map - first frame + --map-scans scans, the workload of tools/overlay_runs.py - from the same perturbed priors in three forms:
+replayed on the FROZEN map - first frame + --map-scans scans, the workload of tools/runs_workload.py - from the same perturbed priors in three forms:
   runs        ONE lk_batch_replay_runs_dev call: a run per filter slot, state, covariance and time stamps carried from scan to scan;
   chunks      the same runs as two calls, the first K / 2 scans of every run and then the rest with LK_RUNS_CONTINUE;
   independent the same R*K scans, cut to n_slots = R at a time, as independent scans through lk_batch_replay_scans_imu_dev (K calls, every scan
@@ -8,70 +8,22 @@ replayed on the FROZEN map - first frame + --map-scans scans, the workload of to
               per scan.  This form alone also runs under a library that lacks the new entry (LEGKILO_HIP_LIB=<the parent's build> --forms independent).
 us per scan: median over --reps timed calls after --warmup untimed ones, with min .. max; the priors are armed outside the timed region.
 Usage: replay_runs.py [--runs R] [--scans K] [--distinct D] [--reps N] [--warmup W] [--forms LIST] [--commit TEXT] [--json PATH]"""
-import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))   # scenes.py: the synthetic room / trajectory / first-frame helpers the tests use
-import lk_pkg  # noqa: E402
+import runs_workload as rw
+from runs_workload import binding
 
-lk_pkg.load()
-import scenes  # noqa: E402
-from legkilo_amd import binding, synth  # noqa: E402
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--runs", type=int, default=1024)
-ap.add_argument("--scans", type=int, default=4, help="scans per run")
-ap.add_argument("--distinct", type=int, default=8, help="different trajectory segments among the runs")
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
+ap = rw.parser()
 ap.add_argument("--forms", default="independent,runs,chunks", help="comma-separated, measured in this order")
-ap.add_argument("--map-scans", type=int, default=3, help="scans replayed live behind the first frame before the map is frozen")
-ap.add_argument("--commit", default="", help="recorded in the JSON")
-ap.add_argument("--json", default="")
 args = ap.parse_args()
-R, K, D = args.runs, args.scans, min(args.distinct, args.runs)
 
-sc = scenes.Scene()
-g = binding.LegKiloHip(sc.cfg(n_slots=R))
-t0 = 1.0
-x0 = scenes.init_filter(g, sc, t0)
-scenes.first_frame(g, sc, t0, x0)
-scenes.replay_vlp(g, sc, t0, args.map_scans)
-
-# the D segments: K scans 0.1 s apart, each with its IMU records; run r replays segment r % D from its own perturbed prior
-seg_scans, seg_tb, seg_imu = [], [], []
-for d in range(D):
-    tbs = [t0 + 0.1 * (args.map_scans + 1) + 0.37 * d + 0.1 * j for j in range(K)]
-    seg_scans.append([scenes.vlp_scan_input(sc, tb, 500 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_imu.append([synth.imu_stream(sc.traj, tb, tb + 0.1, seed=6000 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_tb.append(tbs)
-rng = np.random.default_rng(2468)
-seg_of = [r % D for r in range(R)]
-
-
-def tables(lo, hi):
-    """Scans lo .. hi of every run as a batch of runs, and the same scans scan-major (scan j of every run, then scan j + 1: the independent form's
-    calls), both over one point and one message array."""
-    t = binding.flatten_runs([seg_scans[seg_of[r]][lo:hi] for r in range(R)], [seg_tb[seg_of[r]][lo:hi] for r in range(R)],
-                             imus=[seg_imu[seg_of[r]][lo:hi] for r in range(R)])
-    t["msg_off"] = np.r_[0, np.cumsum(t["n_msg"])]
-    return t
-
-
-whole = tables(0, K)
-d_pts, d_imu = g.device_malloc(whole["pts"].nbytes), g.device_malloc(whole["msgs"].nbytes)
-g.h2d(d_pts, whole["pts"])
-g.h2d(d_imu, whole["msgs"])
-tb_flat = whole["t_begin"]
-x_scan = np.array([synth.initial_state(sc.traj, t, sc.P, rng, 0.02, 0.5) for t in tb_flat])   # a prior per scan: the independent form's; a run starts from its first scan's
-P_scan = np.tile((1e-4 * np.eye(30)).reshape(1, 900), (R, 1))
+w = rw.Workload(args, per_scan=True)   # a prior per scan: the independent form's; a run starts from its first scan's
+R, K, D, g, seg_scans, tables, whole, d_pts, d_imu = w.R, w.K, w.D, w.g, w.seg_scans, w.tables, w.t, w.d_pts, w.d_imu
+tb_flat, x_scan, P_scan = w.tb, w.x, w.P
 # the two chunks of a run are not contiguous in the run-major arrays: each half gets arrays of its own
 half = K // 2
 parts = []
@@ -79,9 +31,7 @@ if "chunks" in args.forms.split(","):
     assert 1 <= half < K
     for lo, hi in ((0, half), (half, K)):
         t = tables(lo, hi)
-        t["d_pts"], t["d_imu"] = g.device_malloc(t["pts"].nbytes), g.device_malloc(t["msgs"].nbytes)
-        g.h2d(t["d_pts"], t["pts"])
-        g.h2d(t["d_imu"], t["msgs"])
+        t["d_pts"], t["d_imu"] = w.upload(t)
         parts.append(t)
 # the independent form: R consecutive scans of the run-major array at a time (runs of K: call c holds the runs c R / K .. (c + 1) R / K whole)
 indep = []
@@ -138,5 +88,4 @@ if args.json:
         f.write("\n")
 for t in parts:
     g.device_free(t["d_pts"]), g.device_free(t["d_imu"])
-g.device_free(d_pts), g.device_free(d_imu)
-g.close()
+w.close()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Measurement on one MI355X, everything through the C-ABI: what the per-bucket poses and the registered cloud of the run replays cost, on the workload
-of tools/replay_runs.py / tools/overlay_runs.py - R runs of K consecutive config-1 scans (only_imu_use: each scan with its IMU records), map = first
-frame + --map-scans scans, perturbed priors.  Forms, per entry (frozen: lk_batch_replay_runs_dev, overlay: lk_batch_replay_overlay_runs_dev):
+of tools/runs_workload.py - R runs of K consecutive config-1 scans (only_imu_use: each scan with its IMU records), map = first frame + --map-scans
+scans, perturbed priors.  Forms, per entry (frozen: lk_batch_replay_runs_dev, overlay: lk_batch_replay_overlay_runs_dev):
   plain_*    the EXISTING entry.  These two also run under a library that lacks the new entries (LEGKILO_HIP_LIB=<the parent's build> --forms
              plain_frozen,plain_overlay --json PARENT.json); a later run with --parent-json PARENT.json records both and says whether the new median lies
              inside the parent's min .. max range widened by the new run's own range - run-to-run spread is the only margin there is;
@@ -12,67 +12,30 @@ frame + --map-scans scans, perturbed priors.  Forms, per entry (frozen: lk_batch
              the first --live-runs runs.
 us per scan: median over --reps timed calls after --warmup untimed ones, with min .. max; the priors are armed outside the timed region.
 Usage: runs_cloud.py [--runs R] [--scans K] [--distinct D] [--reps N] [--warmup W] [--live-runs L] [--forms LIST] [--parent-json PATH] [--commit TEXT] [--json PATH]"""
-import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))   # scenes.py: the synthetic room / trajectory / first-frame helpers the tests use
-import lk_pkg  # noqa: E402
-
-lk_pkg.load()
-import scenes  # noqa: E402
-from legkilo_amd import binding, synth  # noqa: E402
+import runs_workload as rw
+from runs_workload import binding
 
 ALL = "plain_frozen,records_frozen,cloud_frozen,plain_overlay,records_overlay,cloud_overlay,register,live"
 COPY_CEILING_TBS = 6.29   # DESIGN.md: the measured device-to-device copy rate of this card
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--runs", type=int, default=1024)
-ap.add_argument("--scans", type=int, default=4, help="scans per run")
-ap.add_argument("--distinct", type=int, default=8, help="different trajectory segments among the runs")
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
+ap = rw.parser()
 ap.add_argument("--forms", default=ALL, help="comma-separated, measured in this order")
 ap.add_argument("--live-runs", type=int, default=16, help="runs of the live form (it costs ~6 ms per scan)")
-ap.add_argument("--map-scans", type=int, default=3, help="scans replayed live behind the first frame before the map is frozen")
 ap.add_argument("--parent-json", default="", help="this tool's JSON of the plain forms under the parent commit's library, same machine, same session")
-ap.add_argument("--commit", default="", help="recorded in the JSON")
-ap.add_argument("--json", default="")
 args = ap.parse_args()
-R, K, D = args.runs, args.scans, min(args.distinct, args.runs)
 forms = args.forms.split(",")
 
-sc = scenes.Scene()
-g = binding.LegKiloHip(sc.cfg(n_slots=R))
-t0 = 1.0
-x0 = scenes.init_filter(g, sc, t0)
-scenes.first_frame(g, sc, t0, x0)
-scenes.replay_vlp(g, sc, t0, args.map_scans)
+w = rw.Workload(args)
+R, K, D, g, d_pts, d_imu, n_pts, x_run, P_run = w.R, w.K, w.D, w.g, w.d_pts, w.d_imu, w.n_pts, w.x, w.P
+run_off, scan_off, tb, n_msg, msg_off = w.run_off, w.scan_off, w.tb, w.n_msg, w.msg_off
 start = (g.map_export(), g.get_last_slide_position())
-
-seg_scans, seg_tb, seg_imu = [], [], []
-for d in range(D):
-    tbs = [t0 + 0.1 * (args.map_scans + 1) + 0.37 * d + 0.1 * j for j in range(K)]
-    seg_scans.append([scenes.vlp_scan_input(sc, tb, 500 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_imu.append([synth.imu_stream(sc.traj, tb, tb + 0.1, seed=6000 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_tb.append(tbs)
-rng = np.random.default_rng(2468)
-seg_of = [r % D for r in range(R)]
-t = binding.flatten_runs([seg_scans[seg_of[r]] for r in range(R)], [seg_tb[seg_of[r]] for r in range(R)], imus=[seg_imu[seg_of[r]] for r in range(R)])
-run_off, scan_off, tb, n_msg = t["run_off"], t["scan_off"], t["t_begin"], t["n_msg"]
-msg_off = np.r_[0, np.cumsum(n_msg)]
-n_pts = len(t["pts"])
-d_pts, d_imu, d_world = g.device_malloc(t["pts"].nbytes), g.device_malloc(t["msgs"].nbytes), g.device_malloc(16 * n_pts)
-g.h2d(d_pts, t["pts"])
-g.h2d(d_imu, t["msgs"])
-x_run = np.array([synth.initial_state(sc.traj, tb[r * K], sc.P, rng, 0.02, 0.5) for r in range(R)])
-P_run = np.tile((1e-4 * np.eye(30)).reshape(1, 900), (R, 1))
+d_world = g.device_malloc(16 * n_pts)
 n_buckets = 0
 
 
@@ -164,6 +127,4 @@ if args.json:
                        reps=args.reps, warmup=args.warmup, map_scans=args.map_scans, points_per_scan=pps, us_per_scan=us,
                        parent=None if parent is None else dict(library=parent["library"], us_per_scan=parent["us_per_scan"]), plain_entries_vs_parent=verdict), f, indent=1)
         f.write("\n")
-for d in (d_pts, d_imu, d_world):
-    g.device_free(d)
-g.close()
+w.close(d_world)

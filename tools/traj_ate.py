@@ -1,9 +1,9 @@
 #!/usr/bin/env python
 """Measurement on one MI355X, everything through the C-ABI: what scoring every run of a batched run replay against ground truth costs, on the workload
-of tools/runs_cloud.py - R runs of K consecutive config-1 scans (only_imu_use), map = first frame + --map-scans scans, perturbed priors, replayed once
-by lk_batch_replay_runs_cloud_dev so that the handle holds the bucket table.  Ground truth: the synthetic trajectory at every bucket's stamp.
-One difference from that workload: a run's scans start 0.1 s + 1 us apart, not 0.1 s.  The last point of a synthetic scan carries the float32 offset
-0.1f = 0.1 + 1.5e-9, so with back-to-back scans the last bucket of a scan is stamped 1.5 ns AFTER the first bucket of the next one, and the entry
+of tools/runs_workload.py - R runs of K consecutive config-1 scans (only_imu_use), map = first frame + --map-scans scans, perturbed priors, replayed
+once by lk_batch_replay_runs_cloud_dev so that the handle holds the bucket table.  Ground truth: the synthetic trajectory at every bucket's stamp.
+One difference from the other tools' use of it: a run's scans start 0.1 s + 1 us apart, not 0.1 s.  The last point of a synthetic scan carries the
+float32 offset 0.1f = 0.1 + 1.5e-9, so with back-to-back scans the last bucket of a scan is stamped 1.5 ns AFTER the first bucket of the next one, and the entry
 refuses a trajectory whose stamps decrease (--scan-gap 0 shows the refusal).
   device    lk_runs_ate_dev with and without LK_ATE_ALIGN: the whole entry between two HIP events on the handle's stream (offset upload, one launch,
             the copy of the records) and as wall time, and the launch alone from the library's launch profiler;
@@ -12,64 +12,24 @@ refuses a trajectory whose stamps decrease (--scan-gap 0 shows the refusal).
   replays   the plain and the recording frozen-map replay re-taken (us per scan), beside profiles/runs_cloud.json's figures.
 Median over --reps timed calls after --warmup untimed ones, with min .. max.  The device's rmse is compared with the baseline's per run.
 Usage: traj_ate.py [--runs R] [--scans K] [--distinct D] [--reps N] [--warmup W] [--commit TEXT] [--json PATH]"""
-import argparse
-import ctypes as C
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))   # scenes.py: the synthetic room / trajectory / first-frame helpers the tests use
-import lk_pkg  # noqa: E402
+import runs_workload as rw
+from runs_workload import ROOT, binding, stats
+from legkilo_amd import tum  # noqa: E402
 
-lk_pkg.load()
-import scenes  # noqa: E402
-from legkilo_amd import binding, synth, tum  # noqa: E402
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--runs", type=int, default=1024)
-ap.add_argument("--scans", type=int, default=4, help="scans per run")
-ap.add_argument("--distinct", type=int, default=8, help="different trajectory segments among the runs")
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
-ap.add_argument("--map-scans", type=int, default=3)
+ap = rw.parser(os.path.join(ROOT, "profiles", "traj_ate.json"))
 ap.add_argument("--max-dt", type=float, default=1e-3)
 ap.add_argument("--scan-gap", type=float, default=1e-6, help="seconds between the end of a scan and the start of the next one of its run")
-ap.add_argument("--commit", default="", help="recorded in the JSON")
-ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "traj_ate.json"))
 args = ap.parse_args()
-R, K, D = args.runs, args.scans, min(args.distinct, args.runs)
 
-sc = scenes.Scene()
-g = binding.LegKiloHip(sc.cfg(n_slots=R))
-t0 = 1.0
-x0 = scenes.init_filter(g, sc, t0)
-scenes.first_frame(g, sc, t0, x0)
-scenes.replay_vlp(g, sc, t0, args.map_scans)
-
-seg_scans, seg_tb, seg_imu = [], [], []
-for d in range(D):
-    tbs = [t0 + 0.1 * (args.map_scans + 1) + 0.37 * d + (0.1 + args.scan_gap) * j for j in range(K)]
-    seg_scans.append([scenes.vlp_scan_input(sc, tb, 500 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_imu.append([synth.imu_stream(sc.traj, tb, tb + 0.1, seed=6000 + K * d + j) for j, tb in enumerate(tbs)])
-    seg_tb.append(tbs)
-rng = np.random.default_rng(2468)
-seg_of = [r % D for r in range(R)]
-t = binding.flatten_runs([seg_scans[seg_of[r]] for r in range(R)], [seg_tb[seg_of[r]] for r in range(R)], imus=[seg_imu[seg_of[r]] for r in range(R)])
-run_off, scan_off, tb, n_msg = t["run_off"], t["scan_off"], t["t_begin"], t["n_msg"]
-d_pts, d_imu = g.device_malloc(t["pts"].nbytes), g.device_malloc(t["msgs"].nbytes)
-g.h2d(d_pts, t["pts"])
-g.h2d(d_imu, t["msgs"])
-x_run = np.array([synth.initial_state(sc.traj, tb[r * K], sc.P, rng, 0.02, 0.5) for r in range(R)])
-P_run = np.tile((1e-4 * np.eye(30)).reshape(1, 900), (R, 1))
-
-
-def stats(v):
-    return dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+w = rw.Workload(args, scan_gap=args.scan_gap)
+R, K, D, sc, g, d_pts, d_imu, x_run, P_run = w.R, w.K, w.D, w.sc, w.g, w.d_pts, w.d_imu, w.x, w.P
+run_off, scan_off, tb, n_msg = w.run_off, w.scan_off, w.tb, w.n_msg
 
 
 def replay(records):
@@ -101,43 +61,15 @@ gt = np.ascontiguousarray(np.concatenate([gt_t[:, None], gt_pos], axis=1))
 d_gt = g.device_malloc(gt.nbytes)
 g.h2d(d_gt, gt)
 
-hip, stream = g.L, C.c_void_p(g.stream())   # HIP events of the runtime the library itself is linked against, on the handle's stream
-ev = [C.c_void_p(), C.c_void_p()]
-for e in ev:
-    assert hip.hipEventCreate(C.byref(e)) == 0
-
-
-def timed(call):
-    res = []
-    for _ in range(args.warmup + args.reps):
-        assert hip.hipEventRecord(ev[0], stream) == 0
-        t1 = time.perf_counter()
-        call()
-        wall = time.perf_counter() - t1
-        ms = C.c_float()
-        assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0 and hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-        res.append((float(ms.value), wall * 1e3))
-    return res[args.warmup:]
-
-
+timer = rw.EventTimer(g, args)
+timed = timer.timed
 device, last = {}, {}
 for name, align in (("plain", False), ("align", True)):
     def call():
         last[name] = g.runs_ate_dev(rbo, d_gt, d_gt + 8, 32, rbo, args.max_dt, align=align)
 
     res = timed(call)
-    g.profile_reset()
-    g.profile_enable(True)
-    kern = []
-    try:
-        for _ in range(args.reps):
-            g.profile_reset()
-            call()
-            n, ms = g.profile_get("traj_ate")
-            assert n == 1, n
-            kern.append(ms)
-    finally:
-        g.profile_enable(False)
+    kern = rw.per_launch(g, call, ("traj_ate",), args.reps, count=1)["traj_ate"]
     # bytes the launch asks for per record: the estimate's stamp twice (order check, search), the ground truth's once plus the search's last two
     # probes (the earlier ones hit the cache), and per pass over the pairs (pair + residual, with alignment also centroid + covariance) the
     # 4-byte partner word and 24 B of position from either side
@@ -193,8 +125,5 @@ if args.json:
                        warmup=args.warmup, max_dt=args.max_dt, scan_gap=args.scan_gap, bucket_records=B, device=device, baseline=baseline, max_abs_rmse_difference=agree,
                        replays_us_per_scan=replays, replays_us_per_scan_stored=stored_us), f, indent=1)
         f.write("\n")
-for e in ev:
-    hip.hipEventDestroy(e)
-for d in (d_pts, d_imu, d_gt):
-    g.device_free(d)
-g.close()
+timer.close()
+w.close(d_gt)

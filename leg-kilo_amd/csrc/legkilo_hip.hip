@@ -1390,34 +1390,117 @@ int lk_map_import_dev(lk_handle* h, const void* d_blob, size_t bytes) {
     return LK_OK;
 }
 
-// ------------------------------------------------------------------ voxel-grid centroid filter + time sort
+// ------------------------------------------------------------------ the lidar front end: sensor decode, voxel-grid centroid filter + time sort (lk_pre_kernels.h)
+// One body in two stages over the S messages / scans of a call: front_decode (keep flags, compaction, scatter) and front_grid (bounds, cell keys, cell
+// sort, cells, centroids, time sort, gather).  lk_decode_scan_dev is the first at S = 1, lk_preprocess_scan_dev the second at S = 1 on the caller's
+// points, lk_decode_scans_dev both.  Host round trips per call, none per message: one after the decode (per-message decoded counts and raw times), one
+// after the centroids (per-scan overflow words and cell offsets: the time sort's size) and one at the end.  Both sorts are stable and stay inside a
+// scan (lk_prim_sort_pairs_in_segments, a segment per scan), so ties keep the input order whatever S is.
 namespace {
-struct PrePool {   // the per-call view of h->pre
-    lk_point *raw, *cells, *out;
-    unsigned int *k0, *k1, *flags, *pos, *misc;
-    int *v0, *v1, *starts;
+struct FrontPool {   // the per-call view of h->pre
+    unsigned int *flags, *pos, *sid, *k0, *k1, *v0, *v1;   // sid: null with one scan, and so are msg_off / pt_off (the kernels' "everything is scan 0")
+    int* starts;
+    lk_point *dec, *cells;
+    unsigned long long* msg_off;
+    unsigned int *pt_off, *dec_off, *err, *cell_off, *misc;
+    int* mm;
+    double* first_last;
+    lk_point* io_out;        // the host wrappers' device copies: the cloud that goes back ...
+    unsigned char* io_in;    // ... and what came up (raw lk_points or message bytes); the device entries carve none
 };
-// carves the arrays for P points out of `base` (nullptr: only counts) and returns the bytes they take
-size_t pre_carve(void* base, size_t P, PrePool& d) {
+// carves the arrays for P points of S messages out of `base` (nullptr: only counts) and returns the bytes they take; the host wrappers' staging arrays
+// come last, so that the device entry's view of the same buffer is the same but for them
+size_t front_carve(void* base, size_t P, size_t S, size_t n_io, size_t in_bytes, FrontPool& d) {
     LkCarve c(base, 256);
-    d.raw = c.take<lk_point>(P), d.cells = c.take<lk_point>(P), d.out = c.take<lk_point>(P);
-    d.k0 = c.take<unsigned int>(P), d.k1 = c.take<unsigned int>(P), d.flags = c.take<unsigned int>(P), d.pos = c.take<unsigned int>(P);
-    d.misc = c.take<unsigned int>(32);
-    d.v0 = c.take<int>(P), d.v1 = c.take<int>(P), d.starts = c.take<int>(P);
+    d.flags = c.take<unsigned int>(P), d.pos = c.take<unsigned int>(P);
+    d.sid = S > 1 ? c.take<unsigned int>(P) : nullptr;
+    d.k0 = c.take<unsigned int>(P), d.k1 = c.take<unsigned int>(P), d.v0 = c.take<unsigned int>(P), d.v1 = c.take<unsigned int>(P);
+    d.starts = c.take<int>(P);
+    d.dec = c.take<lk_point>(P), d.cells = c.take<lk_point>(P);
+    d.msg_off = S > 1 ? c.take<unsigned long long>(S) : nullptr;
+    d.pt_off = S > 1 ? c.take<unsigned int>(S + 1) : nullptr;
+    // dec_off [S + 1] | mm [6 S] | err [S] | cell_off [S + 1] taken as ONE array: lk_preprocess_scan_dev writes the first three with one copy, err | cell_off are read back with one
+    d.dec_off = c.take<unsigned int>(9 * S + 2);
+    d.mm = base ? reinterpret_cast<int*>(d.dec_off + S + 1) : nullptr;
+    d.err = base ? d.dec_off + 7 * S + 1 : nullptr, d.cell_off = base ? d.err + S : nullptr;
+    d.misc = c.take<unsigned int>(8);
+    d.first_last = c.take<double>(2 * S);
+    d.io_out = c.take<lk_point>(n_io), d.io_in = c.take<unsigned char>(in_bytes);
     return c.total();
 }
 }  // namespace
-// The arrays are laid out for the call's n: an entry that hands one of them to another entry (lk_preprocess_scan -> lk_preprocess_scan_dev)
-// passes the same n on, so both see the same layout.  The rocPRIM temporary storage is sized for n as well (every sort and scan of the
-// call runs over at most n elements).
-static int pre_reserve(lk_handle* h, size_t n, PrePool& d) {
-    const size_t need = pre_carve(nullptr, n, d);
-    LKCHK(reserve(h, h->pre, need, pre_carve(nullptr, n + n / 4 + 1024, d) - need));
-    pre_carve(h->pre.p, n, d);
+// The arrays are laid out for the call's P and S: a wrapper that hands a staging array to a device entry passes the same P and S on, so both see the same
+// layout.  A call of ONE message grows the buffer ahead (a live stream's scans differ a little in size).  The rocPRIM temporary storage is sized
+// for P as well (every sort and scan of the call runs over at most P elements).
+static int front_reserve(lk_handle* h, size_t P, size_t S, size_t n_io, size_t in_bytes, FrontPool& d) {
+    const size_t need = front_carve(nullptr, P, S, n_io, in_bytes, d), G = P + P / 4 + 1024;
+    LKCHK(reserve(h, h->pre, need, S == 1 ? front_carve(nullptr, G, 1, n_io ? G : 0, in_bytes / P * G, d) - need : 0));
+    front_carve(h->pre.p, P, S, n_io, in_bytes, d);
     size_t t1 = 0, t2 = 0;
-    HIPCHK(h, lk_prim_sort_pairs(nullptr, t1, d.k0, d.k1, d.v0, d.v1, n, 0, 32, h->stream));
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t2, d.flags, d.pos, n, h->stream));
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, d.flags, d.pos, P, h->stream));
+    HIPCHK(h, lk_prim_sort_pairs_in_segments(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)P, (unsigned int)S, d.dec_off, d.dec_off + 1, 0, 32, h->stream));
     return reserve(h, h->prim_tmp, std::max(t1, t2));
+}
+
+// decode stage: the kept points of S messages (P raw points in all; S > 1: d.msg_off / d.pt_off are on their way, base = the buffer they count from; one
+// message: base = its first byte) into `out`, in input order.  Leaves dec_off, the raw first / last times and every scan's initial bounds / overflow
+// word on the device and brings dec_off [S + 1] and first_last [2 S] to the host.  label: the prefix of the launches' profile names
+static int front_decode(lk_handle* h, const char* label, const FrontPool& d, const unsigned char* base, size_t S, size_t P, const LkDecodeArgs& a,
+                        lk_point* out, unsigned int* dec_off, double* first_last) {
+    const std::string L(label);
+    const unsigned int n = (unsigned int)P, nb = (n + 255) / 256;
+    LAUNCH(h, (L + "flags").c_str(), hipLaunchKernelGGL(lk_dscan_flags_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a, d.flags));
+    size_t tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, P, h->stream));
+    LAUNCH(h, (L + "scatter").c_str(), hipLaunchKernelGGL(lk_dscan_scatter_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a,
+                                                          d.flags, d.pos, out, d.sid, d.dec_off, d.first_last, d.mm, d.err));
+    HIPCHK(h, hipMemcpyAsync(dec_off, d.dec_off, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(first_last, d.first_last, 8 * 2 * S, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
+}
+
+// grid stage: D points of S scans (scan s = [dec_off[s], dec_off[s + 1]) on the device, with sid, initial bounds and overflow words) -> per-scan bounds and
+// cell keys, a stable sort by cell inside each scan, cells (a new one at every scan boundary), centroids, the scans' offsets over the cells (cell_off
+// [S + 1], to the host), a stable sort by time inside each scan's cells, the gather into d_out.  who: names the entry and the message in the overflow
+// refusal (null: the bare text of the one-scan entries)
+static int front_grid(lk_handle* h, const char* label, const char* who, const FrontPool& d, const lk_point* pts, unsigned int D, size_t S, float leaf,
+                      lk_point* d_out, unsigned int* cell_off) {
+    const std::string L(label);
+    const unsigned int Si = (unsigned int)S, db = (D + 255) / 256;
+    const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
+    const unsigned int gy = S == 1 ? std::min(db, 1024u) : std::min(64u, std::max(1u, D / Si / 2048u));   // (the bounds' atomics are order-free)
+    LAUNCH(h, (L + "minmax").c_str(), hipLaunchKernelGGL(lk_dscan_minmax_kernel, dim3(Si, gy), dim3(256), 0, h->stream, pts, d.dec_off, d.mm));
+    LAUNCH(h, (L + "cellidx").c_str(), hipLaunchKernelGGL(lk_dscan_cellidx_kernel, dim3(db), dim3(256), 0, h->stream, pts, D, inv, d.mm, d.sid, d.k0, d.v0, d.err));
+    size_t tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_sort_pairs_in_segments(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, D, Si, d.dec_off, d.dec_off + 1, 0, 32, h->stream));
+    LAUNCH(h, (L + "heads").c_str(), hipLaunchKernelGGL(lk_dscan_heads_kernel, dim3(db), dim3(256), 0, h->stream, d.k1, d.sid, D, d.flags));
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, D, h->stream));
+    // one scan: its offsets over the cells are { 0, cells } - the starts kernel writes the total there itself, and the launch of the offsets is saved
+    unsigned int* ncells_d = S == 1 ? d.cell_off + 1 : d.misc;
+    LAUNCH(h, (L + "starts").c_str(), hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(db), dim3(256), 0, h->stream, d.flags, d.pos, (int)D, d.starts, ncells_d));
+    LAUNCH(h, (L + "centroid").c_str(), hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(db), dim3(256), 0, h->stream, pts, (const int*)d.v1, d.starts, ncells_d,
+                                                           (int)D, d.cells, d.k0, (int*)d.v0));
+    if (S > 1)
+        LAUNCH(h, (L + "celloff").c_str(), hipLaunchKernelGGL(lk_dscan_celloff_kernel, dim3((Si + 1 + 255) / 256), dim3(256), 0, h->stream, d.dec_off, d.pos, ncells_d,
+                                                              (int)S, d.cell_off));
+    std::vector<unsigned int> ec(2 * S + 1);   // err [S] | cell_off [S + 1]
+    HIPCHK(h, hipMemcpyAsync(ec.data(), d.err, 4 * (2 * S + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (S == 1) ec[1] = 0u;
+    for (size_t s = 0; s < S; ++s)
+        if (ec[s])
+            return fail(h, LK_ERR_INVALID, (who ? std::string(who) + ": message " + std::to_string(s) + ": " : std::string()) +
+                                               "voxel grid leaf too small for the cloud extent (index overflow)");
+    const unsigned int Cn = ec[2 * S];
+    tb = h->prim_tmp.cap;
+    HIPCHK(h, lk_prim_sort_pairs_in_segments(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, Cn, Si, d.cell_off, d.cell_off + 1, 0, 32, h->stream));
+    LAUNCH(h, (L + "gather").c_str(), hipLaunchKernelGGL(lk_pre_gather_kernel, dim3((Cn + 255) / 256), dim3(256), 0, h->stream, d.cells, (const int*)d.v1, (int)Cn,
+                                                         d_out));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::copy(ec.begin() + S, ec.end(), cell_off);
+    return LK_OK;
 }
 
 // what lk_decode_scan(s)_dev refuse in a point layout (nullptr: none)
@@ -1437,26 +1520,14 @@ int lk_decode_scan_dev(lk_handle* h, const void* d_msg, size_t n_points, const l
     if (!d_msg || !layout || !d_out || !n_out || n_points == 0 || filter_num < 1 || n_points > 0x7fffffffu)
         return fail(h, LK_ERR_INVALID, "lk_decode_scan: bad argument");
     if (const char* e = cloud_layout_error(layout)) return fail(h, LK_ERR_INVALID, e);
-    PrePool d;
-    int rc = pre_reserve(h, n_points, d);
-    if (rc) return rc;
+    FrontPool d;
+    LKCHK(front_reserve(h, n_points, 1, 0, 0, d));
     LkDecodeArgs a;
     a.lay = *layout, a.time_scale = time_scale, a.filter_num = filter_num, a.blind = blind;
-    const int n = (int)n_points, nb = (n + 255) / 256;
-    unsigned int* n_out_d = d.misc + 7;
-    double* fl = reinterpret_cast<double*>(d.misc + 8);
-    LAUNCH(h, "decode_flags", hipLaunchKernelGGL(lk_decode_flags_kernel, dim3(nb), dim3(256), 0, h->stream,
-                                                 (const unsigned char*)d_msg, n, a, d.flags));
-    size_t tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, n_points, h->stream));
-    LAUNCH(h, "decode_scatter", hipLaunchKernelGGL(lk_decode_scatter_kernel, dim3(nb), dim3(256), 0, h->stream,
-                                                   (const unsigned char*)d_msg, n, a, d.flags, d.pos, d_out, n_out_d, fl));
-    unsigned int cnt = 0;
+    unsigned int dec_off[2] = {0, 0};
     double tfl[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&cnt, n_out_d, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(tfl, fl, sizeof(tfl), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_out = cnt;
+    LKCHK(front_decode(h, "decode_", d, (const unsigned char*)d_msg, 1, n_points, a, d_out, dec_off, tfl));
+    *n_out = dec_off[1];
     const double base = layout->lidar_type == 3 ? 0.0 : header_stamp;  // lidar_processing.cc:34-35,63-64 vs :91-92
     if (begin_time) *begin_time = base + tfl[0];
     if (end_time) *end_time = base + tfl[1];
@@ -1467,103 +1538,29 @@ int lk_decode_scan(lk_handle* h, const void* msg, size_t n_points, const lk_clou
                    float blind, double header_stamp, lk_point* out, size_t* n_out, double* begin_time, double* end_time) {
     CHECK_H(h);
     if (!msg || !layout || !out || n_points == 0) return fail(h, LK_ERR_INVALID, "lk_decode_scan: bad argument");
-    void* d_msg = nullptr;
     const size_t bytes = n_points * (size_t)layout->point_step;
-    HIPCHK(h, hipMalloc(&d_msg, bytes));
-    PrePool d;
-    int rc = pre_reserve(h, n_points, d);
-    if (rc == LK_OK) {
-        hipMemcpyAsync(d_msg, msg, bytes, hipMemcpyHostToDevice, h->stream);
-        rc = lk_decode_scan_dev(h, d_msg, n_points, layout, time_scale, filter_num, blind, header_stamp, d.out, n_out, begin_time, end_time);
-        if (rc == LK_OK) {
-            hipMemcpyAsync(out, d.out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream);
-            hipStreamSynchronize(h->stream);
-        }
-    }
-    hipFree(d_msg);
-    return rc;
+    FrontPool d;
+    LKCHK(front_reserve(h, n_points, 1, n_points, bytes, d));
+    HIPCHK(h, hipMemcpyAsync(d.io_in, msg, bytes, hipMemcpyHostToDevice, h->stream));
+    LKCHK(lk_decode_scan_dev(h, d.io_in, n_points, layout, time_scale, filter_num, blind, header_stamp, d.io_out, n_out, begin_time, end_time));
+    HIPCHK(h, hipMemcpyAsync(out, d.io_out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
 }
 
 int lk_preprocess_scan_dev(lk_handle* h, const lk_point* d_raw, size_t n_raw, float leaf, lk_point* d_out, size_t* n_out) {
     CHECK_H(h);
     if (!d_raw || !d_out || !n_out || n_raw == 0 || !(leaf > 0.f)) return fail(h, LK_ERR_INVALID, "lk_preprocess_scan: bad argument");
     if (n_raw > 0x7fffffffu) return fail(h, LK_ERR_INVALID, "too many points");
-    PrePool d;
-    int rc = pre_reserve(h, n_raw, d);
-    if (rc) return rc;
-    const int n = (int)n_raw;
-    const int nb = (n + 255) / 256;
-    const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
-    int* mm = reinterpret_cast<int*>(d.misc);
-    const int init[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-    unsigned int* err = d.misc + 6;
-    unsigned int* ncells_d = d.misc + 7;
-    LAUNCH(h, "pre_minmax", hipLaunchKernelGGL(lk_pre_minmax_kernel, dim3(std::min(nb, 1024)), dim3(256), 0, h->stream, d_raw, n, mm));
-    LAUNCH(h, "pre_cellidx", hipLaunchKernelGGL(lk_pre_cellidx_kernel, dim3(nb), dim3(256), 0, h->stream, d_raw, n, inv, mm, d.k0,
-                                                d.v0, err));
-    size_t tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, n_raw, 0, 32, h->stream));
-    LAUNCH(h, "pre_heads", hipLaunchKernelGGL(lk_pre_heads_kernel, dim3(nb), dim3(256), 0, h->stream, d.k1, n, d.flags));
-    tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, n_raw, h->stream));
-    LAUNCH(h, "pre_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(nb), dim3(256), 0, h->stream, d.flags, d.pos, n,
-                                               d.starts, ncells_d));
-    LAUNCH(h, "pre_centroid", hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(nb), dim3(256), 0, h->stream, d_raw, d.v1,
-                                                 d.starts, ncells_d, n, d.cells, d.k0, d.v0));
-    unsigned int host_misc[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(host_misc, err, sizeof(host_misc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (host_misc[0]) return fail(h, LK_ERR_INVALID, "voxel grid leaf too small for the cloud extent (index overflow)");
-    const size_t nc = host_misc[1];
-    tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, nc, 0, 32, h->stream));
-    LAUNCH(h, "pre_gather", hipLaunchKernelGGL(lk_pre_gather_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream,
-                                               d.cells, d.v1, (int)nc, d_out));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_out = nc;
+    FrontPool d;
+    LKCHK(front_reserve(h, n_raw, 1, 0, 0, d));
+    // what the decode stage leaves behind for a scan: dec_off = { 0, n } | the initial bounds | the overflow word
+    const unsigned int init[9] = {0u, (unsigned int)n_raw, 0x7fffffffu, 0x7fffffffu, 0x7fffffffu, 0x80000000u, 0x80000000u, 0x80000000u, 0u};
+    HIPCHK(h, hipMemcpyAsync(d.dec_off, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+    unsigned int cell_off[2] = {0, 0};
+    LKCHK(front_grid(h, "pre_", nullptr, d, d_raw, (unsigned int)n_raw, 1, leaf, d_out, cell_off));
+    *n_out = cell_off[1];
     return LK_OK;
-}
-
-// ------------------------------------------------------------------ a run's lidar front end in one call (lk_pre_kernels.h, lk_dscan_*)
-// Three host round trips per call, none per message: after the decode (per-message decoded counts and raw times: empty messages are refused),
-// after the centroids (per-scan overflow words and cell offsets) and at the end.  Both sorts are rocPRIM's stable segmented radix sort with one
-// segment per scan, so ties keep the order the per-scan chain's global sorts keep.
-namespace {
-struct DscPool {   // the per-call view of h->dsc
-    unsigned int *flags, *pos, *sid, *k0, *k1, *v0, *v1;
-    int* starts;
-    lk_point *dec, *cells;
-    unsigned long long* msg_off;
-    unsigned int *pt_off, *dec_off, *cell_off, *err, *misc;
-    int* mm;
-    double* first_last;
-};
-// carves the arrays for P raw points of S messages out of `base` (nullptr: only counts) and returns the bytes they take
-size_t dsc_carve(void* base, size_t P, size_t S, DscPool& d) {
-    LkCarve c(base, 256);
-    d.flags = c.take<unsigned int>(P), d.pos = c.take<unsigned int>(P), d.sid = c.take<unsigned int>(P);
-    d.k0 = c.take<unsigned int>(P), d.k1 = c.take<unsigned int>(P), d.v0 = c.take<unsigned int>(P), d.v1 = c.take<unsigned int>(P);
-    d.starts = c.take<int>(P);
-    d.dec = c.take<lk_point>(P), d.cells = c.take<lk_point>(P);
-    d.msg_off = c.take<unsigned long long>(S);
-    d.pt_off = c.take<unsigned int>(S + 1), d.dec_off = c.take<unsigned int>(S + 1);
-    d.cell_off = c.take<unsigned int>(2 * S + 1), d.err = d.cell_off ? d.cell_off + S + 1 : nullptr;   // cell_off [S + 1] | err [S] taken as ONE array: they are read back with one copy
-    d.misc = c.take<unsigned int>(8);
-    d.mm = c.take<int>(6 * S);
-    d.first_last = c.take<double>(2 * S);
-    return c.total();
-}
-}  // namespace
-
-static int dsc_reserve(lk_handle* h, size_t P, size_t S, DscPool& d) {
-    LKCHK(reserve(h, h->dsc, dsc_carve(nullptr, P, S, d)));
-    dsc_carve(h->dsc.p, P, S, d);
-    size_t t1 = 0, t2 = 0;
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, d.flags, d.pos, P, h->stream));
-    HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)P, (unsigned int)S, d.dec_off, d.dec_off + 1, 0, 32,
-                                           h->stream));
-    return reserve(h, h->prim_tmp, std::max(t1, t2));
 }
 
 int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const uint64_t* msg_off, const uint32_t* n_points,
@@ -1588,62 +1585,25 @@ int lk_decode_scans_dev(lk_handle* h, const void* d_msgs, size_t n_msgs, const u
             return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: more than 0x7fffffff points from message " + std::to_string(s) + " on: split the run");
     }
     pt_off[S] = (unsigned int)P;
-    DscPool d;
-    int rc = dsc_reserve(h, P, S, d);
-    if (rc) return rc;
+    FrontPool d;
+    LKCHK(front_reserve(h, P, S, 0, 0, d));
     LkDecodeArgs a;
     a.lay = *layout, a.time_scale = time_scale, a.filter_num = filter_num, a.blind = blind;
-    const unsigned int n = (unsigned int)P, nb = (n + 255) / 256, Si = (unsigned int)S;
     const unsigned char* base = (const unsigned char*)d_msgs;
-    HIPCHK(h, hipMemcpyAsync(d.msg_off, msg_off, 8 * S, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d.pt_off, pt_off.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
-    // 1. decode: keep flags, compaction, scatter
-    LAUNCH(h, "dscan_flags", hipLaunchKernelGGL(lk_dscan_flags_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a, d.flags));
-    size_t tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, P, h->stream));
-    LAUNCH(h, "dscan_scatter", hipLaunchKernelGGL(lk_dscan_scatter_kernel, dim3(nb), dim3(256), 0, h->stream, base, d.msg_off, d.pt_off, (int)S, n, a,
-                                                  d.flags, d.pos, d.dec, d.sid, d.dec_off, d.first_last, d.mm, d.err));
-    std::vector<unsigned int> dec_off(S + 1);
+    if (S > 1) {
+        HIPCHK(h, hipMemcpyAsync(d.msg_off, msg_off, 8 * S, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d.pt_off, pt_off.data(), 4 * (S + 1), hipMemcpyHostToDevice, h->stream));
+    } else {
+        base += msg_off[0];
+    }
+    std::vector<unsigned int> dec_off(S + 1), cell_off(S + 1);
     std::vector<double> fl(2 * S);
-    HIPCHK(h, hipMemcpyAsync(dec_off.data(), d.dec_off, 4 * (S + 1), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(fl.data(), d.first_last, 8 * 2 * S, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    LKCHK(front_decode(h, "dscan_", d, base, S, P, a, d.dec, dec_off.data(), fl.data()));
     for (size_t s = 0; s < S; ++s)
         if (dec_off[s + 1] == dec_off[s])
             return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: message " + std::to_string(s) + " decodes to no points (filter_num / blind)");
-    const unsigned int D = dec_off[S], db = (D + 255) / 256;
-    // 2. voxel grid: per-scan bounds and cell keys, a stable sort by cell inside each scan, cells (a new one at every scan boundary), centroids
-    const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
-    const unsigned int gy = std::min(64u, std::max(1u, D / Si / 2048u));
-    LAUNCH(h, "dscan_minmax", hipLaunchKernelGGL(lk_dscan_minmax_kernel, dim3(Si, gy), dim3(256), 0, h->stream, d.dec, d.dec_off, d.mm));
-    LAUNCH(h, "dscan_cellidx", hipLaunchKernelGGL(lk_dscan_cellidx_kernel, dim3(db), dim3(256), 0, h->stream, d.dec, D, inv, d.mm, d.sid, d.k0, d.v0,
-                                                  d.err));
-    tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, D, Si, d.dec_off, d.dec_off + 1, 0, 32, h->stream));
-    LAUNCH(h, "dscan_heads", hipLaunchKernelGGL(lk_dscan_heads_kernel, dim3(db), dim3(256), 0, h->stream, d.k1, d.sid, D, d.flags));
-    tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_exclusive_scan(h->prim_tmp.p, tb, d.flags, d.pos, D, h->stream));
-    unsigned int* ncells_d = d.misc;
-    LAUNCH(h, "dscan_starts", hipLaunchKernelGGL(lk_pre_starts_kernel, dim3(db), dim3(256), 0, h->stream, d.flags, d.pos, (int)D, d.starts, ncells_d));
-    LAUNCH(h, "dscan_centroid", hipLaunchKernelGGL(lk_pre_centroid_kernel, dim3(db), dim3(256), 0, h->stream, d.dec, (const int*)d.v1, d.starts, ncells_d,
-                                                 (int)D, d.cells, d.k0, (int*)d.v0));
-    LAUNCH(h, "dscan_celloff", hipLaunchKernelGGL(lk_dscan_celloff_kernel, dim3((Si + 1 + 255) / 256), dim3(256), 0, h->stream, d.dec_off, d.pos, ncells_d,
-                                                  (int)S, d.cell_off));
-    std::vector<unsigned int> ce(2 * S + 1);   // cell_off [S + 1] | err [S]
-    HIPCHK(h, hipMemcpyAsync(ce.data(), d.cell_off, 4 * (2 * S + 1), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t s = 0; s < S; ++s)
-        if (ce[S + 1 + s])
-            return fail(h, LK_ERR_INVALID, "lk_decode_scans_dev: message " + std::to_string(s) +
-                                               ": voxel grid leaf too small for the cloud extent (index overflow)");
-    const unsigned int Cn = ce[S];
-    // 3. time sort inside each scan's cells, gather into the caller's buffer
-    tb = h->prim_tmp.cap;
-    HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, Cn, Si, d.cell_off, d.cell_off + 1, 0, 32, h->stream));
-    LAUNCH(h, "dscan_gather", hipLaunchKernelGGL(lk_pre_gather_kernel, dim3((Cn + 255) / 256), dim3(256), 0, h->stream, d.cells, (const int*)d.v1, (int)Cn,
-                                               d_out));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t s = 0; s <= S; ++s) scan_off[s] = ce[s];
+    LKCHK(front_grid(h, "dscan_", "lk_decode_scans_dev", d, d.dec, dec_off[S], S, leaf, d_out, cell_off.data()));
+    for (size_t s = 0; s <= S; ++s) scan_off[s] = cell_off[s];
     for (size_t s = 0; s < S; ++s) {
         const double b = layout->lidar_type == 3 ? 0.0 : header_stamp[s];  // lidar_processing.cc:34-35,63-64 vs :91-92
         if (t_begin) t_begin[s] = b + fl[2 * s];
@@ -1687,11 +1647,7 @@ static int mcl_reserve(lk_handle* h, size_t N, size_t F, size_t n_io, MclPool& d
     mcl_carve(h->mcl.p, N, F, n_io, d);
     size_t t1 = 0, t2 = 0;
     HIPCHK(h, lk_prim_exclusive_scan(nullptr, t1, d.k0, d.v0, N, h->stream));
-    if (F > 1)
-        HIPCHK(h, lk_prim_segmented_sort_pairs(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)N, (unsigned int)F, d.file_off, d.file_off + 1, 0, 31,
-                                               h->stream));
-    else
-        HIPCHK(h, lk_prim_sort_pairs(nullptr, t2, d.k0, d.k1, (const int*)d.v0, (int*)d.v1, N, 0, 31, h->stream));
+    HIPCHK(h, lk_prim_sort_pairs_in_segments(nullptr, t2, d.k0, d.k1, d.v0, d.v1, (unsigned int)N, (unsigned int)F, d.file_off, d.file_off + 1, 0, 31, h->stream));
     return reserve(h, h->prim_tmp, std::max(t1, t2));
 }
 
@@ -1732,7 +1688,7 @@ int lk_downsample_clouds_dev(lk_handle* h, const float* d_world, size_t n_files,
     const float inv = 1.0f / leaf;  // inverse_leaf_size_, float as in PCL
     HIPCHK(h, hipMemcpyAsync(d.file_off, foff.data(), 4 * (F + 1), hipMemcpyHostToDevice, h->stream));
     // 1. per-file bounds with the non-finite / range words, the files' grids
-    const unsigned int gy = (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / F)), std::max<size_t>(1, biggest / 4096));
+    const unsigned int gy = bounds_rows(F, biggest);
     LAUNCH(h, "mc_init", hipLaunchKernelGGL(lk_mc_init_kernel, dim3(fb), dim3(256), 0, h->stream, d.mm, d.status, (int)Fi));
     LAUNCH(h, "mc_bounds", hipLaunchKernelGGL(lk_mc_bounds_kernel, dim3(Fi, gy), dim3(256), 0, h->stream, pts, d.file_off, inv, d.mm, d.status));
     LAUNCH(h, "mc_grid", hipLaunchKernelGGL(lk_mc_grid_kernel, dim3(fb), dim3(256), 0, h->stream, d.mm, d.status, inv, (int)Fi, d.grid));
@@ -1746,10 +1702,7 @@ int lk_downsample_clouds_dev(lk_handle* h, const float* d_world, size_t n_files,
     // 2. a cell key per point, a stable sort by key inside each file, cells (a new one at every file boundary), their first points
     LAUNCH(h, "mc_keys", hipLaunchKernelGGL(lk_mc_keys_kernel, dim3(nb), dim3(256), 0, h->stream, pts, n, d.file_off, (int)Fi, inv, d.grid, d.k0, d.v0));
     size_t tb = h->prim_tmp.cap;
-    if (F > 1)
-        HIPCHK(h, lk_prim_segmented_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, n, Fi, d.file_off, d.file_off + 1, 0, 31, h->stream));
-    else
-        HIPCHK(h, lk_prim_sort_pairs(h->prim_tmp.p, tb, d.k0, d.k1, (const int*)d.v0, (int*)d.v1, N, 0, 31, h->stream));
+    HIPCHK(h, lk_prim_sort_pairs_in_segments(h->prim_tmp.p, tb, d.k0, d.k1, d.v0, d.v1, n, Fi, d.file_off, d.file_off + 1, 0, 31, h->stream));
     unsigned int *flags = d.k0, *pos = d.v0, *ncells_d = d.misc;
     LAUNCH(h, "mc_heads", hipLaunchKernelGGL(lk_mc_heads_kernel, dim3(nb), dim3(256), 0, h->stream, d.k1, n, d.file_off, (int)Fi, flags));
     tb = h->prim_tmp.cap;
@@ -1790,13 +1743,11 @@ int lk_downsample_clouds(lk_handle* h, const float* world, size_t n_files, const
 int lk_preprocess_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float leaf, lk_point* out_sorted, size_t* n_out) {
     CHECK_H(h);
     if (!raw || !out_sorted || n_raw == 0) return fail(h, LK_ERR_INVALID, "lk_preprocess_scan: bad argument");
-    PrePool d;
-    int rc = pre_reserve(h, n_raw, d);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(d.raw, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
-    rc = lk_preprocess_scan_dev(h, d.raw, n_raw, leaf, d.out, n_out);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(out_sorted, d.out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream));
+    FrontPool d;
+    LKCHK(front_reserve(h, n_raw, 1, n_raw, sizeof(lk_point) * n_raw, d));
+    HIPCHK(h, hipMemcpyAsync(d.io_in, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
+    LKCHK(lk_preprocess_scan_dev(h, reinterpret_cast<const lk_point*>(d.io_in), n_raw, leaf, d.io_out, n_out));
+    HIPCHK(h, hipMemcpyAsync(out_sorted, d.io_out, sizeof(lk_point) * (*n_out), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return LK_OK;
 }
@@ -1806,19 +1757,17 @@ int lk_process_raw_scan(lk_handle* h, const lk_point* raw, size_t n_raw, float l
     CHECK_H(h);
     if (!raw || n_raw == 0) return fail(h, LK_ERR_INVALID, "empty scan");
     if (n_imu && n_kin) return fail(h, LK_ERR_INVALID, "pass either IMU or kin+IMU messages, not both");
-    PrePool d;
-    int rc = pre_reserve(h, n_raw, d);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(d.raw, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
+    FrontPool d;
+    LKCHK(front_reserve(h, n_raw, 1, n_raw, sizeof(lk_point) * n_raw, d));
+    HIPCHK(h, hipMemcpyAsync(d.io_in, raw, sizeof(lk_point) * n_raw, hipMemcpyHostToDevice, h->stream));
     size_t nd = 0;
-    rc = lk_preprocess_scan_dev(h, d.raw, n_raw, leaf, d.out, &nd);
-    if (rc) return rc;
+    LKCHK(lk_preprocess_scan_dev(h, reinterpret_cast<const lk_point*>(d.io_in), n_raw, leaf, d.io_out, &nd));
     if (nd > h->map.max_scan) return fail(h, LK_ERR_CAPACITY, "downsampled scan exceeds max_scan_points");
     std::vector<lk_point> sorted(nd);
-    HIPCHK(h, hipMemcpyAsync(sorted.data(), d.out, sizeof(lk_point) * nd, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(sorted.data(), d.io_out, sizeof(lk_point) * nd, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (n_down) *n_down = nd;
-    return run_scan(h, sorted.data(), d.out, nd, t_begin, imus, n_imu, kins, n_kin, nullptr, out);
+    return run_scan(h, sorted.data(), d.io_out, nd, t_begin, imus, n_imu, kins, n_kin, nullptr, out);
 }
 
 // ------------------------------------------------------------------ batch replay against the frozen map

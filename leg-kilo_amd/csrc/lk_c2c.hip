@@ -130,12 +130,8 @@ struct C2cIndex {
     std::vector<unsigned int> h_off;   // the host copy of d_off: alive until the caller has synchronised
 };
 static dim3 c2c_blocks(size_t n) { return dim3((unsigned int)((n + 255) / 256)); }
-static unsigned int c2c_stride_blocks(size_t clouds, size_t biggest) {
-    return (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / clouds)), std::max<size_t>(1, biggest / 4096));
-}
 static int c2c_sort(lk_handle* h, void* tmp, size_t& tb, const C2cIndex& x, size_t N, size_t n) {
-    if (n > 1) HIPCHK(h, lk_prim_segmented_sort_pairs(tmp, tb, x.k0, x.k1, x.v0, x.v1, (unsigned int)N, (unsigned int)n, x.d_off, x.d_off + 1, 0, 31, h->stream));
-    else HIPCHK(h, lk_prim_sort_pairs(tmp, tb, x.k0, x.k1, (const int*)x.v0, (int*)x.v1, N, 0, 31, h->stream));
+    HIPCHK(h, lk_prim_sort_pairs_in_segments(tmp, tb, x.k0, x.k1, x.v0, x.v1, (unsigned int)N, (unsigned int)n, x.d_off, x.d_off + 1, 0, 31, h->stream));
     return LK_OK;
 }
 // bounds and status of one side's clouds in use (d_off64, d_used: the device copies of off and used, already on their way)
@@ -145,7 +141,7 @@ static int c2c_bounds(lk_handle* h, const float4* pts, const uint64_t* off, size
     for (unsigned int c : used) big = std::max(big, (size_t)(off[c + 1] - off[c]));
     LAUNCH(h, "c2c_init", hipLaunchKernelGGL(lk_c2c_init_kernel, c2c_blocks(n), dim3(256), 0, h->stream, mm, status, (unsigned int)n));
     if (!used.empty())
-        LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)used.size(), c2c_stride_blocks(used.size(), big)), dim3(256), 0, h->stream,
+        LAUNCH(h, "c2c_bounds", hipLaunchKernelGGL(lk_c2c_bounds_kernel, dim3((unsigned int)used.size(), bounds_rows(used.size(), big)), dim3(256), 0, h->stream,
                                                    pts, d_off64, d_used, reach, mm, status));
     return LK_OK;
 }

@@ -129,8 +129,7 @@ struct lk_handle {
     uint64_t ov_gen = 0;       // the snapshot the last overlay replay ran against (lk_overlay_export reads base blocks / planes of THAT map)
     bool grid_enable = true;   // LEGKILO_GRID=0 keeps batch replay on the hash table (A/B)
     int* d_grid_mm = nullptr;
-    DevBuf pre;                   // scratch of lk_decode_scan / lk_preprocess_scan (PrePool)
-    DevBuf dsc;                   // scratch of lk_decode_scans_dev (DscPool)
+    DevBuf pre;                   // scratch of the lidar front end: lk_decode_scan(_dev), lk_preprocess_scan(_dev), lk_decode_scans_dev, lk_process_raw_scan (FrontPool)
     DevBuf mcl;                   // scratch of lk_downsample_clouds(_dev) (MclPool)
     // batch replay with a per-scan insert overlay (lk_overlay_kernels.h): the pools of all slots, grow-only
     LkOverlay ov = {};
@@ -333,6 +332,12 @@ struct MapCompact {
 static bool lk_xid_enabled() {
     static const bool v = getenv("LEGKILO_XID") == nullptr || atoi(getenv("LEGKILO_XID")) != 0;
     return v;
+}
+
+// Rows of a bounds launch over many clouds (grid = clouds x rows, the rows of a cloud stride over its points): a row per 4096 points of the
+// biggest cloud, at most 1024, and at most 2^18 blocks in all   (map clouds: a cloud per file; cloud scores)
+static inline unsigned int bounds_rows(size_t clouds, size_t biggest) {
+    return (unsigned int)std::min<size_t>(std::min<size_t>(1024, std::max<size_t>(1, (1u << 18) / clouds)), std::max<size_t>(1, biggest / 4096));
 }
 
 static unsigned int next_pow2(unsigned int v) {

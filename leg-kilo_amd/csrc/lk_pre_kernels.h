@@ -5,6 +5,9 @@
 //   std::sort by curvature at KILO.cc:369-370                   -> stable radix sort on the order-preserving bit image
 // Definition (PCL leaves the order inside a cell and the output order undefined): oracle/preprocess_oracle.py.
 // HBM-bound streaming kernels: one lk_point (16 B, float4) per lane, coalesced.
+// ONE set of kernels for a scan and for a run of scans (front_decode / front_grid in legkilo_hip.hip): the kernels that must know a point's
+// scan (lk_dscan_*, further down) take the run's tables, or null pointers when the call holds one message; lk_pre_starts / centroid / gather
+// run over all cells of a call, whatever scans they belong to.
 #pragma once
 #include "lk_device.h"
 
@@ -34,16 +37,6 @@ __device__ __forceinline__ void lk_pre_minmax_merge(int lo[3], int hi[3], int* m
         atomicMax(&mm[3 + c], max(max(smax[c][0], smax[c][1]), max(smax[c][2], smax[c][3])));
     }
 }
-__global__ void __launch_bounds__(256) lk_pre_minmax_kernel(const lk_point* __restrict__ pts, int n, int* mm) {
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float4 p = reinterpret_cast<const float4*>(pts)[i];
-        const int v[3] = {lk_f2ord(p.x), lk_f2ord(p.y), lk_f2ord(p.z)};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lo[c] = min(lo[c], v[c]), hi[c] = max(hi[c], v[c]);
-    }
-    lk_pre_minmax_merge(lo, hi, mm);
-}
 
 // cell index idx = ijk0 + ijk1*div0 + ijk2*div0*div1 with ijk = floor(p * inv) - min_b (float arithmetic)
 __device__ __forceinline__ void lk_cell_grid(const int* __restrict__ mm, float inv, int mn[3], int dv[3]) {
@@ -57,22 +50,6 @@ __device__ __forceinline__ bool lk_cell_overflow(const int dv[3]) { return (doub
 __device__ __forceinline__ unsigned int lk_cell_key(float4 p, float inv, const int mn[3], const int dv[3]) {
     const int i0 = (int)floorf(p.x * inv) - mn[0], i1 = (int)floorf(p.y * inv) - mn[1], i2 = (int)floorf(p.z * inv) - mn[2];
     return (unsigned int)(i0 + i1 * dv[0] + i2 * dv[0] * dv[1]);
-}
-__global__ void __launch_bounds__(256)
-    lk_pre_cellidx_kernel(const lk_point* __restrict__ pts, int n, float inv, const int* __restrict__ mm,
-                          unsigned int* __restrict__ keys, int* __restrict__ vals, unsigned int* err) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int mn[3], dv[3];
-    lk_cell_grid(mm, inv, mn, dv);
-    if (i == 0 && lk_cell_overflow(dv)) atomicOr(err, 1u);  // PCL refuses this too
-    keys[i] = lk_cell_key(reinterpret_cast<const float4*>(pts)[i], inv, mn, dv);
-    vals[i] = i;
-}
-
-__global__ void __launch_bounds__(256) lk_pre_heads_kernel(const unsigned int* __restrict__ keys, int n, unsigned int* __restrict__ flags) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) flags[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
 
 __global__ void __launch_bounds__(256)
@@ -162,42 +139,13 @@ __device__ __forceinline__ float lk_decode_time(const unsigned char* t0, const u
     }
     return curv;
 }
-// per point: keep flag
-__global__ void __launch_bounds__(256)
-    lk_decode_flags_kernel(const unsigned char* __restrict__ data, int n, LkDecodeArgs a, unsigned int* __restrict__ flags) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    flags[i] = lk_decode_keep(data + (size_t)i * a.lay.point_step, i, a);
-}
-// scatter the kept points in input order; time arithmetic per handler
-__global__ void __launch_bounds__(256)
-    lk_decode_scatter_kernel(const unsigned char* __restrict__ data, int n, LkDecodeArgs a, const unsigned int* __restrict__ flags,
-                             const unsigned int* __restrict__ pos, lk_point* __restrict__ out, unsigned int* __restrict__ n_out,
-                             double* __restrict__ first_last) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned char* p0 = data + a.lay.off_time;
-    const unsigned char* pl = data + (size_t)(n - 1) * a.lay.point_step + a.lay.off_time;
-    const unsigned char* p = data + (size_t)i * a.lay.point_step;
-    double first_d, last_d;
-    const float curv = lk_decode_time(p0, pl, p, a, first_d, last_d);
-    if (i == 0) first_last[0] = first_d, first_last[1] = last_d;
-    if (i == n - 1) *n_out = pos[i] + flags[i];
-    if (flags[i]) {
-        lk_point o;
-        o.x = lk_ld_f32(p + a.lay.off_x), o.y = lk_ld_f32(p + a.lay.off_y), o.z = lk_ld_f32(p + a.lay.off_z);
-        o.curvature = curv;
-        out[pos[i]] = o;
-    }
-}
 
-
-// ---------------------------------------------------------------- a run's PointCloud2 messages in one call (lk_decode_scans_dev)
-// The per-scan chain above - decode flags, compaction, scatter, then min/max, cell keys, cell sort, heads, starts, centroids, time sort,
-// gather - over all messages at once.  Message s = raw points [pt_off[s], pt_off[s+1]) of the run, its bytes at base + msg_off[s].  Every
-// per-point quantity is the per-scan kernels' own arithmetic (the helpers above) with the point index counted from its message's first
-// point; the decoded points of message s are [dec_off[s], dec_off[s+1]) and carry their message id (sid), which keeps bounds, cell keys
-// and cells inside their scan.
+// ---------------------------------------------------------------- the front end over S messages (lk_decode_scan_dev, lk_preprocess_scan_dev: S = 1; lk_decode_scans_dev)
+// Decode flags, compaction, scatter, then min/max, cell keys, cell sort, heads, starts, centroids, time sort, gather, over all messages of a
+// call at once.  Message s = raw points [pt_off[s], pt_off[s+1]) of the call, its bytes at base + msg_off[s]; the point index of every
+// per-point quantity counts from its message's first point.  The decoded points of message s are [dec_off[s], dec_off[s+1]) and carry their
+// message id (sid), which keeps bounds, cell keys and cells inside their scan.  ONE message has no tables: pt_off == nullptr means "all n
+// points are message 0, at base", sid == nullptr "every point is scan 0" (branches the whole grid takes the same way).
 __device__ __forceinline__ int lk_msg_of_point(const unsigned int* __restrict__ pt_off, int S, unsigned int i) {
     int lo = 0, hi = S;   // pt_off[lo] <= i < pt_off[hi]
     while (hi - lo > 1) {
@@ -207,17 +155,28 @@ __device__ __forceinline__ int lk_msg_of_point(const unsigned int* __restrict__ 
     }
     return lo;
 }
+struct LkMsgPoint {
+    int s;                       // the point's message
+    unsigned int j, m;           // its index in the message, the message's points
+    const unsigned char* bytes;  // the message's first byte
+};
+__device__ __forceinline__ LkMsgPoint lk_msg_point(const unsigned char* __restrict__ base, const unsigned long long* __restrict__ msg_off,
+                                                   const unsigned int* __restrict__ pt_off, int S, unsigned int n, unsigned int i) {
+    if (!pt_off) return {0, i, n, base};
+    const int s = lk_msg_of_point(pt_off, S, i);
+    return {s, i - pt_off[s], pt_off[s + 1] - pt_off[s], base + msg_off[s]};
+}
+// per point: keep flag
 __global__ void __launch_bounds__(256)
     lk_dscan_flags_kernel(const unsigned char* __restrict__ base, const unsigned long long* __restrict__ msg_off, const unsigned int* __restrict__ pt_off,
                           int S, unsigned int n, LkDecodeArgs a, unsigned int* __restrict__ flags) {
     const unsigned int i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const int s = lk_msg_of_point(pt_off, S, i);
-    const unsigned int j = i - pt_off[s];
-    flags[i] = lk_decode_keep(base + msg_off[s] + (size_t)j * a.lay.point_step, (int)j, a);
+    const LkMsgPoint q = lk_msg_point(base, msg_off, pt_off, S, n, i);
+    flags[i] = lk_decode_keep(q.bytes + (size_t)q.j * a.lay.point_step, (int)q.j, a);
 }
-// scatter the kept points in input order with their message id; the first point of a message also writes the message's first / last
-// raw time, its first decoded index and the initial bounds / overflow word of its scan
+// scatter the kept points in input order (time arithmetic per handler) with their message id; the first point of a message also writes the
+// message's first / last raw time, its first decoded index and the initial bounds / overflow word of its scan
 __global__ void __launch_bounds__(256)
     lk_dscan_scatter_kernel(const unsigned char* __restrict__ base, const unsigned long long* __restrict__ msg_off, const unsigned int* __restrict__ pt_off,
                             int S, unsigned int n, LkDecodeArgs a, const unsigned int* __restrict__ flags, const unsigned int* __restrict__ pos,
@@ -225,13 +184,12 @@ __global__ void __launch_bounds__(256)
                             int* __restrict__ mm, unsigned int* __restrict__ err) {
     const unsigned int i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const int s = lk_msg_of_point(pt_off, S, i);
-    const unsigned int j = i - pt_off[s], m = pt_off[s + 1] - pt_off[s];
-    const unsigned char* mb = base + msg_off[s];
-    const unsigned char* p = mb + (size_t)j * a.lay.point_step;
+    const LkMsgPoint q = lk_msg_point(base, msg_off, pt_off, S, n, i);
+    const int s = q.s;
+    const unsigned char* p = q.bytes + (size_t)q.j * a.lay.point_step;
     double first_d, last_d;
-    const float curv = lk_decode_time(mb + a.lay.off_time, mb + (size_t)(m - 1) * a.lay.point_step + a.lay.off_time, p, a, first_d, last_d);
-    if (j == 0) {
+    const float curv = lk_decode_time(q.bytes + a.lay.off_time, q.bytes + (size_t)(q.m - 1) * a.lay.point_step + a.lay.off_time, p, a, first_d, last_d);
+    if (q.j == 0) {
         first_last[2 * s] = first_d, first_last[2 * s + 1] = last_d;
         dec_off[s] = pos[i];
 #pragma unroll
@@ -244,7 +202,7 @@ __global__ void __launch_bounds__(256)
         o.x = lk_ld_f32(p + a.lay.off_x), o.y = lk_ld_f32(p + a.lay.off_y), o.z = lk_ld_f32(p + a.lay.off_z);
         o.curvature = curv;
         out[pos[i]] = o;
-        sid[pos[i]] = (unsigned int)s;
+        if (sid) sid[pos[i]] = (unsigned int)s;
     }
 }
 // per-scan bounds: blockIdx.x = scan, gridDim.y blocks stride over its decoded points
@@ -260,24 +218,24 @@ __global__ void __launch_bounds__(256) lk_dscan_minmax_kernel(const lk_point* __
     }
     lk_pre_minmax_merge(lo, hi, mm + 6 * s);
 }
-// cell keys under each scan's own bounds; the scan's first point reports its overflow
+// cell keys under each scan's own bounds; the scan's first point reports its overflow (PCL refuses this too)
 __global__ void __launch_bounds__(256)
     lk_dscan_cellidx_kernel(const lk_point* __restrict__ pts, unsigned int n, float inv, const int* __restrict__ mm, const unsigned int* __restrict__ sid,
                             unsigned int* __restrict__ keys, unsigned int* __restrict__ vals, unsigned int* __restrict__ err) {
     const unsigned int i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const unsigned int s = sid[i];
+    const unsigned int s = sid ? sid[i] : 0u;
     int mn[3], dv[3];
     lk_cell_grid(mm + 6 * s, inv, mn, dv);
-    if ((i == 0 || sid[i - 1] != s) && lk_cell_overflow(dv)) err[s] = 1u;
+    if ((i == 0 || (sid && sid[i - 1] != s)) && lk_cell_overflow(dv)) err[s] = 1u;
     keys[i] = lk_cell_key(reinterpret_cast<const float4*>(pts)[i], inv, mn, dv);
     vals[i] = i;
 }
-// lk_pre_heads_kernel with a new cell at every scan boundary as well (equal keys of two scans are two cells)
+// a cell starts where the sorted key changes, and at every scan boundary as well (equal keys of two scans are two cells)
 __global__ void __launch_bounds__(256)
     lk_dscan_heads_kernel(const unsigned int* __restrict__ keys, const unsigned int* __restrict__ sid, unsigned int n, unsigned int* __restrict__ flags) {
     const unsigned int i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) flags[i] = (i == 0 || keys[i] != keys[i - 1] || sid[i] != sid[i - 1]) ? 1u : 0u;
+    if (i < n) flags[i] = (i == 0 || keys[i] != keys[i - 1] || (sid && sid[i] != sid[i - 1])) ? 1u : 0u;
 }
 // first cell of every scan (the rank of its first decoded point among the cell heads) and the total: the scans' CSR offsets over the cells
 __global__ void __launch_bounds__(256)

@@ -16,6 +16,12 @@ hipError_t lk_prim_exclusive_scan(void* tmp, size_t& bytes, const unsigned int* 
 hipError_t lk_prim_segmented_sort_pairs(void* tmp, size_t& bytes, const unsigned int* keys_in, unsigned int* keys_out, const unsigned int* vals_in,
                                         unsigned int* vals_out, unsigned int n, unsigned int n_segments, const unsigned int* begin, const unsigned int* end,
                                         unsigned int bit0, unsigned int bit1, hipStream_t stream);
+// the same sort for segments that tile [0, n) (begin[0] = 0, end[n_segments - 1] = n): the segmented sort gives a segment to ONE workgroup, so a single
+// segment - all n pairs - goes through the device-wide stable sort instead; same result, same calling convention (the size query takes the same branch)
+// (the voxel grids of the lidar front end - a segment per scan -, of the map clouds - per file - and of the cloud scores - per cloud)
+hipError_t lk_prim_sort_pairs_in_segments(void* tmp, size_t& bytes, const unsigned int* keys_in, unsigned int* keys_out, const unsigned int* vals_in,
+                                          unsigned int* vals_out, unsigned int n, unsigned int n_segments, const unsigned int* begin, const unsigned int* end,
+                                          unsigned int bit0, unsigned int bit1, hipStream_t stream);
 // inclusive scan of per-leg transition maps under composition (the leg kinematics front end's contact detectors, lk_kin.hip): byte = 4 x 2 bits,
 // bits 2j / 2j+1 = the image of state 0 / 1 of leg j; out[i] = in[i] o ... o in[0] (in[0] applied first).  Associative, not commutative: order kept.
 hipError_t lk_prim_compose_scan(void* tmp, size_t& bytes, const unsigned char* in, unsigned char* out, size_t n, hipStream_t stream);

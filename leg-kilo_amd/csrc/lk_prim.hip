@@ -17,6 +17,12 @@ hipError_t lk_prim_segmented_sort_pairs(void* tmp, size_t& bytes, const unsigned
                                         unsigned int bit0, unsigned int bit1, hipStream_t stream) {
     return rocprim::segmented_radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, n_segments, begin, end, bit0, bit1, stream);
 }
+hipError_t lk_prim_sort_pairs_in_segments(void* tmp, size_t& bytes, const unsigned int* keys_in, unsigned int* keys_out, const unsigned int* vals_in,
+                                          unsigned int* vals_out, unsigned int n, unsigned int n_segments, const unsigned int* begin, const unsigned int* end,
+                                          unsigned int bit0, unsigned int bit1, hipStream_t stream) {
+    if (n_segments > 1) return lk_prim_segmented_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, n_segments, begin, end, bit0, bit1, stream);
+    return lk_prim_sort_pairs(tmp, bytes, keys_in, keys_out, (const int*)vals_in, (int*)vals_out, n, bit0, bit1, stream);   // (the values are only moved)
+}
 namespace {
 struct LkComposeMaps {   // (a then b): leg j of the result maps x to b_j(a_j(x))
     __host__ __device__ unsigned char operator()(unsigned char a, unsigned char b) const {

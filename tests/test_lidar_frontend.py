@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cloudcases as cc
 import preprocess_oracle as po
 import scenes
 from legkilo_amd import config, synth
@@ -356,3 +357,150 @@ def test_bag_bytes_to_poses_leg_fusion_and_imu(oracle_lib, hip_lib):
         for d in dptrs:
             g.device_free(d)
         g.close()
+
+
+# ------------------------------------------------------------------ one body for a scan and a run
+def _oracle(raw, lidar_type, fn, blind, leaf, stamp):
+    dec, b, e = po.decode(raw, lidar_type, cc.SCALE[lidar_type], fn, blind, header_stamp=float(stamp))
+    return dec, po.preprocess(dec, leaf), b, e
+
+
+def _assert_run_equals_oracle_and_chain(dev, msgs, lidar_type, fn, blind, leaf, seed=0, chain=True):
+    """lk_decode_scans_dev on msgs == po.decode + po.preprocess per message (bits) == the per-scan entries on the same device bytes."""
+    buf, msg_off, n_points = synth.pack_cloud_run(msgs, seed=seed)
+    stamps = cc.run_stamps(len(msgs))
+    layout, scale = synth.cloud_layout(lidar_type), cc.SCALE[lidar_type]
+    dev.g.h2d(dev.d_msgs, buf)
+    got, tb, te, so = dev.batch(msg_off, n_points, stamps, layout, scale, fn, blind, leaf)
+    want = [_oracle(m, lidar_type, fn, blind, leaf, stamps[s]) for s, m in enumerate(msgs)]
+    assert [int(v) for v in so] == [0] + [int(v) for v in np.cumsum([len(w[1]) for w in want])]
+    for s, (_, w, b, e) in enumerate(want):
+        assert got[s].tobytes() == w.tobytes(), (s, len(got[s]), len(w))
+        assert (tb[s], te[s]) == (b, e), s
+    if chain:
+        outs, cb, ce = dev.per_scan(msg_off, n_points, stamps, layout, scale, fn, blind, leaf)
+        for s in range(len(msgs)):
+            assert outs[s].tobytes() == got[s].tobytes(), s
+        assert np.array_equal(cb, tb) and np.array_equal(ce, te)
+    return want
+
+
+@pytest.fixture(scope="module")
+def tied_cloud():
+    """20 610 points at leaf 0.5: ten copies, 16 m apart in x, of cloudcases' order_visible (cells of 3 .. 300 points whose float32 sums depend on
+    the order) and stamps (one cell per lattice site) clouds.  Sent with cc.as_message its stamps are the 50 bins of 2 ms: the time sort meets
+    runs of equal keys, and the single-block radix sort (up to 1 024 pairs) holds neither the points nor the cells."""
+    leaf = 0.5
+    base = np.concatenate([cc.grid_case(f"order_visible[{leaf}]").pts, cc.grid_case(f"stamps[{leaf}]").pts])
+    copies = []
+    for k in range(10):
+        c = base.copy()
+        c["x"] = (c["x"].astype(np.float64) + 32 * leaf * k).astype(np.float32)
+        copies.append(c)
+    return np.concatenate(copies), leaf
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lidar_type", [1, 2, 3])
+def test_one_message_runs_take_the_other_sort(hip_lib, scene, run9, tied_cloud, lidar_type):
+    """A run of ONE message goes through the device-wide sort, not the segmented one: 1, 255, 256, 257 and 1 025 points (every point kept, so
+    the sorts see these sizes: either side of a block and of the single-block sort's 1 024), and one message of 20 610 points with full cells and
+    tied stamps.  Each equals the oracle and the per-scan entries bit for bit."""
+    big, big_leaf = tied_cloud
+    assert len(big) > 20000
+    dev = _Dev(hip_lib, scene, len(big) * 64, len(big), len(big))
+    try:
+        for n in (1, 255, 256, 257, 1025):
+            raw = synth.cloud_message(run9[1][:n], lidar_type, 100.0, seed=n)
+            want = _assert_run_equals_oracle_and_chain(dev, [raw], lidar_type, 1, 0.0, 0.3, seed=n)
+            assert len(want[0][0]) == n
+        want = _assert_run_equals_oracle_and_chain(dev, [cc.as_message(big, lidar_type, seed=5)], lidar_type, 1, 0.0, big_leaf, seed=6)
+        dec, out = want[0][0], want[0][1]
+        assert len(dec) == len(big) and 1024 < len(out) < len(dec) // 4                  # several points per cell
+        assert len(np.unique(out["curvature"])) < len(out) // 4                          # stamps tie in groups
+    finally:
+        dev.close()
+
+
+def _in_cell(n, cell, seed, leaf=0.5):
+    rng = np.random.default_rng(seed)
+    pts = np.zeros(n, dtype=synth.POINT_DTYPE)
+    xyz = (np.array(cell) + rng.uniform(0.1, 0.9, size=(n, 3))) * leaf
+    pts["x"], pts["y"], pts["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    return pts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lidar_type", [1, 2, 3])
+def test_two_message_boundary(hip_lib, scene, lidar_type):
+    """Runs of (1, 257) and (257, 1) points whose cell keys are equal on both sides of the scan boundary (keys count from each scan's own
+    minimum): two scans, so the message ids must decide - taken for one scan, the boundary cells would merge and share one set of bounds."""
+    one = _in_cell(1, (4, 2, 1), 1)
+    two_cells = np.concatenate([_in_cell(128, (0, 0, 0), 2), _in_cell(129, (1, 0, 0), 3)])[::-1].copy()
+    one_cell = _in_cell(257, (1, 1, 0), 4)
+    runs = ([one, two_cells], [one_cell, one])
+    for a, b in runs:
+        assert cc.sorted_keys(a, 0.5)[-1] == cc.sorted_keys(b, 0.5)[0] == 0
+    dev = _Dev(hip_lib, scene, 258 * 64, 257, 258)
+    try:
+        for k, clouds in enumerate(runs):
+            want = _assert_run_equals_oracle_and_chain(dev, [cc.as_message(c, lidar_type, seed=s) for s, c in enumerate(clouds)], lidar_type, 1, 0.0, 0.5,
+                                                       seed=k)
+            assert [len(w[1]) for w in want] == ([1, 2], [1, 1])[k]
+    finally:
+        dev.close()
+
+
+def _small_first_frame(g, scene, t0=2.0):
+    """The filter at the scene's state at t0 and a small map under it (2 500 points of a static scan): what lk_process_raw_scan needs."""
+    x0 = scenes.init_filter(g, scene, t0)
+    raw = synth.vlp16_scan(scene.world, scenes.Frozen(scene.traj, t0), t0, scene.P)[::11][:2500]
+    xb = scenes.xyz_of(raw)
+    g.map_build(scenes.world_of(x0, xb, scene.P), xb)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("poison", [False, True])
+def test_the_shared_pool_keeps_its_promises(hip_lib, scene, run9, monkeypatch, poison):
+    """One handle, one scratch pool for every front-end entry: a 7-message run, lk_preprocess_scan_dev on 300 points, the run again, the host
+    wrappers on a message larger than anything seen (the pool regrows, the staging arrays move), lk_process_raw_scan.  Every output equals the
+    oracle's bit for bit, the pose a fresh handle's.  Once more with fresh pools full of 0x5a bytes."""
+    if poison:
+        monkeypatch.setenv("LEGKILO_POISON_POOLS", "1")
+    else:
+        monkeypatch.delenv("LEGKILO_POISON_POOLS", raising=False)
+    lt, fn, blind, leaf = 1, 3, 0.0, 0.3
+    sizes = [1, 257, 2, 256, 255, 1025, 64]
+    msgs = [synth.cloud_message(run9[k][100 * k:100 * k + n], lt, 100.0 + 0.1 * k, seed=40 + k) for k, n in enumerate(sizes)]
+    big = synth.cloud_message(run9[8], lt, 101.0, seed=48)
+    assert len(big) > 4 * sum(sizes)
+    big_dec, big_out, big_b, big_e = _oracle(big, lt, fn, 1.5, leaf, 101.0)
+    pre = synth.preprocess_velodyne(synth.vlp16_scan(scene.world, scene.traj, 2.1, scene.P, seed_noise=3004), 3, 1.5)[:3000]
+    imus = synth.imu_stream(scene.traj, 2.1, 2.2, seed=3004)
+    fresh = hip_lib.LegKiloHip(scene.cfg())
+    try:
+        _small_first_frame(fresh, scene)
+        want_pose, want_nd = fresh.process_raw_scan(pre, leaf, 2.1, imus=imus)
+        want_x = fresh.get_state()[0]
+    finally:
+        fresh.close()
+    dev = _Dev(hip_lib, scene, sum(sizes) * 64, max(sizes), sum(sizes))
+    try:
+        g = dev.g
+        _small_first_frame(g, scene)
+        _assert_run_equals_oracle_and_chain(dev, msgs, lt, fn, blind, leaf, seed=9, chain=False)
+        pts300 = run9[7][:300]
+        g.h2d(dev.d_dec, pts300)
+        n300 = g.preprocess_scan_dev(dev.d_dec, 300, leaf, dev.d_ds)
+        got300 = np.zeros(n300, dtype=synth.POINT_DTYPE)
+        g.d2h(got300, dev.d_ds)
+        assert got300.tobytes() == po.preprocess(pts300, leaf).tobytes()
+        _assert_run_equals_oracle_and_chain(dev, msgs, lt, fn, blind, leaf, seed=9, chain=False)
+        dec, b, e = g.decode_scan(big.tobytes(), len(big), synth.cloud_layout(lt), cc.SCALE[lt], fn, 1.5, header_stamp=101.0)
+        assert dec.tobytes() == big_dec.tobytes() and (b, e) == (big_b, big_e)
+        assert g.preprocess_scan(dec, leaf).tobytes() == big_out.tobytes() and len(big_out) > sum(sizes)
+        pose, nd = g.process_raw_scan(pre, leaf, 2.1, imus=imus)
+        assert nd == want_nd == len(po.preprocess(pre, leaf)) and bytes(pose) == bytes(want_pose)
+        assert g.get_state()[0].tobytes() == want_x.tobytes()
+    finally:
+        dev.close()

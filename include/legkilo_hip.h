@@ -675,6 +675,70 @@ int lk_clouds_c2c(lk_handle* h,
                   size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
                   double max_dist, const double* thr, uint32_t n_thr,
                   lk_c2c* out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off);
+/* Rigid alignment of many pairs of clouds in one call: fine registration (point-to-point ICP) of a query cloud to a reference cloud from an initial
+ * guess within max_dist of the answer - what puts a slot's map, which lies in the frame of its first pose, into a survey's frame so that
+ * lk_clouds_c2c_dev means something.  The loop runs on the device with no host round trip between iterations.  leg-kilo_amd/cloudmetrics.py's
+ * align / transform are the numpy statements.  Point-to-plane, scale and global (coarse) registration are not offered.
+ * The clouds, offsets, pairs, max_dist, thr / n_thr and the optional nn outputs have exactly the layout and rules of lk_clouds_c2c_dev.
+ * T0: HOST, n_pairs x 12 doubles, row-major R then t; NULL means the identity.  max_iter: 0 .. 1000.  eps_rot: radians, eps_trans: metres; both
+ * finite and >= 0.  out: HOST, one lk_align per pair, every byte written.  c2c_out: HOST, optional, one lk_c2c per pair.
+ * Per pair T = (R, t) maps query to reference, r ~ R q + t, and starts as T0[k].  All arithmetic is float64, without fused multiply-add.
+ *   search under T  the moved point is m = ((R[3a] * x + R[3a+1] * y) + R[3a+2] * z) + t[a] per axis a, kept in float64 and never rounded to float32;
+ *                   dx = m_x - (double)r.x (dy, dz likewise), d2 = (dx*dx + dy*dy) + dz*dz; j(i) minimises (d2, j), the point is matched when
+ *                   d2 <= max_dist * max_dist.  A moved point that is not finite or has |m / max_dist| >= 2^30 is unmatched in that search - not
+ *                   an error of the pair.  A definition by brute force: the grid is not part of it.
+ *   solve           over the n matched points, from the ORIGINAL query points as doubles: pbar = (sum p_i) / n, rbar = (sum r_j(i)) / n,
+ *                   S[3a+b] = sum (p_i - pbar)_a (r_j(i) - rbar)_b, R' = the proper rotation of Horn's closed form for S (the one of
+ *                   lk_traj_ate_dev's alignment), t' = rbar - R' pbar.  Nothing is composed, so rounding does not build up over the iterations;
+ *                   the centroids are taken first and the centred products second, so rounding is of order 2^-53 extent^2 wherever the clouds lie.
+ *   step            step_rot = the angle of E = R' R^T as atan2(s, c), s = 0.5 |(E21 - E12, E02 - E20, E10 - E01)|, c = 0.5 (trace E - 1);
+ *                   step_trans = |(R' pbar + t') - (R pbar + t)|.
+ *   loop            1. search under T.  2. if iters == max_iter, or the pair has stopped, this search is the final one.  3. otherwise, if n < 3:
+ *                   LK_ALIGN_FEW, stop - this search is final and T stays.  4. otherwise solve, T = T', iters += 1.  5. if step_rot <= eps_rot
+ *                   and step_trans <= eps_trans: LK_ALIGN_CONVERGED, the next search is final.  A pair takes iters + 1 searches; max_iter == 0
+ *                   returns T0 with its figures.  (A solve that repeats the one before it to the bit has both steps exactly 0.)
+ *   final search    fills c2c_out[k] - the fields and rules of lk_c2c on the moved points, so c2c_out[k].rmse is the rmse under the returned T - and
+ *                   the optional d_nn_idx / d_nn_d2 / nn_off.
+ * A pair's sums are taken in an order that depends on the pair's own two clouds, T0[k] and the scalar arguments only: its record has the same bits
+ * whatever else the call holds.
+ * A pair with LK_ALIGN_NONFINITE or LK_ALIGN_RANGE (of the INPUT clouds, as lk_c2c's bits) or LK_ALIGN_BAD_T0 (a non-finite entry in T0[k]) gets T0[k]
+ * copied through, NaN figures, n_matched_first 0, iters 0, every nn entry unmatched; the other pairs are unaffected.  T0's rotation is not checked
+ * for orthogonality: the first solve replaces it.  Synchronous; no filter slot, map, overlay or bucket table is touched.
+ * LK_ERR_INVALID before anything is launched, the message naming the argument: every refusal of lk_clouds_c2c_dev, max_iter > 1000, an eps that is
+ * not finite or is < 0, out NULL.  LK_ERR_CAPACITY as for lk_clouds_c2c_dev.  A refused call writes nothing.
+ * lk_clouds_align: the same with query, ref, nn_idx and nn_d2 in HOST memory, like lk_clouds_c2c.
+ * lk_clouds_transform_dev writes moved clouds: record off[c] + i of d_in goes to entry off[c] - off[0] + i of d_out, x y z the moved point above
+ * under T[c] (HOST, n_clouds x 12 doubles) rounded ONCE to float32, w copied bit for bit - a float32 cloud is what lk_clouds_c2c_dev,
+ * lk_clouds_mme_dev and a PCD writer take next.  d_out may be exactly d_in + 4 * off[0] floats (in place); any other overlap, a null or misaligned
+ * (16 bytes) pointer, decreasing offsets, n_clouds == 0 and a non-finite T entry are LK_ERR_INVALID; 2^32 records or clouds or more LK_ERR_CAPACITY. */
+typedef struct lk_align {          /* 136 bytes */
+    double   rot[9], trans[3];     /* T: r ~ R q + t */
+    double   rmse_first;           /* rmse of the matched distances of the FIRST search (under T0); NaN when none matched */
+    double   step_rot, step_trans; /* of the last solve; NaN when iters == 0 */
+    uint64_t n_matched_first;
+    uint32_t iters;                /* solves taken */
+    uint32_t status;               /* LK_ALIGN_* bits */
+} lk_align;
+#define LK_ALIGN_NONFINITE 1u
+#define LK_ALIGN_RANGE     2u
+#define LK_ALIGN_FEW       4u
+#define LK_ALIGN_CONVERGED 8u
+#define LK_ALIGN_BAD_T0    16u
+int lk_clouds_align_dev(lk_handle* h,
+                        const float* d_query, size_t n_qclouds, const uint64_t* q_off,
+                        const float* d_ref,   size_t n_rclouds, const uint64_t* r_off,
+                        size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
+                        double max_dist, const double* thr, uint32_t n_thr,
+                        const double* T0, uint32_t max_iter, double eps_rot, double eps_trans,
+                        lk_align* out, lk_c2c* c2c_out, uint32_t* d_nn_idx, double* d_nn_d2, uint64_t* nn_off);
+int lk_clouds_align(lk_handle* h,
+                    const float* query, size_t n_qclouds, const uint64_t* q_off,
+                    const float* ref,   size_t n_rclouds, const uint64_t* r_off,
+                    size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
+                    double max_dist, const double* thr, uint32_t n_thr,
+                    const double* T0, uint32_t max_iter, double eps_rot, double eps_trans,
+                    lk_align* out, lk_c2c* c2c_out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off);
+int lk_clouds_transform_dev(lk_handle* h, const float* d_in, size_t n_clouds, const uint64_t* off, const double* T, float* d_out);
 /* Map scores that need NO reference, of many clouds in one call: mean map entropy (MME) and mean plane variance (MPV) over a map cloud itself -
  * both lower for a crisper map.  What a recorded run without ground truth or survey ranks its slots by; beside lk_clouds_c2c_dev, one small record
  * per cloud for the host.  leg-kilo_amd/cloudmetrics.py's mme is the numpy statement.

@@ -273,6 +273,35 @@ def c2c_dtype():
     return dt
 
 
+class lk_align(C.Structure):
+    _fields_ = [
+        ("rot", C.c_double * 9),
+        ("trans", C.c_double * 3),
+        ("rmse_first", C.c_double),
+        ("step_rot", C.c_double),
+        ("step_trans", C.c_double),
+        ("n_matched_first", C.c_uint64),
+        ("iters", C.c_uint32),
+        ("status", C.c_uint32),
+    ]
+
+
+LK_ALIGN_NONFINITE = 1   # lk_align.status: a coordinate of either INPUT cloud of the pair was not finite
+LK_ALIGN_RANGE = 2       # lk_align.status: |p / max_dist| >= 2^30 in either input cloud of the pair
+LK_ALIGN_FEW = 4         # lk_align.status: a search matched fewer than 3 points; T is the one of that search
+LK_ALIGN_CONVERGED = 8   # lk_align.status: the last solve moved by no more than eps_rot and eps_trans
+LK_ALIGN_BAD_T0 = 16     # lk_align.status: T0 of the pair held a non-finite entry
+
+
+def align_dtype():
+    """numpy view of lk_align (136 B): the records of lk_clouds_align_dev / lk_clouds_align."""
+    import numpy as np
+
+    dt = np.dtype(lk_align)
+    assert dt.itemsize == C.sizeof(lk_align) == 136
+    return dt
+
+
 class lk_mme(C.Structure):
     _fields_ = [
         ("mme", C.c_double),

@@ -647,9 +647,10 @@ class LegKiloHip:
         return self._traj_call(self.L.lk_runs_rpe_dev, abi.rpe_dtype(), (), run_bucket_off, (d_gt_t, d_gt_pos, d_gt_rot, gt_stride), gt_off, (max_dt, delta),
                                abi.LK_RPE_INDEX, by_index, flags)
 
-    def _c2c_call(self, fn, query, q_off, ref, r_off, pairs, max_dist, thr, nn_idx, nn_d2, want_nn_off):
-        """What the two C2C exports share - the host tables and the records: fn(handle, query, tables, ref, tables, pairs, max_dist, thr, records,
-        nn arrays).  Returns (records, nn_off or None)."""
+    def _c2c_call(self, fn, query, q_off, ref, r_off, pairs, max_dist, thr, nn_idx, nn_d2, want_nn_off, mid=(), want_c2c=True):
+        """What the C2C and alignment exports share - the host tables and the records: fn(handle, query, tables, ref, tables, pairs, max_dist, thr,
+        *mid, records, nn arrays); mid: what the alignment entries take in front of the lk_c2c records, which they accept as NULL (want_c2c False).
+        Returns (records, nn_off or None)."""
         qo = np.ascontiguousarray(q_off, dtype=np.uint64)
         ro = np.ascontiguousarray(r_off, dtype=np.uint64)
         pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
@@ -658,7 +659,7 @@ class LegKiloHip:
         res = np.zeros(max(len(pr), 1), dtype=abi.c2c_dtype())
         nn_off = np.zeros(len(pr) + 1, dtype=np.uint64) if want_nn_off else None
         self._chk(fn(self.h, query, max(len(qo) - 1, 0), _p(qo), ref, max(len(ro) - 1, 0), _p(ro), len(pr), _p(pq), _p(pref), max_dist,
-                     _p(th) if len(th) else None, len(th), _p(res), nn_idx, nn_d2, _p(nn_off)))
+                     _p(th) if len(th) else None, len(th), *mid, _p(res) if want_c2c else None, nn_idx, nn_d2, _p(nn_off)))
         return res[:len(pr)], nn_off
 
     def clouds_c2c_dev(self, d_query, q_off, d_ref, r_off, pairs, max_dist, thr=(), d_nn_idx=0, d_nn_d2=0):
@@ -683,6 +684,50 @@ class LegKiloHip:
         idx, d2 = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.float64)
         res, nn_off = self._c2c_call(self.L.lk_clouds_c2c, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, _p(idx), _p(d2), True)
         return res, nn_off, idx[:total], d2[:total]
+
+    def _align_call(self, fn, query, q_off, ref, r_off, pairs, max_dist, thr, T0, max_iter, eps_rot, eps_trans, nn_idx, nn_d2, want_c2c):
+        """What the two alignment exports share on top of _c2c_call: T0 as n rows of 12 doubles (R row-major, then t; None: the identity) and
+        the lk_align records.  Returns (align records, lk_c2c records or None, nn_off)."""
+        n = len(np.asarray(pairs).reshape(-1, 2))
+        t0 = None if T0 is None else np.ascontiguousarray(T0, dtype=np.float64).reshape(-1, 12)
+        assert t0 is None or len(t0) == n, "T0: one row of 12 doubles per pair"
+        out = np.zeros(max(n, 1), dtype=abi.align_dtype())
+        mid = (_p(t0) if t0 is not None else None, int(max_iter), float(eps_rot), float(eps_trans), _p(out))
+        res, nn_off = self._c2c_call(fn, query, q_off, ref, r_off, pairs, max_dist, thr, nn_idx, nn_d2, True, mid, want_c2c)
+        return out[:n], (res if want_c2c else None), nn_off
+
+    def clouds_align_dev(self, d_query, q_off, d_ref, r_off, pairs, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e-6, thr=(), d_nn_idx=0,
+                         d_nn_d2=0, want_c2c=True):
+        """Rigid alignment (point-to-point ICP) of many pairs of clouds in device memory (lk_clouds_align_dev): clouds_c2c_dev's clouds, tables and
+        pairs; per pair T = (R, t) with r ~ R q + t starts as T0[k] (12 doubles, R row-major then t; None: the identity) and takes up to max_iter
+        solves, each from the matches of a search under the current T, until a solve moves by no more than eps_rot (radians) and eps_trans
+        (metres).  Returns (abi.align_dtype() records, lk_c2c records of the final search or None, nn_off); d_nn_idx / d_nn_d2 take the final
+        search's neighbours.  cloudmetrics.align is the numpy statement; clouds_transform_dev writes the moved clouds."""
+        return self._align_call(self.L.lk_clouds_align_dev, d_query, q_off, d_ref, r_off, pairs, max_dist, thr, T0, max_iter, eps_rot, eps_trans,
+                                d_nn_idx or None, d_nn_d2 or None, want_c2c)
+
+    def clouds_align(self, query, q_off, ref, r_off, pairs, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e-6, thr=(), want_nn=False):
+        """The same with both sides in host memory (lk_clouds_align): query, ref float32 [n, 4].  Returns (align records, lk_c2c records, nn_off),
+        with want_nn (..., nn_idx uint32, nn_d2 float64)."""
+        q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1, 4)
+        r = np.ascontiguousarray(ref, dtype=np.float32).reshape(-1, 4)
+        if not want_nn:
+            return self._align_call(self.L.lk_clouds_align, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, T0, max_iter, eps_rot, eps_trans, None, None, True)
+        qo = np.asarray(q_off, dtype=np.uint64)
+        total = int(sum(int(qo[a + 1] - qo[a]) for a in np.asarray(pairs, dtype=np.int64).reshape(-1, 2)[:, 0]))
+        idx, d2 = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.float64)
+        out, res, nn_off = self._align_call(self.L.lk_clouds_align, _p(q), q_off, _p(r), r_off, pairs, max_dist, thr, T0, max_iter, eps_rot, eps_trans,
+                                            _p(idx), _p(d2), True)
+        return out, res, nn_off, idx[:total], d2[:total]
+
+    def clouds_transform_dev(self, d_in, off, T, d_out):
+        """Moved clouds in device memory (lk_clouds_transform_dev): record off[c] + i of d_in goes to entry off[c] - off[0] + i of d_out with x y z
+        moved under T[c] (12 doubles, R row-major then t) in float64 and rounded once to float32, w copied.  d_out may be d_in + 16 * off[0] bytes
+        (in place).  cloudmetrics.transform is the numpy statement."""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        t = np.ascontiguousarray(T, dtype=np.float64).reshape(-1, 12)
+        assert len(t) == max(len(o) - 1, 0), "T: one row of 12 doubles per cloud"
+        self._chk(self.L.lk_clouds_transform_dev(self.h, d_in, max(len(o) - 1, 0), _p(o), _p(t) if len(t) else None, d_out))
 
     def _mme_call(self, fn, clouds, off, radius, min_pts, n_arr, h_arr, lmin_arr):
         """What the two MME exports share - the offset table and the records: fn(handle, clouds, table, radius, min_pts, records, per-point arrays).

@@ -65,6 +65,145 @@ def c2c(query, ref, max_dist, thr=()):
     return out
 
 
+LK_ALIGN_NONFINITE, LK_ALIGN_RANGE, LK_ALIGN_FEW, LK_ALIGN_CONVERGED, LK_ALIGN_BAD_T0 = 1, 2, 4, 8, 16
+
+
+def move(cloud, T):
+    """The float64 moved points [n, 3] of lk_clouds_align_dev: m = ((R[a,0] x + R[a,1] y) + R[a,2] z) + t[a] from the float32 coordinates; T = 12
+    doubles, R row-major then t."""
+    p = np.asarray(cloud, dtype=np.float32)[:, :3].astype(np.float64)
+    T = np.asarray(T, dtype=np.float64).reshape(12)
+    return np.stack([((T[3 * a] * p[:, 0] + T[3 * a + 1] * p[:, 1]) + T[3 * a + 2] * p[:, 2]) + T[9 + a] for a in range(3)], axis=1)
+
+
+def transform(cloud, T):
+    """lk_clouds_transform_dev's statement for one cloud of x y z w records: the moved points rounded once to float32, w kept bit for bit."""
+    rec = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4)
+    out = rec.copy()
+    with np.errstate(over="ignore", invalid="ignore"):
+        out[:, :3] = move(rec, T).astype(np.float32)
+    out[:, 3].view(np.uint32)[:] = rec[:, 3].view(np.uint32)
+    return out
+
+
+def nearest_moved(moved, ref, max_dist, block=2048):
+    """(j, d2, matched) of float64 moved points [n, 3] over the whole float32 reference cloud by brute force, as lk_clouds_align_dev's search under
+    T: a point that is not finite or has |m / max_dist| >= 2^30 is unmatched; j = NO_MATCH and d2 = inf where unmatched.  (By brute force the
+    guard changes nothing - a float32 reference point in range lies 64 max_dist or more inside the bound - it is stated because the definition
+    states it; what it protects is the cell arithmetic of the grid search.)"""
+    m = np.asarray(moved, dtype=np.float64).reshape(-1, 3)
+    r = np.asarray(ref, dtype=np.float32)[:, :3].astype(np.float64)
+    j = np.full(len(m), NO_MATCH, dtype=np.uint32)
+    d2 = np.full(len(m), np.inf)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ok = (np.abs(m / max_dist) < 2.0 ** 30).all(axis=1)
+    if len(r) and ok.any():
+        idx = np.flatnonzero(ok)
+        block = max(1, min(block, (1 << 21) // len(r)))
+        for a in range(0, len(idx), block):
+            sel = idx[a:a + block]
+            d = m[sel, None, :] - r[None, :, :]
+            s = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            k = np.argmin(s, axis=1)
+            j[sel], d2[sel] = k, s[np.arange(len(k)), k]
+    matched = d2 <= max_dist * max_dist
+    j[~matched], d2[~matched] = NO_MATCH, np.inf
+    return j, d2, matched
+
+
+def horn_rotation(S):
+    """The proper rotation of Horn's closed form for the centred cross-covariance S [3, 3] (S[a, b] = sum p_a r_b): the unit quaternion that is
+    the eigenvector of the largest eigenvalue of the symmetric 4 x 4 matrix N, through numpy.linalg.eigh."""
+    S = np.asarray(S, dtype=np.float64).reshape(3, 3)
+    if not np.isfinite(S).all() or not np.abs(S).max() > 0.0:
+        return np.eye(3)
+    S = S / np.abs(S).max()
+    (Sxx, Sxy, Sxz), (Syx, Syy, Syz), (Szx, Szy, Szz) = S
+    N = np.array([[Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx],
+                  [Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz],
+                  [Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy],
+                  [Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz]])
+    w, x, y, z = np.linalg.eigh(N)[1][:, -1]
+    n = np.sqrt((w * w + x * x) + (y * y + z * z))
+    w, x, y, z = w / n, x / n, y / n, z / n
+    return np.array([[(w * w + x * x) - (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                     [2.0 * (x * y + w * z), (w * w + y * y) - (x * x + z * z), 2.0 * (y * z - w * x)],
+                     [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), (w * w + z * z) - (x * x + y * y)]])
+
+
+def align_step(T, Tn, pbar):
+    """(step_rot, step_trans) from T to Tn (12 doubles each) as lk_clouds_align_dev states them: the angle of R' R^T in the atan2 form, and the
+    distance the query centroid pbar moves."""
+    R, Rn = np.asarray(T[:9]).reshape(3, 3), np.asarray(Tn[:9]).reshape(3, 3)
+    E = np.array([[(Rn[i, 0] * R[j, 0] + Rn[i, 1] * R[j, 1]) + Rn[i, 2] * R[j, 2] for j in range(3)] for i in range(3)])
+    v = np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]])
+    s, c = 0.5 * np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]), 0.5 * (((E[0, 0] + E[1, 1]) + E[2, 2]) - 1.0)
+    mv = lambda X: np.array([((X[3 * a] * pbar[0] + X[3 * a + 1] * pbar[1]) + X[3 * a + 2] * pbar[2]) + X[9 + a] for a in range(3)])   # noqa: E731
+    d = mv(Tn) - mv(T)
+    return float(np.arctan2(s, c)), float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
+
+
+def align(query, ref, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e-6, thr=(), variant=None):
+    """Rigid alignment of one pair as lk_clouds_align_dev defines it: search under T by brute force on the float64 moved points, Horn's solve from
+    the original points of the matched pairs, until a solve moves by no more than both eps or max_iter solves are taken.  Returns a dict: T [12]
+    (R row-major, then t), iters, status, rmse_first, n_matched_first, step_rot, step_trans, first = (j, matched) of the first search, and c2c -
+    the final search as c2c's dict (j, d2, matched, rmse, mean, max, n_query, n_matched, n_within, worst, status).
+    variant (test aid): one of the wrong restatements tests/test_align_host.py expects to fail - "compose", "reflect", "all_n", "one_eps"."""
+    q, r = np.asarray(query, dtype=np.float32)[:, :3], np.asarray(ref, dtype=np.float32)[:, :3]
+    n = len(q)
+    thr = [float(t) for t in thr]
+    T = np.array([1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0, 0, 0, 0]) if T0 is None else np.asarray(T0, dtype=np.float64).reshape(12).copy()
+    st = status(q, r, max_dist) | (0 if np.isfinite(T).all() else LK_ALIGN_BAD_T0)
+    none = dict(j=np.full(n, NO_MATCH, dtype=np.uint32), d2=np.full(n, np.inf), matched=np.zeros(n, dtype=bool), rmse=np.nan, mean=np.nan, max=np.nan,
+                n_query=n, n_matched=0, n_within=[0] * len(thr), worst=0, status=st & 3)
+    out = dict(T=T, iters=0, status=st, rmse_first=np.nan, n_matched_first=0, step_rot=np.nan, step_trans=np.nan, first=(none["j"], none["matched"]), c2c=none)
+    if st:
+        return out
+    q64, r64 = q.astype(np.float64), r.astype(np.float64)
+    iters, stopped, first = 0, False, None
+    while True:
+        j, d2, m = nearest_moved(move(q, T), r, max_dist)
+        if first is None:
+            first = (j.copy(), m.copy())
+            out.update(n_matched_first=int(m.sum()), rmse_first=float(np.sqrt(d2[m].sum() / m.sum())) if m.any() else np.nan, first=first)
+        if iters == max_iter or stopped:
+            break
+        if m.sum() < 3:
+            st |= LK_ALIGN_FEW
+            break
+        P, G = q64[m], r64[j[m]]
+        cnt = n if variant == "all_n" else len(P)
+        pbar, rbar = P.sum(axis=0) / cnt, G.sum(axis=0) / cnt
+        if variant == "compose":      # the solve from the MOVED points, composed onto T, about the origin instead of the centroids
+            Pm = move(q[m], T)
+            Rd = horn_rotation(Pm.T @ G)
+            td = rbar - Rd @ (Pm.sum(axis=0) / cnt)
+            Rn = Rd @ T[:9].reshape(3, 3)
+            Tn = np.r_[Rn.reshape(9), Rd @ T[9:] + td]
+        else:
+            S = (P - pbar).T @ (G - rbar)
+            if variant == "reflect":  # SVD without the determinant fix
+                U, _, Vt = np.linalg.svd(S)
+                Rn = Vt.T @ U.T
+            else:
+                Rn = horn_rotation(S)
+            Tn = np.r_[Rn.reshape(9), rbar - np.array([(Rn[a, 0] * pbar[0] + Rn[a, 1] * pbar[1]) + Rn[a, 2] * pbar[2] for a in range(3)])]
+        step_rot, step_trans = align_step(T, Tn, pbar)
+        T, iters = Tn, iters + 1
+        out.update(step_rot=step_rot, step_trans=step_trans)
+        if step_rot <= eps_rot and (variant == "one_eps" or step_trans <= eps_trans):
+            st |= LK_ALIGN_CONVERGED
+            stopped = True
+    fin = dict(none, status=0)
+    fin.update(j=j, d2=d2, matched=m)
+    if m.any():
+        v = d2[m]
+        fin.update(rmse=float(np.sqrt(v.sum() / len(v))), mean=float(np.sqrt(v).sum() / len(v)), max=float(np.sqrt(v.max())), n_matched=int(len(v)),
+                   n_within=[int((v <= t * t).sum()) for t in thr], worst=int(np.flatnonzero(m)[np.argmax(v)]))
+    out.update(T=T, iters=iters, status=st, c2c=fin)
+    return out
+
+
 def fscore(acc_rec, comp_rec, k):
     """(precision, recall, F) at threshold k from the records of the two directions: acc_rec - the map as query against the survey, comp_rec - the
     survey as query against the map (lk_c2c records, or c2c's dicts).  precision = n_within[k] / n_query of the first, recall the same of the

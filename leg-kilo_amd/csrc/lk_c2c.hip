@@ -1,17 +1,21 @@
 // lk_c2c.hip - the map-cloud metric unit of liblegkilo_hip.so (see lk_internal.h): cloud-to-cloud nearest-neighbour distance of many pairs of clouds
 // in one call (lk_c2c_kernels.h, arithmetic in lk_c2c.h) and the two C-ABI entries around it - lk_clouds_c2c_dev over clouds in HBM (a run replay's
 // d_world_out, lk_downsample_clouds_dev's d_out), lk_clouds_c2c over clouds in host memory - and, on the same search structure (c2c_index), the
-// scores that need no reference: mean map entropy and mean plane variance (lk_mme_kernels.h, arithmetic in lk_mme.h), lk_clouds_mme_dev / lk_clouds_mme.
+// scores that need no reference: mean map entropy and mean plane variance (lk_mme_kernels.h, arithmetic in lk_mme.h), lk_clouds_mme_dev / lk_clouds_mme,
+// and the rigid alignment of a query cloud to its reference (lk_align_kernels.h, arithmetic in lk_align.h): lk_clouds_align_dev / lk_clouds_align run
+// c2c_run's call with the search iterated under a transform, lk_clouds_transform_dev writes the moved clouds.
 // What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
 // use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
 #define LK_TU_C2C 1
 #include "lk_internal.h"
 #include "lk_c2c_kernels.h"
+#include "lk_align_kernels.h"
 #include "lk_mme_kernels.h"
 
 static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
 static_assert(sizeof(lk_mme) == 64, "lk_mme must be 64 B");
+static_assert(sizeof(lk_align) == 136, "lk_align must be 136 B");
 static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
 
 namespace {
@@ -27,6 +31,12 @@ struct C2cArgs {   // the arguments both entries share, as the caller gave them
     uint32_t* nn_idx;
     double* nn_d2;
     uint64_t* nn_off;
+};
+struct AlignArgs {   // what lk_clouds_align(_dev) adds to them (C2cArgs::out is then c2c_out, which may be null)
+    const double* T0;
+    uint32_t max_iter;
+    double eps_rot, eps_trans;
+    lk_align* out;
 };
 struct C2cSpan {   // a named range of bytes (p = 0: not given)
     const char* name;
@@ -174,8 +184,9 @@ static int c2c_index(lk_handle* h, const float4* pts, const uint64_t* off, size_
     return LK_OK;
 }
 
-// the call behind c2c_check, on DEVICE clouds and DEVICE nn arrays (null: the library's own)
-static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
+// the call behind c2c_check, on DEVICE clouds and DEVICE nn arrays (null: the library's own).  al: the alignment's arguments - step 3 is then the
+// loop of lk_align_kernels.h, enqueued back to back: max_iter + 1 searches with max_iter solves between them, and the same final reduce
+static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs* al = nullptr) {
     const size_t NQ = a.n_q, NR = a.n_r, P = a.n_pairs, N = (size_t)(a.r_off[NR] - a.r_off[0]);
     const std::vector<unsigned int> uq = used_clouds(a.pair_q, P, NQ), ur = used_clouds(a.pair_r, P, NR);
     LkC2cQuery q = {};
@@ -183,6 +194,8 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     unsigned long long *d_qoff = nullptr, *d_nnoff = nullptr;
     unsigned int *d_pq = nullptr, *d_pr = nullptr, *d_uq = nullptr, *q_status = nullptr;
     int* q_mm = nullptr;
+    LkAlignCall call = {};
+    double* d_T0 = nullptr;
     auto carve = [&](void* base) {
         LkCarve c(base, 256);
         d_qoff = c.take<unsigned long long>(NQ + 1), x.d_off64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
@@ -195,6 +208,7 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
         x.recs = c.take<LkC2cRec>(N);
         q.nn_idx = c2c_or_own(c, a.nn_idx, total), q.nn_d2 = c2c_or_own(c, a.nn_d2, total);   // (c2c_check: both or neither)
         q.out = c.take<lk_c2c>(P);
+        d_T0 = c.take<double>(al ? 12 * P : 0), call.rec = c.take<lk_align>(al ? P : 0), call.done = c.take<unsigned int>(al ? P : 0);
         return c.total();
     };
     const size_t bytes = carve(nullptr);
@@ -219,12 +233,35 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total) {
     q.reach2 = lk_c2c_reach2(a.max_dist);
     for (uint32_t k = 0; k < 4; ++k) q.thr2[k] = k < a.n_thr ? a.thr[k] * a.thr[k] : 0.0;
     q.n_pairs = (unsigned int)P, q.n_thr = a.n_thr;
-    if (total) LAUNCH(h, "c2c_query", hipLaunchKernelGGL(lk_c2c_query_kernel, c2c_blocks(total), dim3(256), 0, h->stream, q, (unsigned long long)total));
+    std::vector<double> t0;          // alive until the stream has been synchronised
+    std::vector<lk_align> arec;
+    if (!al) {
+        if (total) LAUNCH(h, "c2c_query", hipLaunchKernelGGL(lk_c2c_query_kernel, c2c_blocks(total), dim3(256), 0, h->stream, q, (unsigned long long)total));
+    } else {
+        t0.resize(12 * P);
+        for (size_t k = 0; k < P; ++k)
+            for (int i = 0; i < 12; ++i) t0[12 * k + i] = al->T0 ? al->T0[12 * k + i] : ((i == 0 || i == 4 || i == 8) ? 1.0 : 0.0);
+        HIPCHK(h, hipMemcpyAsync(d_T0, t0.data(), 8 * t0.size(), hipMemcpyHostToDevice, h->stream));
+        call.q = q, call.r_pts = rpts, call.r_off64 = x.d_off64, call.T0 = d_T0;
+        call.max_dist = a.max_dist, call.eps_rot = al->eps_rot, call.eps_trans = al->eps_trans;
+        LAUNCH(h, "align_init", hipLaunchKernelGGL(lk_align_init_kernel, c2c_blocks(P), dim3(256), 0, h->stream, call));
+        for (uint32_t it = 0; it <= al->max_iter; ++it) {
+            if (total)
+                LAUNCH(h, "align_search", hipLaunchKernelGGL(lk_align_search_kernel, c2c_blocks(total), dim3(256), 0, h->stream, call, (unsigned long long)total, it == 0 ? 1 : 0));
+            if (it < al->max_iter) LAUNCH(h, "align_solve", hipLaunchKernelGGL(lk_align_solve_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, call));
+        }
+    }
     LAUNCH(h, "c2c_reduce", hipLaunchKernelGGL(lk_c2c_reduce_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, q));
     std::vector<lk_c2c> rec(P);
     HIPCHK(h, hipMemcpyAsync(rec.data(), q.out, sizeof(lk_c2c) * P, hipMemcpyDeviceToHost, h->stream));
+    if (al) {
+        if (al->max_iter == 0) LAUNCH(h, "align_first_is_last", hipLaunchKernelGGL(lk_align_first_is_last_kernel, c2c_blocks(P), dim3(256), 0, h->stream, call));
+        arec.resize(P);
+        HIPCHK(h, hipMemcpyAsync(arec.data(), call.rec, sizeof(lk_align) * P, hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(a.out, rec.data(), sizeof(lk_c2c) * P);
+    if (a.out) memcpy(a.out, rec.data(), sizeof(lk_c2c) * P);
+    if (al) memcpy(al->out, arec.data(), sizeof(lk_align) * P);
     if (a.nn_off)
         for (size_t k = 0; k <= P; ++k) a.nn_off[k] = nnoff[k];
     return LK_OK;
@@ -296,6 +333,88 @@ int lk_clouds_c2c(lk_handle* h, const float* query, size_t n_qclouds, const uint
     a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
     LKCHK(c2c_run(h, a, total));
     return st.fetch(h);
+}
+
+// what lk_clouds_align(_dev) refuses: every refusal of the C2C entry of the same memory, then its own arguments
+static int align_check(lk_handle* h, const char* who, const C2cArgs& a, const AlignArgs& al, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    lk_c2c sink;
+    C2cArgs c = a;
+    c.out = &sink;   // (c2c_out is optional here; `out` is checked below)
+    LKCHK(c2c_check(h, who, c, cloud_align, total));
+    if (!al.out) return fail(h, LK_ERR_INVALID, w + "null argument (out)");
+    if (al.max_iter > 1000u) return fail(h, LK_ERR_INVALID, w + "max_iter is " + std::to_string(al.max_iter) + ": at most 1000");
+    if (!std::isfinite(al.eps_rot) || al.eps_rot < 0.0) return fail(h, LK_ERR_INVALID, w + "eps_rot must be finite and at least 0");
+    if (!std::isfinite(al.eps_trans) || al.eps_trans < 0.0) return fail(h, LK_ERR_INVALID, w + "eps_trans must be finite and at least 0");
+    return LK_OK;
+}
+
+int lk_clouds_align_dev(lk_handle* h, const float* d_query, size_t n_qclouds, const uint64_t* q_off, const float* d_ref, size_t n_rclouds, const uint64_t* r_off,
+                        size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r, double max_dist, const double* thr, uint32_t n_thr, const double* T0,
+                        uint32_t max_iter, double eps_rot, double eps_trans, lk_align* out, lk_c2c* c2c_out, uint32_t* d_nn_idx, double* d_nn_d2, uint64_t* nn_off) {
+    CHECK_H(h);
+    const C2cArgs a = {d_query, d_ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, c2c_out, d_nn_idx, d_nn_d2, nn_off};
+    const AlignArgs al = {T0, max_iter, eps_rot, eps_trans, out};
+    size_t total = 0;
+    LKCHK(align_check(h, "lk_clouds_align_dev", a, al, 16, &total));
+    return c2c_run(h, a, total, &al);
+}
+
+int lk_clouds_align(lk_handle* h, const float* query, size_t n_qclouds, const uint64_t* q_off, const float* ref, size_t n_rclouds, const uint64_t* r_off,
+                    size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r, double max_dist, const double* thr, uint32_t n_thr, const double* T0,
+                    uint32_t max_iter, double eps_rot, double eps_trans, lk_align* out, lk_c2c* c2c_out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off) {
+    CHECK_H(h);
+    C2cArgs a = {query, ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, c2c_out, nn_idx, nn_d2, nn_off};
+    const AlignArgs al = {T0, max_iter, eps_rot, eps_trans, out};
+    size_t total = 0;
+    LKCHK(align_check(h, "lk_clouds_align", a, al, 4, &total));
+    C2cStage st;
+    st.in = {{query, q_off, n_qclouds}, {ref, r_off, n_rclouds}};
+    st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
+    LKCHK(st.upload(h));
+    a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
+    a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
+    a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
+    LKCHK(c2c_run(h, a, total, &al));
+    return st.fetch(h);
+}
+
+int lk_clouds_transform_dev(lk_handle* h, const float* d_in, size_t n_clouds, const uint64_t* off, const double* T, float* d_out) {
+    CHECK_H(h);
+    const std::string w = "lk_clouds_transform_dev: ";
+    if (n_clouds == 0) return fail(h, LK_ERR_INVALID, w + "n_clouds is 0");
+    if (!d_in) return fail(h, LK_ERR_INVALID, w + "null argument (d_in)");
+    if (!off) return fail(h, LK_ERR_INVALID, w + "null argument (off)");
+    if (!T) return fail(h, LK_ERR_INVALID, w + "null argument (T)");
+    if (!d_out) return fail(h, LK_ERR_INVALID, w + "null argument (d_out)");
+    if ((uintptr_t)d_in & 15) return fail(h, LK_ERR_INVALID, w + "d_in must be 16-byte aligned");
+    if ((uintptr_t)d_out & 15) return fail(h, LK_ERR_INVALID, w + "d_out must be 16-byte aligned");
+    LKCHK(c2c_offsets_check(h, w, "off", off, n_clouds));
+    for (size_t k = 0; k < 12 * n_clouds; ++k)
+        if (!std::isfinite(T[k])) return fail(h, LK_ERR_INVALID, w + "T[" + std::to_string(k / 12) + "] holds a non-finite entry");
+    const uint64_t N = off[n_clouds] - off[0];
+    if (n_clouds >= 0xffffffffull || N >= (1ull << 32)) return fail(h, LK_ERR_CAPACITY, w + "2^32 records or clouds or more: split the call");
+    const float* first = d_in + 4 * off[0];
+    const C2cSpan in = {"d_in", (uintptr_t)first, 16u * (size_t)N}, out = {"d_out", (uintptr_t)d_out, 16u * (size_t)N};
+    if (d_out != first && overlaps(in, out)) return fail(h, LK_ERR_INVALID, w + "d_out overlaps d_in (in place is d_out == d_in + 4 * off[0] exactly)");
+    unsigned long long* d_rel = nullptr;
+    double* d_T = nullptr;
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        d_rel = c.take<unsigned long long>(n_clouds + 1), d_T = c.take<double>(12 * n_clouds);
+        return c.total();
+    };
+    LKCHK(reserve(h, h->c2c, carve(nullptr)));
+    carve(h->c2c.p);
+    std::vector<unsigned long long> rel(n_clouds + 1);
+    for (size_t c = 0; c <= n_clouds; ++c) rel[c] = off[c] - off[0];
+    HIPCHK(h, hipMemcpyAsync(d_rel, rel.data(), 8 * rel.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_T, T, 96 * n_clouds, hipMemcpyHostToDevice, h->stream));
+    if (N)
+        LAUNCH(h, "clouds_transform", hipLaunchKernelGGL(lk_clouds_transform_kernel, c2c_blocks((size_t)N), dim3(256), 0, h->stream, reinterpret_cast<const float4*>(first),
+                                                         d_rel, (unsigned int)n_clouds, d_T, reinterpret_cast<float4*>(d_out), (unsigned long long)N));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LK_OK;
 }
 
 }  // extern "C"

@@ -182,8 +182,8 @@ struct lk_handle {
     std::map<std::string, ProfEntry> prof;
     std::string err;
     DevBuf traj;                  // lk_traj_ate_dev / lk_runs_ate_dev and the _rpe_ pair (lk_traj.hip): offset tables, partner words, the records, the refusal word
-    DevBuf c2c;                   // lk_clouds_c2c(_dev), lk_clouds_mme(_dev) (lk_c2c.hip): tables, bounds, grids, keys and sorted records of the indexed clouds, per-point arrays, the records
-    DevBuf c2c_io;                // lk_clouds_c2c, lk_clouds_mme: device copies of the host clouds and of the host per-point arrays
+    DevBuf c2c;                   // lk_clouds_c2c(_dev), lk_clouds_mme(_dev), lk_clouds_align(_dev), lk_clouds_transform_dev (lk_c2c.hip): tables, bounds, grids, keys and sorted records of the indexed clouds, per-point arrays, the records, an alignment's T0 / records / done words
+    DevBuf c2c_io;                // lk_clouds_c2c, lk_clouds_mme, lk_clouds_align: device copies of the host clouds and of the host per-point arrays
 };
 
 extern thread_local std::string g_err;   // defined in legkilo_hip.hip (lk_last_error(NULL) reads it)

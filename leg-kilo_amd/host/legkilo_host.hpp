@@ -460,6 +460,35 @@ class KiloPath {
         if (nn_off) *nn_off = off;
         return out;
     }
+    // lk_clouds_align_dev: map clouds aligned to a reference cloud where they lie (point-to-point ICP, the loop on the device) - cloudsC2cDev's
+    // clouds, tables and pairs; T0 = 12 doubles per pair, R row-major then t with r ~ R q + t (empty: the identity; lk_runs_ate_dev with LK_ATE_ALIGN
+    // gives a run's rot / trans), up to max_iter solves until one moves by no more than eps_rot (radians) and eps_trans (metres).  One lk_align per
+    // pair; c2c_out takes the lk_c2c records of the final search, the nn outputs its neighbours.
+    std::vector<lk_align> cloudsAlignDev(const float* d_query, const std::vector<uint64_t>& q_off, const float* d_ref, const std::vector<uint64_t>& r_off,
+                                         const std::vector<std::pair<uint32_t, uint32_t>>& pairs, double max_dist, const std::vector<double>& T0 = {},
+                                         uint32_t max_iter = 30, double eps_rot = 1e-6, double eps_trans = 1e-6, std::vector<lk_c2c>* c2c_out = nullptr,
+                                         const std::vector<double>& thr = {}, uint32_t* d_nn_idx = nullptr, double* d_nn_d2 = nullptr,
+                                         std::vector<uint64_t>* nn_off = nullptr) {
+        if (q_off.size() < 2 || r_off.size() < 2 || pairs.empty()) throw std::runtime_error("cloudsAlignDev: an offset table or the pairs are empty");
+        if (!T0.empty() && T0.size() != 12 * pairs.size()) throw std::runtime_error("cloudsAlignDev: T0 holds 12 doubles per pair");
+        std::vector<uint32_t> pq(pairs.size()), pr(pairs.size());
+        for (size_t k = 0; k < pairs.size(); ++k) pq[k] = pairs[k].first, pr[k] = pairs[k].second;
+        std::vector<lk_align> out(pairs.size());
+        std::vector<lk_c2c> c2c(pairs.size());
+        std::vector<uint64_t> off(pairs.size() + 1);
+        dev_->check(lk_clouds_align_dev(dev_->h(), d_query, q_off.size() - 1, q_off.data(), d_ref, r_off.size() - 1, r_off.data(), pairs.size(), pq.data(),
+                                        pr.data(), max_dist, thr.empty() ? nullptr : thr.data(), (uint32_t)thr.size(), T0.empty() ? nullptr : T0.data(), max_iter,
+                                        eps_rot, eps_trans, out.data(), c2c.data(), d_nn_idx, d_nn_d2, off.data()));
+        if (c2c_out) *c2c_out = c2c;
+        if (nn_off) *nn_off = off;
+        return out;
+    }
+    // lk_clouds_transform_dev: the moved clouds - record off[c] + i of d_in to entry off[c] - off[0] + i of d_out under T[c] (12 doubles a cloud),
+    // rounded once to float32, w copied; d_out may be d_in + 4 * off[0] (in place).  What cloudsC2cDev / cloudsMmeDev take after an alignment.
+    void cloudsTransformDev(const float* d_in, const std::vector<uint64_t>& off, const std::vector<double>& T, float* d_out) {
+        if (off.size() < 2 || T.size() != 12 * (off.size() - 1)) throw std::runtime_error("cloudsTransformDev: the offset table is empty or T does not hold 12 doubles per cloud");
+        dev_->check(lk_clouds_transform_dev(dev_->h(), d_in, off.size() - 1, off.data(), T.data(), d_out));
+    }
     // lk_clouds_mme_dev: map clouds scored WITHOUT a reference where they lie - mean map entropy and mean plane variance, both lower for a crisper
     // map.  Cloud c = the 16-byte x y z w records off[c] .. off[c + 1]) at d_clouds (a replay's d_world_out, downsampleCloudsDev's output and
     // offsets).  A point's neighbourhood is every record of its cloud within `radius`, itself included; min_pts (>= 4) of them make it dense.  One

@@ -678,7 +678,7 @@ int lk_clouds_c2c(lk_handle* h,
 /* Rigid alignment of many pairs of clouds in one call: fine registration (point-to-point ICP) of a query cloud to a reference cloud from an initial
  * guess within max_dist of the answer - what puts a slot's map, which lies in the frame of its first pose, into a survey's frame so that
  * lk_clouds_c2c_dev means something.  The loop runs on the device with no host round trip between iterations.  leg-kilo_amd/cloudmetrics.py's
- * align / transform are the numpy statements.  Point-to-plane, scale and global (coarse) registration are not offered.
+ * align / transform are the numpy statements.  Point-to-plane is lk_clouds_align_plane_dev below; scale and global (coarse) registration are not offered.
  * The clouds, offsets, pairs, max_dist, thr / n_thr and the optional nn outputs have exactly the layout and rules of lk_clouds_c2c_dev.
  * T0: HOST, n_pairs x 12 doubles, row-major R then t; NULL means the identity.  max_iter: 0 .. 1000.  eps_rot: radians, eps_trans: metres; both
  * finite and >= 0.  out: HOST, one lk_align per pair, every byte written.  c2c_out: HOST, optional, one lk_c2c per pair.
@@ -739,6 +739,60 @@ int lk_clouds_align(lk_handle* h,
                     const double* T0, uint32_t max_iter, double eps_rot, double eps_trans,
                     lk_align* out, lk_c2c* c2c_out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off);
 int lk_clouds_transform_dev(lk_handle* h, const float* d_in, size_t n_clouds, const uint64_t* off, const double* T, float* d_out);
+/* Point-to-plane alignment of many pairs of clouds in one call: lk_clouds_align_dev with the solve replaced by a 6-dof linearised step against the
+ * reference's per-point normals - the remedy for matches that slide along walls and floor.  leg-kilo_amd/cloudmetrics.py's align_plane is the
+ * numpy statement.  Arguments, layout, rules and refusals are lk_clouds_align_dev's, plus two:
+ * d_ref_normals: DEVICE, 16-byte aligned, one 16-byte record (nx ny nz w) per reference record at the same index as d_ref (record r_off[c] + j is the
+ * normal of reference point j of cloud c); w is not read.  A normal is used AS GIVEN, not normalised; a record with a non-finite component marks
+ * its point as "has no plane".  Any producer may fill the array; lk_clouds_normals_dev is the library's own.
+ * pl_out: HOST, optional, one lk_align_plane per pair.  out is lk_align, unchanged, with one more status bit, LK_ALIGN_DEGENERATE.
+ * Per pair T = (R, t) starts as T0[k].  All arithmetic is float64, without fused multiply-add.
+ *   search under T  exactly lk_clouds_align_dev's; matching ignores the normals, so rmse_first, n_matched_first, c2c_out and the nn outputs mean
+ *                   what they mean there.
+ *   used set U      the matched points whose reference normal has three finite components.
+ *   pass 1          over U with m_i the moved point: n_u, mbar = (sum m_i) / n_u, pbar = (sum p_i) / n_u of the ORIGINAL points, and sum e_i^2,
+ *                   e_i = (nx*dx + ny*dy) + nz*dz, dx = m_x - (double)r.x (dy, dz likewise).
+ *   too few         n_u < 6: LK_ALIGN_FEW - this search is final and T stays.
+ *   pass 2          c_i = m_i - mbar, the row a_i = (c_i x n, n) of six entries, H += a a^T (21 upper terms), g += a e.  The rows are centred on
+ *                   mbar, so rounding is of order 2^-53 extent^2 wherever the clouds lie.
+ *   solve           D = diag(H)^(-1/2); a diagonal entry <= 0 is LK_ALIGN_DEGENERATE.  Cholesky of D H D in natural order without pivoting; a pivot
+ *                   (the diagonal entry before its square root) <= 2^-20 is LK_ALIGN_DEGENERATE - this search is final and T stays.  Otherwise
+ *                   x = -D (D H D)^-1 D g = (omega, v).  A single plane, parallel planes, a corridor without end walls leave directions
+ *                   unobserved: the entry reports that and does not drift along them.
+ *   update          a rotation about mbar, then v: theta = |omega|, dR = the rotation of the unit quaternion (cos(theta/2), sin(theta/2) omega / theta)
+ *                   (the identity for theta == 0), R1 = dR R, R' = the proper rotation nearest R1 (Horn's closed form on R1 transposed, which
+ *                   returns a rotation as itself), t' = dR (t - mbar) + (mbar + v).  The re-orthonormalisation keeps R a rotation to rounding
+ *                   over any max_iter.
+ *   step, loop      step_rot and step_trans of lk_clouds_align_dev from T to T' with pbar, its stop rule and its loop, unchanged.
+ *   final search    also gives rmse_plane = sqrt(sum e_i^2 / n_u) and n_used = n_u under the returned T; rmse_plane_first and n_used_first are
+ *                   those of the first search.  NaN with nothing to average.
+ * A pair's sums are taken in an order that depends on its own clouds, normals, T0[k] and the scalar arguments only.  A pair closed by a status of
+ * its inputs or of T0 gets NaN and 0 in its lk_align_plane.
+ * LK_ERR_INVALID before anything is launched: every refusal of lk_clouds_align_dev, d_ref_normals NULL or misaligned, or overlapping d_nn_idx or
+ * d_nn_d2.  A refused call writes nothing.
+ * lk_clouds_align_plane: the same with query, ref, ref_normals, nn_idx and nn_d2 in HOST memory. */
+typedef struct lk_align_plane {    /* 32 bytes */
+    double   rmse_plane_first;     /* rms plane residual over the used points of the FIRST search; NaN when none */
+    double   rmse_plane;           /* the same of the final search, under the returned T */
+    uint64_t n_used_first, n_used;
+} lk_align_plane;
+#define LK_ALIGN_DEGENERATE 32u    /* lk_align.status: the normals of the used points leave a direction unobserved; T is the one of that search */
+int lk_clouds_align_plane_dev(lk_handle* h,
+                              const float* d_query, size_t n_qclouds, const uint64_t* q_off,
+                              const float* d_ref,   size_t n_rclouds, const uint64_t* r_off,
+                              size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
+                              double max_dist, const double* thr, uint32_t n_thr,
+                              const double* T0, uint32_t max_iter, double eps_rot, double eps_trans,
+                              const float* d_ref_normals, lk_align* out, lk_align_plane* pl_out,
+                              lk_c2c* c2c_out, uint32_t* d_nn_idx, double* d_nn_d2, uint64_t* nn_off);
+int lk_clouds_align_plane(lk_handle* h,
+                          const float* query, size_t n_qclouds, const uint64_t* q_off,
+                          const float* ref,   size_t n_rclouds, const uint64_t* r_off,
+                          size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r,
+                          double max_dist, const double* thr, uint32_t n_thr,
+                          const double* T0, uint32_t max_iter, double eps_rot, double eps_trans,
+                          const float* ref_normals, lk_align* out, lk_align_plane* pl_out,
+                          lk_c2c* c2c_out, uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off);
 /* Map scores that need NO reference, of many clouds in one call: mean map entropy (MME) and mean plane variance (MPV) over a map cloud itself -
  * both lower for a crisper map.  What a recorded run without ground truth or survey ranks its slots by; beside lk_clouds_c2c_dev, one small record
  * per cloud for the host.  leg-kilo_amd/cloudmetrics.py's mme is the numpy statement.
@@ -784,6 +838,29 @@ int lk_clouds_mme_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, cons
                       lk_mme* out, uint32_t* d_n, double* d_h, double* d_lmin);
 int lk_clouds_mme(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts,
                   lk_mme* out, uint32_t* n, double* hh, double* lmin);
+/* Per-point normals of many clouds in one call: what lk_clouds_align_plane_dev takes as d_ref_normals.  leg-kilo_amd/cloudmetrics.py's normals is
+ * the numpy statement.  Layout, offsets, alignment, status bits (LK_MME_NONFINITE, LK_MME_RANGE) and capacity limits are exactly lk_clouds_mme_dev's.
+ * Definition, for point i: N_i, s, M and C = (M - s s^T / n_i) / (n_i - 1) are word for word lk_clouds_mme_dev's, so n_i equals its d_n.
+ * l0 <= l1 <= l2: the eigenvalues of C, sorted (closed form, absolute error a few ulp of l2).
+ *   planarity  w = (l1 - l0) / l2, and w = 0 when l2 <= 0.
+ *   validity   VALID when n_i >= min_pts and w >= min_planarity.
+ *   record     d_normals (DEVICE, 16-byte aligned, 16 B per record): record off[c] + i has (nx, ny, nz, w) as float32 at entry off[c] - off[0] + i.
+ *              n = the unit eigenvector of l0, rounded once to float32; its sign makes the float64 component of largest magnitude positive, the
+ *              first such component on ties.  A point that is not valid gets NaN in nx ny nz; it keeps its w when n_i >= min_pts, a sparse
+ *              one gets NaN in w too.
+ * out: HOST, n_clouds records, every byte written.  A cloud with a status bit has n_valid 0 and NaN in all four floats of its records.
+ * LK_ERR_INVALID before anything is launched: lk_clouds_mme_dev's refusals with min_pts < 3 in the place of < 4, min_planarity not finite or outside
+ * [0, 1], a null or misaligned d_normals, d_normals overlapping the input.  LK_ERR_CAPACITY as there.  A refused call writes nothing.
+ * lk_clouds_normals: the same with clouds and normals in HOST memory (4-byte alignment). */
+typedef struct lk_normals {        /* 24 bytes */
+    uint64_t n_points, n_valid;
+    uint32_t status;               /* 0, LK_MME_NONFINITE, LK_MME_RANGE (bits) */
+    uint32_t pad;                  /* written 0 */
+} lk_normals;
+int lk_clouds_normals_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, double min_planarity,
+                          lk_normals* out, float* d_normals);
+int lk_clouds_normals(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, double min_planarity,
+                      lk_normals* out, float* normals);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

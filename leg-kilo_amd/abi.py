@@ -329,6 +329,45 @@ def mme_dtype():
     return dt
 
 
+class lk_align_plane(C.Structure):
+    _fields_ = [
+        ("rmse_plane_first", C.c_double),
+        ("rmse_plane", C.c_double),
+        ("n_used_first", C.c_uint64),
+        ("n_used", C.c_uint64),
+    ]
+
+
+LK_ALIGN_DEGENERATE = 32   # lk_align.status (lk_clouds_align_plane_dev): the used points' normals leave a direction unobserved; T is that search's
+
+
+def align_plane_dtype():
+    """numpy view of lk_align_plane (32 B): the optional records of lk_clouds_align_plane_dev / lk_clouds_align_plane."""
+    import numpy as np
+
+    dt = np.dtype(lk_align_plane)
+    assert dt.itemsize == C.sizeof(lk_align_plane) == 32
+    return dt
+
+
+class lk_normals(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_uint64),
+        ("n_valid", C.c_uint64),
+        ("status", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
+def normals_dtype():
+    """numpy view of lk_normals (24 B): the records of lk_clouds_normals_dev / lk_clouds_normals."""
+    import numpy as np
+
+    dt = np.dtype(lk_normals)
+    assert dt.itemsize == C.sizeof(lk_normals) == 24
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

@@ -720,6 +720,67 @@ class LegKiloHip:
                                             _p(idx), _p(d2), True)
         return out, res, nn_off, idx[:total], d2[:total]
 
+    def _align_plane_call(self, fn, query, q_off, ref, r_off, normals, pairs, max_dist, thr, T0, max_iter, eps_rot, eps_trans, nn_idx, nn_d2, want_c2c):
+        """What the two point-to-plane exports share on top of _c2c_call: _align_call's T0 and lk_align records, the reference normals and the
+        lk_align_plane records.  Returns (align records, plane records, lk_c2c records or None, nn_off)."""
+        n = len(np.asarray(pairs).reshape(-1, 2))
+        t0 = None if T0 is None else np.ascontiguousarray(T0, dtype=np.float64).reshape(-1, 12)
+        assert t0 is None or len(t0) == n, "T0: one row of 12 doubles per pair"
+        out = np.zeros(max(n, 1), dtype=abi.align_dtype())
+        pl = np.zeros(max(n, 1), dtype=abi.align_plane_dtype())
+        mid = (_p(t0) if t0 is not None else None, int(max_iter), float(eps_rot), float(eps_trans), normals, _p(out), _p(pl))
+        res, nn_off = self._c2c_call(fn, query, q_off, ref, r_off, pairs, max_dist, thr, nn_idx, nn_d2, True, mid, want_c2c)
+        return out[:n], pl[:n], (res if want_c2c else None), nn_off
+
+    def clouds_align_plane_dev(self, d_query, q_off, d_ref, r_off, d_ref_normals, pairs, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e-6, thr=(),
+                               d_nn_idx=0, d_nn_d2=0, want_c2c=True):
+        """Point-to-plane alignment of many pairs of clouds in device memory (lk_clouds_align_plane_dev): clouds_align_dev's arguments and
+        d_ref_normals, one 16-byte nx ny nz w record per reference record at the same index as d_ref (clouds_normals_dev writes them; a record
+        with a non-finite component has no plane).  Returns (abi.align_dtype() records, abi.align_plane_dtype() records, lk_c2c records of the
+        final search or None, nn_off).  cloudmetrics.align_plane is the numpy statement."""
+        return self._align_plane_call(self.L.lk_clouds_align_plane_dev, d_query, q_off, d_ref, r_off, d_ref_normals or None, pairs, max_dist, thr, T0, max_iter,
+                                      eps_rot, eps_trans, d_nn_idx or None, d_nn_d2 or None, want_c2c)
+
+    def clouds_align_plane(self, query, q_off, ref, r_off, ref_normals, pairs, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e-6, thr=(), want_nn=False):
+        """The same with both sides and the normals in host memory (lk_clouds_align_plane): float32 [n, 4] each.  Returns (align records, plane
+        records, lk_c2c records, nn_off), with want_nn (..., nn_idx uint32, nn_d2 float64)."""
+        q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1, 4)
+        r = np.ascontiguousarray(ref, dtype=np.float32).reshape(-1, 4)
+        nr = np.ascontiguousarray(ref_normals, dtype=np.float32).reshape(-1, 4)
+        assert len(nr) == len(r), "ref_normals: one record per reference record"
+        if not want_nn:
+            return self._align_plane_call(self.L.lk_clouds_align_plane, _p(q), q_off, _p(r), r_off, _p(nr), pairs, max_dist, thr, T0, max_iter, eps_rot, eps_trans,
+                                          None, None, True)
+        qo = np.asarray(q_off, dtype=np.uint64)
+        total = int(sum(int(qo[a + 1] - qo[a]) for a in np.asarray(pairs, dtype=np.int64).reshape(-1, 2)[:, 0]))
+        idx, d2 = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.float64)
+        out, pl, res, nn_off = self._align_plane_call(self.L.lk_clouds_align_plane, _p(q), q_off, _p(r), r_off, _p(nr), pairs, max_dist, thr, T0, max_iter, eps_rot,
+                                                      eps_trans, _p(idx), _p(d2), True)
+        return out, pl, res, nn_off, idx[:total], d2[:total]
+
+    def _normals_call(self, fn, clouds, off, radius, min_pts, min_planarity, normals):
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.normals_dtype())
+        self._chk(fn(self.h, clouds, n, _p(o), radius, min_pts, min_planarity, _p(res), normals))
+        return res[:n]
+
+    def clouds_normals_dev(self, d_clouds, off, radius, d_normals, min_pts=5, min_planarity=0.0):
+        """Per-point normals of many clouds in device memory (lk_clouds_normals_dev): clouds_mme_dev's clouds, table, radius and neighbourhoods; record
+        off[c] + i gets (nx, ny, nz, planarity) float32 at entry off[c] - off[0] + i of d_normals - NaN in nx ny nz where the point has fewer than
+        min_pts (>= 3) neighbours or a planarity below min_planarity.  Returns abi.normals_dtype() records, one per cloud; cloudmetrics.normals is
+        the numpy statement."""
+        return self._normals_call(self.L.lk_clouds_normals_dev, d_clouds, off, radius, min_pts, min_planarity, d_normals or None)
+
+    def clouds_normals(self, clouds, off, radius, min_pts=5, min_planarity=0.0):
+        """The same with the clouds in host memory (lk_clouds_normals): clouds float32 [n, 4].  Returns (records, normals float32 [total, 4])."""
+        c = np.ascontiguousarray(clouds, dtype=np.float32).reshape(-1, 4)
+        o = np.asarray(off, dtype=np.uint64)
+        total = int(o[-1] - o[0]) if len(o) else 0
+        nr = np.zeros((max(total, 1), 4), dtype=np.float32)
+        res = self._normals_call(self.L.lk_clouds_normals, _p(c), off, radius, min_pts, min_planarity, _p(nr))
+        return res, nr[:total]
+
     def clouds_transform_dev(self, d_in, off, T, d_out):
         """Moved clouds in device memory (lk_clouds_transform_dev): record off[c] + i of d_in goes to entry off[c] - off[0] + i of d_out with x y z
         moved under T[c] (12 doubles, R row-major then t) in float64 and rounded once to float32, w copied.  d_out may be d_in + 16 * off[0] bytes

@@ -1,5 +1,5 @@
-"""Map-cloud metrics on the host: the float64 numpy statements of lk_clouds_c2c_dev's and lk_clouds_mme_dev's definitions (include/legkilo_hip.h)
-and the F-score built on the former's records.  Brute force in blocks - the reference of the tests and of tools/map_c2c.py / map_mme.py, not a fast
+"""Map-cloud metrics on the host: the float64 numpy statements of the definitions of lk_clouds_c2c_dev, lk_clouds_align_dev,
+lk_clouds_align_plane_dev, lk_clouds_normals_dev and lk_clouds_mme_dev (include/legkilo_hip.h) and the F-score built on the first one's records.  Brute force in blocks - the reference of the tests and of tools/map_c2c.py / map_mme.py, not a fast
 path; touches no device."""
 import numpy as np
 
@@ -201,6 +201,164 @@ def align(query, ref, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e
         fin.update(rmse=float(np.sqrt(v.sum() / len(v))), mean=float(np.sqrt(v).sum() / len(v)), max=float(np.sqrt(v.max())), n_matched=int(len(v)),
                    n_within=[int((v <= t * t).sum()) for t in thr], worst=int(np.flatnonzero(m)[np.argmax(v)]))
     out.update(T=T, iters=iters, status=st, c2c=fin)
+    return out
+
+
+LK_ALIGN_DEGENERATE = 32
+PLANE_MIN_USED = 6
+PLANE_PIVOT = 2.0 ** -20
+
+
+def quat_to_rot(w, x, y, z):
+    return np.array([[(w * w + x * x) - (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                     [2.0 * (x * y + w * z), (w * w + y * y) - (x * x + z * z), 2.0 * (y * z - w * x)],
+                     [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), (w * w + z * z) - (x * x + y * y)]])
+
+
+def nearest_rotation(R1):
+    """The proper rotation nearest R1 [3, 3] as lk_clouds_align_plane_dev takes it: Horn's closed form on R1 TRANSPOSED (S[a, b] = sum p_a g_b with
+    g = R p and sum p p^T = 1 is R^T), which returns a rotation as itself."""
+    return horn_rotation(np.asarray(R1, dtype=np.float64).reshape(3, 3).T)
+
+
+def plane_solve(H, g, scale=True):
+    """x = -D (D H D)^-1 D g by Cholesky in natural order without pivoting, D = diag(H)^(-1/2); None for a diagonal entry <= 0 or a pivot <= 2^-20
+    (an unobserved direction).  scale False (test aid): no D, the pivot test on H itself."""
+    H, g = np.asarray(H, dtype=np.float64).reshape(6, 6), np.asarray(g, dtype=np.float64).reshape(6)
+    dg = np.diag(H)
+    if not (dg > 0.0).all():
+        return None
+    d = 1.0 / np.sqrt(dg) if scale else np.ones(6)
+    A = (H * d[:, None]) * d[None, :]
+    L = np.zeros((6, 6))
+    for j in range(6):
+        s = A[j, j] - (L[j, :j] * L[j, :j]).sum()
+        if not s > PLANE_PIVOT:
+            return None
+        L[j, j] = np.sqrt(s)
+        for i in range(j + 1, 6):
+            L[i, j] = (A[i, j] - (L[i, :j] * L[j, :j]).sum()) / L[j, j]
+    y = np.zeros(6)
+    for i in range(6):
+        y[i] = (d[i] * g[i] - (L[i, :i] * y[:i]).sum()) / L[i, i]
+    for i in range(5, -1, -1):
+        y[i] = (y[i] - (L[i + 1:, i] * y[i + 1:]).sum()) / L[i, i]
+    return -(d * y)
+
+
+def align_plane(query, ref, ref_normals, max_dist, T0=None, max_iter=30, eps_rot=1e-6, eps_trans=1e-6, thr=(), variant=None):
+    """Point-to-plane alignment of one pair as lk_clouds_align_plane_dev defines it: align's search (the normals play no part in it), then over the
+    matched points whose reference normal is finite the 6 x 6 normal equations about the moved centroid, the scaled Cholesky solve, the rotation
+    about that centroid composed onto T and re-orthonormalised.  ref_normals [m, >= 3] float32, used as given.  Returns align's dict and
+    rmse_plane_first, rmse_plane, n_used_first, n_used.
+    variant (test aid): one of the wrong restatements tests/test_plane_host.py expects to fail - "origin", "no_scale", "unit_normals",
+    "count_invalid", "no_ortho"."""
+    q, r = np.asarray(query, dtype=np.float32)[:, :3], np.asarray(ref, dtype=np.float32)[:, :3]
+    nr = np.asarray(ref_normals, dtype=np.float32)
+    nr = nr.reshape(-1, nr.shape[-1] if nr.ndim == 2 else 4)[:, :3].astype(np.float64)
+    n = len(q)
+    thr = [float(t) for t in thr]
+    T = np.array([1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0, 0, 0, 0]) if T0 is None else np.asarray(T0, dtype=np.float64).reshape(12).copy()
+    st = status(q, r, max_dist) | (0 if np.isfinite(T).all() else LK_ALIGN_BAD_T0)
+    none = dict(j=np.full(n, NO_MATCH, dtype=np.uint32), d2=np.full(n, np.inf), matched=np.zeros(n, dtype=bool), rmse=np.nan, mean=np.nan, max=np.nan,
+                n_query=n, n_matched=0, n_within=[0] * len(thr), worst=0, status=st & 3)
+    out = dict(T=T, iters=0, status=st, rmse_first=np.nan, n_matched_first=0, step_rot=np.nan, step_trans=np.nan, first=(none["j"], none["matched"]), c2c=none,
+               rmse_plane_first=np.nan, rmse_plane=np.nan, n_used_first=0, n_used=0)
+    if st:
+        return out
+    q64, r64 = q.astype(np.float64), r.astype(np.float64)
+    fin = np.isfinite(nr).all(axis=1) if len(nr) else np.zeros(0, dtype=bool)
+    if variant == "unit_normals":
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nr = nr / np.sqrt((nr * nr).sum(axis=1))[:, None]
+    iters, stopped, first = 0, False, None
+    while True:
+        moved = move(q, T)
+        j, d2, m = nearest_moved(moved, r, max_dist)
+        u = m.copy()
+        u[m] = fin[j[m]]
+        cnt = int(m.sum()) if variant == "count_invalid" else int(u.sum())
+        Mv, G, Nn, P = moved[u], r64[j[u]], nr[j[u]], q64[u]
+        D = Mv - G
+        e = (Nn[:, 0] * D[:, 0] + Nn[:, 1] * D[:, 1]) + Nn[:, 2] * D[:, 2]
+        rp = float(np.sqrt((e * e).sum() / cnt)) if cnt else np.nan
+        if first is None:
+            first = (j.copy(), m.copy())
+            out.update(n_matched_first=int(m.sum()), rmse_first=float(np.sqrt(d2[m].sum() / m.sum())) if m.any() else np.nan, first=first, rmse_plane_first=rp,
+                       n_used_first=cnt)
+        out.update(rmse_plane=rp, n_used=cnt)
+        if iters == max_iter or stopped:
+            break
+        if cnt < PLANE_MIN_USED:
+            st |= LK_ALIGN_FEW
+            break
+        mbar, pbar = Mv.sum(axis=0) / cnt, P.sum(axis=0) / cnt
+        about = np.zeros(3) if variant == "origin" else mbar
+        Cc = Mv - about
+        A = np.concatenate([np.cross(Cc, Nn), Nn], axis=1)
+        x = plane_solve(A.T @ A, A.T @ e, scale=variant != "no_scale")
+        if x is None:
+            st |= LK_ALIGN_DEGENERATE
+            break
+        if variant == "origin":       # (the same step in exact arithmetic: v about mbar = v about the origin + omega x mbar)
+            x = np.r_[x[:3], x[3:] + np.cross(x[:3], mbar)]
+        theta = np.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2])
+        dR = np.eye(3) if theta == 0.0 else quat_to_rot(np.cos(theta / 2.0), np.sin(theta / 2.0) * x[0] / theta, np.sin(theta / 2.0) * x[1] / theta,
+                                                        np.sin(theta / 2.0) * x[2] / theta)
+        R1 = dR @ T[:9].reshape(3, 3)
+        Rn = R1 if variant == "no_ortho" else nearest_rotation(R1)
+        Tn = np.r_[Rn.reshape(9), dR @ (T[9:] - mbar) + (mbar + x[3:])]
+        step_rot, step_trans = align_step(T, Tn, pbar)
+        T, iters = Tn, iters + 1
+        out.update(step_rot=step_rot, step_trans=step_trans)
+        if step_rot <= eps_rot and step_trans <= eps_trans:
+            st |= LK_ALIGN_CONVERGED
+            stopped = True
+    fin_rec = dict(none, status=0)
+    fin_rec.update(j=j, d2=d2, matched=m)
+    if m.any():
+        v = d2[m]
+        fin_rec.update(rmse=float(np.sqrt(v.sum() / len(v))), mean=float(np.sqrt(v).sum() / len(v)), max=float(np.sqrt(v.max())), n_matched=int(len(v)),
+                       n_within=[int((v <= t * t).sum()) for t in thr], worst=int(np.flatnonzero(m)[np.argmax(v)]))
+    out.update(T=T, iters=iters, status=st, c2c=fin_rec)
+    return out
+
+
+def normals(cloud, radius, min_pts=5, min_planarity=0.0, variant=None):
+    """Per-point normals of one cloud as lk_clouds_normals_dev defines them: mme's neighbourhoods and covariance, l0 <= l1 <= l2 its eigenvalues,
+    planarity w = (l1 - l0) / l2 (0 when l2 <= 0), valid when n_i >= min_pts and w >= min_planarity; the normal is the unit eigenvector of l0 with the
+    float64 component of largest magnitude positive (the first on ties), rounded once to float32.  Returns a dict: rec float32 [m, 4] (nx ny nz w;
+    NaN in nx ny nz where the point is not valid, in w too where it is sparse), n uint32 [m], w float64 [m], valid / dense bool [m], vec float64
+    [m, 3] (the oriented eigenvector of every dense point), n_points, n_valid, status.  variant "sign_f32" (test aid): the sign rule applied to
+    the float32 rounding."""
+    m = len(cloud)
+    st = mme_status(cloud, radius)
+    out = dict(rec=np.full((m, 4), np.nan, dtype=np.float32), n=np.zeros(m, dtype=np.uint32), w=np.full(m, np.nan), valid=np.zeros(m, dtype=bool),
+               dense=np.zeros(m, dtype=bool), vec=np.full((m, 3), np.nan), n_points=m, n_valid=0, status=st)
+    if st or not m:
+        return out
+    n, s, mm = mme_moments(cloud, radius)
+    dense = n >= min_pts
+    out["n"], out["dense"] = n, dense
+    if not dense.any():
+        return out
+    nn, sd, md = n[dense].astype(np.float64), s[dense], mm[dense]
+    pairs = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+    c = np.stack([(md[:, k] - sd[:, i] * sd[:, j] / nn) / (nn - 1.0) for k, (i, j) in enumerate(pairs)], axis=1)
+    full = np.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]], axis=1).reshape(-1, 3, 3)
+    ev, V = np.linalg.eigh(full)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = np.where(ev[:, 2] > 0.0, (ev[:, 1] - ev[:, 0]) / ev[:, 2], 0.0)
+    vec = V[:, :, 0].copy()
+    mag = np.abs(vec.astype(np.float32).astype(np.float64)) if variant == "sign_f32" else np.abs(vec)
+    lead = vec[np.arange(len(vec)), np.argmax(mag, axis=1)]
+    vec[lead < 0.0] *= -1.0
+    ok = w >= min_planarity
+    di = np.flatnonzero(dense)
+    out["w"][di], out["vec"][di], out["valid"][di] = w, vec, ok
+    out["rec"][di, 3] = w.astype(np.float32)
+    out["rec"][di[ok], :3] = vec[ok].astype(np.float32)
+    out["n_valid"] = int(ok.sum())
     return out
 
 

@@ -3,7 +3,10 @@
 // d_world_out, lk_downsample_clouds_dev's d_out), lk_clouds_c2c over clouds in host memory - and, on the same search structure (c2c_index), the
 // scores that need no reference: mean map entropy and mean plane variance (lk_mme_kernels.h, arithmetic in lk_mme.h), lk_clouds_mme_dev / lk_clouds_mme,
 // and the rigid alignment of a query cloud to its reference (lk_align_kernels.h, arithmetic in lk_align.h): lk_clouds_align_dev / lk_clouds_align run
-// c2c_run's call with the search iterated under a transform, lk_clouds_transform_dev writes the moved clouds.
+// c2c_run's call with the search iterated under a transform, lk_clouds_transform_dev writes the moved clouds; lk_clouds_align_plane_dev /
+// lk_clouds_align_plane are the same loop with the point-to-plane solve between the searches (lk_align_plane_kernels.h, arithmetic in
+// lk_align_plane.h) against per-point normals of the reference, which lk_clouds_normals_dev / lk_clouds_normals make from MME's neighbourhood walk
+// (lk_normals_kernels.h, arithmetic in lk_normals.h).
 // What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
 // use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
@@ -11,11 +14,15 @@
 #include "lk_internal.h"
 #include "lk_c2c_kernels.h"
 #include "lk_align_kernels.h"
+#include "lk_align_plane_kernels.h"
 #include "lk_mme_kernels.h"
+#include "lk_normals_kernels.h"
 
 static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
 static_assert(sizeof(lk_mme) == 64, "lk_mme must be 64 B");
 static_assert(sizeof(lk_align) == 136, "lk_align must be 136 B");
+static_assert(sizeof(lk_align_plane) == 32, "lk_align_plane must be 32 B");
+static_assert(sizeof(lk_normals) == 24, "lk_normals must be 24 B");
 static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
 
 namespace {
@@ -37,6 +44,8 @@ struct AlignArgs {   // what lk_clouds_align(_dev) adds to them (C2cArgs::out is
     uint32_t max_iter;
     double eps_rot, eps_trans;
     lk_align* out;
+    const float* ref_normals;   // lk_clouds_align_plane(_dev) only (DEVICE in c2c_run): the solve between two searches is then the point-to-plane one
+    lk_align_plane* pl_out;     // may be null
 };
 struct C2cSpan {   // a named range of bytes (p = 0: not given)
     const char* name;
@@ -196,6 +205,8 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs
     int* q_mm = nullptr;
     LkAlignCall call = {};
     double* d_T0 = nullptr;
+    lk_align_plane* d_pl = nullptr;
+    const bool plane = al && al->ref_normals;
     auto carve = [&](void* base) {
         LkCarve c(base, 256);
         d_qoff = c.take<unsigned long long>(NQ + 1), x.d_off64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
@@ -209,6 +220,7 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs
         q.nn_idx = c2c_or_own(c, a.nn_idx, total), q.nn_d2 = c2c_or_own(c, a.nn_d2, total);   // (c2c_check: both or neither)
         q.out = c.take<lk_c2c>(P);
         d_T0 = c.take<double>(al ? 12 * P : 0), call.rec = c.take<lk_align>(al ? P : 0), call.done = c.take<unsigned int>(al ? P : 0);
+        d_pl = c.take<lk_align_plane>(plane ? P : 0);
         return c.total();
     };
     const size_t bytes = carve(nullptr);
@@ -235,6 +247,7 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs
     q.n_pairs = (unsigned int)P, q.n_thr = a.n_thr;
     std::vector<double> t0;          // alive until the stream has been synchronised
     std::vector<lk_align> arec;
+    std::vector<lk_align_plane> prec;
     if (!al) {
         if (total) LAUNCH(h, "c2c_query", hipLaunchKernelGGL(lk_c2c_query_kernel, c2c_blocks(total), dim3(256), 0, h->stream, q, (unsigned long long)total));
     } else {
@@ -248,20 +261,28 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs
         for (uint32_t it = 0; it <= al->max_iter; ++it) {
             if (total)
                 LAUNCH(h, "align_search", hipLaunchKernelGGL(lk_align_search_kernel, c2c_blocks(total), dim3(256), 0, h->stream, call, (unsigned long long)total, it == 0 ? 1 : 0));
-            if (it < al->max_iter) LAUNCH(h, "align_solve", hipLaunchKernelGGL(lk_align_solve_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, call));
+            if (plane)   // (also after the last search: every pair's final search gets its plane figures there)
+                LAUNCH(h, "align_plane_solve", hipLaunchKernelGGL(lk_align_plane_solve_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, call,
+                                                                  reinterpret_cast<const float4*>(al->ref_normals), d_pl, it == 0 ? 1 : 0, it == al->max_iter ? 1 : 0));
+            else if (it < al->max_iter) LAUNCH(h, "align_solve", hipLaunchKernelGGL(lk_align_solve_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, call));
         }
     }
     LAUNCH(h, "c2c_reduce", hipLaunchKernelGGL(lk_c2c_reduce_kernel, dim3((unsigned int)P), dim3(256), 0, h->stream, q));
     std::vector<lk_c2c> rec(P);
     HIPCHK(h, hipMemcpyAsync(rec.data(), q.out, sizeof(lk_c2c) * P, hipMemcpyDeviceToHost, h->stream));
     if (al) {
-        if (al->max_iter == 0) LAUNCH(h, "align_first_is_last", hipLaunchKernelGGL(lk_align_first_is_last_kernel, c2c_blocks(P), dim3(256), 0, h->stream, call));
+        if (al->max_iter == 0 && !plane) LAUNCH(h, "align_first_is_last", hipLaunchKernelGGL(lk_align_first_is_last_kernel, c2c_blocks(P), dim3(256), 0, h->stream, call));
         arec.resize(P);
         HIPCHK(h, hipMemcpyAsync(arec.data(), call.rec, sizeof(lk_align) * P, hipMemcpyDeviceToHost, h->stream));
+        if (plane && al->pl_out) {
+            prec.resize(P);
+            HIPCHK(h, hipMemcpyAsync(prec.data(), d_pl, sizeof(lk_align_plane) * P, hipMemcpyDeviceToHost, h->stream));
+        }
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (a.out) memcpy(a.out, rec.data(), sizeof(lk_c2c) * P);
     if (al) memcpy(al->out, arec.data(), sizeof(lk_align) * P);
+    if (!prec.empty()) memcpy(al->pl_out, prec.data(), sizeof(lk_align_plane) * P);
     if (a.nn_off)
         for (size_t k = 0; k <= P; ++k) a.nn_off[k] = nnoff[k];
     return LK_OK;
@@ -373,6 +394,51 @@ int lk_clouds_align(lk_handle* h, const float* query, size_t n_qclouds, const ui
     st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
     LKCHK(st.upload(h));
     a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
+    a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
+    a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
+    LKCHK(c2c_run(h, a, total, &al));
+    return st.fetch(h);
+}
+
+// what lk_clouds_align_plane(_dev) refuses: every refusal of the alignment entry of the same memory, then the normals
+static int align_plane_check(lk_handle* h, const char* who, const C2cArgs& a, const AlignArgs& al, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    LKCHK(align_check(h, who, a, al, cloud_align, total));
+    if (!al.ref_normals) return fail(h, LK_ERR_INVALID, w + "null argument (ref_normals)");
+    if ((uintptr_t)al.ref_normals & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "ref_normals must be " + std::to_string(cloud_align) + "-byte aligned");
+    const C2cSpan nrm = {"ref_normals", (uintptr_t)al.ref_normals + 16u * (uintptr_t)a.r_off[0], 16u * (size_t)(a.r_off[a.n_r] - a.r_off[0])};
+    const C2cSpan idx = {"nn_idx", (uintptr_t)a.nn_idx, 4 * *total}, d2 = {"nn_d2", (uintptr_t)a.nn_d2, 8 * *total};
+    LKCHK(c2c_overlap_check(h, w, idx, &nrm, 1, "ref_normals", nullptr, 0));
+    return c2c_overlap_check(h, w, d2, &nrm, 1, "ref_normals", nullptr, 0);
+}
+
+int lk_clouds_align_plane_dev(lk_handle* h, const float* d_query, size_t n_qclouds, const uint64_t* q_off, const float* d_ref, size_t n_rclouds, const uint64_t* r_off,
+                              size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r, double max_dist, const double* thr, uint32_t n_thr, const double* T0,
+                              uint32_t max_iter, double eps_rot, double eps_trans, const float* d_ref_normals, lk_align* out, lk_align_plane* pl_out, lk_c2c* c2c_out,
+                              uint32_t* d_nn_idx, double* d_nn_d2, uint64_t* nn_off) {
+    CHECK_H(h);
+    const C2cArgs a = {d_query, d_ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, c2c_out, d_nn_idx, d_nn_d2, nn_off};
+    const AlignArgs al = {T0, max_iter, eps_rot, eps_trans, out, d_ref_normals, pl_out};
+    size_t total = 0;
+    LKCHK(align_plane_check(h, "lk_clouds_align_plane_dev", a, al, 16, &total));
+    return c2c_run(h, a, total, &al);
+}
+
+int lk_clouds_align_plane(lk_handle* h, const float* query, size_t n_qclouds, const uint64_t* q_off, const float* ref, size_t n_rclouds, const uint64_t* r_off,
+                          size_t n_pairs, const uint32_t* pair_q, const uint32_t* pair_r, double max_dist, const double* thr, uint32_t n_thr, const double* T0,
+                          uint32_t max_iter, double eps_rot, double eps_trans, const float* ref_normals, lk_align* out, lk_align_plane* pl_out, lk_c2c* c2c_out,
+                          uint32_t* nn_idx, double* nn_d2, uint64_t* nn_off) {
+    CHECK_H(h);
+    C2cArgs a = {query, ref, n_qclouds, n_rclouds, n_pairs, q_off, r_off, pair_q, pair_r, max_dist, thr, n_thr, c2c_out, nn_idx, nn_d2, nn_off};
+    AlignArgs al = {T0, max_iter, eps_rot, eps_trans, out, ref_normals, pl_out};
+    size_t total = 0;
+    LKCHK(align_plane_check(h, "lk_clouds_align_plane", a, al, 4, &total));
+    C2cStage st;
+    st.in = {{query, q_off, n_qclouds}, {ref, r_off, n_rclouds}, {ref_normals, r_off, n_rclouds}};
+    st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
+    LKCHK(st.upload(h));
+    a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
+    al.ref_normals = reinterpret_cast<const float*>(st.in[2].dev);
     a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
     a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
     LKCHK(c2c_run(h, a, total, &al));
@@ -515,6 +581,95 @@ int lk_clouds_mme(lk_handle* h, const float* clouds, size_t n_clouds, const uint
     a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
     a.n = static_cast<uint32_t*>(st.out[0].dev), a.hh = static_cast<double*>(st.out[1].dev), a.lmin = static_cast<double*>(st.out[2].dev);
     LKCHK(mme_run(h, a, total));
+    return st.fetch(h);
+}
+
+}  // extern "C"
+
+namespace {
+struct NormalsArgs {   // the arguments both entries share, as the caller gave them
+    const float* clouds;
+    size_t n_clouds;
+    const uint64_t* off;
+    double radius;
+    uint32_t min_pts;
+    double min_planarity;
+    lk_normals* out;
+    float* normals;
+};
+}  // namespace
+
+// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals with min_pts from 3 on, then the entry's own.  *total: records in all
+static int normals_check(lk_handle* h, const char* who, const NormalsArgs& a, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    lk_mme sink;
+    const MmeArgs m = {a.clouds, a.n_clouds, a.off, a.radius, a.min_pts < 4 ? 4u : a.min_pts, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
+    LKCHK(mme_check(h, who, m, cloud_align, total));
+    if (a.min_pts < 3) return fail(h, LK_ERR_INVALID, w + "min_pts is " + std::to_string(a.min_pts) + ": at least 3 (two points span no plane)");
+    if (!std::isfinite(a.min_planarity) || a.min_planarity < 0.0 || a.min_planarity > 1.0) return fail(h, LK_ERR_INVALID, w + "min_planarity must be finite and in 0 .. 1");
+    if (!a.normals) return fail(h, LK_ERR_INVALID, w + "null argument (normals)");
+    if ((uintptr_t)a.normals & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "normals must be " + std::to_string(cloud_align) + "-byte aligned");
+    const C2cSpan in = {"clouds", (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0], 16u * *total}, o = {"normals", (uintptr_t)a.normals, 16u * *total};
+    return c2c_overlap_check(h, w, o, &in, 1, "the input clouds", nullptr, 0);
+}
+
+// the call behind normals_check, on DEVICE clouds and a DEVICE record array
+static int normals_run(lk_handle* h, const NormalsArgs& a, size_t N) {
+    const size_t NC = a.n_clouds;
+    std::vector<unsigned int> used;   // every non-empty cloud
+    for (size_t c = 0; c < NC; ++c)
+        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+    C2cIndex x = {};
+    LkNormalsCall m = {};
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
+        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
+        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
+        x.recs = c.take<LkC2cRec>(N);
+        m.out = c.take<lk_normals>(NC);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
+    carve(h->c2c.p);
+    LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.radius, x));
+    m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs, m.normals = reinterpret_cast<float4*>(a.normals);
+    m.reach2 = lk_c2c_reach2(a.radius), m.min_planarity = a.min_planarity;
+    m.n_clouds = (unsigned int)NC, m.min_pts = a.min_pts, m.total = (unsigned int)N;
+    if (N) LAUNCH(h, "normals_point", hipLaunchKernelGGL(lk_normals_point_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+    LAUNCH(h, "normals_count", hipLaunchKernelGGL(lk_normals_count_kernel, dim3((unsigned int)NC), dim3(256), 0, h->stream, m));
+    std::vector<lk_normals> rec(NC);
+    HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_normals) * NC, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(a.out, rec.data(), sizeof(lk_normals) * NC);
+    return LK_OK;
+}
+
+extern "C" {
+
+int lk_clouds_normals_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, double min_planarity,
+                          lk_normals* out, float* d_normals) {
+    CHECK_H(h);
+    const NormalsArgs a = {d_clouds, n_clouds, off, radius, min_pts, min_planarity, out, d_normals};
+    size_t total = 0;
+    LKCHK(normals_check(h, "lk_clouds_normals_dev", a, 16, &total));
+    return normals_run(h, a, total);
+}
+
+int lk_clouds_normals(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, double min_planarity, lk_normals* out,
+                      float* normals) {
+    CHECK_H(h);
+    NormalsArgs a = {clouds, n_clouds, off, radius, min_pts, min_planarity, out, normals};
+    size_t total = 0;
+    LKCHK(normals_check(h, "lk_clouds_normals", a, 4, &total));
+    C2cStage st;
+    st.in = {{clouds, off, n_clouds}};
+    st.out = {{normals, 16, total}};
+    LKCHK(st.upload(h));
+    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
+    a.normals = static_cast<float*>(st.out[0].dev);
+    LKCHK(normals_run(h, a, total));
     return st.fetch(h);
 }
 

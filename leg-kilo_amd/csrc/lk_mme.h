@@ -35,14 +35,18 @@ LK_C2C_HD void lk_mme_add(LkMmeAcc* a, float qx, float qy, float qz, float rx, f
     a->m[0] = a->m[0] + ux * ux, a->m[1] = a->m[1] + ux * uy, a->m[2] = a->m[2] + ux * uz;
     a->m[3] = a->m[3] + uy * uy, a->m[4] = a->m[4] + uy * uz, a->m[5] = a->m[5] + uz * uz;
 }
+// the covariance of a neighbourhood of two records or more from its sums (lk_normals.h takes it too): C = (M - s s^T / n) / (n - 1): xx xy xz yy yz zz
+LK_C2C_HD void lk_mme_cov(const LkMmeAcc& a, double* c) {
+    const double n = (double)a.n, n1 = (double)(a.n - 1u);
+    c[0] = (a.m[0] - a.s[0] * a.s[0] / n) / n1, c[1] = (a.m[1] - a.s[0] * a.s[1] / n) / n1, c[2] = (a.m[2] - a.s[0] * a.s[2] / n) / n1;
+    c[3] = (a.m[3] - a.s[1] * a.s[1] / n) / n1, c[4] = (a.m[4] - a.s[1] * a.s[2] / n) / n1, c[5] = (a.m[5] - a.s[2] * a.s[2] / n) / n1;
+}
 // class and figures of one point from its sums; h is NaN unless SCORED, lmin NaN when SPARSE.  min_pts >= 4 (below four points det is 0 by rank).
 LK_C2C_HD void lk_mme_finish(const LkMmeAcc& a, unsigned int min_pts, unsigned int* cls, double* h, double* lmin) {
     *cls = LK_MME_SPARSE, *h = NAN, *lmin = NAN;
     if (a.n < min_pts) return;
-    const double n = (double)a.n, n1 = (double)(a.n - 1u);
-    double c[6];   // C = (M - s s^T / n) / (n - 1): xx xy xz yy yz zz
-    c[0] = (a.m[0] - a.s[0] * a.s[0] / n) / n1, c[1] = (a.m[1] - a.s[0] * a.s[1] / n) / n1, c[2] = (a.m[2] - a.s[0] * a.s[2] / n) / n1;
-    c[3] = (a.m[3] - a.s[1] * a.s[1] / n) / n1, c[4] = (a.m[4] - a.s[1] * a.s[2] / n) / n1, c[5] = (a.m[5] - a.s[2] * a.s[2] / n) / n1;
+    double c[6];
+    lk_mme_cov(a, c);
     const double tr = (c[0] + c[3]) + c[5];
     const double det = (c[0] * (c[3] * c[5] - c[4] * c[4]) - c[1] * (c[1] * c[5] - c[4] * c[2])) + c[2] * (c[1] * c[4] - c[3] * c[2]);
     const double t = tr / 3.0;

@@ -483,6 +483,39 @@ class KiloPath {
         if (nn_off) *nn_off = off;
         return out;
     }
+    // lk_clouds_align_plane_dev: cloudsAlignDev with the point-to-plane solve against d_ref_normals (one nx ny nz w record per reference record, at
+    // d_ref's index; cloudsNormalsDev writes them).  pl_out takes the lk_align_plane records; LK_ALIGN_DEGENERATE marks a pair whose used normals
+    // leave a direction unobserved.
+    std::vector<lk_align> cloudsAlignPlaneDev(const float* d_query, const std::vector<uint64_t>& q_off, const float* d_ref, const std::vector<uint64_t>& r_off,
+                                              const float* d_ref_normals, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, double max_dist,
+                                              const std::vector<double>& T0 = {}, uint32_t max_iter = 30, double eps_rot = 1e-6, double eps_trans = 1e-6,
+                                              std::vector<lk_align_plane>* pl_out = nullptr, std::vector<lk_c2c>* c2c_out = nullptr, const std::vector<double>& thr = {},
+                                              uint32_t* d_nn_idx = nullptr, double* d_nn_d2 = nullptr, std::vector<uint64_t>* nn_off = nullptr) {
+        if (q_off.size() < 2 || r_off.size() < 2 || pairs.empty()) throw std::runtime_error("cloudsAlignPlaneDev: an offset table or the pairs are empty");
+        if (!T0.empty() && T0.size() != 12 * pairs.size()) throw std::runtime_error("cloudsAlignPlaneDev: T0 holds 12 doubles per pair");
+        std::vector<uint32_t> pq(pairs.size()), pr(pairs.size());
+        for (size_t k = 0; k < pairs.size(); ++k) pq[k] = pairs[k].first, pr[k] = pairs[k].second;
+        std::vector<lk_align> out(pairs.size());
+        std::vector<lk_align_plane> pl(pairs.size());
+        std::vector<lk_c2c> c2c(pairs.size());
+        std::vector<uint64_t> off(pairs.size() + 1);
+        dev_->check(lk_clouds_align_plane_dev(dev_->h(), d_query, q_off.size() - 1, q_off.data(), d_ref, r_off.size() - 1, r_off.data(), pairs.size(), pq.data(),
+                                              pr.data(), max_dist, thr.empty() ? nullptr : thr.data(), (uint32_t)thr.size(), T0.empty() ? nullptr : T0.data(),
+                                              max_iter, eps_rot, eps_trans, d_ref_normals, out.data(), pl.data(), c2c.data(), d_nn_idx, d_nn_d2, off.data()));
+        if (pl_out) *pl_out = pl;
+        if (c2c_out) *c2c_out = c2c;
+        if (nn_off) *nn_off = off;
+        return out;
+    }
+    // lk_clouds_normals_dev: per-point normals where the clouds lie - cloudsMmeDev's clouds, table and neighbourhoods; record off[c] + i gets
+    // (nx, ny, nz, planarity) at entry off[c] - off[0] + i of d_normals, NaN in nx ny nz below min_pts (>= 3) neighbours or min_planarity.
+    std::vector<lk_normals> cloudsNormalsDev(const float* d_clouds, const std::vector<uint64_t>& off, double radius, float* d_normals, uint32_t min_pts = 5,
+                                             double min_planarity = 0.0) {
+        if (off.size() < 2) throw std::runtime_error("cloudsNormalsDev: the offset table is empty");
+        std::vector<lk_normals> out(off.size() - 1);
+        dev_->check(lk_clouds_normals_dev(dev_->h(), d_clouds, off.size() - 1, off.data(), radius, min_pts, min_planarity, out.data(), d_normals));
+        return out;
+    }
     // lk_clouds_transform_dev: the moved clouds - record off[c] + i of d_in to entry off[c] - off[0] + i of d_out under T[c] (12 doubles a cloud),
     // rounded once to float32, w copied; d_out may be d_in + 4 * off[0] (in place).  What cloudsC2cDev / cloudsMmeDev take after an alignment.
     void cloudsTransformDev(const float* d_in, const std::vector<uint64_t>& off, const std::vector<double>& T, float* d_out) {

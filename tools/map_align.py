@@ -12,7 +12,10 @@ Beside it, on the same clouds:
              the clouds, a numpy Horn solve per file (over the first --host-files files, scaled by points), the moved clouds back up;
   route (b): lk_memcpy_d2h once, then an ICP with scipy.spatial.cKDTree on the host (first --host-files files, scaled by points), where scipy imports.
 The accuracy form of lk_clouds_c2c_dev, the run replay and lk_downsample_clouds_dev are timed before and after (tools/map_c2c.py's figures).
-Usage: map_align.py [--runs R] [--scans K] [--distinct D] [--leaf M] [--max-dist M] [--max-iter N] [--eps-rot RAD] [--eps-trans M] [--t0-deg DEG] [--t0-m M]
+--plane: the point-to-plane entry instead (lk_clouds_align_plane_dev) with the survey's normals from lk_clouds_normals_dev (--normal-radius,
+--normal-min-pts, --normal-min-planarity), beside lk_clouds_align_dev on the same clouds and T0 in the same session; the normals entry is timed on the
+survey and on the map clouds beside lk_clouds_mme_dev at the same radius; routes (a) and (b) are left out.
+Usage: map_align.py [--plane] [--runs R] [--scans K] [--distinct D] [--leaf M] [--max-dist M] [--max-iter N] [--eps-rot RAD] [--eps-trans M] [--t0-deg DEG] [--t0-m M]
                     [--ref-files F] [--reps N] [--warmup W] [--host-files F] [--commit TEXT] [--json PATH]"""
 import json
 import os
@@ -39,6 +42,10 @@ ap.add_argument("--t0-deg", type=float, default=2.0)
 ap.add_argument("--t0-m", type=float, default=0.1)
 ap.add_argument("--ref-files", type=int, default=8)
 ap.add_argument("--host-files", type=int, default=16)
+ap.add_argument("--plane", action="store_true")
+ap.add_argument("--normal-radius", type=float, default=0.3)
+ap.add_argument("--normal-min-pts", type=int, default=5)
+ap.add_argument("--normal-min-planarity", type=float, default=0.3)
 args = ap.parse_args()
 
 w = rw.Workload(args)
@@ -105,32 +112,108 @@ def align(max_iter=args.max_iter, key="align"):
     return call
 
 
-whole = timed(align())
-rec, crec, _ = last["align"]
-LAUNCHES = ("align_init", "align_search", "align_solve", "c2c_reduce")
-tot = rw.per_launch(g, align(), LAUNCHES, args.reps)
-counts = {}
-g.profile_reset(), g.profile_enable(True)
-align()()
-for k in LAUNCHES:
-    counts[k] = int(g.profile_get(k)[0])
-g.profile_enable(False)
-one_search = rw.per_launch(g, align(0, "align0"), ("align_search",), args.reps, count=1)["align_search"]
-one = rw.per_launch(g, align(1, "align1"), ("align_search", "align_solve"), args.reps)
-one_solve = one["align_solve"]
-angle = np.degrees(np.arccos(np.clip((rec["rot"][:, 0] + rec["rot"][:, 4] + rec["rot"][:, 8] - 1) / 2, -1, 1)))
-shift = np.linalg.norm(rec["rot"].reshape(-1, 3, 3) @ centre + rec["trans"] - centre, axis=1)
-iters = rec["iters"].astype(int)
-form = dict(max_dist=md, max_iter=args.max_iter, eps_rot=args.eps_rot, eps_trans=args.eps_trans, pairs=F, query_points=int(crec["n_query"].sum()), reference_points=n_ref,
-            t0=dict(degrees=args.t0_deg, metres=args.t0_m, about="the survey's centroid", seed=1357), **both(whole),
-            one_search_launch_ms=stats(one_search), one_solve_launch_ms=stats(one_solve), launches_per_call=counts,
-            launch_totals_ms={k: stats(v) for k, v in tot.items()},
-            iterations=dict(histogram={str(k): int((iters == k).sum()) for k in sorted(set(iters.tolist()))}, mean=float(iters.mean()), max=int(iters.max())),
-            converged_pairs=int(((rec["status"] & abi.LK_ALIGN_CONVERGED) != 0).sum()), few_pairs=int(((rec["status"] & abi.LK_ALIGN_FEW) != 0).sum()),
-            bad_pairs=int((rec["status"] & 19 != 0).sum()), rmse_first_median=float(np.nanmedian(rec["rmse_first"])), rmse_last_median=float(np.nanmedian(crec["rmse"])),
-            matched_first=int(rec["n_matched_first"].sum()), matched_last=int(crec["n_matched"].sum()),
-            final_T_from_identity=dict(degrees_median=float(np.median(angle)), degrees_max=float(angle.max()), metres_at_centroid_median=float(np.median(shift)),
-                                       metres_at_centroid_max=float(shift.max())))
+def align_plane(max_iter=args.max_iter, key="plane"):
+    def call():
+        last[key] = g.clouds_align_plane_dev(d_out, out_off, d_ref, ref_off, d_nrm, pairs, md, T0, max_iter, args.eps_rot, args.eps_trans, thr)
+    return call
+
+
+def measure(make, key, solve):
+    """One alignment entry on the workload: the whole call, its launch totals and counts, one search launch, one solve launch, what the pairs did."""
+    whole = timed(make())
+    rec, crec = last[key][0], last[key][-2]
+    launches = ("align_init", "align_search", solve, "c2c_reduce")
+    tot = rw.per_launch(g, make(), launches, args.reps)
+    counts = {}
+    g.profile_reset(), g.profile_enable(True)
+    make()()
+    for k in launches:
+        counts[k] = int(g.profile_get(k)[0])
+    g.profile_enable(False)
+    one_search = rw.per_launch(g, make(0, key + "0"), ("align_search",), args.reps, count=1)["align_search"]
+    one_solve = rw.per_launch(g, make(1, key + "1"), ("align_search", solve), args.reps)[solve]
+    extra = {}
+    if solve == "align_plane_solve":            # (with max_iter 1 the kernel runs twice: the solve, then the closing first pass, which max_iter 0 runs alone)
+        closing = rw.per_launch(g, make(0, key + "0"), (solve,), args.reps, count=1)[solve]
+        one_solve = [max(v - float(np.median(closing)), 0.0) for v in one_solve]
+        extra["one_closing_pass_launch_ms"] = stats(closing)
+    angle = np.degrees(np.arccos(np.clip((rec["rot"][:, 0] + rec["rot"][:, 4] + rec["rot"][:, 8] - 1) / 2, -1, 1)))
+    shift = np.linalg.norm(rec["rot"].reshape(-1, 3, 3) @ centre + rec["trans"] - centre, axis=1)
+    iters = rec["iters"].astype(int)
+    return dict(max_dist=md, max_iter=args.max_iter, eps_rot=args.eps_rot, eps_trans=args.eps_trans, pairs=F, query_points=int(crec["n_query"].sum()), reference_points=n_ref,
+                t0=dict(degrees=args.t0_deg, metres=args.t0_m, about="the survey's centroid", seed=1357), **both(whole),
+                one_search_launch_ms=stats(one_search), one_solve_launch_ms=stats(one_solve), **extra, launches_per_call=counts,
+                launch_totals_ms={k: stats(v) for k, v in tot.items()},
+                iterations=dict(histogram={str(k): int((iters == k).sum()) for k in sorted(set(iters.tolist()))}, mean=float(iters.mean()), max=int(iters.max())),
+                converged_pairs=int(((rec["status"] & abi.LK_ALIGN_CONVERGED) != 0).sum()), few_pairs=int(((rec["status"] & abi.LK_ALIGN_FEW) != 0).sum()),
+                degenerate_pairs=int(((rec["status"] & abi.LK_ALIGN_DEGENERATE) != 0).sum()),
+                bad_pairs=int((rec["status"] & 19 != 0).sum()), rmse_first_median=float(np.nanmedian(rec["rmse_first"])), rmse_last_median=float(np.nanmedian(crec["rmse"])),
+                matched_first=int(rec["n_matched_first"].sum()), matched_last=int(crec["n_matched"].sum()),
+                final_T_from_identity=dict(degrees_median=float(np.median(angle)), degrees_max=float(angle.max()), metres_at_centroid_median=float(np.median(shift)),
+                                           metres_at_centroid_max=float(shift.max())))
+
+
+def show(name, form):
+    print(f"  {name}: {form['event_ms']['median']:.3f} ms between events ({form['event_ms']['min']:.3f} .. {form['event_ms']['max']:.3f}), wall {form['wall_ms']['median']:.3f}; "
+          f"one search {form['one_search_launch_ms']['median']:.3f} ms, one solve {form['one_solve_launch_ms']['median']:.3f} ms; launches {form['launches_per_call']}")
+    print("  launch totals: " + ", ".join(f"{k} {v['median']:.3f}" for k, v in form["launch_totals_ms"].items()))
+    print(f"  iterations {form['iterations']}, converged {form['converged_pairs']}, degenerate {form['degenerate_pairs']}, few {form['few_pairs']}, bad {form['bad_pairs']}; "
+          f"rmse {form['rmse_first_median']:.4f} -> {form['rmse_last_median']:.4f} m; final T from the identity: {form['final_T_from_identity']}")
+
+
+def chain_lines():
+    for k in ("replay", "downsample", "c2c_accuracy"):
+        print(f"  {k:12s}: before {before[k]['event_ms']['median']:.3f} ms ({before[k]['event_ms']['min']:.3f} .. {before[k]['event_ms']['max']:.3f}), "
+              f"after {after[k]['event_ms']['median']:.3f} ms ({after[k]['event_ms']['min']:.3f} .. {after[k]['event_ms']['max']:.3f})")
+
+
+if args.plane:
+    d_nrm, d_map_nrm = g.device_malloc(16 * max(n_ref, 1)), g.device_malloc(16 * n_map)
+    nr_args = (args.normal_radius, args.normal_min_pts, args.normal_min_planarity)
+
+    def normals_survey():
+        last["nrm"] = g.clouds_normals_dev(d_ref, ref_off, nr_args[0], d_nrm, nr_args[1], nr_args[2])
+
+    def normals_map():
+        last["nrm_map"] = g.clouds_normals_dev(d_out, out_off, nr_args[0], d_map_nrm, nr_args[1], nr_args[2])
+
+    def mme_survey():
+        g.clouds_mme_dev(d_ref, ref_off, nr_args[0], max(nr_args[1], 4))
+
+    def mme_map():
+        g.clouds_mme_dev(d_out, out_off, nr_args[0], max(nr_args[1], 4))
+
+    normals = dict(radius=nr_args[0], min_pts=nr_args[1], min_planarity=nr_args[2], survey=both(timed(normals_survey)), survey_mme_same_radius=both(timed(mme_survey)),
+                   map_clouds=both(timed(normals_map)), map_clouds_mme_same_radius=both(timed(mme_map)))
+    normals.update(survey_valid=int(last["nrm"]["n_valid"].sum()), survey_points=n_ref, map_valid=int(last["nrm_map"]["n_valid"].sum()), map_points=n_map)
+    normals_survey()
+    plane = measure(align_plane, "plane", "align_plane_solve")
+    pl = last["plane"][1]
+    plane.update(used_first=int(pl["n_used_first"].sum()), used_last=int(pl["n_used"].sum()), rmse_plane_first_median=float(np.nanmedian(pl["rmse_plane_first"])),
+                 rmse_plane_last_median=float(np.nanmedian(pl["rmse_plane"])))
+    point = measure(align, "align", "align_solve")
+    after = chain()
+    print(f"{R} runs x {K} config-1 scans -> {F} map clouds of {n_map} points (leaf {args.leaf}), survey of {n_ref} points; T0 {args.t0_deg} deg, {args.t0_m} m")
+    print(f"  normals (radius {nr_args[0]}, min_pts {nr_args[1]}, planarity {nr_args[2]}): survey {normals['survey']['event_ms']['median']:.3f} ms "
+          f"({normals['survey_valid']} of {n_ref} valid; mme {normals['survey_mme_same_radius']['event_ms']['median']:.3f} ms), map clouds "
+          f"{normals['map_clouds']['event_ms']['median']:.3f} ms ({normals['map_valid']} of {n_map} valid; mme {normals['map_clouds_mme_same_radius']['event_ms']['median']:.3f} ms)")
+    show("point-to-plane", plane)
+    print(f"  used {plane['used_first']} -> {plane['used_last']}, plane rmse {plane['rmse_plane_first_median']:.4f} -> {plane['rmse_plane_last_median']:.5f} m")
+    show("point-to-point", point)
+    chain_lines()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(tool="tools/map_align.py --plane", commit=args.commit, library=os.path.basename(binding.LIB_PATH), runs=R, scans_per_run=K, distinct_segments=D,
+                           leaf=args.leaf, reps=args.reps, warmup=args.warmup, registered_points=n_pts, map_clouds=F, map_points=n_map, survey_points=n_ref,
+                           ref_files=args.ref_files, normals=normals, align_plane=plane, align=point, chain_before=before, chain_after=after), f, indent=1)
+            f.write("\n")
+    timer.close()
+    w.close(d_world, d_out, d_ref, d_moved, d_nrm, d_map_nrm)
+    raise SystemExit(0)
+
+form = measure(align, "align", "align_solve")
+counts = form["launches_per_call"]
+iters = last["align"][0]["iters"].astype(int)
 
 # ---- route (a): one iteration the parent commit's way - C2C with nn outputs on the moved clouds, everything down, a numpy Horn solve per file, the clouds up
 g.clouds_transform_dev(d_out, out_off, T0, d_moved)
@@ -211,18 +294,12 @@ else:
 after = chain()
 
 print(f"{R} runs x {K} config-1 scans -> {F} map clouds of {n_map} points (leaf {args.leaf}), survey of {n_ref} points; T0 {args.t0_deg} deg, {args.t0_m} m")
-print(f"  align: {form['event_ms']['median']:.3f} ms between events ({form['event_ms']['min']:.3f} .. {form['event_ms']['max']:.3f}), wall {form['wall_ms']['median']:.3f}; "
-      f"one search {form['one_search_launch_ms']['median']:.3f} ms, one solve {form['one_solve_launch_ms']['median']:.3f} ms; launches {counts}")
-print(f"  launch totals: " + ", ".join(f"{k} {v['median']:.3f}" for k, v in form["launch_totals_ms"].items()))
-print(f"  iterations {form['iterations']}, converged {form['converged_pairs']}, few {form['few_pairs']}, bad {form['bad_pairs']}; rmse {form['rmse_first_median']:.4f} -> "
-      f"{form['rmse_last_median']:.4f} m; final T from the identity: {form['final_T_from_identity']}")
+show("align", form)
 print(f"  route (a) per iteration: c2c+nn {ra['c2c_with_nn']['event_ms']['median']:.2f} + d2h {ra['d2h']['wall_ms']['median']:.2f} + numpy solve "
       f"{ra['numpy_solve']['wall_ms_all_files_scaled']:.0f} + h2d {ra['h2d']['wall_ms']['median']:.2f} = {ra['per_iteration_ms']:.0f} ms; x {form['iterations']['mean']:.2f} iterations = "
       f"{ra['for_the_mean_iterations_ms']:.0f} ms")
 print(f"  route (b): d2h {rb['d2h']['wall_ms']['median']:.2f} ms + {rb['host']}")
-for k in ("replay", "downsample", "c2c_accuracy"):
-    print(f"  {k:12s}: before {before[k]['event_ms']['median']:.3f} ms ({before[k]['event_ms']['min']:.3f} .. {before[k]['event_ms']['max']:.3f}), "
-          f"after {after[k]['event_ms']['median']:.3f} ms ({after[k]['event_ms']['min']:.3f} .. {after[k]['event_ms']['max']:.3f})")
+chain_lines()
 if args.json:
     with open(args.json, "w") as f:
         json.dump(dict(tool="tools/map_align.py", commit=args.commit, library=os.path.basename(binding.LIB_PATH), runs=R, scans_per_run=K, distinct_segments=D, leaf=args.leaf,

@@ -861,6 +861,56 @@ int lk_clouds_normals_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, 
                           lk_normals* out, float* d_normals);
 int lk_clouds_normals(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double radius, uint32_t min_pts, double min_planarity,
                       lk_normals* out, float* normals);
+/* Outliers removed from many map clouds in one call: PCL's RadiusOutlierRemoval and StatisticalOutlierRemoval in one pass, between the voxel grid
+ * and a saved, scored or aligned map.  A point needs k neighbours within `reach`, and a mean distance to its k nearest that does not stand out of
+ * its cloud's.  leg-kilo_amd/cloudmetrics.py's sor is the numpy statement.
+ * Layout, offsets, alignment, status conditions and capacity limits are exactly lk_clouds_mme_dev's, with `reach` in the place of `radius`; w is
+ * never interpreted but is COPIED with its record.
+ * Definition, by brute force; all arithmetic in float64 from the float32 coordinates, without fused multiply-add; no grid is part of it:
+ *   candidates     of point i: every record j != i of the same cloud with d2(i, j) <= reach * reach, d2 exactly lk_clouds_c2c_dev's, reach * reach
+ *                  one rounded product.  Exclusion is BY INDEX: a duplicate of i is a candidate at distance 0.  cnt_i = their number, which is
+ *                  lk_clouds_mme_dev's d_n at radius == reach, minus 1.
+ *   isolated       cnt_i < k: the radius criterion.  dbar_i = NaN, the point is removed and takes no part in the statistics.
+ *   dbar_i         otherwise, with d2_(1) <= ... <= d2_(k) the k smallest candidate values (a multiset: equal d2 give equal roots, so which of
+ *                  several tied records is taken does not matter), dbar_i = (sqrt(d2_(1)) + ... + sqrt(d2_(k))) / k, the sum taken in that
+ *                  ascending order, one term after the other.
+ *   statistics     over the n_s non-isolated points of the cloud: mu = (sum dbar_i) / n_s, sigma = sqrt(sum (dbar_i - mu)^2 / (n_s - 1)) - the
+ *                  mean first, the centred squares second - and sigma = 0 when n_s == 1; thr = mu + n_sigma * sigma, and thr = +inf when
+ *                  n_sigma is +inf (no product is taken: radius-only filtering).  n_s == 0 gives NaN in all three.  Both sums run in an order of
+ *                  the library's that depends on the cloud alone: its record has the same bits whatever else the call holds.
+ *   kept           not isolated and dbar_i <= thr (a cloud of nothing but duplicates has dbar = mu = thr = 0 and keeps every point).
+ *                  n_outliers counts the non-isolated points that are not kept; worst = the index of the largest dbar_i.
+ * out: HOST, n_clouds records, every byte written.
+ * Outputs, each optional and independent, except that out_off is required with d_out or d_src_idx:
+ *   d_out      (DEVICE, 16-byte aligned, room for off[n_clouds] - off[0] records) the kept records of cloud c in INPUT ORDER, all 16 bytes bit for
+ *              bit, as records out_off[c] .. out_off[c+1]) of d_out; out_off: HOST, n_clouds + 1 entries, written by the call, out_off[0] == 0.
+ *              Nothing behind out_off[n_clouds] records is written.  d_out / out_off are what lk_clouds_c2c_dev, lk_clouds_mme_dev,
+ *              lk_clouds_normals_dev and the align entries take as they are.
+ *   d_src_idx  (DEVICE, 4-byte aligned, as many entries) for each output record its index within its input cloud: a caller's normals or any other
+ *              side array follow the filter with one gather.
+ *   d_keep (1 / 0, bytes), d_cnt (uint32), d_dbar (float64, NaN where isolated): per-point arrays, record off[c] + i at entry off[c] - off[0] + i.
+ * A cloud with a non-finite coordinate gets LK_SOR_NONFINITE, one with |p / reach| >= 2^30 LK_SOR_RANGE: NaN figures, zero counts but n_points, an
+ * empty output range, keep 0, cnt 0 and dbar NaN in its per-point entries; the other clouds of the call are unaffected.  Synchronous; no filter
+ * slot, map, overlay or bucket table is touched.
+ * LK_ERR_INVALID before anything is launched, the message naming the argument: n_clouds == 0, a null d_clouds, off or out, decreasing offsets,
+ * k == 0 or k > LK_SOR_MAX_K, reach not finite or <= 0, n_sigma NaN, < 0 or -inf, d_out or d_src_idx without out_off, a misaligned pointer (16 bytes
+ * for the clouds and d_out, 4 for d_src_idx and d_cnt, 8 for d_dbar), an output that overlaps the input or another output.  LK_ERR_CAPACITY as for
+ * lk_clouds_mme_dev.  A refused call writes nothing.
+ * lk_clouds_sor: the same with clouds, out_cloud, src_idx, keep, cnt and dbar in HOST memory (4-byte alignment for the clouds); the range is
+ * uploaded for the call and the arrays that were asked for are copied back. */
+#define LK_SOR_MAX_K 32u
+#define LK_SOR_NONFINITE 1u
+#define LK_SOR_RANGE     2u
+typedef struct lk_sor {            /* 64 bytes */
+    double   mu, sigma, thr;       /* over the non-isolated points; NaN with nothing to average or status != 0 */
+    uint64_t n_points, n_isolated, n_outliers, n_kept;   /* n_points = n_isolated + n_outliers + n_kept when status == 0 */
+    uint32_t worst;                /* index within the cloud of the largest dbar_i, the first on ties; 0 when none */
+    uint32_t status;               /* 0, LK_SOR_NONFINITE, LK_SOR_RANGE (bits) */
+} lk_sor;
+int lk_clouds_sor_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, uint32_t k, double reach, double n_sigma,
+                      lk_sor* out, float* d_out, uint64_t* out_off, uint32_t* d_src_idx, uint8_t* d_keep, uint32_t* d_cnt, double* d_dbar);
+int lk_clouds_sor(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, uint32_t k, double reach, double n_sigma,
+                  lk_sor* out, float* out_cloud, uint64_t* out_off, uint32_t* src_idx, uint8_t* keep, uint32_t* cnt, double* dbar);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

@@ -368,6 +368,34 @@ def normals_dtype():
     return dt
 
 
+class lk_sor(C.Structure):
+    _fields_ = [
+        ("mu", C.c_double),
+        ("sigma", C.c_double),
+        ("thr", C.c_double),
+        ("n_points", C.c_uint64),
+        ("n_isolated", C.c_uint64),
+        ("n_outliers", C.c_uint64),
+        ("n_kept", C.c_uint64),
+        ("worst", C.c_uint32),
+        ("status", C.c_uint32),
+    ]
+
+
+LK_SOR_MAX_K = 32       # lk_clouds_sor_dev: the largest k
+LK_SOR_NONFINITE = 1    # lk_sor.status: a coordinate of the cloud was not finite
+LK_SOR_RANGE = 2        # lk_sor.status: |p / reach| >= 2^30 in the cloud
+
+
+def sor_dtype():
+    """numpy view of lk_sor (64 B): the records of lk_clouds_sor_dev / lk_clouds_sor."""
+    import numpy as np
+
+    dt = np.dtype(lk_sor)
+    assert dt.itemsize == C.sizeof(lk_sor) == 64
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

@@ -820,6 +820,42 @@ class LegKiloHip:
         res = self._mme_call(self.L.lk_clouds_mme, _p(c), off, radius, min_pts, _p(cnt), _p(hh), _p(lm))
         return res, cnt[:total], hh[:total], lm[:total]
 
+    def _sor_call(self, fn, clouds, off, k, reach, n_sigma, out_cloud, want_off, src_idx, keep, cnt, dbar):
+        """What the two outlier-filter exports share - the offset tables and the records: fn(handle, clouds, table, k, reach, n_sigma, records,
+        outputs).  Returns (records, out_off or None)."""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.sor_dtype())
+        out_off = np.zeros(n + 1, dtype=np.uint64) if want_off else None
+        self._chk(fn(self.h, clouds, n, _p(o), int(k), float(reach), float(n_sigma), _p(res), out_cloud, _p(out_off), src_idx, keep, cnt, dbar))
+        return res[:n], out_off
+
+    def clouds_sor_dev(self, d_clouds, off, k, reach, n_sigma, d_out=0, d_src_idx=0, d_keep=0, d_cnt=0, d_dbar=0, want_off=None):
+        """Outliers removed from many clouds in device memory (lk_clouds_sor_dev): clouds_mme_dev's clouds and table.  A point with fewer than k
+        (1 .. 32) other records within `reach` is isolated; the others get dbar, the mean distance to their k nearest, and are kept when dbar <=
+        mu + n_sigma * sigma of their cloud (n_sigma = inf: the radius criterion alone).  d_out (device, room for off[-1] - off[0] records) takes
+        the kept records in input order, cloud c at out_off[c] : out_off[c + 1]; d_src_idx their indices within their input clouds; d_keep uint8,
+        d_cnt uint32, d_dbar float64 one entry per input record (0: none, each on its own).  Returns (abi.sor_dtype() records, out_off uint64 or
+        None - given with d_out or d_src_idx, or when want_off is set); cloudmetrics.sor is the numpy statement."""
+        want = bool(d_out or d_src_idx) if want_off is None else want_off
+        return self._sor_call(self.L.lk_clouds_sor_dev, d_clouds, off, k, reach, n_sigma, d_out or None, want, d_src_idx or None, d_keep or None, d_cnt or None,
+                              d_dbar or None)
+
+    def clouds_sor(self, clouds, off, k, reach, n_sigma, want_points=False):
+        """The same with the clouds in host memory (lk_clouds_sor): clouds float32 [n, 4] (x y z w records).  Returns (records, out_cloud float32
+        [n_kept, 4], out_off uint64, src_idx uint32 [n_kept]), with want_points also (keep uint8, cnt uint32, dbar float64), entry
+        off[c] - off[0] + i for record off[c] + i."""
+        c = np.ascontiguousarray(clouds, dtype=np.float32).reshape(-1, 4)
+        o = np.asarray(off, dtype=np.uint64)
+        total = int(o[-1] - o[0]) if len(o) else 0
+        out, src = np.zeros((max(total, 1), 4), dtype=np.float32), np.zeros(max(total, 1), dtype=np.uint32)
+        keep, cnt, dbar = (np.zeros(max(total, 1), dtype=np.uint8), np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1))) if want_points else (None,) * 3
+        res, out_off = self._sor_call(self.L.lk_clouds_sor, _p(c), off, k, reach, n_sigma, _p(out), True, _p(src), _p(keep), _p(cnt), _p(dbar))
+        m = int(out_off[-1])
+        if not want_points:
+            return res, out[:m], out_off, src[:m]
+        return res, out[:m], out_off, src[:m], keep[:total], cnt[:total], dbar[:total]
+
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
         file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at

@@ -437,3 +437,78 @@ def mme(cloud, radius, min_pts=5):
             out.update(mme=float(hs.sum() / len(sc)), h_max=float(hs.max()), worst=int(sc[np.argmax(hs)]))
     out["dense"], out["flat"], out["scored"] = out["cls"] != MME_SPARSE, out["cls"] == MME_FLAT, out["cls"] == MME_SCORED
     return out
+
+
+LK_SOR_MAX_K = 32
+LK_SOR_NONFINITE = LK_MME_NONFINITE
+LK_SOR_RANGE = LK_MME_RANGE
+
+
+def sor_tree_sum(v):
+    """The sum of a cloud's per-point values in lk_sor_stats_kernel's order: lane t of 256 adds the entries t, t + 256, ... one after the other, then
+    the partial sums meet in a halving tree.  (Entries that take no part are passed as +0.0, which changes no bit of a sum of non-negative terms.)"""
+    v = np.asarray(v, dtype=np.float64)
+    rows = np.concatenate([v, np.zeros((-len(v)) % 256)]).reshape(-1, 256)
+    part = np.cumsum(rows, axis=0)[-1] if len(rows) else np.zeros(256)
+    o = 128
+    while o:
+        part = part[:o] + part[o:2 * o]
+        o >>= 1
+    return float(part[0])
+
+
+def sor(cloud, k, reach, n_sigma, variant=None, block=1024):
+    """The statistical outlier filter of one cloud as lk_clouds_sor_dev defines it, by brute force: the candidates of point i are the records j != i
+    (by index) with d2 <= reach * reach, cnt_i their number; with cnt_i < k the point is isolated (dbar NaN), else dbar_i is the mean of the roots of
+    the k smallest candidate d2, summed in ascending order one after the other; mu and sigma (divisor n_s - 1, 0 for a single point) over the
+    non-isolated points, thr = mu + n_sigma * sigma (+inf for n_sigma = inf), kept when dbar_i <= thr.  Returns a dict: keep bool [m], cnt uint32
+    [m], dbar float64 [m], src_idx (the kept points' indices), and the record fields mu, sigma, thr, n_points, n_isolated, n_outliers, n_kept, worst,
+    status.  variant (test aid, one thing wrong each): "with_self", "self_by_coords", "isolated_in_stats", "biased", "strict_thr", "strict_reach",
+    "root_of_mean"."""
+    p = np.asarray(cloud, dtype=np.float32)[:, :3].astype(np.float64)
+    m, k = len(p), int(k)
+    st = mme_status(cloud, reach)
+    out = dict(keep=np.zeros(m, dtype=bool), cnt=np.zeros(m, dtype=np.uint32), dbar=np.full(m, np.nan), src_idx=np.zeros(0, dtype=np.uint32), mu=np.nan,
+               sigma=np.nan, thr=np.nan, n_points=m, n_isolated=0, n_outliers=0, n_kept=0, worst=0, status=st)
+    if st or not m:
+        return out
+    r2 = reach * reach
+    cnt, dbar = out["cnt"], out["dbar"]
+    block = max(1, min(block, (1 << 21) // m))
+    for a in range(0, m, block):
+        d = p[a:a + block, None, :] - p[None, :, :]                     # q - r, as d2 is stated
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        inside = d2 < r2 if variant == "strict_reach" else d2 <= r2
+        rows = np.arange(len(d))
+        if variant == "self_by_coords":
+            inside &= ~(d == 0.0).all(axis=2)
+        elif variant != "with_self":
+            inside[rows, a + rows] = False
+        cnt[a:a + block] = inside.sum(axis=1)
+        masked = np.where(inside, d2, np.inf)
+        if m < k:
+            masked = np.concatenate([masked, np.full((len(d), k - m), np.inf)], axis=1)
+        least = np.sort(np.partition(masked, k - 1, axis=1)[:, :k], axis=1)       # the k smallest, ascending
+        with np.errstate(invalid="ignore"):
+            if variant == "root_of_mean":
+                dbar[a:a + block] = np.sqrt(np.cumsum(least, axis=1)[:, -1] / k)
+            else:
+                dbar[a:a + block] = np.cumsum(np.sqrt(least), axis=1)[:, -1] / k   # (cumsum: one term after the other, no pairwise tree)
+    iso = cnt < k
+    dbar[iso] = np.nan
+    stat = np.where(iso, reach, dbar) if variant == "isolated_in_stats" else dbar
+    ok = ~np.isnan(stat)
+    n_s = int(ok.sum())
+    out["n_isolated"] = int(iso.sum())
+    if n_s:
+        mu = sor_tree_sum(np.where(ok, stat, 0.0)) / n_s
+        e = np.where(ok, stat - mu, 0.0)
+        div = n_s if variant == "biased" else n_s - 1
+        sigma = float(np.sqrt(sor_tree_sum(e * e) / div)) if n_s > 1 else 0.0
+        thr = np.inf if n_sigma == np.inf else mu + n_sigma * sigma
+        with np.errstate(invalid="ignore"):
+            keep = (dbar < thr) if variant == "strict_thr" else (dbar <= thr)
+        out.update(mu=mu, sigma=sigma, thr=float(thr), keep=keep, n_kept=int(keep.sum()), worst=int(np.nanargmax(dbar)) if (~iso).any() else 0)
+        out["n_outliers"] = int((~iso).sum()) - out["n_kept"]
+    out["src_idx"] = np.flatnonzero(out["keep"]).astype(np.uint32)
+    return out

@@ -6,7 +6,8 @@
 // c2c_run's call with the search iterated under a transform, lk_clouds_transform_dev writes the moved clouds; lk_clouds_align_plane_dev /
 // lk_clouds_align_plane are the same loop with the point-to-plane solve between the searches (lk_align_plane_kernels.h, arithmetic in
 // lk_align_plane.h) against per-point normals of the reference, which lk_clouds_normals_dev / lk_clouds_normals make from MME's neighbourhood walk
-// (lk_normals_kernels.h, arithmetic in lk_normals.h).
+// (lk_normals_kernels.h, arithmetic in lk_normals.h); lk_clouds_sor_dev / lk_clouds_sor remove a cloud's outliers by the mean distance to the k nearest
+// neighbours (lk_sor_kernels.h, arithmetic in lk_sor.h) and write the kept records as clouds every entry above takes.
 // What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
 // use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
@@ -17,12 +18,14 @@
 #include "lk_align_plane_kernels.h"
 #include "lk_mme_kernels.h"
 #include "lk_normals_kernels.h"
+#include "lk_sor_kernels.h"
 
 static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
 static_assert(sizeof(lk_mme) == 64, "lk_mme must be 64 B");
 static_assert(sizeof(lk_align) == 136, "lk_align must be 136 B");
 static_assert(sizeof(lk_align_plane) == 32, "lk_align_plane must be 32 B");
 static_assert(sizeof(lk_normals) == 24, "lk_normals must be 24 B");
+static_assert(sizeof(lk_sor) == 64, "lk_sor must be 64 B");
 static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
 
 namespace {
@@ -670,6 +673,145 @@ int lk_clouds_normals(lk_handle* h, const float* clouds, size_t n_clouds, const 
     a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
     a.normals = static_cast<float*>(st.out[0].dev);
     LKCHK(normals_run(h, a, total));
+    return st.fetch(h);
+}
+
+}  // extern "C"
+
+namespace {
+struct SorArgs {   // the arguments both entries share, as the caller gave them
+    const float* clouds;
+    size_t n_clouds;
+    const uint64_t* off;
+    uint32_t k;
+    double reach, n_sigma;
+    lk_sor* out;
+    float* out_cloud;
+    uint64_t* out_off;
+    uint32_t* src_idx;
+    uint8_t* keep;
+    uint32_t* cnt;
+    double* dbar;
+};
+}  // namespace
+
+// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals with the reach as the radius, then the entry's own.  *total: records in all
+static int sor_check(lk_handle* h, const char* who, const SorArgs& a, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    if (!std::isfinite(a.reach) || !(a.reach > 0.0)) return fail(h, LK_ERR_INVALID, w + "reach must be finite and above 0");
+    lk_mme sink;
+    const MmeArgs m = {a.clouds, a.n_clouds, a.off, a.reach, 4u, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
+    LKCHK(mme_check(h, who, m, cloud_align, total));
+    if (a.k == 0 || a.k > LK_SOR_MAX_K) return fail(h, LK_ERR_INVALID, w + "k is " + std::to_string(a.k) + ": 1 .. " + std::to_string(LK_SOR_MAX_K));
+    if (!(a.n_sigma >= 0.0)) return fail(h, LK_ERR_INVALID, w + "n_sigma must be 0 or above (+inf: the radius criterion alone)");
+    if (a.out_cloud && !a.out_off) return fail(h, LK_ERR_INVALID, w + "out_cloud needs out_off");
+    if (a.src_idx && !a.out_off) return fail(h, LK_ERR_INVALID, w + "src_idx needs out_off");
+    if ((uintptr_t)a.out_cloud & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "out_cloud must be " + std::to_string(cloud_align) + "-byte aligned");
+    if ((uintptr_t)a.src_idx & 3) return fail(h, LK_ERR_INVALID, w + "src_idx must be 4-byte aligned");
+    if ((uintptr_t)a.cnt & 3) return fail(h, LK_ERR_INVALID, w + "cnt must be 4-byte aligned");
+    if ((uintptr_t)a.dbar & 7) return fail(h, LK_ERR_INVALID, w + "dbar must be 8-byte aligned");
+    const C2cSpan in = {"clouds", (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0], 16u * *total};
+    const C2cSpan o[5] = {{"out_cloud", (uintptr_t)a.out_cloud, 16 * *total}, {"src_idx", (uintptr_t)a.src_idx, 4 * *total}, {"keep", (uintptr_t)a.keep, *total},
+                          {"cnt", (uintptr_t)a.cnt, 4 * *total}, {"dbar", (uintptr_t)a.dbar, 8 * *total}};
+    for (int i = 0; i < 5; ++i) LKCHK(c2c_overlap_check(h, w, o[i], &in, 1, "the input clouds", o + i + 1, 4 - i));
+    return LK_OK;
+}
+
+template <int CAP>
+static void sor_point_launch(lk_handle* h, const LkSorCall& m, size_t N) {
+    hipLaunchKernelGGL(lk_sor_point_kernel<CAP>, c2c_blocks(N), dim3(256), 0, h->stream, m);
+}
+
+// the call behind sor_check, on DEVICE clouds and DEVICE outputs (null: not asked for; what a later kernel needs is then the library's own).
+// *n_out: records written to out_cloud / src_idx
+static int sor_run(lk_handle* h, const SorArgs& a, size_t N, size_t* n_out) {
+    const size_t NC = a.n_clouds;
+    std::vector<unsigned int> used;   // every non-empty cloud
+    for (size_t c = 0; c < NC; ++c)
+        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+    const bool flags = a.keep || a.out_off, places = a.out_off != nullptr, moved = a.out_cloud || a.src_idx;
+    C2cIndex x = {};
+    LkSorCall m = {};
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
+        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
+        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
+        x.recs = c.take<LkC2cRec>(N);
+        m.dbar = c2c_or_own(c, a.dbar, N);
+        m.flag = c.take<unsigned int>(flags ? N + 1 : 0), m.scan = c.take<unsigned int>(places ? N + 1 : 0);
+        m.thr = c.take<double>(NC), m.out_off = c.take<unsigned int>(places ? NC + 1 : 0);
+        m.out = c.take<lk_sor>(NC);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
+    carve(h->c2c.p);
+    size_t scan_tmp = 0;
+    if (places) {   // (before anything is launched: growing the temporary storage waits for the stream)
+        HIPCHK(h, lk_prim_exclusive_scan(nullptr, scan_tmp, m.flag, m.scan, N + 1, h->stream));
+        LKCHK(reserve(h, h->prim_tmp, scan_tmp));
+    }
+    LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.reach, x));
+    m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
+    m.in = reinterpret_cast<const uint4*>(a.clouds) + a.off[0];
+    m.cnt = a.cnt, m.keep = a.keep, m.out_pts = reinterpret_cast<uint4*>(a.out_cloud), m.src_idx = a.src_idx;
+    m.reach2 = lk_c2c_reach2(a.reach), m.n_sigma = a.n_sigma;
+    m.n_clouds = (unsigned int)NC, m.k = a.k, m.total = (unsigned int)N;
+    if (N) {
+        const int cap = lk_sor_cap_of(a.k);
+        if (cap == LK_SOR_CAP_SMALL) LAUNCH(h, "sor_point", sor_point_launch<LK_SOR_CAP_SMALL>(h, m, N));
+        else if (cap == LK_SOR_CAP_MID) LAUNCH(h, "sor_point", sor_point_launch<LK_SOR_CAP_MID>(h, m, N));
+        else LAUNCH(h, "sor_point", sor_point_launch<LK_SOR_CAP_BIG>(h, m, N));
+    }
+    LAUNCH(h, "sor_stats", hipLaunchKernelGGL(lk_sor_stats_kernel, dim3((unsigned int)NC), dim3(256), 0, h->stream, m));
+    std::vector<lk_sor> rec(NC);
+    std::vector<unsigned int> ooff(places ? NC + 1 : 0);
+    HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_sor) * NC, hipMemcpyDeviceToHost, h->stream));
+    if (flags) LAUNCH(h, "sor_flag", hipLaunchKernelGGL(lk_sor_flag_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
+    if (places) {
+        size_t tb = h->prim_tmp.cap;
+        hipError_t scanned = hipSuccess;
+        LAUNCH(h, "sor_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, m.scan, N + 1, h->stream));
+        HIPCHK(h, scanned);
+        LAUNCH(h, "sor_offsets", hipLaunchKernelGGL(lk_sor_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, m));
+        HIPCHK(h, hipMemcpyAsync(ooff.data(), m.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
+        if (moved && N) LAUNCH(h, "sor_scatter", hipLaunchKernelGGL(lk_sor_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(a.out, rec.data(), sizeof(lk_sor) * NC);
+    if (places)
+        for (size_t c = 0; c <= NC; ++c) a.out_off[c] = ooff[c];
+    if (n_out) *n_out = places ? ooff[NC] : 0;
+    return LK_OK;
+}
+
+extern "C" {
+
+int lk_clouds_sor_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, uint32_t k, double reach, double n_sigma, lk_sor* out, float* d_out,
+                      uint64_t* out_off, uint32_t* d_src_idx, uint8_t* d_keep, uint32_t* d_cnt, double* d_dbar) {
+    CHECK_H(h);
+    const SorArgs a = {d_clouds, n_clouds, off, k, reach, n_sigma, out, d_out, out_off, d_src_idx, d_keep, d_cnt, d_dbar};
+    size_t total = 0;
+    LKCHK(sor_check(h, "lk_clouds_sor_dev", a, 16, &total));
+    return sor_run(h, a, total, nullptr);
+}
+
+int lk_clouds_sor(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, uint32_t k, double reach, double n_sigma, lk_sor* out, float* out_cloud,
+                  uint64_t* out_off, uint32_t* src_idx, uint8_t* keep, uint32_t* cnt, double* dbar) {
+    CHECK_H(h);
+    SorArgs a = {clouds, n_clouds, off, k, reach, n_sigma, out, out_cloud, out_off, src_idx, keep, cnt, dbar};
+    size_t total = 0, n_out = 0;
+    LKCHK(sor_check(h, "lk_clouds_sor", a, 4, &total));
+    C2cStage st;
+    st.in = {{clouds, off, n_clouds}};
+    st.out = {{out_cloud, 16, total}, {src_idx, 4, total}, {keep, 1, total}, {cnt, 4, total}, {dbar, 8, total}};
+    LKCHK(st.upload(h));
+    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
+    a.out_cloud = static_cast<float*>(st.out[0].dev), a.src_idx = static_cast<uint32_t*>(st.out[1].dev), a.keep = static_cast<uint8_t*>(st.out[2].dev);
+    a.cnt = static_cast<uint32_t*>(st.out[3].dev), a.dbar = static_cast<double*>(st.out[4].dev);
+    LKCHK(sor_run(h, a, total, &n_out));
+    st.out[0].count = st.out[1].count = n_out;   // nothing behind the kept records is written
     return st.fetch(h);
 }
 

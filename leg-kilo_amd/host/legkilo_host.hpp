@@ -533,6 +533,23 @@ class KiloPath {
         dev_->check(lk_clouds_mme_dev(dev_->h(), d_clouds, off.size() - 1, off.data(), radius, min_pts, out.data(), d_n, d_h, d_lmin));
         return out;
     }
+    // lk_clouds_sor_dev: outliers removed from map clouds where they lie - cloudsMmeDev's clouds and table.  A point with fewer than k (1 .. 32)
+    // other records within `reach` is isolated; the others are kept when the mean distance to their k nearest is at most mu + n_sigma * sigma of
+    // their cloud (n_sigma = infinity: the radius criterion alone).  d_out (room for off.back() - off.front() records) takes the kept records in
+    // input order, cloud c at (*out_off)[c] .. (*out_off)[c + 1]) - what cloudsC2cDev, cloudsMmeDev, cloudsNormalsDev and the align entries take
+    // as they are; d_src_idx their indices within their input clouds; d_keep / d_cnt / d_dbar (each optional) one entry per input record.
+    std::vector<lk_sor> cloudsSorDev(const float* d_clouds, const std::vector<uint64_t>& off, uint32_t k, double reach, double n_sigma, float* d_out = nullptr,
+                                     std::vector<uint64_t>* out_off = nullptr, uint32_t* d_src_idx = nullptr, uint8_t* d_keep = nullptr, uint32_t* d_cnt = nullptr,
+                                     double* d_dbar = nullptr) {
+        if (off.size() < 2) throw std::runtime_error("cloudsSorDev: the offset table is empty");
+        if ((d_out || d_src_idx) && !out_off) throw std::runtime_error("cloudsSorDev: d_out and d_src_idx need out_off");
+        std::vector<lk_sor> out(off.size() - 1);
+        std::vector<uint64_t> oo(off.size());
+        dev_->check(lk_clouds_sor_dev(dev_->h(), d_clouds, off.size() - 1, off.data(), k, reach, n_sigma, out.data(), d_out, out_off ? oo.data() : nullptr, d_src_idx,
+                                      d_keep, d_cnt, d_dbar));
+        if (out_off) *out_off = oo;
+        return out;
+    }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
     // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with

@@ -911,6 +911,65 @@ int lk_clouds_sor_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, cons
                       lk_sor* out, float* d_out, uint64_t* out_off, uint32_t* d_src_idx, uint8_t* d_keep, uint32_t* d_cnt, double* d_dbar);
 int lk_clouds_sor(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, uint32_t k, double reach, double n_sigma,
                   lk_sor* out, float* out_cloud, uint64_t* out_off, uint32_t* src_idx, uint8_t* keep, uint32_t* cnt, double* dbar);
+/* Many map clouds clustered in one call: DBSCAN (Open3D's cluster_dbscan, scikit-learn's DBSCAN), and with min_pts == 1 PCL's
+ * EuclideanClusterExtraction - the connected components within `reach`.  It says which points belong together, which none of the per-point entries
+ * above can: a detached clump or a ghost trail is locally as dense as a wall and passes lk_clouds_sor_dev; it goes with a minimum cluster size or
+ * with LK_CLUSTER_KEEP_LARGEST.  leg-kilo_amd/cloudmetrics.py's cluster is the numpy statement.
+ * Layout, offsets, alignment, status conditions and capacity limits are exactly lk_clouds_mme_dev's, with `reach` in the place of `radius`; w is
+ * never interpreted but is COPIED with its record.
+ * Definition, by brute force; every decision is taken on d2 - exactly lk_clouds_c2c_dev's, in float64 from the float32 coordinates, without fused
+ * multiply-add - against reach * reach, one rounded product; no grid is part of it:
+ *   neighbourhood  n_i = the number of records j of the same cloud with d2(i, j) <= reach * reach.  i itself counts, and so do duplicates: n_i is
+ *                  lk_clouds_mme_dev's d_n at radius == reach and lk_clouds_sor_dev's d_cnt + 1.
+ *   CORE           n_i >= min_pts (scikit-learn's and Open3D's convention: the point counts itself).
+ *   clusters       the connected components of the graph on the CORE points of one cloud with an edge where d2 <= reach * reach.  A point that
+ *                  is not core never carries a link: two clusters that touch only through a border point stay two.
+ *   BORDER         not core, with at least one core point within reach.  It joins the cluster of the core point j that minimises (d2, j)
+ *                  lexicographically - the smallest index on equal d2, lk_clouds_c2c_dev's rule.  (Not the usual first-visit rule: this one does
+ *                  not depend on any order of traversal.)
+ *   NOISE          everything else; its label is 0xffffffff.
+ *   numbering      the clusters of a cloud are numbered 0 .. n_clusters - 1 in ascending order of their smallest CORE member's index within the
+ *                  cloud; a border point with a smaller index does not change the order.
+ *   size           of a cluster: its core plus its border members.
+ *   kept           a point of a cluster with min_size <= size <= max_size (0 and 1 mean the same for min_size; max_size 0xffffffff: no bound).
+ *                  With LK_CLUSTER_KEEP_LARGEST only the points of the largest cluster within those bounds are kept; among clusters of equal
+ *                  size the smallest id is the largest.
+ * All of it is whole numbers: a cloud's labels, ids, sizes and record have the same bits whatever else the call holds, and from run to run.
+ * out: HOST, n_clouds records, every byte written.  largest / largest_size: the largest cluster of the cloud (whatever the bounds) and its size.
+ * Outputs, each optional and independent, except that cl_off is required with d_cl_size or d_cl_first and out_off with d_out or d_src_idx:
+ *   d_label (uint32: the cluster's id within its cloud, or 0xffffffff), d_kind (bytes: 0 noise, 1 border, 2 core), d_n (uint32: n_i): DEVICE
+ *              per-point arrays, record off[c] + i at entry off[c] - off[0] + i.
+ *   d_cl_size, d_cl_first  (DEVICE, uint32, room for off[n_clouds] - off[0] entries) cluster k of cloud c at entry cl_off[c] + k: its size and its
+ *              smallest core index within the cloud.  cl_off: HOST, n_clouds + 1 entries, written by the call, cl_off[0] == 0.  Nothing behind
+ *              cl_off[n_clouds] entries is written.
+ *   d_out, out_off, d_src_idx  exactly lk_clouds_sor_dev's: the kept records of cloud c in INPUT ORDER, all 16 bytes bit for bit, as records
+ *              out_off[c] .. out_off[c+1]) of d_out, and for each its index within its input cloud.  They are what lk_clouds_c2c_dev,
+ *              lk_clouds_mme_dev, lk_clouds_normals_dev, lk_clouds_sor_dev and the align entries take as they are.
+ * A cloud with a non-finite coordinate gets LK_CLUSTER_NONFINITE, one with |p / reach| >= 2^30 LK_CLUSTER_RANGE: zero counts but n_points, label
+ * 0xffffffff, kind 0 and n 0 in its per-point entries, no clusters and an empty output range; the other clouds of the call are unaffected.
+ * Synchronous; no filter slot, map, overlay or bucket table is touched.
+ * LK_ERR_INVALID before anything is launched, the message naming the argument: n_clouds == 0, a null d_clouds, off or out, decreasing offsets,
+ * reach not finite or <= 0, min_pts == 0, min_size > max_size, an unknown flag, d_cl_size or d_cl_first without cl_off, d_out or d_src_idx without
+ * out_off, a misaligned pointer (16 bytes for the clouds and d_out, 4 for the uint32 arrays), an output that overlaps the input or another
+ * output.  LK_ERR_CAPACITY as for lk_clouds_mme_dev.  A refused call writes nothing.
+ * lk_clouds_cluster: the same with the clouds and every array in HOST memory (4-byte alignment for the clouds); the range is uploaded for the call
+ * and the arrays that were asked for are copied back. */
+#define LK_CLUSTER_KEEP_LARGEST 1u
+#define LK_CLUSTER_NONFINITE 1u
+#define LK_CLUSTER_RANGE     2u
+typedef struct lk_cluster {        /* 64 bytes */
+    uint64_t n_points, n_core, n_border, n_noise, n_kept;   /* n_points = n_core + n_border + n_noise when status == 0 */
+    uint32_t n_clusters, n_kept_clusters;
+    uint32_t largest, largest_size;   /* id and size of the largest cluster, the smallest id among equals; 0 and 0 when there is no cluster */
+    uint32_t status;               /* 0, LK_CLUSTER_NONFINITE, LK_CLUSTER_RANGE (bits) */
+    uint32_t pad;                  /* written 0 */
+} lk_cluster;
+int lk_clouds_cluster_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double reach, uint32_t min_pts, uint32_t min_size,
+                          uint32_t max_size, uint32_t flags, lk_cluster* out, uint32_t* d_label, uint8_t* d_kind, uint32_t* d_n, uint32_t* d_cl_size,
+                          uint32_t* d_cl_first, uint64_t* cl_off, float* d_out, uint64_t* out_off, uint32_t* d_src_idx);
+int lk_clouds_cluster(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double reach, uint32_t min_pts, uint32_t min_size,
+                      uint32_t max_size, uint32_t flags, lk_cluster* out, uint32_t* label, uint8_t* kind, uint32_t* n, uint32_t* cl_size,
+                      uint32_t* cl_first, uint64_t* cl_off, float* out_cloud, uint64_t* out_off, uint32_t* src_idx);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

@@ -396,6 +396,37 @@ def sor_dtype():
     return dt
 
 
+class lk_cluster(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_uint64),
+        ("n_core", C.c_uint64),
+        ("n_border", C.c_uint64),
+        ("n_noise", C.c_uint64),
+        ("n_kept", C.c_uint64),
+        ("n_clusters", C.c_uint32),
+        ("n_kept_clusters", C.c_uint32),
+        ("largest", C.c_uint32),
+        ("largest_size", C.c_uint32),
+        ("status", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
+LK_CLUSTER_KEEP_LARGEST = 1   # lk_clouds_cluster_dev flags: keep the largest cluster within the size bounds only
+LK_CLUSTER_NONFINITE = 1      # lk_cluster.status: a coordinate of the cloud was not finite
+LK_CLUSTER_RANGE = 2          # lk_cluster.status: |p / reach| >= 2^30 in the cloud
+LK_CLUSTER_NOISE = 0xFFFFFFFF   # d_label of a noise point
+
+
+def cluster_dtype():
+    """numpy view of lk_cluster (64 B): the records of lk_clouds_cluster_dev / lk_clouds_cluster."""
+    import numpy as np
+
+    dt = np.dtype(lk_cluster)
+    assert dt.itemsize == C.sizeof(lk_cluster) == 64
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

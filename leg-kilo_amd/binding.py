@@ -856,6 +856,49 @@ class LegKiloHip:
             return res, out[:m], out_off, src[:m]
         return res, out[:m], out_off, src[:m], keep[:total], cnt[:total], dbar[:total]
 
+    def _cluster_call(self, fn, clouds, off, reach, min_pts, min_size, max_size, flags, label, kind, n_arr, cl_size, cl_first, want_cl_off, out_cloud, want_off, src_idx):
+        """What the two clustering exports share - the offset tables and the records: fn(handle, clouds, table, reach, min_pts, the size bounds, flags,
+        records, outputs).  Returns (records, cl_off or None, out_off or None)."""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.cluster_dtype())
+        cl_off = np.zeros(n + 1, dtype=np.uint64) if want_cl_off else None
+        out_off = np.zeros(n + 1, dtype=np.uint64) if want_off else None
+        self._chk(fn(self.h, clouds, n, _p(o), float(reach), int(min_pts), int(min_size), int(max_size), int(flags), _p(res), label, kind, n_arr, cl_size, cl_first,
+                     _p(cl_off), out_cloud, _p(out_off), src_idx))
+        return res[:n], cl_off, out_off
+
+    def clouds_cluster_dev(self, d_clouds, off, reach, min_pts=1, min_size=0, max_size=0xFFFFFFFF, flags=0, d_label=0, d_kind=0, d_n=0, d_cl_size=0, d_cl_first=0,
+                           d_out=0, d_src_idx=0, want_cl_off=None, want_off=None):
+        """Many clouds in device memory clustered (lk_clouds_cluster_dev, DBSCAN; min_pts = 1: the connected components within `reach`):
+        clouds_mme_dev's clouds and table.  A point with at least min_pts records within `reach`, itself among them, is core; core points within
+        reach of each other share a cluster; another point joins the cluster of its nearest core point within reach or is noise.  d_label uint32
+        (the cluster's id within its cloud, 0xffffffff for noise), d_kind uint8 (0 noise, 1 border, 2 core), d_n uint32: one entry per input record;
+        d_cl_size / d_cl_first uint32: cluster k of cloud c at entry cl_off[c] + k; d_out / d_src_idx: the points of the clusters with min_size <=
+        size <= max_size (flags = abi.LK_CLUSTER_KEEP_LARGEST: of the largest of them) in input order, cloud c at out_off[c] : out_off[c + 1]
+        (0: none, each on its own).  Returns (abi.cluster_dtype() records, cl_off uint64 or None, out_off uint64 or None) - a table is given with
+        the arrays that need it, or when its want_ is set; cloudmetrics.cluster is the numpy statement."""
+        wc = bool(d_cl_size or d_cl_first) if want_cl_off is None else want_cl_off
+        wo = bool(d_out or d_src_idx) if want_off is None else want_off
+        return self._cluster_call(self.L.lk_clouds_cluster_dev, d_clouds, off, reach, min_pts, min_size, max_size, flags, d_label or None, d_kind or None, d_n or None,
+                                  d_cl_size or None, d_cl_first or None, wc, d_out or None, wo, d_src_idx or None)
+
+    def clouds_cluster(self, clouds, off, reach, min_pts=1, min_size=0, max_size=0xFFFFFFFF, flags=0):
+        """The same with the clouds in host memory (lk_clouds_cluster): clouds float32 [n, 4] (x y z w records).  Returns a dict: res (records), label
+        uint32, kind uint8, n uint32 (entry off[c] - off[0] + i for record off[c] + i), cl_size, cl_first uint32 and cl_off uint64, out float32
+        [n_kept, 4], out_off uint64, src_idx uint32 [n_kept]."""
+        c = np.ascontiguousarray(clouds, dtype=np.float32).reshape(-1, 4)
+        o = np.asarray(off, dtype=np.uint64)
+        total = int(o[-1] - o[0]) if len(o) else 0
+        u32 = lambda: np.zeros(max(total, 1), dtype=np.uint32)   # noqa: E731
+        label, kind, n_arr, cl_size, cl_first, src = u32(), np.zeros(max(total, 1), dtype=np.uint8), u32(), u32(), u32(), u32()
+        out = np.zeros((max(total, 1), 4), dtype=np.float32)
+        res, cl_off, out_off = self._cluster_call(self.L.lk_clouds_cluster, _p(c), off, reach, min_pts, min_size, max_size, flags, _p(label), _p(kind), _p(n_arr),
+                                                  _p(cl_size), _p(cl_first), True, _p(out), True, _p(src))
+        k, m = int(cl_off[-1]), int(out_off[-1])
+        return dict(res=res, label=label[:total], kind=kind[:total], n=n_arr[:total], cl_size=cl_size[:k], cl_first=cl_first[:k], cl_off=cl_off, out=out[:m],
+                    out_off=out_off, src_idx=src[:m])
+
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
         file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at

@@ -512,3 +512,111 @@ def sor(cloud, k, reach, n_sigma, variant=None, block=1024):
         out["n_outliers"] = int((~iso).sum()) - out["n_kept"]
     out["src_idx"] = np.flatnonzero(out["keep"]).astype(np.uint32)
     return out
+
+
+LK_CLUSTER_KEEP_LARGEST = 1
+LK_CLUSTER_NONFINITE = LK_MME_NONFINITE
+LK_CLUSTER_RANGE = LK_MME_RANGE
+LK_CLUSTER_NOISE = 0xFFFFFFFF
+CLUSTER_NOISE, CLUSTER_BORDER, CLUSTER_CORE = 0, 1, 2
+CLUSTER_VARIANTS = ("border_links", "no_self", "strict_reach", "border_smallest_index", "ids_by_member")
+
+
+def cluster_pairs(cloud, reach, strict=False, block=1024):
+    """Every ordered pair i != j (by index) of a cloud's records with d2 <= reach * reach, by brute force -> (i, j, d2), i ascending."""
+    p = np.asfortranarray(np.asarray(cloud, dtype=np.float32)[:, :3].astype(np.float64))
+    m = len(p)
+    r2 = reach * reach
+    ii, jj, dd = [], [], []
+    block = max(1, min(block, (1 << 21) // max(m, 1)))
+    for a in range(0, m, block):
+        dx, dy, dz = (p[a:a + block, None, k] - p[None, :, k] for k in range(3))   # q - r, as d2 is stated
+        d2 = (dx * dx + dy * dy) + dz * dz
+        inside = d2 < r2 if strict else d2 <= r2
+        rows = np.arange(len(dx))
+        inside[rows, a + rows] = False
+        i, j = np.nonzero(inside)
+        ii.append(i + a), jj.append(j), dd.append(d2[i, j])
+    cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dtype=dt)   # noqa: E731
+    return cat(ii, np.int64), cat(jj, np.int64), cat(dd, np.float64)
+
+
+def cluster(cloud, reach, min_pts=1, min_size=0, max_size=0xFFFFFFFF, flags=0, variant=None):
+    """DBSCAN of one cloud as lk_clouds_cluster_dev defines it, by brute force with a sequential union-find: n_i = the records within reach, the point
+    itself among them; core when n_i >= min_pts; clusters = the connected components of the core points under d2 <= reach * reach; a point that is not
+    core joins the cluster of the core point that minimises (d2, index) or is noise; clusters numbered by their smallest core index; kept = in a
+    cluster with min_size <= size <= max_size, under LK_CLUSTER_KEEP_LARGEST the largest of those only (the smallest id among equals).  Returns a
+    dict: label uint32 [m] (LK_CLUSTER_NOISE for noise), kind uint8 [m], n uint32 [m], cl_size / cl_first uint32 [n_clusters], keep bool [m],
+    src_idx, and the record fields n_points, n_core, n_border, n_noise, n_kept, n_clusters, n_kept_clusters, largest, largest_size, status.
+    variant (test aid, one thing wrong each): CLUSTER_VARIANTS."""
+    m = len(cloud)
+    st = mme_status(cloud, reach)
+    out = dict(label=np.full(m, LK_CLUSTER_NOISE, dtype=np.uint32), kind=np.zeros(m, dtype=np.uint8), n=np.zeros(m, dtype=np.uint32),
+               cl_size=np.zeros(0, dtype=np.uint32), cl_first=np.zeros(0, dtype=np.uint32), keep=np.zeros(m, dtype=bool), src_idx=np.zeros(0, dtype=np.uint32),
+               n_points=m, n_core=0, n_border=0, n_noise=0, n_kept=0, n_clusters=0, n_kept_clusters=0, largest=0, largest_size=0, status=st)
+    if st or not m:
+        return out
+    i, j, d2 = cluster_pairs(cloud, reach, strict=variant == "strict_reach")
+    n = np.bincount(i, minlength=m).astype(np.uint32) + 1
+    core = n - 1 >= min_pts if variant == "no_self" else n >= min_pts
+    parent = list(range(m))
+
+    def find(v):
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+
+    linked = (core[i] | core[j]) if variant == "border_links" else (core[i] & core[j])
+    for a, b in zip(i[linked & (j < i)].tolist(), j[linked & (j < i)].tolist()):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+    root = np.full(m, -1, dtype=np.int64)
+    for v in np.flatnonzero(core).tolist():
+        root[v] = find(v)
+    if variant == "border_links":   # (a root may then be a border point: name the component by its smallest core member, as the rule says)
+        for v in np.flatnonzero(core).tolist():
+            root[v] = find(v)
+        for r in np.unique(root[core]).tolist():
+            root[core & (root == r)] = np.flatnonzero(core & (root == r))[0]
+    kind = np.where(core, CLUSTER_CORE, CLUSTER_NOISE).astype(np.uint8)
+    cand = ~core[i] & core[j]
+    bi, bj, bd = i[cand], j[cand], d2[cand]
+    order = np.lexsort((bj, bi)) if variant == "border_smallest_index" else np.lexsort((bj, bd, bi))
+    bi, bj = bi[order], bj[order]
+    firsts = np.r_[True, bi[1:] != bi[:-1]] if len(bi) else np.zeros(0, dtype=bool)
+    root[bi[firsts]] = root[bj[firsts]]
+    kind[bi[firsts]] = CLUSTER_BORDER
+    member = root >= 0
+    roots = np.unique(root[member])                                     # ascending smallest core index: the numbering
+    if variant == "ids_by_member" and len(roots):
+        roots = roots[np.argsort([np.flatnonzero(root == r)[0] for r in roots], kind="stable")]
+    ids = np.full(m, LK_CLUSTER_NOISE, dtype=np.int64)
+    lookup = {int(r): k for k, r in enumerate(roots.tolist())}
+    ids[member] = [lookup[int(r)] for r in root[member]]
+    size = np.bincount(ids[member], minlength=len(roots)).astype(np.uint32)
+    ok = (size >= min_size) & (size <= max_size)
+    kept_ids = np.flatnonzero(ok)
+    if flags & LK_CLUSTER_KEEP_LARGEST and len(kept_ids):
+        kept_ids = kept_ids[[int(np.argmax(size[kept_ids]))]]           # (argmax: the first among equals)
+    keep = member & np.isin(ids, kept_ids)
+    out.update(label=ids.astype(np.uint32), kind=kind, n=n, cl_size=size, cl_first=roots.astype(np.uint32), keep=keep, src_idx=np.flatnonzero(keep).astype(np.uint32),
+               n_core=int(core.sum()), n_border=int((kind == CLUSTER_BORDER).sum()), n_noise=int((kind == CLUSTER_NOISE).sum()), n_kept=int(keep.sum()),
+               n_clusters=len(roots), n_kept_clusters=len(kept_ids), largest=int(np.argmax(size)) if len(size) else 0, largest_size=int(size.max()) if len(size) else 0)
+    return out
+
+
+def cluster_clouds(clouds, reach, min_pts=1, min_size=0, max_size=0xFFFFFFFF, flags=0, variant=None):
+    """cluster() of every cloud of one call -> a list of its dicts.  variant "across_clouds" (test aid): the clouds of the call taken as one cloud and
+    the labels cut apart afterwards, so that links cross the clouds' boundaries."""
+    if variant != "across_clouds":
+        return [cluster(c, reach, min_pts, min_size, max_size, flags, variant) for c in clouds]
+    whole = cluster(np.concatenate([np.asarray(c, dtype=np.float32).reshape(-1, 3) for c in clouds]), reach, min_pts, min_size, max_size, flags)
+    out, at = [], 0
+    for c in clouds:
+        part = {k: (v[at:at + len(c)] if k in ("label", "kind", "n", "keep") else v) for k, v in whole.items()}
+        part["n_points"] = len(c)
+        out.append(part)
+        at += len(c)
+    return out

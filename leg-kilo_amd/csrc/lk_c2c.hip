@@ -7,7 +7,9 @@
 // lk_clouds_align_plane are the same loop with the point-to-plane solve between the searches (lk_align_plane_kernels.h, arithmetic in
 // lk_align_plane.h) against per-point normals of the reference, which lk_clouds_normals_dev / lk_clouds_normals make from MME's neighbourhood walk
 // (lk_normals_kernels.h, arithmetic in lk_normals.h); lk_clouds_sor_dev / lk_clouds_sor remove a cloud's outliers by the mean distance to the k nearest
-// neighbours (lk_sor_kernels.h, arithmetic in lk_sor.h) and write the kept records as clouds every entry above takes.
+// neighbours (lk_sor_kernels.h, arithmetic in lk_sor.h) and write the kept records as clouds every entry above takes; lk_clouds_cluster_dev /
+// lk_clouds_cluster label a cloud's points by DBSCAN cluster - connected components for min_pts 1 - and write the points of the clusters whose size
+// is in bounds the same way (lk_cluster_kernels.h, arithmetic and the union-find in lk_cluster.h).
 // What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
 // use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
@@ -19,6 +21,7 @@
 #include "lk_mme_kernels.h"
 #include "lk_normals_kernels.h"
 #include "lk_sor_kernels.h"
+#include "lk_cluster_kernels.h"
 
 static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
 static_assert(sizeof(lk_mme) == 64, "lk_mme must be 64 B");
@@ -26,6 +29,7 @@ static_assert(sizeof(lk_align) == 136, "lk_align must be 136 B");
 static_assert(sizeof(lk_align_plane) == 32, "lk_align_plane must be 32 B");
 static_assert(sizeof(lk_normals) == 24, "lk_normals must be 24 B");
 static_assert(sizeof(lk_sor) == 64, "lk_sor must be 64 B");
+static_assert(sizeof(lk_cluster) == 64, "lk_cluster must be 64 B");
 static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
 
 namespace {
@@ -812,6 +816,160 @@ int lk_clouds_sor(lk_handle* h, const float* clouds, size_t n_clouds, const uint
     a.cnt = static_cast<uint32_t*>(st.out[3].dev), a.dbar = static_cast<double*>(st.out[4].dev);
     LKCHK(sor_run(h, a, total, &n_out));
     st.out[0].count = st.out[1].count = n_out;   // nothing behind the kept records is written
+    return st.fetch(h);
+}
+
+}  // extern "C"
+
+namespace {
+struct ClusterArgs {   // the arguments both entries share, as the caller gave them
+    const float* clouds;
+    size_t n_clouds;
+    const uint64_t* off;
+    double reach;
+    uint32_t min_pts, min_size, max_size, flags;
+    lk_cluster* out;
+    uint32_t* label;
+    uint8_t* kind;
+    uint32_t *n, *cl_size, *cl_first;
+    uint64_t* cl_off;
+    float* out_cloud;
+    uint64_t* out_off;
+    uint32_t* src_idx;
+};
+}  // namespace
+
+// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals with the reach as the radius, then the entry's own.  *total: records in all
+static int cluster_check(lk_handle* h, const char* who, const ClusterArgs& a, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    if (!std::isfinite(a.reach) || !(a.reach > 0.0)) return fail(h, LK_ERR_INVALID, w + "reach must be finite and above 0");
+    lk_mme sink;
+    const MmeArgs m = {a.clouds, a.n_clouds, a.off, a.reach, 4u, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
+    LKCHK(mme_check(h, who, m, cloud_align, total));
+    if (a.min_pts == 0) return fail(h, LK_ERR_INVALID, w + "min_pts is 0: at least 1 (a point counts itself)");
+    if (a.min_size > a.max_size) return fail(h, LK_ERR_INVALID, w + "min_size is " + std::to_string(a.min_size) + ", above max_size " + std::to_string(a.max_size));
+    if (a.flags & ~LK_CLUSTER_KEEP_LARGEST) return fail(h, LK_ERR_INVALID, w + "flags holds an unknown bit: 0 or LK_CLUSTER_KEEP_LARGEST");
+    if (a.cl_size && !a.cl_off) return fail(h, LK_ERR_INVALID, w + "cl_size needs cl_off");
+    if (a.cl_first && !a.cl_off) return fail(h, LK_ERR_INVALID, w + "cl_first needs cl_off");
+    if (a.out_cloud && !a.out_off) return fail(h, LK_ERR_INVALID, w + "out_cloud needs out_off");
+    if (a.src_idx && !a.out_off) return fail(h, LK_ERR_INVALID, w + "src_idx needs out_off");
+    if ((uintptr_t)a.out_cloud & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "out_cloud must be " + std::to_string(cloud_align) + "-byte aligned");
+    const C2cSpan in = {"clouds", (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0], 16u * *total};
+    const C2cSpan o[7] = {{"out_cloud", (uintptr_t)a.out_cloud, 16 * *total}, {"src_idx", (uintptr_t)a.src_idx, 4 * *total}, {"label", (uintptr_t)a.label, 4 * *total},
+                          {"kind", (uintptr_t)a.kind, *total}, {"n", (uintptr_t)a.n, 4 * *total}, {"cl_size", (uintptr_t)a.cl_size, 4 * *total},
+                          {"cl_first", (uintptr_t)a.cl_first, 4 * *total}};
+    for (int i = 1; i < 7; ++i)
+        if (i != 3 && (o[i].p & 3)) return fail(h, LK_ERR_INVALID, w + o[i].name + " must be 4-byte aligned");
+    for (int i = 0; i < 7; ++i) LKCHK(c2c_overlap_check(h, w, o[i], &in, 1, "the input clouds", o + i + 1, 6 - i));
+    return LK_OK;
+}
+
+// the call behind cluster_check, on DEVICE clouds and DEVICE outputs (null: not asked for; what a later kernel needs is then the library's own).
+// *n_cl: entries written to cl_size / cl_first, *n_out: records written to out_cloud / src_idx
+static int cluster_run(lk_handle* h, const ClusterArgs& a, size_t N, size_t* n_cl, size_t* n_out) {
+    const size_t NC = a.n_clouds;
+    std::vector<unsigned int> used;   // every non-empty cloud
+    for (size_t c = 0; c < NC; ++c)
+        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+    const bool places = a.out_off != nullptr, moved = a.out_cloud || a.src_idx;
+    C2cIndex x = {};
+    LkClusterCall m = {};
+    LkSorCall s = {};   // the scan's offsets and the scatter are lk_sor_kernels.h's
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
+        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
+        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
+        x.recs = c.take<LkC2cRec>(N);
+        m.core = c.take<unsigned char>(N), m.parent = c.take<unsigned int>(N), m.root = c.take<unsigned int>(N);
+        m.n = c2c_or_own(c, a.n, N), m.kind = c2c_or_own(c, a.kind, N);
+        m.rflag = c.take<unsigned int>(N + 1), m.rscan = c.take<unsigned int>(N + 1), m.size = c.take<unsigned int>(N), m.first = c.take<unsigned int>(N);
+        m.cl_off = c.take<unsigned int>(NC + 1), m.kept_id = c.take<unsigned int>(NC);
+        m.flag = c.take<unsigned int>(places ? N + 1 : 0), s.scan = c.take<unsigned int>(places ? N + 1 : 0), s.out_off = c.take<unsigned int>(places ? NC + 1 : 0);
+        m.out = c.take<lk_cluster>(NC);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
+    carve(h->c2c.p);
+    size_t scan_tmp = 0;   // (before anything is launched: growing the temporary storage waits for the stream)
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, scan_tmp, m.rflag, m.rscan, N + 1, h->stream));
+    LKCHK(reserve(h, h->prim_tmp, scan_tmp));
+    LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.reach, x));
+    m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
+    m.label = a.label, m.cl_size = a.cl_size, m.cl_first = a.cl_first;
+    m.reach2 = lk_c2c_reach2(a.reach);
+    m.n_clouds = (unsigned int)NC, m.total = (unsigned int)N, m.min_pts = a.min_pts, m.min_size = a.min_size, m.max_size = a.max_size;
+    m.keep_largest = a.flags & LK_CLUSTER_KEEP_LARGEST;
+    s.off = m.off, s.n_clouds = m.n_clouds, s.total = m.total, s.flag = m.flag;
+    s.in = reinterpret_cast<const uint4*>(a.clouds) + a.off[0], s.out_pts = reinterpret_cast<uint4*>(a.out_cloud), s.src_idx = a.src_idx;
+    if (N) {
+        LAUNCH(h, "cluster_count", hipLaunchKernelGGL(lk_cluster_count_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+        LAUNCH(h, "cluster_link", hipLaunchKernelGGL(lk_cluster_link_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+        LAUNCH(h, "cluster_assign", hipLaunchKernelGGL(lk_cluster_assign_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+        HIPCHK(h, hipMemsetAsync(m.size, 0, 4 * N, h->stream));
+    }
+    LAUNCH(h, "cluster_rootflag", hipLaunchKernelGGL(lk_cluster_rootflag_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
+    size_t tb = h->prim_tmp.cap;
+    hipError_t scanned = hipSuccess;
+    LAUNCH(h, "cluster_ids", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.rflag, m.rscan, N + 1, h->stream));
+    HIPCHK(h, scanned);
+    if (N) LAUNCH(h, "cluster_label", hipLaunchKernelGGL(lk_cluster_label_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+    LAUNCH(h, "cluster_record", hipLaunchKernelGGL(lk_cluster_record_kernel, dim3((unsigned int)NC), dim3(256), 0, h->stream, m));
+    LAUNCH(h, "cluster_tables", hipLaunchKernelGGL(lk_cluster_tables_kernel, c2c_blocks(std::max(N, NC + 1)), dim3(256), 0, h->stream, m));
+    std::vector<lk_cluster> rec(NC);
+    std::vector<unsigned int> coff(NC + 1), ooff(places ? NC + 1 : 0);
+    HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_cluster) * NC, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(coff.data(), m.cl_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
+    if (places) {
+        LAUNCH(h, "cluster_flag", hipLaunchKernelGGL(lk_cluster_flag_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
+        tb = h->prim_tmp.cap;
+        LAUNCH(h, "cluster_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, s.scan, N + 1, h->stream));
+        HIPCHK(h, scanned);
+        LAUNCH(h, "cluster_offsets", hipLaunchKernelGGL(lk_sor_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, s));
+        HIPCHK(h, hipMemcpyAsync(ooff.data(), s.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
+        if (moved && N) LAUNCH(h, "cluster_scatter", hipLaunchKernelGGL(lk_sor_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(a.out, rec.data(), sizeof(lk_cluster) * NC);
+    if (a.cl_off)
+        for (size_t c = 0; c <= NC; ++c) a.cl_off[c] = coff[c];
+    if (places)
+        for (size_t c = 0; c <= NC; ++c) a.out_off[c] = ooff[c];
+    if (n_cl) *n_cl = coff[NC];
+    if (n_out) *n_out = places ? ooff[NC] : 0;
+    return LK_OK;
+}
+
+extern "C" {
+
+int lk_clouds_cluster_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double reach, uint32_t min_pts, uint32_t min_size,
+                          uint32_t max_size, uint32_t flags, lk_cluster* out, uint32_t* d_label, uint8_t* d_kind, uint32_t* d_n, uint32_t* d_cl_size,
+                          uint32_t* d_cl_first, uint64_t* cl_off, float* d_out, uint64_t* out_off, uint32_t* d_src_idx) {
+    CHECK_H(h);
+    const ClusterArgs a = {d_clouds, n_clouds, off, reach, min_pts, min_size, max_size, flags, out, d_label, d_kind, d_n, d_cl_size, d_cl_first, cl_off, d_out, out_off, d_src_idx};
+    size_t total = 0;
+    LKCHK(cluster_check(h, "lk_clouds_cluster_dev", a, 16, &total));
+    return cluster_run(h, a, total, nullptr, nullptr);
+}
+
+int lk_clouds_cluster(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double reach, uint32_t min_pts, uint32_t min_size,
+                      uint32_t max_size, uint32_t flags, lk_cluster* out, uint32_t* label, uint8_t* kind, uint32_t* n, uint32_t* cl_size, uint32_t* cl_first,
+                      uint64_t* cl_off, float* out_cloud, uint64_t* out_off, uint32_t* src_idx) {
+    CHECK_H(h);
+    ClusterArgs a = {clouds, n_clouds, off, reach, min_pts, min_size, max_size, flags, out, label, kind, n, cl_size, cl_first, cl_off, out_cloud, out_off, src_idx};
+    size_t total = 0, n_cl = 0, n_out = 0;
+    LKCHK(cluster_check(h, "lk_clouds_cluster", a, 4, &total));
+    C2cStage st;
+    st.in = {{clouds, off, n_clouds}};
+    st.out = {{label, 4, total}, {kind, 1, total}, {n, 4, total}, {cl_size, 4, total}, {cl_first, 4, total}, {out_cloud, 16, total}, {src_idx, 4, total}};
+    LKCHK(st.upload(h));
+    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
+    a.label = static_cast<uint32_t*>(st.out[0].dev), a.kind = static_cast<uint8_t*>(st.out[1].dev), a.n = static_cast<uint32_t*>(st.out[2].dev);
+    a.cl_size = static_cast<uint32_t*>(st.out[3].dev), a.cl_first = static_cast<uint32_t*>(st.out[4].dev);
+    a.out_cloud = static_cast<float*>(st.out[5].dev), a.src_idx = static_cast<uint32_t*>(st.out[6].dev);
+    LKCHK(cluster_run(h, a, total, &n_cl, &n_out));
+    st.out[3].count = st.out[4].count = n_cl, st.out[5].count = st.out[6].count = n_out;   // nothing behind the clusters and the kept records is written
     return st.fetch(h);
 }
 

@@ -550,6 +550,34 @@ class KiloPath {
         if (out_off) *out_off = oo;
         return out;
     }
+    // lk_clouds_cluster_dev: map clouds clustered where they lie (DBSCAN; min_pts = 1: the connected components within `reach`) - cloudsMmeDev's
+    // clouds and table.  A point with min_pts records within `reach`, itself among them, is core; core points within reach of each other share a
+    // cluster; another point joins the cluster of its nearest core point or is noise.  The arrays of ClusterOut (each optional, device memory) take a
+    // label, a kind and n_i per input record, a size and a first core index per cluster - cluster k of cloud c at (*cl_off)[c] + k - and the points
+    // of the clusters with min_size <= size <= max_size (flags LK_CLUSTER_KEEP_LARGEST: of the largest of them) in input order, cloud c at
+    // (*out_off)[c] .. (*out_off)[c + 1]), what cloudsSorDev, cloudsMmeDev, cloudsC2cDev and the align entries take as they are.
+    struct ClusterOut {   // (value-initialised: every pointer null)
+        uint32_t* d_label;
+        uint8_t* d_kind;
+        uint32_t *d_n, *d_cl_size, *d_cl_first;
+        std::vector<uint64_t>* cl_off;
+        float* d_out;
+        std::vector<uint64_t>* out_off;
+        uint32_t* d_src_idx;
+    };
+    std::vector<lk_cluster> cloudsClusterDev(const float* d_clouds, const std::vector<uint64_t>& off, double reach, uint32_t min_pts = 1, uint32_t min_size = 0,
+                                             uint32_t max_size = 0xffffffffu, uint32_t flags = 0, const ClusterOut& o = ClusterOut()) {
+        if (off.size() < 2) throw std::runtime_error("cloudsClusterDev: the offset table is empty");
+        if ((o.d_cl_size || o.d_cl_first) && !o.cl_off) throw std::runtime_error("cloudsClusterDev: d_cl_size and d_cl_first need cl_off");
+        if ((o.d_out || o.d_src_idx) && !o.out_off) throw std::runtime_error("cloudsClusterDev: d_out and d_src_idx need out_off");
+        std::vector<lk_cluster> out(off.size() - 1);
+        std::vector<uint64_t> co(off.size()), oo(off.size());
+        dev_->check(lk_clouds_cluster_dev(dev_->h(), d_clouds, off.size() - 1, off.data(), reach, min_pts, min_size, max_size, flags, out.data(), o.d_label, o.d_kind, o.d_n,
+                                          o.d_cl_size, o.d_cl_first, o.cl_off ? co.data() : nullptr, o.d_out, o.out_off ? oo.data() : nullptr, o.d_src_idx));
+        if (o.cl_off) *o.cl_off = co;
+        if (o.out_off) *o.out_off = oo;
+        return out;
+    }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
     // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with

@@ -970,6 +970,74 @@ int lk_clouds_cluster_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, 
 int lk_clouds_cluster(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double reach, uint32_t min_pts, uint32_t min_size,
                       uint32_t max_size, uint32_t flags, lk_cluster* out, uint32_t* label, uint8_t* kind, uint32_t* n, uint32_t* cl_size,
                       uint32_t* cl_first, uint64_t* cl_off, float* out_cloud, uint64_t* out_off, uint32_t* src_idx);
+/* Dominant planes peeled off many map clouds in one call, by RANSAC: PCL's SACSegmentation with SACMODEL_PLANE (axis null) or
+ * SACMODEL_PERPENDICULAR_PLANE (axis given; "the floor" is axis = (0,0,1)), repeated on what is left.  It is the step PCL's recipe puts IN FRONT of
+ * EuclideanClusterExtraction - without it everything that stands on the floor is one component of lk_clouds_cluster_dev - and it says which planes
+ * a cloud consists of, with how many points and what normal each.  Every entry above decides from a point's neighbourhood; this one fits a global
+ * model, and needs no cell index.  leg-kilo_amd/cloudmetrics.py's planes is the numpy statement.
+ * Layout, offsets, alignment and capacity limits are exactly lk_clouds_mme_dev's; w is never interpreted but is COPIED with its record.
+ * Definition, by brute force; all arithmetic is float64 from the float32 coordinates, one rounding per operation, no fused multiply-add; no decision
+ * holds a square root or a division.  A ROUND r works on the REMAINDER of a cloud: the m records not yet on a plane, in input order, numbered
+ * 0 .. m-1 by their position in the remainder.
+ *   sampler     lk_planes_sample(seed, r, h, m): u_k = splitmix64(seed + (r * LK_PLANES_MAX_HYP + h) * 4 + k), k = 0, 1, 2, where splitmix64(x) is
+ *               z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31 (mod 2^64).
+ *               i0 = mulhi64(u0, m); i1 = mulhi64(u1, m-1), raised by one if >= i0; i2 = mulhi64(u2, m-2), raised by one if >= min(i0, i1) and
+ *               then by one if >= max(i0, i1).  Three distinct positions.  The cloud's index is NOT an input: a cloud's result does not depend on
+ *               what else the call holds.
+ *   hypothesis  h = 0 .. n_hyp-1: a, b, c = the sampled records; u = b - a, v = c - a; mvec = u x v, each component two products and one
+ *               subtraction (uy*vz - uz*vy, uz*vx - ux*vz, ux*vy - uy*vx); q = (mx*mx + my*my) + mz*mz.  SKIPPED (score 0) when q is 0 or not
+ *               finite, and with an axis when g*g < ((cos_max_angle*cos_max_angle) * q) * aa, g = (mx*ax + my*ay) + mz*az, aa = (ax*ax + ay*ay)
+ *               + az*az: the plane's normal is then further than the angle from the axis, either way round.
+ *   score       the number of remainder records p with s*s <= t2q, e = p - a, s = (mx*ex + my*ey) + mz*ez, t2q = (dist*dist) * q.  The three
+ *               sample points count (their s is 0 or a rounding of it; they are counted by the same test).
+ *   winner      the largest score, the smallest h among equal scores.  If that score is < min_inliers the cloud is finished.  Otherwise the
+ *               winner's inliers are plane r: they get label r and leave the remainder, and round r + 1 runs on what is left.  A cloud is also
+ *               finished at r == max_planes or when m < max(3, min_inliers).
+ *   reported, never fed back into a decision: over the plane's inliers the centroid, then the centred 3 x 3 covariance divided by n (sums in an
+ *               order that depends on the cloud alone), its eigen-decomposition (lk_eig3.h): eig[3] ascending, normal = the unit eigenvector of
+ *               eig[0], with normal . axis >= 0 when an axis is given and otherwise its component of largest magnitude positive (the first on
+ *               ties); d = -normal . centroid; rmse = sqrt(max(eig[0], 0)).  Membership is the winning hypothesis's and nothing else.
+ * Labels, counts, hyp and the kept records are whole numbers and bits of the input: the same from run to run and whatever else the call holds.
+ * out: HOST, n_clouds records, every byte written.  planes: HOST, n_clouds * max_planes records, plane r of cloud c at entry c * max_planes + r,
+ * every byte written, unused entries zero.
+ * Outputs, each optional and independent, except that out_off is required with d_out or d_src_idx:
+ *   d_label    (DEVICE, uint32) per point, record off[c] + i at entry off[c] - off[0] + i: the plane's number, or 0xffffffff.
+ *   d_out, out_off, d_src_idx  exactly lk_clouds_sor_dev's.  The kept set is the REMAINDER - ground and wall removal in front of
+ *              lk_clouds_cluster_dev - or with LK_PLANES_KEEP_PLANES the points on planes.
+ * A cloud with a non-finite coordinate gets LK_PLANES_NONFINITE, one with a |coordinate| >= 2^30 LK_PLANES_RANGE (below it no intermediate of the
+ * score overflows): no planes, zero counts but n_points, labels 0xffffffff and an empty output range; the other clouds of the call are unaffected.
+ * Synchronous; no filter slot, map, overlay or bucket table is touched.
+ * LK_ERR_INVALID before anything is launched, the message naming the argument: n_clouds == 0, a null d_clouds, off, out or planes, decreasing
+ * offsets, dist not finite or <= 0, n_hyp 0 or above LK_PLANES_MAX_HYP, max_planes 0 or above LK_PLANES_MAX_PLANES, min_inliers < 3, an axis that
+ * is not finite or is zero, cos_max_angle outside [0, 1] or NaN, an unknown flag, d_out or d_src_idx without out_off, a misaligned pointer (16 bytes
+ * for the clouds and d_out, 4 for the uint32 arrays), an output that overlaps the input or another output.  LK_ERR_CAPACITY as for
+ * lk_clouds_mme_dev.  A refused call writes nothing.
+ * lk_clouds_planes: the same with the clouds and every array in HOST memory (4-byte alignment for the clouds). */
+#define LK_PLANES_MAX_HYP 4096u
+#define LK_PLANES_MAX_PLANES 16u
+#define LK_PLANES_KEEP_PLANES 1u
+#define LK_PLANES_NONFINITE 1u
+#define LK_PLANES_RANGE     2u
+typedef struct lk_plane {          /* 96 bytes */
+    double normal[3], d;           /* normal . p + d = 0 */
+    double centroid[3];
+    double eig[3];                 /* of the covariance / n, ascending */
+    double rmse;
+    uint32_t n_inliers;
+    uint32_t hyp;                  /* the winning hypothesis */
+} lk_plane;
+typedef struct lk_planes {         /* 64 bytes */
+    uint64_t n_points, n_on_planes, n_rest, n_kept;   /* n_points = n_on_planes + n_rest when status == 0 */
+    uint32_t n_planes;
+    uint32_t status;               /* 0, LK_PLANES_NONFINITE, LK_PLANES_RANGE (bits) */
+    uint32_t pad[6];               /* written 0 */
+} lk_planes;
+int lk_clouds_planes_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double dist, uint32_t n_hyp, uint32_t max_planes,
+                         uint32_t min_inliers, const double* axis, double cos_max_angle, uint64_t seed, uint32_t flags, lk_planes* out, lk_plane* planes,
+                         uint32_t* d_label, float* d_out, uint64_t* out_off, uint32_t* d_src_idx);
+int lk_clouds_planes(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double dist, uint32_t n_hyp, uint32_t max_planes,
+                     uint32_t min_inliers, const double* axis, double cos_max_angle, uint64_t seed, uint32_t flags, lk_planes* out, lk_plane* planes,
+                     uint32_t* label, float* out_cloud, uint64_t* out_off, uint32_t* src_idx);
 /* Per-scan overlay capacities: root voxels a scan's inserts may touch or create, octree nodes and live point blocks of those voxels.
  * 0 (default) = sized by the library: a first guess from the scan size (n_pts / 18 roots), afterwards the previous replay's high-water
  * marks + 25 %, and a scan that outgrows such pools makes them grow and the batch run again (no error).  Capacities set HERE are the

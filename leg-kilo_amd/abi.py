@@ -427,6 +427,56 @@ def cluster_dtype():
     return dt
 
 
+class lk_plane(C.Structure):
+    _fields_ = [
+        ("normal", C.c_double * 3),
+        ("d", C.c_double),
+        ("centroid", C.c_double * 3),
+        ("eig", C.c_double * 3),
+        ("rmse", C.c_double),
+        ("n_inliers", C.c_uint32),
+        ("hyp", C.c_uint32),
+    ]
+
+
+class lk_planes(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_uint64),
+        ("n_on_planes", C.c_uint64),
+        ("n_rest", C.c_uint64),
+        ("n_kept", C.c_uint64),
+        ("n_planes", C.c_uint32),
+        ("status", C.c_uint32),
+        ("pad", C.c_uint32 * 6),
+    ]
+
+
+LK_PLANES_MAX_HYP = 4096       # lk_clouds_planes_dev: the most hypotheses of a round
+LK_PLANES_MAX_PLANES = 16      # and the most planes of a cloud
+LK_PLANES_KEEP_PLANES = 1      # lk_clouds_planes_dev flags: the kept set is the points on planes, not the remainder
+LK_PLANES_NONFINITE = 1        # lk_planes.status: a coordinate of the cloud was not finite
+LK_PLANES_RANGE = 2            # lk_planes.status: a |coordinate| >= 2^30 in the cloud
+LK_PLANES_NONE = 0xFFFFFFFF    # d_label of a point on no plane
+
+
+def planes_dtype():
+    """numpy view of lk_planes (64 B): the per-cloud records of lk_clouds_planes_dev / lk_clouds_planes."""
+    import numpy as np
+
+    dt = np.dtype(lk_planes)
+    assert dt.itemsize == C.sizeof(lk_planes) == 64
+    return dt
+
+
+def plane_dtype():
+    """numpy view of lk_plane (96 B): the per-plane records of lk_clouds_planes_dev / lk_clouds_planes, plane r of cloud c at c * max_planes + r."""
+    import numpy as np
+
+    dt = np.dtype(lk_plane)
+    assert dt.itemsize == C.sizeof(lk_plane) == 96
+    return dt
+
+
 class lk_run_options(C.Structure):
     _fields_ = [("sliding_thresh", C.c_double), ("half_map_size", C.c_int32), ("pad_", C.c_int32)]
 

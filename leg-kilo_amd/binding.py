@@ -899,6 +899,46 @@ class LegKiloHip:
         return dict(res=res, label=label[:total], kind=kind[:total], n=n_arr[:total], cl_size=cl_size[:k], cl_first=cl_first[:k], cl_off=cl_off, out=out[:m],
                     out_off=out_off, src_idx=src[:m])
 
+    def _planes_call(self, fn, clouds, off, dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, label, out_cloud, want_off, src_idx):
+        """What the two plane-extraction exports share - the offset tables and the records: fn(handle, clouds, table, the RANSAC's arguments, records,
+        outputs).  Returns (per-cloud records, per-plane records [n_clouds, max_planes], out_off or None)."""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        res = np.zeros(max(n, 1), dtype=abi.planes_dtype())
+        pl = np.zeros((max(n, 1), max(int(max_planes), 1)), dtype=abi.plane_dtype())
+        ax = None if axis is None else np.ascontiguousarray(axis, dtype=np.float64).reshape(3)
+        out_off = np.zeros(n + 1, dtype=np.uint64) if want_off else None
+        self._chk(fn(self.h, clouds, n, _p(o), float(dist), int(n_hyp), int(max_planes), int(min_inliers), _p(ax), float(cos_max_angle), int(seed), int(flags),
+                     _p(res), _p(pl), label, out_cloud, _p(out_off), src_idx))
+        return res[:n], pl[:n], out_off
+
+    def clouds_planes_dev(self, d_clouds, off, dist, n_hyp=256, max_planes=4, min_inliers=100, axis=None, cos_max_angle=0.0, seed=0, flags=0, d_label=0, d_out=0,
+                          d_src_idx=0, want_off=None):
+        """Dominant planes peeled off many clouds in device memory (lk_clouds_planes_dev, RANSAC): clouds_mme_dev's clouds and table.  Per round n_hyp
+        planes through three sampled records of what is left; the one with the most records within `dist` wins (the smallest number among equals), its
+        records become plane r, up to max_planes rounds while a winner holds min_inliers.  axis (3 floats) with cos_max_angle keeps the planes whose
+        normal lies within that angle of the axis.  d_label uint32 per input record (the plane's number, 0xffffffff: none); d_out / d_src_idx: the
+        remainder (flags = abi.LK_PLANES_KEEP_PLANES: the points on planes) in input order, cloud c at out_off[c] : out_off[c + 1] (0: none, each on
+        its own).  Returns (abi.planes_dtype() records, abi.plane_dtype() records [n_clouds, max_planes], out_off uint64 or None);
+        cloudmetrics.planes is the numpy statement."""
+        wo = bool(d_out or d_src_idx) if want_off is None else want_off
+        return self._planes_call(self.L.lk_clouds_planes_dev, d_clouds, off, dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, d_label or None,
+                                 d_out or None, wo, d_src_idx or None)
+
+    def clouds_planes(self, clouds, off, dist, n_hyp=256, max_planes=4, min_inliers=100, axis=None, cos_max_angle=0.0, seed=0, flags=0):
+        """The same with the clouds in host memory (lk_clouds_planes): clouds float32 [n, 4] (x y z w records).  Returns a dict: res (per-cloud
+        records), planes (per-plane records [n_clouds, max_planes]), label uint32 (entry off[c] - off[0] + i for record off[c] + i), out float32
+        [n_kept, 4], out_off uint64, src_idx uint32 [n_kept]."""
+        c = np.ascontiguousarray(clouds, dtype=np.float32).reshape(-1, 4)
+        o = np.asarray(off, dtype=np.uint64)
+        total = int(o[-1] - o[0]) if len(o) else 0
+        label, src = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.uint32)
+        out = np.zeros((max(total, 1), 4), dtype=np.float32)
+        res, pl, out_off = self._planes_call(self.L.lk_clouds_planes, _p(c), off, dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, _p(label),
+                                             _p(out), True, _p(src))
+        m = int(out_off[-1])
+        return dict(res=res, planes=pl, label=label[:total], out=out[:m], out_off=out_off, src_idx=src[:m])
+
     def downsample_clouds_dev(self, d_world, file_off, leaf, d_out):
         """Downsampled map clouds of many files in one call (lk_downsample_clouds_dev): file f = the 16-byte x y z intensity records
         file_off[f] : file_off[f + 1] at the device pointer d_world (a run replay's d_world_out; pcd_file_offsets gives the table), pcl::VoxelGrid at

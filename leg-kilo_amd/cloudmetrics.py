@@ -1,5 +1,5 @@
 """Map-cloud metrics on the host: the float64 numpy statements of the definitions of lk_clouds_c2c_dev, lk_clouds_align_dev,
-lk_clouds_align_plane_dev, lk_clouds_normals_dev and lk_clouds_mme_dev (include/legkilo_hip.h) and the F-score built on the first one's records.  Brute force in blocks - the reference of the tests and of tools/map_c2c.py / map_mme.py, not a fast
+lk_clouds_align_plane_dev, lk_clouds_normals_dev, lk_clouds_mme_dev, lk_clouds_sor_dev, lk_clouds_cluster_dev and lk_clouds_planes_dev (include/legkilo_hip.h) and the F-score built on the first one's records.  Brute force in blocks - the reference of the tests and of tools/map_c2c.py / map_mme.py, not a fast
 path; touches no device."""
 import numpy as np
 
@@ -620,3 +620,154 @@ def cluster_clouds(clouds, reach, min_pts=1, min_size=0, max_size=0xFFFFFFFF, fl
         out.append(part)
         at += len(c)
     return out
+
+
+LK_PLANES_MAX_HYP = 4096
+LK_PLANES_MAX_PLANES = 16
+LK_PLANES_KEEP_PLANES = 1
+LK_PLANES_NONFINITE = LK_MME_NONFINITE
+LK_PLANES_RANGE = LK_MME_RANGE
+LK_PLANES_NONE = 0xFFFFFFFF
+PLANES_GROUP, PLANES_TILE, PLANES_CHUNK = 64, 256, 2048   # lk_planes.h's LK_PLANES_GROUP / _TILE / _CHUNK: where the score kernel's paths change
+PLANES_VARIANTS = ("strict", "normalised", "ties_last", "input_indices", "samples_not_counted", "axis_without_aa", "cloud_in_sampler")
+_U64 = (1 << 64) - 1
+
+
+def planes_mix(x):
+    """splitmix64 of a uint64 array: the state advanced by the golden gamma, then the finaliser."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(x, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def planes_mulhi(u, m):
+    """The high 64 bits of u * m for a uint64 array u and 0 <= m < 2^32, in uint64 arithmetic that does not wrap."""
+    m, s = np.uint64(m), np.uint64(32)
+    return ((u >> s) * m + (((u & np.uint64(0xFFFFFFFF)) * m) >> s)) >> s
+
+
+def planes_sample(seed, r, h, m):
+    """lk_planes_sample for an array of hypotheses h: three distinct remainder positions below m each -> int64 [len(h), 3]."""
+    with np.errstate(over="ignore"):
+        ctr = (np.uint64(r) * np.uint64(LK_PLANES_MAX_HYP) + np.asarray(h, dtype=np.uint64)) * np.uint64(4) + np.uint64(int(seed) & _U64)
+        i0 = planes_mulhi(planes_mix(ctr), m).astype(np.int64)
+        i1 = planes_mulhi(planes_mix(ctr + np.uint64(1)), m - 1).astype(np.int64)
+        i2 = planes_mulhi(planes_mix(ctr + np.uint64(2)), m - 2).astype(np.int64)
+    i1 += i1 >= i0
+    lo, hi = np.minimum(i0, i1), np.maximum(i0, i1)
+    i2 += i2 >= lo
+    i2 += i2 >= hi
+    return np.stack([i0, i1, i2], axis=1)
+
+
+def planes_status(cloud):
+    p = np.asarray(cloud, dtype=np.float32).reshape(len(cloud), -1)[:, :3].astype(np.float64)
+    fin = np.isfinite(p)
+    return (0 if fin.all() else LK_PLANES_NONFINITE) | (LK_PLANES_RANGE if (np.abs(p[fin]) >= 2.0 ** 30).any() else 0)
+
+
+def planes_hypotheses(p, idx, dist, axis=None, cos_max_angle=0.0, variant=None):
+    """The hypotheses through the sampled records p[idx[:, 0 .. 2]] -> (a [H, 3], mvec [H, 3], t2q [H]); t2q is -1 where the hypothesis is skipped."""
+    a, b, c = p[idx[:, 0]], p[idx[:, 1]], p[idx[:, 2]]
+    u, v = b - a, c - a
+    mv = np.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]], axis=1)
+    q = (mv[:, 0] * mv[:, 0] + mv[:, 1] * mv[:, 1]) + mv[:, 2] * mv[:, 2]
+    ok = (q > 0.0) & np.isfinite(q)
+    if axis is not None:
+        ax = np.asarray(axis, dtype=np.float64)
+        g = (mv[:, 0] * ax[0] + mv[:, 1] * ax[1]) + mv[:, 2] * ax[2]
+        aa = 1.0 if variant == "axis_without_aa" else (ax[0] * ax[0] + ax[1] * ax[1]) + ax[2] * ax[2]
+        ok &= ~(g * g < ((cos_max_angle * cos_max_angle) * q) * aa)
+    if variant == "normalised":   # (what the definition avoids: a root and three divisions in front of every decision)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mv = np.where(ok[:, None], mv / np.sqrt(q)[:, None], mv)
+        q = np.where(ok, 1.0, q)
+    return a, mv, np.where(ok, (dist * dist) * q, -1.0)
+
+
+def planes_inside(p, a, mv, t2q, variant=None, block=64, margin=None):
+    """s * s <= t2q of every hypothesis against every record of p -> bool [H, m].  margin: a list whose entry 0 is lowered to the smallest
+    |s * s - t2q| / t2q met among the hypotheses that are not skipped."""
+    out = np.zeros((len(a), len(p)), dtype=bool)
+    for b in range(0, len(a), block):
+        e = p[None, :, :] - a[b:b + block, None, :]
+        m = mv[b:b + block, None, :]
+        s = (m[..., 0] * e[..., 0] + m[..., 1] * e[..., 1]) + m[..., 2] * e[..., 2]
+        t = t2q[b:b + block, None]
+        out[b:b + block] = (s * s < t) if variant == "strict" else (s * s <= t)
+        if margin is not None and (t > 0.0).any() and len(p):
+            margin[0] = min(margin[0], float((np.abs(s * s - t) / np.where(t > 0.0, t, 1.0))[(t > 0.0)[:, 0]].min()))
+    return out
+
+
+def planes_fit(pts, axis=None):
+    """The reported coefficients of one plane from its inliers [n, 3] float64, sums in lk_planes_refit_kernel's order for a cloud that holds nothing
+    else: centroid, covariance / n, eigh -> dict(normal, d, centroid, eig, rmse)."""
+    n = len(pts)
+    cen = np.array([sor_tree_sum(pts[:, k]) for k in range(3)]) / n
+    dv = pts - cen
+    c = {(i, j): sor_tree_sum(dv[:, i] * dv[:, j]) / n for i in range(3) for j in range(i, 3)}
+    full = np.array([[c[min(i, j), max(i, j)] for j in range(3)] for i in range(3)])
+    ev, vec = np.linalg.eigh(full)
+    nrm = vec[:, 0]
+    if axis is not None:
+        flip = not (float(np.dot(nrm, np.asarray(axis, dtype=np.float64))) >= 0.0)
+    else:
+        flip = nrm[int(np.argmax(np.abs(nrm)))] < 0.0   # (argmax: the first among equals)
+    nrm = -nrm if flip else nrm
+    return dict(normal=nrm, d=-float(np.dot(nrm, cen)), centroid=cen, eig=ev, rmse=float(np.sqrt(max(ev[0], 0.0))))
+
+
+def planes(cloud, dist, n_hyp, max_planes, min_inliers, axis=None, cos_max_angle=0.0, seed=0, flags=0, variant=None, cloud_index=0, trace=None):
+    """The dominant planes of one cloud as lk_clouds_planes_dev defines them, by brute force: per round the sampler's three positions in the remainder,
+    u x v, the score s * s <= dist^2 |u x v|^2 over the remainder, the largest score and the smallest h among equals; the winner's inliers become
+    plane r and leave.  Returns a dict: label uint32 [m] (LK_PLANES_NONE: on no plane), keep bool [m], src_idx, planes (a list of dicts: normal, d,
+    centroid, eig, rmse, n_inliers, hyp), and the record fields n_points, n_on_planes, n_rest, n_kept, n_planes, status.
+    variant (test aid, one thing wrong each): PLANES_VARIANTS; cloud_index is read by "cloud_in_sampler" alone.  trace: a list that takes, per round,
+    (the remainder's input indices, the sampled positions [H, 3], the scores [H], the winner, the smallest |s * s - t2q| / t2q of the round)."""
+    m = len(cloud)
+    pts = np.asarray(cloud, dtype=np.float32).reshape(m, -1)[:, :3].astype(np.float64) if m else np.zeros((0, 3))
+    st = planes_status(cloud) if m else 0
+    out = dict(label=np.full(m, LK_PLANES_NONE, dtype=np.uint32), keep=np.zeros(m, dtype=bool), src_idx=np.zeros(0, dtype=np.uint32), planes=[],
+               n_points=m, n_on_planes=0, n_rest=0, n_kept=0, n_planes=0, status=st)
+    if st:
+        return out
+    alive = np.ones(m, dtype=bool)
+    hs = np.arange(n_hyp)
+    sd = (int(seed) + (cloud_index << 40 if variant == "cloud_in_sampler" else 0)) & _U64
+    for r in range(max_planes):
+        rem = np.flatnonzero(alive)
+        if len(rem) < max(3, min_inliers):
+            break
+        idx = planes_sample(sd, r, hs, len(rem))
+        p = pts[rem]
+        p_s = pts if variant == "input_indices" else p   # (the positions taken as indices of the INPUT: right in round 0 only)
+        a, mv, t2q = planes_hypotheses(p_s, idx, dist, axis, cos_max_angle, variant)
+        gap = [np.inf]
+        inside = planes_inside(p, a, mv, t2q, variant, margin=gap if trace is not None else None)
+        if variant == "samples_not_counted":
+            for k in range(3):
+                inside[hs, idx[:, k]] = False
+        score = inside.sum(axis=1)
+        w = int(len(score) - 1 - np.argmax(score[::-1])) if variant == "ties_last" else int(np.argmax(score))
+        if trace is not None:
+            trace.append((rem, idx, score.copy(), w, gap[0]))
+        if score[w] < min_inliers:
+            break
+        members = rem[inside[w]]
+        out["label"][members] = r
+        alive[members] = False
+        fit = planes_fit(pts[members], axis)
+        fit.update(n_inliers=int(score[w]), hyp=w)
+        out["planes"].append(fit)
+    on = int((~alive).sum())
+    keep = ~alive if flags & LK_PLANES_KEEP_PLANES else alive
+    out.update(keep=keep, src_idx=np.flatnonzero(keep).astype(np.uint32), n_on_planes=on, n_rest=m - on, n_kept=int(keep.sum()), n_planes=len(out["planes"]))
+    return out
+
+
+def planes_clouds(clouds, dist, n_hyp, max_planes, min_inliers, axis=None, cos_max_angle=0.0, seed=0, flags=0, variant=None):
+    """planes() of every cloud of one call -> a list of its dicts (variant "cloud_in_sampler": each with its index in the call)."""
+    return [planes(c, dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, variant, cloud_index=k) for k, c in enumerate(clouds)]

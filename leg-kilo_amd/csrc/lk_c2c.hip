@@ -9,7 +9,9 @@
 // (lk_normals_kernels.h, arithmetic in lk_normals.h); lk_clouds_sor_dev / lk_clouds_sor remove a cloud's outliers by the mean distance to the k nearest
 // neighbours (lk_sor_kernels.h, arithmetic in lk_sor.h) and write the kept records as clouds every entry above takes; lk_clouds_cluster_dev /
 // lk_clouds_cluster label a cloud's points by DBSCAN cluster - connected components for min_pts 1 - and write the points of the clusters whose size
-// is in bounds the same way (lk_cluster_kernels.h, arithmetic and the union-find in lk_cluster.h).
+// is in bounds the same way (lk_cluster_kernels.h, arithmetic and the union-find in lk_cluster.h); lk_clouds_planes_dev / lk_clouds_planes peel the
+// dominant planes off a cloud by RANSAC - no cell index, hypotheses x records - and write the remainder or the planes' points the same way
+// (lk_planes_kernels.h, arithmetic in lk_planes.h).
 // What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
 // use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
@@ -22,6 +24,7 @@
 #include "lk_normals_kernels.h"
 #include "lk_sor_kernels.h"
 #include "lk_cluster_kernels.h"
+#include "lk_planes_kernels.h"
 
 static_assert(sizeof(lk_c2c) == 80, "lk_c2c must be 80 B");
 static_assert(sizeof(lk_mme) == 64, "lk_mme must be 64 B");
@@ -30,6 +33,8 @@ static_assert(sizeof(lk_align_plane) == 32, "lk_align_plane must be 32 B");
 static_assert(sizeof(lk_normals) == 24, "lk_normals must be 24 B");
 static_assert(sizeof(lk_sor) == 64, "lk_sor must be 64 B");
 static_assert(sizeof(lk_cluster) == 64, "lk_cluster must be 64 B");
+static_assert(sizeof(lk_planes) == 64 && sizeof(lk_plane) == 96, "lk_planes must be 64 B, lk_plane 96 B");
+static_assert(LK_PLANES_HYP_LIMIT == LK_PLANES_MAX_HYP && LK_PLANES_CHUNK % LK_PLANES_TILE == 0, "lk_planes.h lays the sampler's counter out by LK_PLANES_MAX_HYP");
 static_assert(sizeof(LkC2cRec) == 16 && sizeof(LkC2cGrid) == 40, "a reference record in cell order is 16 B, a grid 40 B");
 
 namespace {
@@ -970,6 +975,177 @@ int lk_clouds_cluster(lk_handle* h, const float* clouds, size_t n_clouds, const 
     a.out_cloud = static_cast<float*>(st.out[5].dev), a.src_idx = static_cast<uint32_t*>(st.out[6].dev);
     LKCHK(cluster_run(h, a, total, &n_cl, &n_out));
     st.out[3].count = st.out[4].count = n_cl, st.out[5].count = st.out[6].count = n_out;   // nothing behind the clusters and the kept records is written
+    return st.fetch(h);
+}
+
+}  // extern "C"
+
+namespace {
+struct PlanesArgs {   // the arguments both entries share, as the caller gave them
+    const float* clouds;
+    size_t n_clouds;
+    const uint64_t* off;
+    double dist;
+    uint32_t n_hyp, max_planes, min_inliers;
+    const double* axis;
+    double cos_max_angle;
+    uint64_t seed;
+    uint32_t flags;
+    lk_planes* out;
+    lk_plane* planes;
+    uint32_t* label;
+    float* out_cloud;
+    uint64_t* out_off;
+    uint32_t* src_idx;
+};
+}  // namespace
+
+// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals of the clouds and the table, then the entry's own.  *total: records in all
+static int planes_check(lk_handle* h, const char* who, const PlanesArgs& a, unsigned int cloud_align, size_t* total) {
+    const std::string w = std::string(who) + ": ";
+    lk_mme sink;
+    const MmeArgs m = {a.clouds, a.n_clouds, a.off, 1.0, 4u, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
+    LKCHK(mme_check(h, who, m, cloud_align, total));
+    if (!a.planes) return fail(h, LK_ERR_INVALID, w + "null argument (planes)");
+    if (!std::isfinite(a.dist) || !(a.dist > 0.0)) return fail(h, LK_ERR_INVALID, w + "dist must be finite and above 0");
+    if (a.n_hyp == 0 || a.n_hyp > LK_PLANES_MAX_HYP) return fail(h, LK_ERR_INVALID, w + "n_hyp is " + std::to_string(a.n_hyp) + ": 1 .. LK_PLANES_MAX_HYP");
+    if (a.max_planes == 0 || a.max_planes > LK_PLANES_MAX_PLANES)
+        return fail(h, LK_ERR_INVALID, w + "max_planes is " + std::to_string(a.max_planes) + ": 1 .. LK_PLANES_MAX_PLANES");
+    if (a.min_inliers < 3) return fail(h, LK_ERR_INVALID, w + "min_inliers is " + std::to_string(a.min_inliers) + ": at least 3 (the sample points count)");
+    if (a.axis) {
+        const bool finite = std::isfinite(a.axis[0]) && std::isfinite(a.axis[1]) && std::isfinite(a.axis[2]);
+        const double aa = finite ? lk_planes_axis(a.axis, 0.0).aa : 0.0;
+        if (!finite || !(aa > 0.0) || !std::isfinite(aa)) return fail(h, LK_ERR_INVALID, w + "axis must be finite and not zero");
+    }
+    if (!(a.cos_max_angle >= 0.0 && a.cos_max_angle <= 1.0)) return fail(h, LK_ERR_INVALID, w + "cos_max_angle must lie in 0 .. 1");
+    if (a.flags & ~LK_PLANES_KEEP_PLANES) return fail(h, LK_ERR_INVALID, w + "flags holds an unknown bit: 0 or LK_PLANES_KEEP_PLANES");
+    if (a.out_cloud && !a.out_off) return fail(h, LK_ERR_INVALID, w + "out_cloud needs out_off");
+    if (a.src_idx && !a.out_off) return fail(h, LK_ERR_INVALID, w + "src_idx needs out_off");
+    if ((uintptr_t)a.out_cloud & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "out_cloud must be " + std::to_string(cloud_align) + "-byte aligned");
+    const C2cSpan in = {"clouds", (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0], 16u * *total};
+    const C2cSpan o[3] = {{"out_cloud", (uintptr_t)a.out_cloud, 16 * *total}, {"src_idx", (uintptr_t)a.src_idx, 4 * *total}, {"label", (uintptr_t)a.label, 4 * *total}};
+    for (int i = 1; i < 3; ++i)
+        if (o[i].p & 3) return fail(h, LK_ERR_INVALID, w + o[i].name + " must be 4-byte aligned");
+    for (int i = 0; i < 3; ++i) LKCHK(c2c_overlap_check(h, w, o[i], &in, 1, "the input clouds", o + i + 1, 2 - i));
+    return LK_OK;
+}
+
+// the call behind planes_check, on DEVICE clouds and DEVICE outputs (null: not asked for).  *n_out: records written to out_cloud / src_idx
+static int planes_run(lk_handle* h, const PlanesArgs& a, size_t N, size_t* n_out) {
+    const size_t NC = a.n_clouds, NP = NC * a.max_planes;
+    std::vector<unsigned int> used, roff(NC + 1), cfirst(NC + 1, 0u);   // every non-empty cloud; the table from the first record; the score blocks in front of a cloud
+    for (size_t c = 0; c < NC; ++c) {
+        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+        cfirst[c + 1] = cfirst[c] + (unsigned int)((a.off[c + 1] - a.off[c] + LK_PLANES_CHUNK - 1) / LK_PLANES_CHUNK);
+    }
+    for (size_t c = 0; c <= NC; ++c) roff[c] = (unsigned int)(a.off[c] - a.off[0]);
+    const bool places = a.out_off != nullptr, moved = a.out_cloud || a.src_idx;
+    unsigned long long* d_off64 = nullptr;
+    unsigned int *d_off = nullptr, *d_used = nullptr, *d_status = nullptr, *d_cfirst = nullptr;
+    int* d_mm = nullptr;
+    LkPlanesCall m = {};
+    LkSorCall s = {};   // the output offsets and the scatter are lk_sor_kernels.h's
+    auto carve = [&](void* base) {
+        LkCarve c(base, 256);
+        d_off64 = c.take<unsigned long long>(NC + 1), d_off = c.take<unsigned int>(NC + 1), d_used = c.take<unsigned int>(used.size());
+        d_cfirst = c.take<unsigned int>(NC + 1), d_status = c.take<unsigned int>(NC), d_mm = c.take<int>(6 * NC);
+        m.flag = c.take<unsigned int>(N + 1), m.scan = c.take<unsigned int>(N + 1), m.rem = c.take<float4>(N), m.label = c2c_or_own(c, a.label, N);
+        m.score = c.take<unsigned int>(NC * a.n_hyp), m.done = c.take<unsigned int>(NC), m.n_planes = c.take<unsigned int>(NC), m.win_h = c.take<unsigned int>(NC);
+        m.win = c.take<LkPlanesHyp>(NC), m.planes = c.take<lk_plane>(NP), m.csum = c.take<double>(6 * NP), m.out = c.take<lk_planes>(NC);
+        s.out_off = c.take<unsigned int>(places ? NC + 1 : 0);
+        return c.total();
+    };
+    const size_t bytes = carve(nullptr);
+    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
+    carve(h->c2c.p);
+    size_t scan_tmp = 0;   // (before anything is launched: growing the temporary storage waits for the stream)
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, scan_tmp, m.flag, m.scan, N + 1, h->stream));
+    LKCHK(reserve(h, h->prim_tmp, scan_tmp));
+    HIPCHK(h, hipMemcpyAsync(d_off64, a.off, 8 * (NC + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_off, roff.data(), 4 * (NC + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_cfirst, cfirst.data(), 4 * (NC + 1), hipMemcpyHostToDevice, h->stream));
+    if (!used.empty()) HIPCHK(h, hipMemcpyAsync(d_used, used.data(), 4 * used.size(), hipMemcpyHostToDevice, h->stream));
+    // the status words: lk_c2c_out_of_range at an edge of 1 is |coordinate| >= 2^30
+    LKCHK(c2c_bounds(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, d_off64, d_used, 1.0, d_mm, d_status));
+    m.off = d_off, m.status = d_status, m.chunk_first = d_cfirst, m.in = reinterpret_cast<const float4*>(a.clouds) + a.off[0];
+    m.axis = lk_planes_axis(a.axis, a.cos_max_angle), m.dist2 = a.dist * a.dist, m.seed = a.seed;
+    m.n_clouds = (unsigned int)NC, m.total = (unsigned int)N, m.n_hyp = a.n_hyp, m.max_planes = a.max_planes, m.min_inliers = a.min_inliers;
+    m.keep_planes = a.flags & LK_PLANES_KEEP_PLANES;
+    HIPCHK(h, hipMemsetAsync(m.done, 0, 4 * NC, h->stream));
+    HIPCHK(h, hipMemsetAsync(m.n_planes, 0, 4 * NC, h->stream));
+    HIPCHK(h, hipMemsetAsync(m.planes, 0, sizeof(lk_plane) * NP, h->stream));
+    LAUNCH(h, "planes_init", hipLaunchKernelGGL(lk_planes_init_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
+    const dim3 score_grid(cfirst[NC], (a.n_hyp + LK_PLANES_GROUP - 1) / LK_PLANES_GROUP);
+    size_t tb = 0;
+    hipError_t scanned = hipSuccess;
+    for (uint32_t r = 0; r < a.max_planes && N; ++r) {
+        m.round = r;
+        tb = h->prim_tmp.cap;
+        LAUNCH(h, "planes_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, m.scan, N + 1, h->stream));
+        HIPCHK(h, scanned);
+        LAUNCH(h, "planes_compact", hipLaunchKernelGGL(lk_planes_compact_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+        HIPCHK(h, hipMemsetAsync(m.score, 0, 4 * NC * a.n_hyp, h->stream));
+        LAUNCH(h, "planes_score", hipLaunchKernelGGL(lk_planes_score_kernel, score_grid, dim3(256), 0, h->stream, m));
+        LAUNCH(h, "planes_argmax", hipLaunchKernelGGL(lk_planes_argmax_kernel, dim3((unsigned int)NC), dim3(64), 0, h->stream, m));
+        LAUNCH(h, "planes_mark", hipLaunchKernelGGL(lk_planes_mark_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+    }
+    if (N) {
+        LAUNCH(h, "planes_refit", hipLaunchKernelGGL(lk_planes_refit_kernel, dim3((unsigned int)NC, a.max_planes), dim3(256), 0, h->stream, m));
+        LAUNCH(h, "planes_fit", hipLaunchKernelGGL(lk_planes_fit_kernel, c2c_blocks(NP), dim3(256), 0, h->stream, m));
+    }
+    LAUNCH(h, "planes_record", hipLaunchKernelGGL(lk_planes_record_kernel, c2c_blocks(NC), dim3(256), 0, h->stream, m));
+    std::vector<lk_planes> rec(NC);
+    std::vector<lk_plane> prec(NP);
+    std::vector<unsigned int> ooff(places ? NC + 1 : 0);
+    HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_planes) * NC, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(prec.data(), m.planes, sizeof(lk_plane) * NP, hipMemcpyDeviceToHost, h->stream));
+    if (places) {
+        s.off = m.off, s.n_clouds = m.n_clouds, s.total = m.total, s.flag = m.flag, s.scan = m.scan;
+        s.in = reinterpret_cast<const uint4*>(a.clouds) + a.off[0], s.out_pts = reinterpret_cast<uint4*>(a.out_cloud), s.src_idx = a.src_idx;
+        if (N) LAUNCH(h, "planes_keep", hipLaunchKernelGGL(lk_planes_keep_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+        tb = h->prim_tmp.cap;
+        LAUNCH(h, "planes_keep_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, m.scan, N + 1, h->stream));
+        HIPCHK(h, scanned);
+        LAUNCH(h, "planes_offsets", hipLaunchKernelGGL(lk_sor_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, s));
+        HIPCHK(h, hipMemcpyAsync(ooff.data(), s.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
+        if (moved && N) LAUNCH(h, "planes_scatter", hipLaunchKernelGGL(lk_sor_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(a.out, rec.data(), sizeof(lk_planes) * NC);
+    memcpy(a.planes, prec.data(), sizeof(lk_plane) * NP);
+    if (places)
+        for (size_t c = 0; c <= NC; ++c) a.out_off[c] = ooff[c];
+    if (n_out) *n_out = places ? ooff[NC] : 0;
+    return LK_OK;
+}
+
+extern "C" {
+
+int lk_clouds_planes_dev(lk_handle* h, const float* d_clouds, size_t n_clouds, const uint64_t* off, double dist, uint32_t n_hyp, uint32_t max_planes,
+                         uint32_t min_inliers, const double* axis, double cos_max_angle, uint64_t seed, uint32_t flags, lk_planes* out, lk_plane* planes,
+                         uint32_t* d_label, float* d_out, uint64_t* out_off, uint32_t* d_src_idx) {
+    CHECK_H(h);
+    const PlanesArgs a = {d_clouds, n_clouds, off, dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, out, planes, d_label, d_out, out_off, d_src_idx};
+    size_t total = 0;
+    LKCHK(planes_check(h, "lk_clouds_planes_dev", a, 16, &total));
+    return planes_run(h, a, total, nullptr);
+}
+
+int lk_clouds_planes(lk_handle* h, const float* clouds, size_t n_clouds, const uint64_t* off, double dist, uint32_t n_hyp, uint32_t max_planes,
+                     uint32_t min_inliers, const double* axis, double cos_max_angle, uint64_t seed, uint32_t flags, lk_planes* out, lk_plane* planes,
+                     uint32_t* label, float* out_cloud, uint64_t* out_off, uint32_t* src_idx) {
+    CHECK_H(h);
+    PlanesArgs a = {clouds, n_clouds, off, dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, out, planes, label, out_cloud, out_off, src_idx};
+    size_t total = 0, n_out = 0;
+    LKCHK(planes_check(h, "lk_clouds_planes", a, 4, &total));
+    C2cStage st;
+    st.in = {{clouds, off, n_clouds}};
+    st.out = {{label, 4, total}, {out_cloud, 16, total}, {src_idx, 4, total}};
+    LKCHK(st.upload(h));
+    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
+    a.label = static_cast<uint32_t*>(st.out[0].dev), a.out_cloud = static_cast<float*>(st.out[1].dev), a.src_idx = static_cast<uint32_t*>(st.out[2].dev);
+    LKCHK(planes_run(h, a, total, &n_out));
+    st.out[1].count = st.out[2].count = n_out;   // nothing behind the kept records is written
     return st.fetch(h);
 }
 

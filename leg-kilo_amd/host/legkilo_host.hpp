@@ -578,6 +578,33 @@ class KiloPath {
         if (o.out_off) *o.out_off = oo;
         return out;
     }
+    // lk_clouds_planes_dev: the dominant planes peeled off map clouds where they lie (RANSAC; PCL's SACSegmentation with SACMODEL_PLANE, with an axis
+    // SACMODEL_PERPENDICULAR_PLANE, repeated on what is left) - cloudsMmeDev's clouds and table.  Per round n_hyp planes through three sampled
+    // records of the remainder; the one with the most records within `dist` wins, its records become plane r; up to max_planes rounds while a
+    // winner holds min_inliers.  The arrays of PlanesOut (each optional, device memory) take a label per input record and the remainder (flags
+    // LK_PLANES_KEEP_PLANES: the points on planes) in input order, cloud c at (*out_off)[c] .. (*out_off)[c + 1]) - ground and wall removal in
+    // front of cloudsClusterDev.  *planes (optional) takes plane r of cloud c at c * max_planes + r.
+    struct PlanesOut {   // (value-initialised: every pointer null)
+        std::vector<lk_plane>* planes;
+        uint32_t* d_label;
+        float* d_out;
+        std::vector<uint64_t>* out_off;
+        uint32_t* d_src_idx;
+    };
+    std::vector<lk_planes> cloudsPlanesDev(const float* d_clouds, const std::vector<uint64_t>& off, double dist, uint32_t n_hyp = 256, uint32_t max_planes = 4,
+                                           uint32_t min_inliers = 100, const double* axis = nullptr, double cos_max_angle = 0.0, uint64_t seed = 0, uint32_t flags = 0,
+                                           const PlanesOut& o = PlanesOut()) {
+        if (off.size() < 2) throw std::runtime_error("cloudsPlanesDev: the offset table is empty");
+        if ((o.d_out || o.d_src_idx) && !o.out_off) throw std::runtime_error("cloudsPlanesDev: d_out and d_src_idx need out_off");
+        std::vector<lk_planes> out(off.size() - 1);
+        std::vector<lk_plane> pl((off.size() - 1) * (size_t)(max_planes ? max_planes : 1));
+        std::vector<uint64_t> oo(off.size());
+        dev_->check(lk_clouds_planes_dev(dev_->h(), d_clouds, off.size() - 1, off.data(), dist, n_hyp, max_planes, min_inliers, axis, cos_max_angle, seed, flags, out.data(),
+                                         pl.data(), o.d_label, o.d_out, o.out_off ? oo.data() : nullptr, o.d_src_idx));
+        if (o.planes) *o.planes = pl;
+        if (o.out_off) *o.out_off = oo;
+        return out;
+    }
     // lk_overlay_commit: run (slot) `slot`'s overlay of the last replay with insert becomes part of the handle's map, in HBM - the map KILO::process
     // of that run would have left on a private copy; the other slots' overlays are stale afterwards.  adopt_filter (LK_COMMIT_ADOPT_FILTER): the
     // slot's whole filter record goes to slot 0, so that the live entries go on from the committed map.  Windowed mapping: replay a window with

@@ -3,11 +3,9 @@
 // T = (R, t), the nearest-neighbour search of lk_c2c.h for a query coordinate that is a DOUBLE (the moved point is never rounded to float32), the
 // terms of the two passes of a solve (centroids first, centred products second), the step between two transforms and the stop decision.
 //
-// The double-coordinate forms are overloads of lk_c2c_cell, lk_c2c_axis, lk_c2c_d2 and lk_c2c_search: the float functions of lk_c2c.h keep their
-// text and their bits.  The 27-cell argument at the top of lk_c2c.h holds for a double query coordinate unchanged: it only uses that fl(dx*dx) <=
-// d2 <= fl(max_dist^2), that squaring is strictly monotone on doubles and that p -> floor(p / edge) is monotone and moves by at most one over a
-// distance of edge - none of which asks how many bits the query coordinate has.  (dx is now always a rounded difference, by less than 2^-53 of
-// max_dist where it matters: the same one place as there, a reference point at exactly max_dist.)  A moved point is searched only when it is finite
+// The search is lk_c2c.h's: its walk and its visitor take the query coordinate as it comes, and the double-coordinate overloads of lk_c2c_cell,
+// lk_c2c_axis and lk_c2c_d2 stand there in front of the walk, with the reason why the 27-cell argument does not ask how many bits the query
+// coordinate has.  What this header adds to the search is the move in front of it and the guard: a moved point is searched only when it is finite
 // and |m / max_dist| < 2^30 per axis (lk_align_in_range), so its cell and a difference of two cells stay inside a long long and an int as there.
 // No FMA is spelled out and the units that include this build with -ffp-contract=off; the host build rounds as the device does up to sqrt and atan2.
 // Plain C++ that compiles for the host as it stands, like lk_c2c.h.
@@ -35,46 +33,7 @@ LK_C2C_HD bool lk_align_finite12(const double* T) {
     return ok;
 }
 
-// ---- lk_c2c.h's search for a double query coordinate
-LK_C2C_HD double lk_c2c_d2(double qx, double qy, double qz, float rx, float ry, float rz) {
-    const double dx = qx - (double)rx, dy = qy - (double)ry, dz = qz - (double)rz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-LK_C2C_HD long long lk_c2c_cell(double p, double edge) { return (long long)floor(p / edge); }
-LK_C2C_HD bool lk_c2c_axis(double q, double edge, int mn, int dv, long long* lo, long long* hi) {
-    const long long i = lk_c2c_cell(q, edge) - mn;
-    *lo = i - 1 < 0 ? 0 : i - 1, *hi = i + 1 > dv - 1 ? dv - 1 : i + 1;
-    return *lo <= *hi;
-}
-// as lk_c2c_search(float ...): the minimiser of (d2, j) among the records with d2 <= reach2, or 0xffffffff and +inf
-LK_C2C_HD void lk_c2c_search(double qx, double qy, double qz, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n,
-                             double reach2, unsigned int* j, double* d2) {
-    unsigned int best_j = 0xffffffffu;
-    double best = INFINITY;
-    long long lo[3], hi[3];
-    bool any = lk_c2c_axis(qy, g.edge, g.mn[1], g.dv[1], &lo[1], &hi[1]) & lk_c2c_axis(qz, g.edge, g.mn[2], g.dv[2], &lo[2], &hi[2]);
-    any &= lk_c2c_axis(qx, g.edge, g.mn[0], g.dv[0], &lo[0], &hi[0]);
-    if (any && n) {
-        for (long long i2 = lo[2]; i2 <= hi[2]; ++i2) {
-            for (long long i1 = lo[1]; i1 <= hi[1]; ++i1) {
-                const long long row = i1 * g.dv[0] + i2 * (long long)g.dv[0] * g.dv[1], k0 = row + lo[0], k1 = row + hi[0];
-                unsigned int a = 0, b = n;   // the first record with key >= k0
-                while (a < b) {
-                    const unsigned int m = a + (b - a) / 2;
-                    if ((long long)keys[m] < k0) a = m + 1;
-                    else b = m;
-                }
-                for (; a < n && (long long)keys[a] <= k1; ++a) {
-                    const LkC2cRec r = recs[a];
-                    const double v = lk_c2c_d2(qx, qy, qz, r.x, r.y, r.z);
-                    if (lk_c2c_matched(v, reach2) && (v < best || (v == best && r.idx < best_j))) best = v, best_j = r.idx;
-                }
-            }
-        }
-    }
-    *j = best_j, *d2 = best;
-}
-// one query point under T against one reference cloud: moved, guarded, searched.
+// one query point under T against one reference cloud: moved, guarded, searched (lk_c2c_search on the double coordinates).
 // LK_ALIGN_NO_GUARD (test aid of the host probe only): the search without the range guard.  By brute force the guard changes no result (a float32
 // reference point in range lies 64 max_dist or more inside the bound); what it protects is lk_c2c_cell's conversion of floor(m / edge) to an
 // integer, which is undefined from 2^63 on - the probe's sanitizers tell.

@@ -1,6 +1,7 @@
 // lk_c2c.h - the arithmetic of the cloud-to-cloud distance (lk_clouds_c2c_dev, lk_c2c_kernels.h) that the device route and its CPU twin
 // (tools/probes/c2c_host.cc, tests/test_c2c_host.py) share: the squared distance, the matched test, the cell of a point, the cell-edge rule, the
-// clipped neighbour ranges and the search of one query point through the sorted cells of one reference cloud.
+// clipped neighbour ranges, the walk of one query point through the sorted cells of one cloud (lk_c2c_walk - the ONE copy of it: lk_align.h, lk_mme.h,
+// lk_sor.h and lk_cluster.h bring a visitor each) and the search of one query point on it.
 //
 // The RESULT is defined without a grid (include/legkilo_hip.h): j(i) minimises (d2, j) over the whole reference cloud, kept when d2 <= max_dist^2.
 // The grid only has to hold every reference point with d2 <= max_dist^2 among the cells it visits.  It does: fl(dx*dx) <= d2 <= fl(max_dist^2) and
@@ -74,15 +75,31 @@ LK_C2C_HD bool lk_c2c_axis(float q, double edge, int mn, int dv, long long* lo, 
     return *lo <= *hi;
 }
 
-// One query point against one reference cloud: `keys` - the cloud's n cell keys in ascending order, `recs` - its records in that order.  The three
-// x-neighbours of a cell are consecutive keys, so a row is one range of keys: nine lower bounds cover the 27 cells.  *j, *d2: the minimiser of
-// (d2, j) among the records with d2 <= reach2, or 0xffffffff and +inf; *seen (may be null): records whose distance was evaluated.
-// LK_C2C_WRAP_BUG (test aid of the host probe only): the x range as plain i - 1 .. i + 1, so that a row's range runs on into the next row's first
-// cells.  The distance test still rejects what lies there - the result stands, the work does not: `seen` tells.
-LK_C2C_HD void lk_c2c_search(float qx, float qy, float qz, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n,
-                             double reach2, unsigned int* j, double* d2, unsigned int* seen) {
-    unsigned int best_j = 0xffffffffu, count = 0;
-    double best = INFINITY;
+// The same for a query coordinate that is a DOUBLE (lk_align.h: a moved point is never rounded to float32): overloads, declared in front of the walk
+// because its calls on fundamental types find only what is declared by then.  The 27-cell argument above holds for them unchanged - it never asks
+// how many bits the query coordinate has; dx is then always a rounded difference, by less than 2^-53 of max_dist where it matters.
+LK_C2C_HD double lk_c2c_d2(double qx, double qy, double qz, float rx, float ry, float rz) {
+    const double dx = qx - (double)rx, dy = qy - (double)ry, dz = qz - (double)rz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+LK_C2C_HD long long lk_c2c_cell(double p, double edge) { return (long long)floor(p / edge); }
+LK_C2C_HD bool lk_c2c_axis(double q, double edge, int mn, int dv, long long* lo, long long* hi) {
+    const long long i = lk_c2c_cell(q, edge) - mn;
+    *lo = i - 1 < 0 ? 0 : i - 1, *hi = i + 1 > dv - 1 ? dv - 1 : i + 1;
+    return *lo <= *hi;
+}
+
+// THE walk: one query point (Q = float or double) through the sorted cells of one cloud - `keys`: the cloud's n cell keys in ascending order, `recs`:
+// its records in that order.  The three x-neighbours of a cell are consecutive keys, so a row is one range of keys: nine lower bounds cover the 27
+// cells.  visit(a, r, lk_c2c_d2(q, r)) is called for every record r at sorted place a of those cells - rows in ascending (z, y), keys ascending
+// within a row, records of equal key in input order - whatever its distance; *seen (may be null): records visited.  Every neighbourhood of the
+// map-cloud families is this walk with a visitor: the nearest record (below, lk_align.h), the moments (lk_mme.h), the k smallest (lk_sor.h), the
+// count, the link and the nearest core point (lk_cluster.h).
+// LK_C2C_WRAP_BUG (test aid of the host probe c2c_host.cc only): the x range as plain i - 1 .. i + 1, so that a row's range runs on into the next
+// row's first cells.  The distance test still rejects what lies there - the result stands, the work does not: `seen` tells.
+template <class Q, class V>
+LK_C2C_HD void lk_c2c_walk(Q qx, Q qy, Q qz, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n, V& visit, unsigned int* seen) {
+    unsigned int count = 0;
     long long lo[3], hi[3];
     bool any = lk_c2c_axis(qy, g.edge, g.mn[1], g.dv[1], &lo[1], &hi[1]) & lk_c2c_axis(qz, g.edge, g.mn[2], g.dv[2], &lo[2], &hi[2]);
 #ifdef LK_C2C_WRAP_BUG
@@ -102,13 +119,28 @@ LK_C2C_HD void lk_c2c_search(float qx, float qy, float qz, const LkC2cGrid& g, c
                 }
                 for (; a < n && (long long)keys[a] <= k1; ++a) {
                     const LkC2cRec r = recs[a];
-                    const double v = lk_c2c_d2(qx, qy, qz, r.x, r.y, r.z);
+                    visit(a, r, lk_c2c_d2(qx, qy, qz, r.x, r.y, r.z));
                     ++count;
-                    if (lk_c2c_matched(v, reach2) && (v < best || (v == best && r.idx < best_j))) best = v, best_j = r.idx;
                 }
             }
         }
     }
-    *j = best_j, *d2 = best;
     if (seen) *seen = count;
+}
+
+// the record that minimises (d2, index) among those with d2 <= reach2; none: j = 0xffffffff, best = +inf
+struct LkC2cNearest {
+    double reach2, best;
+    unsigned int j;
+    LK_C2C_HD void operator()(unsigned int, const LkC2cRec& r, double d2) {
+        if (lk_c2c_matched(d2, reach2) && (d2 < best || (d2 == best && r.idx < j))) best = d2, j = r.idx;
+    }
+};
+// One query point against one reference cloud: *j, *d2 - the minimiser, or 0xffffffff and +inf; *seen (may be null): records whose distance was evaluated
+template <class Q>
+LK_C2C_HD void lk_c2c_search(Q qx, Q qy, Q qz, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n, double reach2,
+                             unsigned int* j, double* d2, unsigned int* seen = nullptr) {
+    LkC2cNearest v = {reach2, INFINITY, 0xffffffffu};
+    lk_c2c_walk(qx, qy, qz, g, keys, recs, n, v, seen);
+    *j = v.j, *d2 = v.best;
 }

@@ -12,8 +12,11 @@
 // is in bounds the same way (lk_cluster_kernels.h, arithmetic and the union-find in lk_cluster.h); lk_clouds_planes_dev / lk_clouds_planes peel the
 // dominant planes off a cloud by RANSAC - no cell index, hypotheses x records - and write the remainder or the planes' points the same way
 // (lk_planes_kernels.h, arithmetic in lk_planes.h).
-// What the two families share is written once: c2c_offsets_check / c2c_overlap_check (refusals), c2c_bounds (bounds and status of one side's clouds in
-// use), c2c_or_own (the caller's per-point array or one of ours) and C2cStage (the host entries' trip through c2c_io).
+// What the families share is written once.  Every neighbourhood is lk_c2c.h's ONE walk of the 27 cells with the family's visitor.  On the host:
+// c2c_offsets_check / c2c_overlap_check and, for the single-cloud families, clouds_check_args / clouds_check_table (refusals, in MME's order);
+// c2c_bounds (bounds and status of one side's clouds in use); c2c_carve and C2cIndex::take (the layout of a call in h->c2c and the index's tables in
+// it); nonempty_clouds; c2c_or_own (the caller's per-point array or one of ours); scan_reserve and C2cTail (the compaction tail of the families that
+// write kept records out: scan, output offsets, scatter); C2cStage (the host entries' trip through c2c_io).
 // Two host round trips per call: none before the sort (the grids are built where the bounds lie), one at the end for the records.
 #define LK_TU_C2C 1
 #include "lk_internal.h"
@@ -147,8 +150,8 @@ static std::vector<unsigned int> used_clouds(const uint32_t* pair, size_t n_pair
     return u;
 }
 
-// The search structure of one side's clouds (steps 1 and 2 of a call), shared by lk_clouds_c2c(_dev) and lk_clouds_mme(_dev): the device tables, carved
-// by the caller out of its own scratch.  N = off[n] - off[0] records in all.
+// The search structure of one side's clouds (steps 1 and 2 of a call), shared by every family that walks cells: the device tables, which take() carves
+// out of the caller's layout for n clouds, n_used of them in use, N = off[n] - off[0] records in all.
 struct C2cIndex {
     unsigned long long* d_off64;   // [n + 1], as given
     unsigned int* d_off;           // [n + 1], counted from the first record
@@ -159,7 +162,30 @@ struct C2cIndex {
     unsigned int *k0, *k1, *v0, *v1;   // [N]: k1 = the sorted keys
     LkC2cRec* recs;                // [N], in that order
     std::vector<unsigned int> h_off;   // the host copy of d_off: alive until the caller has synchronised
+    void take(LkCarve& c, size_t n, size_t n_used, size_t N) {
+        d_off64 = c.take<unsigned long long>(n + 1), d_off = c.take<unsigned int>(n + 1), d_used = c.take<unsigned int>(n_used);
+        status = c.take<unsigned int>(n), mm = c.take<int>(6 * n), grid = c.take<LkC2cGrid>(n);
+        k0 = c.take<unsigned int>(N), k1 = c.take<unsigned int>(N), v0 = c.take<unsigned int>(N), v1 = c.take<unsigned int>(N);
+        recs = c.take<LkC2cRec>(N);
+    }
 };
+// every non-empty cloud: what the single-cloud families have in use
+static std::vector<unsigned int> nonempty_clouds(const uint64_t* off, size_t n) {
+    std::vector<unsigned int> used;
+    for (size_t c = 0; c < n; ++c)
+        if (off[c + 1] > off[c]) used.push_back((unsigned int)c);
+    return used;
+}
+// a layout (lk_carve.h) over h->c2c: counted, reserved with a quarter of slack, then handed out
+template <class F>
+static int c2c_carve(lk_handle* h, F&& layout) {
+    LkCarve count(nullptr, 256);
+    layout(count);
+    LKCHK(reserve(h, h->c2c, count.total(), count.total() / 4));
+    LkCarve c(h->c2c.p, 256);
+    layout(c);
+    return LK_OK;
+}
 static dim3 c2c_blocks(size_t n) { return dim3((unsigned int)((n + 255) / 256)); }
 static int c2c_sort(lk_handle* h, void* tmp, size_t& tb, const C2cIndex& x, size_t N, size_t n) {
     HIPCHK(h, lk_prim_sort_pairs_in_segments(tmp, tb, x.k0, x.k1, x.v0, x.v1, (unsigned int)N, (unsigned int)n, x.d_off, x.d_off + 1, 0, 31, h->stream));
@@ -219,25 +245,16 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs
     double* d_T0 = nullptr;
     lk_align_plane* d_pl = nullptr;
     const bool plane = al && al->ref_normals;
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        d_qoff = c.take<unsigned long long>(NQ + 1), x.d_off64 = c.take<unsigned long long>(NR + 1), d_nnoff = c.take<unsigned long long>(P + 1);
-        x.d_off = c.take<unsigned int>(NR + 1), d_pq = c.take<unsigned int>(P), d_pr = c.take<unsigned int>(P);
-        d_uq = c.take<unsigned int>(uq.size()), x.d_used = c.take<unsigned int>(ur.size());
-        q_status = c.take<unsigned int>(NQ), x.status = c.take<unsigned int>(NR);
-        q_mm = c.take<int>(6 * NQ), x.mm = c.take<int>(6 * NR);
-        x.grid = c.take<LkC2cGrid>(NR);
-        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
-        x.recs = c.take<LkC2cRec>(N);
+    LKCHK(c2c_carve(h, [&](LkCarve& c) {
+        x.take(c, NR, ur.size(), N);
+        d_qoff = c.take<unsigned long long>(NQ + 1), d_nnoff = c.take<unsigned long long>(P + 1);
+        d_pq = c.take<unsigned int>(P), d_pr = c.take<unsigned int>(P), d_uq = c.take<unsigned int>(uq.size());
+        q_status = c.take<unsigned int>(NQ), q_mm = c.take<int>(6 * NQ);
         q.nn_idx = c2c_or_own(c, a.nn_idx, total), q.nn_d2 = c2c_or_own(c, a.nn_d2, total);   // (c2c_check: both or neither)
         q.out = c.take<lk_c2c>(P);
         d_T0 = c.take<double>(al ? 12 * P : 0), call.rec = c.take<lk_align>(al ? P : 0), call.done = c.take<unsigned int>(al ? P : 0);
         d_pl = c.take<lk_align_plane>(plane ? P : 0);
-        return c.total();
-    };
-    const size_t bytes = carve(nullptr);
-    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
-    carve(h->c2c.p);
+    }));
     // the host tables of the query side and of the pairs
     std::vector<unsigned long long> nnoff(P + 1, 0ull);
     for (size_t k = 0; k < P; ++k) nnoff[k + 1] = nnoff[k] + (a.q_off[a.pair_q[k] + 1] - a.q_off[a.pair_q[k]]);
@@ -305,10 +322,34 @@ static int c2c_run(lk_handle* h, const C2cArgs& a, size_t total, const AlignArgs
 // copies the arrays back and synchronises once
 namespace {
 struct C2cStage {
-    struct In { const float* host; const uint64_t* off; size_t n_clouds; float4* dev; std::vector<uint64_t> rel; };   // rel = off - off[0]
-    struct Out { void* host; size_t elem, count; void* dev; };                                                        // host null: not asked for, dev null
+    struct In {   // rel = off - off[0]
+        const float* host; const uint64_t* off; size_t n_clouds; float4* dev; std::vector<uint64_t> rel;
+        const float* f() const { return reinterpret_cast<const float*>(dev); }
+    };
+    struct Out {   // host null: not asked for, dev null
+        void* host; size_t elem, count; void* dev;
+        template <typename T> operator T*() const { return static_cast<T*>(dev); }   // the device twin as the array it stands for
+    };
     std::vector<In> in;
     std::vector<Out> out;
+    // the pair families: the query and the reference clouds (and what else lies along the reference records), nn_idx and nn_d2; `a` then names the twins
+    int upload_pairs(lk_handle* h, C2cArgs& a, size_t total, const float** along_ref = nullptr) {
+        in = {{a.query, a.q_off, a.n_q}, {a.ref, a.r_off, a.n_r}};
+        if (along_ref) in.push_back({*along_ref, a.r_off, a.n_r});
+        out = {{a.nn_idx, 4, total}, {a.nn_idx ? a.nn_d2 : nullptr, 8, total}};
+        LKCHK(upload(h));
+        a.query = in[0].f(), a.ref = in[1].f(), a.q_off = in[0].rel.data(), a.r_off = in[1].rel.data();
+        a.nn_idx = out[0], a.nn_d2 = out[1];
+        if (along_ref) *along_ref = in[2].f();
+        return LK_OK;
+    }
+    // the single-cloud families: the clouds; the caller lists `out`
+    int upload_clouds(lk_handle* h, const float*& clouds, size_t n_clouds, const uint64_t*& off) {
+        in = {{clouds, off, n_clouds}};
+        LKCHK(upload(h));
+        clouds = in[0].f(), off = in[0].rel.data();
+        return LK_OK;
+    }
     int upload(lk_handle* h) {
         auto carve = [&](void* base) {
             LkCarve c(base, 256);
@@ -358,12 +399,7 @@ int lk_clouds_c2c(lk_handle* h, const float* query, size_t n_qclouds, const uint
     size_t total = 0;
     LKCHK(c2c_check(h, "lk_clouds_c2c", a, 4, &total));
     C2cStage st;
-    st.in = {{query, q_off, n_qclouds}, {ref, r_off, n_rclouds}};
-    st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
-    LKCHK(st.upload(h));
-    a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
-    a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
-    a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
+    LKCHK(st.upload_pairs(h, a, total));
     LKCHK(c2c_run(h, a, total));
     return st.fetch(h);
 }
@@ -402,12 +438,7 @@ int lk_clouds_align(lk_handle* h, const float* query, size_t n_qclouds, const ui
     size_t total = 0;
     LKCHK(align_check(h, "lk_clouds_align", a, al, 4, &total));
     C2cStage st;
-    st.in = {{query, q_off, n_qclouds}, {ref, r_off, n_rclouds}};
-    st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
-    LKCHK(st.upload(h));
-    a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
-    a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
-    a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
+    LKCHK(st.upload_pairs(h, a, total));
     LKCHK(c2c_run(h, a, total, &al));
     return st.fetch(h);
 }
@@ -446,13 +477,7 @@ int lk_clouds_align_plane(lk_handle* h, const float* query, size_t n_qclouds, co
     size_t total = 0;
     LKCHK(align_plane_check(h, "lk_clouds_align_plane", a, al, 4, &total));
     C2cStage st;
-    st.in = {{query, q_off, n_qclouds}, {ref, r_off, n_rclouds}, {ref_normals, r_off, n_rclouds}};
-    st.out = {{nn_idx, 4, total}, {nn_idx ? nn_d2 : nullptr, 8, total}};
-    LKCHK(st.upload(h));
-    a.query = reinterpret_cast<const float*>(st.in[0].dev), a.ref = reinterpret_cast<const float*>(st.in[1].dev);
-    al.ref_normals = reinterpret_cast<const float*>(st.in[2].dev);
-    a.q_off = st.in[0].rel.data(), a.r_off = st.in[1].rel.data();
-    a.nn_idx = static_cast<uint32_t*>(st.out[0].dev), a.nn_d2 = static_cast<double*>(st.out[1].dev);
+    LKCHK(st.upload_pairs(h, a, total, &al.ref_normals));
     LKCHK(c2c_run(h, a, total, &al));
     return st.fetch(h);
 }
@@ -510,25 +535,87 @@ struct MmeArgs {   // the arguments both entries share, as the caller gave them
 };
 }  // namespace
 
-// what both entries refuse before anything is launched; cloud_align: 16 for device clouds, 4 for host ones.  *total: records in all
+// What every single-cloud family refuses about its clouds, in two halves.  The order of refusals is lk_clouds_mme(_dev)'s, and a caller that passes
+// several bad arguments is told about the first in it: (1) n_clouds 0; (2) clouds, off, out null, in that order; (3) clouds misaligned -
+// clouds_check_args.  (4) the family's own per-point arrays misaligned, its radius, its min_pts - MME's and the normals' radius stand HERE, between
+// the halves; the reach of the filter and of the clustering is refused in front of (1).  (5) off decreases; (6) 2^31 - 1 clouds; (7) 2^31 records
+// in all; (8) 2^32 - 1 records in a cloud - clouds_check_table, which also sets *total: records in all.  (9) everything else of the family's own.
+// cloud_align: 16 for device clouds, 4 for host ones.
+static int clouds_check_args(lk_handle* h, const std::string& w, const float* clouds, size_t n_clouds, const uint64_t* off, const void* out, unsigned int cloud_align) {
+    if (n_clouds == 0) return fail(h, LK_ERR_INVALID, w + "n_clouds is 0");
+    if (!clouds) return fail(h, LK_ERR_INVALID, w + "null argument (clouds)");
+    if (!off) return fail(h, LK_ERR_INVALID, w + "null argument (off)");
+    if (!out) return fail(h, LK_ERR_INVALID, w + "null argument (out)");
+    if ((uintptr_t)clouds & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "clouds must be " + std::to_string(cloud_align) + "-byte aligned");
+    return LK_OK;
+}
+static int clouds_check_table(lk_handle* h, const std::string& w, size_t n_clouds, const uint64_t* off, size_t* total) {
+    LKCHK(c2c_offsets_check(h, w, "off", off, n_clouds));
+    if (n_clouds >= 0x7fffffffull) return fail(h, LK_ERR_CAPACITY, w + "2^31 - 1 clouds or more");
+    if (off[n_clouds] - off[0] >= (1ull << 31)) return fail(h, LK_ERR_CAPACITY, w + "the clouds hold 2^31 records or more in all: split the call");
+    for (size_t c = 0; c < n_clouds; ++c)   // (cannot happen under the bound above; the header states both)
+        if (off[c + 1] - off[c] >= 0xffffffffull) return fail(h, LK_ERR_CAPACITY, w + "cloud " + std::to_string(c) + " holds 2^32 - 1 records or more");
+    *total = (size_t)(off[n_clouds] - off[0]);
+    return LK_OK;
+}
+static int radius_check(lk_handle* h, const std::string& w, const char* name, double r) {
+    if (!std::isfinite(r) || !(r > 0.0)) return fail(h, LK_ERR_INVALID, w + name + " must be finite and above 0");
+    return LK_OK;
+}
+// the scan's temporary storage for n words, before anything is launched: growing it waits for the stream
+static int scan_reserve(lk_handle* h, const unsigned int* in, unsigned int* out, size_t n) {
+    size_t tb = 0;
+    HIPCHK(h, lk_prim_exclusive_scan(nullptr, tb, in, out, n, h->stream));
+    return reserve(h, h->prim_tmp, tb);
+}
+
+// The compaction tail of the families that write their kept records out as clouds (outlier filter, clustering, plane extraction): each brings the
+// keep words of its own flag kernel; the scan over them, the output offsets, their copy to the host and the scatter are enqueued here, and after the
+// caller's synchronisation finish() fills the caller's out_off.  No out_off: no places were asked for, and nothing here does anything.
+struct C2cTail {
+    LkCompactCall c = {};
+    uint64_t* out_off;                 // the caller's table
+    bool moved;                        // out_cloud or src_idx asked for
+    std::vector<unsigned int> h_off;   // the host copy of c.out_off: alive until the caller has synchronised
+    C2cTail(const float* clouds, const uint64_t* off, float* out_cloud, uint64_t* out_off_, uint32_t* src_idx) : out_off(out_off_), moved(out_cloud || src_idx) {
+        c.in = reinterpret_cast<const uint4*>(clouds) + off[0], c.out_pts = reinterpret_cast<uint4*>(out_cloud), c.src_idx = src_idx;
+    }
+    // out_off and the scan's array; a family that has one for scans of its own (own_scan false) points c.scan at it instead
+    void take(LkCarve& cv, size_t NC, size_t N, bool own_scan = true) {
+        if (own_scan) c.scan = cv.take<unsigned int>(out_off ? N + 1 : 0);
+        c.out_off = cv.take<unsigned int>(out_off ? NC + 1 : 0);
+    }
+    // behind the family's flag kernel (the scan's temporary storage is reserved: scan_reserve).  d_off: the clouds' table from the first record
+    int enqueue(lk_handle* h, const unsigned int* d_off, unsigned int* flag, size_t NC, size_t N, const char* scan_name, const char* offsets_name, const char* scatter_name) {
+        if (!out_off) return LK_OK;
+        c.off = d_off, c.flag = flag, c.n_clouds = (unsigned int)NC, c.total = (unsigned int)N;
+        h_off.resize(NC + 1);
+        size_t tb = h->prim_tmp.cap;
+        hipError_t scanned = hipSuccess;
+        LAUNCH(h, scan_name, scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, c.flag, c.scan, N + 1, h->stream));
+        HIPCHK(h, scanned);
+        LAUNCH(h, offsets_name, hipLaunchKernelGGL(lk_c2c_compact_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, c));
+        HIPCHK(h, hipMemcpyAsync(h_off.data(), c.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
+        if (moved && N) LAUNCH(h, scatter_name, hipLaunchKernelGGL(lk_c2c_compact_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, c));
+        return LK_OK;
+    }
+    // after the synchronisation.  *n_out: records written to out_cloud / src_idx
+    void finish(size_t* n_out) const {
+        for (size_t k = 0; k < h_off.size(); ++k) out_off[k] = h_off[k];
+        if (n_out) *n_out = h_off.empty() ? 0 : h_off.back();
+    }
+};
+
+// what both entries refuse before anything is launched
 static int mme_check(lk_handle* h, const char* who, const MmeArgs& a, unsigned int cloud_align, size_t* total) {
     const std::string w = std::string(who) + ": ";
-    if (a.n_clouds == 0) return fail(h, LK_ERR_INVALID, w + "n_clouds is 0");
-    if (!a.clouds) return fail(h, LK_ERR_INVALID, w + "null argument (clouds)");
-    if (!a.off) return fail(h, LK_ERR_INVALID, w + "null argument (off)");
-    if (!a.out) return fail(h, LK_ERR_INVALID, w + "null argument (out)");
-    if ((uintptr_t)a.clouds & (cloud_align - 1)) return fail(h, LK_ERR_INVALID, w + "clouds must be " + std::to_string(cloud_align) + "-byte aligned");
+    LKCHK(clouds_check_args(h, w, a.clouds, a.n_clouds, a.off, a.out, cloud_align));
     if ((uintptr_t)a.n & 3) return fail(h, LK_ERR_INVALID, w + "n must be 4-byte aligned");
     if ((uintptr_t)a.hh & 7) return fail(h, LK_ERR_INVALID, w + "h must be 8-byte aligned");
     if ((uintptr_t)a.lmin & 7) return fail(h, LK_ERR_INVALID, w + "lmin must be 8-byte aligned");
-    if (!std::isfinite(a.radius) || !(a.radius > 0.0)) return fail(h, LK_ERR_INVALID, w + "radius must be finite and above 0");
+    LKCHK(radius_check(h, w, "radius", a.radius));
     if (a.min_pts < 4) return fail(h, LK_ERR_INVALID, w + "min_pts is " + std::to_string(a.min_pts) + ": at least 4 (below four points det is 0 by rank)");
-    LKCHK(c2c_offsets_check(h, w, "off", a.off, a.n_clouds));
-    if (a.n_clouds >= 0x7fffffffull) return fail(h, LK_ERR_CAPACITY, w + "2^31 - 1 clouds or more");
-    if (a.off[a.n_clouds] - a.off[0] >= (1ull << 31)) return fail(h, LK_ERR_CAPACITY, w + "the clouds hold 2^31 records or more in all: split the call");
-    for (size_t c = 0; c < a.n_clouds; ++c)   // (cannot happen under the bound above; the header states both)
-        if (a.off[c + 1] - a.off[c] >= 0xffffffffull) return fail(h, LK_ERR_CAPACITY, w + "cloud " + std::to_string(c) + " holds 2^32 - 1 records or more");
-    *total = (size_t)(a.off[a.n_clouds] - a.off[0]);
+    LKCHK(clouds_check_table(h, w, a.n_clouds, a.off, total));
     const C2cSpan in = {"clouds", (uintptr_t)a.clouds + 16u * (uintptr_t)a.off[0], 16u * *total};
     const C2cSpan o[3] = {{"n", (uintptr_t)a.n, 4 * *total}, {"h", (uintptr_t)a.hh, 8 * *total}, {"lmin", (uintptr_t)a.lmin, 8 * *total}};
     for (int i = 0; i < 3; ++i) LKCHK(c2c_overlap_check(h, w, o[i], &in, 1, "the input clouds", o + i + 1, 2 - i));
@@ -538,24 +625,14 @@ static int mme_check(lk_handle* h, const char* who, const MmeArgs& a, unsigned i
 // the call behind mme_check, on DEVICE clouds and DEVICE per-point arrays (null: the library's own)
 static int mme_run(lk_handle* h, const MmeArgs& a, size_t N) {
     const size_t NC = a.n_clouds;
-    std::vector<unsigned int> used;   // every non-empty cloud
-    for (size_t c = 0; c < NC; ++c)
-        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+    const std::vector<unsigned int> used = nonempty_clouds(a.off, NC);
     C2cIndex x = {};
     LkMmeCall m = {};
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
-        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
-        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
-        x.recs = c.take<LkC2cRec>(N);
+    LKCHK(c2c_carve(h, [&](LkCarve& c) {
+        x.take(c, NC, used.size(), N);
         m.n = c2c_or_own(c, a.n, N), m.h = c2c_or_own(c, a.hh, N), m.lmin = c2c_or_own(c, a.lmin, N);
         m.out = c.take<lk_mme>(NC);
-        return c.total();
-    };
-    const size_t bytes = carve(nullptr);
-    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
-    carve(h->c2c.p);
+    }));
     LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.radius, x));
     m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
     m.reach2 = lk_c2c_reach2(a.radius);
@@ -587,11 +664,9 @@ int lk_clouds_mme(lk_handle* h, const float* clouds, size_t n_clouds, const uint
     size_t total = 0;
     LKCHK(mme_check(h, "lk_clouds_mme", a, 4, &total));
     C2cStage st;
-    st.in = {{clouds, off, n_clouds}};
     st.out = {{n, 4, total}, {hh, 8, total}, {lmin, 8, total}};
-    LKCHK(st.upload(h));
-    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
-    a.n = static_cast<uint32_t*>(st.out[0].dev), a.hh = static_cast<double*>(st.out[1].dev), a.lmin = static_cast<double*>(st.out[2].dev);
+    LKCHK(st.upload_clouds(h, a.clouds, a.n_clouds, a.off));
+    a.n = st.out[0], a.hh = st.out[1], a.lmin = st.out[2];
     LKCHK(mme_run(h, a, total));
     return st.fetch(h);
 }
@@ -611,12 +686,12 @@ struct NormalsArgs {   // the arguments both entries share, as the caller gave t
 };
 }  // namespace
 
-// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals with min_pts from 3 on, then the entry's own.  *total: records in all
+// what both entries refuse before anything is launched: the clouds' refusals with the radius where lk_clouds_mme(_dev) has it, then the entry's own
 static int normals_check(lk_handle* h, const char* who, const NormalsArgs& a, unsigned int cloud_align, size_t* total) {
     const std::string w = std::string(who) + ": ";
-    lk_mme sink;
-    const MmeArgs m = {a.clouds, a.n_clouds, a.off, a.radius, a.min_pts < 4 ? 4u : a.min_pts, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
-    LKCHK(mme_check(h, who, m, cloud_align, total));
+    LKCHK(clouds_check_args(h, w, a.clouds, a.n_clouds, a.off, a.out, cloud_align));
+    LKCHK(radius_check(h, w, "radius", a.radius));
+    LKCHK(clouds_check_table(h, w, a.n_clouds, a.off, total));
     if (a.min_pts < 3) return fail(h, LK_ERR_INVALID, w + "min_pts is " + std::to_string(a.min_pts) + ": at least 3 (two points span no plane)");
     if (!std::isfinite(a.min_planarity) || a.min_planarity < 0.0 || a.min_planarity > 1.0) return fail(h, LK_ERR_INVALID, w + "min_planarity must be finite and in 0 .. 1");
     if (!a.normals) return fail(h, LK_ERR_INVALID, w + "null argument (normals)");
@@ -628,23 +703,10 @@ static int normals_check(lk_handle* h, const char* who, const NormalsArgs& a, un
 // the call behind normals_check, on DEVICE clouds and a DEVICE record array
 static int normals_run(lk_handle* h, const NormalsArgs& a, size_t N) {
     const size_t NC = a.n_clouds;
-    std::vector<unsigned int> used;   // every non-empty cloud
-    for (size_t c = 0; c < NC; ++c)
-        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
+    const std::vector<unsigned int> used = nonempty_clouds(a.off, NC);
     C2cIndex x = {};
     LkNormalsCall m = {};
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
-        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
-        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
-        x.recs = c.take<LkC2cRec>(N);
-        m.out = c.take<lk_normals>(NC);
-        return c.total();
-    };
-    const size_t bytes = carve(nullptr);
-    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
-    carve(h->c2c.p);
+    LKCHK(c2c_carve(h, [&](LkCarve& c) { x.take(c, NC, used.size(), N), m.out = c.take<lk_normals>(NC); }));
     LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.radius, x));
     m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs, m.normals = reinterpret_cast<float4*>(a.normals);
     m.reach2 = lk_c2c_reach2(a.radius), m.min_planarity = a.min_planarity;
@@ -676,11 +738,9 @@ int lk_clouds_normals(lk_handle* h, const float* clouds, size_t n_clouds, const 
     size_t total = 0;
     LKCHK(normals_check(h, "lk_clouds_normals", a, 4, &total));
     C2cStage st;
-    st.in = {{clouds, off, n_clouds}};
     st.out = {{normals, 16, total}};
-    LKCHK(st.upload(h));
-    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
-    a.normals = static_cast<float*>(st.out[0].dev);
+    LKCHK(st.upload_clouds(h, a.clouds, a.n_clouds, a.off));
+    a.normals = st.out[0];
     LKCHK(normals_run(h, a, total));
     return st.fetch(h);
 }
@@ -704,13 +764,12 @@ struct SorArgs {   // the arguments both entries share, as the caller gave them
 };
 }  // namespace
 
-// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals with the reach as the radius, then the entry's own.  *total: records in all
+// what both entries refuse before anything is launched: the reach, the clouds' refusals, then the entry's own
 static int sor_check(lk_handle* h, const char* who, const SorArgs& a, unsigned int cloud_align, size_t* total) {
     const std::string w = std::string(who) + ": ";
-    if (!std::isfinite(a.reach) || !(a.reach > 0.0)) return fail(h, LK_ERR_INVALID, w + "reach must be finite and above 0");
-    lk_mme sink;
-    const MmeArgs m = {a.clouds, a.n_clouds, a.off, a.reach, 4u, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
-    LKCHK(mme_check(h, who, m, cloud_align, total));
+    LKCHK(radius_check(h, w, "reach", a.reach));
+    LKCHK(clouds_check_args(h, w, a.clouds, a.n_clouds, a.off, a.out, cloud_align));
+    LKCHK(clouds_check_table(h, w, a.n_clouds, a.off, total));
     if (a.k == 0 || a.k > LK_SOR_MAX_K) return fail(h, LK_ERR_INVALID, w + "k is " + std::to_string(a.k) + ": 1 .. " + std::to_string(LK_SOR_MAX_K));
     if (!(a.n_sigma >= 0.0)) return fail(h, LK_ERR_INVALID, w + "n_sigma must be 0 or above (+inf: the radius criterion alone)");
     if (a.out_cloud && !a.out_off) return fail(h, LK_ERR_INVALID, w + "out_cloud needs out_off");
@@ -735,36 +794,21 @@ static void sor_point_launch(lk_handle* h, const LkSorCall& m, size_t N) {
 // *n_out: records written to out_cloud / src_idx
 static int sor_run(lk_handle* h, const SorArgs& a, size_t N, size_t* n_out) {
     const size_t NC = a.n_clouds;
-    std::vector<unsigned int> used;   // every non-empty cloud
-    for (size_t c = 0; c < NC; ++c)
-        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
-    const bool flags = a.keep || a.out_off, places = a.out_off != nullptr, moved = a.out_cloud || a.src_idx;
+    const std::vector<unsigned int> used = nonempty_clouds(a.off, NC);
+    const bool flags = a.keep || a.out_off;
     C2cIndex x = {};
     LkSorCall m = {};
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
-        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
-        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
-        x.recs = c.take<LkC2cRec>(N);
+    C2cTail t(a.clouds, a.off, a.out_cloud, a.out_off, a.src_idx);
+    LKCHK(c2c_carve(h, [&](LkCarve& c) {
+        x.take(c, NC, used.size(), N);
         m.dbar = c2c_or_own(c, a.dbar, N);
-        m.flag = c.take<unsigned int>(flags ? N + 1 : 0), m.scan = c.take<unsigned int>(places ? N + 1 : 0);
-        m.thr = c.take<double>(NC), m.out_off = c.take<unsigned int>(places ? NC + 1 : 0);
-        m.out = c.take<lk_sor>(NC);
-        return c.total();
-    };
-    const size_t bytes = carve(nullptr);
-    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
-    carve(h->c2c.p);
-    size_t scan_tmp = 0;
-    if (places) {   // (before anything is launched: growing the temporary storage waits for the stream)
-        HIPCHK(h, lk_prim_exclusive_scan(nullptr, scan_tmp, m.flag, m.scan, N + 1, h->stream));
-        LKCHK(reserve(h, h->prim_tmp, scan_tmp));
-    }
+        m.flag = c.take<unsigned int>(flags ? N + 1 : 0), m.thr = c.take<double>(NC), m.out = c.take<lk_sor>(NC);
+        t.take(c, NC, N);
+    }));
+    if (a.out_off) LKCHK(scan_reserve(h, m.flag, t.c.scan, N + 1));
     LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.reach, x));
     m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
-    m.in = reinterpret_cast<const uint4*>(a.clouds) + a.off[0];
-    m.cnt = a.cnt, m.keep = a.keep, m.out_pts = reinterpret_cast<uint4*>(a.out_cloud), m.src_idx = a.src_idx;
+    m.cnt = a.cnt, m.keep = a.keep;
     m.reach2 = lk_c2c_reach2(a.reach), m.n_sigma = a.n_sigma;
     m.n_clouds = (unsigned int)NC, m.k = a.k, m.total = (unsigned int)N;
     if (N) {
@@ -775,23 +819,12 @@ static int sor_run(lk_handle* h, const SorArgs& a, size_t N, size_t* n_out) {
     }
     LAUNCH(h, "sor_stats", hipLaunchKernelGGL(lk_sor_stats_kernel, dim3((unsigned int)NC), dim3(256), 0, h->stream, m));
     std::vector<lk_sor> rec(NC);
-    std::vector<unsigned int> ooff(places ? NC + 1 : 0);
     HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_sor) * NC, hipMemcpyDeviceToHost, h->stream));
     if (flags) LAUNCH(h, "sor_flag", hipLaunchKernelGGL(lk_sor_flag_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
-    if (places) {
-        size_t tb = h->prim_tmp.cap;
-        hipError_t scanned = hipSuccess;
-        LAUNCH(h, "sor_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, m.scan, N + 1, h->stream));
-        HIPCHK(h, scanned);
-        LAUNCH(h, "sor_offsets", hipLaunchKernelGGL(lk_sor_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, m));
-        HIPCHK(h, hipMemcpyAsync(ooff.data(), m.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
-        if (moved && N) LAUNCH(h, "sor_scatter", hipLaunchKernelGGL(lk_sor_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
-    }
+    LKCHK(t.enqueue(h, m.off, m.flag, NC, N, "sor_scan", "sor_offsets", "sor_scatter"));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     memcpy(a.out, rec.data(), sizeof(lk_sor) * NC);
-    if (places)
-        for (size_t c = 0; c <= NC; ++c) a.out_off[c] = ooff[c];
-    if (n_out) *n_out = places ? ooff[NC] : 0;
+    t.finish(n_out);
     return LK_OK;
 }
 
@@ -813,12 +846,9 @@ int lk_clouds_sor(lk_handle* h, const float* clouds, size_t n_clouds, const uint
     size_t total = 0, n_out = 0;
     LKCHK(sor_check(h, "lk_clouds_sor", a, 4, &total));
     C2cStage st;
-    st.in = {{clouds, off, n_clouds}};
     st.out = {{out_cloud, 16, total}, {src_idx, 4, total}, {keep, 1, total}, {cnt, 4, total}, {dbar, 8, total}};
-    LKCHK(st.upload(h));
-    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
-    a.out_cloud = static_cast<float*>(st.out[0].dev), a.src_idx = static_cast<uint32_t*>(st.out[1].dev), a.keep = static_cast<uint8_t*>(st.out[2].dev);
-    a.cnt = static_cast<uint32_t*>(st.out[3].dev), a.dbar = static_cast<double*>(st.out[4].dev);
+    LKCHK(st.upload_clouds(h, a.clouds, a.n_clouds, a.off));
+    a.out_cloud = st.out[0], a.src_idx = st.out[1], a.keep = st.out[2], a.cnt = st.out[3], a.dbar = st.out[4];
     LKCHK(sor_run(h, a, total, &n_out));
     st.out[0].count = st.out[1].count = n_out;   // nothing behind the kept records is written
     return st.fetch(h);
@@ -844,13 +874,12 @@ struct ClusterArgs {   // the arguments both entries share, as the caller gave t
 };
 }  // namespace
 
-// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals with the reach as the radius, then the entry's own.  *total: records in all
+// what both entries refuse before anything is launched: the reach, the clouds' refusals, then the entry's own
 static int cluster_check(lk_handle* h, const char* who, const ClusterArgs& a, unsigned int cloud_align, size_t* total) {
     const std::string w = std::string(who) + ": ";
-    if (!std::isfinite(a.reach) || !(a.reach > 0.0)) return fail(h, LK_ERR_INVALID, w + "reach must be finite and above 0");
-    lk_mme sink;
-    const MmeArgs m = {a.clouds, a.n_clouds, a.off, a.reach, 4u, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
-    LKCHK(mme_check(h, who, m, cloud_align, total));
+    LKCHK(radius_check(h, w, "reach", a.reach));
+    LKCHK(clouds_check_args(h, w, a.clouds, a.n_clouds, a.off, a.out, cloud_align));
+    LKCHK(clouds_check_table(h, w, a.n_clouds, a.off, total));
     if (a.min_pts == 0) return fail(h, LK_ERR_INVALID, w + "min_pts is 0: at least 1 (a point counts itself)");
     if (a.min_size > a.max_size) return fail(h, LK_ERR_INVALID, w + "min_size is " + std::to_string(a.min_size) + ", above max_size " + std::to_string(a.max_size));
     if (a.flags & ~LK_CLUSTER_KEEP_LARGEST) return fail(h, LK_ERR_INVALID, w + "flags holds an unknown bit: 0 or LK_CLUSTER_KEEP_LARGEST");
@@ -873,41 +902,26 @@ static int cluster_check(lk_handle* h, const char* who, const ClusterArgs& a, un
 // *n_cl: entries written to cl_size / cl_first, *n_out: records written to out_cloud / src_idx
 static int cluster_run(lk_handle* h, const ClusterArgs& a, size_t N, size_t* n_cl, size_t* n_out) {
     const size_t NC = a.n_clouds;
-    std::vector<unsigned int> used;   // every non-empty cloud
-    for (size_t c = 0; c < NC; ++c)
-        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
-    const bool places = a.out_off != nullptr, moved = a.out_cloud || a.src_idx;
+    const std::vector<unsigned int> used = nonempty_clouds(a.off, NC);
     C2cIndex x = {};
     LkClusterCall m = {};
-    LkSorCall s = {};   // the scan's offsets and the scatter are lk_sor_kernels.h's
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
-        x.d_off64 = c.take<unsigned long long>(NC + 1), x.d_off = c.take<unsigned int>(NC + 1), x.d_used = c.take<unsigned int>(used.size());
-        x.status = c.take<unsigned int>(NC), x.mm = c.take<int>(6 * NC), x.grid = c.take<LkC2cGrid>(NC);
-        x.k0 = c.take<unsigned int>(N), x.k1 = c.take<unsigned int>(N), x.v0 = c.take<unsigned int>(N), x.v1 = c.take<unsigned int>(N);
-        x.recs = c.take<LkC2cRec>(N);
+    C2cTail t(a.clouds, a.off, a.out_cloud, a.out_off, a.src_idx);
+    LKCHK(c2c_carve(h, [&](LkCarve& c) {
+        x.take(c, NC, used.size(), N);
         m.core = c.take<unsigned char>(N), m.parent = c.take<unsigned int>(N), m.root = c.take<unsigned int>(N);
         m.n = c2c_or_own(c, a.n, N), m.kind = c2c_or_own(c, a.kind, N);
         m.rflag = c.take<unsigned int>(N + 1), m.rscan = c.take<unsigned int>(N + 1), m.size = c.take<unsigned int>(N), m.first = c.take<unsigned int>(N);
         m.cl_off = c.take<unsigned int>(NC + 1), m.kept_id = c.take<unsigned int>(NC);
-        m.flag = c.take<unsigned int>(places ? N + 1 : 0), s.scan = c.take<unsigned int>(places ? N + 1 : 0), s.out_off = c.take<unsigned int>(places ? NC + 1 : 0);
-        m.out = c.take<lk_cluster>(NC);
-        return c.total();
-    };
-    const size_t bytes = carve(nullptr);
-    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
-    carve(h->c2c.p);
-    size_t scan_tmp = 0;   // (before anything is launched: growing the temporary storage waits for the stream)
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, scan_tmp, m.rflag, m.rscan, N + 1, h->stream));
-    LKCHK(reserve(h, h->prim_tmp, scan_tmp));
+        m.flag = c.take<unsigned int>(a.out_off ? N + 1 : 0), m.out = c.take<lk_cluster>(NC);
+        t.take(c, NC, N);
+    }));
+    LKCHK(scan_reserve(h, m.rflag, m.rscan, N + 1));   // (the tail's scan is as long)
     LKCHK(c2c_index(h, reinterpret_cast<const float4*>(a.clouds), a.off, NC, used, a.reach, x));
     m.off = x.d_off, m.status = x.status, m.grid = x.grid, m.keys = x.k1, m.recs = x.recs;
     m.label = a.label, m.cl_size = a.cl_size, m.cl_first = a.cl_first;
     m.reach2 = lk_c2c_reach2(a.reach);
     m.n_clouds = (unsigned int)NC, m.total = (unsigned int)N, m.min_pts = a.min_pts, m.min_size = a.min_size, m.max_size = a.max_size;
     m.keep_largest = a.flags & LK_CLUSTER_KEEP_LARGEST;
-    s.off = m.off, s.n_clouds = m.n_clouds, s.total = m.total, s.flag = m.flag;
-    s.in = reinterpret_cast<const uint4*>(a.clouds) + a.off[0], s.out_pts = reinterpret_cast<uint4*>(a.out_cloud), s.src_idx = a.src_idx;
     if (N) {
         LAUNCH(h, "cluster_count", hipLaunchKernelGGL(lk_cluster_count_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
         LAUNCH(h, "cluster_link", hipLaunchKernelGGL(lk_cluster_link_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
@@ -923,26 +937,17 @@ static int cluster_run(lk_handle* h, const ClusterArgs& a, size_t N, size_t* n_c
     LAUNCH(h, "cluster_record", hipLaunchKernelGGL(lk_cluster_record_kernel, dim3((unsigned int)NC), dim3(256), 0, h->stream, m));
     LAUNCH(h, "cluster_tables", hipLaunchKernelGGL(lk_cluster_tables_kernel, c2c_blocks(std::max(N, NC + 1)), dim3(256), 0, h->stream, m));
     std::vector<lk_cluster> rec(NC);
-    std::vector<unsigned int> coff(NC + 1), ooff(places ? NC + 1 : 0);
+    std::vector<unsigned int> coff(NC + 1);
     HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_cluster) * NC, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(coff.data(), m.cl_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
-    if (places) {
-        LAUNCH(h, "cluster_flag", hipLaunchKernelGGL(lk_cluster_flag_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
-        tb = h->prim_tmp.cap;
-        LAUNCH(h, "cluster_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, s.scan, N + 1, h->stream));
-        HIPCHK(h, scanned);
-        LAUNCH(h, "cluster_offsets", hipLaunchKernelGGL(lk_sor_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, s));
-        HIPCHK(h, hipMemcpyAsync(ooff.data(), s.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
-        if (moved && N) LAUNCH(h, "cluster_scatter", hipLaunchKernelGGL(lk_sor_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, s));
-    }
+    if (a.out_off) LAUNCH(h, "cluster_flag", hipLaunchKernelGGL(lk_cluster_flag_kernel, c2c_blocks(N + 1), dim3(256), 0, h->stream, m));
+    LKCHK(t.enqueue(h, m.off, m.flag, NC, N, "cluster_scan", "cluster_offsets", "cluster_scatter"));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     memcpy(a.out, rec.data(), sizeof(lk_cluster) * NC);
     if (a.cl_off)
         for (size_t c = 0; c <= NC; ++c) a.cl_off[c] = coff[c];
-    if (places)
-        for (size_t c = 0; c <= NC; ++c) a.out_off[c] = ooff[c];
     if (n_cl) *n_cl = coff[NC];
-    if (n_out) *n_out = places ? ooff[NC] : 0;
+    t.finish(n_out);
     return LK_OK;
 }
 
@@ -966,13 +971,9 @@ int lk_clouds_cluster(lk_handle* h, const float* clouds, size_t n_clouds, const 
     size_t total = 0, n_cl = 0, n_out = 0;
     LKCHK(cluster_check(h, "lk_clouds_cluster", a, 4, &total));
     C2cStage st;
-    st.in = {{clouds, off, n_clouds}};
     st.out = {{label, 4, total}, {kind, 1, total}, {n, 4, total}, {cl_size, 4, total}, {cl_first, 4, total}, {out_cloud, 16, total}, {src_idx, 4, total}};
-    LKCHK(st.upload(h));
-    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
-    a.label = static_cast<uint32_t*>(st.out[0].dev), a.kind = static_cast<uint8_t*>(st.out[1].dev), a.n = static_cast<uint32_t*>(st.out[2].dev);
-    a.cl_size = static_cast<uint32_t*>(st.out[3].dev), a.cl_first = static_cast<uint32_t*>(st.out[4].dev);
-    a.out_cloud = static_cast<float*>(st.out[5].dev), a.src_idx = static_cast<uint32_t*>(st.out[6].dev);
+    LKCHK(st.upload_clouds(h, a.clouds, a.n_clouds, a.off));
+    a.label = st.out[0], a.kind = st.out[1], a.n = st.out[2], a.cl_size = st.out[3], a.cl_first = st.out[4], a.out_cloud = st.out[5], a.src_idx = st.out[6];
     LKCHK(cluster_run(h, a, total, &n_cl, &n_out));
     st.out[3].count = st.out[4].count = n_cl, st.out[5].count = st.out[6].count = n_out;   // nothing behind the clusters and the kept records is written
     return st.fetch(h);
@@ -1000,12 +1001,11 @@ struct PlanesArgs {   // the arguments both entries share, as the caller gave th
 };
 }  // namespace
 
-// what both entries refuse before anything is launched: lk_clouds_mme(_dev)'s refusals of the clouds and the table, then the entry's own.  *total: records in all
+// what both entries refuse before anything is launched: the clouds' refusals, then the entry's own
 static int planes_check(lk_handle* h, const char* who, const PlanesArgs& a, unsigned int cloud_align, size_t* total) {
     const std::string w = std::string(who) + ": ";
-    lk_mme sink;
-    const MmeArgs m = {a.clouds, a.n_clouds, a.off, 1.0, 4u, a.out ? &sink : nullptr, nullptr, nullptr, nullptr};
-    LKCHK(mme_check(h, who, m, cloud_align, total));
+    LKCHK(clouds_check_args(h, w, a.clouds, a.n_clouds, a.off, a.out, cloud_align));
+    LKCHK(clouds_check_table(h, w, a.n_clouds, a.off, total));
     if (!a.planes) return fail(h, LK_ERR_INVALID, w + "null argument (planes)");
     if (!std::isfinite(a.dist) || !(a.dist > 0.0)) return fail(h, LK_ERR_INVALID, w + "dist must be finite and above 0");
     if (a.n_hyp == 0 || a.n_hyp > LK_PLANES_MAX_HYP) return fail(h, LK_ERR_INVALID, w + "n_hyp is " + std::to_string(a.n_hyp) + ": 1 .. LK_PLANES_MAX_HYP");
@@ -1033,34 +1033,24 @@ static int planes_check(lk_handle* h, const char* who, const PlanesArgs& a, unsi
 // the call behind planes_check, on DEVICE clouds and DEVICE outputs (null: not asked for).  *n_out: records written to out_cloud / src_idx
 static int planes_run(lk_handle* h, const PlanesArgs& a, size_t N, size_t* n_out) {
     const size_t NC = a.n_clouds, NP = NC * a.max_planes;
-    std::vector<unsigned int> used, roff(NC + 1), cfirst(NC + 1, 0u);   // every non-empty cloud; the table from the first record; the score blocks in front of a cloud
-    for (size_t c = 0; c < NC; ++c) {
-        if (a.off[c + 1] > a.off[c]) used.push_back((unsigned int)c);
-        cfirst[c + 1] = cfirst[c] + (unsigned int)((a.off[c + 1] - a.off[c] + LK_PLANES_CHUNK - 1) / LK_PLANES_CHUNK);
-    }
+    const std::vector<unsigned int> used = nonempty_clouds(a.off, NC);
+    std::vector<unsigned int> roff(NC + 1), cfirst(NC + 1, 0u);   // the table from the first record; the score blocks in front of a cloud
+    for (size_t c = 0; c < NC; ++c) cfirst[c + 1] = cfirst[c] + (unsigned int)((a.off[c + 1] - a.off[c] + LK_PLANES_CHUNK - 1) / LK_PLANES_CHUNK);
     for (size_t c = 0; c <= NC; ++c) roff[c] = (unsigned int)(a.off[c] - a.off[0]);
-    const bool places = a.out_off != nullptr, moved = a.out_cloud || a.src_idx;
     unsigned long long* d_off64 = nullptr;
     unsigned int *d_off = nullptr, *d_used = nullptr, *d_status = nullptr, *d_cfirst = nullptr;
     int* d_mm = nullptr;
     LkPlanesCall m = {};
-    LkSorCall s = {};   // the output offsets and the scatter are lk_sor_kernels.h's
-    auto carve = [&](void* base) {
-        LkCarve c(base, 256);
+    C2cTail t(a.clouds, a.off, a.out_cloud, a.out_off, a.src_idx);
+    LKCHK(c2c_carve(h, [&](LkCarve& c) {
         d_off64 = c.take<unsigned long long>(NC + 1), d_off = c.take<unsigned int>(NC + 1), d_used = c.take<unsigned int>(used.size());
         d_cfirst = c.take<unsigned int>(NC + 1), d_status = c.take<unsigned int>(NC), d_mm = c.take<int>(6 * NC);
         m.flag = c.take<unsigned int>(N + 1), m.scan = c.take<unsigned int>(N + 1), m.rem = c.take<float4>(N), m.label = c2c_or_own(c, a.label, N);
         m.score = c.take<unsigned int>(NC * a.n_hyp), m.done = c.take<unsigned int>(NC), m.n_planes = c.take<unsigned int>(NC), m.win_h = c.take<unsigned int>(NC);
         m.win = c.take<LkPlanesHyp>(NC), m.planes = c.take<lk_plane>(NP), m.csum = c.take<double>(6 * NP), m.out = c.take<lk_planes>(NC);
-        s.out_off = c.take<unsigned int>(places ? NC + 1 : 0);
-        return c.total();
-    };
-    const size_t bytes = carve(nullptr);
-    LKCHK(reserve(h, h->c2c, bytes, bytes / 4));
-    carve(h->c2c.p);
-    size_t scan_tmp = 0;   // (before anything is launched: growing the temporary storage waits for the stream)
-    HIPCHK(h, lk_prim_exclusive_scan(nullptr, scan_tmp, m.flag, m.scan, N + 1, h->stream));
-    LKCHK(reserve(h, h->prim_tmp, scan_tmp));
+        t.take(c, NC, N, false), t.c.scan = m.scan;   // the rounds' scan array: free again when the tail runs
+    }));
+    LKCHK(scan_reserve(h, m.flag, m.scan, N + 1));
     HIPCHK(h, hipMemcpyAsync(d_off64, a.off, 8 * (NC + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_off, roff.data(), 4 * (NC + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_cfirst, cfirst.data(), 4 * (NC + 1), hipMemcpyHostToDevice, h->stream));
@@ -1096,26 +1086,14 @@ static int planes_run(lk_handle* h, const PlanesArgs& a, size_t N, size_t* n_out
     LAUNCH(h, "planes_record", hipLaunchKernelGGL(lk_planes_record_kernel, c2c_blocks(NC), dim3(256), 0, h->stream, m));
     std::vector<lk_planes> rec(NC);
     std::vector<lk_plane> prec(NP);
-    std::vector<unsigned int> ooff(places ? NC + 1 : 0);
     HIPCHK(h, hipMemcpyAsync(rec.data(), m.out, sizeof(lk_planes) * NC, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(prec.data(), m.planes, sizeof(lk_plane) * NP, hipMemcpyDeviceToHost, h->stream));
-    if (places) {
-        s.off = m.off, s.n_clouds = m.n_clouds, s.total = m.total, s.flag = m.flag, s.scan = m.scan;
-        s.in = reinterpret_cast<const uint4*>(a.clouds) + a.off[0], s.out_pts = reinterpret_cast<uint4*>(a.out_cloud), s.src_idx = a.src_idx;
-        if (N) LAUNCH(h, "planes_keep", hipLaunchKernelGGL(lk_planes_keep_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
-        tb = h->prim_tmp.cap;
-        LAUNCH(h, "planes_keep_scan", scanned = lk_prim_exclusive_scan(h->prim_tmp.p, tb, m.flag, m.scan, N + 1, h->stream));
-        HIPCHK(h, scanned);
-        LAUNCH(h, "planes_offsets", hipLaunchKernelGGL(lk_sor_offsets_kernel, c2c_blocks(NC + 1), dim3(256), 0, h->stream, s));
-        HIPCHK(h, hipMemcpyAsync(ooff.data(), s.out_off, 4 * (NC + 1), hipMemcpyDeviceToHost, h->stream));
-        if (moved && N) LAUNCH(h, "planes_scatter", hipLaunchKernelGGL(lk_sor_scatter_kernel, c2c_blocks(N), dim3(256), 0, h->stream, s));
-    }
+    if (a.out_off && N) LAUNCH(h, "planes_keep", hipLaunchKernelGGL(lk_planes_keep_kernel, c2c_blocks(N), dim3(256), 0, h->stream, m));
+    LKCHK(t.enqueue(h, m.off, m.flag, NC, N, "planes_keep_scan", "planes_offsets", "planes_scatter"));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     memcpy(a.out, rec.data(), sizeof(lk_planes) * NC);
     memcpy(a.planes, prec.data(), sizeof(lk_plane) * NP);
-    if (places)
-        for (size_t c = 0; c <= NC; ++c) a.out_off[c] = ooff[c];
-    if (n_out) *n_out = places ? ooff[NC] : 0;
+    t.finish(n_out);
     return LK_OK;
 }
 
@@ -1139,11 +1117,9 @@ int lk_clouds_planes(lk_handle* h, const float* clouds, size_t n_clouds, const u
     size_t total = 0, n_out = 0;
     LKCHK(planes_check(h, "lk_clouds_planes", a, 4, &total));
     C2cStage st;
-    st.in = {{clouds, off, n_clouds}};
     st.out = {{label, 4, total}, {out_cloud, 16, total}, {src_idx, 4, total}};
-    LKCHK(st.upload(h));
-    a.clouds = reinterpret_cast<const float*>(st.in[0].dev), a.off = st.in[0].rel.data();
-    a.label = static_cast<uint32_t*>(st.out[0].dev), a.out_cloud = static_cast<float*>(st.out[1].dev), a.src_idx = static_cast<uint32_t*>(st.out[2].dev);
+    LKCHK(st.upload_clouds(h, a.clouds, a.n_clouds, a.off));
+    a.label = st.out[0], a.out_cloud = st.out[1], a.src_idx = st.out[2];
     LKCHK(planes_run(h, a, total, &n_out));
     st.out[1].count = st.out[2].count = n_out;   // nothing behind the kept records is written
     return st.fetch(h);

@@ -201,3 +201,29 @@ __global__ void __launch_bounds__(256) lk_c2c_reduce_kernel(LkC2cQuery a) {
     r.worst = none ? 0u : p.worst, r.status = st;
     a.out[k] = r;
 }
+
+// The compaction tail of the families that write kept records out as clouds (outlier filter, clustering, plane extraction): each brings its own keep
+// words, lk_prim_exclusive_scan over them gives every kept record its place, and these two kernels do the rest.
+struct LkCompactCall {
+    const unsigned int* off;    // [n_clouds + 1], counted from the first record
+    unsigned int n_clouds, total;
+    const unsigned int* flag;   // [total + 1] keep words, the last one 0
+    unsigned int* scan;         // [total + 1] their exclusive prefix sum
+    unsigned int* out_off;      // [n_clouds + 1]
+    const uint4* in;            // the call's first record: input order, [total]
+    uint4* out_pts;             // may be null
+    unsigned int* src_idx;      // may be null
+};
+// the output offsets: kept records in front of every cloud's first record
+__global__ void __launch_bounds__(256) lk_c2c_compact_offsets_kernel(LkCompactCall a) {
+    const unsigned int c = blockIdx.x * 256u + threadIdx.x;
+    if (c <= a.n_clouds) a.out_off[c] = a.scan[a.off[c]];
+}
+// the kept records to their places, all 16 bytes as they are (four 32-bit words: a NaN payload survives), and their indices within their input clouds
+__global__ void __launch_bounds__(256) lk_c2c_compact_scatter_kernel(LkCompactCall a) {
+    const unsigned int g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= a.total || !a.flag[g]) return;
+    const unsigned int j = a.scan[g];
+    if (a.out_pts) a.out_pts[j] = a.in[g];
+    if (a.src_idx) a.src_idx[j] = g - a.off[lk_c2c_cloud_of(a.off, a.n_clouds, g)];
+}

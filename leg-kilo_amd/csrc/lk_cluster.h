@@ -1,9 +1,9 @@
 // lk_cluster.h - the arithmetic of the clustering of map clouds (lk_clouds_cluster_dev, lk_cluster_kernels.h) that the device route and its CPU twin
-// (tools/probes/cluster_host.cc, tests/test_cluster_host.py) share: ONE walk of a point through the sorted cells of its own cloud with a visitor per
-// candidate record, the three visitors (count, link, nearest core), and the union-find over the core points.
+// (tools/probes/cluster_host.cc, tests/test_cluster_host.py) share: the three visitors (count, link, nearest core) that lk_c2c.h's walk calls per
+// candidate record, and the union-find over the core points.
 //
-// The RESULT is defined without a grid (include/legkilo_hip.h): every decision is lk_c2c_d2(i, j) <= reach * reach, and lk_c2c.h's argument holds
-// word for word - every record within reach lies in the 27 cells around the point's own.  Everything here is whole numbers and comparisons of d2,
+// The RESULT is defined without a grid (include/legkilo_hip.h): every decision is lk_c2c_d2(i, j) <= reach * reach, and by the argument at the head
+// of lk_c2c.h every record within reach lies in the 27 cells that lk_c2c_walk visits.  Everything here is whole numbers and comparisons of d2,
 // so the walk's order leaves no trace: n_i is a count, the nearest core candidate minimises (d2, index), and the union-find ends with the same roots
 // whatever order the unions arrive in.
 //
@@ -75,38 +75,8 @@ LK_C2C_HD void lk_cluster_unite(unsigned int* parent, unsigned int x, unsigned i
     }
 }
 
-// One point of a cloud against the cloud itself: lk_mme_walk's loops - the same 27 cells and nine lower bounds - with a visitor in the place of
-// lk_mme_add.  `keys` - the cloud's n cell keys in ascending order, `recs` - its records in that order.  visit(a, r, d2) is called for every record
-// r at sorted place a of the 27 cells, the query itself included.  *seen (may be null): records visited.
-template <class V>
-LK_C2C_HD void lk_cluster_walk(float qx, float qy, float qz, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n, V& visit,
-                               unsigned int* seen) {
-    unsigned int count = 0;
-    long long lo[3], hi[3];
-    const bool any = lk_c2c_axis(qx, g.edge, g.mn[0], g.dv[0], &lo[0], &hi[0]) & lk_c2c_axis(qy, g.edge, g.mn[1], g.dv[1], &lo[1], &hi[1]) &
-                     lk_c2c_axis(qz, g.edge, g.mn[2], g.dv[2], &lo[2], &hi[2]);
-    if (any && n) {
-        for (long long i2 = lo[2]; i2 <= hi[2]; ++i2) {
-            for (long long i1 = lo[1]; i1 <= hi[1]; ++i1) {
-                const long long row = i1 * g.dv[0] + i2 * (long long)g.dv[0] * g.dv[1], k0 = row + lo[0], k1 = row + hi[0];
-                unsigned int a = 0, b = n;   // the first record with key >= k0
-                while (a < b) {
-                    const unsigned int m = a + (b - a) / 2;
-                    if ((long long)keys[m] < k0) a = m + 1;
-                    else b = m;
-                }
-                for (; a < n && (long long)keys[a] <= k1; ++a) {
-                    const LkC2cRec r = recs[a];
-                    visit(a, r, lk_c2c_d2(qx, qy, qz, r.x, r.y, r.z));
-                    ++count;
-                }
-            }
-        }
-    }
-    if (seen) *seen = count;
-}
-
-// n_i: the records within reach, the point itself and its duplicates among them
+// The visitors of lk_c2c_walk, one point of a cloud against the cloud itself (the walk calls them for every record of the 27 cells, the query itself
+// included).  n_i: the records within reach, the point itself and its duplicates among them
 struct LkClusterCount {
     double reach2;
     unsigned int n;

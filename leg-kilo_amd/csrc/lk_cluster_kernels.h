@@ -14,7 +14,7 @@
 //                             bits), at a root the cluster's first core index;
 //   lk_cluster_record_kernel  one block per cloud: the counts, `largest` with its tie rule, the clusters in bounds and the one that is kept under
 //                             LK_CLUSTER_KEEP_LARGEST;
-//   lk_cluster_flag_kernel    a keep word per record; the scan, the output offsets and the scatter behind it are lk_sor_kernels.h's.
+//   lk_cluster_flag_kernel    a keep word per record; the scan, the output offsets and the scatter behind it are lk_c2c_kernels.h's compaction tail.
 // DESIGN.md section 4q says what was measured.
 #pragma once
 #include "lk_cluster.h"
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) lk_cluster_count_kernel(LkClusterCall a) 
     if (a.status[c] == 0u) {
         const LkC2cRec q = a.recs[g];
         LkClusterCount v = {a.reach2, 0u};
-        lk_cluster_walk(q.x, q.y, q.z, a.grid[c], a.keys + b, a.recs + b, a.off[c + 1] - b, v, nullptr);
+        lk_c2c_walk(q.x, q.y, q.z, a.grid[c], a.keys + b, a.recs + b, a.off[c + 1] - b, v, nullptr);
         pos = b + q.idx, n = v.n, core = lk_cluster_is_core(n, a.min_pts);
     }
     a.n[pos] = n, a.kind[pos] = core ? 2 : 0, a.core[g] = core ? 1 : 0, a.parent[pos] = pos;
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256) lk_cluster_link_kernel(LkClusterCall a) {
     const unsigned int c = lk_c2c_cloud_of(a.off, a.n_clouds, g), b = a.off[c];
     const LkC2cRec q = a.recs[g];
     LkClusterLink v = {a.reach2, a.core + b, a.parent, b, q.idx};
-    lk_cluster_walk(q.x, q.y, q.z, a.grid[c], a.keys + b, a.recs + b, a.off[c + 1] - b, v, nullptr);
+    lk_c2c_walk(q.x, q.y, q.z, a.grid[c], a.keys + b, a.recs + b, a.off[c + 1] - b, v, nullptr);
 }
 
 __global__ void __launch_bounds__(256) lk_cluster_assign_kernel(LkClusterCall a) {
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(256) lk_cluster_assign_kernel(LkClusterCall a)
             root = lk_cluster_root(a.parent, pos);
         } else {
             LkClusterNearest v = {a.reach2, a.core + b, INFINITY, LK_CLUSTER_NONE};
-            lk_cluster_walk(q.x, q.y, q.z, a.grid[c], a.keys + b, a.recs + b, a.off[c + 1] - b, v, nullptr);
+            lk_c2c_walk(q.x, q.y, q.z, a.grid[c], a.keys + b, a.recs + b, a.off[c + 1] - b, v, nullptr);
             if (v.j != LK_CLUSTER_NONE) root = lk_cluster_root(a.parent, b + v.j), a.kind[pos] = 1;
         }
     }

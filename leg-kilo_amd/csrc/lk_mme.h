@@ -1,12 +1,12 @@
 // lk_mme.h - the arithmetic of the reference-free map scores (lk_clouds_mme_dev, lk_mme_kernels.h) that the device route and its CPU twin
 // (tools/probes/mme_host.cc, tests/test_mme_host.py) share: the second moments of a point's neighbourhood about the point itself, the covariance with
-// its determinant, the flatness floor, the entropy and the smallest eigenvalue, and the walk of one point through the sorted cells of its own cloud.
+// its determinant, the flatness floor, the entropy and the smallest eigenvalue, and the visitor that sums them on lk_c2c.h's walk.
 //
 // The RESULT is defined without a grid (include/legkilo_hip.h): N_i holds every record j of the cloud with lk_c2c_d2(i, j) <= r * r, i itself among
-// them.  The grid is lk_c2c.h's with the radius as the reach, and the argument there holds word for word: every member lies in the 27 cells around
-// the point's own.  The offsets u_j = p_j - p_i are bounded by r whatever the cloud's coordinates, so the sums carry rounding of order 2^-53 r^2.
-// The order of a sum is the walk's: rows of cells in ascending (z, y), keys ascending inside a row, records of equal key in input order - a function
-// of the cloud's own records and of the radius.
+// them.  The grid and the walk are lk_c2c.h's with the radius as the reach (lk_c2c_walk; the argument at the head of that file is why every member
+// lies in the 27 cells around the point's own).  The offsets u_j = p_j - p_i are bounded by r whatever the cloud's coordinates, so the sums carry
+// rounding of order 2^-53 r^2.  The order of a sum is the walk's: rows of cells in ascending (z, y), keys ascending inside a row, records of equal
+// key in input order - a function of the cloud's own records and of the radius.
 // No FMA is spelled out and the units that include this build with -ffp-contract=off.  Plain C++ that compiles for the host as it stands.
 #pragma once
 #include "lk_c2c.h"
@@ -62,33 +62,17 @@ LK_C2C_HD void lk_mme_finish(const LkMmeAcc& a, unsigned int min_pts, unsigned i
     *h = 0.5 * (8.5136311992280364508 + log(det));   // 3 ln(2 pi e) = 8.51363119922803645...
 }
 
-// One point of a cloud against the cloud itself: `keys` - the cloud's n cell keys in ascending order, `recs` - its records in that order.  The same
-// 27 cells and nine lower bounds as lk_c2c_search, but every record within reach is ADDED where the search keeps the minimum.  *seen (may be null):
-// records whose distance was evaluated.
+// One point of a cloud against the cloud itself: lk_c2c_walk with every record within reach ADDED where the search keeps the minimum (lk_mme_add
+// takes its own d2: the walk's expression, the walk's bits).  *seen (may be null): records whose distance was evaluated.
+struct LkMmeVisit {
+    LkMmeAcc* acc;
+    float qx, qy, qz;
+    double reach2;
+    LK_C2C_HD void operator()(unsigned int, const LkC2cRec& r, double) { lk_mme_add(acc, qx, qy, qz, r.x, r.y, r.z, reach2); }
+};
 LK_C2C_HD void lk_mme_walk(float qx, float qy, float qz, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n, double reach2,
                            LkMmeAcc* acc, unsigned int* seen) {
-    unsigned int count = 0;
-    long long lo[3], hi[3];
     lk_mme_clear(acc);
-    const bool any = lk_c2c_axis(qx, g.edge, g.mn[0], g.dv[0], &lo[0], &hi[0]) & lk_c2c_axis(qy, g.edge, g.mn[1], g.dv[1], &lo[1], &hi[1]) &
-                     lk_c2c_axis(qz, g.edge, g.mn[2], g.dv[2], &lo[2], &hi[2]);
-    if (any && n) {
-        for (long long i2 = lo[2]; i2 <= hi[2]; ++i2) {
-            for (long long i1 = lo[1]; i1 <= hi[1]; ++i1) {
-                const long long row = i1 * g.dv[0] + i2 * (long long)g.dv[0] * g.dv[1], k0 = row + lo[0], k1 = row + hi[0];
-                unsigned int a = 0, b = n;   // the first record with key >= k0
-                while (a < b) {
-                    const unsigned int m = a + (b - a) / 2;
-                    if ((long long)keys[m] < k0) a = m + 1;
-                    else b = m;
-                }
-                for (; a < n && (long long)keys[a] <= k1; ++a) {
-                    const LkC2cRec r = recs[a];
-                    lk_mme_add(acc, qx, qy, qz, r.x, r.y, r.z, reach2);
-                    ++count;
-                }
-            }
-        }
-    }
-    if (seen) *seen = count;
+    LkMmeVisit v = {acc, qx, qy, qz, reach2};
+    lk_c2c_walk(qx, qy, qz, g, keys, recs, n, v, seen);
 }

@@ -16,7 +16,7 @@
 //   lk_planes_mark_kernel     one thread per record: the winner's test again, the label, the alive word cleared.
 // Behind the rounds lk_planes_refit_kernel, one block per (cloud, plane), sums the plane's records in input order - lane-strided partial sums, then a
 // fixed tree, lk_sor_stats_kernel's scheme, the centroid first and the centred products second - lk_planes_fit_kernel, one thread per plane, turns the
-// sums into the coefficients (lk_eig3.h), and lk_planes_record_kernel writes the cloud's record.  The kept records leave through lk_sor_kernels.h's offsets and scatter kernels.  Inside a kernel no thread waits for another workgroup.
+// sums into the coefficients (lk_eig3.h), and lk_planes_record_kernel writes the cloud's record.  The kept records leave through lk_c2c_kernels.h's compaction tail.  Inside a kernel no thread waits for another workgroup.
 // DESIGN.md section 4r says what was measured.
 #pragma once
 #include "lk_planes.h"

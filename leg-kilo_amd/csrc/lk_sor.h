@@ -1,9 +1,9 @@
 // lk_sor.h - the arithmetic of the statistical outlier filter of map clouds (lk_clouds_sor_dev, lk_sor_kernels.h) that the device route and its CPU
-// twin (tools/probes/sor_host.cc, tests/test_sor_host.py) share: the list of the k smallest squared distances of a point, the walk of one point
-// through the sorted cells of its own cloud that fills it, the mean neighbour distance, the threshold and the keep test.
+// twin (tools/probes/sor_host.cc, tests/test_sor_host.py) share: the list of the k smallest squared distances of a point, the visitor that fills it
+// on lk_c2c.h's walk, the mean neighbour distance, the threshold and the keep test.
 //
 // The RESULT is defined without a grid (include/legkilo_hip.h): the candidates of point i are the records j != i of its cloud with
-// lk_c2c_d2(i, j) <= reach * reach, and lk_c2c.h's argument holds word for word - every candidate lies in the 27 cells around the point's own.  The k
+// lk_c2c_d2(i, j) <= reach * reach, and by the argument at the head of lk_c2c.h every candidate lies in the 27 cells that lk_c2c_walk visits.  The k
 // smallest of a multiset do not depend on the order in which its members arrive, so the walk's order leaves no trace in dbar_i.
 // The list is LkSorList<CAP>: CAP doubles in ascending order, +inf where nothing was entered yet.  Every index into it is a compile-time constant
 // (the loops below unroll fully), so on the device it lives in registers; a list indexed by a runtime k would go to scratch.  CAP >= k, and the
@@ -39,16 +39,19 @@ LK_C2C_HD void lk_sor_insert(LkSorList<CAP>* l, double d) {
     }
     l->v[0] = d < l->v[0] ? d : l->v[0];
 }
-// record r (index ridx within the cloud) against the query q (index qidx): a candidate when it is another record - by INDEX, a duplicate of q is one at
-// distance 0 - and lk_c2c_d2 <= reach2; it enters the list when it is below the list's last place
+// the walk's visitor.  Record r against the query (index qidx within the cloud): a candidate when it is another record - by INDEX, a duplicate of
+// the query is one at distance 0 - and d2 <= reach2; it enters the list when it is below the list's last place
 template <int CAP>
-LK_C2C_HD void lk_sor_add(LkSorList<CAP>* l, float qx, float qy, float qz, unsigned int qidx, float rx, float ry, float rz, unsigned int ridx, double reach2) {
-    if (ridx == qidx) return;
-    const double d2 = lk_c2c_d2(qx, qy, qz, rx, ry, rz);
-    if (!lk_c2c_matched(d2, reach2)) return;
-    l->cnt += 1u;
-    if (d2 < l->v[CAP - 1]) lk_sor_insert(l, d2);
-}
+struct LkSorVisit {
+    LkSorList<CAP>* l;
+    unsigned int qidx;
+    double reach2;
+    LK_C2C_HD void operator()(unsigned int, const LkC2cRec& r, double d2) {
+        if (r.idx == qidx || !lk_c2c_matched(d2, reach2)) return;
+        l->cnt += 1u;
+        if (d2 < l->v[CAP - 1]) lk_sor_insert(l, d2);
+    }
+};
 // dbar of a point from its list: NaN when it has fewer than k candidates (ISOLATED), else the mean of the roots of the k smallest d2, the sum taken
 // in ascending order, one term after the other
 template <int CAP>
@@ -65,34 +68,12 @@ LK_C2C_HD double lk_sor_sigma(double ss, unsigned long long n_s) { return n_s > 
 LK_C2C_HD double lk_sor_thr(double mu, double sigma, double n_sigma) { return n_sigma == INFINITY ? INFINITY : mu + n_sigma * sigma; }
 LK_C2C_HD bool lk_sor_kept(double dbar, double thr) { return dbar <= thr; }   // (false for an isolated point's NaN, and under a status cloud's NaN thr)
 
-// One point of a cloud against the cloud itself: lk_mme_walk's loops - the same 27 cells and nine lower bounds - with lk_sor_add in the place of
-// lk_mme_add.  `keys` - the cloud's n cell keys in ascending order, `recs` - its records in that order.  *seen (may be null): records whose distance
-// was evaluated or that were the query itself.
+// One point of a cloud against the cloud itself: lk_c2c_walk with that visitor.  *seen (may be null): records the walk visited, the query itself
+// among them.
 template <int CAP>
 LK_C2C_HD void lk_sor_walk(float qx, float qy, float qz, unsigned int qidx, const LkC2cGrid& g, const unsigned int* keys, const LkC2cRec* recs, unsigned int n,
                            double reach2, LkSorList<CAP>* list, unsigned int* seen) {
-    unsigned int count = 0;
-    long long lo[3], hi[3];
     lk_sor_clear(list);
-    const bool any = lk_c2c_axis(qx, g.edge, g.mn[0], g.dv[0], &lo[0], &hi[0]) & lk_c2c_axis(qy, g.edge, g.mn[1], g.dv[1], &lo[1], &hi[1]) &
-                     lk_c2c_axis(qz, g.edge, g.mn[2], g.dv[2], &lo[2], &hi[2]);
-    if (any && n) {
-        for (long long i2 = lo[2]; i2 <= hi[2]; ++i2) {
-            for (long long i1 = lo[1]; i1 <= hi[1]; ++i1) {
-                const long long row = i1 * g.dv[0] + i2 * (long long)g.dv[0] * g.dv[1], k0 = row + lo[0], k1 = row + hi[0];
-                unsigned int a = 0, b = n;   // the first record with key >= k0
-                while (a < b) {
-                    const unsigned int m = a + (b - a) / 2;
-                    if ((long long)keys[m] < k0) a = m + 1;
-                    else b = m;
-                }
-                for (; a < n && (long long)keys[a] <= k1; ++a) {
-                    const LkC2cRec r = recs[a];
-                    lk_sor_add(list, qx, qy, qz, qidx, r.x, r.y, r.z, r.idx, reach2);
-                    ++count;
-                }
-            }
-        }
-    }
-    if (seen) *seen = count;
+    LkSorVisit<CAP> v = {list, qidx, reach2};
+    lk_c2c_walk(qx, qy, qz, g, keys, recs, n, v, seen);
 }

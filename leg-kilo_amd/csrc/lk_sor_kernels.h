@@ -7,9 +7,9 @@
 //                             registers (lk_sor.h); CAP is chosen from k on the host.  cnt_i and dbar_i go to position rec.idx - input order;
 //   lk_sor_stats_kernel       one block per cloud over dbar in input order, lk_mme_reduce_kernel's scheme - lane-strided partial sums, then a fixed
 //                             tree - twice: the mean first, the centred squares second; then the counts under the threshold, and the record;
-//   lk_sor_flag_kernel        a keep word per record (and the caller's d_keep byte); lk_prim_exclusive_scan over all of them gives every kept
-//                             record its place and, read at the cloud starts, the offsets of the output clouds (lk_sor_offsets_kernel);
-//   lk_sor_scatter_kernel     the kept records to their places, all 16 bytes as they are, and their indices within their input clouds.
+//   lk_sor_flag_kernel        a keep word per record (and the caller's d_keep byte).  What follows is lk_c2c_kernels.h's compaction tail, shared
+//                             with clustering and plane extraction: lk_prim_exclusive_scan over the keep words gives every kept record its place
+//                             and, read at the cloud starts, the offsets of the output clouds; the scatter moves the kept records there.
 // DESIGN.md section 4p says what was measured.
 #pragma once
 #include "lk_sor.h"
@@ -20,16 +20,11 @@ struct LkSorCall {
     const LkC2cGrid* grid;        // [n_clouds]
     const unsigned int* keys;     // sorted, all clouds
     const LkC2cRec* recs;         // in that order
-    const uint4* in;              // the call's first record: input order, [total]
     unsigned int* cnt;            // per-point arrays, input order, [total]; cnt and keep may be null
     double* dbar;
     unsigned char* keep;
     unsigned int* flag;           // [total + 1] keep words, the last one 0
-    unsigned int* scan;           // [total + 1] their exclusive prefix sum
     double* thr;                  // [n_clouds]
-    unsigned int* out_off;        // [n_clouds + 1]
-    uint4* out_pts;               // may be null
-    unsigned int* src_idx;        // may be null
     double reach2, n_sigma;
     unsigned int n_clouds, k, total;
     lk_sor* out;                  // [n_clouds], device
@@ -140,16 +135,4 @@ __global__ void __launch_bounds__(256) lk_sor_flag_kernel(LkSorCall a) {
     const unsigned int kept = lk_sor_kept(a.dbar[g], a.thr[c]) ? 1u : 0u;
     a.flag[g] = kept;
     if (a.keep) a.keep[g] = (unsigned char)kept;
-}
-// the output offsets: kept records in front of every cloud's first record
-__global__ void __launch_bounds__(256) lk_sor_offsets_kernel(LkSorCall a) {
-    const unsigned int c = blockIdx.x * 256u + threadIdx.x;
-    if (c <= a.n_clouds) a.out_off[c] = a.scan[a.off[c]];
-}
-__global__ void __launch_bounds__(256) lk_sor_scatter_kernel(LkSorCall a) {
-    const unsigned int g = blockIdx.x * 256u + threadIdx.x;
-    if (g >= a.total || !a.flag[g]) return;
-    const unsigned int j = a.scan[g];
-    if (a.out_pts) a.out_pts[j] = a.in[g];
-    if (a.src_idx) a.src_idx[j] = g - a.off[lk_c2c_cloud_of(a.off, a.n_clouds, g)];
 }

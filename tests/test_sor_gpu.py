@@ -204,6 +204,15 @@ def test_null_outputs_host_entry_and_poisoned_pools(g, hip_lib, main_group, clea
         assert res.tobytes() == full["res"].tobytes() and np.array_equal(off, full["off"])
     finally:
         only_off.free()
+    edge = [sc.CASES[n]["cloud"] for n in ("s1", "s0", "s257")]         # an empty cloud between one record and 257, the offsets alone
+    _, edge_full = run_once(g, edge, *MAIN)
+    edge_off = Call(g, edge, *MAIN, want=(False,) * 5)
+    try:
+        res, off = g.clouds_sor_dev(edge_off.gc.ptr, edge_off.off, *MAIN, want_off=True)
+        assert res.tobytes() == edge_full["res"].tobytes() and np.array_equal(off, edge_full["off"]) and off[1] == off[2]
+        assert np.array_equal(np.diff(off.astype(np.int64)), res["n_kept"].astype(np.int64)) and res["n_points"].tolist() == [1, 0, 257]
+    finally:
+        edge_off.free()
     rec, roff = records(clouds)
     hres, hout, hoff, hsrc, hkeep, hcnt, hdbar = g.clouds_sor(rec, roff, *MAIN, want_points=True)
     assert hres.tobytes() == full["res"].tobytes() and np.array_equal(hoff, full["off"]) and np.array_equal(hout.view(np.uint32), full["out"])

@@ -12,22 +12,14 @@
 // point; j = 4294967295 and d2 = inf where the point is unmatched.  A truncated file is an error (exit status 2).
 // -DLK_ALIGN_NO_GUARD: see lk_align.h - the search without the range guard; the test expects the sanitizers to stop the sheared case (guard_t0).
 #include "../../leg-kilo_amd/csrc/lk_align.h"
+#include "c2c_index_host.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
-#include <algorithm>
-#include <utility>
-#include <vector>
 
 static bool read_exact(FILE* f, void* dst, size_t bytes) { return bytes == 0 || fread(dst, 1, bytes, f) == bytes; }
 
-struct Index {
-    LkC2cGrid g;
-    std::vector<unsigned int> keys;
-    std::vector<LkC2cRec> recs;
-};
-
-static void search_all(const double* T, const std::vector<float>& q, double max_dist, const Index& x, std::vector<unsigned int>& j, std::vector<double>& d2) {
+static void search_all(const double* T, const std::vector<float>& q, double max_dist, const HostIndex& x, std::vector<unsigned int>& j, std::vector<double>& d2) {
     const double reach2 = lk_c2c_reach2(max_dist);
     for (size_t i = 0; i < j.size(); ++i)
         lk_align_search(T, q[3 * i], q[3 * i + 1], q[3 * i + 2], max_dist, x.g, x.keys.data(), x.recs.data(), (unsigned int)x.recs.size(), reach2, &j[i], &d2[i]);
@@ -63,27 +55,10 @@ int main(int argc, char** argv) {
             fprintf(stderr, "align_host: truncated cloud\n");
             return 2;
         }
-        unsigned int status = 0;
-        for (const std::vector<float>* c : {&q, &r})
-            for (float v : *c) status |= !isfinite(v) ? 1u : lk_c2c_out_of_range(v, max_dist) ? 2u : 0u;
+        unsigned int status = host_status(q, max_dist) | host_status(r, max_dist);
         if (!lk_align_finite12(T)) status |= 16u;
-        Index x;
-        lk_c2c_grid_of_nothing(max_dist, &x.g);
-        x.keys.resize(nr), x.recs.resize(nr);
-        if (!(status & 3u) && nr) {
-            float lo[3], hi[3];
-            for (int c = 0; c < 3; ++c) lo[c] = hi[c] = r[c];
-            for (unsigned int i = 0; i < nr; ++i)
-                for (int c = 0; c < 3; ++c) lo[c] = std::min(lo[c], r[3 * i + c]), hi[c] = std::max(hi[c], r[3 * i + c]);
-            lk_c2c_grid(lo, hi, max_dist, &x.g);
-            std::vector<std::pair<unsigned int, unsigned int>> order(nr);
-            for (unsigned int i = 0; i < nr; ++i) order[i] = {lk_c2c_key(r[3 * i], r[3 * i + 1], r[3 * i + 2], x.g), i};
-            std::sort(order.begin(), order.end());
-            for (unsigned int i = 0; i < nr; ++i) {
-                const unsigned int s = order[i].second;
-                x.keys[i] = order[i].first, x.recs[i] = LkC2cRec{r[3 * s], r[3 * s + 1], r[3 * s + 2], s};
-            }
-        }
+        HostIndex x;
+        host_index(r, nr, max_dist, !(status & 3u), x);
         std::vector<unsigned int> j(nq, 0xffffffffu), j_first(nq, 0xffffffffu);
         std::vector<double> d2(nq, INFINITY);
         uint64_t iters = 0, n_first = 0;

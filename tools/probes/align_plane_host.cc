@@ -16,38 +16,12 @@
 // Test aids: -DLK_ALIGN_PLANE_ORIGIN, -DLK_ALIGN_PLANE_NO_ORTHO (lk_align_plane.h), -DLK_NORMALS_SIGN_F32 (lk_normals.h).
 #include "../../leg-kilo_amd/csrc/lk_align_plane.h"
 #include "../../leg-kilo_amd/csrc/lk_normals.h"
+#include "c2c_index_host.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
-#include <algorithm>
-#include <utility>
-#include <vector>
 
 static bool read_exact(FILE* f, void* dst, size_t bytes) { return bytes == 0 || fread(dst, 1, bytes, f) == bytes; }
-
-struct Index {
-    LkC2cGrid g;
-    std::vector<unsigned int> keys;
-    std::vector<LkC2cRec> recs;
-};
-// the sorted records of one cloud with `reach` as the cell edge (nothing for a cloud with a status or without points)
-static void build_index(const std::vector<float>& r, unsigned int nr, double reach, bool ok, Index& x) {
-    lk_c2c_grid_of_nothing(reach, &x.g);
-    x.keys.resize(nr), x.recs.resize(nr);
-    if (!ok || !nr) return;
-    float lo[3], hi[3];
-    for (int c = 0; c < 3; ++c) lo[c] = hi[c] = r[c];
-    for (unsigned int i = 0; i < nr; ++i)
-        for (int c = 0; c < 3; ++c) lo[c] = std::min(lo[c], r[3 * i + c]), hi[c] = std::max(hi[c], r[3 * i + c]);
-    lk_c2c_grid(lo, hi, reach, &x.g);
-    std::vector<std::pair<unsigned int, unsigned int>> order(nr);
-    for (unsigned int i = 0; i < nr; ++i) order[i] = {lk_c2c_key(r[3 * i], r[3 * i + 1], r[3 * i + 2], x.g), i};
-    std::sort(order.begin(), order.end());
-    for (unsigned int i = 0; i < nr; ++i) {
-        const unsigned int s = order[i].second;
-        x.keys[i] = order[i].first, x.recs[i] = LkC2cRec{r[3 * s], r[3 * s + 1], r[3 * s + 2], s};
-    }
-}
 
 static int run_normals(FILE* f) {
     for (;;) {
@@ -66,10 +40,9 @@ static int run_normals(FILE* f) {
             fprintf(stderr, "align_plane_host: truncated cloud\n");
             return 2;
         }
-        unsigned int status = 0;
-        for (float v : p) status |= !isfinite(v) ? 1u : lk_c2c_out_of_range(v, radius) ? 2u : 0u;
-        Index x;
-        build_index(p, n, radius, !status, x);
+        const unsigned int status = host_status(p, radius);
+        HostIndex x;
+        host_index(p, n, radius, !status, x);
         const double reach2 = lk_c2c_reach2(radius);
         std::vector<unsigned int> cnt(n, 0u);
         std::vector<float> rec(4 * (size_t)n, NAN);
@@ -109,12 +82,10 @@ static int run_align(FILE* f) {
             fprintf(stderr, "align_plane_host: truncated cloud\n");
             return 2;
         }
-        unsigned int status = 0;
-        for (const std::vector<float>* c : {&q, &r})
-            for (float v : *c) status |= !isfinite(v) ? 1u : lk_c2c_out_of_range(v, max_dist) ? 2u : 0u;
+        unsigned int status = host_status(q, max_dist) | host_status(r, max_dist);
         if (!lk_align_finite12(T)) status |= 16u;
-        Index x;
-        build_index(r, nr, max_dist, !(status & 3u), x);
+        HostIndex x;
+        host_index(r, nr, max_dist, !(status & 3u), x);
         const double reach2 = lk_c2c_reach2(max_dist);
         std::vector<unsigned int> j(nq, 0xffffffffu), j_first(nq, 0xffffffffu);
         std::vector<double> d2(nq, INFINITY);

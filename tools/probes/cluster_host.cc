@@ -1,6 +1,6 @@
 // Host build of leg-kilo_amd/csrc/lk_cluster.h for tests/test_cluster_host.py - a program of its own, the CPU twin of the device route of
 // lk_clouds_cluster_dev (lk_cluster_kernels.h): bounds, lk_c2c_grid with the reach as the cell edge, a key per record, the records sorted by (key,
-// index) - std::sort in the place of the stable radix sort - then the kernels' phases one sorted record after the other: lk_cluster_walk with the
+// index) - std::sort in the place of the stable radix sort - then the kernels' phases one sorted record after the other: lk_c2c_walk with the
 // count visitor, with the link visitor over the union-find, the roots and the nearest core candidate of every other point, a number per root in
 // ascending order, the sizes, the record and the keep flags.
 //   g++ -O1 -g -ffp-contract=off -fsanitize=address,undefined -o cluster_host cluster_host.cc
@@ -13,12 +13,10 @@
 #include <math.h>
 #include <cmath>
 #include "../../leg-kilo_amd/csrc/lk_cluster.h"
+#include "c2c_index_host.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
-#include <algorithm>
-#include <utility>
-#include <vector>
 
 static bool read_exact(FILE* f, void* dst, size_t bytes) { return bytes == 0 || fread(dst, 1, bytes, f) == bytes; }
 
@@ -48,26 +46,12 @@ int main(int argc, char** argv) {
             fprintf(stderr, "cluster_host: truncated cloud\n");
             return 2;
         }
-        unsigned int status = 0;
-        for (float v : p) status |= !isfinite(v) ? 1u : lk_c2c_out_of_range(v, reach) ? 2u : 0u;
-        LkC2cGrid g;
-        lk_c2c_grid_of_nothing(reach, &g);
-        std::vector<unsigned int> keys(n);
-        std::vector<LkC2cRec> recs(n);
-        if (!status && n) {
-            float lo[3], hi[3];
-            for (int c = 0; c < 3; ++c) lo[c] = hi[c] = p[c];
-            for (unsigned int i = 0; i < n; ++i)
-                for (int c = 0; c < 3; ++c) lo[c] = std::min(lo[c], p[3 * i + c]), hi[c] = std::max(hi[c], p[3 * i + c]);
-            lk_c2c_grid(lo, hi, reach, &g);
-            std::vector<std::pair<unsigned int, unsigned int>> order(n);
-            for (unsigned int i = 0; i < n; ++i) order[i] = {lk_c2c_key(p[3 * i], p[3 * i + 1], p[3 * i + 2], g), i};
-            std::sort(order.begin(), order.end());
-            for (unsigned int i = 0; i < n; ++i) {
-                const unsigned int s = order[i].second;
-                keys[i] = order[i].first, recs[i] = LkC2cRec{p[3 * s], p[3 * s + 1], p[3 * s + 2], s};
-            }
-        }
+        const unsigned int status = host_status(p, reach);
+        HostIndex x;
+        host_index(p, n, reach, !status, x);
+        const LkC2cGrid& g = x.g;
+        const std::vector<unsigned int>& keys = x.keys;
+        const std::vector<LkC2cRec>& recs = x.recs;
         printf("cloud %u status %u edge %a doublings %d cells %d %d %d\n", n, status, g.edge, g.doublings, g.dv[0], g.dv[1], g.dv[2]);
         const double reach2 = lk_c2c_reach2(reach);
         std::vector<unsigned int> cnt(n, 0u), seen(n, 0u), parent(n), root(n, LK_CLUSTER_NONE);
@@ -77,14 +61,14 @@ int main(int argc, char** argv) {
             for (unsigned int s = 0; s < n; ++s) {   // count
                 const LkC2cRec q = recs[s];
                 LkClusterCount v = {reach2, 0u};
-                lk_cluster_walk(q.x, q.y, q.z, g, keys.data(), recs.data(), n, v, &seen[q.idx]);
+                lk_c2c_walk(q.x, q.y, q.z, g, keys.data(), recs.data(), n, v, &seen[q.idx]);
                 cnt[q.idx] = v.n, core[s] = lk_cluster_is_core(v.n, min_pts) ? 1 : 0, kind[q.idx] = core[s] ? 2 : 0;
             }
             for (unsigned int s = 0; s < n; ++s) {   // link
                 if (!core[s]) continue;
                 const LkC2cRec q = recs[s];
                 LkClusterLink v = {reach2, core.data(), parent.data(), 0u, q.idx};
-                lk_cluster_walk(q.x, q.y, q.z, g, keys.data(), recs.data(), n, v, nullptr);
+                lk_c2c_walk(q.x, q.y, q.z, g, keys.data(), recs.data(), n, v, nullptr);
             }
             for (unsigned int s = 0; s < n; ++s) {   // assign
                 const LkC2cRec q = recs[s];
@@ -93,7 +77,7 @@ int main(int argc, char** argv) {
                     continue;
                 }
                 LkClusterNearest v = {reach2, core.data(), INFINITY, LK_CLUSTER_NONE};
-                lk_cluster_walk(q.x, q.y, q.z, g, keys.data(), recs.data(), n, v, nullptr);
+                lk_c2c_walk(q.x, q.y, q.z, g, keys.data(), recs.data(), n, v, nullptr);
                 if (v.j != LK_CLUSTER_NONE) root[q.idx] = lk_cluster_root(parent.data(), v.j), kind[q.idx] = 1;
             }
         }

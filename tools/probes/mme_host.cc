@@ -17,12 +17,10 @@
 #define floor trunc
 #endif
 #include "../../leg-kilo_amd/csrc/lk_mme.h"
+#include "c2c_index_host.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
-#include <algorithm>
-#include <utility>
-#include <vector>
 
 static bool read_exact(FILE* f, void* dst, size_t bytes) { return bytes == 0 || fread(dst, 1, bytes, f) == bytes; }
 
@@ -61,26 +59,12 @@ int main(int argc, char** argv) {
             fprintf(stderr, "mme_host: truncated cloud\n");
             return 2;
         }
-        unsigned int status = 0;
-        for (float v : p) status |= !isfinite(v) ? 1u : lk_c2c_out_of_range(v, radius) ? 2u : 0u;
-        LkC2cGrid g;
-        lk_c2c_grid_of_nothing(radius, &g);
-        std::vector<unsigned int> keys(n);
-        std::vector<LkC2cRec> recs(n);
-        if (!status && n) {
-            float lo[3], hi[3];
-            for (int c = 0; c < 3; ++c) lo[c] = hi[c] = p[c];
-            for (unsigned int i = 0; i < n; ++i)
-                for (int c = 0; c < 3; ++c) lo[c] = std::min(lo[c], p[3 * i + c]), hi[c] = std::max(hi[c], p[3 * i + c]);
-            lk_c2c_grid(lo, hi, radius, &g);
-            std::vector<std::pair<unsigned int, unsigned int>> order(n);
-            for (unsigned int i = 0; i < n; ++i) order[i] = {lk_c2c_key(p[3 * i], p[3 * i + 1], p[3 * i + 2], g), i};
-            std::sort(order.begin(), order.end());
-            for (unsigned int i = 0; i < n; ++i) {
-                const unsigned int s = order[i].second;
-                keys[i] = order[i].first, recs[i] = LkC2cRec{p[3 * s], p[3 * s + 1], p[3 * s + 2], s};
-            }
-        }
+        const unsigned int status = host_status(p, radius);
+        HostIndex x;
+        host_index(p, n, radius, !status, x);
+        const LkC2cGrid& g = x.g;
+        const std::vector<unsigned int>& keys = x.keys;
+        const std::vector<LkC2cRec>& recs = x.recs;
         printf("cloud %u status %u edge %a doublings %d cells %d %d %d\n", n, status, g.edge, g.doublings, g.dv[0], g.dv[1], g.dv[2]);
         const double reach2 = lk_c2c_reach2(radius);
         std::vector<unsigned int> cnt(n, 0u), cls(n, 0u), seen(n, 0u);

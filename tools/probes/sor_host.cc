@@ -13,12 +13,10 @@
 #include <math.h>
 #include <cmath>
 #include "../../leg-kilo_amd/csrc/lk_sor.h"
+#include "c2c_index_host.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
-#include <algorithm>
-#include <utility>
-#include <vector>
 
 static bool read_exact(FILE* f, void* dst, size_t bytes) { return bytes == 0 || fread(dst, 1, bytes, f) == bytes; }
 
@@ -70,26 +68,12 @@ int main(int argc, char** argv) {
             fprintf(stderr, "sor_host: truncated cloud\n");
             return 2;
         }
-        unsigned int status = 0;
-        for (float v : p) status |= !isfinite(v) ? 1u : lk_c2c_out_of_range(v, reach) ? 2u : 0u;
-        LkC2cGrid g;
-        lk_c2c_grid_of_nothing(reach, &g);
-        std::vector<unsigned int> keys(n);
-        std::vector<LkC2cRec> recs(n);
-        if (!status && n) {
-            float lo[3], hi[3];
-            for (int c = 0; c < 3; ++c) lo[c] = hi[c] = p[c];
-            for (unsigned int i = 0; i < n; ++i)
-                for (int c = 0; c < 3; ++c) lo[c] = std::min(lo[c], p[3 * i + c]), hi[c] = std::max(hi[c], p[3 * i + c]);
-            lk_c2c_grid(lo, hi, reach, &g);
-            std::vector<std::pair<unsigned int, unsigned int>> order(n);
-            for (unsigned int i = 0; i < n; ++i) order[i] = {lk_c2c_key(p[3 * i], p[3 * i + 1], p[3 * i + 2], g), i};
-            std::sort(order.begin(), order.end());
-            for (unsigned int i = 0; i < n; ++i) {
-                const unsigned int s = order[i].second;
-                keys[i] = order[i].first, recs[i] = LkC2cRec{p[3 * s], p[3 * s + 1], p[3 * s + 2], s};
-            }
-        }
+        const unsigned int status = host_status(p, reach);
+        HostIndex x;
+        host_index(p, n, reach, !status, x);
+        const LkC2cGrid& g = x.g;
+        const std::vector<unsigned int>& keys = x.keys;
+        const std::vector<LkC2cRec>& recs = x.recs;
         const int cap = lk_sor_cap_of(k);
         printf("cloud %u status %u edge %a doublings %d cells %d %d %d cap %d\n", n, status, g.edge, g.doublings, g.dv[0], g.dv[1], g.dv[2], cap);
         const double reach2 = lk_c2c_reach2(reach);
